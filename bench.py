@@ -9,11 +9,18 @@ CPU baseline of the reference's op sequence beside it.
            --master-port 29500 bench.py --gpus 8 --steps 20 --warmup 5       # what the driver does
     python bench.py --config c2                      # the single 3x3 layer, fp32 in -> fp32 out
     python bench.py --config c5                      # ResNet(HBlock,[3,4,6,3]) + fp16 MFMA stem, 128 img/GPU
+    python bench.py --full                           # + sustained record, other engines, roofline, CPU baseline
+    python bench.py --dump-outputs DIR               # + the last timed step's outputs as DIR/<name>.npy
 
 One "step" = one pass of the hot path over one synthetic batch per GPU, inputs resident in HBM before
 the timed region.  Weak scaling: every rank processes its own batch; for the networks the
 [B,1000] logits of all ranks are all-gathered over RCCL at the end of every step (the only exchange
 the path has).  Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set-up, spin-up, warm-up, the K timed steps, the outputs (with
+--dump-outputs) and the line.  --full adds everything else the line can carry: the `sustained` record (--sustain,
+default 3 s with --full), the other engines / exact-fp32 stem / two batches in flight (--no-extras drops them), the
+roofline block (--no-roofline) and the CPU baseline with the GPU config-1 leg (--no-cpu-baseline).
 
 Timing: --spinup untimed steps (default ~1 s of work: the clocks of an idle GPU come up within a few hundred ms and
 settle over the first second — with 0.25 s the 20 timed steps read 2-5 % below the 3 s sustained figure of the same run),
@@ -79,9 +86,9 @@ def parse_args():
                     help="process-group backend.  nccl = RCCL (one rank per GPU, the real thing); gloo: the same bench "
                          "code with host-staged collectives — lets N ranks share ONE GPU (RCCL refuses that), which is "
                          "how the N > 1 paths are exercised on a one-GPU box (tests/test_gpu_dist.py)")
-    ap.add_argument("--sustain", type=float, default=3.0,
+    ap.add_argument("--sustain", type=float, default=None,
                     help="seconds of the same step run (and timed) after the K timed steps: the `sustained` record, "
-                         "with the engine clock sampled right behind it (0 = skip)")
+                         "with the engine clock sampled right behind it (default: 3 with --full, else 0 = skip)")
     ap.add_argument("--streams", type=int, default=0,
                     help="graph engine: batches in flight per GPU (graph-captured executors on their own HIP "
                          "streams, replayed round-robin; 1 = strictly one batch at a time).  Default: 2 for ResNet-18, 4 "
@@ -104,7 +111,18 @@ def parse_args():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the exact-fp32-stem and one-batch-at-a-time lines")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline as well: the sustained record, the other engines and "
+                         "extras, the roofline block, the CPU baseline (each still dropped by its --no-* option).  "
+                         "Without --full those three options are implied and --sustain defaults to 0")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32; "
+                         "an array over DUMP_MAX_ELEMS elements as a fixed, seeded sample of them)")
     a = ap.parse_args()
+    if not a.full:
+        a.no_cpu_baseline = a.no_roofline = a.no_extras = True
+    if a.sustain is None:
+        a.sustain = 3.0 if a.full else 0.0
     if a.steps <= 0:
         a.steps = 200 if a.config == "c5" else 20
     if a.warmup < 0:
@@ -324,6 +342,29 @@ def cpu_baseline():
                       f"torch {torch.__version__} CPU, fp32, {tot3:.1f} s)",
             "c1_resnet18_32x32_b32": {"value": 32 / t1, "unit": "images/s", "s_per_batch": t1},
             "c2_conv3x3_128_56x56_b256": {"value": 256 / t2, "unit": "images/s", "s_per_batch": t2}}
+
+
+DUMP_MAX_ELEMS = 1 << 22      # 16 MB of float32 per dumped array (config 2's [256,128,56,56] output is 102.8 M elements)
+
+
+def dump_outputs(outputs, path):
+    """--dump-outputs: every array the timed path returned in its last step as ``path/<name>.npy`` (float32).  An array
+    of more than DUMP_MAX_ELEMS elements is stored as a fixed sample: its elements at the sorted, distinct flat indices
+    drawn by ``np.random.default_rng(0).integers(0, size, DUMP_MAX_ELEMS)`` — the same positions in every run of the same
+    shape.  Returns ``{name: {"shape": full shape, "stored": elements written}}`` for the JSON line."""
+    os.makedirs(path, exist_ok=True)
+    rec = {}
+    for name, t in outputs.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            idx = np.unique(np.random.default_rng(0).integers(0, flat.numel(), DUMP_MAX_ELEMS))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arr = flat.float().cpu().numpy()
+        if flat.numel() == t.numel():
+            arr = arr.reshape(tuple(t.shape))
+        np.save(os.path.join(path, name + ".npy"), arr)
+        rec[name] = {"shape": list(t.shape), "stored": int(arr.size)}
+    return rec
 
 
 def rccl_log_path(rank):
@@ -617,9 +658,9 @@ def main():
         return dt, out
 
     if args.config == "c2":
-        rec = bench_c2(args, world, rank, device, info, timed)
+        rec, outputs = bench_c2(args, world, rank, device, info, timed)
     else:
-        rec = bench_net(args, world, rank, device, info, timed)
+        rec, outputs = bench_net(args, world, rank, device, info, timed)
     # rank -> device: LOCAL_RANK -> cuda:LOCAL_RANK (examples/imagenet.py:139-147), never through HIP_VISIBLE_DEVICES;
     # gloo rehearsals on fewer GPUs than ranks wrap around (LOCAL_RANK % visible GPUs)
     rank_devices = [int(v) for v in all_gather_scalar(device.index, device, torch.int64)] if world > 1 else [device.index]
@@ -640,6 +681,8 @@ def main():
             rec["cpu_baseline"] = cpu_baseline()
             if args.config == "c3":     # the small-batch latency regime of config 1, on the GPU, next to its CPU number
                 rec["cpu_baseline"]["c1_resnet18_32x32_b32"]["gpu"] = gpu_c1(device)
+        if args.dump_outputs:
+            rec["dumped_outputs"] = dump_outputs(outputs, args.dump_outputs)
         print(json.dumps(rec), flush=True)
     barrier()
     if dist.is_initialized():
@@ -735,7 +778,7 @@ def bench_c2(args, world, rank, device, info, timed):
         rec["roofline_config2_as_worded"] = as_worded(roof)
         rec["packed_input_only"] = {"images_per_s": roof["images_per_s_kernel"], "us": roof["avg_kernel_us"],
                                     "frac": roof["frac"]}
-    return rec
+    return rec, {"out": out}
 
 
 @contextlib.contextmanager
@@ -952,7 +995,7 @@ def bench_net(args, world, rank, device, info, timed):
     else:
         per_rank_ms = [dt_local / args.steps * 1e3]
     if rank != 0:
-        return None
+        return None, None
     value = world * B * args.steps / dt
     name = "ResNet(HBlock,[3,4,6,3]) (BASELINE config 5: build-defined, the reference cannot construct it)" if c5 \
         else "binary ResNet-18 (bnn.models resnet18, XNOR recipe of examples/cifar10.py, conv1+fc real-valued)"
@@ -1014,7 +1057,7 @@ def bench_net(args, world, rank, device, info, timed):
         rec["int_alu_probe_Tlane_ops"] = {
             name: round(hipops.probe_int_alu(4096, device, mode)["lane_ops_per_s"] / 1e12, 2)
             for mode, name in hipops.PROBE_MODES.items()}
-    return rec
+    return rec, {"logits": logits}
 
 
 class _Fresh(torch.nn.Module):

@@ -130,6 +130,31 @@ def test_bench_line_plain_vs_one_rank_under_the_launcher():
     assert 0.5 < launched["value"] / plain["value"] < 2.0
 
 
+@pytest.mark.parametrize("config,batch,name,shape", [("c3", 32, "logits", (32, 1000)),
+                                                     ("c2", 16, "out", (16, 128, 56, 56))])
+def test_bench_plain_line_is_lean_and_dumps_the_same_outputs_twice(tmp_path, config, batch, name, shape):
+    """A plain run carries the headline only (no --full records), and `--dump-outputs` writes what its last timed step
+    returned: float32, the same bits from two runs with the same arguments; config 2's 6.4 M-element output is stored
+    as the fixed sample of DUMP_MAX_ELEMS draws."""
+    import numpy as np
+    args = ["--config", config, "--steps", "4", "--warmup", "1", "--spinup", "2", "--batch", str(batch)]
+    recs, arrs = [], []
+    for run in ("a", "b"):
+        recs.append(_run_bench([sys.executable, "bench.py", "--gpus", "1"] + args + ["--dump-outputs", str(tmp_path / run)]))
+        arrs.append(np.load(tmp_path / run / f"{name}.npy"))
+    for rec in recs:
+        assert rec["steps"] == 4 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["value"] > 0
+        assert not {"sustained", "engines", "roofline", "cpu_baseline", "two_batches_in_flight"} & set(rec)
+        assert rec["dumped_outputs"][name]["shape"] == list(shape)
+    a, b = arrs
+    assert a.dtype == np.float32 and np.isfinite(a).all() and np.array_equal(a, b)
+    n = int(np.prod(shape))
+    if n > (1 << 22):       # distinct positions of 4 M draws
+        assert a.ndim == 1 and a.size == recs[0]["dumped_outputs"][name]["stored"] and (1 << 21) < a.size < (1 << 22)
+    else:
+        assert a.shape == shape
+
+
 # ---- round 4: two ranks on ONE GPU (gloo), DDP over RCCL ------------------------------------------------------------
 
 @pytest.mark.parametrize("engine", ["graph", "graph_fresh", "net_call", "layerwise"])

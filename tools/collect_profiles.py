@@ -34,13 +34,13 @@ def stamped(line, cmd):
 
 
 line = open(os.path.join(src, "bench.json")).read().strip().splitlines()[-1]
-open(os.path.join(dst, f"{tag}_bench.json"), "w").write(stamped(line, "python bench.py --steps 20 --warmup 5") + "\n")
+open(os.path.join(dst, f"{tag}_bench.json"), "w").write(stamped(line, "python bench.py --full --steps 20 --warmup 5") + "\n")
 for extra in ("c2", "c5"):
     fn = os.path.join(src, f"bench_{extra}.json")
     if os.path.exists(fn) and open(fn).read().strip():
         ln = open(fn).read().strip().splitlines()[-1]
-        cmd = {"c2": "python bench.py --config c2 --steps 20 --warmup 5",
-               "c5": "python bench.py --config c5 --no-cpu-baseline --no-roofline"}[extra]
+        cmd = {"c2": "python bench.py --full --config c2 --steps 20 --warmup 5",
+               "c5": "python bench.py --full --config c5 --no-cpu-baseline --no-roofline"}[extra]
         open(os.path.join(dst, f"{tag}_bench_{extra}.json"), "w").write(stamped(ln, cmd) + "\n")
 stats = glob.glob(os.path.join(src, "stats", "**", "*kernel_stats.csv"), recursive=True)
 if stats:

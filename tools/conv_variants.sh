@@ -21,6 +21,6 @@ else
     echo "=== $k (${CFG[$k]})"
     [ -z "${STEM:-}" ] && BNN_AMD_LIB="$V/$k/libbnn_hip.so" ONLY="${ONLY:-}" timeout 300 python "$R/tools/bench_conv.py" 2>&1 | grep -v amdgpu.ids
     [ -n "${STEM:-}" ] && BNN_AMD_LIB="$V/$k/libbnn_hip.so" timeout 300 python "$R/tools/bench_stem.py" 2>&1 | grep "stem"
-    [ -n "${NET:-}" ] && BNN_AMD_LIB="$V/$k/libbnn_hip.so" timeout 300 python "$R/bench.py" --steps 20 --warmup 5 --no-cpu-baseline --no-roofline 2>&1 | tail -1 | cut -c1-200
+    [ -n "${NET:-}" ] && BNN_AMD_LIB="$V/$k/libbnn_hip.so" timeout 300 python "$R/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline --no-roofline 2>&1 | tail -1 | cut -c1-200
   done
 fi

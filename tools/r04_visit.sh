@@ -6,7 +6,7 @@ R="${GRAFT_REPO_ROOT:-$(pwd)}"; TAG="${1:-r4}"; OUT="$R/gpurun_out/$TAG"; mkdir 
 echo "== smoke"; timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
 echo "== new tests"; timeout 1200 python -m pytest tests/test_gpu_dropin.py tests/test_gpu_dist.py -x -q 2>&1 | tail -30 | tee "$OUT/pytest_new.txt"
 echo "== pytest -m gpu"; timeout 1200 python -m pytest tests -q -m gpu --deselect tests/test_gpu_dropin.py --deselect tests/test_gpu_dist.py 2>&1 | tail -15 | tee "$OUT/pytest_gpu.txt"
-echo "== bench"; timeout 900 python bench.py --steps 20 --warmup 5 2> "$OUT/bench.err" | tail -1 > "$OUT/bench.json"; cut -c1-600 "$OUT/bench.json"; tail -5 "$OUT/bench.err"
+echo "== bench"; timeout 900 python bench.py --full --steps 20 --warmup 5 2> "$OUT/bench.err" | tail -1 > "$OUT/bench.json"; cut -c1-600 "$OUT/bench.json"; tail -5 "$OUT/bench.err"
 python - <<PY
 import json
 try:
