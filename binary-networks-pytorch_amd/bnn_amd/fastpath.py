@@ -12,7 +12,9 @@ A layer takes the HIP path when ALL of the following hold (otherwise the torch c
 * autograd is not recording (``torch.no_grad()`` / inference); when it IS recording, ``Conv2d`` takes the
   training variant (HIP forward, fp32 library backward with the straight-through estimator:
   ``bnn_amd/training.py``), ``Conv1d``/``Linear`` fall back to the composition
-* ``groups == 1``, ``padding_mode == 'zeros'``, numeric padding
+* ``padding_mode == 'zeros'``, numeric padding, and either ``groups == 1`` or — ``Conv2d`` / ``Conv1d`` under inference
+  only — ``groups > 1`` (grouped and depthwise layers: ``pack_act`` + ``bnn_hip_bconv2d_grouped``, two launches; the
+  training forward and the fused executors keep declining them)
 
 When those hold and ``libbnn_hip.so`` cannot be loaded the call raises ``NativeError``: there is
 no CPU or eager stand-in for the GPU path.
@@ -128,8 +130,14 @@ def _numeric_padding(layer) -> bool:
     return not isinstance(layer.padding, str) and layer.padding_mode == "zeros" and layer.groups == 1
 
 
+def _grouped_numeric_padding(layer) -> bool:
+    """A grouped / depthwise layer the inference path takes (``bnn_hip_bconv2d_grouped``).  ``_numeric_padding`` keeps
+    rejecting these: the training forward and the fused executors rely on it."""
+    return not isinstance(layer.padding, str) and layer.padding_mode == "zeros" and layer.groups > 1
+
+
 def plan_conv2d(layer, x: torch.Tensor) -> Optional[Plan]:
-    if x.dim() != 4 or not _numeric_padding(layer):
+    if x.dim() != 4 or not (_numeric_padding(layer) or _grouped_numeric_padding(layer)):
         return None
     plan = _recognise(layer, layer.out_channels)
     return plan if plan is not None and _eligible(layer, x, plan) else None
@@ -144,7 +152,7 @@ def plan_conv2d_train(layer, x: torch.Tensor) -> Optional[Plan]:
 
 
 def plan_conv1d(layer, x: torch.Tensor) -> Optional[Plan]:
-    if x.dim() != 3 or not _numeric_padding(layer):
+    if x.dim() != 3 or not (_numeric_padding(layer) or _grouped_numeric_padding(layer)):
         return None
     plan = _recognise(layer, layer.out_channels)
     return plan if plan is not None and _eligible(layer, x, plan) else None
@@ -180,7 +188,8 @@ def packed_weight(layer, plan: Plan, sync: bool = True, fresh: bool = False) -> 
     if master is not None:          # a DataParallel replica: cached on the layer it was replicated from
         return _replica_packed_weight(layer, master, plan, fresh)
     w = layer.weight
-    key = (w.data_ptr(), w._version, str(w.device), tuple(w.shape), plan.center, plan.compute_alpha)
+    groups = getattr(layer, "groups", 1)
+    key = (w.data_ptr(), w._version, str(w.device), tuple(w.shape), plan.center, plan.compute_alpha, groups)
     cached = layer.__dict__.get("_bnn_packed")
     sync = sync or cached is None
     if cached is not None and cached[1].zero_probe is not None and (sync or fresh or cached[0] != key):
@@ -197,12 +206,18 @@ def packed_weight(layer, plan: Plan, sync: bool = True, fresh: bool = False) -> 
     if cached is not None and cached[0] == key and not fresh:
         return cached[1]
     sync = sync or layer.__dict__.get("_bnn_zero_seen", False)
-    pw = hipops.pack_weight(w, plan.center, plan.compute_alpha, sync=sync)
+    pw = _pack(w, plan, groups, sync)
     if pw.has_zero:  # once a layer has shown an exact zero it is always packed synchronously (mask-aware)
         layer.__dict__["_bnn_zero_seen"] = True
     layer.__dict__["_bnn_packed"] = (key, pw)
     _bump("weight_packs")
     return pw
+
+
+def _pack(w: torch.Tensor, plan: Plan, groups: int, sync: bool) -> hipops.PackedWeight:
+    if groups != 1:   # the windowed layout of bnn_hip_bconv2d_grouped
+        return hipops.pack_weight_grouped(w, groups, plan.center, plan.compute_alpha, sync=sync)
+    return hipops.pack_weight(w, plan.center, plan.compute_alpha, sync=sync)
 
 
 def _replica_packed_weight(layer, master, plan: Plan, fresh: bool = False) -> hipops.PackedWeight:
@@ -213,7 +228,8 @@ def _replica_packed_weight(layer, master, plan: Plan, fresh: bool = False) -> hi
     version instead of one per forward."""
     mw = master.weight
     w = layer.weight
-    key = (mw.data_ptr(), mw._version, tuple(mw.shape), plan.center, plan.compute_alpha)
+    groups = getattr(layer, "groups", 1)
+    key = (mw.data_ptr(), mw._version, tuple(mw.shape), plan.center, plan.compute_alpha, groups)
     cache = master.__dict__.setdefault("_bnn_packed_replicas", {})
     dev = str(w.device)
     hit = cache.get(dev)
@@ -221,7 +237,7 @@ def _replica_packed_weight(layer, master, plan: Plan, fresh: bool = False) -> hi
         return hit[1]
     # ``fresh`` (the training forward): never trust the cache — a ``.data`` write on the master does not move its
     # version counter, and the fused backward re-derives What from the current values (forward and backward must agree)
-    pw = hipops.pack_weight(w, plan.center, plan.compute_alpha, sync=True)
+    pw = _pack(w, plan, groups, sync=True)
     cache[dev] = (key, pw)
     _bump("weight_packs")
     return pw
@@ -253,6 +269,11 @@ def conv2d(layer, x: torch.Tensor, plan: Plan) -> torch.Tensor:
     """HIP evaluation of ``bnn.layers.Conv2d.forward`` (bnn/layers/conv.py:90-97)."""
     native.require()
     pw = packed_weight(layer, plan)
+    if layer.groups != 1:   # grouped / depthwise: the sign planes, then the grouped kernel (csrc/bconv_grouped.hip)
+        out = hipops.bconv2d_grouped(hipops.pack_act(x), pw, _f32(layer.bias), _f32(plan.scale), layer.stride,
+                                     layer.padding, layer.dilation)
+        _bump("conv2d")
+        return out.to(x.dtype)
     # one launch: sign(x) is computed inside the convolution kernel (csrc/bconv_fly.hip)
     out = hipops.bconv2d_direct(x, pw, _f32(layer.bias), _f32(plan.scale), layer.stride, layer.padding,
                                 layer.dilation)
@@ -273,6 +294,11 @@ def conv1d(layer, x: torch.Tensor, plan: Plan) -> torch.Tensor:
     """``Conv1d`` as an ``H == 1`` 2-D convolution (bnn/layers/conv.py:36-43)."""
     native.require()
     pw = packed_weight(layer, plan)
+    if layer.groups != 1:
+        out = hipops.bconv2d_grouped(hipops.pack_act(x.unsqueeze(2)), pw, _f32(layer.bias), _f32(plan.scale),
+                                     (1, layer.stride[0]), (0, layer.padding[0]), (1, layer.dilation[0]))
+        _bump("conv1d")
+        return out.squeeze(2).to(x.dtype)
     out = hipops.bconv2d_direct(x.unsqueeze(2), pw, _f32(layer.bias), _f32(plan.scale), (1, layer.stride[0]),
                                 (0, layer.padding[0]), (1, layer.dilation[0]))
     _bump("conv1d")

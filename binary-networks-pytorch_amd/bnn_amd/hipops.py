@@ -86,6 +86,10 @@ class PackedWeight:
     shape: Tuple[int, int, int, int]  # logical (O, C, KH, KW)
     # deferred zero check (pack_weight(..., sync=False)): pinned host copy of the flag + the event after it
     zero_probe: Optional[tuple] = None
+    # pack_weight_grouped: shape = (O, C / groups, KH, KW) in the windowed block-diagonal layout (include/bnn_hip.h),
+    # read only by bconv2d_grouped (windowed = True also for groups == 1 from that packer)
+    groups: int = 1
+    windowed: bool = False
 
     def zero_found_later(self) -> bool:
         """True if a pack made with ``sync=False`` turned out to contain a zero weight (waits for the copy)."""
@@ -447,6 +451,53 @@ def pack_weight(w: torch.Tensor, center: bool = False, compute_alpha: bool = Tru
     return PackedWeight(wbits, wnz, alpha, has_zero, (O, C, KH, KW))
 
 
+def pack_weight_grouped(w: torch.Tensor, groups: int, center: bool = False, compute_alpha: bool = True,
+                        sync: bool = True) -> PackedWeight:
+    """``XNORWeightBinarizer`` of a grouped weight ``[O, C / groups, KH, KW]`` (``Conv1d``: ``[O, C / groups, K]``) into
+    the windowed block-diagonal layout of ``bnn_hip_bconv2d_grouped`` (include/bnn_hip.h).  Centring and alpha reduce
+    over the group's channels as the reference does; alpha has the bits of ``pack_weight`` of the same tensor.  fp16
+    weights and ``sync`` as in ``pack_weight``."""
+    half = w.dtype == torch.float16
+    if half:
+        w = w.detach().float()
+    w = _require_cuda_f32(w.detach(), "weight")
+    if w.dim() == 3:
+        w = w[:, :, None, :]
+    if w.dim() != 4:
+        raise native.NativeError(f"bnn_amd: unsupported grouped weight rank {w.dim()}")
+    w = w.contiguous()
+    lib = native.require()
+    O, Cg, KH, KW = w.shape
+    if groups < 1 or O % groups:
+        raise native.NativeError(f"bnn_amd: {O} output channels do not split into {groups} groups")
+    L = native.grouped_weight_layout(O, Cg * groups, groups, KH, KW)
+    with torch.cuda.device(w.device):
+        wbits = torch.empty(L.n_words, dtype=torch.int32, device=w.device)
+        wnz = torch.empty(L.n_words, dtype=torch.int32, device=w.device)
+        alpha = torch.empty(L.o_pad, dtype=torch.float32, device=w.device)
+        flag = torch.zeros(1, dtype=torch.int32, device=w.device)
+        native.check(lib.bnn_hip_pack_weight_grouped_f32(w.data_ptr(), O, Cg, groups, KH, KW, int(center),
+                                                         int(compute_alpha), wbits.data_ptr(), wnz.data_ptr(),
+                                                         alpha.data_ptr(), flag.data_ptr(), _stream(w.device)),
+                     "bnn_hip_pack_weight_grouped_f32")
+        if half:
+            alpha = alpha.half().float()
+        if not sync:
+            host = torch.empty(1, dtype=torch.int32, pin_memory=True)
+            host.copy_(flag, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(w.device))
+            return PackedWeight(wbits, wnz, alpha, False, (O, Cg, KH, KW), (host, ev), groups=groups, windowed=True)
+        has_zero = bool(flag.item())
+    return PackedWeight(wbits, wnz, alpha, has_zero, (O, Cg, KH, KW), groups=groups, windowed=True)
+
+
+def _ungrouped(w: PackedWeight, what: str) -> None:
+    if w.groups != 1 or w.windowed:
+        raise native.NativeError(f"bnn_amd: {what} takes a dense weight pack (pack_weight); this one is grouped "
+                                 f"(groups={w.groups}, pack_weight_grouped): use bconv2d_grouped")
+
+
 def conv_out_hw(H, W, KH, KW, stride, padding, dilation) -> Tuple[int, int]:
     sh, sw = _pair(stride)
     ph, pw = _pair(padding)
@@ -484,6 +535,7 @@ def bconv2d(a: PackedAct, w: PackedWeight, bias: Optional[torch.Tensor] = None,
             force_generic: bool = False, raw_dot: bool = False,
             weights: Optional[str] = None) -> torch.Tensor:
     """Binary convolution on packed operands -> fp32 NCHW (or int32 dot when ``raw_dot``)."""
+    _ungrouped(w, "bconv2d")
     lib = native.require()
     d = _desc(a.shape, w.shape, stride, padding, dilation, _flags(w, force_generic, weights, a))
     ho, wo = conv_out_hw(d.H, d.W, d.KH, d.KW, stride, padding, dilation)
@@ -511,6 +563,44 @@ def bconv2d(a: PackedAct, w: PackedWeight, bias: Optional[torch.Tensor] = None,
                 st = lib.bnn_hip_bconv2d(*args, w.alpha.data_ptr(), _ptr(bias), _ptr(post_scale),
                                          out[n0:n1].data_ptr(), _stream(dev))
             native.check(st, "bnn_hip_bconv2d")
+    return out
+
+
+def bconv2d_grouped(a: PackedAct, w: PackedWeight, bias: Optional[torch.Tensor] = None,
+                    post_scale: Optional[torch.Tensor] = None, stride=1, padding=0, dilation=1,
+                    raw_dot: bool = False) -> torch.Tensor:
+    """Grouped / depthwise binary convolution on packed operands (``bnn_hip_bconv2d_grouped``): ``a`` holds all C input
+    channels, ``w`` comes from ``pack_weight_grouped`` (any ``groups``, 1 included) -> fp32 NCHW, or the int32 dot when
+    ``raw_dot``."""
+    if not w.windowed:
+        raise native.NativeError("bnn_amd: bconv2d_grouped reads the layout of pack_weight_grouped, not of pack_weight")
+    lib = native.require()
+    N, C, H, W = a.shape
+    O, Cg, KH, KW = w.shape
+    if Cg * w.groups != C:
+        raise native.NativeError(f"bnn_amd: grouped weight reads {Cg} x {w.groups} channels, the input has {C}")
+    d = _desc(a.shape, (O, C, KH, KW), stride, padding, dilation, 0)
+    ho, wo = conv_out_hw(H, W, KH, KW, stride, padding, dilation)
+    dev = a.P.device
+    bias = _per_channel(bias, O, "bias")
+    post_scale = _per_channel(post_scale, O, "post_scale")
+    if raw_dot and (bias is not None or post_scale is not None):
+        raise ValueError("raw_dot returns the integer dot: no bias / post_scale")
+    with torch.cuda.device(dev):
+        out = torch.empty((N, O, ho, wo), dtype=torch.int32 if raw_dot else torch.float32, device=dev)
+        if N == 0:
+            return out
+        per_img = max(O * ho * wo, 2 * H * W * ((C + 63) // 64), 2 * ho * wo * ((O + 63) // 64))
+        step = _batch_step(N, per_img, max(O, (C + 63) // 64))
+        for n0 in range(0, N, step):
+            n1 = min(N, n0 + step)
+            dd = native.ConvDesc.from_buffer_copy(d)
+            dd.N = n1 - n0
+            native.check(lib.bnn_hip_bconv2d_grouped(ctypes.byref(dd), w.groups, a.P[n0:n1].data_ptr(),
+                                                     a.M[n0:n1].data_ptr(), w.wbits.data_ptr(), w.wnz.data_ptr(),
+                                                     None if raw_dot else w.alpha.data_ptr(), _ptr(bias),
+                                                     _ptr(post_scale), out[n0:n1].data_ptr(), _stream(dev)),
+                         "bnn_hip_bconv2d_grouped")
     return out
 
 
@@ -550,6 +640,7 @@ def bconv2d_direct(x: torch.Tensor, w: PackedWeight, bias: Optional[torch.Tensor
     ``route``: ``None`` picks per shape (``_prefers_two_launches``); ``"direct"`` / ``"packed"`` force one (tools)."""
     if route not in (None, "direct", "packed"):
         raise ValueError("route must be None, 'direct' or 'packed'")
+    _ungrouped(w, "bconv2d_direct")
     if x.dtype == torch.float16:
         if not x.is_cuda:
             raise native.NativeError(f"bnn_amd: activation must live on a HIP device, got {x.device}")
@@ -608,6 +699,7 @@ def bconv2d_fused(a: PackedAct, w: PackedWeight, *, bias=None, post_scale=None, 
     preallocated ``[N, C_total, Ho, Wo]`` tensor (``torch.cat`` in place); ``residual`` then has
     ``C_total`` channels too.  The remaining keyword arguments are the pre-activation switches of
     ``BNN_HIP_EPI_*`` (include/bnn_hip.h); ``throughput``: ``BNN_HIP_FLAG_THROUGHPUT`` (several batches in flight)."""
+    _ungrouped(w, "bconv2d_fused")
     lib = native.require()
     d = _desc(a.shape, w.shape, stride, padding, dilation, _flags(w, force_generic, weights, a, throughput))
     ho, wo = conv_out_hw(d.H, d.W, d.KH, d.KW, stride, padding, dilation)

@@ -50,6 +50,7 @@ EXPORTED_SYMBOLS = (
     "bnn_hip_avgpool2_bn_pack2_f32", "bnn_hip_hblock_pack_weights_cl", "bnn_hip_stem7x7_bn_relu_pool_pack_affine_f32",
     "bnn_hip_hblock_pool_supported", "bnn_hip_hblock_pool_forward",
     "bnn_hip_hblock_shortcut_supported", "bnn_hip_hblock_pack_shortcut_weights", "bnn_hip_hblock_shortcut_forward",
+    "bnn_hip_grouped_weight_layout", "bnn_hip_pack_weight_grouped_f32", "bnn_hip_bconv2d_grouped",
 )
 
 
@@ -210,6 +211,9 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.bnn_hip_hblock_shortcut_supported.argtypes = [ctypes.POINTER(HBlockDesc)]
     lib.bnn_hip_hblock_pack_shortcut_weights.argtypes = [_i, _i, _vp, _vp, _vp]
     lib.bnn_hip_hblock_shortcut_forward.argtypes = [ctypes.POINTER(HBlockDesc)] + [_vp] * 10
+    lib.bnn_hip_grouped_weight_layout.argtypes = [_i, _i, _i, _i, _i, ctypes.POINTER(WLayout)]
+    lib.bnn_hip_pack_weight_grouped_f32.argtypes = [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]
+    lib.bnn_hip_bconv2d_grouped.argtypes = [ctypes.POINTER(ConvDesc), _i] + [_vp] * 9
 
 
 def load() -> Optional[ctypes.CDLL]:
@@ -256,6 +260,13 @@ def check(status: int, what: str) -> None:
 def weight_layout(O: int, C: int, KH: int, KW: int) -> WLayout:
     L = WLayout()
     check(require().bnn_hip_weight_layout(O, C, KH, KW, ctypes.byref(L)), "bnn_hip_weight_layout")
+    return L
+
+
+def grouped_weight_layout(O: int, C: int, groups: int, KH: int, KW: int) -> WLayout:
+    """Windowed block-diagonal layout of a grouped weight (``cw32`` = words per tap): include/bnn_hip.h."""
+    L = WLayout()
+    check(require().bnn_hip_grouped_weight_layout(O, C, groups, KH, KW, ctypes.byref(L)), "bnn_hip_grouped_weight_layout")
     return L
 
 

@@ -1,0 +1,111 @@
+// bconv_grouped.hip — grouped and depthwise binary convolutions (groups > 1) on the gfx950 integer ALU.
+//
+// Replaces bnn/layers/conv.py:90-97 for a layer built with groups = G: output channel o reads only the Cg = C / G input
+// channels of its group o / Og (Og = O / G) — the BATS cells' SepConv / DilConv (bnn/models/layers/bats_ops.py:108-173,
+// Conv2d(groups=12)) and the BATS ImageNet stem (bnn/models/bats.py:165,170, groups = C / 20).
+//
+// Weights: the windowed block-diagonal layout of include/bnn_hip.h (bnn_hip_grouped_weight_layout).  The 32 output
+// channels of block ob read S consecutive 32-bit activation words per tap from w_lo(ob) = ((32 ob / Og) Cg) / 32 on; the
+// group mask is folded into the non-zero mask Z, so the dot is exactly the zero-aware form of bconv.hip:
+//     N   = (P | M) & Z_j                 non-zero products of channel j
+//     D   = N & ~(W_j ^ M)                disagreeing positions (one v_bitop3_b32, disagree_nz(): a non-zero activation
+//                                         disagrees with the weight iff its minus bit equals the weight's plus bit)
+//     dot = popcount(N) - 2 popcount(D)   = popcount((P|M)&Z) - 2 popcount(disagree(W, M, P) & Z)
+// Four vector instructions per word and output channel (v_and, v_bitop3, two v_bcnt); W_j and Z_j are wave-uniform and
+// come through the scalar cache (two s_load_dwordx16 per plane and (tap, word)), the activation words are per-lane loads.
+//
+// Work decomposition: lane = output pixel (flattened over N, Ho, Wo; stores coalesced per channel), one wave = 64 pixels
+// x one 32-channel block, as in bconv.hip's generic kernel.  These layers are small in K (Cg KH KW = 72 .. 400 on the
+// BATS shapes): the fp32 output store, not the integer ALU, bounds most of them (tools/bench_grouped.py).
+#include "bconv_core.h"
+
+namespace bnn {
+
+// D = n & ~(w ^ m) in ONE v_bitop3_b32 (truth table 0x90: src0 set and src1 == src2), with the weight word w as the
+// scalar operand.  Written out because hipcc, seeing n = (p | m) & z, re-associates the plain expression into
+// bitop3(z, xnor(w, m), p | m): three instructions per word and channel instead of one.
+__device__ __forceinline__ uint32_t disagree_nz(uint32_t n, uint32_t w, uint32_t m) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  uint32_t r;
+  asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x90" : "=v"(r) : "v"(n), "s"(w), "v"(m));
+  return r;
+#else
+  return n & ~(w ^ m);
+#endif
+}
+
+// FAST: 24-bit index multiplies (decode_pixel<true>), when small_indices() holds.
+template <bool FAST>
+__global__ __launch_bounds__(64) void bconv_grouped_kernel(
+    const uint32_t* __restrict__ P, const uint32_t* __restrict__ M, const uint32_t* __restrict__ W,
+    const uint32_t* __restrict__ Z, BNN_EPI_PARAMS, const Geo g, const int Cg, const int Og, const int S) {
+  BNN_EPI_INIT;
+  // 1-D grid, block-major: consecutive workgroups walk the pixel tiles of one 32-channel block (the same weight words)
+  const int ob = (int)(blockIdx.x / (unsigned)g.tiles);
+  const int tile = (int)blockIdx.x - ob * g.tiles;
+  const Pix px = decode_pixel<FAST>(g, tile * kWave + threadIdx.x);
+  const int taps = g.KH * g.KW;
+  const int w_lo = (ob * kOCB) / Og * Cg / 32;
+  const int nw = min(S, g.cw32 - w_lo);  // window words that exist in the planes (the rest has Z == 0): never >= cw32
+  const int plane = g.H * g.Wd;
+  const uint32_t* __restrict__ wblk = W + (size_t)ob * taps * S * kOCB;
+  const uint32_t* __restrict__ zblk = Z + (size_t)ob * taps * S * kOCB;
+
+  int nzc[kOCB], dis[kOCB];
+#pragma unroll
+  for (int j = 0; j < kOCB; ++j) { nzc[j] = 0; dis[j] = 0; }
+  const int iy0 = px.oy * g.sh - g.ph, ix0 = px.ox * g.sw - g.pw;
+  for (int t = 0; t < taps; ++t) {
+    const int ky = t / g.KW, kx = t - ky * g.KW;
+    const int iy = iy0 + ky * g.dh, ix = ix0 + kx * g.dw;
+    // taps in the zero padding (applied after sign(): conv.py:91-92) read pixel 0 and contribute P = M = 0
+    const bool ok = (unsigned)iy < (unsigned)g.H && (unsigned)ix < (unsigned)g.Wd;
+    const int pix = ok ? iy * g.Wd + ix : 0;
+    for (int s = 0; s < nw; ++s) {
+      const int w = w_lo + s;
+      // word w of the pixel: plane (w >> 1), half (w & 1); BYTES below 2^32 (capi.hip keeps the planes < 2^29 words)
+      const unsigned boff = ((px.in_base + (unsigned)((w >> 1) * plane + pix)) * 2u + (unsigned)(w & 1)) * 4u;
+      const uint32_t pw = ld_off(P, boff), mw = ld_off(M, boff);
+      const uint32_t p = ok ? pw : 0u, m = ok ? mw : 0u;
+      const uint32_t pm = p | m;
+      WStream<kOCB> wv, zv;
+      const size_t woff = ((size_t)t * S + s) * kOCB;
+      load_wblock<kOCB>(wblk + woff, wv);
+      load_wblock<kOCB>(zblk + woff, zv);
+      static_for<kOCB>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        const uint32_t n = pm & zv.v[j];
+        nzc[j] = popc_acc(n, nzc[j]);
+        dis[j] = popc_acc(disagree_nz(n, wv.v[j], m), dis[j]);
+      });
+    }
+  }
+  int dotv[kOCB];
+#pragma unroll
+  for (int j = 0; j < kOCB; ++j) dotv[j] = nzc[j] - 2 * dis[j];
+  uint32_t pbits = 0u, mbits = 0u;
+  float resv[kOCB];  // (no residual in this epilogue)
+  // the float operations of the other kernels: fmaf(alpha, dot, bias) [* post_scale] (or the int32 dot: EF_RAW).  A whole
+  // block takes the straight-line form (no per-lane / per-channel guards; lanes past the last pixel were clamped to it
+  // and store the same value to the same place).
+  if ((ob + 1) * kOCB <= g.O) epilogue<kOCB, EP_PLAIN, true>(g, px, ob * kOCB, dotv, resv, epi, pbits, mbits);
+  else epilogue<kOCB, EP_PLAIN>(g, px, ob * kOCB, dotv, resv, epi, pbits, mbits);
+}
+
+// p: geometry of the whole convolution (p.C = all input channels, p.cw32 = their words per pixel); S: words per tap of the
+// weight layout (bnn_hip_grouped_weight_layout).  capi.hip has checked sizes, alignments and C % groups == O % groups == 0.
+int launch_bconv_grouped(const ConvP& p, int groups, int S, hipStream_t s) {
+  const Geo g = make_geo(p);
+  const unsigned nb = (unsigned)((p.O + kOCB - 1) / kOCB);
+  const dim3 grid((unsigned)g.tiles * nb);
+  const int Cg = p.C / groups, Og = p.O / groups;
+  if (small_indices(p))
+    hipLaunchKernelGGL((bconv_grouped_kernel<true>), grid, dim3(kWave), 0, s, p.P, p.M, p.W, p.Z, BNN_EPI_ACTUALS, g,
+                       Cg, Og, S);
+  else
+    hipLaunchKernelGGL((bconv_grouped_kernel<false>), grid, dim3(kWave), 0, s, p.P, p.M, p.W, p.Z, BNN_EPI_ACTUALS, g,
+                       Cg, Og, S);
+  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+}
+
+}  // namespace bnn

@@ -165,6 +165,12 @@ int launch_pack_weight(const float* w, int O, int C, int KH, int KW, int center,
                        int32_t* zero_flag, hipStream_t stream);
 bool ds_fold_applies(const ConvP& p, int flags);
 int launch_bconv(const ConvP& p, int flags, hipStream_t s);
+// grouped / depthwise convolutions: pack_weight.hip (the windowed layout, L from bnn_hip_grouped_weight_layout) and
+// bconv_grouped.hip (p.C = all input channels, p.W / p.Z in that layout with S words per tap)
+int launch_pack_weight_grouped(const float* w, int O, int Cg, int groups, int center, int compute_alpha,
+                               const bnn_hip_wlayout& L, uint32_t* wbits, uint32_t* wnz, float* alpha,
+                               int32_t* zero_flag, hipStream_t stream);
+int launch_bconv_grouped(const ConvP& p, int groups, int S, hipStream_t s);
 // bconv_fly.hip: the whole layer in one launch, activations (fp32, or fp16 when x_half) binarised on the fly into LDS.
 // p.P / p.M are unused; p.alpha / bias / scale / out as for launch_bconv.  `plan` may be null (default plan).
 bool fly_supported(const ConvP& p);

@@ -135,6 +135,37 @@ int run_conv(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, c
   return bnn::launch_bconv(p, d->flags, static_cast<hipStream_t>(stream));
 }
 
+// Grouped convolutions (include/bnn_hip.h, bnn_hip_grouped_weight_layout): S = the most 32-bit activation words one
+// 32-channel output block reads per tap.  Not a loop over every block (O may be ~2^30): block windows repeat.
+//   Og < 32:  shifting a whole block by T blocks with 32 T = m Og, m = lcm(32 / gcd(32, Cg), 32 / gcd(32, Og)) <= 32,
+//             moves both of its group bounds by m and its window by m Cg, a multiple of 32 channels: the same word count.
+//             T = m Og / 32 < 32, so the first 33 blocks and the (possibly partial) last one cover every window.
+//   Og >= 32: a block spans one group g or straddles g | g+1 (when (g+1) Og is not a multiple of 32).  Those windows
+//             depend on g only through g Cg mod 32 and (g+1) Og mod 32 (period <= 32); a lone group's window is inside
+//             the window of some block, so counting every one of them never exceeds the true maximum.
+inline long long window_words(long long a, long long len) { return (a + len - 1) / 32 - a / 32 + 1; }
+long long grouped_words_per_tap(long long O, long long C, long long G) {
+  const long long Cg = C / G, Og = O / G, nb = (O + 31) / 32;
+  long long S = 0;
+  auto block = [&](long long ob) {
+    const long long o0 = 32 * ob, o1 = (O < o0 + 32 ? O : o0 + 32) - 1;
+    const long long glo = o0 / Og, ghi = o1 / Og;
+    const long long w = window_words(glo * Cg, (ghi - glo + 1) * Cg);
+    if (w > S) S = w;
+  };
+  if (Og < 32) {
+    for (long long ob = 0; ob < nb && ob < 33; ++ob) block(ob);
+    block(nb - 1);
+  } else {
+    for (long long g = 0; g < G && g < 64; ++g) {
+      long long w = window_words(g * Cg, Cg);
+      if (g + 1 < G && ((g + 1) * Og) % 32 != 0) w = window_words(g * Cg, 2 * Cg);
+      if (w > S) S = w;
+    }
+  }
+  return S;
+}
+
 bnn::ConvP empty_convp() {
   bnn::ConvP p;
   std::memset(&p, 0, sizeof(p));
@@ -512,6 +543,73 @@ int bnn_hip_bconv2d(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_
   bnn::ConvP p = empty_convp();
   p.alpha = alpha; p.bias = bias; p.scale = post_scale; p.out = out;
   return run_conv(d, P, M, wbits, wnz, p, stream);
+}
+
+int bnn_hip_grouped_weight_layout(int O, int C, int groups, int KH, int KW, bnn_hip_wlayout* out) {
+  if (!out || O <= 0 || C <= 0 || groups <= 0 || KH <= 0 || KW <= 0) return BNN_HIP_ERR_INVALID_ARG;
+  if (C % groups != 0 || O % groups != 0) return BNN_HIP_ERR_INVALID_ARG;
+  const long long o_pad = ((long long)O + BNN_HIP_OCB - 1) / BNN_HIP_OCB * BNN_HIP_OCB;
+  const long long taps = mulc(KH, KW);
+  if (taps > 0x7fffffffLL || o_pad > 0x7fffffffLL || mulc(o_pad, taps) > kMaxElems) return BNN_HIP_ERR_TOO_LARGE;
+  const long long S = grouped_words_per_tap(O, C, groups);
+  if (mulc(o_pad, taps, S) > kMaxElems) return BNN_HIP_ERR_TOO_LARGE;
+  out->cw32 = (int32_t)S;
+  out->cwc = (int32_t)S;
+  out->nchunk = 1;
+  out->taps = (int32_t)taps;
+  out->o_pad = (int32_t)o_pad;
+  out->reserved = 0;
+  out->n_words = o_pad * taps * S;
+  return BNN_HIP_OK;
+}
+
+int bnn_hip_pack_weight_grouped_f32(const float* w, int O, int Cg, int groups, int KH, int KW, int center,
+                                    int compute_alpha, uint32_t* wbits, uint32_t* wnz, float* alpha,
+                                    int32_t* zero_flag, void* stream) {
+  if (!w || !wbits || !wnz || !alpha || !zero_flag || Cg <= 0 || groups <= 0) return BNN_HIP_ERR_INVALID_ARG;
+  if ((long long)Cg * groups > 0x7fffffffLL) return BNN_HIP_ERR_TOO_LARGE;
+  bnn_hip_wlayout L;
+  const int st = bnn_hip_grouped_weight_layout(O, Cg * groups, groups, KH, KW, &L);
+  if (st != BNN_HIP_OK) return st;
+  // the fp32 weight itself is read with 64-bit offsets, but its size must be a valid tensor
+  if (mulc(O, Cg, L.taps) > kMaxElems) return BNN_HIP_ERR_TOO_LARGE;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_pack_weight_grouped(w, O, Cg, groups, center, compute_alpha, L, wbits, wnz, alpha, zero_flag,
+                                         static_cast<hipStream_t>(stream));
+}
+
+int bnn_hip_bconv2d_grouped(const bnn_hip_conv_desc* d, int groups, const uint64_t* P, const uint64_t* M,
+                            const uint32_t* wbits, const uint32_t* wnz, const float* alpha, const float* bias,
+                            const float* post_scale, float* out, void* stream) {
+  int Ho = 0, Wo = 0;
+  const int st = check_desc(d, &Ho, &Wo);
+  if (st != BNN_HIP_OK) return st;
+  if (groups <= 0 || d->C % groups != 0 || d->O % groups != 0) return BNN_HIP_ERR_INVALID_ARG;
+  if (!P || !M || !wbits || !wnz || !out) return BNN_HIP_ERR_INVALID_ARG;
+  if (!alpha && (bias || post_scale)) return BNN_HIP_ERR_INVALID_ARG;  // raw dot: no epilogue constants
+  if (!aligned(P, 16) || !aligned(M, 16) || !aligned(wbits, 16) || !aligned(wnz, 16) || !aligned(out, 4))
+    return BNN_HIP_ERR_INVALID_ARG;
+  bnn_hip_wlayout L, G;
+  bnn_hip_weight_layout(d->O, d->C, d->KH, d->KW, &L);  // the activation words per pixel (cw32); check_desc: in range
+  const int sg = bnn_hip_grouped_weight_layout(d->O, d->C, groups, d->KH, d->KW, &G);
+  if (sg != BNN_HIP_OK) return sg;
+  bnn::ConvP p = empty_convp();
+  p.alpha = alpha; p.bias = bias; p.scale = post_scale; p.out = out; p.raw = alpha == nullptr;
+  p.P = reinterpret_cast<const uint32_t*>(P);
+  p.M = reinterpret_cast<const uint32_t*>(M);
+  p.W = wbits;
+  p.Z = wnz;
+  p.N = d->N; p.H = d->H; p.Wd = d->W; p.Ho = Ho; p.Wo = Wo; p.O = d->O;
+  p.KH = d->KH; p.KW = d->KW; p.sh = d->stride_h; p.sw = d->stride_w;
+  p.ph = d->pad_h; p.pw = d->pad_w; p.dh = d->dil_h; p.dw = d->dil_w;
+  p.cw32 = L.cw32; p.cwc = L.cw32; p.nchunk = 1;  // (one chunk: the grouped kernel walks its window, not chunks)
+  p.npix = d->N * Ho * Wo;
+  p.C = d->C;
+  p.c_off = 0; p.c_tot = d->O;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  Range range(p.raw ? "bnn_hip_bconv2d_grouped_dot" : "bnn_hip_bconv2d_grouped");
+  return bnn::launch_bconv_grouped(p, groups, G.cw32, static_cast<hipStream_t>(stream));
 }
 
 int bnn_hip_bconv2d_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M,

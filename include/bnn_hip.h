@@ -62,7 +62,9 @@ extern "C" {
 #endif
 
 /* ABI 15 (round 6): + bnn_hip_hblock_{supported,layout_of,pack_weights,forward} (the hierarchical block in one launch);
- * + bnn_hip_avgpool2_bn_pack2_f32 (the pool in front of a pre-activation stage + both sign planes it feeds).
+ * + bnn_hip_avgpool2_bn_pack2_f32 (the pool in front of a pre-activation stage + both sign planes it feeds);
+ * + bnn_hip_grouped_weight_layout, bnn_hip_pack_weight_grouped_f32, bnn_hip_bconv2d_grouped (grouped / depthwise
+ * convolutions: additive entry points of ABI 15, no struct or signature changed).
  * ABI 14 (round 5): + bnn_hip_stem7x7_wgrad_f32 / bnn_hip_stem7x7_wgrad_workspace_bytes (weight gradient of the stem
  * convolution: the training backward of that layer); + bnn_hip_avgpool2x2_backward_f32, bnn_hip_xnor_grad_pack_weight_f32; + bnn_hip_avgpool_fc_ws_f32 / bnn_hip_avgpool_fc_workspace_bytes (the head as two streaming launches
  * through a workspace); + bnn_hip_stem7x7_conv_f32 (the stem's convolution alone: the training forward); the table of bnn_hip_sign_thresholds_f32 holds FOUR words per channel (was two) and kmax < 2^20.
@@ -87,7 +89,8 @@ typedef enum bnn_hip_status {
 } bnn_hip_status;
 
 /* Geometry of one binary convolution (mirrors torch.nn.Conv2d hyper-parameters that
- * bnn.layers.Conv2d forwards unchanged: bnn/layers/conv.py:68-83). groups == 1 only. */
+ * bnn.layers.Conv2d forwards unchanged: bnn/layers/conv.py:68-83). groups == 1, except for
+ * bnn_hip_bconv2d_grouped, which takes `groups` as an argument of its own. */
 typedef struct bnn_hip_conv_desc {
   int32_t N, C, H, W;          /* input  [N,C,H,W]                        */
   int32_t O, KH, KW;           /* weight [O,C,KH,KW]                      */
@@ -435,6 +438,41 @@ int bnn_hip_bconv2d_dot(const bnn_hip_conv_desc* d,
                         const uint64_t* P, const uint64_t* M,
                         const uint32_t* wbits, const uint32_t* wnz,
                         int32_t* dot, void* stream);
+
+/* ---- Grouped and depthwise binary convolutions (additive entry points of ABI 15): bnn.layers.Conv2d / Conv1d built
+ * with groups = G > 1 (bnn/layers/conv.py:90-97 passes `groups` to conv2d; the BATS cells' SepConv / DilConv,
+ * bnn/models/layers/bats_ops.py:108-173, and the BATS ImageNet stem, bnn/models/bats.py:165,170).
+ * Notation: C input channels, O output channels, Cg = C / G, Og = O / G; output channel o reads input channels
+ * [(o / Og) Cg, (o / Og + 1) Cg).  Output block ob (32 channels o0 = 32 ob .. o1 = min(O, o0 + 32) - 1) reads the groups
+ * g_lo = o0 / Og .. g_hi = o1 / Og, i.e. the 32-bit activation words
+ *     w_lo(ob) = (g_lo Cg) / 32  ..  w_hi(ob) = ((g_hi + 1) Cg - 1) / 32.
+ * Windowed block-diagonal weight layout: S = max over ob of (w_hi - w_lo + 1) words per tap, and
+ *     wbits[ob][tap][s][j], wnz[ob][tap][s][j]   (uint32; j = o % 32 innermost: one (tap, word) of a block is 32
+ *                                                consecutive words, a scalar-cache stream)
+ * word s covers the absolute input channels 32 (w_lo(ob) + s) + b.  wbits bit b: sign(W) == +1; wnz bit b: W != 0 AND
+ * the channel belongs to output channel o's group.  Pad output channels, window words past w_hi and words past the
+ * activation planes are all zero in wnz.  The dot is the zero-aware form of bnn_hip_bconv2d:
+ *     dot = popcount((P | M) & Z) - 2 popcount(disagree(W, M, P) & Z)
+ * Depthwise (Cg = Og = 1) has S = 1.  bnn_hip_wlayout fields for this layout: cw32 = cwc = S (words per tap), nchunk = 1,
+ * taps = KH KW, o_pad = O rounded up to 32, n_words = o_pad taps S, reserved = 0.
+ *
+ * HOST: the layout of a [O, C/groups, KH, KW] weight; C and O multiples of groups.                                      */
+int bnn_hip_grouped_weight_layout(int O, int C, int groups, int KH, int KW, bnn_hip_wlayout* out);
+/* XNORWeightBinarizer of a grouped weight w [O, Cg, KH, KW] (fp32 contiguous) into that layout.  center / compute_alpha
+ * reduce over Cg and Cg KH KW as the reference does (bnn/ops.py:116-140): alpha[o_pad] holds the same bits as
+ * bnn_hip_pack_weight_f32 of the same [O, Cg, KH, KW] tensor; *zero_flag as there.                                      */
+int bnn_hip_pack_weight_grouped_f32(const float* w, int O, int Cg, int groups, int KH, int KW, int center,
+                                    int compute_alpha, uint32_t* wbits, uint32_t* wnz, float* alpha,
+                                    int32_t* zero_flag, void* stream);
+/* The grouped convolution on bnn_hip_pack_act_f32 planes of all C = d->C input channels (d->O outputs, d->flags
+ * ignored: the group mask makes every launch zero-aware).  out: float32 [N,O,Ho,Wo],
+ *     out[n,o,y,x] = fmaf(alpha[o], dot, bias ? bias[o] : 0) * (post_scale ? post_scale[o] : 1)
+ * alpha == NULL: `out` is an int32 [N,O,Ho,Wo] tensor and receives the integer dot (bias and post_scale must be NULL).
+ * groups == 1 gives the bits of bnn_hip_bconv2d with BNN_HIP_FLAG_WEIGHT_ZEROS.  Same size limits and alignments as
+ * bnn_hip_bconv2d (wnz is required, 16-byte aligned).                                                                   */
+int bnn_hip_bconv2d_grouped(const bnn_hip_conv_desc* d, int groups, const uint64_t* P, const uint64_t* M,
+                            const uint32_t* wbits, const uint32_t* wnz, const float* alpha, const float* bias,
+                            const float* post_scale, float* out, void* stream);
 
 /* Binary fully-connected layer: x packed as [B][ceil(F/64)] planes (pack_act with
  * H=W=1, i.e. [B][ceil(F/64)] words), weight packed with KH=KW=1.  out: float32 [B,O].                         */

@@ -353,6 +353,40 @@ int launch_bn_relu_pool_bwd(const float* gy, const float* p, const unsigned char
   REQUIRE(gy && p && code && x && m && is && partial && work && dx && S >= 1);
   return BNN_HIP_OK;
 }
+// grouped convolutions (csrc/bconv_grouped.hip, pack_weight.hip): the windowed weight layout must hold every block's window
+static void check_group_windows(long long O, long long C, long long G, long long S, long long cw32) {
+  REQUIRE(G >= 1 && C % G == 0 && O % G == 0 && S >= 1);
+  const long long Cg = C / G, Og = O / G, nb = (O + 31) / 32;
+  for (int k = 0; k < 40; ++k) {   // the first blocks, the last ones and random ones
+    const long long ob = k < 16 ? k : k < 24 ? nb - 1 - (k - 16) : (long long)(rnd() % (uint64_t)nb);
+    if (ob < 0 || ob >= nb) continue;
+    const long long o0 = 32 * ob, o1 = (O < o0 + 32 ? O : o0 + 32) - 1;
+    const long long w_lo = (o0 / Og) * Cg / 32, w_hi = ((o1 / Og + 1) * Cg - 1) / 32;
+    REQUIRE(w_lo >= 0 && w_lo <= w_hi && w_hi - w_lo + 1 <= S);
+    if (cw32 > 0) REQUIRE(w_hi < cw32);  // the kernel reads words w_lo .. min(w_lo + S, cw32) - 1
+  }
+}
+int launch_pack_weight_grouped(const float* w, int O, int Cg, int groups, int, int, const bnn_hip_wlayout& L,
+                               uint32_t* wb, uint32_t* wz, float* alpha, int32_t* flag, hipStream_t) {
+  ++g_reached;
+  REQUIRE(w && wb && wz && alpha && flag && O > 0 && Cg > 0 && groups > 0 && O % groups == 0);
+  REQUIRE(L.cw32 >= 1 && L.cwc == L.cw32 && L.nchunk == 1 && L.o_pad >= O && L.o_pad % 32 == 0 && L.taps > 0);
+  REQUIRE(L.n_words == (int64_t)L.o_pad * L.taps * L.cw32 && L.n_words <= (1LL << 31) - 1);
+  REQUIRE((long long)O * Cg * L.taps <= (1LL << 31) - 1);
+  check_group_windows(O, (long long)Cg * groups, groups, L.cw32, 0);
+  return BNN_HIP_OK;
+}
+int launch_bconv_grouped(const ConvP& p, int groups, int S, hipStream_t) {
+  ++g_reached;
+  check_convp(p);
+  REQUIRE((long long)p.N * p.H * p.Wd * ((p.C + 63) / 64) <= kPlaneWords);
+  REQUIRE(p.P && p.M && p.W && p.Z && p.out && al(p.P, 16) && al(p.M, 16) && al(p.W, 16) && al(p.Z, 16) && al(p.out, 4));
+  REQUIRE(p.raw ? (!p.alpha && !p.bias && !p.scale) : p.alpha != nullptr);
+  REQUIRE(!p.outP && !p.outM && !p.res && !p.bn_a && !p.ds_P);
+  REQUIRE((long long)((p.O + 31) / 32 * 32) * p.KH * p.KW * S <= (1LL << 31) - 1);
+  check_group_windows(p.O, p.C, groups, S, p.cw32);
+  return BNN_HIP_OK;
+}
 int launch_probe_int_alu(int mode, int iters, double* r, double*, hipStream_t) { REQUIRE(iters > 0 && r); (void)mode; return BNN_HIP_OK; }
 int launch_probe_clock(int it, double* mhz, double*, hipStream_t) { REQUIRE(it > 0 && mhz); return BNN_HIP_OK; }
 }  // namespace bnn
@@ -381,6 +415,15 @@ bnn_hip_conv_desc pick_desc() {
   d.flags = (int)(rnd() % 128);
   return d;
 }
+// a group count for C / O: mostly one that divides them (the BATS shapes, depthwise), sometimes anything
+int pick_groups(int C, int O) {
+  const uint64_t r = rnd() % 8;
+  if (r == 0) return pick_int();
+  if (r == 1) return C;
+  const int g[] = {1, 2, 3, 4, 12, 16};
+  const int v = g[rnd() % 6];
+  return (C > 0 && O > 0 && C % v == 0 && O % v == 0) ? v : 1;
+}
 bool status_ok(int st) { return st <= 0 && st >= -5; }
 }  // namespace
 
@@ -391,7 +434,7 @@ int main(int argc, char** argv) {
   for (long it = 0; it < iters; ++it) {
     ++g_calls;
     int st = 0;
-    switch (rnd() % 44) {
+    switch (rnd() % 47) {
       case 0: { bnn_hip_conv_desc d = pick_desc();
         st = bnn_hip_bconv2d(rnd() % 16 ? &d : nullptr, pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<uint32_t>(),
                              pick_ptr<uint32_t>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), stream);
@@ -548,6 +591,25 @@ int main(int argc, char** argv) {
                                                 pick_ptr<uint32_t>(), stream); break;
       case 33: st = bnn_hip_xnor_grad_pack_weight_f32(pick_ptr<float>(), pick_int(), pick_int(), pick_int(), pick_int(), pick_int(),
                                                       pick_ptr<float>(), pick_ptr<float>(), stream); break;
+      case 44: { bnn_hip_wlayout L; const int O = pick_int(), C = pick_int(), G = pick_groups(C, O);
+        st = bnn_hip_grouped_weight_layout(O, C, G, pick_int(), pick_int(), rnd() % 16 ? &L : nullptr);
+        if (st == BNN_HIP_OK && (L.cw32 < 1 || L.nchunk != 1 || L.n_words != (int64_t)L.o_pad * L.taps * L.cw32))
+          broken("grouped weight layout");
+        if (st == BNN_HIP_OK) bnn::check_group_windows(O, C, G, L.cw32, 2 * ((C + 63LL) / 64));
+        break; }
+      case 45: { const int O = pick_int(), Cg = pick_int(), G = rnd() % 4 ? pick_groups(O, O) : pick_int();
+        st = bnn_hip_pack_weight_grouped_f32(pick_ptr<float>(), O, Cg, G, pick_int(), pick_int(), pick_int(), pick_int(),
+                                             pick_ptr<uint32_t>(), pick_ptr<uint32_t>(), pick_ptr<float>(),
+                                             pick_ptr<int32_t>(), stream);
+        break; }
+      case 46: { bnn_hip_conv_desc d = pick_desc();
+        if (rnd() % 2) { d.O = d.C; }   // depthwise / BATS-like: C == O
+        const bool raw = rnd() % 4 == 0;
+        st = bnn_hip_bconv2d_grouped(rnd() % 16 ? &d : nullptr, pick_groups(d.C, d.O), pick_ptr<uint64_t>(),
+                                     pick_ptr<uint64_t>(), pick_ptr<uint32_t>(), pick_ptr<uint32_t>(),
+                                     raw ? nullptr : pick_ptr<float>(), raw ? nullptr : pick_ptr<float>(),
+                                     raw ? nullptr : pick_ptr<float>(), pick_ptr<float>(), stream);
+        break; }
       default: { bnn_hip_conv_desc d = pick_desc();
         (void)bnn_hip_shortcut_fold_supported(rnd() % 16 ? &d : nullptr, pick_int());
         st = bnn_hip_blinear(pick_int(), pick_int(), pick_int(), pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<uint32_t>(),
