@@ -973,11 +973,12 @@ int bnn_hip_hblock_forward(const bnn_hip_hblock_desc* d, const uint64_t* in_P, c
   const int st = check_hblock(d);
   if (st != BNN_HIP_OK) return st;
   if (!in_P || !weights || !consts || !residual || !out || residual == out) return BNN_HIP_ERR_INVALID_ARG;
-  if (!aligned(in_P, 8) || !aligned(weights, 64) || !aligned(consts, 8) || !aligned(residual, 4) || !aligned(out, 4) ||
+  if (!aligned(in_P, 8) || !aligned(weights, 64) || !aligned(consts, 32) || !aligned(residual, 4) || !aligned(out, 4) ||
       (out_P && !aligned(out_P, 8)))
     return BNN_HIP_ERR_INVALID_ARG;
   if (d->flags & BNN_HIP_HBLOCK_CHANNEL_LANES) {
     if (!bnn::hblock_cl_supported(d)) return BNN_HIP_ERR_UNSUPPORTED;
+    if (d->W == 14 && (!aligned(residual, 8) || !aligned(out, 8))) return BNN_HIP_ERR_INVALID_ARG;   // two pixels per access
     g_launches.fetch_add(1, std::memory_order_relaxed);
     Range range("bnn_hip_hblock_forward(channel lanes)");
     return bnn::launch_hblock_cl(d, in_P, weights, consts, residual, out, out_P, static_cast<hipStream_t>(stream));
@@ -1000,7 +1001,7 @@ int bnn_hip_hblock_pool_forward(const bnn_hip_hblock_desc* d, const uint64_t* in
   if (st != BNN_HIP_OK) return st;
   if (d->flags & BNN_HIP_HBLOCK_CHANNEL_LANES) return BNN_HIP_ERR_INVALID_ARG;
   if (!in_P || !weights || !consts || !pool_consts || !residual || !out_P1 || !out_P2 || !out_M2) return BNN_HIP_ERR_INVALID_ARG;
-  if (!aligned(in_P, 8) || !aligned(weights, 64) || !aligned(consts, 8) || !aligned(pool_consts, 32) || !aligned(residual, 4) ||
+  if (!aligned(in_P, 8) || !aligned(weights, 64) || !aligned(consts, 32) || !aligned(pool_consts, 32) || !aligned(residual, 4) ||
       !aligned(out_P1, 8) || !aligned(out_P2, 8) || !aligned(out_M2, 8))
     return BNN_HIP_ERR_INVALID_ARG;
   if (!bnn::hblock_pool_supported(d)) return BNN_HIP_ERR_UNSUPPORTED;
@@ -1031,11 +1032,12 @@ int bnn_hip_hblock_shortcut_forward(const bnn_hip_hblock_desc* d, const uint64_t
   const int st = check_hblock(d);
   if (st != BNN_HIP_OK) return st;
   if (!in_P || !weights || !consts || !sc_P || !sc_M || !sc_weights || !sc_alpha || !out || !out_P) return BNN_HIP_ERR_INVALID_ARG;
-  if (!aligned(in_P, 8) || !aligned(weights, 64) || !aligned(consts, 8) || !aligned(sc_P, 8) || !aligned(sc_M, 8) ||
+  if (!aligned(in_P, 8) || !aligned(weights, 64) || !aligned(consts, 32) || !aligned(sc_P, 8) || !aligned(sc_M, 8) ||
       !aligned(sc_weights, 32) || !aligned(sc_alpha, 32) || !aligned(out, 4) || !aligned(out_P, 8))
     return BNN_HIP_ERR_INVALID_ARG;
   if (d->flags & BNN_HIP_HBLOCK_CHANNEL_LANES) {   // (weights: those of bnn_hip_hblock_pack_weights_cl)
     if (!bnn::hblock_cl_ds_supported(d)) return BNN_HIP_ERR_UNSUPPORTED;
+    if (d->W == 14 && !aligned(out, 8)) return BNN_HIP_ERR_INVALID_ARG;              // two pixels per store
     g_launches.fetch_add(1, std::memory_order_relaxed);
     Range range("bnn_hip_hblock_shortcut_forward(channel lanes)");
     return bnn::launch_hblock_cl_ds(d, in_P, weights, consts, sc_P, sc_M, sc_weights, sc_alpha, out, out_P,

@@ -552,6 +552,11 @@ typedef struct bnn_hip_hblock_desc {
   int32_t waves;            /* 0 = 16; wavefronts per workgroup, 1..16                                                */
   int32_t reserved;
 } bnn_hip_hblock_desc;
+/* Alignment, all three hblock entry points (bnn_hip_hblock_forward, _pool_forward, _shortcut_forward): `consts` 32 bytes (the
+ * kernels read it eight floats at a time; the layout's offsets keep every piece on such a boundary), `weights` 64 bytes, the
+ * uint64 planes 8 bytes, the fp32 tensors 4 bytes — except with BNN_HIP_HBLOCK_CHANNEL_LANES on 14 x 14 images, where
+ * `residual` and `out` are accessed two pixels at a time and must be 8-byte aligned.  A misaligned pointer is refused with
+ * BNN_HIP_ERR_INVALID_ARG before any launch.                                                                          */
 typedef struct bnn_hip_hblock_layout {
   int64_t weight_words;     /* uint32 words of the weight buffer (64-byte aligned)                                    */
   int64_t w_off[3];         /* word offset of conv1 / conv2 / conv3 in it                                             */

@@ -131,8 +131,8 @@ bool hblock_cl_ds_supported(const bnn_hip_hblock_desc* d) {
 int launch_hblock_cl_ds(const bnn_hip_hblock_desc* d, const uint64_t* inP, const uint32_t* W, const float* Kc, const uint64_t* p,
                         const uint64_t* m, const uint32_t* w, const float* a, float* out, uint64_t* outP, hipStream_t) {
   ++g_reached;
-  REQUIRE(d && inP && W && Kc && p && m && w && a && out && outP && al(w, 32) && al(a, 32) && al(outP, 8));
-  REQUIRE(d->N > 0 && d->planes == 2 * d->C_in && d->H == d->W);
+  REQUIRE(d && inP && W && Kc && p && m && w && a && out && outP && al(w, 32) && al(a, 32) && al(outP, 8) && al(Kc, 32));
+  REQUIRE(d->N > 0 && d->planes == 2 * d->C_in && d->H == d->W && (d->W != 14 || al(out, 8)));
   return BNN_HIP_OK;
 }
 bool hblock_ds_supported(const bnn_hip_hblock_desc* d) {
@@ -141,7 +141,8 @@ bool hblock_ds_supported(const bnn_hip_hblock_desc* d) {
 int launch_hblock_ds(const bnn_hip_hblock_desc* d, const uint64_t* inP, const uint32_t* W, const float* Kc, const uint64_t* p,
                      const uint64_t* m, const uint32_t* w, const float* a, float* out, uint64_t* outP, hipStream_t) {
   ++g_reached;
-  REQUIRE(d && inP && W && Kc && p && m && w && a && out && outP && al(w, 32) && al(a, 32) && al(outP, 8) && al(p, 8) && al(m, 8));
+  REQUIRE(d && inP && W && Kc && p && m && w && a && out && outP && al(w, 32) && al(a, 32) && al(outP, 8) && al(p, 8) && al(m, 8) &&
+          al(Kc, 32));
   REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->planes == 2 * d->C_in);
   return BNN_HIP_OK;
 }
@@ -157,7 +158,7 @@ bool hblock_pool_supported(const bnn_hip_hblock_desc* d) {
 int launch_hblock_pool(const bnn_hip_hblock_desc* d, const uint64_t* inP, const uint32_t* W, const float* Kc, const float* Kp,
                        const float* res, uint64_t* o1, uint64_t* o2, uint64_t* o3, hipStream_t) {
   ++g_reached;
-  REQUIRE(d && inP && W && Kc && Kp && res && o1 && o2 && o3 && al(Kp, 32) && al(o1, 8) && al(o2, 8) && al(o3, 8));
+  REQUIRE(d && inP && W && Kc && Kp && res && o1 && o2 && o3 && al(Kc, 32) && al(Kp, 32) && al(o1, 8) && al(o2, 8) && al(o3, 8));
   REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->H % 2 == 0 && d->W % 2 == 0 && d->C_in == d->planes);
   return BNN_HIP_OK;
 }
@@ -168,7 +169,7 @@ int launch_hblock_pack_weights(int C_in, int planes, const uint32_t* const w[3],
 int launch_hblock(const bnn_hip_hblock_desc* d, const uint64_t* inP, const uint32_t* W, const float* Kc, const float* res,
                   float* out, uint64_t* outP, hipStream_t) {
   ++g_reached;
-  REQUIRE(d && inP && W && Kc && res && out && res != out && al(inP, 8) && al(W, 64) && (!outP || al(outP, 8)));
+  REQUIRE(d && inP && W && Kc && res && out && res != out && al(inP, 8) && al(W, 64) && al(Kc, 32) && (!outP || al(outP, 8)));
   REQUIRE(stub_hb_shape(d->C_in, d->planes) && (long long)d->N * d->planes * d->H * d->W <= kConvElems);
   REQUIRE((long long)d->N * ((d->C_in + 63) / 64) * d->H * d->W <= kPlaneWords);
   return BNN_HIP_OK;
@@ -184,8 +185,8 @@ int launch_hblock_cl_pack_weights(int C_in, int planes, const uint32_t* const w[
 int launch_hblock_cl(const bnn_hip_hblock_desc* d, const uint64_t* inP, const uint32_t* W, const float* Kc, const float* res,
                      float* out, uint64_t* outP, hipStream_t) {
   ++g_reached;
-  REQUIRE(d && inP && W && Kc && res && out && res != out && al(inP, 8) && al(W, 64) && (!outP || al(outP, 8)));
-  REQUIRE(d->planes % 256 == 0 && d->H == d->W && (d->H == 7 || d->H == 14));
+  REQUIRE(d && inP && W && Kc && res && out && res != out && al(inP, 8) && al(W, 64) && al(Kc, 32) && (!outP || al(outP, 8)));
+  REQUIRE(d->planes % 256 == 0 && d->H == d->W && (d->H == 7 || d->H == 14) && (d->W != 14 || (al(res, 8) && al(out, 8))));
   return BNN_HIP_OK;
 }
 int launch_orpool_packed(const uint64_t* P, int N, int C, int H, int W, int k, uint64_t* oP, uint64_t* oM, hipStream_t) {
