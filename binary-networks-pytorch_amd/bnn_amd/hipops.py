@@ -29,6 +29,34 @@ def _batch_step(n: int, per_img_elems: int, chan_factor: int) -> int:
     return max(1, step)
 
 
+def _launch_images(n: int, C: int, O: int, c_total: int, in_elems: int, out_pixels: int) -> int:
+    """Images one convolution launch covers (``_batch_step``): the fp32 output holds ``c_total`` channels, the input
+    ``in_elems`` fp32-sized elements per image (sign planes count twice: they are limited to 2^29 uint64 words per
+    launch, half the fp32 element budget: capi.hip check_desc), the output planes ``O`` channels."""
+    per_img = max(c_total * out_pixels, in_elems, 2 * out_pixels * ((O + 63) // 64))
+    return _batch_step(n, per_img, max(c_total, O, (C + 63) // 64))
+
+
+def _stem_launch_images(n: int, H: int, W: int, ho: int, wo: int) -> int:
+    """Images one stem launch covers: the kernels address x ``[n, 3, H, W]`` and the output ``[n, 64, ho, wo]`` through
+    32-bit buffer descriptors, so each stays below 2^32 - 512 bytes (include/bnn_hip.h)."""
+    return max(1, min(n, _MAX_DESC_BYTES // max(12 * H * W, 256 * ho * wo)))
+
+
+def _desc_slices(d: native.ConvDesc, step: int):
+    """``(n0, n1, descriptor of images [n0, n1))`` for each launch of the descriptor's batch cut into ``step`` images."""
+    for n0 in range(0, d.N, step):
+        n1 = min(d.N, n0 + step)
+        dd = native.ConvDesc.from_buffer_copy(d)
+        dd.N = n1 - n0
+        yield n0, n1, dd
+
+
+def _half_hw(H: int, W: int) -> Tuple[int, int]:
+    """Output extents of the stem's stride-2 stages: conv 7x7 / 2 / 3 and MaxPool 3x3 / 2 / 1 alike."""
+    return (H - 1) // 2 + 1, (W - 1) // 2 + 1
+
+
 def _pair(v) -> Tuple[int, int]:
     if isinstance(v, int):
         return v, v
@@ -51,6 +79,15 @@ def _require_cuda_f32(t: torch.Tensor, what: str) -> torch.Tensor:
     if t.dtype != torch.float32:
         raise native.NativeError(f"bnn_amd: {what} must be float32, got {t.dtype}")
     return t.contiguous()
+
+
+def _require_cuda_act(x: torch.Tensor) -> torch.Tensor:
+    """An activation the packing kernels read: fp16 stays as it is, everything else must be fp32, on a HIP device."""
+    if x.dtype != torch.float16:
+        return _require_cuda_f32(x, "activation")
+    if not x.is_cuda:
+        raise native.NativeError(f"bnn_amd: activation must live on a HIP device, got {x.device}")
+    return x.contiguous()
 
 
 def _per_channel(t: Optional[torch.Tensor], n: int, what: str) -> Optional[torch.Tensor]:
@@ -108,12 +145,7 @@ def empty_packed(N: int, C: int, H: int, W: int, device) -> PackedAct:
 
 def pack_act(x: torch.Tensor) -> PackedAct:
     """``BasicInputBinarizer`` on device: fp32 (or fp16) NCHW -> bit planes (bnn/ops.py:151-152)."""
-    if x.dtype == torch.float16:
-        if not x.is_cuda:
-            raise native.NativeError(f"bnn_amd: activation must live on a HIP device, got {x.device}")
-        x = x.contiguous()
-    else:
-        x = _require_cuda_f32(x, "activation")
+    x = _require_cuda_act(x)
     if x.dim() != 4:
         raise native.NativeError(f"bnn_amd: pack_act expects NCHW, got shape {tuple(x.shape)}")
     lib = native.require()
@@ -201,8 +233,7 @@ def stem7x7(x: torch.Tensor, w: torch.Tensor, bn_scale: torch.Tensor, bn_shift: 
         raise native.NativeError("bnn_amd: stem7x7 expects x [N,3,H,W] and w [64,3,7,7]")
     lib = native.require()
     N, _, H, W = x.shape
-    hc, wc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    hp, wp = (hc - 1) // 2 + 1, (wc - 1) // 2 + 1
+    hp, wp = _half_hw(*_half_hw(H, W))
     bn_scale = _per_channel(bn_scale, 64, "bn_scale")
     bn_shift = _per_channel(bn_shift, 64, "bn_shift")
     with torch.cuda.device(x.device):
@@ -215,9 +246,7 @@ def stem7x7(x: torch.Tensor, w: torch.Tensor, bn_scale: torch.Tensor, bn_shift: 
         else:
             y = torch.empty((N, 64, hp, wp), dtype=torch.float32, device=x.device) if out_f32 else None
             pk = empty_packed(N, 64, hp, wp, x.device) if out_packed else None
-        # the kernel addresses x and out through 32-bit buffer descriptors: a launch stays below 2^32 - 512 bytes per
-        # tensor (include/bnn_hip.h) — larger batches go in several launches
-        step = max(1, min(N, _MAX_DESC_BYTES // max(12 * H * W, 256 * hp * wp)))
+        step = _stem_launch_images(N, H, W, hp, wp)   # larger batches go in several launches
         flags = native.STEM_EXACT_FP32 if exact_fp32 else (native.STEM_FP16 if fp16 else 0)
         if pack_affine is not None:
             if exact_fp32 or pk is None:
@@ -251,10 +280,10 @@ def stem7x7_conv(x: torch.Tensor, w: torch.Tensor, fp16: bool = False) -> torch.
         raise native.NativeError("bnn_amd: stem7x7_conv expects x [N,3,H,W] and w [64,3,7,7]")
     lib = native.require()
     N, _, H, W = x.shape
-    hc, wc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    hc, wc = _half_hw(H, W)
     with torch.cuda.device(x.device):
         y = torch.empty((N, 64, hc, wc), dtype=torch.float32, device=x.device)
-        step = max(1, min(N, _MAX_DESC_BYTES // max(12 * H * W, 256 * hc * wc)))   # 32-bit descriptors (see stem7x7)
+        step = _stem_launch_images(N, H, W, hc, wc)
         for n0 in range(0, N, step):
             n1 = min(N, n0 + step)
             native.check(lib.bnn_hip_stem7x7_conv_f32(x[n0:n1].data_ptr(), w.data_ptr(), n1 - n0, H, W,
@@ -279,8 +308,7 @@ def stem7x7_wgrad(x: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
     if x.dim() != 4 or x.shape[1] != 3:
         raise native.NativeError(f"bnn_amd: stem7x7_wgrad expects x [N,3,H,W], got {tuple(x.shape)}")
     N, _, H, W = x.shape
-    hc, wc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    if tuple(dy.shape) != (N, 64, hc, wc):
+    if tuple(dy.shape) != (N, 64) + _half_hw(H, W):
         raise native.NativeError("bnn_amd: stem7x7_wgrad expects x [N,3,H,W] and dy [N,64,Hc,Wc]")
     lib = native.require()
     with torch.cuda.device(x.device):
@@ -407,6 +435,37 @@ def bn_relu_maxpool_pack(x: torch.Tensor, bn_scale=None, bn_shift=None, relu: bo
     return y, pk
 
 
+def _weight_f32(w: torch.Tensor) -> Tuple[torch.Tensor, bool]:
+    """The weight as fp32 on its HIP device + whether it came as fp16 (a `.half()` model: the sign bits are those of the
+    exact fp32 widening; ``_run_weight_pack`` rounds alpha to fp16)."""
+    half = w.dtype == torch.float16
+    if half:
+        w = w.detach().float()
+    return _require_cuda_f32(w.detach(), "weight"), half
+
+
+def _run_weight_pack(w: torch.Tensor, half: bool, L: native.WLayout, what: str, sync: bool, launch, **kind) -> PackedWeight:
+    """What ``pack_weight`` and ``pack_weight_grouped`` share: the buffers of layout ``L``, the launch
+    (``launch(wbits, wnz, alpha, zero flag, stream)`` -> status of the entry point ``what``) and the zero-weight flag's
+    way back to the host (their ``sync``).  ``kind``: the ``PackedWeight`` fields beyond those of a dense pack."""
+    with torch.cuda.device(w.device):
+        wbits = torch.empty(L.n_words, dtype=torch.int32, device=w.device)
+        wnz = torch.empty(L.n_words, dtype=torch.int32, device=w.device)
+        alpha = torch.empty(L.o_pad, dtype=torch.float32, device=w.device)
+        flag = torch.zeros(1, dtype=torch.int32, device=w.device)
+        native.check(launch(wbits.data_ptr(), wnz.data_ptr(), alpha.data_ptr(), flag.data_ptr(), _stream(w.device)), what)
+        if half:  # the reference computes alpha in the weight's own dtype (bnn/ops.py:116-127)
+            alpha = alpha.half().float()
+        if not sync:
+            host = torch.empty(1, dtype=torch.int32, pin_memory=True)
+            host.copy_(flag, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(w.device))
+            return PackedWeight(wbits, wnz, alpha, False, tuple(w.shape), (host, ev), **kind)
+        has_zero = bool(flag.item())
+    return PackedWeight(wbits, wnz, alpha, has_zero, tuple(w.shape), **kind)
+
+
 def pack_weight(w: torch.Tensor, center: bool = False, compute_alpha: bool = True,
                 sync: bool = True) -> PackedWeight:
     """``XNORWeightBinarizer`` on device (bnn/ops.py:116-140).  Synchronises once to read the
@@ -415,10 +474,7 @@ def pack_weight(w: torch.Tensor, center: bool = False, compute_alpha: bool = Tru
     ``sync=False`` (training: the weight changes every step) assumes "no exact zero" and returns at once;
     the flag travels to pinned host memory asynchronously and ``PackedWeight.zero_found_later()`` tells
     afterwards whether the assumption held (the caller then re-packs with ``sync=True``)."""
-    half = w.dtype == torch.float16
-    if half:   # a `.half()` model: the sign bits are those of the exact fp32 widening; alpha is rounded to fp16 below
-        w = w.detach().float()
-    w = _require_cuda_f32(w.detach(), "weight")
+    w, half = _weight_f32(w)
     if w.dim() == 2:
         w = w[:, :, None, None]
     elif w.dim() == 3:
@@ -428,27 +484,9 @@ def pack_weight(w: torch.Tensor, center: bool = False, compute_alpha: bool = Tru
     w = w.contiguous()
     lib = native.require()
     O, C, KH, KW = w.shape
-    L = native.weight_layout(O, C, KH, KW)
-    with torch.cuda.device(w.device):
-        wbits = torch.empty(L.n_words, dtype=torch.int32, device=w.device)
-        wnz = torch.empty(L.n_words, dtype=torch.int32, device=w.device)
-        alpha = torch.empty(L.o_pad, dtype=torch.float32, device=w.device)
-        flag = torch.zeros(1, dtype=torch.int32, device=w.device)
-        native.check(lib.bnn_hip_pack_weight_f32(w.data_ptr(), O, C, KH, KW, int(center),
-                                                 int(compute_alpha), wbits.data_ptr(),
-                                                 wnz.data_ptr(), alpha.data_ptr(), flag.data_ptr(),
-                                                 _stream(w.device)),
-                     "bnn_hip_pack_weight_f32")
-        if half:  # the reference computes alpha in the weight's own dtype (bnn/ops.py:116-127)
-            alpha = alpha.half().float()
-        if not sync:
-            host = torch.empty(1, dtype=torch.int32, pin_memory=True)
-            host.copy_(flag, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(w.device))
-            return PackedWeight(wbits, wnz, alpha, False, (O, C, KH, KW), (host, ev))
-        has_zero = bool(flag.item())
-    return PackedWeight(wbits, wnz, alpha, has_zero, (O, C, KH, KW))
+    return _run_weight_pack(w, half, native.weight_layout(O, C, KH, KW), "bnn_hip_pack_weight_f32", sync,
+                            lambda *out: lib.bnn_hip_pack_weight_f32(w.data_ptr(), O, C, KH, KW, int(center),
+                                                                     int(compute_alpha), *out))
 
 
 def pack_weight_grouped(w: torch.Tensor, groups: int, center: bool = False, compute_alpha: bool = True,
@@ -457,10 +495,7 @@ def pack_weight_grouped(w: torch.Tensor, groups: int, center: bool = False, comp
     the windowed block-diagonal layout of ``bnn_hip_bconv2d_grouped`` (include/bnn_hip.h).  Centring and alpha reduce
     over the group's channels as the reference does; alpha has the bits of ``pack_weight`` of the same tensor.  fp16
     weights and ``sync`` as in ``pack_weight``."""
-    half = w.dtype == torch.float16
-    if half:
-        w = w.detach().float()
-    w = _require_cuda_f32(w.detach(), "weight")
+    w, half = _weight_f32(w)
     if w.dim() == 3:
         w = w[:, :, None, :]
     if w.dim() != 4:
@@ -471,25 +506,10 @@ def pack_weight_grouped(w: torch.Tensor, groups: int, center: bool = False, comp
     if groups < 1 or O % groups:
         raise native.NativeError(f"bnn_amd: {O} output channels do not split into {groups} groups")
     L = native.grouped_weight_layout(O, Cg * groups, groups, KH, KW)
-    with torch.cuda.device(w.device):
-        wbits = torch.empty(L.n_words, dtype=torch.int32, device=w.device)
-        wnz = torch.empty(L.n_words, dtype=torch.int32, device=w.device)
-        alpha = torch.empty(L.o_pad, dtype=torch.float32, device=w.device)
-        flag = torch.zeros(1, dtype=torch.int32, device=w.device)
-        native.check(lib.bnn_hip_pack_weight_grouped_f32(w.data_ptr(), O, Cg, groups, KH, KW, int(center),
-                                                         int(compute_alpha), wbits.data_ptr(), wnz.data_ptr(),
-                                                         alpha.data_ptr(), flag.data_ptr(), _stream(w.device)),
-                     "bnn_hip_pack_weight_grouped_f32")
-        if half:
-            alpha = alpha.half().float()
-        if not sync:
-            host = torch.empty(1, dtype=torch.int32, pin_memory=True)
-            host.copy_(flag, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(w.device))
-            return PackedWeight(wbits, wnz, alpha, False, (O, Cg, KH, KW), (host, ev), groups=groups, windowed=True)
-        has_zero = bool(flag.item())
-    return PackedWeight(wbits, wnz, alpha, has_zero, (O, Cg, KH, KW), groups=groups, windowed=True)
+    return _run_weight_pack(w, half, L, "bnn_hip_pack_weight_grouped_f32", sync,
+                            lambda *out: lib.bnn_hip_pack_weight_grouped_f32(w.data_ptr(), O, Cg, groups, KH, KW, int(center),
+                                                                             int(compute_alpha), *out),
+                            groups=groups, windowed=True)
 
 
 def _ungrouped(w: PackedWeight, what: str) -> None:
@@ -548,13 +568,8 @@ def bconv2d(a: PackedAct, w: PackedWeight, bias: Optional[torch.Tensor] = None,
         if d.N == 0:
             return out
         # one launch addresses < 2^31 elements: split the batch when a tensor is larger
-        # (the planes are limited to 2^29 uint64 words per launch, half the fp32 element budget: capi.hip check_desc)
-        per_img = max(d.O * ho * wo, 2 * d.H * d.W * ((d.C + 63) // 64), 2 * ho * wo * ((d.O + 63) // 64))
-        step = _batch_step(d.N, per_img, max(d.O, (d.C + 63) // 64))
-        for n0 in range(0, d.N, step):
-            n1 = min(d.N, n0 + step)
-            dd = native.ConvDesc.from_buffer_copy(d)
-            dd.N = n1 - n0
+        step = fused_launch_images(d.N, d.C, d.H, d.W, d.O, (d.KH, d.KW), stride, padding, dilation)
+        for n0, n1, dd in _desc_slices(d, step):
             args = (ctypes.byref(dd), a.P[n0:n1].data_ptr(), a.M[n0:n1].data_ptr(),
                     w.wbits.data_ptr(), w.wnz.data_ptr())
             if raw_dot:
@@ -590,12 +605,8 @@ def bconv2d_grouped(a: PackedAct, w: PackedWeight, bias: Optional[torch.Tensor] 
         out = torch.empty((N, O, ho, wo), dtype=torch.int32 if raw_dot else torch.float32, device=dev)
         if N == 0:
             return out
-        per_img = max(O * ho * wo, 2 * H * W * ((C + 63) // 64), 2 * ho * wo * ((O + 63) // 64))
-        step = _batch_step(N, per_img, max(O, (C + 63) // 64))
-        for n0 in range(0, N, step):
-            n1 = min(N, n0 + step)
-            dd = native.ConvDesc.from_buffer_copy(d)
-            dd.N = n1 - n0
+        step = fused_launch_images(N, C, H, W, O, (KH, KW), stride, padding, dilation)
+        for n0, n1, dd in _desc_slices(d, step):
             native.check(lib.bnn_hip_bconv2d_grouped(ctypes.byref(dd), w.groups, a.P[n0:n1].data_ptr(),
                                                      a.M[n0:n1].data_ptr(), w.wbits.data_ptr(), w.wnz.data_ptr(),
                                                      None if raw_dot else w.alpha.data_ptr(), _ptr(bias),
@@ -611,7 +622,7 @@ def direct_plan(x_shape, w: PackedWeight, stride=1, padding=0, dilation=1) -> Op
     d = _desc(tuple(x_shape), w.shape, stride, padding, dilation, native.FLAG_WEIGHT_ZEROS if w.has_zero else 0)
     plan = native.FlyPlan()
     st = lib.bnn_hip_bconv2d_direct_plan(ctypes.byref(d), ctypes.byref(plan))
-    if st == -2:      # BNN_HIP_ERR_UNSUPPORTED
+    if st == native.ERR_UNSUPPORTED:
         return None
     native.check(st, "bnn_hip_bconv2d_direct_plan")
     return plan
@@ -641,12 +652,7 @@ def bconv2d_direct(x: torch.Tensor, w: PackedWeight, bias: Optional[torch.Tensor
     if route not in (None, "direct", "packed"):
         raise ValueError("route must be None, 'direct' or 'packed'")
     _ungrouped(w, "bconv2d_direct")
-    if x.dtype == torch.float16:
-        if not x.is_cuda:
-            raise native.NativeError(f"bnn_amd: activation must live on a HIP device, got {x.device}")
-        x = x.contiguous()
-    else:
-        x = _require_cuda_f32(x, "activation")
+    x = _require_cuda_act(x)
     if x.dim() != 4:
         raise native.NativeError(f"bnn_amd: bconv2d_direct expects NCHW, got shape {tuple(x.shape)}")
     lib = native.require()
@@ -661,18 +667,14 @@ def bconv2d_direct(x: torch.Tensor, w: PackedWeight, bias: Optional[torch.Tensor
         out = torch.empty((d.N, d.O, ho, wo), dtype=torch.float32, device=dev)
         if d.N == 0:
             return out
-        per_img = max(d.O * ho * wo, d.C * d.H * d.W, 2 * ho * wo * ((d.O + 63) // 64))
-        step = _batch_step(d.N, per_img, max(d.O, (d.C + 63) // 64))
+        step = _launch_images(d.N, d.C, d.O, d.O, d.C * d.H * d.W, ho * wo)   # (the input is fp32 / fp16 elements here)
         dtype = native.DTYPE_F16 if x.dtype == torch.float16 else native.DTYPE_F32
-        for n0 in range(0, d.N, step):
-            n1 = min(d.N, n0 + step)
-            dd = native.ConvDesc.from_buffer_copy(d)
-            dd.N = n1 - n0
+        for n0, n1, dd in _desc_slices(d, step):
             st = lib.bnn_hip_bconv2d_direct(ctypes.byref(dd), x[n0:n1].data_ptr(), dtype, w.wbits.data_ptr(),
                                             w.wnz.data_ptr(), w.alpha.data_ptr(), _ptr(bias), _ptr(post_scale),
                                             out[n0:n1].data_ptr(), None if plan is None else ctypes.byref(plan),
                                             _stream(dev))
-            if st == -2 and plan is None:   # BNN_HIP_ERR_UNSUPPORTED: the two-launch form of the same layer
+            if st == native.ERR_UNSUPPORTED and plan is None:   # the two-launch form of the same layer
                 out[n0:n1] = bconv2d(pack_act(x[n0:n1]), w, bias, post_scale, stride, padding, dilation,
                                      force_generic=force_generic)
                 continue
@@ -747,10 +749,7 @@ def bconv2d_fused(a: PackedAct, w: PackedWeight, *, bias=None, post_scale=None, 
         pk = empty_packed(d.N, d.O, ho, wo, dev) if out_packed else None
         # one launch addresses < 2^31 elements: split the batch when a tensor is larger (like bconv2d)
         step = fused_launch_images(d.N, d.C, d.H, d.W, d.O, (d.KH, d.KW), stride, padding, dilation, c_total)
-        for n0 in range(0, d.N, step):
-            n1 = min(d.N, n0 + step)
-            dd = native.ConvDesc.from_buffer_copy(d)
-            dd.N = n1 - n0
+        for n0, n1, dd in _desc_slices(d, step):
             e = native.Epilogue(w.alpha.data_ptr(), _ptr(bias), _ptr(post_scale), _ptr(bn_scale),
                                 _ptr(bn_shift), None if residual is None else residual[n0:n1].data_ptr(),
                                 _ptr(prelu), int(bool(relu)), eflags,
@@ -833,13 +832,30 @@ def _hblock_desc(N, c_in, H, W, planes, throughput=False, rows_per_band=0, image
     return native.HBlockDesc(N, c_in, H, W, planes, flags, rows_per_band, images_per_band, waves, 0)
 
 
+def _hblock_query(symbol: str, *geometry_and_plan) -> bool:
+    """One of the ``bnn_hip_hblock_*_supported`` questions for ``_hblock_desc(*geometry_and_plan)``."""
+    return bool(getattr(native.require(), symbol)(ctypes.byref(_hblock_desc(*geometry_and_plan))))
+
+
+def _hblock_launch(pack: "HBlockPack", a: PackedAct, throughput, rows_per_band, images_per_band, waves, channel_lanes=False):
+    """``(descriptor, weight buffer)`` of a launch on planes ``a``: the channel-lane kernels read their own weight order."""
+    N, c_in, H, W = a.shape
+    d = _hblock_desc(N, c_in, H, W, pack.planes, throughput, rows_per_band, images_per_band, waves, channel_lanes)
+    return d, (pack.channel_lane_weights() if channel_lanes else pack.weights)
+
+
+def _nonneg_planes(N: int, C: int, H: int, W: int, dev) -> PackedAct:
+    """Planes a kernel fills for a non-negative tensor: a fresh P, and the shared all-zero M it never writes."""
+    shp = (N, C // 64, H, W)
+    return PackedAct(torch.empty(shp, dtype=torch.int64, device=dev), _zero_plane(shp, dev), (N, C, H, W), nonneg=True)
+
+
 def hblock_supported(N: int, c_in: int, H: int, W: int, planes: int, throughput: bool = False, rows_per_band: int = 0,
                      images_per_band: int = 0, waves: int = 0, channel_lanes: bool = False) -> bool:
     """Whether ``hblock_forward`` covers this geometry (with this plan) on the current device.  ``channel_lanes``: the
     small-image form of the kernel (csrc/hblock_cl.hip: 14 x 14 / 7 x 7, lanes = output channels)."""
-    lib = native.require()
-    d = _hblock_desc(N, c_in, H, W, planes, throughput, rows_per_band, images_per_band, waves, channel_lanes)
-    return bool(lib.bnn_hip_hblock_supported(ctypes.byref(d)))
+    return _hblock_query("bnn_hip_hblock_supported", N, c_in, H, W, planes, throughput, rows_per_band, images_per_band, waves,
+                         channel_lanes)
 
 
 def hblock_forward(a: PackedAct, pack: HBlockPack, residual: torch.Tensor, out_packed: bool = True,
@@ -860,14 +876,10 @@ def hblock_forward(a: PackedAct, pack: HBlockPack, residual: torch.Tensor, out_p
     dev = a.P.device
     with torch.cuda.device(dev):
         y = torch.empty_like(residual)
-        pk = None
-        if out_packed:
-            pk = PackedAct(torch.empty((N, pack.planes // 64, H, W), dtype=torch.int64, device=dev),
-                           _zero_plane((N, pack.planes // 64, H, W), dev), (N, pack.planes, H, W), nonneg=True)
+        pk = _nonneg_planes(N, pack.planes, H, W, dev) if out_packed else None
         if N == 0:
             return y, pk
-        d = _hblock_desc(N, c_in, H, W, pack.planes, throughput, rows_per_band, images_per_band, waves, channel_lanes)
-        wbuf = pack.channel_lane_weights() if channel_lanes else pack.weights
+        d, wbuf = _hblock_launch(pack, a, throughput, rows_per_band, images_per_band, waves, channel_lanes)
         native.check(lib.bnn_hip_hblock_forward(ctypes.byref(d), a.P.data_ptr(), wbuf.data_ptr(),
                                                 pack.consts.data_ptr(), residual.data_ptr(), y.data_ptr(),
                                                 None if pk is None else pk.P.data_ptr(), _stream(dev)),
@@ -878,9 +890,8 @@ def hblock_forward(a: PackedAct, pack: HBlockPack, residual: torch.Tensor, out_p
 def hblock_shortcut_supported(N: int, c_in: int, H: int, W: int, planes: int, throughput: bool = False, rows_per_band: int = 0,
                               images_per_band: int = 0, waves: int = 0, channel_lanes: bool = False) -> bool:
     """Whether ``hblock_shortcut_forward`` covers this geometry (with this plan) on the current device."""
-    lib = native.require()
-    d = _hblock_desc(N, c_in, H, W, planes, throughput, rows_per_band, images_per_band, waves, channel_lanes)
-    return bool(lib.bnn_hip_hblock_shortcut_supported(ctypes.byref(d)))
+    return _hblock_query("bnn_hip_hblock_shortcut_supported", N, c_in, H, W, planes, throughput, rows_per_band,
+                         images_per_band, waves, channel_lanes)
 
 
 def hblock_shortcut_pack(w: PackedWeight):
@@ -915,13 +926,10 @@ def hblock_shortcut_forward(a: PackedAct, pack: HBlockPack, sc: PackedAct, sc_pa
     dev = a.P.device
     with torch.cuda.device(dev):
         y = torch.empty((N, pack.planes, H, W), dtype=torch.float32, device=dev)
-        shp = (N, pack.planes // 64, H, W)
-        pk = PackedAct(torch.empty(shp, dtype=torch.int64, device=dev), _zero_plane(shp, dev), (N, pack.planes, H, W),
-                       nonneg=True)
+        pk = _nonneg_planes(N, pack.planes, H, W, dev)
         if N == 0:
             return y, pk
-        d = _hblock_desc(N, c_in, H, W, pack.planes, throughput, rows_per_band, images_per_band, waves, channel_lanes)
-        wbuf = pack.channel_lane_weights() if channel_lanes else pack.weights
+        d, wbuf = _hblock_launch(pack, a, throughput, rows_per_band, images_per_band, waves, channel_lanes)
         native.check(lib.bnn_hip_hblock_shortcut_forward(ctypes.byref(d), a.P.data_ptr(), wbuf.data_ptr(),
                                                          pack.consts.data_ptr(), sc.P.data_ptr(), sc.M.data_ptr(),
                                                          wsc.data_ptr(), asc.data_ptr(), y.data_ptr(), pk.P.data_ptr(),
@@ -932,9 +940,8 @@ def hblock_shortcut_forward(a: PackedAct, pack: HBlockPack, sc: PackedAct, sc_pa
 def hblock_pool_supported(N: int, c_in: int, H: int, W: int, planes: int, throughput: bool = False, rows_per_band: int = 0,
                           images_per_band: int = 0, waves: int = 0) -> bool:
     """Whether ``hblock_pool_forward`` covers this geometry (with this plan) on the current device."""
-    lib = native.require()
-    d = _hblock_desc(N, c_in, H, W, planes, throughput, rows_per_band, images_per_band, waves)
-    return bool(lib.bnn_hip_hblock_pool_supported(ctypes.byref(d)))
+    return _hblock_query("bnn_hip_hblock_pool_supported", N, c_in, H, W, planes, throughput, rows_per_band, images_per_band,
+                         waves)
 
 
 def hblock_pool_consts(bn1, bn_ds, planes: int) -> torch.Tensor:
@@ -967,15 +974,12 @@ def hblock_pool_forward(a: PackedAct, pack: HBlockPack, residual: torch.Tensor, 
         raise native.NativeError("bnn_amd: pool_consts must be the buffer of hblock_pool_consts")
     dev = a.P.device
     with torch.cuda.device(dev):
-        shp = (N, pack.planes // 64, H // 2, W // 2)
-        p1 = PackedAct(torch.empty(shp, dtype=torch.int64, device=dev), _zero_plane(shp, dev),
-                       (N, pack.planes, H // 2, W // 2), nonneg=True)
-        p2 = PackedAct(torch.empty(shp, dtype=torch.int64, device=dev), torch.empty(shp, dtype=torch.int64, device=dev),
-                       (N, pack.planes, H // 2, W // 2))
+        p1 = _nonneg_planes(N, pack.planes, H // 2, W // 2, dev)
+        p2 = PackedAct(torch.empty_like(p1.P), torch.empty_like(p1.P), p1.shape)
         if N == 0:
             return p1, p2
-        d = _hblock_desc(N, c_in, H, W, pack.planes, throughput, rows_per_band, images_per_band, waves)
-        native.check(lib.bnn_hip_hblock_pool_forward(ctypes.byref(d), a.P.data_ptr(), pack.weights.data_ptr(),
+        d, wbuf = _hblock_launch(pack, a, throughput, rows_per_band, images_per_band, waves)
+        native.check(lib.bnn_hip_hblock_pool_forward(ctypes.byref(d), a.P.data_ptr(), wbuf.data_ptr(),
                                                      pack.consts.data_ptr(), pool_consts.data_ptr(), residual.data_ptr(),
                                                      p1.P.data_ptr(), p2.P.data_ptr(), p2.M.data_ptr(), _stream(dev)),
                      "bnn_hip_hblock_pool_forward")
@@ -1000,9 +1004,7 @@ def fused_launch_images(N: int, C: int, H: int, W: int, O: int, kernel_size, str
     32-bit addressing is split into several launches): what shape-dependent decisions have to be taken on."""
     kh, kw = _pair(kernel_size)
     ho, wo = conv_out_hw(H, W, kh, kw, stride, padding, dilation)
-    c_total = O if c_total is None else c_total
-    per_img = max(c_total * ho * wo, 2 * H * W * ((C + 63) // 64), 2 * ho * wo * ((O + 63) // 64), 1)
-    return _batch_step(N, per_img, max(c_total, O, (C + 63) // 64))
+    return _launch_images(N, C, O, O if c_total is None else c_total, 2 * H * W * ((C + 63) // 64), ho * wo)
 
 
 def shortcut_fold_supported(a: PackedAct, w: PackedWeight, sc_channels: int, stride=1, padding=0, dilation=1,
@@ -1025,33 +1027,30 @@ def grad_supported(x_shape, w_shape, stride, padding, dilation) -> bool:
     return k == (1, 1) and _pair(stride) == (1, 1) and _pair(padding) == (0, 0)
 
 
-def grad_pack_weight(w_hat: torch.Tensor):
-    """``What = sign(Wc) * alpha`` ([O,C,k,k] fp32, k = 3 or 1) -> (sign fragments for the input-gradient kernel,
-    alpha[O])."""
-    w_hat = _require_cuda_f32(w_hat.detach(), "w_hat")
-    lib = native.require()
-    O, C, k = w_hat.shape[0], w_hat.shape[1], w_hat.shape[2]
-    with torch.cuda.device(w_hat.device):
-        packed = torch.empty(int(lib.bnn_hip_grad_weight_pack_bytes(O, C, k)), dtype=torch.uint8, device=w_hat.device)
-        alpha = torch.empty(O, dtype=torch.float32, device=w_hat.device)
-        native.check(lib.bnn_hip_grad_pack_weight_f32(w_hat.data_ptr(), O, C, k, packed.data_ptr(), alpha.data_ptr(),
-                                                      _stream(w_hat.device)), "bnn_hip_grad_pack_weight_f32")
-    return packed, alpha
-
-
-def xnor_grad_pack_weight(w: torch.Tensor, center: bool, compute_alpha: bool):
-    """``grad_pack_weight(xnor_what(w, center, compute_alpha))`` in one launch (``bnn_hip_xnor_grad_pack_weight_f32``): the
-    sign fragments and ``alpha[O]`` the input-gradient kernel reads, straight from the raw weight — the same bytes."""
-    w = _require_cuda_f32(w.detach(), "weight")
+def _grad_pack(w: torch.Tensor, what: str, symbol: str, *switches):
+    """The two packers of the input-gradient kernel's weight: ``[O,C,k,k]`` fp32 -> (sign fragments, alpha[O]) through the
+    entry point ``symbol(w, O, C, k, *switches, packed, alpha, stream)``."""
+    w = _require_cuda_f32(w.detach(), what)
     lib = native.require()
     O, C, k = w.shape[0], w.shape[1], w.shape[2]
     with torch.cuda.device(w.device):
         packed = torch.empty(int(lib.bnn_hip_grad_weight_pack_bytes(O, C, k)), dtype=torch.uint8, device=w.device)
         alpha = torch.empty(O, dtype=torch.float32, device=w.device)
-        native.check(lib.bnn_hip_xnor_grad_pack_weight_f32(w.data_ptr(), O, C, k, int(center), int(compute_alpha),
-                                                           packed.data_ptr(), alpha.data_ptr(), _stream(w.device)),
-                     "bnn_hip_xnor_grad_pack_weight_f32")
+        native.check(getattr(lib, symbol)(w.data_ptr(), O, C, k, *switches, packed.data_ptr(), alpha.data_ptr(),
+                                          _stream(w.device)), symbol)
     return packed, alpha
+
+
+def grad_pack_weight(w_hat: torch.Tensor):
+    """``What = sign(Wc) * alpha`` ([O,C,k,k] fp32, k = 3 or 1) -> (sign fragments for the input-gradient kernel,
+    alpha[O])."""
+    return _grad_pack(w_hat, "w_hat", "bnn_hip_grad_pack_weight_f32")
+
+
+def xnor_grad_pack_weight(w: torch.Tensor, center: bool, compute_alpha: bool):
+    """``grad_pack_weight(xnor_what(w, center, compute_alpha))`` in one launch (``bnn_hip_xnor_grad_pack_weight_f32``): the
+    sign fragments and ``alpha[O]`` the input-gradient kernel reads, straight from the raw weight — the same bytes."""
+    return _grad_pack(w, "weight", "bnn_hip_xnor_grad_pack_weight_f32", int(center), int(compute_alpha))
 
 
 @dataclass
@@ -1202,6 +1201,14 @@ def bn_act(x: torch.Tensor, bn_scale: torch.Tensor, bn_shift: torch.Tensor, relu
     return y
 
 
+def _bn_train_buffers(lib, x: torch.Tensor):
+    """What every training-BatchNorm entry point needs beside its tensors: two per-channel fp32 results (mean / invstd
+    going forward, dgamma / dbeta going back) and the workspace of ``bnn_hip_bn_train_workspace_bytes``."""
+    N, C, H, W = x.shape
+    return (torch.empty(C, dtype=torch.float32, device=x.device), torch.empty(C, dtype=torch.float32, device=x.device),
+            torch.empty(int(lib.bnn_hip_bn_train_workspace_bytes(N, C, H * W)), dtype=torch.uint8, device=x.device))
+
+
 def bn_train_forward(x: torch.Tensor, gamma, beta, running_mean, running_var, momentum: float, eps: float,
                      relu: bool = False, residual: Optional[torch.Tensor] = None):
     """``relu?(batch_norm(x, training=True) (+ residual))`` in three launches (csrc/bn_train.hip).  Updates the running
@@ -1218,9 +1225,7 @@ def bn_train_forward(x: torch.Tensor, gamma, beta, running_mean, running_var, mo
             raise native.NativeError("bnn_amd: residual shape differs from the BatchNorm input's")
     with torch.cuda.device(x.device):
         y = torch.empty_like(x)
-        mean = torch.empty(C, dtype=torch.float32, device=x.device)
-        invstd = torch.empty(C, dtype=torch.float32, device=x.device)
-        ws = torch.empty(int(lib.bnn_hip_bn_train_workspace_bytes(N, C, H * W)), dtype=torch.uint8, device=x.device)
+        mean, invstd, ws = _bn_train_buffers(lib, x)
         native.check(lib.bnn_hip_bn_train_forward_f32(
             x.data_ptr(), N, C, H * W, _ptr(gamma), _ptr(beta), _ptr(residual), int(bool(relu)), float(eps),
             float(momentum), _ptr(running_mean), _ptr(running_var), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
@@ -1238,9 +1243,7 @@ def bn_train_backward(gy: torch.Tensor, y: Optional[torch.Tensor], x: torch.Tens
     with torch.cuda.device(x.device):
         dx = torch.empty_like(x)
         dres = torch.empty_like(x) if want_dres else None
-        dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
-        dbeta = torch.empty(C, dtype=torch.float32, device=x.device)
-        ws = torch.empty(int(lib.bnn_hip_bn_train_workspace_bytes(N, C, H * W)), dtype=torch.uint8, device=x.device)
+        dgamma, dbeta, ws = _bn_train_buffers(lib, x)
         native.check(lib.bnn_hip_bn_train_backward_f32(
             gy.data_ptr(), _ptr(y), x.data_ptr(), mean.data_ptr(), invstd.data_ptr(), _ptr(gamma), N, C, H * W,
             dx.data_ptr(), _ptr(dres), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), _stream(x.device)),
@@ -1254,13 +1257,11 @@ def bn_relu_maxpool_train_forward(x: torch.Tensor, gamma, beta, running_mean, ru
     x = _require_cuda_f32(x, "BatchNorm input")
     lib = native.require()
     N, C, H, W = x.shape
-    hp, wp = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    hp, wp = _half_hw(H, W)
     with torch.cuda.device(x.device):
         p = torch.empty((N, C, hp, wp), dtype=torch.float32, device=x.device)
         code = torch.empty((N, C, hp, wp), dtype=torch.uint8, device=x.device)
-        mean = torch.empty(C, dtype=torch.float32, device=x.device)
-        invstd = torch.empty(C, dtype=torch.float32, device=x.device)
-        ws = torch.empty(int(lib.bnn_hip_bn_train_workspace_bytes(N, C, H * W)), dtype=torch.uint8, device=x.device)
+        mean, invstd, ws = _bn_train_buffers(lib, x)
         native.check(lib.bnn_hip_bn_relu_maxpool_train_forward_f32(
             x.data_ptr(), N, C, H, W, _ptr(gamma), _ptr(beta), float(eps), float(momentum), _ptr(running_mean),
             _ptr(running_var), p.data_ptr(), code.data_ptr(), mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(),
@@ -1276,9 +1277,7 @@ def bn_relu_maxpool_train_backward(gy: torch.Tensor, p: torch.Tensor, code: torc
     N, C, H, W = x.shape
     with torch.cuda.device(x.device):
         dx = torch.empty_like(x)
-        dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
-        dbeta = torch.empty(C, dtype=torch.float32, device=x.device)
-        ws = torch.empty(int(lib.bnn_hip_bn_train_workspace_bytes(N, C, H * W)), dtype=torch.uint8, device=x.device)
+        dgamma, dbeta, ws = _bn_train_buffers(lib, x)
         native.check(lib.bnn_hip_bn_relu_maxpool_train_backward_f32(
             gy.data_ptr(), p.data_ptr(), code.data_ptr(), x.data_ptr(), mean.data_ptr(), invstd.data_ptr(), _ptr(gamma),
             N, C, H, W, dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), _stream(x.device)),

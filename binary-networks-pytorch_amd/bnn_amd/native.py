@@ -28,30 +28,11 @@ ABI_VERSION = 15
 DTYPE_F32 = 0
 DTYPE_F16 = 1
 
-# every symbol include/bnn_hip.h declares (tests assert the .so exports all of them)
-EXPORTED_SYMBOLS = (
-    "bnn_hip_abi_version", "bnn_hip_status_string", "bnn_hip_launch_count", "bnn_hip_device_info",
-    "bnn_hip_act_words", "bnn_hip_weight_layout", "bnn_hip_pack_act_f32", "bnn_hip_bn_act_pack_f32",
-    "bnn_hip_avgpool_pack_f32", "bnn_hip_bn_relu_maxpool_pack_f32", "bnn_hip_stem7x7_bn_relu_pool_pack_f32",
-    "bnn_hip_pack_weight_f32", "bnn_hip_bconv2d",
-    "bnn_hip_bconv2d_fused", "bnn_hip_bconv2d_dot", "bnn_hip_blinear",
-    "bnn_hip_conv_workspace_bytes", "bnn_hip_bconv2d_f32", "bnn_hip_probe_int_alu", "bnn_hip_avgpool_fc_f32", "bnn_hip_sign_thresholds_f32", "bnn_hip_pack_act_f16", "bnn_hip_orpool_packed",
-    "bnn_hip_grad_weight_pack_bytes", "bnn_hip_grad_pack_weight_f32", "bnn_hip_bconv_grad_input_f32",
-    "bnn_hip_bconv_grad_weight_splits", "bnn_hip_bconv_grad_weight_f32",
-    "bnn_hip_bconv2d_direct", "bnn_hip_bconv2d_direct_plan", "bnn_hip_shortcut_fold_supported",
-    "bnn_hip_probe_clock", "bnn_hip_pack_act_ste_f32", "bnn_hip_bconv_grad_input_packed_f32",
-    "bnn_hip_bconv_grad_weight_packed_f32", "bnn_hip_bn_train_workspace_bytes", "bnn_hip_bn_train_forward_f32",
-    "bnn_hip_bn_train_backward_f32", "bnn_hip_bn_relu_maxpool_train_forward_f32",
-    "bnn_hip_bn_relu_maxpool_train_backward_f32", "bnn_hip_xnor_weight_forward_f32", "bnn_hip_xnor_weight_backward_f32",
-    "bnn_hip_bn_act_f32", "bnn_hip_avgpool_fc_workspace_bytes", "bnn_hip_avgpool_fc_ws_f32",
-    "bnn_hip_stem7x7_conv_f32", "bnn_hip_stem7x7_wgrad_workspace_bytes", "bnn_hip_stem7x7_wgrad_f32",
-    "bnn_hip_avgpool2x2_backward_f32", "bnn_hip_xnor_grad_pack_weight_f32",
-    "bnn_hip_hblock_supported", "bnn_hip_hblock_layout_of", "bnn_hip_hblock_pack_weights", "bnn_hip_hblock_forward",
-    "bnn_hip_avgpool2_bn_pack2_f32", "bnn_hip_hblock_pack_weights_cl", "bnn_hip_stem7x7_bn_relu_pool_pack_affine_f32",
-    "bnn_hip_hblock_pool_supported", "bnn_hip_hblock_pool_forward",
-    "bnn_hip_hblock_shortcut_supported", "bnn_hip_hblock_pack_shortcut_weights", "bnn_hip_hblock_shortcut_forward",
-    "bnn_hip_grouped_weight_layout", "bnn_hip_pack_weight_grouped_f32", "bnn_hip_bconv2d_grouped",
-)
+# status codes of include/bnn_hip.h that Python code compares against (anything else just goes through check())
+OK = 0
+ERR_INVALID_ARG = -1
+ERR_UNSUPPORTED = -2
+ERR_TOO_LARGE = -4
 
 
 class ConvDesc(ctypes.Structure):
@@ -129,91 +110,87 @@ _load_error: Optional[str] = None
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
+_f = ctypes.c_float
+_sz = ctypes.c_size_t
+_dp = ctypes.POINTER(ctypes.c_double)
+_conv_p = ctypes.POINTER(ConvDesc)
+_hblock_p = ctypes.POINTER(HBlockDesc)
+_wlayout_p = ctypes.POINTER(WLayout)
+
+# Every symbol include/bnn_hip.h declares: name -> (restype, argtypes).  load() resolves and declares from this table,
+# so a symbol cannot be exported without its prototype (an undeclared one would pass 64-bit pointers as C ints).
+_PROTOTYPES = {
+    "bnn_hip_abi_version": (_i, []),
+    "bnn_hip_status_string": (ctypes.c_char_p, [_i]),
+    "bnn_hip_launch_count": (ctypes.c_uint64, []),
+    "bnn_hip_device_info": (_i, [_i, ctypes.POINTER(DevInfo)]),
+    "bnn_hip_act_words": (_i, [_i]),
+    "bnn_hip_weight_layout": (_i, [_i, _i, _i, _i, _wlayout_p]),
+    "bnn_hip_grouped_weight_layout": (_i, [_i, _i, _i, _i, _i, _wlayout_p]),
+    "bnn_hip_pack_act_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "bnn_hip_pack_act_f16": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "bnn_hip_pack_act_ste_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "bnn_hip_bn_act_pack_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "bnn_hip_avgpool_pack_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "bnn_hip_avgpool2_bn_pack2_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "bnn_hip_orpool_packed": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "bnn_hip_bn_relu_maxpool_pack_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "bnn_hip_stem7x7_bn_relu_pool_pack_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "bnn_hip_stem7x7_bn_relu_pool_pack_affine_f32": (_i, [_vp] * 6 + [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "bnn_hip_stem7x7_conv_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "bnn_hip_stem7x7_wgrad_workspace_bytes": (_sz, [_i, _i, _i]),
+    "bnn_hip_stem7x7_wgrad_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "bnn_hip_avgpool2x2_backward_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "bnn_hip_avgpool_fc_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "bnn_hip_avgpool_fc_workspace_bytes": (_sz, [_i, _i]),
+    "bnn_hip_avgpool_fc_ws_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    "bnn_hip_pack_weight_f32": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "bnn_hip_pack_weight_grouped_f32": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "bnn_hip_sign_thresholds_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "bnn_hip_bconv2d": (_i, [_conv_p] + [_vp] * 9),
+    "bnn_hip_bconv2d_grouped": (_i, [_conv_p, _i] + [_vp] * 9),
+    "bnn_hip_bconv2d_fused": (_i, [_conv_p] + [_vp] * 4 + [ctypes.POINTER(Epilogue), _vp]),
+    "bnn_hip_shortcut_fold_supported": (_i, [_conv_p, _i]),
+    "bnn_hip_bconv2d_dot": (_i, [_conv_p] + [_vp] * 6),
+    "bnn_hip_blinear": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "bnn_hip_conv_workspace_bytes": (_sz, [_conv_p]),
+    "bnn_hip_bconv2d_f32": (_i, [_conv_p] + [_vp] * 9),
+    "bnn_hip_bconv2d_direct_plan": (_i, [_conv_p, ctypes.POINTER(FlyPlan)]),
+    "bnn_hip_bconv2d_direct": (_i, [_conv_p, _vp, _i] + [_vp] * 6 + [ctypes.POINTER(FlyPlan), _vp]),
+    "bnn_hip_grad_weight_pack_bytes": (_sz, [_i, _i, _i]),
+    "bnn_hip_grad_pack_weight_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "bnn_hip_xnor_grad_pack_weight_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "bnn_hip_bconv_grad_input_f32": (_i, [_vp] * 5 + [_i] * 7 + [_vp]),
+    "bnn_hip_bconv_grad_input_packed_f32": (_i, [_vp] * 5 + [_i] * 7 + [_vp]),
+    "bnn_hip_bconv_grad_weight_splits": (_i, [_i, _i, _i, _i]),
+    "bnn_hip_bconv_grad_weight_f32": (_i, [_vp] * 3 + [_i] * 8 + [_vp]),
+    "bnn_hip_bconv_grad_weight_packed_f32": (_i, [_vp] * 4 + [_i] * 8 + [_vp]),
+    "bnn_hip_xnor_weight_forward_f32": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "bnn_hip_xnor_weight_backward_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "bnn_hip_bn_act_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "bnn_hip_bn_train_workspace_bytes": (_sz, [_i, _i, _i]),
+    "bnn_hip_bn_train_forward_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _f, _f] + [_vp] * 7),
+    "bnn_hip_bn_train_backward_f32": (_i, [_vp] * 6 + [_i, _i, _i] + [_vp] * 6),
+    "bnn_hip_bn_relu_maxpool_train_forward_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _f, _f] + [_vp] * 8),
+    "bnn_hip_bn_relu_maxpool_train_backward_f32": (_i, [_vp] * 7 + [_i, _i, _i, _i] + [_vp] * 5),
+    "bnn_hip_hblock_supported": (_i, [_hblock_p]),
+    "bnn_hip_hblock_layout_of": (_i, [_i, _i, ctypes.POINTER(HBlockLayout)]),
+    "bnn_hip_hblock_pack_weights": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "bnn_hip_hblock_pack_weights_cl": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "bnn_hip_hblock_forward": (_i, [_hblock_p] + [_vp] * 7),
+    "bnn_hip_hblock_pool_supported": (_i, [_hblock_p]),
+    "bnn_hip_hblock_pool_forward": (_i, [_hblock_p] + [_vp] * 9),
+    "bnn_hip_hblock_shortcut_supported": (_i, [_hblock_p]),
+    "bnn_hip_hblock_pack_shortcut_weights": (_i, [_i, _i, _vp, _vp, _vp]),
+    "bnn_hip_hblock_shortcut_forward": (_i, [_hblock_p] + [_vp] * 10),
+    "bnn_hip_probe_int_alu": (_i, [_i, _i, _dp, _dp, _vp]),
+    "bnn_hip_probe_clock": (_i, [_i, _dp, _dp, _vp]),
+}
+EXPORTED_SYMBOLS = tuple(_PROTOTYPES)   # (tests assert the .so exports exactly these)
 
 
 def lib_path() -> str:
     return os.environ.get("BNN_AMD_LIB", DEFAULT_LIB_PATH)
-
-
-def _declare(lib: ctypes.CDLL) -> None:
-    lib.bnn_hip_abi_version.restype = _i
-    lib.bnn_hip_status_string.restype = ctypes.c_char_p
-    lib.bnn_hip_status_string.argtypes = [_i]
-    lib.bnn_hip_launch_count.restype = ctypes.c_uint64
-    lib.bnn_hip_device_info.argtypes = [_i, ctypes.POINTER(DevInfo)]
-    lib.bnn_hip_act_words.argtypes = [_i]
-    lib.bnn_hip_weight_layout.argtypes = [_i, _i, _i, _i, ctypes.POINTER(WLayout)]
-    lib.bnn_hip_pack_act_f32.argtypes = [_vp, _i, _i, _i, _i, _vp, _vp, _vp]
-    lib.bnn_hip_orpool_packed.argtypes = [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]
-    lib.bnn_hip_pack_act_f16.argtypes = [_vp, _i, _i, _i, _i, _vp, _vp, _vp]
-    lib.bnn_hip_avgpool_pack_f32.argtypes = [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]
-    lib.bnn_hip_bn_act_pack_f32.argtypes = [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]
-    lib.bnn_hip_stem7x7_bn_relu_pool_pack_f32.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]
-    lib.bnn_hip_bn_relu_maxpool_pack_f32.argtypes = [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i,
-                                                     _vp, _vp, _vp, _vp]
-    lib.bnn_hip_pack_weight_f32.argtypes = [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]
-    lib.bnn_hip_bconv2d.argtypes = [ctypes.POINTER(ConvDesc)] + [_vp] * 9
-    lib.bnn_hip_shortcut_fold_supported.argtypes = [ctypes.POINTER(ConvDesc), _i]
-    lib.bnn_hip_shortcut_fold_supported.restype = _i
-    lib.bnn_hip_bconv2d_fused.argtypes = [ctypes.POINTER(ConvDesc)] + [_vp] * 4 + \
-        [ctypes.POINTER(Epilogue), _vp]
-    lib.bnn_hip_bconv2d_dot.argtypes = [ctypes.POINTER(ConvDesc)] + [_vp] * 6
-    lib.bnn_hip_blinear.argtypes = [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]
-    lib.bnn_hip_conv_workspace_bytes.restype = ctypes.c_size_t
-    lib.bnn_hip_conv_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc)]
-    lib.bnn_hip_bconv2d_f32.argtypes = [ctypes.POINTER(ConvDesc)] + [_vp] * 9
-    lib.bnn_hip_bconv2d_direct_plan.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(FlyPlan)]
-    lib.bnn_hip_bconv2d_direct.argtypes = [ctypes.POINTER(ConvDesc), _vp, _i] + [_vp] * 6 + \
-        [ctypes.POINTER(FlyPlan), _vp]
-    lib.bnn_hip_stem7x7_bn_relu_pool_pack_affine_f32.argtypes = [_vp] * 6 + [_i, _i, _i, _i, _vp, _vp, _vp, _vp]
-    lib.bnn_hip_stem7x7_conv_f32.argtypes = [_vp, _vp, _i, _i, _i, _i, _vp, _vp]
-    lib.bnn_hip_avgpool_fc_f32.argtypes = [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]
-    lib.bnn_hip_stem7x7_wgrad_workspace_bytes.argtypes = [_i, _i, _i]
-    lib.bnn_hip_stem7x7_wgrad_workspace_bytes.restype = ctypes.c_size_t
-    lib.bnn_hip_stem7x7_wgrad_f32.argtypes = [_vp, _vp, _i, _i, _i, _vp, ctypes.c_size_t, _vp, _vp]
-    lib.bnn_hip_avgpool2x2_backward_f32.argtypes = [_vp, _i, _i, _i, _i, _vp, _vp]
-    lib.bnn_hip_xnor_grad_pack_weight_f32.argtypes = [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]
-    lib.bnn_hip_avgpool_fc_workspace_bytes.argtypes = [_i, _i]
-    lib.bnn_hip_avgpool_fc_workspace_bytes.restype = ctypes.c_size_t
-    lib.bnn_hip_avgpool_fc_ws_f32.argtypes = [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, ctypes.c_size_t, _vp]
-    lib.bnn_hip_sign_thresholds_f32.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]
-    lib.bnn_hip_grad_weight_pack_bytes.restype = ctypes.c_size_t
-    lib.bnn_hip_grad_weight_pack_bytes.argtypes = [_i, _i, _i]
-    lib.bnn_hip_grad_pack_weight_f32.argtypes = [_vp, _i, _i, _i, _vp, _vp, _vp]
-    lib.bnn_hip_bconv_grad_input_f32.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]
-    lib.bnn_hip_bconv_grad_weight_splits.argtypes = [_i, _i, _i, _i]
-    lib.bnn_hip_bconv_grad_weight_f32.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]
-    lib.bnn_hip_pack_act_ste_f32.argtypes = [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]
-    lib.bnn_hip_bconv_grad_input_packed_f32.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]
-    lib.bnn_hip_bconv_grad_weight_packed_f32.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]
-    lib.bnn_hip_bn_train_workspace_bytes.restype = ctypes.c_size_t
-    lib.bnn_hip_bn_train_workspace_bytes.argtypes = [_i, _i, _i]
-    _f = ctypes.c_float
-    lib.bnn_hip_bn_act_f32.argtypes = [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]
-    lib.bnn_hip_bn_act_f32.restype = _i
-    lib.bnn_hip_bn_train_forward_f32.argtypes = [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
-    lib.bnn_hip_bn_train_backward_f32.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]
-    lib.bnn_hip_bn_relu_maxpool_train_forward_f32.argtypes = [_vp, _i, _i, _i, _i, _vp, _vp, _f, _f] + [_vp] * 8
-    lib.bnn_hip_bn_relu_maxpool_train_backward_f32.argtypes = [_vp] * 7 + [_i, _i, _i, _i] + [_vp] * 5
-    lib.bnn_hip_xnor_weight_forward_f32.argtypes = [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]
-    lib.bnn_hip_xnor_weight_backward_f32.argtypes = [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]
-    lib.bnn_hip_probe_int_alu.argtypes = [_i, _i, ctypes.POINTER(ctypes.c_double),
-                                          ctypes.POINTER(ctypes.c_double), _vp]
-    lib.bnn_hip_probe_clock.argtypes = [_i, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _vp]
-    lib.bnn_hip_avgpool2_bn_pack2_f32.argtypes = [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]
-    lib.bnn_hip_hblock_supported.argtypes = [ctypes.POINTER(HBlockDesc)]
-    lib.bnn_hip_hblock_layout_of.argtypes = [_i, _i, ctypes.POINTER(HBlockLayout)]
-    lib.bnn_hip_hblock_pack_weights.argtypes = [_i, _i, _vp, _vp, _vp, _vp, _vp]
-    lib.bnn_hip_hblock_pack_weights_cl.argtypes = [_i, _i, _vp, _vp, _vp, _vp, _vp]
-    lib.bnn_hip_hblock_forward.argtypes = [ctypes.POINTER(HBlockDesc)] + [_vp] * 7
-    lib.bnn_hip_hblock_pool_supported.argtypes = [ctypes.POINTER(HBlockDesc)]
-    lib.bnn_hip_hblock_pool_forward.argtypes = [ctypes.POINTER(HBlockDesc)] + [_vp] * 9
-    lib.bnn_hip_hblock_shortcut_supported.argtypes = [ctypes.POINTER(HBlockDesc)]
-    lib.bnn_hip_hblock_pack_shortcut_weights.argtypes = [_i, _i, _vp, _vp, _vp]
-    lib.bnn_hip_hblock_shortcut_forward.argtypes = [ctypes.POINTER(HBlockDesc)] + [_vp] * 10
-    lib.bnn_hip_grouped_weight_layout.argtypes = [_i, _i, _i, _i, _i, ctypes.POINTER(WLayout)]
-    lib.bnn_hip_pack_weight_grouped_f32.argtypes = [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]
-    lib.bnn_hip_bconv2d_grouped.argtypes = [ctypes.POINTER(ConvDesc), _i] + [_vp] * 9
 
 
 def load() -> Optional[ctypes.CDLL]:
@@ -225,9 +202,9 @@ def load() -> Optional[ctypes.CDLL]:
         path = lib_path()
         try:
             lib = ctypes.CDLL(path)
-            for name in EXPORTED_SYMBOLS:
-                getattr(lib, name)
-            _declare(lib)
+            for name, (restype, argtypes) in _PROTOTYPES.items():
+                fn = getattr(lib, name)
+                fn.restype, fn.argtypes = restype, argtypes
             if lib.bnn_hip_abi_version() != ABI_VERSION:
                 raise OSError(f"ABI version mismatch: {lib.bnn_hip_abi_version()} != {ABI_VERSION}")
             _lib = lib
@@ -252,7 +229,7 @@ def require() -> ctypes.CDLL:
 
 
 def check(status: int, what: str) -> None:
-    if status != 0:
+    if status != OK:
         msg = require().bnn_hip_status_string(status).decode()
         raise NativeError(f"bnn_amd: {what} failed: {msg} (status {status})")
 

@@ -92,36 +92,41 @@ int check_desc(const bnn_hip_conv_desc* d, int* Ho, int* Wo) {
   return BNN_HIP_OK;
 }
 
+// Geometry part of a ConvP from a descriptor that passed check_desc (which proved the dense weight layout in range)
+// and the output extents it returned.  A caller that set no output-channel window (c_tot == 0) gets the whole output.
+void fill_geometry(const bnn_hip_conv_desc* d, int Ho, int Wo, bnn::ConvP* p) {
+  bnn_hip_wlayout L;
+  bnn_hip_weight_layout(d->O, d->C, d->KH, d->KW, &L);
+  p->N = d->N; p->H = d->H; p->Wd = d->W; p->Ho = Ho; p->Wo = Wo; p->O = d->O; p->C = d->C;
+  p->KH = d->KH; p->KW = d->KW; p->sh = d->stride_h; p->sw = d->stride_w;
+  p->ph = d->pad_h; p->pw = d->pad_w; p->dh = d->dil_h; p->dw = d->dil_w;
+  p->cw32 = L.cw32; p->cwc = L.cwc; p->nchunk = L.nchunk;
+  p->npix = d->N * Ho * Wo;
+  if (p->c_tot == 0) { p->c_off = 0; p->c_tot = d->O; }
+}
+
 // Shared tail of every conv entry point: fills the geometry part of `p` and launches.
 int run_conv(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const uint32_t* wbits,
              const uint32_t* wnz, bnn::ConvP p, void* stream) {
   int Ho = 0, Wo = 0;
   const int st = check_desc(d, &Ho, &Wo);
   if (st != BNN_HIP_OK) return st;
+  fill_geometry(d, Ho, Wo, &p);
   if (!P || !M || !wbits) return BNN_HIP_ERR_INVALID_ARG;
   if (!p.out && !(p.outP && p.outM)) return BNN_HIP_ERR_INVALID_ARG;
   if (!p.raw && !p.alpha) return BNN_HIP_ERR_INVALID_ARG;
   if ((p.bn_a == nullptr) != (p.bn_b == nullptr)) return BNN_HIP_ERR_INVALID_ARG;
   if ((p.outP == nullptr) != (p.outM == nullptr)) return BNN_HIP_ERR_INVALID_ARG;
   if ((p.pack_a == nullptr) != (p.pack_b == nullptr)) return BNN_HIP_ERR_INVALID_ARG;
-  if (p.c_tot == 0) { p.c_off = 0; p.c_tot = d->O; }
   if (p.c_off < 0 || p.c_tot <= 0 || (long long)p.c_off + d->O > p.c_tot) return BNN_HIP_ERR_INVALID_ARG;
   if (mulc(d->N, p.c_tot, Ho, Wo) > kMaxConvElems) return BNN_HIP_ERR_TOO_LARGE;
   if ((d->flags & BNN_HIP_FLAG_WEIGHT_ZEROS) && !wnz) return BNN_HIP_ERR_INVALID_ARG;
   if (!aligned(P, 16) || !aligned(M, 16) || !aligned(wbits, 16)) return BNN_HIP_ERR_INVALID_ARG;
   if (p.outP && (!aligned(p.outP, 8) || !aligned(p.outM, 8))) return BNN_HIP_ERR_INVALID_ARG;
-  bnn_hip_wlayout L;
-  bnn_hip_weight_layout(d->O, d->C, d->KH, d->KW, &L);
   p.P = reinterpret_cast<const uint32_t*>(P);
   p.M = reinterpret_cast<const uint32_t*>(M);
   p.W = wbits;
   p.Z = wnz;
-  p.N = d->N; p.H = d->H; p.Wd = d->W; p.Ho = Ho; p.Wo = Wo; p.O = d->O;
-  p.KH = d->KH; p.KW = d->KW; p.sh = d->stride_h; p.sw = d->stride_w;
-  p.ph = d->pad_h; p.pw = d->pad_w; p.dh = d->dil_h; p.dw = d->dil_w;
-  p.cw32 = L.cw32; p.cwc = L.cwc; p.nchunk = L.nchunk;
-  p.npix = d->N * Ho * Wo;
-  p.C = d->C;
   if (p.ds_P) {  // folded shortcut convolution (bnn_hip_epilogue sc_*)
     if (!p.ds_W || !p.ds_alpha || !p.ds_a || !p.ds_b || p.res || p.ds_C <= 0) return BNN_HIP_ERR_INVALID_ARG;
     if (!aligned(p.ds_P, 8) || !aligned(p.ds_W, 16)) return BNN_HIP_ERR_INVALID_ARG;
@@ -172,6 +177,60 @@ bnn::ConvP empty_convp() {
   return p;
 }
 
+// A weight layout of `words` 32-bit words per output channel and tap, read in chunks of `cwc` words (which divides it).
+int fill_layout(long long O, int KH, int KW, long long words, int cwc, bnn_hip_wlayout* out) {
+  const long long o_pad = (O + BNN_HIP_OCB - 1) / BNN_HIP_OCB * BNN_HIP_OCB, taps = mulc(KH, KW);
+  // the packed weight (one bit per weight) addresses words with 31-bit indices; taps and the padded channel count
+  // are ints of the layout struct
+  if (taps > 0x7fffffffLL || o_pad > 0x7fffffffLL || mulc(o_pad, taps, words) > kMaxElems) return BNN_HIP_ERR_TOO_LARGE;
+  out->cw32 = (int32_t)words;
+  out->cwc = cwc;
+  out->nchunk = out->cw32 / cwc;
+  out->taps = (int32_t)taps;
+  out->o_pad = (int32_t)o_pad;
+  out->reserved = 0;
+  out->n_words = o_pad * taps * words;
+  return BNN_HIP_OK;
+}
+
+// Entry contract of the plane-packing kernels (pack_act.hip, pack_ste.hip): fp32 or fp16 NCHW in (`x_align` = its
+// element size), 8-byte plane words out, pixels indexed in 32 bits, one grid row per 64-channel word.
+int check_pack(const void* x, size_t x_align, int N, int C, int H, int W, const uint64_t* P, const uint64_t* M) {
+  if (!x || !P || !M || N <= 0 || C <= 0 || H <= 0 || W <= 0) return BNN_HIP_ERR_INVALID_ARG;
+  if (mulc(N, H, W) > kMaxElems) return BNN_HIP_ERR_TOO_LARGE;
+  if (((long long)C + 63) / 64 > 65535) return BNN_HIP_ERR_UNSUPPORTED;  // grid.y limit
+  if (!aligned(P, 8) || !aligned(M, 8) || !aligned(x, x_align)) return BNN_HIP_ERR_INVALID_ARG;
+  return BNN_HIP_OK;
+}
+
+// Output extent of the stem's convolution (7x7 / 2 / 3) along one dimension; of its MaxPool 3 / 2 / 1 too: apply twice.
+inline long long stem_out(long long v) { return (v - 1) / 2 + 1; }
+// The stem kernels address x and out through 32-bit buffer descriptors (range-checked loads are the zero padding,
+// out-of-range stores are dropped): the input and the [N, 64, ho, wo] output of a launch stay below 2^32 - 512 bytes
+// (4 GiB: ~7100 images of 224 x 224 in, ~5300 out) — larger batches are split by the caller (hipops.stem7x7 does)
+bool stem_fits_descriptors(int N, int H, int W, long long ho, long long wo) {
+  return mulc(N, 12, H, W) <= kMaxDescBytes && mulc(N, 256, ho, wo) <= kMaxDescBytes;
+}
+// The stem's weight gradient indexes x and dy [N, 64, hc, wc] by element, in 31 bits.
+bool stem_wgrad_fits(int N, int H, int W) {
+  return mulc(N, 3, H, W) <= kMaxElems && mulc(N, 64, stem_out(H), stem_out(W)) <= kMaxElems;
+}
+
+// H * W of an image as the int the BatchNorm entry points take, or 0 (which they reject) when it does not fit one
+int checked_hw(int H, int W) { return (int)(mulc(H, W) > 0x7fffffffLL ? 0 : (long long)H * W); }
+
+// Workspace of the training BatchNorm entry points (csrc/bn_train.hip) for (N, C, HW) that passed check_bn, carved
+// from the caller's 8-byte aligned `base` when there is one: [C][splits][2] doubles of partial sums, rounded up to
+// 256 bytes, then 3 C floats of per-channel coefficients.
+struct BnWorkspace { int splits; size_t bytes; double* partial; float* work; };
+BnWorkspace bn_workspace(int N, int C, int HW, void* base) {
+  const int S = bnn::bn_train_splits(N, C, HW);
+  const size_t partial_bytes = align_up((size_t)C * S * 2 * sizeof(double), 256);
+  char* const b = static_cast<char*>(base);
+  return {S, partial_bytes + (size_t)3 * C * sizeof(float), reinterpret_cast<double*>(b),
+          b ? reinterpret_cast<float*>(b + partial_bytes) : nullptr};
+}
+
 }  // namespace
 
 extern "C" {
@@ -214,27 +273,14 @@ int bnn_hip_act_words(int C) { return C > 0 ? (int)(((long long)C + 63) / 64) : 
 
 int bnn_hip_weight_layout(int O, int C, int KH, int KW, bnn_hip_wlayout* out) {
   if (!out || O <= 0 || C <= 0 || KH <= 0 || KW <= 0) return BNN_HIP_ERR_INVALID_ARG;
-  const long long cw32 = 2 * (((long long)C + 63) / 64), o_pad = ((long long)O + BNN_HIP_OCB - 1) / BNN_HIP_OCB * BNN_HIP_OCB;
-  const long long taps = mulc(KH, KW);
-  // the packed weight (one bit per weight) addresses words with 31-bit indices; taps and the padded channel count
-  // are ints of the layout struct
-  if (taps > 0x7fffffffLL || o_pad > 0x7fffffffLL || mulc(o_pad, taps, cw32) > kMaxElems) return BNN_HIP_ERR_TOO_LARGE;
-  out->cw32 = (int32_t)cw32;
-  out->cwc = bnn::choose_cwc(out->cw32, KH, KW);
-  out->nchunk = out->cw32 / out->cwc;
-  out->taps = (int32_t)taps;
-  out->o_pad = (int32_t)o_pad;
-  out->reserved = 0;
-  out->n_words = o_pad * taps * cw32;
-  return BNN_HIP_OK;
+  const int cw32 = (int)(2 * (((long long)C + 63) / 64));
+  return fill_layout(O, KH, KW, cw32, bnn::choose_cwc(cw32, KH, KW), out);
 }
 
 int bnn_hip_pack_act_f32(const float* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M,
                          void* stream) {
-  if (!x || !P || !M || N <= 0 || C <= 0 || H <= 0 || W <= 0) return BNN_HIP_ERR_INVALID_ARG;
-  if (mulc(N, H, W) > kMaxElems) return BNN_HIP_ERR_TOO_LARGE;
-  if (((long long)C + 63) / 64 > 65535) return BNN_HIP_ERR_UNSUPPORTED;  // grid.y limit
-  if (!aligned(P, 8) || !aligned(M, 8) || !aligned(x, 4)) return BNN_HIP_ERR_INVALID_ARG;
+  const int st = check_pack(x, 4, N, C, H, W, P, M);
+  if (st != BNN_HIP_OK) return st;
   g_launches.fetch_add(1, std::memory_order_relaxed);
   BNN_RANGE();
   return bnn::launch_pack_act(x, N, C, H, W, P, M, static_cast<hipStream_t>(stream));
@@ -242,10 +288,8 @@ int bnn_hip_pack_act_f32(const float* x, int N, int C, int H, int W, uint64_t* P
 
 int bnn_hip_pack_act_f16(const void* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M,
                          void* stream) {
-  if (!x || !P || !M || N <= 0 || C <= 0 || H <= 0 || W <= 0) return BNN_HIP_ERR_INVALID_ARG;
-  if (mulc(N, H, W) > kMaxElems) return BNN_HIP_ERR_TOO_LARGE;
-  if (((long long)C + 63) / 64 > 65535) return BNN_HIP_ERR_UNSUPPORTED;  // grid.y limit
-  if (!aligned(P, 8) || !aligned(M, 8) || !aligned(x, 2)) return BNN_HIP_ERR_INVALID_ARG;
+  const int st = check_pack(x, 2, N, C, H, W, P, M);
+  if (st != BNN_HIP_OK) return st;
   g_launches.fetch_add(1, std::memory_order_relaxed);
   BNN_RANGE();
   return bnn::launch_pack_act_f16(x, N, C, H, W, P, M, static_cast<hipStream_t>(stream));
@@ -253,11 +297,9 @@ int bnn_hip_pack_act_f16(const void* x, int N, int C, int H, int W, uint64_t* P,
 
 int bnn_hip_bn_act_pack_f32(const float* x, int N, int C, int H, int W, const float* bn_scale,
                             const float* bn_shift, int relu, uint64_t* P, uint64_t* M, void* stream) {
-  if (!x || !P || !M || N <= 0 || C <= 0 || H <= 0 || W <= 0) return BNN_HIP_ERR_INVALID_ARG;
   if ((bn_scale == nullptr) != (bn_shift == nullptr)) return BNN_HIP_ERR_INVALID_ARG;
-  if (mulc(N, H, W) > kMaxElems) return BNN_HIP_ERR_TOO_LARGE;
-  if (((long long)C + 63) / 64 > 65535) return BNN_HIP_ERR_UNSUPPORTED;  // grid.y limit
-  if (!aligned(P, 8) || !aligned(M, 8) || !aligned(x, 4)) return BNN_HIP_ERR_INVALID_ARG;
+  const int st = check_pack(x, 4, N, C, H, W, P, M);
+  if (st != BNN_HIP_OK) return st;
   g_launches.fetch_add(1, std::memory_order_relaxed);
   BNN_RANGE();
   return bnn::launch_bn_act_pack(x, N, C, H, W, bn_scale, bn_shift, relu, P, M,
@@ -329,14 +371,7 @@ int bnn_hip_stem7x7_bn_relu_pool_pack_f32(const float* x, const float* w, const 
   if ((flags & BNN_HIP_STEM_EXACT_FP32) && (flags & BNN_HIP_STEM_FP16)) return BNN_HIP_ERR_INVALID_ARG;
   if ((P == nullptr) != (M == nullptr)) return BNN_HIP_ERR_INVALID_ARG;
   if (P && (!aligned(P, 8) || !aligned(M, 8))) return BNN_HIP_ERR_INVALID_ARG;
-  // the stem kernels address x and out through 32-bit buffer descriptors (range-checked loads are the zero padding,
-  // out-of-range stores are dropped): every tensor of a launch stays below 2^32 - 16 bytes (4 GiB: ~7100 images of
-  // 224 x 224 in, ~5300 out) — larger batches are split by the caller (hipops.stem7x7 does)
-  {
-    const long long hc = (H - 1) / 2 + 1, wc = (W - 1) / 2 + 1, hp = (hc - 1) / 2 + 1, wp = (wc - 1) / 2 + 1;
-    if (mulc(N, 12, H, W) > kMaxDescBytes || mulc(N, 256, hp, wp) > kMaxDescBytes)
-      return BNN_HIP_ERR_TOO_LARGE;
-  }
+  if (!stem_fits_descriptors(N, H, W, stem_out(stem_out(H)), stem_out(stem_out(W)))) return BNN_HIP_ERR_TOO_LARGE;
   g_launches.fetch_add(1, std::memory_order_relaxed);
   BNN_RANGE();
   return bnn::launch_stem(x, w, bn_scale, bn_shift, N, H, W, flags, out_f32, P, M,
@@ -351,10 +386,7 @@ int bnn_hip_stem7x7_bn_relu_pool_pack_affine_f32(const float* x, const float* w,
     return BNN_HIP_ERR_INVALID_ARG;
   if (flags & ~BNN_HIP_STEM_FP16) return BNN_HIP_ERR_INVALID_ARG;   // (the exact-fp32 stem has no such variant)
   if (!aligned(P, 8) || !aligned(M, 8)) return BNN_HIP_ERR_INVALID_ARG;
-  {
-    const long long hc = (H - 1) / 2 + 1, wc = (W - 1) / 2 + 1, hp = (hc - 1) / 2 + 1, wp = (wc - 1) / 2 + 1;
-    if (mulc(N, 12, H, W) > kMaxDescBytes || mulc(N, 256, hp, wp) > kMaxDescBytes) return BNN_HIP_ERR_TOO_LARGE;
-  }
+  if (!stem_fits_descriptors(N, H, W, stem_out(stem_out(H)), stem_out(stem_out(W)))) return BNN_HIP_ERR_TOO_LARGE;
   g_launches.fetch_add(1, std::memory_order_relaxed);
   BNN_RANGE();
   return bnn::launch_stem_rows_aff(x, w, bn_scale, bn_shift, pack_scale, pack_shift, N, H, W, (flags & BNN_HIP_STEM_FP16) != 0,
@@ -366,10 +398,7 @@ int bnn_hip_stem7x7_conv_f32(const float* x, const float* w, int N, int H, int W
   if (!x || !w || !out || N <= 0 || H <= 0 || W <= 0) return BNN_HIP_ERR_INVALID_ARG;
   if (flags & ~BNN_HIP_STEM_FP16) return BNN_HIP_ERR_INVALID_ARG;
   if (!aligned(x, 4) || !aligned(w, 4) || !aligned(out, 4)) return BNN_HIP_ERR_INVALID_ARG;
-  {  // 32-bit buffer descriptors, as in the fused stem: input and the [N, 64, Hc, Wc] output below 2^32 - 512 bytes
-    const long long hc = (H - 1) / 2 + 1, wc = (W - 1) / 2 + 1;
-    if (mulc(N, 12, H, W) > kMaxDescBytes || mulc(N, 256, hc, wc) > kMaxDescBytes) return BNN_HIP_ERR_TOO_LARGE;
-  }
+  if (!stem_fits_descriptors(N, H, W, stem_out(H), stem_out(W))) return BNN_HIP_ERR_TOO_LARGE;   // (no pooling here)
   g_launches.fetch_add(1, std::memory_order_relaxed);
   BNN_RANGE();
   return bnn::launch_stem_conv(x, w, N, H, W, (flags & BNN_HIP_STEM_FP16) != 0, out, static_cast<hipStream_t>(stream));
@@ -385,9 +414,7 @@ int bnn_hip_avgpool2x2_backward_f32(const float* gy, int N, int C, int Ho, int W
 }
 
 size_t bnn_hip_stem7x7_wgrad_workspace_bytes(int N, int H, int W) {
-  if (N <= 0 || H <= 0 || W <= 0) return 0;
-  const long long hc = (H - 1) / 2 + 1, wc = (W - 1) / 2 + 1;
-  if (mulc(N, 3, H, W) > kMaxElems || mulc(N, 64, hc, wc) > kMaxElems) return 0;
+  if (N <= 0 || H <= 0 || W <= 0 || !stem_wgrad_fits(N, H, W)) return 0;
   return bnn::stem_wgrad_workspace_bytes(N, H, W);
 }
 
@@ -395,10 +422,7 @@ int bnn_hip_stem7x7_wgrad_f32(const float* x, const float* dy, int N, int H, int
                               size_t workspace_bytes, float* dw, void* stream) {
   if (!x || !dy || !dw || !workspace || N <= 0 || H <= 0 || W <= 0) return BNN_HIP_ERR_INVALID_ARG;
   if (!aligned(x, 4) || !aligned(dy, 4) || !aligned(dw, 4) || !aligned(workspace, 4)) return BNN_HIP_ERR_INVALID_ARG;
-  {
-    const long long hc = (H - 1) / 2 + 1, wc = (W - 1) / 2 + 1;
-    if (mulc(N, 3, H, W) > kMaxElems || mulc(N, 64, hc, wc) > kMaxElems) return BNN_HIP_ERR_TOO_LARGE;
-  }
+  if (!stem_wgrad_fits(N, H, W)) return BNN_HIP_ERR_TOO_LARGE;
   if (!bnn::stem_wgrad_supported(H, W)) return BNN_HIP_ERR_UNSUPPORTED;
   if (workspace_bytes < bnn::stem_wgrad_workspace_bytes(N, H, W)) return BNN_HIP_ERR_INVALID_ARG;
   g_launches.fetch_add(2, std::memory_order_relaxed);
@@ -406,11 +430,18 @@ int bnn_hip_stem7x7_wgrad_f32(const float* x, const float* dy, int N, int H, int
   return bnn::launch_stem_wgrad(x, dy, N, H, W, workspace, dw, static_cast<hipStream_t>(stream));
 }
 
-int bnn_hip_avgpool_fc_f32(const float* x, int N, int C, int HW, const float* w_t, const float* bias, int O,
-                           float* out, void* stream) {
+// What both forms of the head (avgpool + fc, csrc/tail.hip) ask of x [N, C, HW], w_t [C, O] and out [N, O].
+static int check_head(const float* x, int N, int C, int HW, const float* w_t, int O, const float* out) {
   if (!x || !w_t || !out || N <= 0 || C <= 0 || HW <= 0 || O <= 0) return BNN_HIP_ERR_INVALID_ARG;
   if (!aligned(x, 4) || !aligned(w_t, 4) || !aligned(out, 4)) return BNN_HIP_ERR_INVALID_ARG;
   if (mulc(N, C, HW) > 4 * kMaxElems || mulc(N, O) > kMaxElems) return BNN_HIP_ERR_TOO_LARGE;
+  return BNN_HIP_OK;
+}
+
+int bnn_hip_avgpool_fc_f32(const float* x, int N, int C, int HW, const float* w_t, const float* bias, int O,
+                           float* out, void* stream) {
+  const int st = check_head(x, N, C, HW, w_t, O, out);
+  if (st != BNN_HIP_OK) return st;
   g_launches.fetch_add(1, std::memory_order_relaxed);
   BNN_RANGE();
   return bnn::launch_avgpool_fc(x, w_t, bias, out, N, C, HW, O, static_cast<hipStream_t>(stream));
@@ -423,18 +454,14 @@ size_t bnn_hip_avgpool_fc_workspace_bytes(int N, int C) {
 
 int bnn_hip_avgpool_fc_ws_f32(const float* x, int N, int C, int HW, const float* w_t, const float* bias, int O,
                               float* out, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!x || !w_t || !out || N <= 0 || C <= 0 || HW <= 0 || O <= 0) return BNN_HIP_ERR_INVALID_ARG;
-  if (!aligned(x, 4) || !aligned(w_t, 4) || !aligned(out, 4)) return BNN_HIP_ERR_INVALID_ARG;
-  if (mulc(N, C, HW) > 4 * kMaxElems || mulc(N, O) > kMaxElems) return BNN_HIP_ERR_TOO_LARGE;
-  if (!bnn::avgpool_fc_ws_supported(C, HW)) {  // the one-kernel form needs no workspace
-    g_launches.fetch_add(1, std::memory_order_relaxed);
-    BNN_RANGE();
-    return bnn::launch_avgpool_fc(x, w_t, bias, out, N, C, HW, O, static_cast<hipStream_t>(stream));
-  }
-  if (!workspace || !aligned(workspace, 16) || workspace_bytes < bnn::avgpool_fc_workspace_bytes(N, C))
+  const int st = check_head(x, N, C, HW, w_t, O, out);
+  if (st != BNN_HIP_OK) return st;
+  const bool two = bnn::avgpool_fc_ws_supported(C, HW);  // else the one-kernel form, which needs no workspace
+  if (two && (!workspace || !aligned(workspace, 16) || workspace_bytes < bnn::avgpool_fc_workspace_bytes(N, C)))
     return BNN_HIP_ERR_INVALID_ARG;
-  g_launches.fetch_add(2, std::memory_order_relaxed);
+  g_launches.fetch_add(two ? 2 : 1, std::memory_order_relaxed);
   BNN_RANGE();
+  if (!two) return bnn::launch_avgpool_fc(x, w_t, bias, out, N, C, HW, O, static_cast<hipStream_t>(stream));
   return bnn::launch_avgpool_fc_ws(x, w_t, bias, out, static_cast<float*>(workspace), N, C, HW, O,
                                    static_cast<hipStream_t>(stream));
 }
@@ -488,10 +515,10 @@ int bnn_hip_bconv_grad_input_packed_f32(const float* g, const float* alpha, cons
 
 int bnn_hip_pack_act_ste_f32(const float* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M, uint64_t* T,
                              void* stream) {
-  if (!x || !P || !M || !T || N <= 0 || C <= 0 || H <= 0 || W <= 0) return BNN_HIP_ERR_INVALID_ARG;
-  if (mulc(N, H, W) > kMaxElems) return BNN_HIP_ERR_TOO_LARGE;
-  if (((long long)C + 63) / 64 > 65535) return BNN_HIP_ERR_UNSUPPORTED;  // grid.y limit
-  if (!aligned(P, 8) || !aligned(M, 8) || !aligned(T, 8) || !aligned(x, 4)) return BNN_HIP_ERR_INVALID_ARG;
+  if (!T) return BNN_HIP_ERR_INVALID_ARG;
+  const int st = check_pack(x, 4, N, C, H, W, P, M);
+  if (st != BNN_HIP_OK) return st;
+  if (!aligned(T, 8)) return BNN_HIP_ERR_INVALID_ARG;
   g_launches.fetch_add(1, std::memory_order_relaxed);
   BNN_RANGE();
   return bnn::launch_pack_ste(x, N, C, H, W, P, M, T, static_cast<hipStream_t>(stream));
@@ -548,19 +575,8 @@ int bnn_hip_bconv2d(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_
 int bnn_hip_grouped_weight_layout(int O, int C, int groups, int KH, int KW, bnn_hip_wlayout* out) {
   if (!out || O <= 0 || C <= 0 || groups <= 0 || KH <= 0 || KW <= 0) return BNN_HIP_ERR_INVALID_ARG;
   if (C % groups != 0 || O % groups != 0) return BNN_HIP_ERR_INVALID_ARG;
-  const long long o_pad = ((long long)O + BNN_HIP_OCB - 1) / BNN_HIP_OCB * BNN_HIP_OCB;
-  const long long taps = mulc(KH, KW);
-  if (taps > 0x7fffffffLL || o_pad > 0x7fffffffLL || mulc(o_pad, taps) > kMaxElems) return BNN_HIP_ERR_TOO_LARGE;
-  const long long S = grouped_words_per_tap(O, C, groups);
-  if (mulc(o_pad, taps, S) > kMaxElems) return BNN_HIP_ERR_TOO_LARGE;
-  out->cw32 = (int32_t)S;
-  out->cwc = (int32_t)S;
-  out->nchunk = 1;
-  out->taps = (int32_t)taps;
-  out->o_pad = (int32_t)o_pad;
-  out->reserved = 0;
-  out->n_words = o_pad * taps * S;
-  return BNN_HIP_OK;
+  const long long S = grouped_words_per_tap(O, C, groups);   // (at most C / 32 + 2: an int)
+  return fill_layout(O, KH, KW, S, (int)S, out);               // one chunk: the grouped kernel walks its window
 }
 
 int bnn_hip_pack_weight_grouped_f32(const float* w, int O, int Cg, int groups, int KH, int KW, int center,
@@ -590,8 +606,7 @@ int bnn_hip_bconv2d_grouped(const bnn_hip_conv_desc* d, int groups, const uint64
   if (!alpha && (bias || post_scale)) return BNN_HIP_ERR_INVALID_ARG;  // raw dot: no epilogue constants
   if (!aligned(P, 16) || !aligned(M, 16) || !aligned(wbits, 16) || !aligned(wnz, 16) || !aligned(out, 4))
     return BNN_HIP_ERR_INVALID_ARG;
-  bnn_hip_wlayout L, G;
-  bnn_hip_weight_layout(d->O, d->C, d->KH, d->KW, &L);  // the activation words per pixel (cw32); check_desc: in range
+  bnn_hip_wlayout G;
   const int sg = bnn_hip_grouped_weight_layout(d->O, d->C, groups, d->KH, d->KW, &G);
   if (sg != BNN_HIP_OK) return sg;
   bnn::ConvP p = empty_convp();
@@ -600,13 +615,8 @@ int bnn_hip_bconv2d_grouped(const bnn_hip_conv_desc* d, int groups, const uint64
   p.M = reinterpret_cast<const uint32_t*>(M);
   p.W = wbits;
   p.Z = wnz;
-  p.N = d->N; p.H = d->H; p.Wd = d->W; p.Ho = Ho; p.Wo = Wo; p.O = d->O;
-  p.KH = d->KH; p.KW = d->KW; p.sh = d->stride_h; p.sw = d->stride_w;
-  p.ph = d->pad_h; p.pw = d->pad_w; p.dh = d->dil_h; p.dw = d->dil_w;
-  p.cw32 = L.cw32; p.cwc = L.cw32; p.nchunk = 1;  // (one chunk: the grouped kernel walks its window, not chunks)
-  p.npix = d->N * Ho * Wo;
-  p.C = d->C;
-  p.c_off = 0; p.c_tot = d->O;
+  fill_geometry(d, Ho, Wo, &p);         // cw32: the activation words per pixel, as for a dense weight
+  p.cwc = p.cw32; p.nchunk = 1;         // (one chunk: the grouped kernel walks its window, not chunks)
   g_launches.fetch_add(1, std::memory_order_relaxed);
   Range range(p.raw ? "bnn_hip_bconv2d_grouped_dot" : "bnn_hip_bconv2d_grouped");
   return bnn::launch_bconv_grouped(p, groups, G.cw32, static_cast<hipStream_t>(stream));
@@ -646,14 +656,7 @@ int bnn_hip_shortcut_fold_supported(const bnn_hip_conv_desc* d, int sc_C) {
   int Ho = 0, Wo = 0;
   if (check_desc(d, &Ho, &Wo) != BNN_HIP_OK) return 0;
   bnn::ConvP p = empty_convp();
-  bnn_hip_wlayout L;
-  bnn_hip_weight_layout(d->O, d->C, d->KH, d->KW, &L);
-  p.N = d->N; p.H = d->H; p.Wd = d->W; p.Ho = Ho; p.Wo = Wo; p.O = d->O; p.C = d->C;
-  p.KH = d->KH; p.KW = d->KW; p.sh = d->stride_h; p.sw = d->stride_w;
-  p.ph = d->pad_h; p.pw = d->pad_w; p.dh = d->dil_h; p.dw = d->dil_w;
-  p.cw32 = L.cw32; p.cwc = L.cwc; p.nchunk = L.nchunk;
-  p.npix = d->N * Ho * Wo;
-  p.c_off = 0; p.c_tot = d->O;
+  fill_geometry(d, Ho, Wo, &p);
   // the epilogue the fold belongs to: BatchNorm + shortcut + ReLU -> fp32 + sign planes (any non-null pointers)
   const float* f = reinterpret_cast<const float*>(&p);
   p.alpha = f; p.bn_a = f; p.bn_b = f; p.relu = true; p.out = &p;
@@ -702,16 +705,8 @@ static int fly_convp(const bnn_hip_conv_desc* d, bnn::ConvP* out) {
   // tensor within a few elements of 2^32 bytes would bring the marker in range.  UNSUPPORTED, not TOO_LARGE: the
   // two-launch form (pack_act + conv) of the same layer has no such limit and callers fall back to it
   if (mulc(d->N, d->C, d->H, d->W) * 4 > kMaxDescBytes) return BNN_HIP_ERR_UNSUPPORTED;
-  bnn::ConvP p = empty_convp();
-  bnn_hip_wlayout L;
-  bnn_hip_weight_layout(d->O, d->C, d->KH, d->KW, &L);
-  p.N = d->N; p.H = d->H; p.Wd = d->W; p.Ho = Ho; p.Wo = Wo; p.O = d->O; p.C = d->C;
-  p.KH = d->KH; p.KW = d->KW; p.sh = d->stride_h; p.sw = d->stride_w;
-  p.ph = d->pad_h; p.pw = d->pad_w; p.dh = d->dil_h; p.dw = d->dil_w;
-  p.cw32 = L.cw32; p.cwc = L.cwc; p.nchunk = L.nchunk;
-  p.npix = d->N * Ho * Wo;
-  p.c_off = 0; p.c_tot = d->O;
-  *out = p;
+  *out = empty_convp();
+  fill_geometry(d, Ho, Wo, out);
   return BNN_HIP_OK;
 }
 
@@ -745,12 +740,17 @@ static bool direct_applies(const bnn_hip_conv_desc* d) {
   return fly_convp(d, &p) == BNN_HIP_OK && bnn::fly_supported(p);
 }
 
+// Workspace of the two-launch form of bnn_hip_bconv2d_f32: the P plane, then the M plane, each rounded up to 256 bytes.
+static size_t conv_plane_bytes(const bnn_hip_conv_desc* d) {
+  const size_t npix = (size_t)d->N * d->H * d->W;
+  return align_up(npix * ((d->C + 63) / 64) * sizeof(uint64_t), 256);
+}
+
 size_t bnn_hip_conv_workspace_bytes(const bnn_hip_conv_desc* d) {
   int Ho = 0, Wo = 0;
   if (check_desc(d, &Ho, &Wo) != BNN_HIP_OK) return 0;   // (bnn_hip_bconv2d_f32 rejects such a descriptor itself)
   if (direct_applies(d)) return 0;
-  const size_t npix = (size_t)d->N * d->H * d->W;
-  return 2 * align_up(npix * ((d->C + 63) / 64) * sizeof(uint64_t), 256);
+  return 2 * conv_plane_bytes(d);
 }
 
 int bnn_hip_bconv2d_f32(const bnn_hip_conv_desc* d, const float* x, const uint32_t* wbits,
@@ -763,11 +763,9 @@ int bnn_hip_bconv2d_f32(const bnn_hip_conv_desc* d, const float* x, const uint32
   int Ho, Wo;
   int st = check_desc(d, &Ho, &Wo);
   if (st != BNN_HIP_OK) return st;
-  const size_t npix = (size_t)d->N * d->H * d->W;
-  const size_t plane = align_up(npix * ((d->C + 63) / 64) * sizeof(uint64_t), 256);
   char* ws = static_cast<char*>(workspace);
   uint64_t* P = reinterpret_cast<uint64_t*>(ws);
-  uint64_t* M = reinterpret_cast<uint64_t*>(ws + plane);
+  uint64_t* M = reinterpret_cast<uint64_t*>(ws + conv_plane_bytes(d));
   st = bnn_hip_pack_act_f32(x, d->N, d->C, d->H, d->W, P, M, stream);
   if (st != BNN_HIP_OK) return st;
   return bnn_hip_bconv2d(d, P, M, wbits, wnz, alpha, bias, post_scale, out, stream);
@@ -824,9 +822,7 @@ static int check_bn(int N, int C, int HW) {
 }
 
 size_t bnn_hip_bn_train_workspace_bytes(int N, int C, int HW) {
-  if (check_bn(N, C, HW) != BNN_HIP_OK) return 0;
-  // [C][splits][2] doubles of partial sums + 3 C floats of per-channel coefficients
-  return align_up((size_t)C * bnn::bn_train_splits(N, C, HW) * 2 * sizeof(double), 256) + (size_t)3 * C * sizeof(float);
+  return check_bn(N, C, HW) == BNN_HIP_OK ? bn_workspace(N, C, HW, nullptr).bytes : 0;
 }
 
 int bnn_hip_bn_train_forward_f32(const float* x, int N, int C, int HW, const float* gamma, const float* beta,
@@ -839,15 +835,13 @@ int bnn_hip_bn_train_forward_f32(const float* x, int N, int C, int HW, const flo
   if ((running_mean == nullptr) != (running_var == nullptr) || !(eps >= 0.0f)) return BNN_HIP_ERR_INVALID_ARG;
   if (!aligned(x, 4) || !aligned(y, 4) || (residual && !aligned(residual, 4)) || !aligned(workspace, 8))
     return BNN_HIP_ERR_INVALID_ARG;
-  const int S = bnn::bn_train_splits(N, C, HW);
-  double* partial = static_cast<double*>(workspace);
-  float* work = reinterpret_cast<float*>(static_cast<char*>(workspace) + align_up((size_t)C * S * 2 * sizeof(double), 256));
+  const BnWorkspace ws = bn_workspace(N, C, HW, workspace);
   g_launches.fetch_add(3, std::memory_order_relaxed);
   BNN_RANGE();
-  const int st2 = bnn::launch_bn_stats(x, N, C, HW, S, partial, static_cast<hipStream_t>(stream));
+  const int st2 = bnn::launch_bn_stats(x, N, C, HW, ws.splits, ws.partial, static_cast<hipStream_t>(stream));
   if (st2 != BNN_HIP_OK) return st2;
-  return bnn::launch_bn_apply(x, partial, S, gamma, beta, residual, relu, y, N, C, HW, eps, momentum, running_mean,
-                              running_var, save_mean, save_invstd, work, static_cast<hipStream_t>(stream));
+  return bnn::launch_bn_apply(x, ws.partial, ws.splits, gamma, beta, residual, relu, y, N, C, HW, eps, momentum, running_mean,
+                              running_var, save_mean, save_invstd, ws.work, static_cast<hipStream_t>(stream));
 }
 
 int bnn_hip_bn_act_f32(const float* x, int N, int C, int HW, const float* scale, const float* shift, const float* residual,
@@ -871,16 +865,14 @@ int bnn_hip_bn_train_backward_f32(const float* gy, const float* y, const float* 
   if (!aligned(gy, 4) || !aligned(x, 4) || !aligned(dx, 4) || (y && !aligned(y, 4)) || (dres && !aligned(dres, 4)) ||
       !aligned(workspace, 8))
     return BNN_HIP_ERR_INVALID_ARG;
-  const int S = bnn::bn_train_splits(N, C, HW);
-  double* partial = static_cast<double*>(workspace);
-  float* work = reinterpret_cast<float*>(static_cast<char*>(workspace) + align_up((size_t)C * S * 2 * sizeof(double), 256));
+  const BnWorkspace ws = bn_workspace(N, C, HW, workspace);
   g_launches.fetch_add(3, std::memory_order_relaxed);
   BNN_RANGE();
-  const int st2 = bnn::launch_bn_bwd_reduce(gy, y, x, save_mean, save_invstd, N, C, HW, S, partial,
+  const int st2 = bnn::launch_bn_bwd_reduce(gy, y, x, save_mean, save_invstd, N, C, HW, ws.splits, ws.partial,
                                             static_cast<hipStream_t>(stream));
   if (st2 != BNN_HIP_OK) return st2;
-  return bnn::launch_bn_bwd_dx(gy, y, x, save_mean, save_invstd, gamma, partial, S, dx, dres, dgamma, dbeta, N, C, HW, work,
-                               static_cast<hipStream_t>(stream));
+  return bnn::launch_bn_bwd_dx(gy, y, x, save_mean, save_invstd, gamma, ws.partial, ws.splits, dx, dres, dgamma, dbeta, N, C,
+                               HW, ws.work, static_cast<hipStream_t>(stream));
 }
 
 int bnn_hip_bn_relu_maxpool_train_forward_f32(const float* x, int N, int C, int H, int W, const float* gamma,
@@ -888,19 +880,19 @@ int bnn_hip_bn_relu_maxpool_train_forward_f32(const float* x, int N, int C, int 
                                               float* running_var, float* pooled, uint8_t* code, float* save_mean,
                                               float* save_invstd, void* workspace, void* stream) {
   if (!x || !pooled || !code || !save_mean || !save_invstd || !workspace || H <= 0 || W <= 0) return BNN_HIP_ERR_INVALID_ARG;
-  const int st = check_bn(N, C, (int)(mulc(H, W) > 0x7fffffffLL ? 0 : (long long)H * W));
+  const int HW = checked_hw(H, W);
+  const int st = check_bn(N, C, HW);
   if (st != BNN_HIP_OK) return st;
   if ((running_mean == nullptr) != (running_var == nullptr) || !(eps >= 0.0f)) return BNN_HIP_ERR_INVALID_ARG;
   if (!aligned(x, 4) || !aligned(pooled, 4) || !aligned(workspace, 8)) return BNN_HIP_ERR_INVALID_ARG;
-  const int HW = H * W, S = bnn::bn_train_splits(N, C, HW);
-  double* partial = static_cast<double*>(workspace);
-  float* work = reinterpret_cast<float*>(static_cast<char*>(workspace) + align_up((size_t)C * S * 2 * sizeof(double), 256));
+  const BnWorkspace ws = bn_workspace(N, C, HW, workspace);
   g_launches.fetch_add(3, std::memory_order_relaxed);
   BNN_RANGE();
-  const int st2 = bnn::launch_bn_stats(x, N, C, HW, S, partial, static_cast<hipStream_t>(stream));
+  const int st2 = bnn::launch_bn_stats(x, N, C, HW, ws.splits, ws.partial, static_cast<hipStream_t>(stream));
   if (st2 != BNN_HIP_OK) return st2;
-  return bnn::launch_bn_relu_pool_fwd(x, partial, S, gamma, beta, pooled, code, N, C, H, W, eps, momentum, running_mean,
-                                      running_var, save_mean, save_invstd, work, static_cast<hipStream_t>(stream));
+  return bnn::launch_bn_relu_pool_fwd(x, ws.partial, ws.splits, gamma, beta, pooled, code, N, C, H, W, eps, momentum,
+                                      running_mean, running_var, save_mean, save_invstd, ws.work,
+                                      static_cast<hipStream_t>(stream));
 }
 
 int bnn_hip_bn_relu_maxpool_train_backward_f32(const float* gy, const float* pooled, const uint8_t* code, const float* x,
@@ -909,17 +901,16 @@ int bnn_hip_bn_relu_maxpool_train_backward_f32(const float* gy, const float* poo
                                                void* workspace, void* stream) {
   if (!gy || !pooled || !code || !x || !save_mean || !save_invstd || !dx || !workspace || H <= 0 || W <= 0)
     return BNN_HIP_ERR_INVALID_ARG;
-  const int st = check_bn(N, C, (int)(mulc(H, W) > 0x7fffffffLL ? 0 : (long long)H * W));
+  const int HW = checked_hw(H, W);
+  const int st = check_bn(N, C, HW);
   if (st != BNN_HIP_OK) return st;
   if (!aligned(gy, 4) || !aligned(pooled, 4) || !aligned(x, 4) || !aligned(dx, 4) || !aligned(workspace, 8))
     return BNN_HIP_ERR_INVALID_ARG;
-  const int HW = H * W, S = bnn::bn_train_splits(N, C, HW);
-  double* partial = static_cast<double*>(workspace);
-  float* work = reinterpret_cast<float*>(static_cast<char*>(workspace) + align_up((size_t)C * S * 2 * sizeof(double), 256));
+  const BnWorkspace ws = bn_workspace(N, C, HW, workspace);
   g_launches.fetch_add(3, std::memory_order_relaxed);
   BNN_RANGE();
-  return bnn::launch_bn_relu_pool_bwd(gy, pooled, code, x, save_mean, save_invstd, gamma, N, C, H, W, S, partial, work, dx,
-                                      dgamma, dbeta, static_cast<hipStream_t>(stream));
+  return bnn::launch_bn_relu_pool_bwd(gy, pooled, code, x, save_mean, save_invstd, gamma, N, C, H, W, ws.splits, ws.partial,
+                                      ws.work, dx, dgamma, dbeta, static_cast<hipStream_t>(stream));
 }
 
 // ---- the hierarchical block in one launch (csrc/hblock.hip) ----
@@ -936,10 +927,29 @@ static int check_hblock(const bnn_hip_hblock_desc* d) {
   return BNN_HIP_OK;
 }
 
+// Whether the form of a kernel the descriptor selects (channel lanes: lanes = output channels, else pixels) covers it.
+using hblock_rule = bool (*)(const bnn_hip_hblock_desc*);
+static bool hblock_form_supported(const bnn_hip_hblock_desc* d, hblock_rule channel_lanes, hblock_rule pixel_lanes) {
+  return (d->flags & BNN_HIP_HBLOCK_CHANNEL_LANES) ? channel_lanes(d) : pixel_lanes(d);
+}
+// the channel-lane kernels move two pixels per access of an fp32 tensor on 14-wide rows
+static bool hblock_fp32_aligned(const bnn_hip_hblock_desc* d, const float* t) {
+  return !(d->flags & BNN_HIP_HBLOCK_CHANNEL_LANES) || d->W != 14 || aligned(t, 8);
+}
+// the operands every forward entry point takes: input planes, the dense weights, the constants buffer
+static bool hblock_operands_ok(const uint64_t* in_P, const uint32_t* weights, const float* consts) {
+  return in_P && weights && consts && aligned(in_P, 8) && aligned(weights, 64) && aligned(consts, 32);
+}
+// bnn_hip_hblock_pack_weights and _pack_weights_cl: the three standard packs in, one 64-byte aligned buffer out
+static int check_hblock_pack(int C_in, int planes, const uint32_t* const w[3], const uint32_t* weights) {
+  if (!w[0] || !w[1] || !w[2] || !weights || C_in <= 0 || planes <= 0) return BNN_HIP_ERR_INVALID_ARG;
+  if (!aligned(w[0], 4) || !aligned(w[1], 4) || !aligned(w[2], 4) || !aligned(weights, 64)) return BNN_HIP_ERR_INVALID_ARG;
+  return BNN_HIP_OK;
+}
+
 int bnn_hip_hblock_supported(const bnn_hip_hblock_desc* d) {
   if (check_hblock(d) != BNN_HIP_OK) return 0;
-  if (d->flags & BNN_HIP_HBLOCK_CHANNEL_LANES) return bnn::hblock_cl_supported(d) ? 1 : 0;
-  return bnn::hblock_supported(d) ? 1 : 0;
+  return hblock_form_supported(d, bnn::hblock_cl_supported, bnn::hblock_supported) ? 1 : 0;
 }
 
 int bnn_hip_hblock_layout_of(int C_in, int planes, bnn_hip_hblock_layout* out) {
@@ -950,9 +960,9 @@ int bnn_hip_hblock_layout_of(int C_in, int planes, bnn_hip_hblock_layout* out) {
 
 int bnn_hip_hblock_pack_weights(int C_in, int planes, const uint32_t* wbits1, const uint32_t* wbits2,
                                 const uint32_t* wbits3, uint32_t* weights, void* stream) {
-  if (!wbits1 || !wbits2 || !wbits3 || !weights || C_in <= 0 || planes <= 0) return BNN_HIP_ERR_INVALID_ARG;
-  if (!aligned(wbits1, 4) || !aligned(wbits2, 4) || !aligned(wbits3, 4) || !aligned(weights, 64)) return BNN_HIP_ERR_INVALID_ARG;
   const uint32_t* const w[3] = {wbits1, wbits2, wbits3};
+  const int st = check_hblock_pack(C_in, planes, w, weights);
+  if (st != BNN_HIP_OK) return st;
   g_launches.fetch_add(3, std::memory_order_relaxed);
   BNN_RANGE();
   return bnn::launch_hblock_pack_weights(C_in, planes, w, weights, static_cast<hipStream_t>(stream));
@@ -960,9 +970,9 @@ int bnn_hip_hblock_pack_weights(int C_in, int planes, const uint32_t* wbits1, co
 
 int bnn_hip_hblock_pack_weights_cl(int C_in, int planes, const uint32_t* wbits1, const uint32_t* wbits2,
                                    const uint32_t* wbits3, uint32_t* weights, void* stream) {
-  if (!wbits1 || !wbits2 || !wbits3 || !weights || C_in <= 0 || planes <= 0) return BNN_HIP_ERR_INVALID_ARG;
-  if (!aligned(wbits1, 4) || !aligned(wbits2, 4) || !aligned(wbits3, 4) || !aligned(weights, 64)) return BNN_HIP_ERR_INVALID_ARG;
   const uint32_t* const w[3] = {wbits1, wbits2, wbits3};
+  const int st = check_hblock_pack(C_in, planes, w, weights);
+  if (st != BNN_HIP_OK) return st;
   g_launches.fetch_add(3, std::memory_order_relaxed);
   BNN_RANGE();
   return bnn::launch_hblock_cl_pack_weights(C_in, planes, w, weights, static_cast<hipStream_t>(stream));
@@ -972,21 +982,15 @@ int bnn_hip_hblock_forward(const bnn_hip_hblock_desc* d, const uint64_t* in_P, c
                            const float* consts, const float* residual, float* out, uint64_t* out_P, void* stream) {
   const int st = check_hblock(d);
   if (st != BNN_HIP_OK) return st;
-  if (!in_P || !weights || !consts || !residual || !out || residual == out) return BNN_HIP_ERR_INVALID_ARG;
-  if (!aligned(in_P, 8) || !aligned(weights, 64) || !aligned(consts, 32) || !aligned(residual, 4) || !aligned(out, 4) ||
-      (out_P && !aligned(out_P, 8)))
-    return BNN_HIP_ERR_INVALID_ARG;
-  if (d->flags & BNN_HIP_HBLOCK_CHANNEL_LANES) {
-    if (!bnn::hblock_cl_supported(d)) return BNN_HIP_ERR_UNSUPPORTED;
-    if (d->W == 14 && (!aligned(residual, 8) || !aligned(out, 8))) return BNN_HIP_ERR_INVALID_ARG;   // two pixels per access
-    g_launches.fetch_add(1, std::memory_order_relaxed);
-    Range range("bnn_hip_hblock_forward(channel lanes)");
-    return bnn::launch_hblock_cl(d, in_P, weights, consts, residual, out, out_P, static_cast<hipStream_t>(stream));
-  }
-  if (!bnn::hblock_supported(d)) return BNN_HIP_ERR_UNSUPPORTED;
+  if (!hblock_operands_ok(in_P, weights, consts) || !residual || !out || residual == out) return BNN_HIP_ERR_INVALID_ARG;
+  if (!aligned(residual, 4) || !aligned(out, 4) || (out_P && !aligned(out_P, 8))) return BNN_HIP_ERR_INVALID_ARG;
+  if (!hblock_form_supported(d, bnn::hblock_cl_supported, bnn::hblock_supported)) return BNN_HIP_ERR_UNSUPPORTED;
+  if (!hblock_fp32_aligned(d, residual) || !hblock_fp32_aligned(d, out)) return BNN_HIP_ERR_INVALID_ARG;
+  const bool cl = (d->flags & BNN_HIP_HBLOCK_CHANNEL_LANES) != 0;
   g_launches.fetch_add(1, std::memory_order_relaxed);
-  BNN_RANGE();
-  return bnn::launch_hblock(d, in_P, weights, consts, residual, out, out_P, static_cast<hipStream_t>(stream));
+  Range range(cl ? "bnn_hip_hblock_forward(channel lanes)" : __func__);
+  return (cl ? bnn::launch_hblock_cl : bnn::launch_hblock)(d, in_P, weights, consts, residual, out, out_P,
+                                                           static_cast<hipStream_t>(stream));
 }
 
 int bnn_hip_hblock_pool_supported(const bnn_hip_hblock_desc* d) {
@@ -1000,9 +1004,9 @@ int bnn_hip_hblock_pool_forward(const bnn_hip_hblock_desc* d, const uint64_t* in
   const int st = check_hblock(d);
   if (st != BNN_HIP_OK) return st;
   if (d->flags & BNN_HIP_HBLOCK_CHANNEL_LANES) return BNN_HIP_ERR_INVALID_ARG;
-  if (!in_P || !weights || !consts || !pool_consts || !residual || !out_P1 || !out_P2 || !out_M2) return BNN_HIP_ERR_INVALID_ARG;
-  if (!aligned(in_P, 8) || !aligned(weights, 64) || !aligned(consts, 32) || !aligned(pool_consts, 32) || !aligned(residual, 4) ||
-      !aligned(out_P1, 8) || !aligned(out_P2, 8) || !aligned(out_M2, 8))
+  if (!hblock_operands_ok(in_P, weights, consts) || !pool_consts || !residual || !out_P1 || !out_P2 || !out_M2)
+    return BNN_HIP_ERR_INVALID_ARG;
+  if (!aligned(pool_consts, 32) || !aligned(residual, 4) || !aligned(out_P1, 8) || !aligned(out_P2, 8) || !aligned(out_M2, 8))
     return BNN_HIP_ERR_INVALID_ARG;
   if (!bnn::hblock_pool_supported(d)) return BNN_HIP_ERR_UNSUPPORTED;
   g_launches.fetch_add(1, std::memory_order_relaxed);
@@ -1013,8 +1017,7 @@ int bnn_hip_hblock_pool_forward(const bnn_hip_hblock_desc* d, const uint64_t* in
 
 int bnn_hip_hblock_shortcut_supported(const bnn_hip_hblock_desc* d) {
   if (check_hblock(d) != BNN_HIP_OK) return 0;
-  if (d->flags & BNN_HIP_HBLOCK_CHANNEL_LANES) return bnn::hblock_cl_ds_supported(d) ? 1 : 0;
-  return bnn::hblock_ds_supported(d) ? 1 : 0;
+  return hblock_form_supported(d, bnn::hblock_cl_ds_supported, bnn::hblock_ds_supported) ? 1 : 0;
 }
 
 int bnn_hip_hblock_pack_shortcut_weights(int C_in, int planes, const uint32_t* wbits, uint32_t* weights, void* stream) {
@@ -1031,23 +1034,18 @@ int bnn_hip_hblock_shortcut_forward(const bnn_hip_hblock_desc* d, const uint64_t
                                     void* stream) {
   const int st = check_hblock(d);
   if (st != BNN_HIP_OK) return st;
-  if (!in_P || !weights || !consts || !sc_P || !sc_M || !sc_weights || !sc_alpha || !out || !out_P) return BNN_HIP_ERR_INVALID_ARG;
-  if (!aligned(in_P, 8) || !aligned(weights, 64) || !aligned(consts, 32) || !aligned(sc_P, 8) || !aligned(sc_M, 8) ||
-      !aligned(sc_weights, 32) || !aligned(sc_alpha, 32) || !aligned(out, 4) || !aligned(out_P, 8))
+  if (!hblock_operands_ok(in_P, weights, consts) || !sc_P || !sc_M || !sc_weights || !sc_alpha || !out || !out_P)
     return BNN_HIP_ERR_INVALID_ARG;
-  if (d->flags & BNN_HIP_HBLOCK_CHANNEL_LANES) {   // (weights: those of bnn_hip_hblock_pack_weights_cl)
-    if (!bnn::hblock_cl_ds_supported(d)) return BNN_HIP_ERR_UNSUPPORTED;
-    if (d->W == 14 && !aligned(out, 8)) return BNN_HIP_ERR_INVALID_ARG;              // two pixels per store
-    g_launches.fetch_add(1, std::memory_order_relaxed);
-    Range range("bnn_hip_hblock_shortcut_forward(channel lanes)");
-    return bnn::launch_hblock_cl_ds(d, in_P, weights, consts, sc_P, sc_M, sc_weights, sc_alpha, out, out_P,
-                                    static_cast<hipStream_t>(stream));
-  }
-  if (!bnn::hblock_ds_supported(d)) return BNN_HIP_ERR_UNSUPPORTED;
+  if (!aligned(sc_P, 8) || !aligned(sc_M, 8) || !aligned(sc_weights, 32) || !aligned(sc_alpha, 32) || !aligned(out, 4) ||
+      !aligned(out_P, 8))
+    return BNN_HIP_ERR_INVALID_ARG;
+  if (!hblock_form_supported(d, bnn::hblock_cl_ds_supported, bnn::hblock_ds_supported)) return BNN_HIP_ERR_UNSUPPORTED;
+  if (!hblock_fp32_aligned(d, out)) return BNN_HIP_ERR_INVALID_ARG;
+  const bool cl = (d->flags & BNN_HIP_HBLOCK_CHANNEL_LANES) != 0;   // (weights: then those of bnn_hip_hblock_pack_weights_cl)
   g_launches.fetch_add(1, std::memory_order_relaxed);
-  BNN_RANGE();
-  return bnn::launch_hblock_ds(d, in_P, weights, consts, sc_P, sc_M, sc_weights, sc_alpha, out, out_P,
-                               static_cast<hipStream_t>(stream));
+  Range range(cl ? "bnn_hip_hblock_shortcut_forward(channel lanes)" : __func__);
+  return (cl ? bnn::launch_hblock_cl_ds : bnn::launch_hblock_ds)(d, in_P, weights, consts, sc_P, sc_M, sc_weights, sc_alpha,
+                                                                 out, out_P, static_cast<hipStream_t>(stream));
 }
 
 int bnn_hip_probe_clock(int spin_iters, double* shader_mhz, double* elapsed_us, void* stream) {

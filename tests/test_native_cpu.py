@@ -26,6 +26,11 @@ def test_library_exports_every_declared_symbol():
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/bnn_hip.h but not exported"
     assert set(native.EXPORTED_SYMBOLS) == set(syms)
+    # every exported symbol carries its prototype on the loaded library (an undeclared one passes pointers as C ints)
+    loaded, text = native.require(), open(os.path.join(ROOT, "include", "bnn_hip.h")).read()
+    for s in native.EXPORTED_SYMBOLS:
+        if not re.search(r"\b%s\s*\(\s*void\s*\)" % s, text):
+            assert getattr(loaded, s).argtypes, f"{s} takes arguments but has no argtypes"
 
 
 def test_legacy_kernels_live_in_their_own_test_only_library():

@@ -432,6 +432,7 @@ int main(int argc, char** argv) {
   const long iters = argc > 1 ? std::atol(argv[1]) : 200000;
   if (argc > 2) g_rng ^= (uint64_t)std::atoll(argv[2]) * 0xD1342543DE82EF95ull + 1;
   void* stream = nullptr;
+  uint64_t digest = 0xCBF29CE484222325ull;
   for (long it = 0; it < iters; ++it) {
     ++g_calls;
     int st = 0;
@@ -619,7 +620,9 @@ int main(int argc, char** argv) {
         break; }
     }
     if (!status_ok(st)) { std::fprintf(stderr, "unknown status %d\n", st); return 2; }
+    digest = (digest ^ (uint64_t)(uint32_t)st) * 0x100000001B3ull;   // FNV-1a over the statuses, in call order
   }
-  std::printf("CAPI_FUZZ_OK calls=%llu reached_launchers=%llu\n", g_calls, g_reached);
+  std::printf("CAPI_FUZZ_OK calls=%llu reached_launchers=%llu status_digest=%016" PRIx64 " launches=%" PRIu64 "\n", g_calls,
+              g_reached, digest, bnn_hip_launch_count());
   return g_reached > g_calls / 200 ? 0 : 3;     // the fuzz must actually get past the validators often enough
 }
