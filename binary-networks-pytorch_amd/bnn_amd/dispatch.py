@@ -1,6 +1,6 @@
 """What ``model(x)`` and ``block(x)`` dispatch to by themselves — the drop-in tiers: ``AutoFusion`` (whole model:
 the fused executor, as eager launches / stem launch + HIP graph / two halves in flight), ``BlockFusion`` (one residual
-block), and ``install_auto_fusion`` (the same dispatch for ResNets of other packages, from ``prepare_binary_model``).
+block), ``OpFusion`` (one BATS cell operation), and ``install_auto_fusion`` (the same dispatch for ResNets of other packages, from ``prepare_binary_model``).
 Reference call being served: ``outputs = net(inputs)`` (examples/cifar10.py:71,140-149)."""
 from __future__ import annotations
 
@@ -18,6 +18,7 @@ import torch.nn as nn
 
 from . import fastpath, native
 from . import tails as _tails
+from .cellops import FusedCellOp
 from .executor import FusedBlocks, FusedResNet, FusionError, is_native_model, resnet_shaped, tap_binary_inputs
 from .pipeline import TwoHalves
 from .models.resnet import ResNet
@@ -107,6 +108,70 @@ def auto_block_forward(block: nn.Module, x: torch.Tensor) -> Optional[torch.Tens
     if st is None:
         st = block.__dict__["_bnn_auto_block"] = BlockFusion()
     return st.run(block, x)
+
+
+class OpFusion:
+    """``BlockFusion`` for the BATS cell operations of ``bnn_amd.models`` (``SepConv``, ``DilConv``, ``ReLUConvBN``): an
+    operation called for inference on a HIP device evaluates itself as ``FusedCellOp(op)`` — ``bn_act_pack`` and one
+    convolution launch with PReLU, channel shuffle and skip in its epilogue, 2 launches and 3 fp32 passes over HBM
+    instead of 6 launches and about 11 passes.  Same conditions as ``BlockFusion``; one instance per operation in
+    ``op.__dict__['_bnn_auto_op']``."""
+
+    def __init__(self) -> None:
+        self.engine = None
+        self.failed_sig = None
+        self.calls = {"fused": 0, "declined": 0}
+        self.lock = threading.Lock()
+
+    def __deepcopy__(self, memo):
+        return OpFusion()
+
+    def __reduce__(self):
+        return (OpFusion, ())
+
+    def run(self, op: nn.Module, x: torch.Tensor) -> Optional[torch.Tensor]:
+        if (op.training or torch.is_grad_enabled() or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4
+                or x.shape[0] == 0 or getattr(op, "_is_replica", False) or _tails._PER_LAYER
+                or os.environ.get("BNN_AMD_AUTOFUSE", "1") == "0" or fastpath.strict_weights() or not native.available()):
+            self.calls["declined"] += 1
+            return None
+        with self.lock:
+            eng = self.engine
+            # (inside a caller's own graph capture nothing may be built or re-derived, as in BlockFusion.run)
+            if torch.cuda.is_current_stream_capturing() and (eng is None or not eng._unchanged()):
+                self.calls["declined"] += 1
+                return None
+            if eng is None:
+                sig = _param_signature(op)
+                if self.failed_sig == sig:
+                    self.calls["declined"] += 1
+                    return None
+                try:
+                    eng = self.engine = FusedCellOp(op)
+                except FusionError:
+                    self.failed_sig = sig
+                    self.calls["declined"] += 1
+                    return None
+            if AutoFusion._hooked(op) or next(op.parameters()).device != x.device:
+                self.calls["declined"] += 1
+                return None
+        try:
+            y = eng(x)
+        except FusionError:
+            with self.lock:
+                self.engine, self.failed_sig = None, _param_signature(op)
+            self.calls["declined"] += 1
+            return None
+        self.calls["fused"] += 1
+        return y
+
+
+def auto_op_forward(op: nn.Module, x: torch.Tensor) -> Optional[torch.Tensor]:
+    """Called at the top of the cell operations' ``forward``: the fused result, or None -> its own forward."""
+    st = op.__dict__.get("_bnn_auto_op")
+    if st is None:
+        st = op.__dict__["_bnn_auto_op"] = OpFusion()
+    return st.run(op, x)
 
 
 class AutoFusion:

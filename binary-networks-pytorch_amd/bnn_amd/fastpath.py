@@ -14,7 +14,8 @@ A layer takes the HIP path when ALL of the following hold (otherwise the torch c
   ``bnn_amd/training.py``), ``Conv1d``/``Linear`` fall back to the composition
 * ``padding_mode == 'zeros'``, numeric padding, and either ``groups == 1`` or — ``Conv2d`` / ``Conv1d`` under inference
   only — ``groups > 1`` (grouped and depthwise layers: ``pack_act`` + ``bnn_hip_bconv2d_grouped``, two launches; the
-  training forward and the fused executors keep declining them)
+  training forward and the ResNet executors keep declining them; inside a BATS cell operation of ``bnn_amd.models``
+  the layer runs as part of ``cellops.FusedCellOp``)
 
 When those hold and ``libbnn_hip.so`` cannot be loaded the call raises ``NativeError``: there is
 no CPU or eager stand-in for the GPU path.
@@ -38,7 +39,7 @@ import torch.nn as nn
 from . import hipops, native
 
 _stats_lock = threading.Lock()
-_stats = {"conv2d": 0, "conv1d": 0, "linear": 0, "weight_packs": 0, "conv2d_train": 0}
+_stats = {"conv2d": 0, "conv1d": 0, "linear": 0, "weight_packs": 0, "conv2d_train": 0, "cell_op": 0}
 
 
 def stats() -> dict:
@@ -255,6 +256,7 @@ def invalidate(module: nn.Module, executors: bool = True) -> int:
         m.__dict__.pop("_bnn_packed_replicas", None)
         if executors:       # a residual block's own fused executor (dispatch.BlockFusion); an executor that re-derives
             m.__dict__.pop("_bnn_auto_block", None)     # ITSELF (refresh) passes False: it may be that very object
+            m.__dict__.pop("_bnn_auto_op", None)        # a cell operation's executor (dispatch.OpFusion)
     from .tails import drop_derived                 # folded BatchNorms / transposed head weights of the per-layer tails
     drop_derived(module)
     return n

@@ -615,6 +615,49 @@ def bconv2d_grouped(a: PackedAct, w: PackedWeight, bias: Optional[torch.Tensor] 
     return out
 
 
+def bconv2d_grouped_fused(a: PackedAct, w: PackedWeight, bias: Optional[torch.Tensor] = None,
+                          post_scale: Optional[torch.Tensor] = None, stride=1, padding=0, dilation=1, *,
+                          prelu: Optional[torch.Tensor] = None, shuffle_groups: int = 1,
+                          residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``bconv2d_grouped`` with the rest of a BATS cell operation in the same launch
+    (``bnn_hip_bconv2d_grouped_fused``): per-channel PReLU, ``channel_shuffle(., shuffle_groups)`` as the store index
+    and the skip connection ``residual + .`` (fp32 ``[N, O, Ho, Wo]``) -> fp32 NCHW.  With none of the three it returns
+    the bits of ``bconv2d_grouped``."""
+    if not w.windowed:
+        raise native.NativeError("bnn_amd: bconv2d_grouped_fused reads the layout of pack_weight_grouped, not of "
+                                 "pack_weight")
+    lib = native.require()
+    N, C, H, W = a.shape
+    O, Cg, KH, KW = w.shape
+    if Cg * w.groups != C:
+        raise native.NativeError(f"bnn_amd: grouped weight reads {Cg} x {w.groups} channels, the input has {C}")
+    shuffle_groups = int(shuffle_groups)
+    if shuffle_groups < 1 or O % shuffle_groups:
+        raise native.NativeError(f"bnn_amd: shuffle_groups={shuffle_groups} does not divide the {O} output channels")
+    d = _desc(a.shape, (O, C, KH, KW), stride, padding, dilation, 0)
+    ho, wo = conv_out_hw(H, W, KH, KW, stride, padding, dilation)
+    dev = a.P.device
+    bias = _per_channel(bias, O, "bias")
+    post_scale = _per_channel(post_scale, O, "post_scale")
+    prelu = _per_channel(prelu, O, "prelu")
+    if residual is not None:
+        residual = _require_cuda_f32(residual, "residual")
+        if tuple(residual.shape) != (N, O, ho, wo):
+            raise native.NativeError(f"bnn_amd: residual shape {tuple(residual.shape)} != output")
+    with torch.cuda.device(dev):
+        out = torch.empty((N, O, ho, wo), dtype=torch.float32, device=dev)
+        if N == 0:
+            return out
+        step = fused_launch_images(N, C, H, W, O, (KH, KW), stride, padding, dilation)
+        for n0, n1, dd in _desc_slices(d, step):
+            native.check(lib.bnn_hip_bconv2d_grouped_fused(
+                ctypes.byref(dd), w.groups, a.P[n0:n1].data_ptr(), a.M[n0:n1].data_ptr(), w.wbits.data_ptr(),
+                w.wnz.data_ptr(), w.alpha.data_ptr(), _ptr(bias), _ptr(post_scale), _ptr(prelu), shuffle_groups,
+                None if residual is None else residual[n0:n1].data_ptr(), out[n0:n1].data_ptr(), _stream(dev)),
+                "bnn_hip_bconv2d_grouped_fused")
+    return out
+
+
 def direct_plan(x_shape, w: PackedWeight, stride=1, padding=0, dilation=1) -> Optional[native.FlyPlan]:
     """The band plan ``bconv2d_direct`` would use for this geometry, or None where the one-launch layer does not
     apply (include/bnn_hip.h: bnn_hip_bconv2d_direct_plan)."""

@@ -149,6 +149,7 @@ _PROTOTYPES = {
     "bnn_hip_sign_thresholds_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "bnn_hip_bconv2d": (_i, [_conv_p] + [_vp] * 9),
     "bnn_hip_bconv2d_grouped": (_i, [_conv_p, _i] + [_vp] * 9),
+    "bnn_hip_bconv2d_grouped_fused": (_i, [_conv_p, _i] + [_vp] * 8 + [_i] + [_vp] * 3),
     "bnn_hip_bconv2d_fused": (_i, [_conv_p] + [_vp] * 4 + [ctypes.POINTER(Epilogue), _vp]),
     "bnn_hip_shortcut_fold_supported": (_i, [_conv_p, _i]),
     "bnn_hip_bconv2d_dot": (_i, [_conv_p] + [_vp] * 6),

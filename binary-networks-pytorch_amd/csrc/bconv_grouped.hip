@@ -34,16 +34,13 @@ __device__ __forceinline__ uint32_t disagree_nz(uint32_t n, uint32_t w, uint32_t
 #endif
 }
 
+// The integer part of one wave: the dot products of its 64 pixels with the 32 output channels of block `ob`.
 // FAST: 24-bit index multiplies (decode_pixel<true>), when small_indices() holds.
 template <bool FAST>
-__global__ __launch_bounds__(64) void bconv_grouped_kernel(
-    const uint32_t* __restrict__ P, const uint32_t* __restrict__ M, const uint32_t* __restrict__ W,
-    const uint32_t* __restrict__ Z, BNN_EPI_PARAMS, const Geo g, const int Cg, const int Og, const int S) {
-  BNN_EPI_INIT;
-  // 1-D grid, block-major: consecutive workgroups walk the pixel tiles of one 32-channel block (the same weight words)
-  const int ob = (int)(blockIdx.x / (unsigned)g.tiles);
-  const int tile = (int)blockIdx.x - ob * g.tiles;
-  const Pix px = decode_pixel<FAST>(g, tile * kWave + threadIdx.x);
+__device__ __forceinline__ void grouped_dots(const uint32_t* __restrict__ P, const uint32_t* __restrict__ M,
+                                             const uint32_t* __restrict__ W, const uint32_t* __restrict__ Z,
+                                             const Geo& g, const Pix& px, const int ob, const int Cg, const int Og,
+                                             const int S, int (&dotv)[kOCB]) {
   const int taps = g.KH * g.KW;
   const int w_lo = (ob * kOCB) / Og * Cg / 32;
   const int nw = min(S, g.cw32 - w_lo);  // window words that exist in the planes (the rest has Z == 0): never >= cw32
@@ -80,9 +77,21 @@ __global__ __launch_bounds__(64) void bconv_grouped_kernel(
       });
     }
   }
-  int dotv[kOCB];
 #pragma unroll
   for (int j = 0; j < kOCB; ++j) dotv[j] = nzc[j] - 2 * dis[j];
+}
+
+template <bool FAST>
+__global__ __launch_bounds__(64) void bconv_grouped_kernel(
+    const uint32_t* __restrict__ P, const uint32_t* __restrict__ M, const uint32_t* __restrict__ W,
+    const uint32_t* __restrict__ Z, BNN_EPI_PARAMS, const Geo g, const int Cg, const int Og, const int S) {
+  BNN_EPI_INIT;
+  // 1-D grid, block-major: consecutive workgroups walk the pixel tiles of one 32-channel block (the same weight words)
+  const int ob = (int)(blockIdx.x / (unsigned)g.tiles);
+  const int tile = (int)blockIdx.x - ob * g.tiles;
+  const Pix px = decode_pixel<FAST>(g, tile * kWave + threadIdx.x);
+  int dotv[kOCB];
+  grouped_dots<FAST>(P, M, W, Z, g, px, ob, Cg, Og, S, dotv);
   uint32_t pbits = 0u, mbits = 0u;
   float resv[kOCB];  // (no residual in this epilogue)
   // the float operations of the other kernels: fmaf(alpha, dot, bias) [* post_scale] (or the int32 dot: EF_RAW).  A whole
@@ -90,6 +99,105 @@ __global__ __launch_bounds__(64) void bconv_grouped_kernel(
   // and store the same value to the same place).
   if ((ob + 1) * kOCB <= g.O) epilogue<kOCB, EP_PLAIN, true>(g, px, ob * kOCB, dotv, resv, epi, pbits, mbits);
   else epilogue<kOCB, EP_PLAIN>(g, px, ob * kOCB, dotv, resv, epi, pbits, mbits);
+}
+
+// Epilogue of a BATS cell operation (bnn/models/layers/bats_ops.py:108-173: y = [x +] channel_shuffle(PReLU(conv), 4)):
+//     v  = fmaf(alpha[o], dot, bias[o]) [* post_scale[o]]            the EP_PLAIN operations, the same bits
+//     v  = v >= 0 ? v : prelu[o] * v                                  (EF_PRELU; the form of bconv_core.h's epilogue)
+//     o' = (o % (O / sg)) * sg + o / (O / sg)                         channel_shuffle(., sg) as a store index
+//     out[n, o', y, x] = res[n, o', y, x] + v                         (EF_RES)
+// The shuffle moves whole channel planes: a store instruction still writes 64 consecutive pixels of ONE plane, only the
+// wave-uniform plane offset (the buffer instruction's scalar operand) changes.  o -> o' runs on the scalar unit, without a
+// division per channel: (q, r) = (o / cpg, o % cpg) of the block's first channel, then r counts up and carries into q.
+// The product with the slope and the add of the residual are two roundings, as in torch: never contracted into an fma.
+// FULL (all 32 channels exist): the straight-line form of epilogue<.., FULL> — the residual loads of a batch of channels
+// are issued first and queue up, each channel then waits for its own (`s_waitcnt vmcnt(n)` counts down) while the stores
+// queue behind them.
+// PRELU / RES are compile-time there: as run-time flags every channel's slope load, select and residual became a branch
+// region of its own with an `s_waitcnt vmcnt(0)` at each join.  The partial last block keeps run-time flags and guards.
+template <bool FULL, bool PRELU = false, bool RES = false>
+__device__ __forceinline__ void cell_epilogue(const Geo& g, const Pix& px, const int o0, const int (&dot)[kOCB],
+                                              const EpiArgs& e, const int sg, const int cpg) {
+#pragma clang fp contract(off)
+  using f2 = __attribute__((ext_vector_type(2))) float;
+  const int hw = g.Ho * g.Wo;
+  const unsigned lane_off = px.out_base * 4u;  // BYTES; host keeps N*c_tot*hw < 2^30
+  const int f = g.flags;
+  const bool hb = (f & EF_BIAS) != 0, hs = (f & EF_SCALE) != 0;
+  unsigned choff[kOCB];  // byte offset of plane o' (wave-uniform)
+  {
+    int q = o0 / cpg, r = o0 - q * cpg;
+#pragma unroll
+    for (int j = 0; j < kOCB; ++j) {
+      choff[j] = (unsigned)(r * sg + q + g.c_off) * (unsigned)hw * 4u;
+      if (++r == cpg) { r = 0; ++q; }
+    }
+  }
+  if constexpr (FULL) {
+    // (the residual loads go out kResBatch channels at a time: all 32 at once cost 30 more VGPRs, a wave per SIMD less)
+    constexpr int kResBatch = 16;
+#pragma unroll
+    for (int j0 = 0; j0 < kOCB; j0 += kResBatch) {
+      [[maybe_unused]] float resv[kResBatch];
+      if constexpr (RES) {
+#pragma unroll
+        for (int j = 0; j < kResBatch; ++j) resv[j] = buf_ld(make_rsrc(e.res), lane_off, choff[j0 + j]);
+      }
+#pragma unroll
+      for (int j = j0; j < j0 + kResBatch; j += 2) {
+        const int o = o0 + j;
+        f2 y = __builtin_elementwise_fma(f2{e.alpha[o], e.alpha[o + 1]}, f2{(float)dot[j], (float)dot[j + 1]},
+                                         hb ? f2{e.bias[o], e.bias[o + 1]} : f2{0.0f, 0.0f});
+        if (hs) y *= f2{e.scale[o], e.scale[o + 1]};
+        float y0 = y.x, y1 = y.y;
+        if constexpr (PRELU) {
+          const float a0 = e.prelu[o], a1 = e.prelu[o + 1];  // (read outside the select: no branch per channel)
+          const float n0 = a0 * y0, n1 = a1 * y1;
+          y0 = (y0 >= 0.0f) ? y0 : n0;
+          y1 = (y1 >= 0.0f) ? y1 : n1;
+        }
+        if constexpr (RES) { y0 = resv[j - j0] + y0; y1 = resv[j - j0 + 1] + y1; }
+        buf_st(make_rsrc(e.out), lane_off, choff[j], y0);
+        buf_st(make_rsrc(e.out), lane_off, choff[j + 1], y1);
+      }
+    }
+  } else {  // channels past O (the pad channels of the weight layout) and dead lanes do not store
+    const bool hp = (f & EF_PRELU) != 0, hr = (f & EF_RES) != 0;
+    float* outf = static_cast<float*>(e.out);
+#pragma unroll
+    for (int j = 0; j < kOCB; ++j) {
+      const int o = o0 + j;
+      if (o < g.O && px.live) {
+        float y = fmaf(e.alpha[o], (float)dot[j], hb ? e.bias[o] : 0.0f);
+        if (hs) y *= e.scale[o];
+        if (hp) y = (y >= 0.0f) ? y : e.prelu[o] * y;
+        if (hr) y = ld_off(reinterpret_cast<const float*>(reinterpret_cast<const char*>(e.res) + choff[j]), lane_off) + y;
+        st_off(reinterpret_cast<float*>(reinterpret_cast<char*>(outf) + choff[j]), lane_off, y);
+      }
+    }
+  }
+}
+
+// The grouped convolution with the cell-operation epilogue: the main loop of bconv_grouped_kernel, one launch for
+// conv + PReLU + channel_shuffle + skip.  sg: shuffle groups (>= 1, divides O), cpg = O / sg.
+template <bool FAST>
+__global__ __launch_bounds__(64) void bconv_grouped_cell_kernel(
+    const uint32_t* __restrict__ P, const uint32_t* __restrict__ M, const uint32_t* __restrict__ W,
+    const uint32_t* __restrict__ Z, BNN_EPI_PARAMS, const Geo g, const int Cg, const int Og, const int S, const int sg,
+    const int cpg) {
+  BNN_EPI_INIT;
+  const int ob = (int)(blockIdx.x / (unsigned)g.tiles);
+  const int tile = (int)blockIdx.x - ob * g.tiles;
+  const Pix px = decode_pixel<FAST>(g, tile * kWave + threadIdx.x);
+  int dotv[kOCB];
+  grouped_dots<FAST>(P, M, W, Z, g, px, ob, Cg, Og, S, dotv);
+  const int o0 = ob * kOCB;
+  if (o0 + kOCB > g.O) return cell_epilogue<false>(g, px, o0, dotv, epi, sg, cpg);
+  const bool hp = (g.flags & EF_PRELU) != 0, hr = (g.flags & EF_RES) != 0;
+  if (hp && hr) cell_epilogue<true, true, true>(g, px, o0, dotv, epi, sg, cpg);
+  else if (hp) cell_epilogue<true, true, false>(g, px, o0, dotv, epi, sg, cpg);
+  else if (hr) cell_epilogue<true, false, true>(g, px, o0, dotv, epi, sg, cpg);
+  else cell_epilogue<true, false, false>(g, px, o0, dotv, epi, sg, cpg);
 }
 
 // p: geometry of the whole convolution (p.C = all input channels, p.cw32 = their words per pixel); S: words per tap of the
@@ -105,6 +213,22 @@ int launch_bconv_grouped(const ConvP& p, int groups, int S, hipStream_t s) {
   else
     hipLaunchKernelGGL((bconv_grouped_kernel<false>), grid, dim3(kWave), 0, s, p.P, p.M, p.W, p.Z, BNN_EPI_ACTUALS, g,
                        Cg, Og, S);
+  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+}
+
+// The same launch with the cell-operation epilogue (p.prelu, p.res optional; p.alpha set): capi.hip has checked, beyond
+// the above, shuffle_groups >= 1 and O % shuffle_groups == 0, and that p.res does not alias p.out.
+int launch_bconv_grouped_cell(const ConvP& p, int groups, int S, int shuffle_groups, hipStream_t s) {
+  const Geo g = make_geo(p);
+  const unsigned nb = (unsigned)((p.O + kOCB - 1) / kOCB);
+  const dim3 grid((unsigned)g.tiles * nb);
+  const int Cg = p.C / groups, Og = p.O / groups, cpg = p.O / shuffle_groups;
+  if (small_indices(p))
+    hipLaunchKernelGGL((bconv_grouped_cell_kernel<true>), grid, dim3(kWave), 0, s, p.P, p.M, p.W, p.Z, BNN_EPI_ACTUALS,
+                       g, Cg, Og, S, shuffle_groups, cpg);
+  else
+    hipLaunchKernelGGL((bconv_grouped_cell_kernel<false>), grid, dim3(kWave), 0, s, p.P, p.M, p.W, p.Z, BNN_EPI_ACTUALS,
+                       g, Cg, Og, S, shuffle_groups, cpg);
   return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
 }
 

@@ -171,6 +171,8 @@ int launch_pack_weight_grouped(const float* w, int O, int Cg, int groups, int ce
                                const bnn_hip_wlayout& L, uint32_t* wbits, uint32_t* wnz, float* alpha,
                                int32_t* zero_flag, hipStream_t stream);
 int launch_bconv_grouped(const ConvP& p, int groups, int S, hipStream_t s);
+// the same convolution with the cell-operation epilogue (PReLU p.prelu, channel_shuffle as a store index, skip p.res)
+int launch_bconv_grouped_cell(const ConvP& p, int groups, int S, int shuffle_groups, hipStream_t s);
 // bconv_fly.hip: the whole layer in one launch, activations (fp32, or fp16 when x_half) binarised on the fly into LDS.
 // p.P / p.M are unused; p.alpha / bias / scale / out as for launch_bconv.  `plan` may be null (default plan).
 bool fly_supported(const ConvP& p);

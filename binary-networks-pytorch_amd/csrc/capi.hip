@@ -231,6 +231,34 @@ BnWorkspace bn_workspace(int N, int C, int HW, void* base) {
           b ? reinterpret_cast<float*>(b + partial_bytes) : nullptr};
 }
 
+// Entry contract of the grouped convolution kernels (csrc/bconv_grouped.hip), shared by bnn_hip_bconv2d_grouped and
+// bnn_hip_bconv2d_grouped_fused: fills `p` (operands, epilogue constants, geometry) and *S, the words per tap of the
+// windowed weight layout.  alpha == NULL asks for the raw dot and excludes the other epilogue constants.
+int check_grouped(const bnn_hip_conv_desc* d, int groups, const uint64_t* P, const uint64_t* M, const uint32_t* wbits,
+                  const uint32_t* wnz, const float* alpha, const float* bias, const float* post_scale, float* out,
+                  bnn::ConvP* p, int* S) {
+  int Ho = 0, Wo = 0;
+  const int st = check_desc(d, &Ho, &Wo);
+  if (st != BNN_HIP_OK) return st;
+  if (groups <= 0 || d->C % groups != 0 || d->O % groups != 0) return BNN_HIP_ERR_INVALID_ARG;
+  if (!P || !M || !wbits || !wnz || !out) return BNN_HIP_ERR_INVALID_ARG;
+  if (!alpha && (bias || post_scale)) return BNN_HIP_ERR_INVALID_ARG;  // raw dot: no epilogue constants
+  if (!aligned(P, 16) || !aligned(M, 16) || !aligned(wbits, 16) || !aligned(wnz, 16) || !aligned(out, 4))
+    return BNN_HIP_ERR_INVALID_ARG;
+  bnn_hip_wlayout G;
+  const int sg = bnn_hip_grouped_weight_layout(d->O, d->C, groups, d->KH, d->KW, &G);
+  if (sg != BNN_HIP_OK) return sg;
+  p->alpha = alpha; p->bias = bias; p->scale = post_scale; p->out = out; p->raw = alpha == nullptr;
+  p->P = reinterpret_cast<const uint32_t*>(P);
+  p->M = reinterpret_cast<const uint32_t*>(M);
+  p->W = wbits;
+  p->Z = wnz;
+  fill_geometry(d, Ho, Wo, p);            // cw32: the activation words per pixel, as for a dense weight
+  p->cwc = p->cw32; p->nchunk = 1;        // (one chunk: the grouped kernel walks its window, not chunks)
+  *S = G.cw32;
+  return BNN_HIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -598,28 +626,36 @@ int bnn_hip_pack_weight_grouped_f32(const float* w, int O, int Cg, int groups, i
 int bnn_hip_bconv2d_grouped(const bnn_hip_conv_desc* d, int groups, const uint64_t* P, const uint64_t* M,
                             const uint32_t* wbits, const uint32_t* wnz, const float* alpha, const float* bias,
                             const float* post_scale, float* out, void* stream) {
-  int Ho = 0, Wo = 0;
-  const int st = check_desc(d, &Ho, &Wo);
-  if (st != BNN_HIP_OK) return st;
-  if (groups <= 0 || d->C % groups != 0 || d->O % groups != 0) return BNN_HIP_ERR_INVALID_ARG;
-  if (!P || !M || !wbits || !wnz || !out) return BNN_HIP_ERR_INVALID_ARG;
-  if (!alpha && (bias || post_scale)) return BNN_HIP_ERR_INVALID_ARG;  // raw dot: no epilogue constants
-  if (!aligned(P, 16) || !aligned(M, 16) || !aligned(wbits, 16) || !aligned(wnz, 16) || !aligned(out, 4))
-    return BNN_HIP_ERR_INVALID_ARG;
-  bnn_hip_wlayout G;
-  const int sg = bnn_hip_grouped_weight_layout(d->O, d->C, groups, d->KH, d->KW, &G);
-  if (sg != BNN_HIP_OK) return sg;
   bnn::ConvP p = empty_convp();
-  p.alpha = alpha; p.bias = bias; p.scale = post_scale; p.out = out; p.raw = alpha == nullptr;
-  p.P = reinterpret_cast<const uint32_t*>(P);
-  p.M = reinterpret_cast<const uint32_t*>(M);
-  p.W = wbits;
-  p.Z = wnz;
-  fill_geometry(d, Ho, Wo, &p);         // cw32: the activation words per pixel, as for a dense weight
-  p.cwc = p.cw32; p.nchunk = 1;         // (one chunk: the grouped kernel walks its window, not chunks)
+  int S = 0;
+  const int st = check_grouped(d, groups, P, M, wbits, wnz, alpha, bias, post_scale, out, &p, &S);
+  if (st != BNN_HIP_OK) return st;
   g_launches.fetch_add(1, std::memory_order_relaxed);
   Range range(p.raw ? "bnn_hip_bconv2d_grouped_dot" : "bnn_hip_bconv2d_grouped");
-  return bnn::launch_bconv_grouped(p, groups, G.cw32, static_cast<hipStream_t>(stream));
+  return bnn::launch_bconv_grouped(p, groups, S, static_cast<hipStream_t>(stream));
+}
+
+int bnn_hip_bconv2d_grouped_fused(const bnn_hip_conv_desc* d, int groups, const uint64_t* P, const uint64_t* M,
+                                  const uint32_t* wbits, const uint32_t* wnz, const float* alpha, const float* bias,
+                                  const float* post_scale, const float* prelu, int shuffle_groups,
+                                  const float* residual, float* out, void* stream) {
+  bnn::ConvP p = empty_convp();
+  int S = 0;
+  const int st = check_grouped(d, groups, P, M, wbits, wnz, alpha, bias, post_scale, out, &p, &S);
+  if (st != BNN_HIP_OK) return st;
+  if (!alpha) return BNN_HIP_ERR_INVALID_ARG;  // the epilogue works on the float value: no raw-dot form
+  if (shuffle_groups < 1 || d->O % shuffle_groups != 0) return BNN_HIP_ERR_INVALID_ARG;
+  // the kernel reads the residual and writes its output through independent (__restrict__) pointers, and the shuffle
+  // makes a wave's stores land on other planes than its loads: the two [N,O,Ho,Wo] tensors must not overlap
+  if (residual) {
+    const uintptr_t r = reinterpret_cast<uintptr_t>(residual), o = reinterpret_cast<uintptr_t>(out);
+    const uintptr_t bytes = (uintptr_t)mulc(d->N, d->O, p.Ho, p.Wo) * 4;   // (check_desc: below 2^32)
+    if (!aligned(residual, 4) || (r < o + bytes && o < r + bytes)) return BNN_HIP_ERR_INVALID_ARG;
+  }
+  p.prelu = prelu; p.res = residual;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_bconv_grouped_cell(p, groups, S, shuffle_groups, static_cast<hipStream_t>(stream));
 }
 
 int bnn_hip_bconv2d_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M,

@@ -64,7 +64,8 @@ extern "C" {
 /* ABI 15 (round 6): + bnn_hip_hblock_{supported,layout_of,pack_weights,forward} (the hierarchical block in one launch);
  * + bnn_hip_avgpool2_bn_pack2_f32 (the pool in front of a pre-activation stage + both sign planes it feeds);
  * + bnn_hip_grouped_weight_layout, bnn_hip_pack_weight_grouped_f32, bnn_hip_bconv2d_grouped (grouped / depthwise
- * convolutions: additive entry points of ABI 15, no struct or signature changed).
+ * convolutions: additive entry points of ABI 15, no struct or signature changed); + bnn_hip_bconv2d_grouped_fused (the
+ * same convolution with PReLU, channel shuffle and skip connection in its launch: additive too).
  * ABI 14 (round 5): + bnn_hip_stem7x7_wgrad_f32 / bnn_hip_stem7x7_wgrad_workspace_bytes (weight gradient of the stem
  * convolution: the training backward of that layer); + bnn_hip_avgpool2x2_backward_f32, bnn_hip_xnor_grad_pack_weight_f32; + bnn_hip_avgpool_fc_ws_f32 / bnn_hip_avgpool_fc_workspace_bytes (the head as two streaming launches
  * through a workspace); + bnn_hip_stem7x7_conv_f32 (the stem's convolution alone: the training forward); the table of bnn_hip_sign_thresholds_f32 holds FOUR words per channel (was two) and kmax < 2^20.
@@ -473,6 +474,20 @@ int bnn_hip_pack_weight_grouped_f32(const float* w, int O, int Cg, int groups, i
 int bnn_hip_bconv2d_grouped(const bnn_hip_conv_desc* d, int groups, const uint64_t* P, const uint64_t* M,
                             const uint32_t* wbits, const uint32_t* wnz, const float* alpha, const float* bias,
                             const float* post_scale, float* out, void* stream);
+/* The same convolution with the epilogue of a BATS cell operation (bnn/models/layers/bats_ops.py:108-173:
+ * y = [x +] channel_shuffle(PReLU(conv(.)), 4)) in the one launch.  Per output channel o and pixel:
+ *     v  = fmaf(alpha[o], dot, bias ? bias[o] : 0) * (post_scale ? post_scale[o] : 1)      the bits of bnn_hip_bconv2d_grouped
+ *     v  = prelu ? (v >= 0 ? v : prelu[o] * v) : v                                         prelu: O floats
+ *     o' = shuffle_groups > 1 ? (o % (O / shuffle_groups)) * shuffle_groups + o / (O / shuffle_groups) : o
+ *     out[n,o',y,x] = residual ? residual[n,o',y,x] + v : v                                residual: float32 [N,O,Ho,Wo]
+ * The product with the slope and the add of the residual are two separately rounded fp32 operations.
+ * Everything bnn_hip_bconv2d_grouped requires, and: alpha != NULL (no raw-dot form); shuffle_groups >= 1 and
+ * O % shuffle_groups == 0; residual, when given, 4-byte aligned and not overlapping `out` (no in-place skip).
+ * prelu == NULL, shuffle_groups == 1, residual == NULL: the bits of bnn_hip_bconv2d_grouped.                             */
+int bnn_hip_bconv2d_grouped_fused(const bnn_hip_conv_desc* d, int groups, const uint64_t* P, const uint64_t* M,
+                                  const uint32_t* wbits, const uint32_t* wnz, const float* alpha, const float* bias,
+                                  const float* post_scale, const float* prelu, int shuffle_groups,
+                                  const float* residual, float* out, void* stream);
 
 /* Binary fully-connected layer: x packed as [B][ceil(F/64)] planes (pack_act with
  * H=W=1, i.e. [B][ceil(F/64)] words), weight packed with KH=KW=1.  out: float32 [B,O].                         */

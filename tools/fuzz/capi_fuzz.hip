@@ -388,6 +388,24 @@ int launch_bconv_grouped(const ConvP& p, int groups, int S, hipStream_t) {
   check_group_windows(p.O, p.C, groups, S, p.cw32);
   return BNN_HIP_OK;
 }
+int launch_bconv_grouped_cell(const ConvP& p, int groups, int S, int shuffle_groups, hipStream_t) {
+  ++g_reached;
+  check_convp(p);
+  REQUIRE((long long)p.N * p.H * p.Wd * ((p.C + 63) / 64) <= kPlaneWords);
+  REQUIRE(p.P && p.M && p.W && p.Z && p.out && al(p.P, 16) && al(p.M, 16) && al(p.W, 16) && al(p.Z, 16) && al(p.out, 4));
+  REQUIRE(!p.raw && p.alpha != nullptr);                                    // no raw-dot form
+  REQUIRE(shuffle_groups >= 1 && p.O % shuffle_groups == 0);               // o -> o' stays inside [0, O)
+  if (p.res) {   // 4-byte aligned and disjoint from the output tensor
+    const uintptr_t r = reinterpret_cast<uintptr_t>(p.res), o = reinterpret_cast<uintptr_t>(p.out);
+    const uintptr_t bytes = (uintptr_t)p.N * p.O * p.Ho * p.Wo * 4;
+    REQUIRE(al(p.res, 4) && (r >= o + bytes || o >= r + bytes));
+  }
+  REQUIRE(p.c_off == 0 && p.c_tot == p.O);                                 // residual and output are [N, O, Ho, Wo]
+  REQUIRE(!p.outP && !p.outM && !p.bn_a && !p.ds_P && !p.relu);
+  REQUIRE((long long)((p.O + 31) / 32 * 32) * p.KH * p.KW * S <= (1LL << 31) - 1);
+  check_group_windows(p.O, p.C, groups, S, p.cw32);
+  return BNN_HIP_OK;
+}
 int launch_probe_int_alu(int mode, int iters, double* r, double*, hipStream_t) { REQUIRE(iters > 0 && r); (void)mode; return BNN_HIP_OK; }
 int launch_probe_clock(int it, double* mhz, double*, hipStream_t) { REQUIRE(it > 0 && mhz); return BNN_HIP_OK; }
 }  // namespace bnn
@@ -436,7 +454,7 @@ int main(int argc, char** argv) {
   for (long it = 0; it < iters; ++it) {
     ++g_calls;
     int st = 0;
-    switch (rnd() % 47) {
+    switch (rnd() % 48) {
       case 0: { bnn_hip_conv_desc d = pick_desc();
         st = bnn_hip_bconv2d(rnd() % 16 ? &d : nullptr, pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<uint32_t>(),
                              pick_ptr<uint32_t>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), stream);
@@ -611,6 +629,17 @@ int main(int argc, char** argv) {
                                      pick_ptr<uint64_t>(), pick_ptr<uint32_t>(), pick_ptr<uint32_t>(),
                                      raw ? nullptr : pick_ptr<float>(), raw ? nullptr : pick_ptr<float>(),
                                      raw ? nullptr : pick_ptr<float>(), pick_ptr<float>(), stream);
+        break; }
+      case 47: { bnn_hip_conv_desc d = pick_desc();
+        if (rnd() % 2) { d.O = d.C; }
+        const int sgs[] = {1, 1, 2, 4, 12};
+        const int sg = rnd() % 8 ? sgs[rnd() % 5] : pick_int();
+        float* out = pick_ptr<float>();
+        const float* res = rnd() % 3 == 0 ? nullptr : rnd() % 4 == 0 ? out : pick_ptr<float>();
+        st = bnn_hip_bconv2d_grouped_fused(rnd() % 16 ? &d : nullptr, pick_groups(d.C, d.O), pick_ptr<uint64_t>(),
+                                           pick_ptr<uint64_t>(), pick_ptr<uint32_t>(), pick_ptr<uint32_t>(),
+                                           pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), sg,
+                                           res, out, stream);
         break; }
       default: { bnn_hip_conv_desc d = pick_desc();
         (void)bnn_hip_shortcut_fold_supported(rnd() % 16 ? &d : nullptr, pick_int());
