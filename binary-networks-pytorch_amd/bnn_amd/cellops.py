@@ -10,6 +10,11 @@ convolution launch whose epilogue applies the PReLU, stores through the shuffle 
 three fp32 passes over HBM (x read by the pack, x read as the skip, y written) instead of about eleven.  The per-layer
 path — torch BatchNorm, ``pack_act``, the grouped kernel, torch PReLU, the ``.contiguous()`` shuffle copy, torch add —
 stays what every call outside ``eval()`` / ``no_grad()`` runs.
+
+``FusedCell(cell)`` evaluates a whole ``Cell`` (reference: ``bnn/models/bats.py:9-83``) the same way: every state is
+binarised once for all the operations that read it (``bn_act_pack_multi``), a node ``s = op1(h1) + op2(h2)`` is the
+second operation's launch adding the first one's result in its epilogue (``bnn_hip_bconv2d_grouped_node``), and that
+launch stores into the node's channel slice of the cell output, so neither the add nor ``torch.cat`` runs.
 """
 from __future__ import annotations
 
@@ -23,6 +28,7 @@ from . import fastpath, hipops, native
 from .executor import FusionError, fold_bn
 
 CELL_OP_NAMES = ("SepConv", "DilConv", "ReLUConvBN")
+MAX_PACK_SETS = 4       # plane sets one bn_act_pack_multi launch writes (include/bnn_hip.h)
 SHUFFLE_GROUPS = 4      # channel_shuffle(., 4) in SepConv.forward / DilConv.forward
 
 
@@ -142,3 +148,332 @@ class FusedCellOp(nn.Module):
                                         padding=conv.padding, dilation=conv.dilation)
         fastpath._bump("cell_op")
         return y
+
+
+def _stride_of(op: nn.Module) -> int:
+    s = getattr(op, "stride", 1)
+    return s[0] if isinstance(s, (tuple, list)) else s
+
+
+def _binary_plan(conv, what: str):
+    if not (isinstance(conv, nn.Conv2d) and hasattr(conv, "activation_pre_process")):
+        raise FusionError(f"{what} is not a binary Conv2d (run prepare_binary_model first)")
+    plan = fastpath._recognise(conv, conv.out_channels)
+    if plan is None:
+        raise FusionError(f"{what}: layer recipe is not BasicInputBinarizer + XNORWeightBinarizer "
+                          "(+ Identity | BasicScaleBinarizer)")
+    if conv.weight.dtype != torch.float32:
+        raise FusionError(f"{what}: only float32 modules are covered")
+    return plan
+
+
+class _Reduce:
+    """Recognition and derived data of one ``FactorizedReduce``: BatchNorm folded for ``bn_act_pack_s2``, the two 1x1
+    stride-2 convolutions as dense launches on the two phases, the PReLU slopes split like the output channels."""
+
+    def __init__(self, m: nn.Module) -> None:
+        bn, act = getattr(m, "bn", None), getattr(m, "activation", None)
+        convs = [getattr(m, n, None) for n in ("conv_1", "conv_2")]
+        if not (isinstance(bn, nn.BatchNorm2d) and isinstance(act, nn.PReLU)
+                and all(isinstance(c, nn.Sequential) and len(c) == 1 for c in convs)):
+            raise FusionError("FactorizedReduce is not bn / conv_1 / conv_2 / activation as the reference defines it")
+        if bn.running_mean is None or bn.running_var is None or bn.running_var.dtype != torch.float32:
+            raise FusionError("FactorizedReduce: BatchNorm2d without float32 running statistics")
+        self.convs = [c[0] for c in convs]
+        self.plans = [_binary_plan(c, "FactorizedReduce convolution") for c in self.convs]
+        half = self.convs[0].out_channels
+        for c in self.convs:
+            if (c.in_channels != bn.num_features or c.out_channels != half or c.groups != 1
+                    or tuple(c.kernel_size) != (1, 1) or tuple(c.stride) != (2, 2) or tuple(c.padding) != (0, 0)
+                    or isinstance(c.padding, str) or c.padding_mode != "zeros"):
+                raise FusionError("FactorizedReduce: the convolutions are not 1x1 / stride 2 / no padding over the "
+                                  "BatchNorm's channels")
+        if act.weight.numel() not in (1, 2 * half):
+            raise FusionError("FactorizedReduce: PReLU width does not fit the concatenated output")
+        self.C_in, self.C_out = bn.num_features, 2 * half
+        self.bn_a, self.bn_b = fold_bn(bn)
+        slope = act.weight.detach().float().reshape(-1)
+        slope = (slope.expand(self.C_out) if slope.numel() == 1 else slope).clone()
+        self.prelu = [slope[:half].contiguous(), slope[half:].contiguous()]
+        self.weights = None
+        if self.convs[0].weight.is_cuda:
+            native.require()
+            self.weights = [fastpath.packed_weight(c, p) for c, p in zip(self.convs, self.plans)]
+
+    def pack(self, x: torch.Tensor):
+        if x.shape[2] % 2 or x.shape[3] % 2:
+            raise FusionError(f"FactorizedReduce needs even H and W, got {tuple(x.shape[2:])}")
+        return hipops.bn_act_pack_s2(x, self.bn_a, self.bn_b, relu=False)
+
+    def conv(self, planes, k: int, out: torch.Tensor) -> None:
+        half = self.C_out // 2
+        hipops.bconv2d_fused(planes[k], self.weights[k], bias=self.convs[k].bias, post_scale=self.plans[k].scale,
+                             prelu=self.prelu[k], out=out, out_c_offset=k * half)
+
+
+class FusedCell(nn.Module):
+    """Inference executor of one BATS ``Cell`` at ``drop_prob = 0``: ``FusedCell(cell)(s0, s1)``.
+
+    Recognition follows ``FusedCellOp`` — class names plus structure (``Cell`` with ``preprocess0`` / ``preprocess1`` /
+    ``_ops`` / ``_indices`` / ``_concat``; operations named ``SepConv``, ``DilConv``, ``FactorizedReduce``, ``Zero`` or
+    torch's ``Identity`` / ``AvgPool2d`` / ``MaxPool2d``), so a cell of the reference's own classes works when handed over
+    explicitly.  ``use_shake_shake``, training mode, an odd ``H`` or ``W`` in front of a ``FactorizedReduce`` and
+    anything unrecognised raise ``FusionError``.
+
+    ``steps`` lists the planned launches and torch calls as ``(kind, detail)`` with kinds ``pack``, ``pack_s2``,
+    ``pack_multi``, ``dense``, ``grouped_node``, ``torch_pool``, ``torch_add``, ``copy``, ``zero``.  A ``Zero`` term is
+    dropped from its node: equal as numbers, only ``-0.0 + 0.0`` would have been ``+0.0``.
+
+    Derived data is keyed on the identity, storage and version of every parameter and buffer of the cell, like
+    ``FusedCellOp``; writes through ``.data`` need ``refresh()`` (or ``fastpath.invalidate(cell)``)."""
+
+    def __init__(self, cell: nn.Module) -> None:
+        super().__init__()
+        self.model = cell
+        self._sig = None
+        self.refresh()
+
+    # ---- recognition and planning ---------------------------------------------------------------------------------
+    def _kind(self, op: nn.Module) -> str:
+        name = type(op).__name__
+        if name in ("SepConv", "DilConv"):
+            return "conv"
+        if name == "FactorizedReduce":
+            return "reduce"
+        if name == "Zero" and isinstance(getattr(op, "stride", None), int):
+            return "zero"
+        if type(op) is nn.Identity:
+            return "identity"
+        if type(op) in (nn.AvgPool2d, nn.MaxPool2d):
+            return "pool"
+        raise FusionError(f"cell: operation {name} is not covered")
+
+    def refresh(self) -> None:
+        """Re-derive everything from the cell's current parameters and buffers."""
+        self._sig = None
+        cell = self.model
+        if type(cell).__name__ != "Cell":
+            raise FusionError(f"{type(cell).__name__} is not a BATS Cell")
+        if cell.training:
+            raise FusionError("FusedCell is inference-only: call .eval() first")
+        if getattr(cell, "use_shake_shake", False):
+            raise FusionError("cell: use_shake_shake is not covered")
+        ops, idx, concat = getattr(cell, "_ops", None), getattr(cell, "_indices", None), getattr(cell, "_concat", None)
+        if not (isinstance(ops, nn.ModuleList) and idx is not None and concat is not None and len(ops) == len(idx)
+                and len(ops) % 2 == 0 and len(ops) == 2 * getattr(cell, "_steps", -1) and len(concat) > 0):
+            raise FusionError("cell: _ops / _indices / _concat / _steps are not as Cell._compile leaves them")
+        n_states = 2 + len(ops) // 2
+        idx, concat = [int(i) for i in idx], [int(c) for c in concat]
+        if any(not 0 <= j < 2 + k // 2 for k, j in enumerate(idx)) or any(not 0 <= c < n_states for c in concat) \
+                or len(set(concat)) != len(concat):
+            raise FusionError("cell: an operation reads a later state, or the concat list repeats or exceeds the states")
+        fastpath.invalidate(cell, executors=False)
+        self._pre = []
+        for name in ("preprocess0", "preprocess1"):
+            m = getattr(cell, name, None)
+            if type(m).__name__ == "ReLUConvBN":
+                self._pre.append(FusedCellOp(m))
+            elif type(m).__name__ == "FactorizedReduce":
+                self._pre.append(_Reduce(m))
+            else:
+                raise FusionError(f"cell: {name} is {type(m).__name__}, not ReLUConvBN / FactorizedReduce")
+        self._kinds = [self._kind(op) for op in ops]
+        self._conv = {k: FusedCellOp(op) for k, op in enumerate(ops) if self._kinds[k] == "conv"}
+        self._red = {k: _Reduce(op) for k, op in enumerate(ops) if self._kinds[k] == "reduce"}
+        widths = {p.C_out if isinstance(p, _Reduce) else p.model.op[1].out_channels for p in self._pre}
+        widths |= {e.model.op[1].in_channels for e in self._conv.values()} | {r.C_in for r in self._red.values()}
+        widths |= {r.C_out for r in self._red.values()}
+        if len(widths) != 1:
+            raise FusionError(f"cell: preprocessing and operations do not share one width ({sorted(widths)})")
+        C = widths.pop()
+        # a reduction cell: every operation on s0 / s1 has stride 2, and the nodes live at half the resolution
+        self._reduction = any(self._kinds[k] == "reduce" or _stride_of(op) == 2 for k, op in enumerate(ops))
+        self._C, self._idx, self._concat, self._n_states = C, idx, concat, n_states
+        # per state: its SepConv / DilConv consumers in chunks of MAX_PACK_SETS, their folded BatchNorms stacked
+        self._packs = {}
+        for j in range(n_states):
+            users = [k for k in self._conv if idx[k] == j]
+            chunks = [users[i:i + MAX_PACK_SETS] for i in range(0, len(users), MAX_PACK_SETS)]
+            self._packs[j] = [(ch, torch.stack([self._conv[k]._bn_a for k in ch]),
+                               torch.stack([self._conv[k]._bn_b for k in ch])) for ch in chunks]
+        self._plan = self._make_plan()
+        self._sig = self._signature()
+
+    def _make_plan(self):
+        """The steps of one forward as ``(kind, detail, run)``; ``run(env)`` works on ``env``: ``in`` (s0, s1), ``state``
+        (list), ``planes`` (operation -> PackedAct), ``out`` (the cell output)."""
+        plan = []
+        C, idx, kinds = self._C, self._idx, self._kinds
+
+        def add(kind, detail, run):
+            plan.append((kind, detail, run))
+
+        # -- the two input states
+        for i, pre in enumerate(self._pre):
+            if isinstance(pre, FusedCellOp):
+                add("pack", {"op": f"preprocess{i}", "sets": 1},
+                    lambda env, i=i, pre=pre: env["planes"].__setitem__(
+                        ("pre", i), hipops.bn_act_pack(env["in"][i], pre._bn_a, pre._bn_b, relu=False)))
+                add("dense", {"op": f"preprocess{i}"}, lambda env, i=i, pre=pre: self._run_rcb(env, i, pre))
+            else:
+                self._plan_reduce(add, f"preprocess{i}", pre, lambda env, i=i: env["in"][i],
+                                  lambda env, y, i=i: env["state"].__setitem__(i, y))
+        add("alloc", None, self._alloc)     # (not a step: the cell output, once the states' shape is known)
+
+        packed = set()
+
+        def need_planes(j):
+            if j in packed:
+                return
+            packed.add(j)
+            for ch, a, b in self._packs[j]:
+                add("pack_multi", {"state": j, "ops": list(ch), "sets": len(ch)},
+                    lambda env, j=j, ch=ch, a=a, b=b: env["planes"].update(
+                        zip(ch, hipops.bn_act_pack_multi(env["state"][j], a, b, relu=False))))
+
+        def other_term(k, tmp):
+            """Plan the non-convolution operation k; returns how to fetch its value from env."""
+            j = idx[k]
+            if kinds[k] == "identity":
+                return lambda env: env["state"][j]
+            if kinds[k] == "pool":
+                op = self.model._ops[k]
+                add("torch_pool", {"op": k, "state": j}, lambda env: env["tmp"].__setitem__(tmp, op(env["state"][j])))
+            else:
+                self._plan_reduce(add, k, self._red[k], lambda env: env["state"][j],
+                                  lambda env, y: env["tmp"].__setitem__(tmp, y))
+            return lambda env: env["tmp"][tmp]
+
+        # -- the nodes
+        for n in range(len(kinds) // 2):
+            s = n + 2
+            terms = [k for k in (2 * n, 2 * n + 1) if kinds[k] != "zero"]
+            convs = [k for k in terms if kinds[k] == "conv"]
+            others = [k for k in terms if kinds[k] != "conv"]
+            dest = lambda env, s=s: self._dest(env, s)      # noqa: E731
+            for k in convs:
+                need_planes(idx[k])
+            if len(convs) == 2:
+                k1, k2 = convs
+                add("grouped_node", {"op": k1, "state": idx[k1], "addend": False, "to": "temporary"},
+                    lambda env, k1=k1, s=s: env["tmp"].__setitem__((s, "h1"), self._run_node(env, k1, None, None)))
+                add("grouped_node", {"op": k2, "state": idx[k2], "addend": True, "to": s},
+                    lambda env, k2=k2, s=s, dest=dest: self._run_node(env, k2, env["tmp"][(s, "h1")], dest(env)))
+            elif len(convs) == 1:
+                get = other_term(others[0], (s, "other")) if others else None
+                add("grouped_node", {"op": convs[0], "state": idx[convs[0]], "addend": get is not None, "to": s},
+                    lambda env, k=convs[0], get=get, dest=dest: self._run_node(
+                        env, k, None if get is None else get(env), dest(env)))
+            elif len(others) == 2:
+                ga, gb = other_term(others[0], (s, "a")), other_term(others[1], (s, "b"))
+                add("torch_add", {"ops": list(others), "to": s},
+                    lambda env, ga=ga, gb=gb, dest=dest: torch.add(self._same(ga(env), gb(env)), gb(env), out=dest(env)))
+            elif len(others) == 1:
+                ga = other_term(others[0], (s, "a"))
+                add("copy", {"op": others[0], "to": s}, lambda env, ga=ga, dest=dest: dest(env).copy_(ga(env)))
+            else:
+                add("zero", {"to": s}, lambda env, dest=dest: dest(env).zero_())
+        # -- input states named in the concat list are copied into their slices
+        for c in self._concat:
+            if c < 2:
+                add("copy", {"state": c, "to": "concat"},
+                    lambda env, c=c: self._slice(env, c).copy_(self._same(env["state"][c], self._slice(env, c))))
+        return plan
+
+    def _plan_reduce(self, add, name, red, src, put) -> None:
+        key = ("reduce", name)
+        add("pack_s2", {"op": name}, lambda env: env["planes"].__setitem__(key, red.pack(src(env))))
+
+        def first(env):
+            p = env["planes"][key]
+            N, _, H, W = p[0].shape
+            y = torch.empty((N, red.C_out, H, W), dtype=torch.float32, device=p[0].P.device)
+            red.conv(p, 0, y)
+            put(env, y)
+            env["tmp"][key] = y
+        add("dense", {"op": name, "half": 0}, first)
+        add("dense", {"op": name, "half": 1}, lambda env: red.conv(env["planes"][key], 1, env["tmp"][key]))
+
+    @property
+    def steps(self):
+        """The planned steps as ``(kind, detail)``, in execution order."""
+        return [(kind, dict(detail)) for kind, detail, _ in self._plan if detail is not None]
+
+    # ---- derived data ---------------------------------------------------------------------------------------------
+    def _signature(self):
+        return tuple((id(t), t.data_ptr(), t._version)
+                     for t in itertools.chain(self.model.parameters(), self.model.buffers()))
+
+    def _unchanged(self) -> bool:
+        return self._sig is not None and not self.model.training and self._signature() == self._sig
+
+    # ---- the steps ------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _same(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+        if a.shape != b.shape:
+            raise FusionError(f"cell: the two terms of a node have shapes {tuple(a.shape)} and {tuple(b.shape)}")
+        return a
+
+    def _run_rcb(self, env, i: int, pre: FusedCellOp) -> None:
+        conv = pre.model.op[1]
+        x = env["in"][i]
+        y, _ = hipops.bconv2d_fused(env["planes"][("pre", i)], pre._weight, bias=conv.bias, post_scale=pre._plan.scale,
+                                    prelu=pre._prelu, residual=x if pre._add_skip else None, residual_after_act=True,
+                                    stride=conv.stride, padding=conv.padding, dilation=conv.dilation)
+        env["state"][i] = y
+
+    def _alloc(self, env) -> None:
+        """The cell output ``[N, len(concat) * C, H, W]`` at the nodes' resolution: every node state named in the concat
+        list IS its channel slice."""
+        s0, s1 = env["state"][0], env["state"][1]
+        self._same(s0, s1)
+        N, C, H, W = s1.shape
+        if self._reduction:
+            H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        env["out"] = torch.empty((N, len(self._concat) * C, H, W), dtype=torch.float32, device=s1.device)
+        env["node_shape"] = (N, C, H, W)
+
+    def _slice(self, env, s: int) -> torch.Tensor:
+        p = self._concat.index(s)
+        return env["out"][:, p * self._C:(p + 1) * self._C]
+
+    def _dest(self, env, s: int) -> torch.Tensor:
+        """Where node state ``s`` is stored: its slice of the cell output, or a tensor of its own."""
+        if env["state"][s] is None:
+            env["state"][s] = self._slice(env, s) if s in self._concat else torch.empty(
+                env["node_shape"], dtype=torch.float32, device=env["out"].device)
+        return env["state"][s]
+
+    def _run_node(self, env, k: int, addend: Optional[torch.Tensor], out: Optional[torch.Tensor]) -> torch.Tensor:
+        e = self._conv[k]
+        conv = e.model.op[1]
+        x = env["state"][self._idx[k]]
+        planes = env["planes"][k]
+        N, _, H, W = planes.shape
+        shape = (N, self._C) + hipops.conv_out_hw(H, W, conv.kernel_size[0], conv.kernel_size[1], conv.stride,
+                                                  conv.padding, conv.dilation)
+        for t in (addend, out):
+            if t is not None and tuple(t.shape) != shape:
+                raise FusionError(f"cell: operation {k} gives {shape}, its node holds {tuple(t.shape)}")
+        return hipops.bconv2d_grouped_node(planes, e._weight, fastpath._f32(conv.bias), fastpath._f32(e._plan.scale),
+                                           conv.stride, conv.padding, conv.dilation, prelu=e._prelu,
+                                           shuffle_groups=e._shuffle, residual=x if e._add_skip else None,
+                                           addend=addend, out=out)
+
+    # ---- forward --------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def forward(self, s0: torch.Tensor, s1: torch.Tensor) -> torch.Tensor:
+        for x in (s0, s1):
+            if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
+                raise FusionError("cell: the inputs must be float32 NCHW tensors on a HIP device")
+        if s0.device != s1.device or s0.shape[0] != s1.shape[0]:
+            raise FusionError("cell: the two inputs differ in device or batch size")
+        if not self._unchanged():
+            self.refresh()
+        if next(self.model.parameters()).device != s0.device:
+            raise FusionError("cell: module and input live on different devices")
+        env = {"in": (s0, s1), "state": [None] * self._n_states, "planes": {}, "tmp": {}, "out": None}
+        for _, _, run in self._plan:
+            run(env)
+        fastpath._bump("cell")
+        return env["out"]

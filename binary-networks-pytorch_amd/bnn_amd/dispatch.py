@@ -1,6 +1,6 @@
 """What ``model(x)`` and ``block(x)`` dispatch to by themselves — the drop-in tiers: ``AutoFusion`` (whole model:
 the fused executor, as eager launches / stem launch + HIP graph / two halves in flight), ``BlockFusion`` (one residual
-block), ``OpFusion`` (one BATS cell operation), and ``install_auto_fusion`` (the same dispatch for ResNets of other packages, from ``prepare_binary_model``).
+block), ``OpFusion`` (one BATS cell operation), ``CellFusion`` (one whole BATS cell), and ``install_auto_fusion`` (the same dispatch for ResNets of other packages, from ``prepare_binary_model``).
 Reference call being served: ``outputs = net(inputs)`` (examples/cifar10.py:71,140-149)."""
 from __future__ import annotations
 
@@ -18,7 +18,7 @@ import torch.nn as nn
 
 from . import fastpath, native
 from . import tails as _tails
-from .cellops import FusedCellOp
+from .cellops import FusedCell, FusedCellOp
 from .executor import FusedBlocks, FusedResNet, FusionError, is_native_model, resnet_shaped, tap_binary_inputs
 from .pipeline import TwoHalves
 from .models.resnet import ResNet
@@ -172,6 +172,84 @@ def auto_op_forward(op: nn.Module, x: torch.Tensor) -> Optional[torch.Tensor]:
     if st is None:
         st = op.__dict__["_bnn_auto_op"] = OpFusion()
     return st.run(op, x)
+
+
+_NO_CELL_FUSION = 0
+
+
+@contextlib.contextmanager
+def no_cell_fusion():
+    """While active, a ``Cell`` does not evaluate itself as ``FusedCell``; its operations still fuse one by one
+    (``OpFusion``) and torch adds and concatenates their results."""
+    global _NO_CELL_FUSION
+    _NO_CELL_FUSION += 1
+    try:
+        yield
+    finally:
+        _NO_CELL_FUSION -= 1
+
+
+class CellFusion:
+    """``OpFusion`` one level up: a ``Cell`` of ``bnn_amd.models`` called for inference on a HIP device evaluates itself
+    as ``FusedCell(cell)`` — every state binarised once for all its consumers, each node's add and the concatenation in
+    the epilogue of a convolution launch.  Same conditions as ``OpFusion``, and ``no_cell_fusion()`` not active; one
+    instance per cell in ``cell.__dict__['_bnn_auto_cell']``."""
+
+    def __init__(self) -> None:
+        self.engine = None
+        self.failed_sig = None
+        self.calls = {"fused": 0, "declined": 0}
+        self.lock = threading.Lock()
+
+    def __deepcopy__(self, memo):
+        return CellFusion()
+
+    def __reduce__(self):
+        return (CellFusion, ())
+
+    def _decline(self):
+        self.calls["declined"] += 1
+        return None
+
+    def run(self, cell: nn.Module, s0: torch.Tensor, s1: torch.Tensor) -> Optional[torch.Tensor]:
+        if (cell.training or torch.is_grad_enabled() or _NO_CELL_FUSION or _tails._PER_LAYER
+                or any(not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4
+                       or x.shape[0] == 0 for x in (s0, s1))
+                or getattr(cell, "_is_replica", False) or os.environ.get("BNN_AMD_AUTOFUSE", "1") == "0"
+                or fastpath.strict_weights() or not native.available()):
+            return self._decline()
+        with self.lock:
+            eng = self.engine
+            # (inside a caller's own graph capture nothing may be built or re-derived, as in BlockFusion.run)
+            if torch.cuda.is_current_stream_capturing() and (eng is None or not eng._unchanged()):
+                return self._decline()
+            if eng is None:
+                sig = _param_signature(cell)
+                if self.failed_sig == sig:
+                    return self._decline()
+                try:
+                    eng = self.engine = FusedCell(cell)
+                except FusionError:
+                    self.failed_sig = sig
+                    return self._decline()
+            if AutoFusion._hooked(cell) or next(cell.parameters()).device != s0.device:
+                return self._decline()
+        try:
+            y = eng(s0, s1)
+        except FusionError:     # e.g. an odd H or W in front of a FactorizedReduce: the cell's own forward reports it
+            with self.lock:
+                self.engine, self.failed_sig = None, _param_signature(cell)
+            return self._decline()
+        self.calls["fused"] += 1
+        return y
+
+
+def auto_cell_forward(cell: nn.Module, s0: torch.Tensor, s1: torch.Tensor) -> Optional[torch.Tensor]:
+    """Called at the top of ``Cell.forward``: the fused cell's output, or None -> its own forward."""
+    st = cell.__dict__.get("_bnn_auto_cell")
+    if st is None:
+        st = cell.__dict__["_bnn_auto_cell"] = CellFusion()
+    return st.run(cell, s0, s1)
 
 
 class AutoFusion:

@@ -39,7 +39,7 @@ import torch.nn as nn
 from . import hipops, native
 
 _stats_lock = threading.Lock()
-_stats = {"conv2d": 0, "conv1d": 0, "linear": 0, "weight_packs": 0, "conv2d_train": 0, "cell_op": 0}
+_stats = {"conv2d": 0, "conv1d": 0, "linear": 0, "weight_packs": 0, "conv2d_train": 0, "cell_op": 0, "cell": 0}
 
 
 def stats() -> dict:
@@ -257,6 +257,7 @@ def invalidate(module: nn.Module, executors: bool = True) -> int:
         if executors:       # a residual block's own fused executor (dispatch.BlockFusion); an executor that re-derives
             m.__dict__.pop("_bnn_auto_block", None)     # ITSELF (refresh) passes False: it may be that very object
             m.__dict__.pop("_bnn_auto_op", None)        # a cell operation's executor (dispatch.OpFusion)
+            m.__dict__.pop("_bnn_auto_cell", None)      # a whole cell's executor (dispatch.CellFusion)
     from .tails import drop_derived                 # folded BatchNorms / transposed head weights of the per-layer tails
     drop_derived(module)
     return n

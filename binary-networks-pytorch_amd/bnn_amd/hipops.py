@@ -183,6 +183,81 @@ def bn_act_pack(x: torch.Tensor, bn_scale=None, bn_shift=None, relu: bool = Fals
     return a
 
 
+def channel_view(t: torch.Tensor, what: str = "tensor"):
+    """``(base tensor, c_offset, c_total)`` of ``t``: a contiguous fp32 NCHW tensor on a HIP device, or a slice
+    ``base[:, c0:c1]`` of one (what a cell state is: a run of channels of the cell's concatenated output).  No copy."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4):
+        raise native.NativeError(f"bnn_amd: {what} must be a float32 NCHW tensor on a HIP device")
+    if t.is_contiguous():
+        return t, 0, t.shape[1]
+    N, C, H, W = t.shape
+    sn, sc, sh, sw = t.stride()
+    hw = H * W
+    off = t.storage_offset()
+    if (sc, sh, sw) == (hw, W, 1) and hw > 0 and sn % hw == 0 and sn // hw >= C:
+        c_total = sn // hw
+        c_off = (off % sn) // hw
+        if (off % sn) % hw == 0 and c_off + C <= c_total and off >= c_off * hw:
+            base = torch.as_strided(t, (N, c_total, H, W), (sn, hw, W, 1), off - c_off * hw)
+            return base, c_off, c_total
+    raise native.NativeError(f"bnn_amd: {what} is neither contiguous nor a channel slice of a contiguous NCHW tensor")
+
+
+def _view_struct(t: torch.Tensor, what: str):
+    base, c_off, c_total = channel_view(t, what)
+    return native.F32View(base.data_ptr(), c_off, c_total), base
+
+
+def bn_act_pack_multi(x: torch.Tensor, bn_scales, bn_shifts, relu: bool = False) -> list:
+    """``K`` plane sets ``sign(bn_k(x))`` from ONE read of ``x`` (``bnn_hip_bn_act_pack_multi_f32``, ``1 <= K <= 4``):
+    ``bn_scales`` / ``bn_shifts`` are ``[K, C]`` (or sequences of ``K`` vectors).  ``x`` may be a channel slice of a wider
+    contiguous tensor (``channel_view``); it is read in place.  Returns ``K`` ``PackedAct``, each with the bits of
+    ``bn_act_pack(x.contiguous(), scale_k, shift_k, relu)``."""
+    view, _keep = _view_struct(x, "activation")
+    N, C, H, W = x.shape
+
+    def table(v, what):
+        v = torch.stack([_per_channel(e, C, what) for e in v]) if isinstance(v, (list, tuple)) else v
+        v = _require_cuda_f32(v.detach(), what)
+        if v.dim() != 2 or v.shape[1] != C:
+            raise native.NativeError(f"bnn_amd: {what} must be [K, {C}]")
+        return v
+    a, b = table(bn_scales, "bn_scales"), table(bn_shifts, "bn_shifts")
+    K = a.shape[0]
+    if not 1 <= K <= 4 or b.shape[0] != K:
+        raise native.NativeError(f"bnn_amd: bn_act_pack_multi takes 1..4 affines, got {K} / {b.shape[0]}")
+    lib = native.require()
+    cw64 = (C + 63) // 64
+    with torch.cuda.device(x.device):
+        P = torch.empty((K, N, cw64, H, W), dtype=torch.int64, device=x.device)
+        M = torch.empty_like(P)
+        if N:
+            native.check(lib.bnn_hip_bn_act_pack_multi_f32(ctypes.byref(view), N, C, H, W, K, a.data_ptr(), b.data_ptr(),
+                                                           int(bool(relu)), P.data_ptr(), M.data_ptr(), _stream(x.device)),
+                         "bnn_hip_bn_act_pack_multi_f32")
+    return [PackedAct(P[k], M[k], (N, C, H, W), bool(relu)) for k in range(K)]
+
+
+def bn_act_pack_s2(x: torch.Tensor, bn_scale=None, bn_shift=None, relu: bool = False):
+    """The binarisation inside ``FactorizedReduce`` (``bnn_hip_bn_act_pack_s2_f32``): ``(phase0, phase1)`` with the bits
+    of ``bn_act_pack`` on ``x[:, :, ::2, ::2]`` and ``x[:, :, 1::2, 1::2]``, from one pass over ``x`` (H and W even;
+    ``x`` may be a channel slice, like ``bn_act_pack_multi``)."""
+    view, _keep = _view_struct(x, "activation")
+    N, C, H, W = x.shape
+    bn_scale = _per_channel(bn_scale, C, "bn_scale")
+    bn_shift = _per_channel(bn_shift, C, "bn_shift")
+    lib = native.require()
+    cw64 = (C + 63) // 64
+    with torch.cuda.device(x.device):
+        P = torch.empty((2, N, cw64, H // 2, W // 2), dtype=torch.int64, device=x.device)
+        M = torch.empty_like(P)
+        if N:
+            native.check(lib.bnn_hip_bn_act_pack_s2_f32(ctypes.byref(view), N, C, H, W, _ptr(bn_scale), _ptr(bn_shift),
+                                                        int(bool(relu)), P.data_ptr(), M.data_ptr(), _stream(x.device)),
+                         "bnn_hip_bn_act_pack_s2_f32")
+    return tuple(PackedAct(P[k], M[k], (N, C, H // 2, W // 2), bool(relu)) for k in range(2))
+
+
 def avgpool_pack(x: torch.Tensor, k: int, nonneg: bool = False) -> PackedAct:
     """``AvgPool2d(k, k, ceil_mode=True, count_include_pad=False)`` + sign, fused
     (shortcut branch of bnn/models/resnet.py:128-133).  ``nonneg``: the caller knows ``x >= 0``
@@ -655,6 +730,64 @@ def bconv2d_grouped_fused(a: PackedAct, w: PackedWeight, bias: Optional[torch.Te
                 w.wnz.data_ptr(), w.alpha.data_ptr(), _ptr(bias), _ptr(post_scale), _ptr(prelu), shuffle_groups,
                 None if residual is None else residual[n0:n1].data_ptr(), out[n0:n1].data_ptr(), _stream(dev)),
                 "bnn_hip_bconv2d_grouped_fused")
+    return out
+
+
+def bconv2d_grouped_node(a: PackedAct, w: PackedWeight, bias: Optional[torch.Tensor] = None,
+                         post_scale: Optional[torch.Tensor] = None, stride=1, padding=0, dilation=1, *,
+                         prelu: Optional[torch.Tensor] = None, shuffle_groups: int = 1,
+                         residual: Optional[torch.Tensor] = None, addend: Optional[torch.Tensor] = None,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``bconv2d_grouped_fused`` as one term of a cell node (``bnn_hip_bconv2d_grouped_node``):
+    ``out = (residual + shuffle(prelu(conv))) + addend``, three roundings, a missing operand skipped.  ``residual``,
+    ``addend`` and ``out`` are ``[N, O, Ho, Wo]`` and each may be a channel slice of a wider contiguous tensor
+    (``channel_view``) — ``out`` typically the node's slice of the cell output, which makes ``torch.cat`` disappear.
+    ``out`` may not share an element with an operand; slices of ONE tensor with disjoint channels are fine.  Returns
+    ``out`` (a new tensor when not given)."""
+    if not w.windowed:
+        raise native.NativeError("bnn_amd: bconv2d_grouped_node reads the layout of pack_weight_grouped, not of "
+                                 "pack_weight")
+    lib = native.require()
+    N, C, H, W = a.shape
+    O, Cg, KH, KW = w.shape
+    if Cg * w.groups != C:
+        raise native.NativeError(f"bnn_amd: grouped weight reads {Cg} x {w.groups} channels, the input has {C}")
+    shuffle_groups = int(shuffle_groups)
+    if shuffle_groups < 1 or O % shuffle_groups:
+        raise native.NativeError(f"bnn_amd: shuffle_groups={shuffle_groups} does not divide the {O} output channels")
+    d = _desc(a.shape, (O, C, KH, KW), stride, padding, dilation, 0)
+    ho, wo = conv_out_hw(H, W, KH, KW, stride, padding, dilation)
+    dev = a.P.device
+    bias = _per_channel(bias, O, "bias")
+    post_scale = _per_channel(post_scale, O, "post_scale")
+    prelu = _per_channel(prelu, O, "prelu")
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty((N, O, ho, wo), dtype=torch.float32, device=dev)
+        views = []
+        for t, what in ((residual, "residual"), (addend, "addend"), (out, "out")):
+            if t is None:
+                views.append(None)
+                continue
+            if tuple(t.shape) != (N, O, ho, wo):
+                raise native.NativeError(f"bnn_amd: {what} shape {tuple(t.shape)} != output {(N, O, ho, wo)}")
+            views.append(channel_view(t, what))
+        if N == 0:
+            return out
+        c_max = max(v[2] for v in views if v is not None)
+        step = fused_launch_images(N, C, H, W, O, (KH, KW), stride, padding, dilation, c_max)
+
+        def arg(v, n0, n1):
+            if v is None:
+                return None
+            return native.F32View(v[0][n0:n1].data_ptr(), v[1], v[2])
+        for n0, n1, dd in _desc_slices(d, step):
+            r, ad, o = (arg(v, n0, n1) for v in views)
+            native.check(lib.bnn_hip_bconv2d_grouped_node(
+                ctypes.byref(dd), w.groups, a.P[n0:n1].data_ptr(), a.M[n0:n1].data_ptr(), w.wbits.data_ptr(),
+                w.wnz.data_ptr(), w.alpha.data_ptr(), _ptr(bias), _ptr(post_scale), _ptr(prelu), shuffle_groups,
+                None if r is None else ctypes.byref(r), None if ad is None else ctypes.byref(ad), o.p, o.c_offset,
+                o.c_total, _stream(dev)), "bnn_hip_bconv2d_grouped_node")
     return out
 
 

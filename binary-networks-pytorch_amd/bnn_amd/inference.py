@@ -8,10 +8,11 @@ The implementation lives in four modules (round 5: this file used to hold all of
                                                                             inside one call)
     tails.py      per_layer_forward, library_tails, cached_fold,            the per-layer path's one-launch tails and
                   eval_tail / eval_stem / eval_head                         the switches of that tier
-    dispatch.py   no_model_fusion, BlockFusion, OpFusion, AutoFusion,       what ``block(x)`` / ``op(x)`` / ``model(x)``
-                  auto_fusion, auto_forward, install_auto_fusion,           dispatch to by themselves (the drop-in tiers)
-                  optimize_for_inference
-    cellops.py    FusedCellOp                                               a BATS cell operation in two launches
+    dispatch.py   no_model_fusion, no_cell_fusion, BlockFusion, OpFusion,   what ``block(x)`` / ``op(x)`` / ``cell(s0, s1)``
+                  CellFusion, AutoFusion, auto_fusion, auto_forward,        / ``model(x)`` dispatch to by themselves (the
+                  install_auto_fusion, optimize_for_inference               drop-in tiers)
+    cellops.py    FusedCellOp, FusedCell                                    a BATS cell operation in two launches; a
+                                                                            whole cell with its adds and its concat in them
 
 ``from bnn_amd.inference import FusedResNet`` etc. keep working; module-level state (``_LIBRARY_TAILS`` ...) is read
 through to the module that owns it.
@@ -22,10 +23,10 @@ from . import dispatch as _dispatch
 from . import executor as _executor
 from . import pipeline as _pipeline
 from . import tails as _tails
-from .cellops import FusedCellOp  # noqa: F401
-from .dispatch import (AutoFusion, BlockFusion, OpFusion, auto_block_forward, auto_forward, auto_fusion,  # noqa: F401
-                       auto_op_forward, install_auto_fusion, no_model_fusion, optimize_for_inference,
-                       uninstall_auto_fusion)
+from .cellops import FusedCell, FusedCellOp  # noqa: F401
+from .dispatch import (AutoFusion, BlockFusion, CellFusion, OpFusion, auto_block_forward,  # noqa: F401
+                       auto_cell_forward, auto_forward, auto_fusion, auto_op_forward, install_auto_fusion,
+                       no_cell_fusion, no_model_fusion, optimize_for_inference, uninstall_auto_fusion)
 from .executor import (FusedBlocks, FusedResNet, FusionError, fold_bn, is_native_model, resnet_shaped,  # noqa: F401
                        tap_binary_inputs)
 from .pipeline import STREAM_PROBE_LOG, PipelinedInference, TwoHalves, concurrent_streams  # noqa: F401

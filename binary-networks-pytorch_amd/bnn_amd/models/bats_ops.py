@@ -1,5 +1,6 @@
-"""The BATS cell operations built on grouped binary convolutions (``bnn/models/layers/bats_ops.py:20-30,
-78-173``): ``SepConv``, ``DilConv`` and ``ReLUConvBN``.
+"""The BATS cell operations built on grouped binary convolutions (``bnn/models/layers/bats_ops.py``):
+``SepConv``, ``DilConv`` and ``ReLUConvBN``, and what a cell needs around them — ``FactorizedReduce``, ``Zero``,
+``drop_path``, ``Genotype`` / ``PRIMITIVES`` / ``OPS``.
 
 Plain float ``nn.Module`` graphs, like ``blocks.py``: the ``nn.Conv2d`` inside becomes a binary layer only after
 ``prepare_binary_model``.  Constructor signatures, attribute names and forward order equal the reference's, so
@@ -13,8 +14,15 @@ and, evaluated for inference on a HIP device, first offers itself to the cell-op
 """
 from __future__ import annotations
 
+from collections import namedtuple
+
 import torch
 import torch.nn as nn
+
+Genotype = namedtuple("Genotype", "normal normal_concat reduce reduce_concat")
+
+PRIMITIVES = ["none", "max_pool_3x3", "avg_pool_3x3", "skip_connect", "sep_conv_3x3", "sep_conv_5x5", "dil_conv_3x3",
+              "dil_conv_5x5"]
 
 
 def channel_shuffle(x: torch.Tensor, groups: int) -> torch.Tensor:
@@ -89,3 +97,67 @@ class ReLUConvBN(_CellOp):
     def _forward(self, x: torch.Tensor) -> torch.Tensor:
         y = self.op(x)
         return x + y if self.skip and self.stride == 1 and self.C_in == self.C_out else y
+
+
+class Zero(nn.Module):
+    """The ``none`` primitive: zeros of the input's shape, ``H`` and ``W`` floor-divided by the stride   (reference:
+    ``bats_ops.py:176-187``; fp32 there whatever the input's dtype, the same here)."""
+
+    def __init__(self, stride: int) -> None:
+        super().__init__()
+        self.stride = stride
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        n, c, h, w = x.size()
+        return torch.zeros(n, c, h // self.stride, w // self.stride, dtype=torch.float32, device=x.device)
+
+
+class FactorizedReduce(nn.Module):
+    """BN - two 1x1 stride-2 convolutions, on the pixels ``(2i, 2j)`` and ``(2i+1, 2j+1)`` - concat - PReLU   (reference:
+    ``bats_ops.py:190-209``).  ``H`` and ``W`` must be even for the two halves to have one shape."""
+
+    def __init__(self, C_in: int, C_out: int, affine: bool = True) -> None:
+        super().__init__()
+        assert C_out % 2 == 0
+        self.activation = nn.PReLU(num_parameters=C_out)
+        self.conv_1 = nn.Sequential(nn.Conv2d(C_in, C_out // 2, 1, stride=2, padding=0, bias=False))
+        self.conv_2 = nn.Sequential(nn.Conv2d(C_in, C_out // 2, 1, stride=2, padding=0, bias=False))
+        self.bn = nn.BatchNorm2d(C_in, affine=affine)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        x = self.bn(x)
+        out = torch.cat([self.conv_1(x), self.conv_2(x[:, :, 1:, 1:])], dim=1)
+        return self.activation(out)
+
+
+def drop_path(x: torch.Tensor, drop_prob: float) -> torch.Tensor:
+    """Drop whole samples of a branch with probability ``drop_prob`` and rescale the kept ones, in place: a Bernoulli
+    mask of shape ``[N, 1, 1, 1]``.  The reference's version (``bats_ops.py:33-39``) builds the mask with
+    ``torch.tensor(x.size(0), 1, 1, 1)``, which raises a ``TypeError``; this one does what that line means.  Only
+    ``Cell.forward`` in training mode calls it."""
+    if drop_prob > 0.:
+        keep_prob = 1. - drop_prob
+        mask = torch.empty(x.size(0), 1, 1, 1, dtype=x.dtype, device=x.device).bernoulli_(keep_prob)
+        x.div_(keep_prob)
+        x.mul_(mask)
+    return x
+
+
+# primitive name -> constructor(C, stride, affine, skip, groups)   (reference: ``bats_ops.py:41-52``; its 'sep_conv_7x7'
+# and 'conv_7x1_1x7' / FactorizedConv entries are not provided: DESIGN.md section 7)
+OPS = {
+    "none": lambda C, stride, affine, skip, groups: Zero(stride),
+    "avg_pool_3x3": lambda C, stride, affine, skip, groups: nn.AvgPool2d(3, stride=stride, padding=1,
+                                                                           count_include_pad=False),
+    "max_pool_3x3": lambda C, stride, affine, skip, groups: nn.MaxPool2d(3, stride=stride, padding=1),
+    "skip_connect": lambda C, stride, affine, skip, groups: (nn.Identity() if stride == 1
+                                                             else FactorizedReduce(C, C, affine=affine)),
+    "sep_conv_3x3": lambda C, stride, affine, skip, groups: SepConv(C, C, 3, stride, 1, affine=affine, skip=skip,
+                                                                    groups=groups),
+    "sep_conv_5x5": lambda C, stride, affine, skip, groups: SepConv(C, C, 5, stride, 2, affine=affine, skip=skip,
+                                                                    groups=groups),
+    "dil_conv_3x3": lambda C, stride, affine, skip, groups: DilConv(C, C, 3, stride, 2, 2, affine=affine, skip=skip,
+                                                                    groups=groups),
+    "dil_conv_5x5": lambda C, stride, affine, skip, groups: DilConv(C, C, 5, stride, 4, 2, affine=affine, skip=skip,
+                                                                    groups=groups),
+}

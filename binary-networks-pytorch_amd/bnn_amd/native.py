@@ -95,6 +95,11 @@ class Epilogue(ctypes.Structure):
                 ("sc_C", ctypes.c_int32), ("sc_in_hw", ctypes.c_int32)]
 
 
+class F32View(ctypes.Structure):
+    """``bnn_hip_f32_view``: channels ``[c_offset, c_offset + C)`` of a contiguous fp32 ``[N, c_total, H, W]`` tensor."""
+    _fields_ = [("p", ctypes.c_void_p), ("c_offset", ctypes.c_int32), ("c_total", ctypes.c_int32)]
+
+
 EPI_RES_AFTER_ACT = 1
 EPI_PACK_BEFORE_RES = 2
 EPI_PACK_RELU = 4
@@ -116,6 +121,7 @@ _dp = ctypes.POINTER(ctypes.c_double)
 _conv_p = ctypes.POINTER(ConvDesc)
 _hblock_p = ctypes.POINTER(HBlockDesc)
 _wlayout_p = ctypes.POINTER(WLayout)
+_view_p = ctypes.POINTER(F32View)
 
 # Every symbol include/bnn_hip.h declares: name -> (restype, argtypes).  load() resolves and declares from this table,
 # so a symbol cannot be exported without its prototype (an undeclared one would pass 64-bit pointers as C ints).
@@ -131,6 +137,8 @@ _PROTOTYPES = {
     "bnn_hip_pack_act_f16": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "bnn_hip_pack_act_ste_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "bnn_hip_bn_act_pack_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "bnn_hip_bn_act_pack_multi_f32": (_i, [_view_p, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "bnn_hip_bn_act_pack_s2_f32": (_i, [_view_p, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "bnn_hip_avgpool_pack_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "bnn_hip_avgpool2_bn_pack2_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "bnn_hip_orpool_packed": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
@@ -150,6 +158,7 @@ _PROTOTYPES = {
     "bnn_hip_bconv2d": (_i, [_conv_p] + [_vp] * 9),
     "bnn_hip_bconv2d_grouped": (_i, [_conv_p, _i] + [_vp] * 9),
     "bnn_hip_bconv2d_grouped_fused": (_i, [_conv_p, _i] + [_vp] * 8 + [_i] + [_vp] * 3),
+    "bnn_hip_bconv2d_grouped_node": (_i, [_conv_p, _i] + [_vp] * 8 + [_i, _view_p, _view_p, _vp, _i, _i, _vp]),
     "bnn_hip_bconv2d_fused": (_i, [_conv_p] + [_vp] * 4 + [ctypes.POINTER(Epilogue), _vp]),
     "bnn_hip_shortcut_fold_supported": (_i, [_conv_p, _i]),
     "bnn_hip_bconv2d_dot": (_i, [_conv_p] + [_vp] * 6),

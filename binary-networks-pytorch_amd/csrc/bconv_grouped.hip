@@ -115,15 +115,29 @@ __global__ __launch_bounds__(64) void bconv_grouped_kernel(
 // queue behind them.
 // PRELU / RES are compile-time there: as run-time flags every channel's slope load, select and residual became a branch
 // region of its own with an `s_waitcnt vmcnt(0)` at each join.  The partial last block keeps run-time flags and guards.
-template <bool FULL, bool PRELU = false, bool RES = false>
+//
+// A cell NODE (bnn_hip_bconv2d_grouped_node; bnn/models/bats.py:61-74: s = op1(h1) + op2(h2)) adds a second operand
+// and lets every fp32 tensor be a channel slice of a wider one:
+//     out[n, c_off + o', y, x] = (res[n, o', y, x] + v) + add[n, o', y, x]      three roundings
+// NodeViews carries what differs from `out`: e.res / nv.add point at channel 0 of their slices, and their per-lane bases
+// are n c_total hw + r with THEIR c_total.  VIEWS = false is the cell operation's epilogue as it was (res shares out's
+// layout, no addend): the same instructions.
+struct NodeViews {
+  const float* add;
+  unsigned res_lane, add_lane;  // BYTES
+};
+template <bool FULL, bool PRELU = false, bool RES = false, bool VIEWS = false, bool ADD = false>
 __device__ __forceinline__ void cell_epilogue(const Geo& g, const Pix& px, const int o0, const int (&dot)[kOCB],
-                                              const EpiArgs& e, const int sg, const int cpg) {
+                                              const EpiArgs& e, const int sg, const int cpg,
+                                              const NodeViews nv = NodeViews{}) {
 #pragma clang fp contract(off)
   using f2 = __attribute__((ext_vector_type(2))) float;
   const int hw = g.Ho * g.Wo;
   const unsigned lane_off = px.out_base * 4u;  // BYTES; host keeps N*c_tot*hw < 2^30
   const int f = g.flags;
   const bool hb = (f & EF_BIAS) != 0, hs = (f & EF_SCALE) != 0;
+  // the operands' own slices start at their channel 0: plane o' of them is choff[] less out's window offset
+  const unsigned res_lane = VIEWS ? nv.res_lane : lane_off, win = VIEWS ? (unsigned)g.c_off * (unsigned)hw * 4u : 0u;
   unsigned choff[kOCB];  // byte offset of plane o' (wave-uniform)
   {
     int q = o0 / cpg, r = o0 - q * cpg;
@@ -135,13 +149,18 @@ __device__ __forceinline__ void cell_epilogue(const Geo& g, const Pix& px, const
   }
   if constexpr (FULL) {
     // (the residual loads go out kResBatch channels at a time: all 32 at once cost 30 more VGPRs, a wave per SIMD less)
-    constexpr int kResBatch = 16;
+    // (with both operands, 8 + 8: the same number of loads in flight)
+    constexpr int kResBatch = (RES && ADD) ? 8 : 16;
 #pragma unroll
     for (int j0 = 0; j0 < kOCB; j0 += kResBatch) {
-      [[maybe_unused]] float resv[kResBatch];
+      [[maybe_unused]] float resv[kResBatch], addv[kResBatch];
       if constexpr (RES) {
 #pragma unroll
-        for (int j = 0; j < kResBatch; ++j) resv[j] = buf_ld(make_rsrc(e.res), lane_off, choff[j0 + j]);
+        for (int j = 0; j < kResBatch; ++j) resv[j] = buf_ld(make_rsrc(e.res), res_lane, choff[j0 + j] - win);
+      }
+      if constexpr (ADD) {
+#pragma unroll
+        for (int j = 0; j < kResBatch; ++j) addv[j] = buf_ld(make_rsrc(nv.add), nv.add_lane, choff[j0 + j] - win);
       }
 #pragma unroll
       for (int j = j0; j < j0 + kResBatch; j += 2) {
@@ -157,6 +176,7 @@ __device__ __forceinline__ void cell_epilogue(const Geo& g, const Pix& px, const
           y1 = (y1 >= 0.0f) ? y1 : n1;
         }
         if constexpr (RES) { y0 = resv[j - j0] + y0; y1 = resv[j - j0 + 1] + y1; }
+        if constexpr (ADD) { y0 = y0 + addv[j - j0]; y1 = y1 + addv[j - j0 + 1]; }
         buf_st(make_rsrc(e.out), lane_off, choff[j], y0);
         buf_st(make_rsrc(e.out), lane_off, choff[j + 1], y1);
       }
@@ -171,7 +191,10 @@ __device__ __forceinline__ void cell_epilogue(const Geo& g, const Pix& px, const
         float y = fmaf(e.alpha[o], (float)dot[j], hb ? e.bias[o] : 0.0f);
         if (hs) y *= e.scale[o];
         if (hp) y = (y >= 0.0f) ? y : e.prelu[o] * y;
-        if (hr) y = ld_off(reinterpret_cast<const float*>(reinterpret_cast<const char*>(e.res) + choff[j]), lane_off) + y;
+        if (hr) y = ld_off(reinterpret_cast<const float*>(reinterpret_cast<const char*>(e.res) + (choff[j] - win)), res_lane) + y;
+        if constexpr (VIEWS) {
+          if (nv.add) y = y + ld_off(reinterpret_cast<const float*>(reinterpret_cast<const char*>(nv.add) + (choff[j] - win)), nv.add_lane);
+        }
         st_off(reinterpret_cast<float*>(reinterpret_cast<char*>(outf) + choff[j]), lane_off, y);
       }
     }
@@ -198,6 +221,39 @@ __global__ __launch_bounds__(64) void bconv_grouped_cell_kernel(
   else if (hp) cell_epilogue<true, true, false>(g, px, o0, dotv, epi, sg, cpg);
   else if (hr) cell_epilogue<true, false, true>(g, px, o0, dotv, epi, sg, cpg);
   else cell_epilogue<true, false, false>(g, px, o0, dotv, epi, sg, cpg);
+}
+
+// The grouped convolution as one term of a cell node: the same main loop, the epilogue above with VIEWS.  res / add point
+// at the first element of their channel slices (capi.hip), ct_res / ct_add are the channel counts of the tensors around
+// them.  PRELU / RES / ADD are compile-time for whole blocks: eight straight-line epilogues, one taken per launch.
+template <bool FAST>
+__global__ __launch_bounds__(64) void bconv_grouped_node_kernel(
+    const uint32_t* __restrict__ P, const uint32_t* __restrict__ M, const uint32_t* __restrict__ W,
+    const uint32_t* __restrict__ Z, BNN_EPI_PARAMS, const float* __restrict__ add, const Geo g, const int Cg,
+    const int Og, const int S, const int sg, const int cpg, const int ct_res, const int ct_add) {
+  BNN_EPI_INIT;
+  const int ob = (int)(blockIdx.x / (unsigned)g.tiles);
+  const int tile = (int)blockIdx.x - ob * g.tiles;
+  const Pix px = decode_pixel<FAST>(g, tile * kWave + threadIdx.x);
+  int dotv[kOCB];
+  grouped_dots<FAST>(P, M, W, Z, g, px, ob, Cg, Og, S, dotv);
+  const int o0 = ob * kOCB, hw = g.Ho * g.Wo;
+  NodeViews nv;
+  nv.add = add;
+  nv.res_lane = (unsigned)(imul<FAST>(imul<FAST>(px.n, ct_res), hw) + px.r) * 4u;
+  nv.add_lane = (unsigned)(imul<FAST>(imul<FAST>(px.n, ct_add), hw) + px.r) * 4u;
+  if (o0 + kOCB > g.O) return cell_epilogue<false, false, false, true>(g, px, o0, dotv, epi, sg, cpg, nv);
+  const int v = ((g.flags & EF_PRELU) ? 4 : 0) | ((g.flags & EF_RES) ? 2 : 0) | (add ? 1 : 0);
+  switch (v) {
+    case 0: return cell_epilogue<true, false, false, true, false>(g, px, o0, dotv, epi, sg, cpg, nv);
+    case 1: return cell_epilogue<true, false, false, true, true>(g, px, o0, dotv, epi, sg, cpg, nv);
+    case 2: return cell_epilogue<true, false, true, true, false>(g, px, o0, dotv, epi, sg, cpg, nv);
+    case 3: return cell_epilogue<true, false, true, true, true>(g, px, o0, dotv, epi, sg, cpg, nv);
+    case 4: return cell_epilogue<true, true, false, true, false>(g, px, o0, dotv, epi, sg, cpg, nv);
+    case 5: return cell_epilogue<true, true, false, true, true>(g, px, o0, dotv, epi, sg, cpg, nv);
+    case 6: return cell_epilogue<true, true, true, true, false>(g, px, o0, dotv, epi, sg, cpg, nv);
+    default: return cell_epilogue<true, true, true, true, true>(g, px, o0, dotv, epi, sg, cpg, nv);
+  }
 }
 
 // p: geometry of the whole convolution (p.C = all input channels, p.cw32 = their words per pixel); S: words per tap of the
@@ -229,6 +285,25 @@ int launch_bconv_grouped_cell(const ConvP& p, int groups, int S, int shuffle_gro
   else
     hipLaunchKernelGGL((bconv_grouped_cell_kernel<false>), grid, dim3(kWave), 0, s, p.P, p.M, p.W, p.Z, BNN_EPI_ACTUALS,
                        g, Cg, Og, S, shuffle_groups, cpg);
+  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+}
+
+// The node launch: p.c_off / p.c_tot window `out`; p.res and `add` (either may be null) point at channel 0 of their
+// slices of [N, ct_res, Ho, Wo] / [N, ct_add, Ho, Wo] tensors.  capi.hip has checked everything launch_bconv_grouped_cell
+// needs, the three views' sizes, and that `out` overlaps neither operand.
+int launch_bconv_grouped_node(const ConvP& p, int groups, int S, int shuffle_groups, const float* add, int ct_res,
+                              int ct_add, hipStream_t s) {
+  const Geo g = make_geo(p);
+  const unsigned nb = (unsigned)((p.O + kOCB - 1) / kOCB);
+  const dim3 grid((unsigned)g.tiles * nb);
+  const int Cg = p.C / groups, Og = p.O / groups, cpg = p.O / shuffle_groups;
+  const long long lim = 1ll << 23;  // (decode_pixel<true>'s products, for the operands' image strides too)
+  if (small_indices(p) && (long long)p.N * ct_res < lim && (long long)p.N * ct_add < lim)
+    hipLaunchKernelGGL((bconv_grouped_node_kernel<true>), grid, dim3(kWave), 0, s, p.P, p.M, p.W, p.Z, BNN_EPI_ACTUALS,
+                       add, g, Cg, Og, S, shuffle_groups, cpg, ct_res, ct_add);
+  else
+    hipLaunchKernelGGL((bconv_grouped_node_kernel<false>), grid, dim3(kWave), 0, s, p.P, p.M, p.W, p.Z, BNN_EPI_ACTUALS,
+                       add, g, Cg, Og, S, shuffle_groups, cpg, ct_res, ct_add);
   return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
 }
 

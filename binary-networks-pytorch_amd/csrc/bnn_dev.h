@@ -118,6 +118,12 @@ int launch_pack_act_f16(const void* x, int N, int C, int H, int W, uint64_t* P, 
                         hipStream_t stream);
 int launch_bn_act_pack(const float* x, int N, int C, int H, int W, const float* bn_a, const float* bn_b,
                        int relu, uint64_t* P, uint64_t* M, hipStream_t stream);
+// the same from channels [c_off, c_off + C) of x [N, c_tot, H, W]: K plane sets [K][N][cw64][H][W] for K affines
+// (scale / shift [K][C]) from one read; and the two stride-2 phases FactorizedReduce reads, [2][N][cw64][H/2][W/2]
+int launch_bn_act_pack_multi(const float* x, int c_off, int c_tot, int N, int C, int H, int W, int K, const float* scale,
+                             const float* shift, int relu, uint64_t* P, uint64_t* M, hipStream_t stream);
+int launch_bn_act_pack_s2(const float* x, int c_off, int c_tot, int N, int C, int H, int W, const float* bn_a,
+                          const float* bn_b, int relu, uint64_t* P, uint64_t* M, hipStream_t stream);
 int launch_avgpool_pack(const float* x, int N, int C, int H, int W, int k, uint64_t* P, uint64_t* M,
                         hipStream_t stream);
 int launch_avgpool2_bn_pack2(const float* x, int N, int C, int H, int W, const float* a1, const float* b1, int relu1,
@@ -173,6 +179,10 @@ int launch_pack_weight_grouped(const float* w, int O, int Cg, int groups, int ce
 int launch_bconv_grouped(const ConvP& p, int groups, int S, hipStream_t s);
 // the same convolution with the cell-operation epilogue (PReLU p.prelu, channel_shuffle as a store index, skip p.res)
 int launch_bconv_grouped_cell(const ConvP& p, int groups, int S, int shuffle_groups, hipStream_t s);
+// one term of a cell node: out windowed by p.c_off / p.c_tot, p.res and `add` at channel 0 of their slices of tensors
+// with ct_res / ct_add channels
+int launch_bconv_grouped_node(const ConvP& p, int groups, int S, int shuffle_groups, const float* add, int ct_res,
+                              int ct_add, hipStream_t s);
 // bconv_fly.hip: the whole layer in one launch, activations (fp32, or fp16 when x_half) binarised on the fly into LDS.
 // p.P / p.M are unused; p.alpha / bias / scale / out as for launch_bconv.  `plan` may be null (default plan).
 bool fly_supported(const ConvP& p);

@@ -203,6 +203,28 @@ int check_pack(const void* x, size_t x_align, int N, int C, int H, int W, const 
   return BNN_HIP_OK;
 }
 
+// A channel-slice view (bnn_hip_f32_view) of C channels: pointer, window, and the whole [N, c_total, H, W] tensor within
+// `max_elems`.  *c_off / *c_tot receive the window with c_total == 0 resolved to C.
+int check_view(const bnn_hip_f32_view* v, int N, int C, long long hw, long long max_elems, int* c_off, int* c_tot) {
+  if (!v || !v->p || !aligned(v->p, 4) || v->c_offset < 0 || v->c_total < 0) return BNN_HIP_ERR_INVALID_ARG;
+  const int tot = v->c_total == 0 ? C : v->c_total;
+  if ((v->c_total == 0 && v->c_offset != 0) || (long long)v->c_offset + C > tot) return BNN_HIP_ERR_INVALID_ARG;
+  if (mulc(N, tot, hw) > max_elems) return BNN_HIP_ERR_TOO_LARGE;
+  *c_off = v->c_offset; *c_tot = tot;
+  return BNN_HIP_OK;
+}
+
+// Whether the channel slices [ao, ao + C) of a [N, at, hw] tensor at `a` and [bo, bo + C) of a [N, bt, hw] tensor at `b`
+// may share an element.  Disjoint: the whole tensors do not overlap, or they are ONE tensor (same base, same c_total)
+// and the channel intervals are disjoint.  Anything else (two bases inside one allocation) counts as overlapping.
+bool views_may_overlap(const void* a, int ao, int at, const void* b, int bo, int bt, int N, int C, long long hw) {
+  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+  const uintptr_t na = (uintptr_t)mulc(N, at, hw) * 4, nb = (uintptr_t)mulc(N, bt, hw) * 4;
+  if (pa + na <= pb || pb + nb <= pa) return false;
+  if (pa == pb && at == bt) return ao < bo + C && bo < ao + C;
+  return true;
+}
+
 // Output extent of the stem's convolution (7x7 / 2 / 3) along one dimension; of its MaxPool 3 / 2 / 1 too: apply twice.
 inline long long stem_out(long long v) { return (v - 1) / 2 + 1; }
 // The stem kernels address x and out through 32-bit buffer descriptors (range-checked loads are the zero padding,
@@ -332,6 +354,35 @@ int bnn_hip_bn_act_pack_f32(const float* x, int N, int C, int H, int W, const fl
   BNN_RANGE();
   return bnn::launch_bn_act_pack(x, N, C, H, W, bn_scale, bn_shift, relu, P, M,
                                  static_cast<hipStream_t>(stream));
+}
+
+int bnn_hip_bn_act_pack_multi_f32(const bnn_hip_f32_view* x, int N, int C, int H, int W, int K, const float* scale,
+                                  const float* shift, int relu, uint64_t* P, uint64_t* M, void* stream) {
+  if (!x || K < 1 || K > 4 || !scale || !shift) return BNN_HIP_ERR_INVALID_ARG;
+  const int st = check_pack(x->p, 4, N, C, H, W, P, M);
+  if (st != BNN_HIP_OK) return st;
+  int c_off = 0, c_tot = 0;
+  const int sv = check_view(x, N, C, mulc(H, W), kSat, &c_off, &c_tot);   // (the kernel indexes x in 64 bits)
+  if (sv != BNN_HIP_OK) return sv;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_bn_act_pack_multi(x->p, c_off, c_tot, N, C, H, W, K, scale, shift, relu, P, M,
+                                       static_cast<hipStream_t>(stream));
+}
+
+int bnn_hip_bn_act_pack_s2_f32(const bnn_hip_f32_view* x, int N, int C, int H, int W, const float* bn_scale,
+                               const float* bn_shift, int relu, uint64_t* P, uint64_t* M, void* stream) {
+  if (!x || (bn_scale == nullptr) != (bn_shift == nullptr)) return BNN_HIP_ERR_INVALID_ARG;
+  const int st = check_pack(x->p, 4, N, C, H, W, P, M);
+  if (st != BNN_HIP_OK) return st;
+  if (H % 2 != 0 || W % 2 != 0) return BNN_HIP_ERR_INVALID_ARG;
+  int c_off = 0, c_tot = 0;
+  const int sv = check_view(x, N, C, mulc(H, W), kSat, &c_off, &c_tot);
+  if (sv != BNN_HIP_OK) return sv;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_bn_act_pack_s2(x->p, c_off, c_tot, N, C, H, W, bn_scale, bn_shift, relu, P, M,
+                                    static_cast<hipStream_t>(stream));
 }
 
 int bnn_hip_avgpool_pack_f32(const float* x, int N, int C, int H, int W, int k, uint64_t* P,
@@ -656,6 +707,41 @@ int bnn_hip_bconv2d_grouped_fused(const bnn_hip_conv_desc* d, int groups, const 
   g_launches.fetch_add(1, std::memory_order_relaxed);
   BNN_RANGE();
   return bnn::launch_bconv_grouped_cell(p, groups, S, shuffle_groups, static_cast<hipStream_t>(stream));
+}
+
+int bnn_hip_bconv2d_grouped_node(const bnn_hip_conv_desc* d, int groups, const uint64_t* P, const uint64_t* M,
+                                 const uint32_t* wbits, const uint32_t* wnz, const float* alpha, const float* bias,
+                                 const float* post_scale, const float* prelu, int shuffle_groups,
+                                 const bnn_hip_f32_view* residual, const bnn_hip_f32_view* addend, float* out,
+                                 int out_c_offset, int out_c_total, void* stream) {
+  bnn::ConvP p = empty_convp();
+  int S = 0;
+  const int st = check_grouped(d, groups, P, M, wbits, wnz, alpha, bias, post_scale, out, &p, &S);
+  if (st != BNN_HIP_OK) return st;
+  if (!alpha) return BNN_HIP_ERR_INVALID_ARG;  // the epilogue works on the float value: no raw-dot form
+  if (shuffle_groups < 1 || d->O % shuffle_groups != 0) return BNN_HIP_ERR_INVALID_ARG;
+  const long long hw = mulc(p.Ho, p.Wo);
+  const bnn_hip_f32_view ov = {out, out_c_offset, out_c_total};
+  const int so = check_view(&ov, d->N, d->O, hw, kMaxConvElems, &p.c_off, &p.c_tot);
+  if (so != BNN_HIP_OK) return so;
+  // the operands: per-lane byte offsets of 32 bits like the output's, and no element shared with it (the kernel reads
+  // them through independent __restrict__ pointers, and the shuffle makes a wave store other planes than it loads)
+  const float* opnd[2] = {nullptr, nullptr};
+  int ct[2] = {d->O, d->O};
+  const bnn_hip_f32_view* views[2] = {residual, addend};
+  for (int i = 0; i < 2; ++i) {
+    if (!views[i]) continue;
+    int off = 0;
+    const int sv = check_view(views[i], d->N, d->O, hw, kMaxConvElems, &off, &ct[i]);
+    if (sv != BNN_HIP_OK) return sv;
+    if (views_may_overlap(out, p.c_off, p.c_tot, views[i]->p, off, ct[i], d->N, d->O, hw)) return BNN_HIP_ERR_INVALID_ARG;
+    opnd[i] = views[i]->p + (size_t)off * (size_t)hw;
+  }
+  p.prelu = prelu; p.res = opnd[0];
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_bconv_grouped_node(p, groups, S, shuffle_groups, opnd[1], ct[0], ct[1],
+                                        static_cast<hipStream_t>(stream));
 }
 
 int bnn_hip_bconv2d_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M,

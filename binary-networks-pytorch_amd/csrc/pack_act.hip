@@ -161,6 +161,169 @@ int launch_bn_act_pack(const float* x, int N, int C, int H, int W, const float* 
   return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
 }
 
+// K BatchNorm + sign() plane sets from ONE read of x (a BATS cell state that feeds K SepConv / DilConv operations, each
+// with a BatchNorm of its own): pack_act_kernel<VP, true> with K affines per loaded value — K fmaf and 2 K class tests.
+// x points at the first element of a channel-slice VIEW: channels [c_off, c_off + C) of [N, c_total, H, W], so the image
+// stride is c_total HW (img_stride) while channel planes stay HW apart.  Plane set k is [N][cw64][H][W] at
+// P + k set_stride, and holds the bits bn_act_pack writes for affine k.  A thread keeps 4 K VP plane words: VP = 4 only up
+// to K = 2 (32 words, as many as K = 4 at VP = 2).
+template <int VP, int K>
+__global__ __launch_bounds__(256) void pack_act_multi_kernel(const float* __restrict__ x, int C, int HW, size_t img_stride,
+                                                             long long npix, int cw64, uint64_t* __restrict__ P,
+                                                             uint64_t* __restrict__ M, size_t set_stride,
+                                                             const float* __restrict__ scale,
+                                                             const float* __restrict__ shift, int relu) {
+  using V = PixVec<float, VP>;
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long pix0 = t * VP;
+  if (pix0 >= npix) return;
+  const int g = blockIdx.y;
+  const int n = (int)(pix0 / HW);
+  const int r = (int)(pix0 - (long long)n * HW);
+  const float* xb = x + (size_t)n * img_stride + r;
+
+  uint32_t pw[K][2][VP], mw[K][2][VP];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+#pragma unroll
+      for (int v = 0; v < VP; ++v) { pw[k][h][v] = 0u; mw[k][h][v] = 0u; }
+    }
+    const int c0 = g * 64 + h * 32;
+    if (c0 + 32 <= C) {
+#pragma unroll 8
+      for (int b = 31; b >= 0; --b) {  // high -> low: shifting left leaves channel c0 + b in bit b
+        const V xv = load_once(reinterpret_cast<const V*>(xb + (size_t)(c0 + b) * HW));
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          const float ca = scale[k * C + c0 + b], cb = shift[k * C + c0 + b];
+#pragma unroll
+          for (int v = 0; v < VP; ++v) {
+            const float u = fmaf(xv.v[v], ca, cb);
+            pw[k][h][v] = (pw[k][h][v] << 1) | (is_pos(u) ? 1u : 0u);
+            mw[k][h][v] = (mw[k][h][v] << 1) | ((!relu && is_neg(u)) ? 1u : 0u);
+          }
+        }
+      }
+    } else {
+      for (int b = 0; b < 32 && c0 + b < C; ++b) {
+        const V xv = load_once(reinterpret_cast<const V*>(xb + (size_t)(c0 + b) * HW));
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          const float ca = scale[k * C + c0 + b], cb = shift[k * C + c0 + b];
+#pragma unroll
+          for (int v = 0; v < VP; ++v) {
+            const float u = fmaf(xv.v[v], ca, cb);
+            pw[k][h][v] |= (is_pos(u) ? 1u : 0u) << b;
+            mw[k][h][v] |= ((!relu && is_neg(u)) ? 1u : 0u) << b;
+          }
+        }
+      }
+    }
+  }
+  const size_t o = ((size_t)n * cw64 + g) * HW + r;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+#pragma unroll
+    for (int v = 0; v < VP; ++v) {
+      P[k * set_stride + o + v] = (uint64_t)pw[k][0][v] | ((uint64_t)pw[k][1][v] << 32);
+      M[k * set_stride + o + v] = (uint64_t)mw[k][0][v] | ((uint64_t)mw[k][1][v] << 32);
+    }
+  }
+}
+
+template <int K>
+static void launch_multi_k(const float* x0, int C, int HW, size_t img_stride, long long npix, int cw64, uint64_t* P,
+                           uint64_t* M, const float* scale, const float* shift, int relu, hipStream_t stream) {
+  // the vector width follows HW and the alignment of the VIEW's first element (every channel plane and image then
+  // starts on the same alignment: HW and c_total HW are multiples of the width)
+  const bool a16 = (reinterpret_cast<uintptr_t>(x0) & 15u) == 0, a8 = (reinterpret_cast<uintptr_t>(x0) & 7u) == 0;
+  const size_t set_stride = (size_t)npix * cw64;
+  auto grid = [&](long long nthr) { return dim3((unsigned)((nthr + 255) / 256), (unsigned)cw64); };
+  if (K <= 2 && HW % 4 == 0 && a16)
+    hipLaunchKernelGGL((pack_act_multi_kernel<4, K>), grid(npix / 4), dim3(256), 0, stream, x0, C, HW, img_stride, npix,
+                       cw64, P, M, set_stride, scale, shift, relu);
+  else if (HW % 2 == 0 && a8)
+    hipLaunchKernelGGL((pack_act_multi_kernel<2, K>), grid(npix / 2), dim3(256), 0, stream, x0, C, HW, img_stride, npix,
+                       cw64, P, M, set_stride, scale, shift, relu);
+  else
+    hipLaunchKernelGGL((pack_act_multi_kernel<1, K>), grid(npix), dim3(256), 0, stream, x0, C, HW, img_stride, npix, cw64,
+                       P, M, set_stride, scale, shift, relu);
+}
+
+// x: the tensor's base; the view is channels [c_off, c_off + C) of c_tot (capi.hip has checked it and 1 <= K <= 4).
+int launch_bn_act_pack_multi(const float* x, int c_off, int c_tot, int N, int C, int H, int W, int K, const float* scale,
+                             const float* shift, int relu, uint64_t* P, uint64_t* M, hipStream_t stream) {
+  const int HW = H * W;
+  const long long npix = (long long)N * HW;
+  const int cw64 = (C + 63) / 64;
+  const float* x0 = x + (size_t)c_off * HW;
+  const size_t img_stride = (size_t)c_tot * HW;
+  switch (K) {
+    case 1: launch_multi_k<1>(x0, C, HW, img_stride, npix, cw64, P, M, scale, shift, relu, stream); break;
+    case 2: launch_multi_k<2>(x0, C, HW, img_stride, npix, cw64, P, M, scale, shift, relu, stream); break;
+    case 3: launch_multi_k<3>(x0, C, HW, img_stride, npix, cw64, P, M, scale, shift, relu, stream); break;
+    default: launch_multi_k<4>(x0, C, HW, img_stride, npix, cw64, P, M, scale, shift, relu, stream); break;
+  }
+  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+}
+
+// The binarisation inside FactorizedReduce (bnn/models/layers/bats_ops.py:204-206: conv_1(bn(x)) at stride 2 and
+// conv_2(bn(x)[:, :, 1:, 1:]) at stride 2, both 1x1): the two convolutions read the pixels (2i, 2j) and (2i+1, 2j+1) of
+// bn(x) and nothing else.  One thread = one output pixel and one 64-channel group; per channel it loads those two values
+// (rows 2i and 2i+1 of the plane: every line of x is fetched once) and writes phase 0 / phase 1 as two plane sets
+// [2][N][cw64][H/2][W/2] with the bits bn_act_pack gives for x[:, :, ::2, ::2] and x[:, :, 1::2, 1::2].
+__global__ __launch_bounds__(256) void pack_act_s2_kernel(const float* __restrict__ x, int C, int W, int Ho, int Wo,
+                                                          size_t img_stride, long long npix, int cw64,
+                                                          uint64_t* __restrict__ P, uint64_t* __restrict__ M,
+                                                          size_t set_stride, const float* __restrict__ bn_a,
+                                                          const float* __restrict__ bn_b, int relu) {
+  const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (q >= npix) return;
+  const int g = blockIdx.y;
+  const int HWo = Ho * Wo;
+  const size_t HW = (size_t)4 * HWo;
+  const int n = (int)(q / HWo);
+  const int r = (int)(q - (long long)n * HWo);
+  const int i = r / Wo, j = r - i * Wo;
+  const float* xb = x + (size_t)n * img_stride + (size_t)(2 * i) * W + 2 * j;
+  uint32_t pw[2][2] = {{0u, 0u}, {0u, 0u}}, mw[2][2] = {{0u, 0u}, {0u, 0u}};  // [phase][half]
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int c0 = g * 64 + h * 32;
+    for (int b = 0; b < 32 && c0 + b < C; ++b) {
+      const float* xc = xb + (size_t)(c0 + b) * HW;
+      const float v[2] = {load_once(xc), load_once(xc + W + 1)};
+      const float ca = bn_a ? bn_a[c0 + b] : 1.0f, cb = bn_a ? bn_b[c0 + b] : 0.0f;
+#pragma unroll
+      for (int ph = 0; ph < 2; ++ph) {
+        const float u = bn_a ? fmaf(v[ph], ca, cb) : v[ph];
+        pw[ph][h] |= (is_pos(u) ? 1u : 0u) << b;
+        mw[ph][h] |= ((!relu && is_neg(u)) ? 1u : 0u) << b;
+      }
+    }
+  }
+  const size_t o = ((size_t)n * cw64 + g) * HWo + r;
+#pragma unroll
+  for (int ph = 0; ph < 2; ++ph) {
+    P[ph * set_stride + o] = (uint64_t)pw[ph][0] | ((uint64_t)pw[ph][1] << 32);
+    M[ph * set_stride + o] = (uint64_t)mw[ph][0] | ((uint64_t)mw[ph][1] << 32);
+  }
+}
+
+// H and W even (capi.hip has checked that and the view).
+int launch_bn_act_pack_s2(const float* x, int c_off, int c_tot, int N, int C, int H, int W, const float* bn_a,
+                          const float* bn_b, int relu, uint64_t* P, uint64_t* M, hipStream_t stream) {
+  const int Ho = H / 2, Wo = W / 2;
+  const long long npix = (long long)N * Ho * Wo;
+  const int cw64 = (C + 63) / 64;
+  const dim3 grid((unsigned)((npix + 255) / 256), (unsigned)cw64);
+  hipLaunchKernelGGL(pack_act_s2_kernel, grid, dim3(256), 0, stream, x + (size_t)c_off * H * W, C, W, Ho, Wo,
+                     (size_t)c_tot * H * W, npix, cw64, P, M, (size_t)npix * cw64, bn_a, bn_b, relu);
+  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+}
+
 // AvgPool2d(k, stride=k, ceil_mode=True, count_include_pad=False) + sign() in one pass: the
 // shortcut branch of a down-sampling stage (bnn/models/resnet.py:128-133).  The sign of an
 // average is the sign of the sum, so the divisor never matters and clipped windows at the

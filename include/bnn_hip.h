@@ -65,7 +65,9 @@ extern "C" {
  * + bnn_hip_avgpool2_bn_pack2_f32 (the pool in front of a pre-activation stage + both sign planes it feeds);
  * + bnn_hip_grouped_weight_layout, bnn_hip_pack_weight_grouped_f32, bnn_hip_bconv2d_grouped (grouped / depthwise
  * convolutions: additive entry points of ABI 15, no struct or signature changed); + bnn_hip_bconv2d_grouped_fused (the
- * same convolution with PReLU, channel shuffle and skip connection in its launch: additive too).
+ * same convolution with PReLU, channel shuffle and skip connection in its launch: additive too);
+ * + bnn_hip_f32_view, bnn_hip_bn_act_pack_multi_f32, bnn_hip_bn_act_pack_s2_f32, bnn_hip_bconv2d_grouped_node (a whole
+ * BATS cell as fused launches: additive as well).
  * ABI 14 (round 5): + bnn_hip_stem7x7_wgrad_f32 / bnn_hip_stem7x7_wgrad_workspace_bytes (weight gradient of the stem
  * convolution: the training backward of that layer); + bnn_hip_avgpool2x2_backward_f32, bnn_hip_xnor_grad_pack_weight_f32; + bnn_hip_avgpool_fc_ws_f32 / bnn_hip_avgpool_fc_workspace_bytes (the head as two streaming launches
  * through a workspace); + bnn_hip_stem7x7_conv_f32 (the stem's convolution alone: the training forward); the table of bnn_hip_sign_thresholds_f32 holds FOUR words per channel (was two) and kmax < 2^20.
@@ -488,6 +490,41 @@ int bnn_hip_bconv2d_grouped_fused(const bnn_hip_conv_desc* d, int groups, const 
                                   const uint32_t* wbits, const uint32_t* wnz, const float* alpha, const float* bias,
                                   const float* post_scale, const float* prelu, int shuffle_groups,
                                   const float* residual, float* out, void* stream);
+
+/* ---- A whole BATS cell (bnn/models/bats.py:9-83) as fused launches: additive entry points of ABI 15. ----
+ * A channel-slice view of a contiguous fp32 NCHW tensor: channels [c_offset, c_offset + C) of [N, c_total, H, W] that
+ * starts at p (C, N, H, W come from the call).  c_total == 0: the tensor is exactly the C channels used (c_offset must
+ * be 0).  p is 4-byte aligned.                                                                                          */
+typedef struct bnn_hip_f32_view {
+  const float* p;
+  int32_t c_offset;
+  int32_t c_total;
+} bnn_hip_f32_view;
+
+/* K BatchNorm + sign() plane sets from ONE read of x (a cell state that feeds K operations, each with its own
+ * BatchNorm): scale / shift are [K][C], 1 <= K <= 4; P / M are [K][N][ceil(C/64)][H][W] uint64.  Plane set k holds the
+ * bits of bnn_hip_bn_act_pack_f32 on a contiguous copy of the view with scale[k] / shift[k] (both required here).      */
+int bnn_hip_bn_act_pack_multi_f32(const bnn_hip_f32_view* x, int N, int C, int H, int W, int K, const float* scale,
+                                  const float* shift, int relu, uint64_t* P, uint64_t* M, void* stream);
+/* The binarisation inside FactorizedReduce (bats_ops.py:204-206): H and W even, one affine (or none: both NULL).
+ * P / M are [2][N][ceil(C/64)][H/2][W/2]: phase 0 holds the pixels (2i, 2j), phase 1 the pixels (2i+1, 2j+1) — the bits
+ * of bnn_hip_bn_act_pack_f32 on x[:, :, ::2, ::2] and on x[:, :, 1::2, 1::2] — from one pass over x.                    */
+int bnn_hip_bn_act_pack_s2_f32(const bnn_hip_f32_view* x, int N, int C, int H, int W, const float* bn_scale,
+                               const float* bn_shift, int relu, uint64_t* P, uint64_t* M, void* stream);
+/* bnn_hip_bconv2d_grouped_fused as one term of a cell node  s = op1(h1) + op2(h2)  that stores into its slice of the
+ * cell's concatenated output.  With v and o' as there:
+ *     out[n, out_c_offset + o', y, x] = (residual ? residual[n,o',y,x] + v : v) + (addend ? addend[n,o',y,x] : 0)
+ * three separately rounded fp32 operations (a missing operand is skipped, not added as zero).  `out` is channels
+ * [out_c_offset, out_c_offset + O) of a [N, out_c_total, Ho, Wo] tensor that starts at `out` (out_c_total == 0: exactly
+ * the O channels); residual / addend are views of O channels at the output resolution, each with a c_total of its own.
+ * `out` must not alias an operand.  Two views are disjoint when their whole tensors do not overlap, or when they have
+ * the same base pointer and c_total and their channel intervals are disjoint (a node reads one slice of the cell
+ * output and writes another).  Every tensor involved stays below 2^30 elements.                                        */
+int bnn_hip_bconv2d_grouped_node(const bnn_hip_conv_desc* d, int groups, const uint64_t* P, const uint64_t* M,
+                                 const uint32_t* wbits, const uint32_t* wnz, const float* alpha, const float* bias,
+                                 const float* post_scale, const float* prelu, int shuffle_groups,
+                                 const bnn_hip_f32_view* residual, const bnn_hip_f32_view* addend, float* out,
+                                 int out_c_offset, int out_c_total, void* stream);
 
 /* Binary fully-connected layer: x packed as [B][ceil(F/64)] planes (pack_act with
  * H=W=1, i.e. [B][ceil(F/64)] words), weight packed with KH=KW=1.  out: float32 [B,O].                         */

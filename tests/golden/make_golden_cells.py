@@ -1,0 +1,99 @@
+#!/usr/bin/env python3
+"""Generate tests/golden/cells.npz by running the REFERENCE implementation of the BATS cells and networks.
+
+Runs only where the reference package is importable; the test-suite and the GPU box use the committed ``cells.npz``.
+Stored: the reference's outputs, state_dict key lists, and per case the sign margin, the reference's own fp32-vs-fp64
+difference ``e_ref`` and the chosen salt (inputs and parameters come from cells_cases.py / gen.py).  The salt printed for
+a case must be the one committed in cells_cases.py; the script fails when it is not.
+
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_cells.py [--find]
+
+``--find`` only searches and prints the salts (for a new case) and writes nothing.
+"""
+from __future__ import annotations
+
+import copy
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+REFERENCE = os.environ.get("BNN_REFERENCE", "/root/reference")
+sys.dont_write_bytecode = True
+sys.path.insert(0, ROOT)
+sys.path.insert(0, REFERENCE)
+
+import torch  # noqa: E402
+
+import bnn  # the reference package  # noqa: E402
+from bnn.models import bats  # noqa: E402
+from bnn.ops import BasicInputBinarizer, XNORWeightBinarizer  # noqa: E402
+
+from tests.golden.cells_cases import (ALL_CASES, GROUPS, IMAGENET_ARGS, MARGIN_FACTOR, binary_inputs,  # noqa: E402
+                                      genotype, sign_margin)
+
+assert os.path.realpath(bnn.__file__).startswith(os.path.realpath(REFERENCE)), bnn.__file__
+torch.set_num_threads(8)
+MAX_SALT = 64
+
+
+def binarise(model):
+    cfg = bnn.BConfig(activation_pre_process=BasicInputBinarizer, activation_post_process=bnn.Identity,
+                      weight_pre_process=XNORWeightBinarizer)
+    return bnn.prepare_binary_model(model, cfg)
+
+
+def try_salt(case, salt):
+    """(out, keys, margin, e_ref) of the reference at this salt, or None when a sign() sits too close to 0."""
+    model = binarise(case.build(bats))
+    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in case.state(shapes, salt).items()})
+    model.eval()
+    x32 = tuple(torch.from_numpy(a) for a in case.inputs(salt))
+    model64 = copy.deepcopy(model).double()
+    with torch.no_grad():
+        out, seen32 = binary_inputs(model, case, x32)
+        _, seen64 = binary_inputs(model64, case, tuple(a.double() for a in x32))
+    assert len(seen32) == len(seen64) > 0
+    same = all(torch.equal(torch.sign(a).double(), torch.sign(b)) for a, b in zip(seen32, seen64))
+    e_ref = max(float((a.double() - b).abs().max()) for a, b in zip(seen32, seen64))
+    margin = sign_margin(seen32)
+    if not same or margin < MARGIN_FACTOR * e_ref:
+        print(f"   {case.name} salt {salt}: margin {margin:.3g} < {MARGIN_FACTOR:g} x e_ref {e_ref:.3g}"
+              f"{'' if same else ' (fp32 and fp64 disagree on a sign)'}: next salt")
+        return None
+    return out.numpy().copy(), list(shapes), margin, e_ref
+
+
+def main():
+    find = "--find" in sys.argv[1:]
+    blob = {}
+    for case in ALL_CASES:
+        for salt in range(MAX_SALT):
+            got = try_salt(case, salt)
+            if got is not None:
+                break
+        else:
+            raise SystemExit(f"{case.name}: no salt below {MAX_SALT} clears the margin")
+        out, keys, margin, e_ref = got
+        assert find or salt == case.salt, \
+            f"{case.name}: the first salt that clears the margin is {salt}; commit it in cells_cases.py"
+        blob[case.name + "/out"] = out
+        blob[case.name + "/keys"] = np.array(keys)
+        blob[case.name + "/margin"] = np.float64(margin)
+        blob[case.name + "/e_ref"] = np.float64(e_ref)
+        blob[case.name + "/salt"] = np.int64(salt)
+        print(f"cells {case.name:14s} salt={salt} out{out.shape} |max|={np.abs(out).max():.4f} margin={margin:.3g} "
+              f"e_ref={e_ref:.3g} keys={len(keys)}")
+    if find:
+        return
+    net = binarise(bats.BATSNetworkImageNet(*IMAGENET_ARGS, genotype(bats, "MIXED"), GROUPS))
+    blob["imagenet/keys"] = np.array(list(net.state_dict().keys()))
+    print(f"cells imagenet keys={len(blob['imagenet/keys'])}")
+    np.savez_compressed(os.path.join(HERE, "cells.npz"), **blob)
+
+
+if __name__ == "__main__":
+    main()

@@ -89,6 +89,19 @@ int launch_bn_act_pack(const float* x, int N, int C, int H, int W, const float* 
                        uint64_t* M, hipStream_t) {
   ++g_reached; check_planes(x, N, C, H, W, P, M, 4); REQUIRE((a == nullptr) == (b == nullptr)); return BNN_HIP_OK;
 }
+static void check_view_planes(const float* x, int c_off, int c_tot, int N, int C, int H, int W, const void* P, const void* M) {
+  check_planes(x, N, C, H, W, P, M, 4);
+  REQUIRE(c_off >= 0 && c_tot > 0 && (long long)c_off + C <= c_tot);
+}
+int launch_bn_act_pack_multi(const float* x, int c_off, int c_tot, int N, int C, int H, int W, int K, const float* a,
+                             const float* b, int, uint64_t* P, uint64_t* M, hipStream_t) {
+  ++g_reached; check_view_planes(x, c_off, c_tot, N, C, H, W, P, M); REQUIRE(K >= 1 && K <= 4 && a && b); return BNN_HIP_OK;
+}
+int launch_bn_act_pack_s2(const float* x, int c_off, int c_tot, int N, int C, int H, int W, const float* a, const float* b, int,
+                          uint64_t* P, uint64_t* M, hipStream_t) {
+  ++g_reached; check_view_planes(x, c_off, c_tot, N, C, H, W, P, M);
+  REQUIRE(H % 2 == 0 && W % 2 == 0 && (a == nullptr) == (b == nullptr)); return BNN_HIP_OK;
+}
 int launch_avgpool_pack(const float* x, int N, int C, int H, int W, int k, uint64_t* P, uint64_t* M, hipStream_t) {
   ++g_reached; REQUIRE(x && P && M && N > 0 && C > 0 && H > 0 && W > 0 && k > 0 && al(P, 8) && al(M, 8)); return BNN_HIP_OK;
 }
@@ -406,6 +419,37 @@ int launch_bconv_grouped_cell(const ConvP& p, int groups, int S, int shuffle_gro
   check_group_windows(p.O, p.C, groups, S, p.cw32);
   return BNN_HIP_OK;
 }
+// one term of a cell node: the three views stay inside the 32-bit byte offsets, and `out` shares no element with an operand
+int launch_bconv_grouped_node(const ConvP& p, int groups, int S, int shuffle_groups, const float* add, int ct_res, int ct_add,
+                              hipStream_t) {
+  ++g_reached;
+  check_convp(p);
+  REQUIRE((long long)p.N * p.H * p.Wd * ((p.C + 63) / 64) <= kPlaneWords);
+  REQUIRE(p.P && p.M && p.W && p.Z && p.out && al(p.P, 16) && al(p.M, 16) && al(p.W, 16) && al(p.Z, 16) && al(p.out, 4));
+  REQUIRE(!p.raw && p.alpha != nullptr);
+  REQUIRE(shuffle_groups >= 1 && p.O % shuffle_groups == 0);
+  const long long hw = (long long)p.Ho * p.Wo;
+  const uintptr_t o = reinterpret_cast<uintptr_t>(p.out), obytes = (uintptr_t)p.N * p.c_tot * hw * 4;
+  const float* opnd[2] = {p.res, add};
+  const int ct[2] = {ct_res, ct_add};
+  for (int i = 0; i < 2; ++i) {
+    if (!opnd[i]) continue;
+    REQUIRE(al(opnd[i], 4) && ct[i] >= p.O && (long long)p.N * ct[i] * hw <= kConvElems);
+    // the launcher receives channel 0 of the slice: either its image-0 run lies outside the output tensor, or inside it
+    // (one tensor, another channel interval) and then clear of the output window of every image
+    const uintptr_t a = reinterpret_cast<uintptr_t>(opnd[i]), run = (uintptr_t)p.O * hw * 4;
+    if (!(a + (uintptr_t)p.N * ct[i] * hw * 4 <= o || a >= o + obytes)) {
+      REQUIRE(ct[i] == p.c_tot && a >= o && (a - o) % (hw * 4) == 0);
+      const uintptr_t c0 = (a - o) / (hw * 4);                   // the operand's first channel in the shared tensor
+      REQUIRE(c0 + p.O <= (uintptr_t)p.c_tot && (c0 + p.O <= (uintptr_t)p.c_off || c0 >= (uintptr_t)(p.c_off + p.O)));
+      (void)run;
+    }
+  }
+  REQUIRE(!p.outP && !p.outM && !p.bn_a && !p.ds_P && !p.relu);
+  REQUIRE((long long)((p.O + 31) / 32 * 32) * p.KH * p.KW * S <= (1LL << 31) - 1);
+  check_group_windows(p.O, p.C, groups, S, p.cw32);
+  return BNN_HIP_OK;
+}
 int launch_probe_int_alu(int mode, int iters, double* r, double*, hipStream_t) { REQUIRE(iters > 0 && r); (void)mode; return BNN_HIP_OK; }
 int launch_probe_clock(int it, double* mhz, double*, hipStream_t) { REQUIRE(it > 0 && mhz); return BNN_HIP_OK; }
 }  // namespace bnn
@@ -443,6 +487,17 @@ int pick_groups(int C, int O) {
   const int v = g[rnd() % 6];
   return (C > 0 && O > 0 && C % v == 0 && O % v == 0) ? v : 1;
 }
+// a channel-slice view of C channels: mostly a valid window, sometimes anything; bases far apart or shared
+bnn_hip_f32_view pick_view(int C) {
+  static const uintptr_t kBases[] = {0, 0x10000, 0x10000, 0x10002, 0x40000000, 0x7fff0000fff0ull};
+  bnn_hip_f32_view v;
+  v.p = reinterpret_cast<const float*>(kBases[rnd() % (sizeof(kBases) / sizeof(uintptr_t))]);
+  const uint64_t r = rnd() % 8;
+  if (r == 0) { v.c_offset = pick_int(); v.c_total = pick_int(); }
+  else if (r == 1) { v.c_offset = 0; v.c_total = 0; }
+  else { v.c_offset = (int)(rnd() % 3) * (C > 0 && C < (1 << 20) ? C : 1); v.c_total = v.c_offset + (C > 0 && C < (1 << 20) ? C : 1) * (int)(1 + rnd() % 3); }
+  return v;
+}
 bool status_ok(int st) { return st <= 0 && st >= -5; }
 }  // namespace
 
@@ -454,7 +509,7 @@ int main(int argc, char** argv) {
   for (long it = 0; it < iters; ++it) {
     ++g_calls;
     int st = 0;
-    switch (rnd() % 48) {
+    switch (rnd() % 51) {
       case 0: { bnn_hip_conv_desc d = pick_desc();
         st = bnn_hip_bconv2d(rnd() % 16 ? &d : nullptr, pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<uint32_t>(),
                              pick_ptr<uint32_t>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), stream);
@@ -640,6 +695,30 @@ int main(int argc, char** argv) {
                                            pick_ptr<uint64_t>(), pick_ptr<uint32_t>(), pick_ptr<uint32_t>(),
                                            pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), sg,
                                            res, out, stream);
+        break; }
+      case 48: { const int C = pick_int(); const bnn_hip_f32_view x = pick_view(C);
+        st = bnn_hip_bn_act_pack_multi_f32(rnd() % 16 ? &x : nullptr, pick_int(), C, pick_int(), pick_int(),
+                                           rnd() % 4 ? 1 + (int)(rnd() % 4) : pick_int(), pick_ptr<float>(), pick_ptr<float>(),
+                                           pick_int(), pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), stream);
+        break; }
+      case 49: { const int C = pick_int(); const bnn_hip_f32_view x = pick_view(C);
+        const int H = rnd() % 4 ? 2 * (int)(1 + rnd() % 16) : pick_int(), W = rnd() % 4 ? 2 * (int)(1 + rnd() % 16) : pick_int();
+        st = bnn_hip_bn_act_pack_s2_f32(rnd() % 16 ? &x : nullptr, pick_int(), C, H, W, pick_ptr<float>(), pick_ptr<float>(),
+                                        pick_int(), pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), stream);
+        break; }
+      case 50: { bnn_hip_conv_desc d = pick_desc();
+        if (rnd() % 2) { d.O = d.C; }
+        const int sgs[] = {1, 1, 2, 4, 12};
+        const int sg = rnd() % 8 ? sgs[rnd() % 5] : pick_int();
+        // the views: often slices of ONE tensor (the cell output), disjoint or overlapping; else anything
+        bnn_hip_f32_view out = pick_view(d.O), res = pick_view(d.O), add = pick_view(d.O);
+        if (rnd() % 2) { res.p = out.p; res.c_total = out.c_total; }
+        if (rnd() % 2) { add.p = out.p; add.c_total = out.c_total; }
+        st = bnn_hip_bconv2d_grouped_node(rnd() % 16 ? &d : nullptr, pick_groups(d.C, d.O), pick_ptr<uint64_t>(),
+                                          pick_ptr<uint64_t>(), pick_ptr<uint32_t>(), pick_ptr<uint32_t>(), pick_ptr<float>(),
+                                          pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), sg,
+                                          rnd() % 3 ? &res : nullptr, rnd() % 3 ? &add : nullptr, const_cast<float*>(out.p),
+                                          out.c_offset, out.c_total, stream);
         break; }
       default: { bnn_hip_conv_desc d = pick_desc();
         (void)bnn_hip_shortcut_fold_supported(rnd() % 16 ? &d : nullptr, pick_int());
