@@ -18,14 +18,13 @@ launch stores into the node's channel slice of the cell output, so neither the a
 """
 from __future__ import annotations
 
-import itertools
 from typing import Optional
 
 import torch
 import torch.nn as nn
 
 from . import fastpath, hipops, native
-from .executor import FusionError, fold_bn
+from .executor import FusionError, fold_bn, param_signature
 
 CELL_OP_NAMES = ("SepConv", "DilConv", "ReLUConvBN")
 MAX_PACK_SETS = 4       # plane sets one bn_act_pack_multi launch writes (include/bnn_hip.h)
@@ -40,21 +39,59 @@ def _pair_of(v, what: str):
     raise FusionError(f"cell op: {what}={v!r} is not numeric")
 
 
-class FusedCellOp(nn.Module):
-    """Inference executor of one BATS cell operation.  Recognition is by structure — the class NAME must be one of
-    ``SepConv`` / ``DilConv`` / ``ReLUConvBN`` and ``module.op`` must be ``Sequential(BatchNorm2d, binary Conv2d,
-    PReLU)`` with ``stride`` / ``skip`` as those classes define them — so an instance of the reference's own classes,
-    handed over explicitly, works as well as one of ``bnn_amd.models``.  Anything else raises ``FusionError``.
+def _binary_plan(conv, what: str):
+    """The recipe of a binary convolution the HIP kernels cover, or ``FusionError`` (messages start with ``what``)."""
+    if not (isinstance(conv, nn.Conv2d) and hasattr(conv, "activation_pre_process")):
+        raise FusionError(f"{what} is not a binary Conv2d (run prepare_binary_model first)")
+    plan = fastpath._recognise(conv, conv.out_channels)
+    if plan is None:
+        raise FusionError(f"{what}: layer recipe is not BasicInputBinarizer + XNORWeightBinarizer "
+                          "(+ Identity | BasicScaleBinarizer)")
+    if conv.weight.dtype != torch.float32:
+        raise FusionError(f"{what}: only float32 modules are covered")
+    return plan
 
-    Derived data (folded BatchNorm, the PReLU slopes as a vector of ``O``, the packed weight) is keyed on the identity,
-    storage and version of every parameter and buffer and re-derived when one changes; writes through ``.data`` need
-    ``refresh()`` (or ``fastpath.invalidate(module)`` for the executor ``module(x)`` dispatches to)."""
+
+def _prelu_slopes(act: nn.PReLU, channels: int) -> torch.Tensor:
+    """The PReLU slopes as a vector of ``channels``: a snapshot, like the folded BatchNorm and the packed weight."""
+    slope = act.weight.detach().float().reshape(-1)
+    return (slope.expand(channels) if slope.numel() == 1 else slope).clone()
+
+
+class _Executor(nn.Module):
+    """What ``FusedCellOp`` and ``FusedCell`` share: derived data keyed on the identity, storage and version of every
+    parameter and buffer of ``model`` (``refresh()`` derives it and sets ``_sig``), and the test of an input."""
+    takes: str      # what the inputs must be, for the error message
 
     def __init__(self, module: nn.Module) -> None:
         super().__init__()
         self.model = module
         self._sig = None
         self.refresh()
+
+    def _unchanged(self) -> bool:
+        return self._sig is not None and not self.model.training and param_signature(self.model) == self._sig
+
+    def _check_inputs(self, *inputs) -> None:
+        for x in inputs:
+            if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
+                raise FusionError(f"{self.takes} on a HIP device")
+
+
+class FusedCellOp(_Executor):
+    """Inference executor of one BATS cell operation.  Recognition is by structure — the class NAME must be one of
+    ``SepConv`` / ``DilConv`` / ``ReLUConvBN`` and ``module.op`` must be ``Sequential(BatchNorm2d, binary Conv2d,
+    PReLU)`` with ``stride`` / ``skip`` as those classes define them — so an instance of the reference's own classes,
+    handed over explicitly, works as well as one of ``bnn_amd.models``.  Anything else raises ``FusionError``.
+
+    Derived data (folded BatchNorm, the launch arguments with the PReLU slopes as a vector of ``O``, the packed weight)
+    is keyed on the identity, storage and version of every parameter and buffer and re-derived when one changes; writes
+    through ``.data`` need ``refresh()`` (or ``fastpath.invalidate(module)`` for the executor ``module(x)`` dispatches to).
+
+    ``forward`` is ``conv(pack(x), x)``; a ``FusedCell`` runs the two steps apart (one pack for several operations) and
+    takes the convolution in its node form, ``conv_node``.  ``bn_a`` / ``bn_b`` are the folded BatchNorm constants the
+    pack applies, ``add_skip`` says whether the convolution launch adds ``x``."""
+    takes = "cell op: the input must be a float32 NCHW tensor"
 
     # ---- recognition ------------------------------------------------------------------------------------------------
     def _recognise(self) -> None:
@@ -73,13 +110,10 @@ class FusedCellOp(nn.Module):
             raise FusionError("FusedCellOp is inference-only: call .eval() first")
         if bn.running_mean is None or bn.running_var is None:
             raise FusionError("cell op: BatchNorm2d without running statistics normalises with batch statistics")
-        plan = fastpath._recognise(conv, conv.out_channels)
-        if plan is None:
-            raise FusionError("cell op: layer recipe is not BasicInputBinarizer + XNORWeightBinarizer "
-                              "(+ Identity | BasicScaleBinarizer)")
+        plan = _binary_plan(conv, "cell op")
         if isinstance(conv.padding, str) or conv.padding_mode != "zeros":
             raise FusionError(f"cell op: padding={conv.padding!r}, padding_mode={conv.padding_mode!r} is not covered")
-        if conv.weight.dtype != torch.float32 or bn.running_var.dtype != torch.float32:
+        if bn.running_var.dtype != torch.float32:
             raise FusionError("cell op: only float32 modules are covered")
         stride = _pair_of(getattr(m, "stride", None), "stride")
         if stride != tuple(conv.stride) or stride[0] != stride[1]:
@@ -92,60 +126,63 @@ class FusedCellOp(nn.Module):
         if kind == "ReLUConvBN":
             if conv.groups != 1 or getattr(m, "C_in", None) != C or getattr(m, "C_out", None) != O:
                 raise FusionError("cell op: ReLUConvBN with groups != 1 or C_in / C_out unlike its convolution")
-            self._add_skip = m.skip and stride[0] == 1 and C == O
+            self.add_skip = m.skip and stride[0] == 1 and C == O
             self._shuffle = 1
         else:
             if C != O or O % SHUFFLE_GROUPS or conv.groups < 2:
                 raise FusionError(f"cell op: {kind} needs C_in == C_out, a multiple of {SHUFFLE_GROUPS}, and groups > 1")
-            self._add_skip = m.skip and stride[0] == 1
+            self.add_skip = m.skip and stride[0] == 1
             self._shuffle = SHUFFLE_GROUPS
         self._plan = plan
         self._grouped = conv.groups != 1
 
     # ---- derived data -----------------------------------------------------------------------------------------------
-    def _signature(self):
-        return tuple((id(t), t.data_ptr(), t._version)
-                     for t in itertools.chain(self.model.parameters(), self.model.buffers()))
-
-    def _unchanged(self) -> bool:
-        return self._sig is not None and not self.model.training and self._signature() == self._sig
-
     def refresh(self) -> None:
         """Re-derive everything from the module's current parameters and buffers."""
         self._sig = None
         self._recognise()
         bn, conv, act = self.model.op
         fastpath.invalidate(self.model, executors=False)
-        self._bn_a, self._bn_b = fold_bn(bn)
-        O = conv.out_channels
-        slope = act.weight.detach().float().reshape(-1)
-        self._prelu = (slope.expand(O) if slope.numel() == 1 else slope).clone()     # a snapshot, like the other two
+        self.bn_a, self.bn_b = fold_bn(bn)
+        # what every form of the convolution launch takes besides planes, weight and skip: bias, post scale, geometry,
+        # PReLU slopes, and the shuffle groups or (ReLUConvBN: the dense convolution's own epilogue) the late residual
+        self._launch = dict(bias=fastpath._f32(conv.bias), post_scale=fastpath._f32(self._plan.scale), stride=conv.stride,
+                            padding=conv.padding, dilation=conv.dilation, prelu=_prelu_slopes(act, conv.out_channels),
+                            **({"shuffle_groups": self._shuffle} if self._grouped else {"residual_after_act": True}))
         self._weight: Optional[hipops.PackedWeight] = None
         if conv.weight.is_cuda:
             native.require()
             self._weight = fastpath.packed_weight(conv, self._plan)
-        self._sig = self._signature()
+        self._sig = param_signature(self.model)
 
-    # ---- forward ----------------------------------------------------------------------------------------------------
+    # ---- the two launches -------------------------------------------------------------------------------------------
+    def pack(self, x: torch.Tensor) -> hipops.PackedAct:
+        """``sign(BatchNorm(x))`` as bit planes (``bn_act_pack``)."""
+        return hipops.bn_act_pack(x, self.bn_a, self.bn_b, relu=False)
+
+    def conv(self, planes: hipops.PackedAct, x: torch.Tensor) -> torch.Tensor:
+        """The convolution launch on ``planes`` (of ``x``: ``pack(x)``, or its set of a ``bn_act_pack_multi``) with
+        PReLU, shuffle and skip in its epilogue: ``bconv2d_grouped_fused``, or ``bconv2d_fused`` for ``ReLUConvBN``."""
+        res = x if self.add_skip else None
+        if self._grouped:
+            return hipops.bconv2d_grouped_fused(planes, self._weight, residual=res, **self._launch)
+        return hipops.bconv2d_fused(planes, self._weight, residual=res, **self._launch)[0]
+
+    def conv_node(self, planes: hipops.PackedAct, x: torch.Tensor, addend: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``conv`` of a ``SepConv`` / ``DilConv`` as one term of a cell node (``bconv2d_grouped_node``): ``addend`` is
+        added in the epilogue and the result stored into ``out``; each may be missing."""
+        return hipops.bconv2d_grouped_node(planes, self._weight, residual=x if self.add_skip else None, addend=addend,
+                                           out=out, **self._launch)
+
     @torch.no_grad()
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
-            raise FusionError("cell op: the input must be a float32 NCHW tensor on a HIP device")
+        self._check_inputs(x)
         if not self._unchanged():
             self.refresh()
-        conv = self.model.op[1]
-        if self._weight is None or conv.weight.device != x.device:
+        if self._weight is None or self._weight.alpha.device != x.device:     # (packed from the current weight)
             raise FusionError("cell op: module and input live on different devices")
-        act = hipops.bn_act_pack(x, self._bn_a, self._bn_b, relu=False)
-        res = x if self._add_skip else None
-        if self._grouped:
-            y = hipops.bconv2d_grouped_fused(act, self._weight, fastpath._f32(conv.bias), fastpath._f32(self._plan.scale),
-                                             conv.stride, conv.padding, conv.dilation, prelu=self._prelu,
-                                             shuffle_groups=self._shuffle, residual=res)
-        else:       # ReLUConvBN: the dense convolution's own epilogue has PReLU and the late residual
-            y, _ = hipops.bconv2d_fused(act, self._weight, bias=conv.bias, post_scale=self._plan.scale,
-                                        prelu=self._prelu, residual=res, residual_after_act=True, stride=conv.stride,
-                                        padding=conv.padding, dilation=conv.dilation)
+        y = self.conv(self.pack(x), x)
         fastpath._bump("cell_op")
         return y
 
@@ -153,18 +190,6 @@ class FusedCellOp(nn.Module):
 def _stride_of(op: nn.Module) -> int:
     s = getattr(op, "stride", 1)
     return s[0] if isinstance(s, (tuple, list)) else s
-
-
-def _binary_plan(conv, what: str):
-    if not (isinstance(conv, nn.Conv2d) and hasattr(conv, "activation_pre_process")):
-        raise FusionError(f"{what} is not a binary Conv2d (run prepare_binary_model first)")
-    plan = fastpath._recognise(conv, conv.out_channels)
-    if plan is None:
-        raise FusionError(f"{what}: layer recipe is not BasicInputBinarizer + XNORWeightBinarizer "
-                          "(+ Identity | BasicScaleBinarizer)")
-    if conv.weight.dtype != torch.float32:
-        raise FusionError(f"{what}: only float32 modules are covered")
-    return plan
 
 
 class _Reduce:
@@ -192,8 +217,7 @@ class _Reduce:
             raise FusionError("FactorizedReduce: PReLU width does not fit the concatenated output")
         self.C_in, self.C_out = bn.num_features, 2 * half
         self.bn_a, self.bn_b = fold_bn(bn)
-        slope = act.weight.detach().float().reshape(-1)
-        slope = (slope.expand(self.C_out) if slope.numel() == 1 else slope).clone()
+        slope = _prelu_slopes(act, self.C_out)
         self.prelu = [slope[:half].contiguous(), slope[half:].contiguous()]
         self.weights = None
         if self.convs[0].weight.is_cuda:
@@ -211,7 +235,7 @@ class _Reduce:
                              prelu=self.prelu[k], out=out, out_c_offset=k * half)
 
 
-class FusedCell(nn.Module):
+class FusedCell(_Executor):
     """Inference executor of one BATS ``Cell`` at ``drop_prob = 0``: ``FusedCell(cell)(s0, s1)``.
 
     Recognition follows ``FusedCellOp`` — class names plus structure (``Cell`` with ``preprocess0`` / ``preprocess1`` /
@@ -226,12 +250,7 @@ class FusedCell(nn.Module):
 
     Derived data is keyed on the identity, storage and version of every parameter and buffer of the cell, like
     ``FusedCellOp``; writes through ``.data`` need ``refresh()`` (or ``fastpath.invalidate(cell)``)."""
-
-    def __init__(self, cell: nn.Module) -> None:
-        super().__init__()
-        self.model = cell
-        self._sig = None
-        self.refresh()
+    takes = "cell: the inputs must be float32 NCHW tensors"
 
     # ---- recognition and planning ---------------------------------------------------------------------------------
     def _kind(self, op: nn.Module) -> str:
@@ -294,10 +313,10 @@ class FusedCell(nn.Module):
         for j in range(n_states):
             users = [k for k in self._conv if idx[k] == j]
             chunks = [users[i:i + MAX_PACK_SETS] for i in range(0, len(users), MAX_PACK_SETS)]
-            self._packs[j] = [(ch, torch.stack([self._conv[k]._bn_a for k in ch]),
-                               torch.stack([self._conv[k]._bn_b for k in ch])) for ch in chunks]
+            self._packs[j] = [(ch, torch.stack([self._conv[k].bn_a for k in ch]),
+                               torch.stack([self._conv[k].bn_b for k in ch])) for ch in chunks]
         self._plan = self._make_plan()
-        self._sig = self._signature()
+        self._sig = param_signature(self.model)
 
     def _make_plan(self):
         """The steps of one forward as ``(kind, detail, run)``; ``run(env)`` works on ``env``: ``in`` (s0, s1), ``state``
@@ -312,9 +331,9 @@ class FusedCell(nn.Module):
         for i, pre in enumerate(self._pre):
             if isinstance(pre, FusedCellOp):
                 add("pack", {"op": f"preprocess{i}", "sets": 1},
-                    lambda env, i=i, pre=pre: env["planes"].__setitem__(
-                        ("pre", i), hipops.bn_act_pack(env["in"][i], pre._bn_a, pre._bn_b, relu=False)))
-                add("dense", {"op": f"preprocess{i}"}, lambda env, i=i, pre=pre: self._run_rcb(env, i, pre))
+                    lambda env, i=i, pre=pre: env["planes"].__setitem__(("pre", i), pre.pack(env["in"][i])))
+                add("dense", {"op": f"preprocess{i}"}, lambda env, i=i, pre=pre: env["state"].__setitem__(
+                    i, pre.conv(env["planes"][("pre", i)], env["in"][i])))
             else:
                 self._plan_reduce(add, f"preprocess{i}", pre, lambda env, i=i: env["in"][i],
                                   lambda env, y, i=i: env["state"].__setitem__(i, y))
@@ -399,28 +418,12 @@ class FusedCell(nn.Module):
         """The planned steps as ``(kind, detail)``, in execution order."""
         return [(kind, dict(detail)) for kind, detail, _ in self._plan if detail is not None]
 
-    # ---- derived data ---------------------------------------------------------------------------------------------
-    def _signature(self):
-        return tuple((id(t), t.data_ptr(), t._version)
-                     for t in itertools.chain(self.model.parameters(), self.model.buffers()))
-
-    def _unchanged(self) -> bool:
-        return self._sig is not None and not self.model.training and self._signature() == self._sig
-
     # ---- the steps ------------------------------------------------------------------------------------------------
     @staticmethod
     def _same(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
         if a.shape != b.shape:
             raise FusionError(f"cell: the two terms of a node have shapes {tuple(a.shape)} and {tuple(b.shape)}")
         return a
-
-    def _run_rcb(self, env, i: int, pre: FusedCellOp) -> None:
-        conv = pre.model.op[1]
-        x = env["in"][i]
-        y, _ = hipops.bconv2d_fused(env["planes"][("pre", i)], pre._weight, bias=conv.bias, post_scale=pre._plan.scale,
-                                    prelu=pre._prelu, residual=x if pre._add_skip else None, residual_after_act=True,
-                                    stride=conv.stride, padding=conv.padding, dilation=conv.dilation)
-        env["state"][i] = y
 
     def _alloc(self, env) -> None:
         """The cell output ``[N, len(concat) * C, H, W]`` at the nodes' resolution: every node state named in the concat
@@ -455,17 +458,12 @@ class FusedCell(nn.Module):
         for t in (addend, out):
             if t is not None and tuple(t.shape) != shape:
                 raise FusionError(f"cell: operation {k} gives {shape}, its node holds {tuple(t.shape)}")
-        return hipops.bconv2d_grouped_node(planes, e._weight, fastpath._f32(conv.bias), fastpath._f32(e._plan.scale),
-                                           conv.stride, conv.padding, conv.dilation, prelu=e._prelu,
-                                           shuffle_groups=e._shuffle, residual=x if e._add_skip else None,
-                                           addend=addend, out=out)
+        return e.conv_node(planes, x, addend, out)
 
     # ---- forward --------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def forward(self, s0: torch.Tensor, s1: torch.Tensor) -> torch.Tensor:
-        for x in (s0, s1):
-            if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
-                raise FusionError("cell: the inputs must be float32 NCHW tensors on a HIP device")
+        self._check_inputs(s0, s1)
         if s0.device != s1.device or s0.shape[0] != s1.shape[0]:
             raise FusionError("cell: the two inputs differ in device or batch size")
         if not self._unchanged():

@@ -1,12 +1,13 @@
 """What ``model(x)`` and ``block(x)`` dispatch to by themselves — the drop-in tiers: ``AutoFusion`` (whole model:
-the fused executor, as eager launches / stem launch + HIP graph / two halves in flight), ``BlockFusion`` (one residual
-block), ``OpFusion`` (one BATS cell operation), ``CellFusion`` (one whole BATS cell), and ``install_auto_fusion`` (the same dispatch for ResNets of other packages, from ``prepare_binary_model``).
+the fused executor, as eager launches / stem launch + HIP graph / two halves in flight), the three tiers of a module that
+fuses itself, stated once in ``_TierFusion`` — ``BlockFusion`` (one residual block), ``OpFusion`` (one BATS cell
+operation), ``CellFusion`` (one whole BATS cell) — and ``install_auto_fusion`` (the same dispatch for ResNets of other
+packages, from ``prepare_binary_model``).
 Reference call being served: ``outputs = net(inputs)`` (examples/cifar10.py:71,140-149)."""
 from __future__ import annotations
 
 import collections
 import contextlib
-import itertools
 import os
 import threading
 import warnings
@@ -19,7 +20,8 @@ import torch.nn as nn
 from . import fastpath, native
 from . import tails as _tails
 from .cellops import FusedCell, FusedCellOp
-from .executor import FusedBlocks, FusedResNet, FusionError, is_native_model, resnet_shaped, tap_binary_inputs
+from .executor import (FusedBlocks, FusedResNet, FusionError, inner_hooks, is_native_model, param_signature,
+                       resnet_shaped, tap_binary_inputs)
 from .pipeline import TwoHalves
 from .models.resnet import ResNet
 
@@ -40,138 +42,112 @@ def no_model_fusion():
         _NO_MODEL_FUSION -= 1
 
 
-class BlockFusion:
-    """The second tier of the drop-in dispatch: a residual block of ``bnn_amd.models`` (``BasicBlock``, ``Bottleneck``,
-    ``PreBasicBlock``, ``HBlock``) called on its own — inside a network that is not laid out like the reference's
-    ``ResNet`` (a CIFAR-style three-stage ResNet-20, a custom backbone), or behind a stem the whole-model executor does
-    not cover — evaluates itself as ``FusedBlocks([block])``: fp32 NCHW in -> ``pack_act`` -> the block's convolutions
-    with BatchNorm / activation / residual add in their epilogues (activations between them as bit planes) -> fp32 NCHW
-    out; 3 launches and 3 fp32 passes over HBM for a ``BasicBlock`` instead of 8 kernels and 13 passes.  Same conditions
-    as ``AutoFusion`` (eval, no autograd, fp32 on a HIP device, no hooks on inner modules, not a replica); one instance
-    per block in ``block.__dict__['_bnn_auto_block']``."""
+def _switched_on() -> bool:
+    """The switches every tier honours: not inside ``per_layer_forward()``, ``BNN_AMD_AUTOFUSE`` not 0, and no strict
+    weights (strict: nothing derived from the weights outlives a call)."""
+    return _tails._PER_LAYER == 0 and os.environ.get("BNN_AMD_AUTOFUSE", "1") != "0" and not fastpath.strict_weights()
+
+
+def _fusable_input(x) -> bool:
+    """What a tier hands to its executor: a float32 NCHW tensor on a HIP device, not empty."""
+    return (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and x.shape[0] != 0)
+
+
+class _TierFusion:
+    """A module of ``bnn_amd.models`` that evaluates ITSELF through a fused executor when called for inference on a HIP
+    device: the state behind ``module(x)``, one instance per module in ``module.__dict__[key]`` (not a sub-module:
+    ``state_dict`` and ``repr`` stay the reference's).  ``run(module, *inputs)`` returns the fused result, or ``None``
+    when the call has to take the module's own forward.  Same conditions as ``AutoFusion``: eval mode, no autograd, every
+    input fp32 NCHW on a HIP device and not empty, not a ``DataParallel`` replica, the shared switches, the library
+    loadable, no hooks on inner modules (they would not fire), module and input on one device; a ``FusionError`` is
+    remembered until the parameters change, and an executor whose run raises one is dropped.  A subclass names its
+    ``key`` and how to ``build`` its executor."""
+    key: str
+
+    @staticmethod
+    def build(module: nn.Module) -> nn.Module:
+        raise NotImplementedError
 
     def __init__(self) -> None:
-        self.engine: Optional["FusedBlocks"] = None
-        self.failed_sig = None
+        self.engine: Optional[nn.Module] = None
+        self.failed_sig = None          # parameter signature for which fusion was refused
         self.calls = {"fused": 0, "declined": 0}
         self.lock = threading.Lock()
 
-    def __deepcopy__(self, memo):
-        return BlockFusion()
+    def __deepcopy__(self, memo):       # copy.deepcopy(module): the copy derives its own executor
+        return type(self)()
 
-    def __reduce__(self):
-        return (BlockFusion, ())
+    def __reduce__(self):               # pickling / torch.save(module): derived data is not saved
+        return (type(self), ())
 
-    def run(self, block: nn.Module, x: torch.Tensor) -> Optional[torch.Tensor]:
-        if (block.training or torch.is_grad_enabled() or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4
-                or x.shape[0] == 0 or getattr(block, "_is_replica", False) or _tails._PER_LAYER
-                or os.environ.get("BNN_AMD_AUTOFUSE", "1") == "0" or fastpath.strict_weights() or not native.available()):
-            self.calls["declined"] += 1
-            return None
+    @classmethod
+    def of(cls, module: nn.Module) -> "_TierFusion":
+        """The module's state of this tier (created on first use)."""
+        st = module.__dict__.get(cls.key)
+        if st is None:
+            st = module.__dict__[cls.key] = cls()
+        return st
+
+    def _decline(self):
+        self.calls["declined"] += 1
+        return None
+
+    wanted = staticmethod(_switched_on)     # (a subclass may ask for more)
+
+    def run(self, module: nn.Module, *inputs: torch.Tensor) -> Optional[torch.Tensor]:
+        if (module.training or torch.is_grad_enabled() or not all(map(_fusable_input, inputs))
+                or getattr(module, "_is_replica", False) or not self.wanted() or not native.available()):
+            return self._decline()
         with self.lock:
             eng = self.engine
             # (inside a caller's own graph capture nothing may be built or re-derived: an executor that is ready runs —
             # its launches are plain kernels on the capturing stream — anything else falls to the per-layer path)
             if torch.cuda.is_current_stream_capturing() and (eng is None or not eng._unchanged()):
-                self.calls["declined"] += 1
-                return None
+                return self._decline()
             if eng is None:
-                sig = _param_signature(block)
+                sig = param_signature(module)
                 if self.failed_sig == sig:
-                    self.calls["declined"] += 1
-                    return None
+                    return self._decline()
                 try:
-                    seq = nn.Sequential(block)
-                    seq.training = False            # (a new container starts in training mode; the block is in eval mode)
-                    eng = self.engine = FusedBlocks(seq)
+                    eng = self.engine = self.build(module)
                 except FusionError:
                     self.failed_sig = sig
-                    self.calls["declined"] += 1
-                    return None
-            if AutoFusion._hooked(block) or next(block.parameters()).device != x.device:
-                self.calls["declined"] += 1
-                return None
+                    return self._decline()
+            if inner_hooks(module) or next(module.parameters()).device != inputs[0].device:
+                return self._decline()
         try:
-            y = eng(x)
-        except FusionError:
+            y = eng(*inputs)
+        except FusionError:     # e.g. an odd H or W in front of a FactorizedReduce: the module's own forward reports it
             with self.lock:
-                self.engine, self.failed_sig = None, _param_signature(block)
-            self.calls["declined"] += 1
-            return None
+                self.engine, self.failed_sig = None, param_signature(module)
+            return self._decline()
         self.calls["fused"] += 1
         return y
 
 
-def auto_block_forward(block: nn.Module, x: torch.Tensor) -> Optional[torch.Tensor]:
-    """Called at the top of the residual blocks' ``forward``: the fused block's output, or None -> its own forward."""
-    st = block.__dict__.get("_bnn_auto_block")
-    if st is None:
-        st = block.__dict__["_bnn_auto_block"] = BlockFusion()
-    return st.run(block, x)
+class BlockFusion(_TierFusion):
+    """The second tier of the drop-in dispatch: a residual block of ``bnn_amd.models`` (``BasicBlock``, ``Bottleneck``,
+    ``PreBasicBlock``, ``HBlock``) called on its own — inside a network that is not laid out like the reference's
+    ``ResNet`` (a CIFAR-style three-stage ResNet-20, a custom backbone), or behind a stem the whole-model executor does
+    not cover — evaluates itself as ``FusedBlocks([block])``: fp32 NCHW in -> ``pack_act`` -> the block's convolutions
+    with BatchNorm / activation / residual add in their epilogues (activations between them as bit planes) -> fp32 NCHW
+    out; 3 launches and 3 fp32 passes over HBM for a ``BasicBlock`` instead of 8 kernels and 13 passes."""
+    key = fastpath.BLOCK_KEY
+
+    @staticmethod
+    def build(block: nn.Module) -> FusedBlocks:
+        seq = nn.Sequential(block)
+        seq.training = False            # (a new container starts in training mode; the block is in eval mode)
+        return FusedBlocks(seq)
 
 
-class OpFusion:
-    """``BlockFusion`` for the BATS cell operations of ``bnn_amd.models`` (``SepConv``, ``DilConv``, ``ReLUConvBN``): an
-    operation called for inference on a HIP device evaluates itself as ``FusedCellOp(op)`` — ``bn_act_pack`` and one
-    convolution launch with PReLU, channel shuffle and skip in its epilogue, 2 launches and 3 fp32 passes over HBM
-    instead of 6 launches and about 11 passes.  Same conditions as ``BlockFusion``; one instance per operation in
-    ``op.__dict__['_bnn_auto_op']``."""
-
-    def __init__(self) -> None:
-        self.engine = None
-        self.failed_sig = None
-        self.calls = {"fused": 0, "declined": 0}
-        self.lock = threading.Lock()
-
-    def __deepcopy__(self, memo):
-        return OpFusion()
-
-    def __reduce__(self):
-        return (OpFusion, ())
-
-    def run(self, op: nn.Module, x: torch.Tensor) -> Optional[torch.Tensor]:
-        if (op.training or torch.is_grad_enabled() or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4
-                or x.shape[0] == 0 or getattr(op, "_is_replica", False) or _tails._PER_LAYER
-                or os.environ.get("BNN_AMD_AUTOFUSE", "1") == "0" or fastpath.strict_weights() or not native.available()):
-            self.calls["declined"] += 1
-            return None
-        with self.lock:
-            eng = self.engine
-            # (inside a caller's own graph capture nothing may be built or re-derived, as in BlockFusion.run)
-            if torch.cuda.is_current_stream_capturing() and (eng is None or not eng._unchanged()):
-                self.calls["declined"] += 1
-                return None
-            if eng is None:
-                sig = _param_signature(op)
-                if self.failed_sig == sig:
-                    self.calls["declined"] += 1
-                    return None
-                try:
-                    eng = self.engine = FusedCellOp(op)
-                except FusionError:
-                    self.failed_sig = sig
-                    self.calls["declined"] += 1
-                    return None
-            if AutoFusion._hooked(op) or next(op.parameters()).device != x.device:
-                self.calls["declined"] += 1
-                return None
-        try:
-            y = eng(x)
-        except FusionError:
-            with self.lock:
-                self.engine, self.failed_sig = None, _param_signature(op)
-            self.calls["declined"] += 1
-            return None
-        self.calls["fused"] += 1
-        return y
-
-
-def auto_op_forward(op: nn.Module, x: torch.Tensor) -> Optional[torch.Tensor]:
-    """Called at the top of the cell operations' ``forward``: the fused result, or None -> its own forward."""
-    st = op.__dict__.get("_bnn_auto_op")
-    if st is None:
-        st = op.__dict__["_bnn_auto_op"] = OpFusion()
-    return st.run(op, x)
+class OpFusion(_TierFusion):
+    """The tier of the BATS cell operations of ``bnn_amd.models`` (``SepConv``, ``DilConv``, ``ReLUConvBN``): an
+    operation evaluates itself as ``FusedCellOp(op)`` — ``bn_act_pack`` and one convolution launch with PReLU, channel
+    shuffle and skip in its epilogue, 2 launches and 3 fp32 passes over HBM instead of 6 launches and about 11 passes."""
+    key = fastpath.OP_KEY
+    build = FusedCellOp
 
 
 _NO_CELL_FUSION = 0
@@ -189,67 +165,31 @@ def no_cell_fusion():
         _NO_CELL_FUSION -= 1
 
 
-class CellFusion:
-    """``OpFusion`` one level up: a ``Cell`` of ``bnn_amd.models`` called for inference on a HIP device evaluates itself
-    as ``FusedCell(cell)`` — every state binarised once for all its consumers, each node's add and the concatenation in
-    the epilogue of a convolution launch.  Same conditions as ``OpFusion``, and ``no_cell_fusion()`` not active; one
-    instance per cell in ``cell.__dict__['_bnn_auto_cell']``."""
+class CellFusion(_TierFusion):
+    """``OpFusion`` one level up: a ``Cell`` of ``bnn_amd.models`` evaluates itself as ``FusedCell(cell)(s0, s1)`` —
+    every state binarised once for all its consumers, each node's add and the concatenation in the epilogue of a
+    convolution launch — unless ``no_cell_fusion()`` is active."""
+    key = fastpath.CELL_KEY
+    build = FusedCell
 
-    def __init__(self) -> None:
-        self.engine = None
-        self.failed_sig = None
-        self.calls = {"fused": 0, "declined": 0}
-        self.lock = threading.Lock()
+    @staticmethod
+    def wanted() -> bool:
+        return _NO_CELL_FUSION == 0 and _switched_on()
 
-    def __deepcopy__(self, memo):
-        return CellFusion()
 
-    def __reduce__(self):
-        return (CellFusion, ())
+def auto_block_forward(block: nn.Module, x: torch.Tensor) -> Optional[torch.Tensor]:
+    """Called at the top of the residual blocks' ``forward``: the fused block's output, or None -> its own forward."""
+    return BlockFusion.of(block).run(block, x)
 
-    def _decline(self):
-        self.calls["declined"] += 1
-        return None
 
-    def run(self, cell: nn.Module, s0: torch.Tensor, s1: torch.Tensor) -> Optional[torch.Tensor]:
-        if (cell.training or torch.is_grad_enabled() or _NO_CELL_FUSION or _tails._PER_LAYER
-                or any(not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4
-                       or x.shape[0] == 0 for x in (s0, s1))
-                or getattr(cell, "_is_replica", False) or os.environ.get("BNN_AMD_AUTOFUSE", "1") == "0"
-                or fastpath.strict_weights() or not native.available()):
-            return self._decline()
-        with self.lock:
-            eng = self.engine
-            # (inside a caller's own graph capture nothing may be built or re-derived, as in BlockFusion.run)
-            if torch.cuda.is_current_stream_capturing() and (eng is None or not eng._unchanged()):
-                return self._decline()
-            if eng is None:
-                sig = _param_signature(cell)
-                if self.failed_sig == sig:
-                    return self._decline()
-                try:
-                    eng = self.engine = FusedCell(cell)
-                except FusionError:
-                    self.failed_sig = sig
-                    return self._decline()
-            if AutoFusion._hooked(cell) or next(cell.parameters()).device != s0.device:
-                return self._decline()
-        try:
-            y = eng(s0, s1)
-        except FusionError:     # e.g. an odd H or W in front of a FactorizedReduce: the cell's own forward reports it
-            with self.lock:
-                self.engine, self.failed_sig = None, _param_signature(cell)
-            return self._decline()
-        self.calls["fused"] += 1
-        return y
+def auto_op_forward(op: nn.Module, x: torch.Tensor) -> Optional[torch.Tensor]:
+    """Called at the top of the cell operations' ``forward``: the fused result, or None -> its own forward."""
+    return OpFusion.of(op).run(op, x)
 
 
 def auto_cell_forward(cell: nn.Module, s0: torch.Tensor, s1: torch.Tensor) -> Optional[torch.Tensor]:
     """Called at the top of ``Cell.forward``: the fused cell's output, or None -> its own forward."""
-    st = cell.__dict__.get("_bnn_auto_cell")
-    if st is None:
-        st = cell.__dict__["_bnn_auto_cell"] = CellFusion()
-    return st.run(cell, s0, s1)
+    return CellFusion.of(cell).run(cell, s0, s1)
 
 
 class AutoFusion:
@@ -322,15 +262,7 @@ class AutoFusion:
 
     @staticmethod
     def enabled() -> bool:
-        return (_tails._PER_LAYER == 0 and _NO_MODEL_FUSION == 0 and os.environ.get("BNN_AMD_AUTOFUSE", "1") != "0"
-                and not fastpath.strict_weights())       # (strict: nothing derived from the weights outlives a call)
-
-    @staticmethod
-    def _hooked(model: nn.Module) -> bool:
-        import torch.nn.modules.module as _mm
-        if _mm._global_forward_hooks or _mm._global_forward_pre_hooks:
-            return True
-        return any(m._forward_hooks or m._forward_pre_hooks for m in model.modules() if m is not model)
+        return _NO_MODEL_FUSION == 0 and _switched_on()
 
     def _decline(self):
         self.calls["declined"] += 1
@@ -345,7 +277,7 @@ class AutoFusion:
             master = self.owner() if self.owner is not None else None
             if master is None or master is model:
                 return None
-            sig = _param_signature(master)
+            sig = param_signature(master)
             if self.failed_sig == sig:
                 return None
             ent = self.replica_engines.get(x.device)
@@ -363,7 +295,7 @@ class AutoFusion:
             return eng
         eng = self.engine
         if eng is None:
-            sig = _param_signature(model)
+            sig = param_signature(model)
             if self.failed_sig == sig:
                 return None
             try:
@@ -378,9 +310,8 @@ class AutoFusion:
         return eng
 
     def run(self, model: nn.Module, x: torch.Tensor) -> Optional[torch.Tensor]:
-        if (model.training or torch.is_grad_enabled() or not isinstance(x, torch.Tensor) or not x.is_cuda
-                or x.dtype != torch.float32 or x.dim() != 4 or x.shape[0] == 0
-                or not self.enabled() or not native.available()):
+        if (model.training or torch.is_grad_enabled() or not _fusable_input(x) or not self.enabled()
+                or not native.available()):
             return self._decline()
         try:
             with self.lock:     # lookup / build / verification / graph capture; the steady-state launches run outside
@@ -388,7 +319,7 @@ class AutoFusion:
                     return self._decline()
                 eng = self._engine_for(model, x)
                 if eng is None or eng.model.fc.weight.device != x.device or (
-                        eng.hooked() if eng.model is model else self._hooked(model)):
+                        eng.hooked() if eng.model is model else inner_hooks(model)):
                     return self._decline()
                 if torch.cuda.is_current_stream_capturing():
                     # the caller is capturing a HIP graph of its own around `net(x)`: no graph replay inside a capture, no
@@ -425,7 +356,7 @@ class AutoFusion:
             return eng.forward_fresh(x) if graph else eng(x)
         except FusionError as exc:      # e.g. parameters moved to the CPU since the executor was built
             with self.lock:
-                self.engine, self.failed_sig, self.reason = None, _param_signature(model), str(exc)
+                self.engine, self.failed_sig, self.reason = None, param_signature(model), str(exc)
                 self.replica_engines.clear()
                 self.halves.clear()
             return self._decline()
@@ -455,7 +386,7 @@ class AutoFusion:
         ok = all(e <= (self.VERIFY_TOL if eq else self.VERIFY_TOL_FLIPPED) for e, eq in zip(err, same)) and \
             2 * sum(same) >= n and set(own_state) == set(fused_state)
         if not ok:
-            self.engine, self.failed_sig = None, _param_signature(model)
+            self.engine, self.failed_sig = None, param_signature(model)
             self.reason = ("fused result differs from the model's own forward (relative logit error per image "
                            f"{[float('%.3g' % e) for e in err]}, same sign() results everywhere: {same})")
             warnings.warn(f"bnn_amd: {type(model).__name__}: {self.reason}; keeping the per-layer path",
@@ -488,10 +419,6 @@ def _sign_digest_planes(P: torch.Tensor, M: torch.Tensor, C: int) -> torch.Tenso
     for plane, sgn in ((P, 1), (M, -1)):      # (pad channels >= C are 0 in both planes: their weights never count)
         out += sgn * (((plane.unsqueeze(2) >> shifts) & 1) * w).sum((1, 2, 3, 4))
     return out
-
-
-def _param_signature(model: nn.Module):
-    return tuple((id(t), t.data_ptr(), t._version) for t in itertools.chain(model.parameters(), model.buffers()))
 
 
 def auto_fusion(model: nn.Module) -> AutoFusion:

@@ -31,6 +31,7 @@ from typing import List, Optional
 
 import torch
 import torch.nn as nn
+import torch.nn.modules.module as _mm
 
 from . import fastpath, hipops, native
 from .layers import Conv2d as BinaryConv2d
@@ -65,6 +66,23 @@ def fold_bn(bn: nn.BatchNorm2d):
     # fma(-mean, scale, bias): the product of two fp32 values is exact in fp64, one rounding to fp32 after the add
     shift = (beta.astype(np.float64) - mean.astype(np.float64) * scale.astype(np.float64)).astype(np.float32)
     return torch.from_numpy(scale).to(dev), torch.from_numpy(shift).to(dev)
+
+
+def param_signature(module: nn.Module):
+    """Changes whenever a parameter or buffer of ``module`` is replaced or written in place (optimizer step,
+    ``load_state_dict``, ``.to()``): what was derived from them must then be rebuilt."""
+    # a fresh walk every time: a Parameter that was REPLACED (setattr, a swapped sub-module) is a new object with
+    # its own storage, which a list captured at refresh() time would never see
+    return tuple((id(t), t.data_ptr(), t._version) for t in itertools.chain(module.parameters(), module.buffers()))
+
+
+def inner_hooks(module: nn.Module, mods=None) -> bool:
+    """Forward (pre-)hooks, global or on inner modules of ``module`` (``mods``: its ``modules()``, when the caller has
+    them collected): they would not fire in a fused executor."""
+    if _mm._global_forward_hooks or _mm._global_forward_pre_hooks:
+        return True
+    return any(m._forward_hooks or m._forward_pre_hooks
+               for m in (module.modules() if mods is None else mods) if m is not module)
 
 
 _TAP = None
@@ -270,7 +288,7 @@ class FusedResNet(nn.Module):
                 self._add_block(blk)
         self._link_hblocks()
         self._graph = None
-        self._sig = self._signature()
+        self._sig = param_signature(self.model)
 
     def _link_hblocks(self) -> None:
         """One-launch form of every hierarchical block that qualifies (csrc/hblock.hip): ReLU activations (all sign
@@ -664,16 +682,8 @@ class FusedResNet(nn.Module):
         c3.run(p, out_packed=False, out_c_offset=half + quarter, **late)
         return y, None
 
-    def _signature(self):
-        """Changes whenever a parameter or buffer of the wrapped model is replaced or written in place
-        (optimizer step, ``load_state_dict``, ``.to()``): the derived data must then be rebuilt."""
-        # a fresh walk every time: a Parameter that was REPLACED (setattr, a swapped sub-module) is a new object with
-        # its own storage, which a list captured at refresh() time would never see
-        return tuple((id(t), t.data_ptr(), t._version)
-                     for t in itertools.chain(self.model.parameters(), self.model.buffers()))
-
     def _slots(self):
-        """(module dict, name) of every parameter / buffer slot of the wrapped model in the order of ``_signature()``
+        """(module dict, name) of every parameter / buffer slot of the wrapped model in the order of ``param_signature``
         (all parameters in module order, then all buffers; shared tensors once), collected once per refresh: the
         per-call staleness check reads the slots directly instead of walking the module tree (a ``net(x)`` call at
         batch 32 is host-bound: the tree walks were most of its 0.27 ms)."""
@@ -689,11 +699,11 @@ class FusedResNet(nn.Module):
         return mods, slots
 
     def _unchanged(self) -> bool:
-        """Cheap form of ``self._signature() == self._sig``: same triples read through the cached slots (no tree walk,
-        early exit), plus the identity of every module's children (a swapped sub-module has other slots)."""
+        """Cheap form of ``param_signature(self.model) == self._sig``: same triples read through the cached slots (no
+        tree walk, early exit), plus the identity of every module's children (a swapped sub-module has other slots)."""
         cache = self.__dict__.get("_fast")
         if cache is None or cache[0] is not self._sig:
-            if self._signature() != self._sig:
+            if param_signature(self.model) != self._sig:
                 return False
             mods, slots = self._slots()
             aligned = tuple((id(d[k]), d[k].data_ptr(), d[k]._version) for d, k in slots) == self._sig
@@ -702,7 +712,7 @@ class FusedResNet(nn.Module):
             return True
         _, mods, slots, children = cache
         if slots is None:                                   # (an unusual module tree: keep the plain comparison)
-            return self._signature() == self._sig
+            return param_signature(self.model) == self._sig
         for (d, k), want in zip(slots, self._sig):
             t = d.get(k)
             if t is None or id(t) != want[0] or t._version != want[2] or t.data_ptr() != want[1]:
@@ -713,13 +723,9 @@ class FusedResNet(nn.Module):
         return True
 
     def hooked(self) -> bool:
-        """Forward (pre-)hooks on inner modules of the wrapped model (they would not fire in the fused executor)."""
-        import torch.nn.modules.module as _mm
-        if _mm._global_forward_hooks or _mm._global_forward_pre_hooks:
-            return True
+        """``inner_hooks`` of the wrapped model, over the module list cached by ``_unchanged``."""
         cache = self.__dict__.get("_fast")
-        mods = cache[1] if cache is not None and cache[0] is self._sig else list(self.model.modules())
-        return any(m._forward_hooks or m._forward_pre_hooks for m in mods if m is not self.model)
+        return inner_hooks(self.model, cache[1] if cache is not None and cache[0] is self._sig else None)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         self._check_current()
@@ -858,7 +864,7 @@ class FusedBlocks(FusedResNet):
             self._add_block(blk)
         self._link_hblocks()
         self._graph = None
-        self._sig = self._signature()
+        self._sig = param_signature(self.model)
 
     @torch.no_grad()
     def _forward_impl(self, x: torch.Tensor) -> torch.Tensor:

@@ -244,6 +244,18 @@ def _replica_packed_weight(layer, master, plan: Plan, fresh: bool = False) -> hi
     return pw
 
 
+# ``module.__dict__`` keys under which a residual block, a cell operation and a cell keep the state of their own fused
+# executor (dispatch.BlockFusion / OpFusion / CellFusion)
+BLOCK_KEY, OP_KEY, CELL_KEY = TIER_KEYS = ("_bnn_auto_block", "_bnn_auto_op", "_bnn_auto_cell")
+
+
+def drop_executor(m: nn.Module) -> None:
+    """Drop the fused executor ``m`` itself dispatches to (not those of its sub-modules): derived data goes with a
+    ``train()`` <-> ``eval()`` switch."""
+    for key in TIER_KEYS:
+        m.__dict__.pop(key, None)
+
+
 def invalidate(module: nn.Module, executors: bool = True) -> int:
     """Drop every cached packed weight under ``module`` (returns how many).  Needed after writing weights
     through ``.data`` (weight clipping ``p.data.clamp_(-1, 1)``, EMA swaps ``p.data.copy_(ema)``, hand-written
@@ -254,10 +266,8 @@ def invalidate(module: nn.Module, executors: bool = True) -> int:
         if m.__dict__.pop("_bnn_packed", None) is not None:
             n += 1
         m.__dict__.pop("_bnn_packed_replicas", None)
-        if executors:       # a residual block's own fused executor (dispatch.BlockFusion); an executor that re-derives
-            m.__dict__.pop("_bnn_auto_block", None)     # ITSELF (refresh) passes False: it may be that very object
-            m.__dict__.pop("_bnn_auto_op", None)        # a cell operation's executor (dispatch.OpFusion)
-            m.__dict__.pop("_bnn_auto_cell", None)      # a whole cell's executor (dispatch.CellFusion)
+        if executors:       # (an executor that re-derives ITSELF (refresh) passes False: it may be that very object)
+            drop_executor(m)
     from .tails import drop_derived                 # folded BatchNorms / transposed head weights of the per-layer tails
     drop_derived(module)
     return n

@@ -1,16 +1,18 @@
 """Fused inference for binary ResNets — facade.
 
-The implementation lives in four modules (round 5: this file used to hold all of it):
+The implementation lives in five modules (round 5: this file used to hold all of it):
 
-    executor.py   fold_bn, tap_binary_inputs, FusedResNet / FusedBlocks     the executors: 19 launches per ResNet-18
-                                                                            forward, eager or as HIP graphs
+    executor.py   fold_bn, tap_binary_inputs, FusedResNet / FusedBlocks,    the executors: 19 launches per ResNet-18
+                  param_signature, inner_hooks                              forward, eager or as HIP graphs; the tests
+                                                                            every executor and tier shares
     pipeline.py   concurrent_streams, PipelinedInference, TwoHalves         several batches in flight (across calls /
                                                                             inside one call)
     tails.py      per_layer_forward, library_tails, cached_fold,            the per-layer path's one-launch tails and
                   eval_tail / eval_stem / eval_head                         the switches of that tier
     dispatch.py   no_model_fusion, no_cell_fusion, BlockFusion, OpFusion,   what ``block(x)`` / ``op(x)`` / ``cell(s0, s1)``
                   CellFusion, AutoFusion, auto_fusion, auto_forward,        / ``model(x)`` dispatch to by themselves (the
-                  install_auto_fusion, optimize_for_inference               drop-in tiers)
+                  install_auto_fusion, optimize_for_inference               drop-in tiers; the three self-fusing ones
+                                                                            are one class, ``_TierFusion``)
     cellops.py    FusedCellOp, FusedCell                                    a BATS cell operation in two launches; a
                                                                             whole cell with its adds and its concat in them
 

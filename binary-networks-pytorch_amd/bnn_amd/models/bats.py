@@ -58,7 +58,8 @@ class Cell(nn.Module):
     def train(self, mode: bool = True):
         # train() <-> eval(): the executor's derived data goes with the mode (bats_ops.py: _CellOp.train)
         if bool(mode) != self.training:
-            self.__dict__.pop("_bnn_auto_cell", None)
+            from ..fastpath import drop_executor
+            drop_executor(self)
         return super().train(mode)
 
     def forward(self, s0: torch.Tensor, s1: torch.Tensor, drop_prob: float = 0.0) -> torch.Tensor:

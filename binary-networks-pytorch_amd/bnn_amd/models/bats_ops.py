@@ -54,7 +54,8 @@ class _CellOp(nn.Module):
     def train(self, mode: bool = True):
         # train() <-> eval(): the executor's derived data goes with the mode (models/blocks.py: _Residual.train)
         if bool(mode) != self.training:
-            self.__dict__.pop("_bnn_auto_op", None)
+            from ..fastpath import drop_executor
+            drop_executor(self)
         return super().train(mode)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:

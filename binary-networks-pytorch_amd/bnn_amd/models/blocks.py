@@ -78,8 +78,9 @@ class _Residual(nn.Module):
         # BatchNorms: `.data` writes made while training (clamps, EMA swaps) reach the first evaluation forward
         # (layers/_base.py: BinaryLayerMixin.train gives the same guarantee for the packed weights)
         if bool(mode) != self.training:
-            self.__dict__.pop("_bnn_auto_block", None)
+            from ..fastpath import drop_executor
             from ..tails import drop_derived
+            drop_executor(self)
             drop_derived(self)
         return super().train(mode)
 

@@ -24,8 +24,8 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "binary-networks-pytorch_amd")]
 import torch  # noqa: E402
 
 import bnn_amd as bnn  # noqa: E402
-from bnn_amd import fastpath, hipops, models, native  # noqa: E402
-from bnn_amd.inference import per_layer_forward  # noqa: E402
+from bnn_amd import fastpath, models, native  # noqa: E402
+from bnn_amd.inference import OpFusion, per_layer_forward  # noqa: E402
 from bnn_amd.ops import BasicInputBinarizer, XNORWeightBinarizer  # noqa: E402
 from tests.golden import gen  # noqa: E402
 
@@ -94,19 +94,13 @@ def main():
                 ref = op(x)
                 assert fastpath.stats()["cell_op"] == before + 1
             err = float((y - ref).abs().max() / ref.abs().max())
-            eng = op.__dict__["_bnn_auto_op"].engine
+            eng = OpFusion.of(op).engine
             conv = op.op[1]
-            act = hipops.bn_act_pack(x, eng._bn_a, eng._bn_b, relu=False)
-            res = x if eng._add_skip else None
-            if conv.groups != 1:
-                def kernel():
-                    return hipops.bconv2d_grouped_fused(act, eng._weight, None, None, conv.stride, conv.padding,
-                                                        conv.dilation, prelu=eng._prelu, shuffle_groups=eng._shuffle,
-                                                        residual=res)
-            else:
-                def kernel():
-                    return hipops.bconv2d_fused(act, eng._weight, prelu=eng._prelu, residual=res, residual_after_act=True,
-                                                stride=conv.stride, padding=conv.padding, dilation=conv.dilation)
+            act = eng.pack(x)
+            res = x if eng.add_skip else None
+
+            def kernel():
+                return eng.conv(act, x)
             t_fused = timed(lambda: op(x), args.iters, args.warmup)
             with per_layer_forward():
                 t_layer = timed(lambda: op(x), args.iters, args.warmup)
