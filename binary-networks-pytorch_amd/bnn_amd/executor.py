@@ -26,8 +26,8 @@ import collections
 import contextlib
 import itertools
 import os
-from dataclasses import dataclass
-from typing import List, Optional
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Tuple, Union
 
 import torch
 import torch.nn as nn
@@ -146,6 +146,75 @@ def _is_float_layer(conv: nn.Module) -> bool:
             and type(conv.activation_post_process).__name__ == "Identity")
 
 
+# ---- one record per entry of ``FusedResNet._blocks``; ``kind`` is what ``_run_blocks`` branches on.  (eq=False: blocks
+# are compared by identity.)  Fields behind "derived lazily" are caches: decided once, on first use ----------------------
+@dataclass(eq=False)
+class _Post:
+    """BasicBlock / Bottleneck: conv-BN-act ... conv-BN-(+id)-act."""
+    kind = "post"
+    convs: List[_Conv]
+    ds: Optional[_Conv] = None              # the binary shortcut convolution with its BatchNorm folded (_shortcut)
+    pool: int = 0                           # kernel of the AvgPool2d(ceil) in front of ``ds``
+    ds_float: Optional[nn.Module] = None    # a real-valued shortcut branch: runs as the torch modules it is
+    # derived lazily (_fold_applies)
+    fold_recipe: Optional[bool] = None      # the layers' recipes allow the shortcut inside the last convolution
+    fold_geo: Dict[Tuple[int, int, int], bool] = field(default_factory=dict)   # (images per launch, H, W) -> the kernel does
+
+
+@dataclass(eq=False)
+class _Pre:
+    """PreBasicBlock: BN-conv-act, BN-conv-act, (+id)."""
+    kind = "pre"
+    bn1: Tuple[torch.Tensor, torch.Tensor]  # (scale, shift) of fold_bn
+    bn2: Tuple[torch.Tensor, torch.Tensor]
+    convs: List[_Conv]
+    ds: Optional[_Conv] = None              # as in _Post
+    pool: int = 0
+    ds_float: Optional[nn.Module] = None
+
+
+@dataclass
+class _HGeo:
+    """What is decided per input geometry (N, H, W) of a hierarchical block with a one-launch form."""
+    ok: bool                                # a one-launch kernel covers the geometry (_hblock_ok)
+    cl: bool                                # ... in its channel-lane form (csrc/hblock_cl.hip)
+    sc: Optional[bool] = None               # the shortcut convolution inside the launch (_run_h); None: not asked yet
+    pooled: Union[None, bool, torch.Tensor] = None   # _pooled_form: None not asked yet, False no, else its constants
+
+
+@dataclass(eq=False)
+class _H:
+    """HBlock: three BN-act-conv stages, cat, (+id)."""
+    kind = "h"
+    planes: int
+    bn: List[Tuple[torch.Tensor, torch.Tensor]]     # bn1, bn2, bn3 folded
+    relu: List[bool]                        # _sign_through of act1, act2, act3
+    convs: List[_Conv]
+    ds_bn: Optional[Tuple[torch.Tensor, torch.Tensor]] = None   # shortcut: BatchNorm -> binary 1x1 (no BN behind it)
+    ds: Optional[_Conv] = None
+    # filled by _link_hblocks
+    hpack: Optional[hipops.HBlockPack] = None       # constants of the one-launch form; None: the block does not qualify
+    hsc: Optional[Tuple[torch.Tensor, torch.Tensor]] = None     # hblock_shortcut_pack of ``ds``: it runs inside the launch
+    geo: Dict[Tuple[int, int, int], _HGeo] = field(default_factory=dict)   # derived lazily, per (N, H, W)
+
+
+@dataclass(eq=False)
+class _Pool:
+    """``nn.AvgPool2d`` in front of a stage of hierarchical blocks."""
+    kind = "pool"
+    mod: nn.Module
+
+
+@dataclass
+class _Handoff:
+    """Travels next to ``(t, packed)`` when ``packed`` is NOT ``sign(t)``: a launch wrote the input planes of ``owner``'s
+    first binary convolution — ``owner``'s bn1 (and ReLU) already applied — and, in ``ds``, the planes of ``owner``'s
+    shortcut BatchNorm when it wrote those too.  Only ``owner`` may read them (``_run_h`` / ``_run_pre`` test for it and
+    pack again otherwise; every other reader of ``packed`` asserts that there is no hand-off)."""
+    owner: Union[_Pre, _H]
+    ds: Optional[hipops.PackedAct] = None
+
+
 _BLOCK_KINDS = {"BasicBlock": BasicBlock, "PreBasicBlock": PreBasicBlock, "Bottleneck": Bottleneck, "HBlock": HBlock}
 _BLOCK_ATTRS = {BasicBlock: ("conv1", "bn1", "act1", "conv2", "bn2", "act2", "downsample"),
                 PreBasicBlock: ("conv1", "bn1", "act1", "conv2", "bn2", "act2", "downsample"),
@@ -215,10 +284,8 @@ class FusedResNet(nn.Module):
         # a down-sampling block's shortcut conv (AvgPool -> binary 1x1 -> BN) computed inside its last conv
         self.fold_shortcut = fold_shortcut
         self._side = {}
-        if not resnet_shaped(model):
-            raise FusionError("FusedResNet covers ResNets laid out like bnn.models.resnet.ResNet")
         self.model = model
-        self._blocks: List[dict] = []
+        self._blocks: List[Union[_Post, _Pre, _H, _Pool]] = []
         self._graph = None
         self._split = collections.OrderedDict()   # (input shape, stream) -> _Split (forward_fresh)
         self.refresh()
@@ -250,8 +317,10 @@ class FusedResNet(nn.Module):
         """(Re)derive packed weights and folded BN constants from the wrapped model.  Runs by itself when a
         parameter/buffer was replaced or written in place (version counters); call it by hand after writes
         through ``.data`` (they bypass the counters), then ``capture`` again if a graph was captured."""
-        native.require()
         m = self.model
+        if not resnet_shaped(m):
+            raise FusionError("FusedResNet covers ResNets laid out like bnn.models.resnet.ResNet")
+        native.require()
         fastpath.invalidate(m, executors=False)
         if m.training:
             raise FusionError("FusedResNet is inference-only: call model.eval() first")
@@ -294,66 +363,62 @@ class FusedResNet(nn.Module):
         """One-launch form of every hierarchical block that qualifies (csrc/hblock.hip): ReLU activations (all sign
         planes non-negative), bias-free 3x3 / stride 1 / padding 1 convolutions without post scale or zero weights.  The
         launch also writes the NEXT block's input planes when that block is a hierarchical block behind a ReLU."""
-        if not getattr(self, "fuse_hblock", True):
+        if not self.fuse_hblock:
             return
         for i, b in enumerate(self._blocks):
-            if b["kind"] != "h":
+            if b.kind != "h":
                 continue
-            convs = b["convs"]
-            ok = all(b["relu"]) and all(
+            convs = b.convs
+            ok = all(b.relu) and all(
                 c.layer.bias is None and c.plan.scale is None and not c.weight.has_zero and c.prelu is None and not c.relu
                 and tuple(c.layer.kernel_size) == (3, 3) and tuple(c.layer.stride) == (1, 1)
                 and tuple(c.layer.padding) == (1, 1) and tuple(c.layer.dilation) == (1, 1) for c in convs)
-            planes = b["planes"]
+            planes = b.planes
             ok = ok and convs[0].layer.out_channels * 2 == planes and convs[1].layer.out_channels * 4 == planes \
                 and convs[2].layer.out_channels * 4 == planes and planes % 64 == 0
             if not ok:
                 continue
             nxt = self._blocks[i + 1] if i + 1 < len(self._blocks) else None
-            nbn = nxt["bn"][0] if (nxt is not None and nxt["kind"] == "h" and nxt["relu"][0]
-                                   and nxt["convs"][0].layer.in_channels == planes) else None
+            nbn = nxt.bn[0] if (nxt is not None and nxt.kind == "h" and nxt.relu[0]
+                                and nxt.convs[0].layer.in_channels == planes) else None
             try:
-                b["hpack"] = hipops.hblock_pack(convs[0].weight, convs[1].weight, convs[2].weight, b["bn"][1], b["bn"][2], nbn)
+                b.hpack = hipops.hblock_pack(convs[0].weight, convs[1].weight, convs[2].weight, b.bn[1], b.bn[2], nbn)
             except native.NativeError:      # a width the one-launch kernel has no instance for
-                b["hpack"] = None
-            b["hgeo"] = {}
+                continue
             # the shortcut convolution of a stage's first block inside the block's launch (bnn_hip_hblock_shortcut_forward):
             # a plain binary 1x1 (no bias, no scale, no zero weights) behind its own BatchNorm, and a next block in the stage
-            b["hsc"] = None
-            if b["hpack"] is not None and b["ds"] is not None and nbn is not None:
-                sc = b["ds"][1]
+            if b.ds is not None and nbn is not None:
+                sc = b.ds
                 lay = sc.layer
                 if (lay.bias is None and sc.plan.scale is None and not sc.weight.has_zero and sc.prelu is None and not sc.relu
                         and sc.bn_scale is None and tuple(lay.kernel_size) == (1, 1) and tuple(lay.stride) == (1, 1)
                         and tuple(lay.padding) == (0, 0) and lay.in_channels * 2 == planes
                         and os.environ.get("BNN_AMD_HBLOCK_SHORTCUT", "1") != "0"):
                     try:
-                        b["hsc"] = hipops.hblock_shortcut_pack(sc.weight)
+                        b.hsc = hipops.hblock_shortcut_pack(sc.weight)
                     except native.NativeError:
-                        b["hsc"] = None
+                        pass
 
     def _add_block(self, blk) -> None:
         """Derive the fused form of one residual block (appends to ``self._blocks``)."""
         if isinstance(blk, nn.AvgPool2d):   # HBlock stages pool in front (bnn_amd/models/resnet.py)
-            self._blocks.append({"kind": "pool", "mod": blk})
+            self._blocks.append(_Pool(blk))
             return
         kind = _block_kind(blk)
         if kind is PreBasicBlock:           # BN-conv-act, BN-conv-act, (+id)   (res_block.py:147-152)
-            entry = {"kind": "pre", "bn1": fold_bn(blk.bn1), "bn2": fold_bn(blk.bn2),
-                     "convs": [self._conv(blk.conv1, None, blk.act1), self._conv(blk.conv2, None, blk.act2)],
-                     "ds": None, "pool": 0}
+            entry = _Pre(bn1=fold_bn(blk.bn1), bn2=fold_bn(blk.bn2),
+                         convs=[self._conv(blk.conv1, None, blk.act1), self._conv(blk.conv2, None, blk.act2)])
             self._shortcut(blk, entry)
             self._blocks.append(entry)
             return
         if kind is HBlock:                  # three BN-act-conv stages, cat, (+id)  (hierarchical_block.py:38-60)
-            entry = {"kind": "h", "planes": blk.conv1.out_channels * 2,
-                     "bn": [fold_bn(blk.bn1), fold_bn(blk.bn2), fold_bn(blk.bn3)],
-                     "relu": [self._sign_through(a) for a in (blk.act1, blk.act2, blk.act3)],
-                     "convs": [self._conv(c, None, None) for c in (blk.conv1, blk.conv2, blk.conv3)],
-                     "ds": None}
+            entry = _H(planes=blk.conv1.out_channels * 2,
+                       bn=[fold_bn(blk.bn1), fold_bn(blk.bn2), fold_bn(blk.bn3)],
+                       relu=[self._sign_through(a) for a in (blk.act1, blk.act2, blk.act3)],
+                       convs=[self._conv(c, None, None) for c in (blk.conv1, blk.conv2, blk.conv3)])
             if blk.downsample is not None:  # BN -> binary 1x1 (no BN behind it)
                 bn, conv = blk.downsample[0], blk.downsample[1]
-                entry["ds"] = (fold_bn(bn), self._conv(conv, None, None))
+                entry.ds_bn, entry.ds = fold_bn(bn), self._conv(conv, None, None)
             self._blocks.append(entry)
             return
         if kind is BasicBlock:           # conv-BN-act, conv-BN-(+id)-act
@@ -363,7 +428,7 @@ class FusedResNet(nn.Module):
                      self._conv(blk.conv3, blk.bn3, blk.act3)]
         else:
             raise FusionError(f"unsupported block {type(blk).__name__}")
-        entry = {"kind": "post", "convs": convs, "ds": None, "pool": 0}
+        entry = _Post(convs)
         self._shortcut(blk, entry)
         self._blocks.append(entry)
 
@@ -375,15 +440,15 @@ class FusedResNet(nn.Module):
         if _is_float_layer(conv):
             # a real-valued shortcut convolution (examples/recepies/imagenet-baseline.yaml keeps
             # layerN.0.downsample.1 out of the binarisation): the branch runs as the torch modules it is
-            entry["ds_float"] = blk.downsample
+            entry.ds_float = blk.downsample
             return
         k = pool.kernel_size if isinstance(pool.kernel_size, int) else pool.kernel_size[0]
         if not (isinstance(pool, nn.AvgPool2d) and pool.ceil_mode and not pool.count_include_pad
                 and pool.padding in (0, (0, 0))):
             raise FusionError("shortcut pooling must be AvgPool2d(k, k, ceil_mode=True, "
                               "count_include_pad=False)")
-        entry["ds"] = self._conv(conv, bn, None)
-        entry["pool"] = k
+        entry.ds = self._conv(conv, bn, None)
+        entry.pool = k
 
     @torch.no_grad()
     def _forward_impl(self, x: torch.Tensor) -> torch.Tensor:
@@ -391,74 +456,74 @@ class FusedResNet(nn.Module):
 
     def _front(self, x: torch.Tensor, out=None):
         """The part that reads the input tensor: the real-valued stem (first layer stays float: examples/cifar10.py:71)
-        -> (fp32 NCHW, sign planes).  ``out``: the results of an earlier call to overwrite (one-kernel stem only)."""
+        -> (fp32 NCHW, sign planes, _Handoff | None).  ``out``: the ``(fp32, planes)`` of an earlier call to overwrite
+        (one-kernel stem only)."""
         m = self.model
         if self._stem_mfma:
             # a hierarchical block behind the stem reads sign(relu(bn1(t))): the stem kernel writes THOSE planes (its own
-            # packing pass over the fp32 tensor disappears); the tag tells _run_h whose planes they are
+            # packing pass over the fp32 tensor disappears); the hand-off tells _run_h whose planes they are
             b0 = self._blocks[0] if self._blocks else None
             aff = None
-            if (b0 is not None and b0["kind"] == "h" and b0.get("hpack") is not None and b0["relu"][0] and b0["ds"] is None
-                    and not self.stem_exact_fp32 and _TAP is None and b0["hpack"].c_in == 64):
-                aff = b0["bn"][0]
+            if (b0 is not None and b0.kind == "h" and b0.hpack is not None and b0.relu[0] and b0.ds is None
+                    and not self.stem_exact_fp32 and _TAP is None and b0.hpack.c_in == 64):
+                aff = b0.bn[0]
             t, pk = hipops.stem7x7(x, m.conv1.weight, self._stem[0], self._stem[1], exact_fp32=self.stem_exact_fp32,
                                    fp16=self.stem_fp16, out=out, pack_affine=aff)
-            if aff is not None:
-                pk._h_for = b0
-            return t, pk
+            return t, pk, (_Handoff(b0) if aff is not None else None)
         if out is not None:
             raise FusionError("only the one-kernel stem writes into preallocated buffers")
         if self._stem is not None:   # the conv runs in the vendor library, its BN -> ReLU -> MaxPool -> sign tail in one pass
             t = m.conv1(x)
-            return hipops.bn_relu_maxpool_pack(t, self._stem[0], self._stem[1], True, *self._stem[2])
+            return (*hipops.bn_relu_maxpool_pack(t, self._stem[0], self._stem[1], True, *self._stem[2]), None)
         # any other stem runs as the torch modules it is (binary layers inside it one launch each); the residual blocks
         # behind it are fused all the same
         t = m.conv1(x) if self._stem_module else m.maxpool(m.relu(m.bn1(m.conv1(x))))
-        return t, hipops.pack_act(t)
+        return t, hipops.pack_act(t), None
 
-    def _back(self, t, packed) -> torch.Tensor:
+    def _back(self, t, packed, left) -> torch.Tensor:
         """Everything behind the stem: residual blocks + real-valued head (last layer stays float)."""
         m = self.model
-        t = self._run_blocks(t, packed)
+        t = self._run_blocks(t, packed, left)
         if self._head is not None:
             return hipops.avgpool_fc(t, *self._head)
         return m.fc(torch.flatten(m.avgpool(t), 1))
 
-    def _run_blocks(self, t, packed):
+    def _run_blocks(self, t, packed, left):
         """The residual blocks: ``t`` fp32 NCHW (may be None when only planes exist), ``packed`` its sign planes
-        or None.  Returns the fp32 output of the last block."""
+        or None — or, with a hand-off ``left``, the planes ``left.owner`` reads.  Returns the fp32 output of the last block."""
         last = len(self._blocks) - 1
         for i, b in enumerate(self._blocks):
             nxt = self._blocks[i + 1] if i < last else None
-            if b["kind"] == "pool":
-                if t is None and packed is not None and getattr(packed, "_h_for", None) is nxt:
+            if b.kind == "pool":
+                if t is None and left is not None and left.owner is nxt:
                     continue                # the previous block's launch pooled and binarised its own output (_run_h)
-                fused = self._pool_into_hblock(b["mod"], nxt, t)
+                fused = self._pool_into_hblock(b.mod, nxt, t)
                 if fused is not None:       # the pool + both sign planes the next stage's first block reads, one pass
-                    t, packed = fused
+                    t, packed, left = fused
                     continue
-                t, packed = b["mod"](t), None
+                t, packed, left = b.mod(t), None, None
                 continue
-            if b["kind"] == "pre":
-                t, packed = self._run_pre(b, nxt, t, packed)
+            if b.kind == "pre":
+                t, packed, left = self._run_pre(b, nxt, t, packed, left)
                 continue
-            if b["kind"] == "h":
-                t, packed = self._run_h(b, t, packed, nxt, self._blocks[i + 2] if i + 2 <= last else None)
+            if b.kind == "h":
+                t, packed, left = self._run_h(b, t, packed, left, nxt, self._blocks[i + 2] if i + 2 <= last else None)
                 continue
+            assert left is None, "sign planes written for another block's first convolution"
             if packed is None:
                 packed = hipops.pack_act(t)
             side = None
             fold = None   # (PackedAct, PackedWeight, bn_scale, bn_shift) of a shortcut conv folded into the last conv
-            if b["ds"] is not None and self._fold_applies(b, packed):
+            if b.ds is not None and self._fold_applies(b, packed):
                 # the shortcut conv (1x1 over the OR-pooled sign planes) is computed inside the block's last conv: no
                 # fp32 shortcut tensor, no 1x1 launch (bnn_hip_epilogue.sc_*)
                 # (pool 2: the kernel ORs the 2 x 2 windows of the block's input planes itself — no OR-pool launch)
-                sc_in = packed if b["pool"] in (0, 1, 2) else hipops.orpool_packed(packed, b["pool"])
+                sc_in = packed if b.pool in (0, 1, 2) else hipops.orpool_packed(packed, b.pool)
                 if _TAP is not None:
-                    _TAP(b["ds"].name, hipops.orpool_packed(packed, b["pool"]) if b["pool"] > 1 else packed)
-                fold = (sc_in, b["ds"].weight, b["ds"].bn_scale, b["ds"].bn_shift)
+                    _TAP(b.ds.name, hipops.orpool_packed(packed, b.pool) if b.pool > 1 else packed)
+                fold = (sc_in, b.ds.weight, b.ds.bn_scale, b.ds.bn_shift)
                 idn = None
-            elif b["ds"] is not None:
+            elif b.ds is not None:
                 # the shortcut branch (HBM-bound avg-pool + a small 1x1 conv) is independent of the block's
                 # first convs (ALU-bound): run it on a second stream and join before the residual is needed
                 dev_ = packed.P.device      # (t is None when the previous block skipped its dead fp32 output)
@@ -467,33 +532,33 @@ class FusedResNet(nn.Module):
                 if side is not None:
                     side.wait_stream(cur)
                 with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
-                    if b["pool"] > 1 and packed.nonneg:   # sign(avg of non-negative values) = OR of the sign bits
-                        sc_in = hipops.orpool_packed(packed, b["pool"])
-                    elif b["pool"] > 1:
-                        sc_in = hipops.avgpool_pack(t, b["pool"])
+                    if b.pool > 1 and packed.nonneg:   # sign(avg of non-negative values) = OR of the sign bits
+                        sc_in = hipops.orpool_packed(packed, b.pool)
+                    elif b.pool > 1:
+                        sc_in = hipops.avgpool_pack(t, b.pool)
                     else:
                         sc_in = packed
-                    idn, _ = b["ds"].run(sc_in, out_f32=True, out_packed=False)
+                    idn, _ = b.ds.run(sc_in, out_f32=True, out_packed=False)
                 if side is not None:
                     if t is not None:
                         t.record_stream(side)
                     packed.P.record_stream(side)
                     sc_in.P.record_stream(side)
                     sc_in.M.record_stream(side)
-            elif b.get("ds_float") is not None:
-                idn = b["ds_float"](t)
+            elif b.ds_float is not None:
+                idn = b.ds_float(t)
             else:
                 idn = t
-            for c in b["convs"][:-1]:           # activations travel between binary layers as bit planes
+            for c in b.convs[:-1]:              # activations travel between binary layers as bit planes
                 _, packed = c.run(packed, out_f32=False, out_packed=True)
             if side is not None:
                 cur.wait_stream(side)
                 idn.record_stream(cur)
             # the fp32 output is dead when the next block reads sign planes only: its convs always do, its shortcut
             # does when it is AvgPool -> binary 1x1 (-> OR-pool of the planes of a non-negative tensor, or no pooling)
-            c2 = b["convs"][-1]
-            dead_f32 = (self.skip_dead_f32 and nxt is not None and nxt["kind"] == "post" and nxt["ds"] is not None
-                        and (nxt["pool"] <= 1 or (c2.relu and c2.prelu is None)))
+            c2 = b.convs[-1]
+            dead_f32 = (self.skip_dead_f32 and nxt is not None and nxt.kind == "post" and nxt.ds is not None
+                        and (nxt.pool <= 1 or (c2.relu and c2.prelu is None)))
             if fold is not None:
                 t, packed = c2.run(packed, out_f32=True, out_packed=True, shortcut=fold)
             else:
@@ -509,28 +574,27 @@ class FusedResNet(nn.Module):
         fp32 output and sign planes are both wanted (a block in the middle of the net)."""
         if not self.fold_shortcut or not packed.nonneg:
             return False
-        ds, c2 = b["ds"], b["convs"][-1]
+        ds, c2 = b.ds, b.convs[-1]
         lay, c2l = ds.layer, c2.layer
-        if "fold_recipe" not in b:
-            b["fold_recipe"] = bool(
+        if b.fold_recipe is None:
+            b.fold_recipe = bool(
                 lay.bias is None and ds.plan.scale is None and not ds.relu and ds.prelu is None
                 and tuple(lay.kernel_size) == (1, 1) and tuple(lay.stride) == (1, 1) and tuple(lay.padding) == (0, 0)
-                and not ds.weight.has_zero and b is not self._blocks[-1] and len(b["convs"]) >= 2
-                and all(c.relu and c.prelu is None for c in b["convs"][:-1])
+                and not ds.weight.has_zero and b is not self._blocks[-1] and len(b.convs) >= 2
+                and all(c.relu and c.prelu is None for c in b.convs[:-1])
                 and c2.relu and c2.prelu is None and c2.layer.bias is None and c2.plan.scale is None)
-            b["fold_geo"] = {}
-        if not b["fold_recipe"]:
+        if not b.fold_recipe:
             return False
         N, _, H, W = packed.shape
-        k = max(b["pool"], 1)
+        k = max(b.pool, 1)
         ho, wo = -(-H // k), -(-W // k)
         n_launch = hipops.fused_launch_images(N, c2l.in_channels, ho, wo, c2l.out_channels, c2l.kernel_size,
                                               c2l.stride, c2l.padding, c2l.dilation)
         key = (n_launch, ho, wo)
-        ok = b["fold_geo"].get(key)
+        ok = b.fold_geo.get(key)
         if ok is None:
             probe = hipops.PackedAct(packed.P, packed.M, (n_launch, c2l.in_channels, ho, wo), nonneg=True)
-            ok = b["fold_geo"][key] = bool(hipops.shortcut_fold_supported(
+            ok = b.fold_geo[key] = bool(hipops.shortcut_fold_supported(
                 probe, c2.weight, lay.in_channels, c2l.stride, c2l.padding, c2l.dilation, throughput=c2.throughput))
         return ok
 
@@ -540,147 +604,135 @@ class FusedResNet(nn.Module):
             self._side[key] = torch.cuda.Stream(device=device)
         return self._side[key]
 
-    def _run_pre(self, b, nxt, t, packed):
+    def _run_pre(self, b, nxt, t, packed, left):
         """PreBasicBlock: the block input travels as fp32 ``t`` (shortcut) and as ``sign(bn1(t))``; the
         latter comes out of the previous block's last epilogue (its ``pack_scale`` = this ``bn1``)."""
-        if packed is None or not getattr(packed, "_pre_bn_of", None) is b:
-            packed = hipops.bn_act_pack(t, *b["bn1"], relu=False)
-        if b["ds"] is not None:
-            sc_in = hipops.avgpool_pack(t, b["pool"]) if b["pool"] > 1 else hipops.pack_act(t)
-            idn, _ = b["ds"].run(sc_in, out_f32=True, out_packed=False)
-        elif b.get("ds_float") is not None:
-            idn = b["ds_float"](t)
+        if left is None or left.owner is not b:
+            packed = hipops.bn_act_pack(t, *b.bn1, relu=False)
+        if b.ds is not None:
+            sc_in = hipops.avgpool_pack(t, b.pool) if b.pool > 1 else hipops.pack_act(t)
+            idn, _ = b.ds.run(sc_in, out_f32=True, out_packed=False)
+        elif b.ds_float is not None:
+            idn = b.ds_float(t)
         else:
             idn = t
-        c1, c2 = b["convs"]
-        _, p1 = c1.run(packed, out_f32=False, out_packed=True, pack_scale=b["bn2"][0], pack_shift=b["bn2"][1])
-        if nxt is not None and nxt["kind"] == "pre":   # binarise for the next block's conv1 right here
+        c1, c2 = b.convs
+        _, p1 = c1.run(packed, out_f32=False, out_packed=True, pack_scale=b.bn2[0], pack_shift=b.bn2[1])
+        if nxt is not None and nxt.kind == "pre":   # binarise for the next block's conv1 right here
             t, pk = c2.run(p1, residual=idn, out_f32=True, out_packed=True, residual_after_act=True,
-                           pack_scale=nxt["bn1"][0], pack_shift=nxt["bn1"][1])
-            pk._pre_bn_of = nxt
-            return t, pk
+                           pack_scale=nxt.bn1[0], pack_shift=nxt.bn1[1])
+            return t, pk, _Handoff(nxt)
         t, _ = c2.run(p1, residual=idn, out_f32=True, out_packed=False, residual_after_act=True)
-        return t, None
+        return t, None, None
 
     def _pool_into_hblock(self, pool, nxt, t):
         """``AvgPool2d(2, 2)`` in front of a hierarchical block that runs as one launch: the pooled tensor is only ever
         binarised — by the block's bn1 -> ReLU and by its shortcut's BatchNorm — so one pass writes both sets of planes
         and (when the block has a shortcut convolution) no fp32 tensor at all.  None: not that case."""
-        if (_TAP is not None or nxt is None or nxt["kind"] != "h" or nxt.get("hpack") is None or t is None
+        if (_TAP is not None or nxt is None or nxt.kind != "h" or nxt.hpack is None or t is None
                 or not isinstance(pool, nn.AvgPool2d) or pool.kernel_size not in (2, (2, 2))
                 or pool.stride not in (2, (2, 2)) or pool.padding not in (0, (0, 0))
-                or t.shape[2] % 2 or t.shape[3] % 2 or not nxt["relu"][0]):
+                or t.shape[2] % 2 or t.shape[3] % 2 or not nxt.relu[0]):
             return None
         N, C, H, W = t.shape
-        hp = nxt["hpack"]
+        hp = nxt.hpack
         if C != hp.c_in or not self._hblock_ok(nxt, N, H // 2, W // 2):
             return None
-        ds_bn = nxt["ds"][0] if nxt["ds"] is not None else None
-        p1, p2, tp = hipops.avgpool2_bn_pack2(t, nxt["bn"][0], True, ds_bn, False, out_f32=ds_bn is None)
-        p1._h_for = nxt
-        p1._ds_planes = p2
-        return tp, p1
+        p1, p2, tp = hipops.avgpool2_bn_pack2(t, nxt.bn[0], True, nxt.ds_bn, False, out_f32=nxt.ds_bn is None)
+        return tp, p1, _Handoff(nxt, p2)
 
     def _hblock_ok(self, b, N, H, W) -> bool:
-        """Whether the one-launch kernel covers this geometry; also decides which form of it runs (``b["hcl"]``): the
-        small-image form (lanes = output channels, csrc/hblock_cl.hip) on 7 x 7 images, and on 14 x 14 images when other
+        """Whether the one-launch kernel covers this geometry; also decides which form of it runs (``b.geo[N, H, W].cl``):
+        the small-image form (lanes = output channels, csrc/hblock_cl.hip) on 7 x 7 images, and on 14 x 14 images when other
         work shares the GPU — there whole images per workgroup win; alone, the pixel-lane kernel splits a 14 x 14 image over
         two workgroups and fills the chip (measured at batch 128, us per block: 7 x 7 53.6 vs 67.1; 14 x 14 shared 60.4 vs
         72.0, alone 60.4 vs 44.8)."""
-        ok = b["hgeo"].get((N, H, W))
-        if ok is None:
-            hp = b["hpack"]
+        g = b.geo.get((N, H, W))
+        if g is None:
+            hp = b.hpack
             cl = (os.environ.get("BNN_AMD_HBLOCK_CL", "1") != "0" and (H == 7 or self.throughput_mode)
                   and hipops.hblock_supported(N, hp.c_in, H, W, hp.planes, self.throughput_mode, channel_lanes=True))
             ok = cl or hipops.hblock_supported(N, hp.c_in, H, W, hp.planes, self.throughput_mode)
-            b["hgeo"][(N, H, W)] = ok
-            b.setdefault("hcl", {})[(N, H, W)] = cl
-        return ok
+            g = b.geo[(N, H, W)] = _HGeo(ok, cl)
+        return g.ok
 
     def _pooled_form(self, b, nxt, nxt2, N, H, W):
         """The constants of ``hipops.hblock_pool_forward`` when block ``b`` ends a stage — ``nxt`` is ``AvgPool2d(2, 2)`` and
         ``nxt2`` a one-launch hierarchical block with a shortcut convolution, so that nobody reads ``b``'s fp32 output —
-        and the kernel covers the geometry; else None."""
-        key = ("pool", N, H, W)
-        hit = b["hgeo"].get(key)
+        and the kernel covers the geometry; else None.  (Behind ``_hblock_ok(b, N, H, W)``: the geometry has its entry.)"""
+        g = b.geo[(N, H, W)]
+        hit = g.pooled
         if hit is None:
             hit = False
-            pool = nxt["mod"] if nxt is not None and nxt["kind"] == "pool" else None
-            hp = b["hpack"]
+            pool = nxt.mod if nxt is not None and nxt.kind == "pool" else None
+            hp = b.hpack
             if (os.environ.get("BNN_AMD_HBLOCK_POOL", "1") != "0" and _TAP is None and pool is not None and nxt2 is not None
-                    and nxt2["kind"] == "h" and nxt2.get("hpack") is not None and nxt2["ds"] is not None and nxt2["relu"][0]
+                    and nxt2.kind == "h" and nxt2.hpack is not None and nxt2.ds is not None and nxt2.relu[0]
                     and isinstance(pool, nn.AvgPool2d) and pool.kernel_size in (2, (2, 2)) and pool.stride in (2, (2, 2))
                     and pool.padding in (0, (0, 0)) and H % 2 == 0 and W % 2 == 0 and hp.c_in == hp.planes
                     and H * W >= int(os.environ.get("BNN_AMD_HBLOCK_POOL_MIN", "784"))
-                    and nxt2["hpack"].c_in == hp.planes and self._hblock_ok(nxt2, N, H // 2, W // 2)
+                    and nxt2.hpack.c_in == hp.planes and self._hblock_ok(nxt2, N, H // 2, W // 2)
                     and hipops.hblock_pool_supported(N, hp.c_in, H, W, hp.planes, self.throughput_mode)):
                 try:
-                    hit = hipops.hblock_pool_consts(nxt2["bn"][0], nxt2["ds"][0], hp.planes)
+                    hit = hipops.hblock_pool_consts(nxt2.bn[0], nxt2.ds_bn, hp.planes)
                 except native.NativeError:      # (a scale that cannot take the average's 1 / 4 exactly)
                     hit = False
-            b["hgeo"][key] = hit
+            g.pooled = hit
         return None if hit is False else hit
 
-    def _run_h(self, b, t, packed=None, nxt=None, nxt2=None):
+    def _run_h(self, b, t, packed=None, left=None, nxt=None, nxt2=None):
         """HBlock: three BN-act-conv stages write their slice of the concatenated output in place, each
         adds its slice of the shortcut and hands ``sign(act(bn_next(o_k)))`` to the next stage.  Returns
-        ``(y, planes of the next block's input | None)``; ``packed``: what the previous block's launch left for this one.
-        The last block of a stage returns ``(None, planes of the next stage's first block)``: pooled and binarised in the
-        same launch (``_pooled_form``)."""
-        mine = packed is not None and getattr(packed, "_h_for", None) is b    # planes the previous launch left for this block
-        if b["ds"] is not None:
-            (sa, sb), conv = b["ds"]
-            sp = getattr(packed, "_ds_planes", None) if mine else None
+        ``(y, planes of the next block's input | None, their _Handoff | None)``; ``packed`` / ``left``: what the previous
+        block's launch left, for this block when ``left.owner is b``.  The last block of a stage returns ``(None, planes of
+        the next stage's first block, ...)``: pooled and binarised in the same launch (``_pooled_form``)."""
+        mine = left is not None and left.owner is b     # planes the previous launch left for this block
+        if b.ds is not None:
+            sp = left.ds if mine else None
             if sp is None:
-                sp = hipops.bn_act_pack(t, sa, sb, relu=False)
-            hp = b.get("hpack")
-            if b.get("hsc") is not None and _TAP is None:
+                sp = hipops.bn_act_pack(t, *b.ds_bn, relu=False)
+            hp = b.hpack
+            if b.hsc is not None and _TAP is None:
                 N, _, H, W = sp.shape
-                key = ("sc", N, H, W)
-                ok = b["hgeo"].get(key)
-                if ok is None:     # (in the form of the block that _hblock_ok chose for this geometry)
-                    ok = b["hgeo"][key] = (self._hblock_ok(b, N, H, W) and
-                                           hipops.hblock_shortcut_supported(N, hp.c_in, H, W, hp.planes, self.throughput_mode,
-                                                                            channel_lanes=b["hcl"][(N, H, W)]))
-                if ok:
+                ok = self._hblock_ok(b, N, H, W)
+                g = b.geo[(N, H, W)]
+                if g.sc is None:   # (in the form of the block that _hblock_ok chose for this geometry)
+                    g.sc = ok and hipops.hblock_shortcut_supported(N, hp.c_in, H, W, hp.planes, self.throughput_mode,
+                                                                   channel_lanes=g.cl)
+                if g.sc:
                     if not mine:
-                        packed = hipops.bn_act_pack(t, *b["bn"][0], relu=True)
-                    y, pk = hipops.hblock_shortcut_forward(packed, hp, sp, b["hsc"], throughput=self.throughput_mode,
-                                                           channel_lanes=b["hcl"][(N, H, W)])
-                    pk._h_for = nxt
-                    return y, pk
-            idn, _ = conv.run(sp, out_f32=True, out_packed=False)
+                        packed = hipops.bn_act_pack(t, *b.bn[0], relu=True)
+                    y, pk = hipops.hblock_shortcut_forward(packed, hp, sp, b.hsc, throughput=self.throughput_mode,
+                                                           channel_lanes=g.cl)
+                    return y, pk, _Handoff(nxt)
+            idn, _ = b.ds.run(sp, out_f32=True, out_packed=False)
         else:
             idn = t
-        c1, c2, c3 = b["convs"]
-        hp = b.get("hpack")
+        c1, c2, c3 = b.convs
+        hp = b.hpack
         if hp is not None and _TAP is None:     # (a tap wants the planes in front of every convolution: launch by launch)
             N, _, H, W = idn.shape
             if self._hblock_ok(b, N, H, W):
                 if not mine:
-                    packed = hipops.bn_act_pack(t, *b["bn"][0], relu=True)
+                    packed = hipops.bn_act_pack(t, *b.bn[0], relu=True)
                 kp = self._pooled_form(b, nxt, nxt2, N, H, W)
                 if kp is not None:
                     p1, p2 = hipops.hblock_pool_forward(packed, hp, idn, kp, throughput=self.throughput_mode)
-                    p1._h_for = nxt2
-                    p1._ds_planes = p2
-                    return None, p1
+                    return None, p1, _Handoff(nxt2, p2)
                 y, pk = hipops.hblock_forward(packed, hp, idn, out_packed=hp.has_next, throughput=self.throughput_mode,
-                                              channel_lanes=b["hcl"][(N, H, W)])
-                if pk is not None:
-                    pk._h_for = nxt
-                return y, pk
-        half = b["planes"] // 2
+                                              channel_lanes=b.geo[(N, H, W)].cl)
+                return y, pk, (_Handoff(nxt) if pk is not None else None)
+        half = b.planes // 2
         quarter = c2.layer.out_channels
-        p = hipops.bn_act_pack(t, *b["bn"][0], relu=b["relu"][0])
-        y = torch.empty((t.shape[0], b["planes"], t.shape[2], t.shape[3]), dtype=torch.float32, device=t.device)
+        p = hipops.bn_act_pack(t, *b.bn[0], relu=b.relu[0])
+        y = torch.empty((t.shape[0], b.planes, t.shape[2], t.shape[3]), dtype=torch.float32, device=t.device)
         late = dict(residual=idn, residual_after_act=True, pack_before_residual=True, out=y, out_f32=True)
-        _, p = c1.run(p, out_packed=True, out_c_offset=0, pack_scale=b["bn"][1][0], pack_shift=b["bn"][1][1],
-                      pack_relu=b["relu"][1], **late)
-        _, p = c2.run(p, out_packed=True, out_c_offset=half, pack_scale=b["bn"][2][0], pack_shift=b["bn"][2][1],
-                      pack_relu=b["relu"][2], **late)
+        _, p = c1.run(p, out_packed=True, out_c_offset=0, pack_scale=b.bn[1][0], pack_shift=b.bn[1][1],
+                      pack_relu=b.relu[1], **late)
+        _, p = c2.run(p, out_packed=True, out_c_offset=half, pack_scale=b.bn[2][0], pack_shift=b.bn[2][1],
+                      pack_relu=b.relu[2], **late)
         c3.run(p, out_packed=False, out_c_offset=half + quarter, **late)
-        return y, None
+        return y, None, None
 
     def _slots(self):
         """(module dict, name) of every parameter / buffer slot of the wrapped model in the order of ``param_signature``
@@ -788,17 +840,17 @@ class FusedResNet(nn.Module):
         dev = example.device
         with torch.cuda.device(dev):
             cur = torch.cuda.current_stream(dev)
-            t0, pk0 = self._front(example)          # allocated on the stream that will replay (the key holds it)
+            t0, pk0, left0 = self._front(example)   # allocated on the stream that will replay (the key holds it)
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(cur)
             with torch.cuda.stream(side):
                 for _ in range(2):
-                    self._back(t0, pk0)
+                    self._back(t0, pk0, left0)
             cur.wait_stream(side)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                gy = self._back(t0, pk0)
-        return _Split(g, t0, pk0, gy)
+                gy = self._back(t0, pk0, left0)
+        return _Split(g, t0, pk0, left0, gy)
 
     @torch.no_grad()
     def forward_fresh(self, x: torch.Tensor, clone: bool = True) -> torch.Tensor:
@@ -818,7 +870,9 @@ class FusedResNet(nn.Module):
                     self._split.popitem(last=False)
             else:
                 self._split.move_to_end(key)
-            self._front(x, out=(sp.t0, sp.pk0))
+            _, _, left = self._front(x, out=(sp.t0, sp.pk0))
+            # the graph reads pk0 as it was captured: as the planes of left0's owner, or as sign(t0)
+            assert (left is None) == (sp.left0 is None), "the stem wrote other sign planes than the captured graph reads"
             sp.graph.replay()
             return sp.gy.clone() if clone else sp.gy
 
@@ -828,6 +882,7 @@ class _Split:
     graph: "torch.cuda.CUDAGraph"
     t0: torch.Tensor            # static fp32 output of the stem
     pk0: hipops.PackedAct       # static sign planes of the stem
+    left0: Optional[_Handoff]   # whose planes pk0 holds when they are not sign(t0): the graph was captured reading them so
     gy: torch.Tensor            # static logits
 
 
@@ -837,21 +892,11 @@ class FusedBlocks(FusedResNet):
     activations between the binary layers travel as bit planes exactly as inside ``FusedResNet``.  For custom
     networks that keep their own stem / head, and for testing the cross-block dataflow on its own."""
 
+    _stem_mfma = False      # no stem: ``forward_fresh`` does not apply
+
     def __init__(self, blocks: nn.Sequential, throughput_mode: bool = False, int_thresholds: bool = True) -> None:
-        nn.Module.__init__(self)
-        self.skip_dead_f32 = True
-        self.int_thresholds = int_thresholds
-        self.throughput_mode = throughput_mode
-        self.overlap_shortcut = True
-        self.fold_shortcut = True
-        self.fuse_hblock = True
-        self._side = {}
-        self.model = blocks
-        self._blocks = []
-        self._graph = None
-        self._split = collections.OrderedDict()
-        self._stem_mfma = False
-        self.refresh()
+        # every other option: FusedResNet's default
+        super().__init__(blocks, throughput_mode=throughput_mode, int_thresholds=int_thresholds)
 
     def refresh(self) -> None:
         native.require()
@@ -868,7 +913,7 @@ class FusedBlocks(FusedResNet):
 
     @torch.no_grad()
     def _forward_impl(self, x: torch.Tensor) -> torch.Tensor:
-        return self._run_blocks(hipops._require_cuda_f32(x, "activation"), None)
+        return self._run_blocks(hipops._require_cuda_f32(x, "activation"), None, None)
 
 
 def _is_float_layer_linear(fc: nn.Module) -> bool:

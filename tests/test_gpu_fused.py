@@ -292,7 +292,7 @@ def test_fused_resnet50_bottleneck_matches_layerwise_and_cpu(activation):
         ref = net(x).numpy()                                   # CPU: torch composition
     net = net.to(DEV)
     fused = FusedResNet(net)
-    assert len(fused._blocks) == 16 and all(len(b["convs"]) == 3 for b in fused._blocks)
+    assert len(fused._blocks) == 16 and all(len(b.convs) == 3 for b in fused._blocks)
     before = fastpath.stats()["conv2d"]
     y = fused(x.to(DEV)).cpu().numpy()
     assert fastpath.stats()["conv2d"] == before
@@ -326,7 +326,7 @@ def test_fused_preactivation_and_hierarchical_nets(kind):
         ref = net(x).numpy()                                   # CPU: torch composition
     net = net.to(DEV)
     fused = FusedResNet(net)
-    kinds = {b["kind"] for b in fused._blocks}
+    kinds = {b.kind for b in fused._blocks}
     assert kinds == ({"pre"} if kind.startswith("pre") else {"h", "pool"})
     before = fastpath.stats()["conv2d"]
     y = fused(x.to(DEV)).cpu().numpy()
@@ -613,7 +613,7 @@ def test_fused_resnet_with_integer_thresholds_is_bit_identical():
     net = _r18()
     x = dev(gen.normal(43, (4, 3, 96, 96)))
     a, b = FusedResNet(net), FusedResNet(net, int_thresholds=False)
-    assert a._blocks[0]["convs"][0].thr is not None and b._blocks[0]["convs"][0].thr is None
+    assert a._blocks[0].convs[0].thr is not None and b._blocks[0].convs[0].thr is None
     assert torch.equal(a(x), b(x))
 
 
@@ -623,7 +623,7 @@ def test_throughput_mode_changes_the_kernel_choice_not_the_result():
     net = _r18()
     x = dev(gen.normal(41, (8, 3, 96, 96)))
     a, b = FusedResNet(net), FusedResNet(net, throughput_mode=True)
-    assert b._blocks[0]["convs"][0].throughput and not a._blocks[0]["convs"][0].throughput
+    assert b._blocks[0].convs[0].throughput and not a._blocks[0].convs[0].throughput
     assert torch.equal(a(x), b(x))
 
 
