@@ -12,10 +12,11 @@ A layer takes the HIP path when ALL of the following hold (otherwise the torch c
 * autograd is not recording (``torch.no_grad()`` / inference); when it IS recording, ``Conv2d`` takes the
   training variant (HIP forward, fp32 library backward with the straight-through estimator:
   ``bnn_amd/training.py``), ``Conv1d``/``Linear`` fall back to the composition
-* ``padding_mode == 'zeros'``, numeric padding, and either ``groups == 1`` or — ``Conv2d`` / ``Conv1d`` under inference
-  only — ``groups > 1`` (grouped and depthwise layers: ``pack_act`` + ``bnn_hip_bconv2d_grouped``, two launches; the
-  training forward and the ResNet executors keep declining them; inside a BATS cell operation of ``bnn_amd.models``
-  the layer runs as part of ``cellops.FusedCellOp``)
+* ``padding_mode == 'zeros'``, numeric padding, and either ``groups == 1`` or — ``Conv2d`` / ``Conv1d`` under inference,
+  ``Conv2d`` under autograd only with ``training.GROUPED`` — ``groups > 1`` (grouped and depthwise layers: ``pack_act``
+  + ``bnn_hip_bconv2d_grouped``, two launches; the ResNet executors keep declining them, and so does the training
+  forward by default; inside a BATS cell operation of ``bnn_amd.models`` the layer runs as part of
+  ``cellops.FusedCellOp``)
 
 When those hold and ``libbnn_hip.so`` cannot be loaded the call raises ``NativeError``: there is
 no CPU or eager stand-in for the GPU path.
@@ -132,8 +133,8 @@ def _numeric_padding(layer) -> bool:
 
 
 def _grouped_numeric_padding(layer) -> bool:
-    """A grouped / depthwise layer the inference path takes (``bnn_hip_bconv2d_grouped``).  ``_numeric_padding`` keeps
-    rejecting these: the training forward and the fused executors rely on it."""
+    """A grouped / depthwise layer the inference path takes (``bnn_hip_bconv2d_grouped``), and — ``training.GROUPED`` —
+    the training forward.  ``_numeric_padding`` keeps rejecting these: the fused executors rely on it."""
     return not isinstance(layer.padding, str) and layer.padding_mode == "zeros" and layer.groups > 1
 
 
@@ -145,8 +146,10 @@ def plan_conv2d(layer, x: torch.Tensor) -> Optional[Plan]:
 
 
 def plan_conv2d_train(layer, x: torch.Tensor) -> Optional[Plan]:
-    """Plan for a training-mode forward (only consulted when ``plan_conv2d`` declined)."""
-    if x.dim() != 4 or not _numeric_padding(layer):
+    """Plan for a training-mode forward (only consulted when ``plan_conv2d`` declined).  Grouped / depthwise layers
+    take it under ``training.GROUPED`` (read at every call; off by default)."""
+    from . import training
+    if x.dim() != 4 or not (_numeric_padding(layer) or (training.GROUPED and _grouped_numeric_padding(layer))):
         return None
     plan = _recognise(layer, layer.out_channels)
     return plan if plan is not None and plan.ste and _eligible_train(layer, x) else None
@@ -295,7 +298,8 @@ def conv2d(layer, x: torch.Tensor, plan: Plan) -> torch.Tensor:
 
 
 def conv2d_train(layer, x: torch.Tensor, plan: Plan) -> torch.Tensor:
-    """Same forward under autograd: HIP kernels forward, fp32 library convolutions backward."""
+    """Same forward under autograd (``training.conv2d_train``): HIP kernels forward, binary-aware HIP gradient kernels
+    or the library's fp32 convolutions backward."""
     from . import training
     native.require()
     out = training.conv2d_train(layer, x, plan, packed_weight(layer, plan, sync=False, fresh=True))

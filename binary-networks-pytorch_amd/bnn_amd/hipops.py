@@ -1316,6 +1316,81 @@ def bconv_grad_weight(g: torch.Tensor, x, ksize: int = 3, stride: int = 1, reduc
         return part[0] if splits == 1 else part.sum(0)
 
 
+def _grouped_grad_desc(x_shape, w_shape, groups, stride, padding, dilation) -> native.ConvDesc:
+    """Descriptor of a grouped layer for the ``bnn_hip_bconv_grouped_grad_*`` entry points: all ``C`` input channels, the
+    weight ``[O, C / groups, KH, KW]``."""
+    N, C, H, W = x_shape
+    O, Cg, KH, KW = w_shape
+    if Cg * groups != C:
+        raise native.NativeError(f"bnn_amd: grouped weight reads {Cg} x {groups} channels, the input has {C}")
+    return _desc(x_shape, (O, C, KH, KW), stride, padding, dilation, 0)
+
+
+def grouped_grad_supported(x_shape, w_shape, groups, stride, padding, dilation) -> bool:
+    """Whether the grouped gradient kernels (csrc/grad_grouped.hip) cover the layer: the library's own answer
+    (``bnn_hip_bconv_grouped_grad_supported``, a host function)."""
+    return grouped_grad_weight_splits(x_shape, w_shape, groups, stride, padding, dilation) > 0
+
+
+def grouped_grad_weight_splits(x_shape, w_shape, groups, stride, padding, dilation) -> int:
+    """How many partial slabs ``bconv_grouped_grad_weight`` writes by default (the library's choice, a host function);
+    0 when the gradient kernels do not cover the layer, or the weight does not belong to the input."""
+    if len(x_shape) != 4 or len(w_shape) != 4 or groups < 1:
+        return 0
+    try:
+        d = _grouped_grad_desc(x_shape, w_shape, groups, stride, padding, dilation)
+    except native.NativeError:
+        return 0
+    return int(native.require().bnn_hip_bconv_grouped_grad_weight_splits(ctypes.byref(d), int(groups)))
+
+
+def _grouped_grad_args(g: torch.Tensor, saved: "SavedAct", w_shape, groups, stride, padding, dilation):
+    g = _require_cuda_f32(g, "grad_output")
+    d = _grouped_grad_desc(saved.shape, w_shape, groups, stride, padding, dilation)
+    ho, wo = conv_out_hw(d.H, d.W, d.KH, d.KW, stride, padding, dilation)
+    if tuple(g.shape) != (d.N, d.O, ho, wo):
+        raise native.NativeError(f"bnn_amd: grad_output {tuple(g.shape)} does not belong to input {tuple(saved.shape)} "
+                                 f"and weight {tuple(w_shape)}")
+    return g, d
+
+
+def bconv_grouped_grad_input(g: torch.Tensor, saved: "SavedAct", what: torch.Tensor, groups: int, stride=1, padding=0,
+                             dilation=1) -> torch.Tensor:
+    """dL/dx of a grouped binary convolution incl. the hard-tanh STE mask (bnn/ops.py:68-73), from ``g``, the fp32
+    ``What [O, C/groups, KH, KW]`` (``xnor_what``) and the mask plane of ``saved`` (``bnn_hip_bconv_grouped_grad_input_f32``)."""
+    what = _require_cuda_f32(what.detach(), "w_hat")
+    g, d = _grouped_grad_args(g, saved, what.shape, groups, stride, padding, dilation)
+    lib = native.require()
+    with torch.cuda.device(g.device):
+        gx = torch.empty(saved.shape, dtype=torch.float32, device=g.device)
+        if d.N:
+            native.check(lib.bnn_hip_bconv_grouped_grad_input_f32(
+                ctypes.byref(d), int(groups), g.data_ptr(), what.data_ptr(), saved.T.data_ptr(), gx.data_ptr(),
+                _stream(g.device)), "bnn_hip_bconv_grouped_grad_input_f32")
+    return gx
+
+
+def bconv_grouped_grad_weight(g: torch.Tensor, saved: "SavedAct", w_shape, groups: int, stride=1, padding=0, dilation=1,
+                              reduce: bool = True, splits: Optional[int] = None) -> torch.Tensor:
+    """dL/dWhat ``[O, C/groups, KH, KW]`` of a grouped binary convolution: correlation of ``g`` with ``sign(x)`` read from
+    the sign planes of ``saved`` (``bnn_hip_bconv_grouped_grad_weight_f32``).  ``splits=None``: the library's choice;
+    ``reduce=False``: the deterministic partial slabs ``[splits, *w_shape]`` as they are."""
+    g, d = _grouped_grad_args(g, saved, w_shape, groups, stride, padding, dilation)
+    lib = native.require()
+    if splits is None:
+        splits = grouped_grad_weight_splits(saved.shape, w_shape, groups, stride, padding, dilation)
+        if splits <= 0:
+            native.check(native.ERR_UNSUPPORTED, "bnn_hip_bconv_grouped_grad_weight_splits")
+    with torch.cuda.device(g.device):
+        part = torch.empty((int(splits), *[int(v) for v in w_shape]), dtype=torch.float32, device=g.device)
+        native.check(lib.bnn_hip_bconv_grouped_grad_weight_f32(
+            ctypes.byref(d), int(groups), g.data_ptr(), saved.sign.P.data_ptr(), saved.sign.M.data_ptr(), part.data_ptr(),
+            int(splits), _stream(g.device)), "bnn_hip_bconv_grouped_grad_weight_f32")
+        if not reduce:
+            return part
+        return part[0] if splits == 1 else part.sum(0)
+
+
 def xnor_what(w: torch.Tensor, center: bool, compute_alpha: bool) -> torch.Tensor:
     """``XNORWeightBinarizer.forward`` value (bnn/ops.py:129-140) in one kernel: ``sign(Wc) * alpha`` as an fp32 tensor
     (no autograd graph).  Same centring / alpha reductions as ``pack_weight``."""

@@ -175,6 +175,10 @@ _PROTOTYPES = {
     "bnn_hip_bconv_grad_weight_splits": (_i, [_i, _i, _i, _i]),
     "bnn_hip_bconv_grad_weight_f32": (_i, [_vp] * 3 + [_i] * 8 + [_vp]),
     "bnn_hip_bconv_grad_weight_packed_f32": (_i, [_vp] * 4 + [_i] * 8 + [_vp]),
+    "bnn_hip_bconv_grouped_grad_supported": (_i, [_conv_p, _i]),
+    "bnn_hip_bconv_grouped_grad_weight_splits": (_i, [_conv_p, _i]),
+    "bnn_hip_bconv_grouped_grad_input_f32": (_i, [_conv_p, _i] + [_vp] * 5),
+    "bnn_hip_bconv_grouped_grad_weight_f32": (_i, [_conv_p, _i] + [_vp] * 4 + [_i, _vp]),
     "bnn_hip_xnor_weight_forward_f32": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "bnn_hip_xnor_weight_backward_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "bnn_hip_bn_act_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),

@@ -22,6 +22,12 @@ forward (``fastpath.packed_weight(..., fresh=True)``).  The forward is ONE launc
 autograd keeps alive; the gradient kernels read the planes (``bnn_hip_bconv_grad_*_packed_f32``) and return the same
 bits as from the fp32 tensor.
 
+Grouped and depthwise layers (``groups > 1``: the BATS cells' ``SepConv`` / ``DilConv``) take the same two autograd
+functions under ``GROUPED``: ``pack_act_ste`` + ``bnn_hip_bconv2d_grouped`` forward, and — where
+``hipops.grouped_grad_supported`` says so — the fp32 VALU gradient kernels of ``csrc/grad_grouped.hip`` on the three bit
+planes, which are then ALL that is kept of the input; other grouped geometries keep the fp32 ``x`` for
+``aten::convolution_backward`` with ``groups``.
+
 Data-parallel training is ordinary ``DistributedDataParallel`` over RCCL (backend ``"nccl"``), one
 process per GPU: the binary layers are ``nn.Module``s with ordinary fp32 Parameters, so gradient
 bucketing / all-reduce needs nothing special (``make_ddp``).
@@ -57,24 +63,78 @@ def saved_input_bytes(reset: bool = False) -> int:
     return n
 
 
-class BinaryConv2dTrainFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w_hat, bias, layer, plan, packed):
-        out = hipops.bconv2d_direct(x, packed, bias, None, layer.stride, layer.padding, layer.dilation)   # one launch
-        stride, padding, dilation = tuple(layer.stride), tuple(layer.padding), tuple(layer.dilation)
-        ctx.x_shape = None
-        if PACKED_STATE and BINARY_GRADS and hipops.grad_supported(x.shape, w_hat.shape, stride, padding, dilation):
+# Grouped / depthwise layers (the BATS cells' SepConv / DilConv) on the HIP path in a training step: pack_act_ste +
+# bnn_hip_bconv2d_grouped forward, the gradient kernels of csrc/grad_grouped.hip backward, the three bit planes as all
+# that is kept of the input.  Off by default (its speed against the library's grouped convolutions is recorded in
+# profiles/grouped_train_bench.jsonl; the default is a later decision); BNN_AMD_TRAIN_GROUPED=1 or
+# `training.GROUPED = True` turns it on — read at every call (fastpath.plan_conv2d_train).
+GROUPED = os.environ.get("BNN_AMD_TRAIN_GROUPED", "0") == "1"
+
+
+def _forward_and_keep(ctx, x, w, bias, layer, packed):
+    """Forward of both autograd functions, and what they keep of ``x`` for the backward (``w``: the tensor saved next to
+    it).  Dense layer: ONE launch, the fp32 ``x`` kept — or, ``PACKED_STATE``, its three bit planes where the gradient
+    kernels cover the geometry.  Grouped layer: the planes are made first (the forward reads the sign planes) and are
+    ALL that is kept where the grouped gradient kernels cover the geometry; otherwise the fp32 ``x`` for the library's
+    backward.  Returns ``(out, (stride, padding, dilation))``."""
+    stride, padding, dilation = tuple(layer.stride), tuple(layer.padding), tuple(layer.dilation)
+    groups = int(layer.groups)
+    sv = None
+    if groups != 1:
+        sv = hipops.pack_act_ste(x)
+        out = hipops.bconv2d_grouped(sv.sign, packed, bias, None, stride, padding, dilation)
+        planes = BINARY_GRADS and hipops.grouped_grad_supported(x.shape, w.shape, groups, stride, padding, dilation)
+    else:
+        out = hipops.bconv2d_direct(x, packed, bias, None, stride, padding, dilation)   # one launch
+        planes = PACKED_STATE and BINARY_GRADS and hipops.grad_supported(x.shape, w.shape, stride, padding, dilation)
+        if planes:
             # the gradient kernels need sign(x) and the mask |x| < 1: three bit planes (3/32 of the fp32 tensor the
             # reference's autograd keeps alive until the backward)
             sv = hipops.pack_act_ste(x)
-            ctx.save_for_backward(sv.sign.P, sv.sign.M, sv.T, w_hat)
-            ctx.x_shape = tuple(x.shape)
-            kept = sv.nbytes()
-        else:
-            ctx.save_for_backward(x, w_hat)
-            kept = x.numel() * x.element_size()
-        global _saved_bytes
-        _saved_bytes += kept
+    if planes:
+        ctx.save_for_backward(sv.sign.P, sv.sign.M, sv.T, w)
+        ctx.x_shape = tuple(x.shape)
+        kept = sv.nbytes()
+    else:
+        ctx.save_for_backward(x, w)
+        ctx.x_shape = None
+        kept = x.numel() * x.element_size()
+    global _saved_bytes
+    _saved_bytes += kept
+    ctx.groups = groups
+    return out, (stride, padding, dilation)
+
+
+def _kept_input(ctx):
+    """``(x, w)`` of ``_forward_and_keep``: ``x`` is the fp32 input or the ``SavedAct`` of its planes."""
+    if ctx.x_shape is None:
+        return ctx.saved_tensors
+    P, M, T, w = ctx.saved_tensors
+    return hipops.SavedAct(hipops.PackedAct(P, M, ctx.x_shape), T, ctx.x_shape), w
+
+
+def _binary_grads(ctx, x, w_shape, stride, padding, dilation) -> bool:
+    """Whether the backward runs on the binary-aware kernels: always when only the planes were kept, else for a dense
+    layer they cover (a grouped layer that kept its fp32 input takes the library's backward)."""
+    return ctx.x_shape is not None or (
+        ctx.groups == 1 and BINARY_GRADS and hipops.grad_supported(x.shape, w_shape, stride, padding, dilation))
+
+
+def _library_backward(ctx, g, x, w_hat, conf, need):
+    """``aten::convolution_backward`` on ``sign(x)`` and the hard-tanh STE mask (bnn/ops.py:68-73)."""
+    stride, padding, dilation, has_bias, bias_shape = conf
+    gx, gw, gb = torch.ops.aten.convolution_backward(
+        g, torch.sign(x), w_hat, list(bias_shape) if has_bias else None, list(stride), list(padding), list(dilation),
+        False, [0, 0], ctx.groups, [bool(v) for v in need])
+    if need[0]:
+        gx = gx.masked_fill(x.abs() >= 1, 0)
+    return gx, gw, gb
+
+
+class BinaryConv2dTrainFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w_hat, bias, layer, plan, packed):
+        out, (stride, padding, dilation) = _forward_and_keep(ctx, x, w_hat, bias, layer, packed)
         ctx.conf = (stride, padding, dilation, bias is not None, None if bias is None else tuple(bias.shape))
         return out
 
@@ -82,29 +142,26 @@ class BinaryConv2dTrainFn(torch.autograd.Function):
     def backward(ctx, g):
         stride, padding, dilation, has_bias, bias_shape = ctx.conf
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]
-        if ctx.x_shape is not None:
-            P, M, T, w_hat = ctx.saved_tensors
-            x = hipops.SavedAct(hipops.PackedAct(P, M, ctx.x_shape), T, ctx.x_shape)
-        else:
-            x, w_hat = ctx.saved_tensors
-        if ctx.x_shape is not None or (
-                BINARY_GRADS and hipops.grad_supported(x.shape, w_hat.shape, stride, padding, dilation)):
-            g = g.contiguous()
+        x, w_hat = _kept_input(ctx)
+        g = g.contiguous()
+        if _binary_grads(ctx, x, w_hat.shape, stride, padding, dilation):
             gx = gw = gb = None
-            if need_x:
-                packed, alpha = hipops.grad_pack_weight(w_hat)
-                gx = hipops.bconv_grad_input(g, x, packed, alpha, w_hat.shape[2], stride[0])   # STE mask fused
-            if need_w:
-                gw = hipops.bconv_grad_weight(g, x, w_hat.shape[2], stride[0])
+            if ctx.groups != 1:
+                geom = (ctx.groups, stride, padding, dilation)
+                if need_x:
+                    gx = hipops.bconv_grouped_grad_input(g, x, w_hat, *geom)                # STE mask fused
+                if need_w:
+                    gw = hipops.bconv_grouped_grad_weight(g, x, w_hat.shape, *geom)
+            else:
+                if need_x:
+                    packed, alpha = hipops.grad_pack_weight(w_hat)
+                    gx = hipops.bconv_grad_input(g, x, packed, alpha, w_hat.shape[2], stride[0])   # STE mask fused
+                if need_w:
+                    gw = hipops.bconv_grad_weight(g, x, w_hat.shape[2], stride[0])
             if need_b:
                 gb = g.sum(dim=(0, 2, 3))
             return gx, gw, gb, None, None, None
-        xh = torch.sign(x)
-        gx, gw, gb = torch.ops.aten.convolution_backward(
-            g.contiguous(), xh, w_hat, list(bias_shape) if has_bias else None, list(stride), list(padding),
-            list(dilation), False, [0, 0], 1, [bool(need_x), bool(need_w), bool(need_b)])
-        if need_x:
-            gx = gx.masked_fill(x.abs() >= 1, 0)   # hard-tanh STE (bnn/ops.py:68-73)
+        gx, gw, gb = _library_backward(ctx, g, x, w_hat, ctx.conf, (need_x, need_w, need_b))
         return (gx if need_x else None, gw if need_w else None, gb if need_b else None, None, None, None)
 
 
@@ -300,19 +357,7 @@ class BinaryConv2dTrainFusedFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, bias, layer, plan, packed):
-        out = hipops.bconv2d_direct(x, packed, bias, None, layer.stride, layer.padding, layer.dilation)   # one launch
-        stride, padding, dilation = tuple(layer.stride), tuple(layer.padding), tuple(layer.dilation)
-        ctx.x_shape = None
-        if PACKED_STATE and BINARY_GRADS and hipops.grad_supported(x.shape, w.shape, stride, padding, dilation):
-            sv = hipops.pack_act_ste(x)
-            ctx.save_for_backward(sv.sign.P, sv.sign.M, sv.T, w)
-            ctx.x_shape = tuple(x.shape)
-            kept = sv.nbytes()
-        else:
-            ctx.save_for_backward(x, w)
-            kept = x.numel() * x.element_size()
-        global _saved_bytes
-        _saved_bytes += kept
+        out, (stride, padding, dilation) = _forward_and_keep(ctx, x, w, bias, layer, packed)
         ctx.conf = (stride, padding, dilation, bias is not None, None if bias is None else tuple(bias.shape),
                     bool(plan.center), bool(plan.compute_alpha))
         return out
@@ -321,39 +366,38 @@ class BinaryConv2dTrainFusedFn(torch.autograd.Function):
     def backward(ctx, g):
         stride, padding, dilation, has_bias, bias_shape, center, compute_alpha = ctx.conf
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]
-        if ctx.x_shape is not None:
-            P, M, T, w = ctx.saved_tensors
-            x = hipops.SavedAct(hipops.PackedAct(P, M, ctx.x_shape), T, ctx.x_shape)
-        else:
-            x, w = ctx.saved_tensors
+        x, w = _kept_input(ctx)
         g = g.contiguous()
         gx = gwhat = gb = None
-        if ctx.x_shape is not None or (
-                BINARY_GRADS and hipops.grad_supported(x.shape, w.shape, stride, padding, dilation)):
-            if need_x:
-                packed, alpha = hipops.xnor_grad_pack_weight(w, center, compute_alpha)   # (one launch, the same bytes)
-                gx = hipops.bconv_grad_input(g, x, packed, alpha, w.shape[2], stride[0])       # STE mask fused
-            if need_w:
-                # the split-K slabs: up to 16 are added inside the hook's kernel (one workgroup per output channel walks them),
-                # the hundreds of a 64-channel layer by the library's parallel reduction
-                gwhat = hipops.bconv_grad_weight(g, x, w.shape[2], stride[0], reduce=False)
-                if gwhat.shape[0] > 16:
-                    gwhat = gwhat.sum(0)
+        if _binary_grads(ctx, x, w.shape, stride, padding, dilation):
+            if ctx.groups != 1:
+                geom = (ctx.groups, stride, padding, dilation)
+                if need_x:      # the grouped kernel reads the fp32 What (wave-uniform per group), not sign fragments
+                    gx = hipops.bconv_grouped_grad_input(g, x, hipops.xnor_what(w, center, compute_alpha), *geom)
+                if need_w:
+                    gwhat = hipops.bconv_grouped_grad_weight(g, x, w.shape, *geom, reduce=False)
+            else:
+                if need_x:
+                    packed, alpha = hipops.xnor_grad_pack_weight(w, center, compute_alpha)   # (one launch, the same bytes)
+                    gx = hipops.bconv_grad_input(g, x, packed, alpha, w.shape[2], stride[0])       # STE mask fused
+                if need_w:
+                    gwhat = hipops.bconv_grad_weight(g, x, w.shape[2], stride[0], reduce=False)
+            # the split-K slabs: up to 16 are added inside the hook's kernel (one workgroup per output channel walks them),
+            # the hundreds of a 64-channel layer by the library's parallel reduction
+            if need_w and gwhat.shape[0] > 16:
+                gwhat = gwhat.sum(0)
             if need_b:
                 gb = g.sum(dim=(0, 2, 3))
         else:
-            w_hat = hipops.xnor_what(w, center, compute_alpha)
-            gx, gwhat, gb = torch.ops.aten.convolution_backward(
-                g, torch.sign(x), w_hat, list(bias_shape) if has_bias else None, list(stride), list(padding),
-                list(dilation), False, [0, 0], 1, [bool(need_x), bool(need_w), bool(need_b)])
-            if need_x:
-                gx = gx.masked_fill(x.abs() >= 1, 0)   # hard-tanh STE (bnn/ops.py:68-73)
+            gx, gwhat, gb = _library_backward(ctx, g, x, hipops.xnor_what(w, center, compute_alpha), ctx.conf[:5],
+                                              (need_x, need_w, need_b))
         gw = hipops.xnor_weight_backward(w, gwhat, center, compute_alpha) if need_w else None
         return (gx if need_x else None, gw, gb if need_b else None, None, None, None)
 
 
 def conv2d_train(layer: nn.Module, x: torch.Tensor, plan, packed) -> torch.Tensor:
-    """``bnn.layers.Conv2d.forward`` with autograd recording: HIP forward, library backward."""
+    """``bnn.layers.Conv2d.forward`` with autograd recording: HIP forward; binary-aware HIP backward where the gradient
+    kernels cover the layer (dense or — ``GROUPED`` — grouped), the library's otherwise."""
     w = layer.weight
     if (FUSED_WEIGHT_HOOK and w.dim() == 4 and w.is_contiguous() and w.shape[2] * w.shape[3] <= 1024
             and not layer.weight_pre_process._forward_hooks and not layer.weight_pre_process._forward_pre_hooks):

@@ -183,6 +183,18 @@ int launch_bconv_grouped_cell(const ConvP& p, int groups, int S, int shuffle_gro
 // with ct_res / ct_add channels
 int launch_bconv_grouped_node(const ConvP& p, int groups, int S, int shuffle_groups, const float* add, int ct_res,
                               int ct_add, hipStream_t s);
+// grad_grouped.hip: the two gradients of a grouped convolution from the saved bit planes (fp32 VALU).  Geometry of a
+// descriptor that passed capi.hip's check_grouped_grad (the one statement of what the kernels cover).
+struct GroupedGradP {
+  int N, C, H, W, O, Ho, Wo, KH, KW;
+  int stride, ph, pw, dh, dw;   // stride_h == stride_w
+  int G;                        // groups; Cg = C / G <= 32, Og = O / G
+};
+int grouped_wgrad_splits(int N, int O, int G, int taps);   // 1 .. min(N, 64)
+int launch_grouped_dgrad(const GroupedGradP& q, const float* g, const float* what, const uint64_t* T, float* gx,
+                         hipStream_t s);
+int launch_grouped_wgrad(const GroupedGradP& q, const float* g, const uint64_t* P, const uint64_t* M, float* part,
+                         int splits, hipStream_t s);
 // bconv_fly.hip: the whole layer in one launch, activations (fp32, or fp16 when x_half) binarised on the fly into LDS.
 // p.P / p.M are unused; p.alpha / bias / scale / out as for launch_bconv.  `plan` may be null (default plan).
 bool fly_supported(const ConvP& p);

@@ -630,6 +630,62 @@ int bnn_hip_bconv_grad_weight_packed_f32(const float* g, const uint64_t* P, cons
   return bnn::launch_wgrad(g, P, M, 1, partial, splits, N, O, C, H, W, ksize, stride, static_cast<hipStream_t>(stream));
 }
 
+// Entry contract of the grouped gradient kernels (csrc/grad_grouped.hip), and the ONE statement of what they cover:
+// groups >= 2 dividing C and O, Cg <= 32 (a thread per channel of the group inside a wave), KH, KW <= 7 (the What tile of
+// 32 output channels fits the LDS), one stride of 1 or 2 for both dimensions; any Og, width, dilation and padding the
+// forward accepts.  g [N,O,Ho,Wo], gx [N,C,H,W] and the weight stay inside the 2^30-element addressing of a launch.
+static int check_grouped_grad(const bnn_hip_conv_desc* d, int groups, bnn::GroupedGradP* q) {
+  int Ho = 0, Wo = 0;
+  const int st = check_desc(d, &Ho, &Wo);
+  if (st != BNN_HIP_OK) return st;
+  if (groups <= 0 || d->C % groups != 0 || d->O % groups != 0) return BNN_HIP_ERR_INVALID_ARG;
+  if (groups == 1) return BNN_HIP_ERR_UNSUPPORTED;   // the dense layers have their own kernels (csrc/grad.hip)
+  if (mulc(d->N, d->C, d->H, d->W) > kMaxConvElems) return BNN_HIP_ERR_TOO_LARGE;
+  if (mulc(d->O, d->C / groups, d->KH, d->KW) > kMaxElems) return BNN_HIP_ERR_TOO_LARGE;
+  if (d->C / groups > 32 || d->KH > 7 || d->KW > 7) return BNN_HIP_ERR_UNSUPPORTED;
+  if (d->stride_h != d->stride_w || d->stride_h > 2) return BNN_HIP_ERR_UNSUPPORTED;
+  *q = bnn::GroupedGradP{d->N, d->C, d->H, d->W, d->O, Ho, Wo, d->KH, d->KW, d->stride_h, d->pad_h, d->pad_w,
+                         d->dil_h, d->dil_w, groups};
+  return BNN_HIP_OK;
+}
+
+int bnn_hip_bconv_grouped_grad_supported(const bnn_hip_conv_desc* d, int groups) {
+  bnn::GroupedGradP q;
+  return check_grouped_grad(d, groups, &q) == BNN_HIP_OK ? 1 : 0;
+}
+
+int bnn_hip_bconv_grouped_grad_weight_splits(const bnn_hip_conv_desc* d, int groups) {
+  bnn::GroupedGradP q;
+  if (check_grouped_grad(d, groups, &q) != BNN_HIP_OK) return 0;
+  return bnn::grouped_wgrad_splits(q.N, q.O, q.G, q.KH * q.KW);
+}
+
+int bnn_hip_bconv_grouped_grad_input_f32(const bnn_hip_conv_desc* d, int groups, const float* g, const float* what,
+                                         const uint64_t* T, float* gx, void* stream) {
+  if (!g || !what || !T || !gx || !aligned(g, 4) || !aligned(what, 4) || !aligned(T, 8) || !aligned(gx, 4))
+    return BNN_HIP_ERR_INVALID_ARG;
+  bnn::GroupedGradP q;
+  const int st = check_grouped_grad(d, groups, &q);
+  if (st != BNN_HIP_OK) return st;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_grouped_dgrad(q, g, what, T, gx, static_cast<hipStream_t>(stream));
+}
+
+int bnn_hip_bconv_grouped_grad_weight_f32(const bnn_hip_conv_desc* d, int groups, const float* g, const uint64_t* P,
+                                          const uint64_t* M, float* partial, int splits, void* stream) {
+  if (!g || !P || !M || !partial || !aligned(g, 4) || !aligned(P, 8) || !aligned(M, 8) || !aligned(partial, 4))
+    return BNN_HIP_ERR_INVALID_ARG;
+  bnn::GroupedGradP q;
+  const int st = check_grouped_grad(d, groups, &q);
+  if (st != BNN_HIP_OK) return st;
+  if (splits < 1 || splits > q.N) return BNN_HIP_ERR_INVALID_ARG;     // (every split holds at least one image)
+  if (splits > 65535) return BNN_HIP_ERR_UNSUPPORTED;                 // (one grid row per split)
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_grouped_wgrad(q, g, P, M, partial, splits, static_cast<hipStream_t>(stream));
+}
+
 int bnn_hip_pack_weight_f32(const float* w, int O, int C, int KH, int KW, int center,
                             int compute_alpha, uint32_t* wbits, uint32_t* wnz, float* alpha,
                             int32_t* zero_flag, void* stream) {

@@ -491,6 +491,29 @@ int bnn_hip_bconv2d_grouped_fused(const bnn_hip_conv_desc* d, int groups, const 
                                   const float* post_scale, const float* prelu, int shuffle_groups,
                                   const float* residual, float* out, void* stream);
 
+/* ---- The gradients of a grouped convolution in a training step (additive entry points of ABI 15;
+ * csrc/grad_grouped.hip).  Both read the bit planes of bnn_hip_pack_act_ste_f32 over all C input channels, never the
+ * fp32 input; plain fp32 arithmetic, no atomics: two runs on the same input give the same bits.
+ *   input gradient   gx[n,c,y,x] = T bit ? sum_{o in group(c)} sum_{ky,kx} g[n,o,qy,qx] what[o, c mod Cg, ky, kx] : +0.0
+ *                    qy = (y + pad_h - dil_h ky) / stride_h where that division is exact and 0 <= qy < Ho (x likewise);
+ *                    what: float32 [O, Cg, KH, KW] (bnn_hip_xnor_weight_forward_f32 of the layer's weight); every
+ *                    element of gx [N,C,H,W] is written.  T = |x| < 1: |x| == 1 is masked (bnn/ops.py:68-73).
+ *   weight gradient  partial[s,o,cg,ky,kx] = sum_{n in split s} sum_{y,x} g[n,o,y,x] sign(x)[n, (o / Og) Cg + cg,
+ *                    stride_h y + dil_h ky - pad_h, stride_w x + dil_w kx - pad_w]   (taps outside the image add nothing)
+ *                    partial: float32 [splits, O, Cg, KH, KW]; split s holds the images [s N / splits, (s + 1) N / splits);
+ *                    the caller adds the slabs (bnn_hip_xnor_weight_backward_f32 does, in slab order).
+ * Covered: groups >= 2 dividing C and O, Cg <= 32, KH, KW <= 7, stride_h == stride_w in {1, 2}; any Og, width, dilation
+ * and padding bnn_hip_bconv2d_grouped accepts; g and gx below 2^30 elements.  groups == 1 is BNN_HIP_ERR_UNSUPPORTED (the
+ * dense layers have bnn_hip_bconv_grad_*); groups <= 0 or not dividing C and O, null or misaligned pointers (planes 8,
+ * fp32 tensors 4 bytes) and splits outside 1 .. N are BNN_HIP_ERR_INVALID_ARG.  d->flags is ignored.
+ * HOST: _supported returns 1 / 0; _weight_splits the library's choice of `splits` (1 .. min(N, 64)), 0 when unsupported. */
+int bnn_hip_bconv_grouped_grad_supported(const bnn_hip_conv_desc* d, int groups);
+int bnn_hip_bconv_grouped_grad_weight_splits(const bnn_hip_conv_desc* d, int groups);
+int bnn_hip_bconv_grouped_grad_input_f32(const bnn_hip_conv_desc* d, int groups, const float* g, const float* what,
+                                         const uint64_t* T, float* gx, void* stream);
+int bnn_hip_bconv_grouped_grad_weight_f32(const bnn_hip_conv_desc* d, int groups, const float* g, const uint64_t* P,
+                                          const uint64_t* M, float* partial, int splits, void* stream);
+
 /* ---- A whole BATS cell (bnn/models/bats.py:9-83) as fused launches: additive entry points of ABI 15. ----
  * A channel-slice view of a contiguous fp32 NCHW tensor: channels [c_offset, c_offset + C) of [N, c_total, H, W] that
  * starts at p (C, N, H, W come from the call).  c_total == 0: the tensor is exactly the C channels used (c_offset must

@@ -450,6 +450,30 @@ int launch_bconv_grouped_node(const ConvP& p, int groups, int S, int shuffle_gro
   check_group_windows(p.O, p.C, groups, S, p.cw32);
   return BNN_HIP_OK;
 }
+// gradients of a grouped convolution (csrc/grad_grouped.hip): the geometry capi.hip's check_grouped_grad states
+static void check_grouped_grad(const GroupedGradP& q) {
+  REQUIRE(q.N > 0 && q.C > 0 && q.H > 0 && q.W > 0 && q.O > 0 && q.Ho > 0 && q.Wo > 0 && q.KH > 0 && q.KW > 0);
+  REQUIRE(q.G >= 2 && q.C % q.G == 0 && q.O % q.G == 0 && q.C / q.G <= 32 && q.KH <= 7 && q.KW <= 7);
+  REQUIRE((q.stride == 1 || q.stride == 2) && q.ph >= 0 && q.pw >= 0 && q.dh > 0 && q.dw > 0);
+  REQUIRE((long long)q.N * q.O * q.Ho * q.Wo <= kConvElems && (long long)q.N * q.C * q.H * q.W <= kConvElems);
+  REQUIRE((long long)q.N * q.H * q.W * ((q.C + 63) / 64) <= kPlaneWords);
+  REQUIRE((long long)q.O * (q.C / q.G) * q.KH * q.KW <= (1LL << 31) - 1);
+}
+int grouped_wgrad_splits(int N, int O, int G, int taps) {
+  REQUIRE(N > 0 && O > 0 && G >= 2 && O % G == 0 && taps > 0 && taps <= 49);
+  return N < 3 ? N : 3;
+}
+int launch_grouped_dgrad(const GroupedGradP& q, const float* g, const float* what, const uint64_t* T, float* gx, hipStream_t) {
+  ++g_reached; check_grouped_grad(q);
+  REQUIRE(g && what && T && gx && al(g, 4) && al(what, 4) && al(T, 8) && al(gx, 4));
+  return BNN_HIP_OK;
+}
+int launch_grouped_wgrad(const GroupedGradP& q, const float* g, const uint64_t* P, const uint64_t* M, float* part, int splits,
+                         hipStream_t) {
+  ++g_reached; check_grouped_grad(q);
+  REQUIRE(g && P && M && part && al(g, 4) && al(P, 8) && al(M, 8) && al(part, 4) && splits >= 1 && splits <= q.N && splits <= 65535);
+  return BNN_HIP_OK;
+}
 int launch_probe_int_alu(int mode, int iters, double* r, double*, hipStream_t) { REQUIRE(iters > 0 && r); (void)mode; return BNN_HIP_OK; }
 int launch_probe_clock(int it, double* mhz, double*, hipStream_t) { REQUIRE(it > 0 && mhz); return BNN_HIP_OK; }
 }  // namespace bnn
@@ -509,7 +533,7 @@ int main(int argc, char** argv) {
   for (long it = 0; it < iters; ++it) {
     ++g_calls;
     int st = 0;
-    switch (rnd() % 51) {
+    switch (rnd() % 53) {
       case 0: { bnn_hip_conv_desc d = pick_desc();
         st = bnn_hip_bconv2d(rnd() % 16 ? &d : nullptr, pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<uint32_t>(),
                              pick_ptr<uint32_t>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), stream);
@@ -719,6 +743,25 @@ int main(int argc, char** argv) {
                                           pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), sg,
                                           rnd() % 3 ? &res : nullptr, rnd() % 3 ? &add : nullptr, const_cast<float*>(out.p),
                                           out.c_offset, out.c_total, stream);
+        break; }
+      case 51: { bnn_hip_conv_desc d = pick_desc();
+        if (rnd() % 2) { d.O = d.C; }
+        const int G = pick_groups(d.C, d.O);
+        const bnn_hip_conv_desc* dp = rnd() % 16 ? &d : nullptr;
+        const int ok = bnn_hip_bconv_grouped_grad_supported(dp, G);
+        if (ok != 0 && ok != 1) broken("grouped grad supported");
+        st = bnn_hip_bconv_grouped_grad_input_f32(dp, G, pick_ptr<float>(), pick_ptr<float>(),
+                                                  pick_ptr<uint64_t>(), pick_ptr<float>(), stream);
+        if (st == BNN_HIP_OK && !ok) broken("grouped input gradient launched on an unsupported geometry");
+        break; }
+      case 52: { bnn_hip_conv_desc d = pick_desc();
+        if (rnd() % 2) { d.O = d.C; }
+        const int G = pick_groups(d.C, d.O);
+        const bnn_hip_conv_desc* dp = rnd() % 16 ? &d : nullptr;
+        const int sp = bnn_hip_bconv_grouped_grad_weight_splits(dp, G);
+        if (sp < 0 || (sp > 0 && sp > d.N) || (sp > 0) != (bnn_hip_bconv_grouped_grad_supported(dp, G) == 1)) broken("grouped grad splits");
+        st = bnn_hip_bconv_grouped_grad_weight_f32(dp, G, pick_ptr<float>(), pick_ptr<uint64_t>(),
+                                                   pick_ptr<uint64_t>(), pick_ptr<float>(), rnd() % 4 ? sp : pick_int(), stream);
         break; }
       default: { bnn_hip_conv_desc d = pick_desc();
         (void)bnn_hip_shortcut_fold_supported(rnd() % 16 ? &d : nullptr, pick_int());
