@@ -18,7 +18,7 @@ launch stores into the node's channel slice of the cell output, so neither the a
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -56,6 +56,17 @@ def _prelu_slopes(act: nn.PReLU, channels: int) -> torch.Tensor:
     """The PReLU slopes as a vector of ``channels``: a snapshot, like the folded BatchNorm and the packed weight."""
     slope = act.weight.detach().float().reshape(-1)
     return (slope.expand(channels) if slope.numel() == 1 else slope).clone()
+
+
+class Preprocessor(NamedTuple):
+    """What ``FusedCell.preprocessor(i)`` tells about ``preprocess{i}``: ``kind`` is ``ReLUConvBN`` or
+    ``FactorizedReduce``; ``bn_a`` / ``bn_b`` the folded BatchNorm in front of its sign(); ``add_skip`` whether it adds its
+    fp32 input (a ``FactorizedReduce`` always reads it: it packs for itself)."""
+    kind: str
+    bn_a: torch.Tensor
+    bn_b: torch.Tensor
+    add_skip: bool
+    C_in: int
 
 
 class _Executor(nn.Module):
@@ -330,8 +341,7 @@ class FusedCell(_Executor):
         # -- the two input states
         for i, pre in enumerate(self._pre):
             if isinstance(pre, FusedCellOp):
-                add("pack", {"op": f"preprocess{i}", "sets": 1},
-                    lambda env, i=i, pre=pre: env["planes"].__setitem__(("pre", i), pre.pack(env["in"][i])))
+                add("pack", {"op": f"preprocess{i}", "sets": 1}, lambda env, i=i, pre=pre: self._pre_pack(env, i, pre))
                 add("dense", {"op": f"preprocess{i}"}, lambda env, i=i, pre=pre: env["state"].__setitem__(
                     i, pre.conv(env["planes"][("pre", i)], env["in"][i])))
             else:
@@ -420,6 +430,12 @@ class FusedCell(_Executor):
 
     # ---- the steps ------------------------------------------------------------------------------------------------
     @staticmethod
+    def _pre_pack(env, i: int, pre: FusedCellOp) -> None:
+        """The ``pack`` step of preprocessor ``i``; nothing to do when the caller handed its planes over."""
+        if ("pre", i) not in env["planes"]:
+            env["planes"][("pre", i)] = pre.pack(env["in"][i])
+
+    @staticmethod
     def _same(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
         if a.shape != b.shape:
             raise FusionError(f"cell: the two terms of a node have shapes {tuple(a.shape)} and {tuple(b.shape)}")
@@ -460,17 +476,53 @@ class FusedCell(_Executor):
                 raise FusionError(f"cell: operation {k} gives {shape}, its node holds {tuple(t.shape)}")
         return e.conv_node(planes, x, addend, out)
 
+    # ---- what a caller that packs for the cell needs to know ------------------------------------------------------
+    def preprocessor(self, i: int) -> "Preprocessor":
+        """Kind, folded BatchNorm and skip of ``preprocess{i}`` (current as of the last ``refresh()``)."""
+        pre = self._pre[i]
+        if isinstance(pre, FusedCellOp):
+            return Preprocessor("ReLUConvBN", pre.bn_a, pre.bn_b, pre.add_skip, pre.model.op[1].in_channels)
+        return Preprocessor("FactorizedReduce", pre.bn_a, pre.bn_b, False, pre.C_in)
+
+    def _handed(self, i: int, s: Optional[torch.Tensor], p) -> tuple:
+        """Checks input ``i`` and the planes handed over for it; returns its (device, batch size)."""
+        pre = self.preprocessor(i)
+        if p is None:
+            if s is None:
+                raise FusionError(f"cell: input {i} is missing and no planes were handed over for it")
+            self._check_inputs(s)
+            return s.device, s.shape[0]
+        if pre.kind != "ReLUConvBN":
+            raise FusionError(f"cell: preprocess{i} is a FactorizedReduce, which packs for itself")
+        if not isinstance(p, hipops.PackedAct) or p.shape[1] != pre.C_in or not p.P.is_cuda:
+            raise FusionError(f"cell: planes[{i}] must be a PackedAct of {pre.C_in} channels on a HIP device")
+        if s is None:
+            if pre.add_skip:
+                raise FusionError(f"cell: preprocess{i} adds its input, so input {i} is needed next to its planes")
+        else:
+            self._check_inputs(s)
+            if tuple(s.shape) != tuple(p.shape) or s.device != p.P.device:
+                raise FusionError(f"cell: planes[{i}] are not those of input {i}")
+        return p.P.device, p.shape[0]
+
     # ---- forward --------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def forward(self, s0: torch.Tensor, s1: torch.Tensor) -> torch.Tensor:
-        self._check_inputs(s0, s1)
-        if s0.device != s1.device or s0.shape[0] != s1.shape[0]:
-            raise FusionError("cell: the two inputs differ in device or batch size")
+    def forward(self, s0: Optional[torch.Tensor], s1: Optional[torch.Tensor], planes=None) -> torch.Tensor:
+        """``cell(s0, s1, 0.0)``.  ``planes``: a pair with, per input, ``None`` or the ``PackedAct`` of
+        ``sign(BatchNorm(s_i))`` made with ``preprocessor(i)``'s ``bn_a`` / ``bn_b`` by somebody who packs one tensor for
+        several cells; that ``ReLUConvBN`` then skips its own pack, and ``s_i`` may be ``None`` unless it adds a skip."""
         if not self._unchanged():
             self.refresh()
-        if next(self.model.parameters()).device != s0.device:
+        planes = (None, None) if planes is None else tuple(planes)
+        if len(planes) != 2:
+            raise FusionError("cell: planes is a pair, one entry per input")
+        (d0, n0), (d1, n1) = self._handed(0, s0, planes[0]), self._handed(1, s1, planes[1])
+        if d0 != d1 or n0 != n1:
+            raise FusionError("cell: the two inputs differ in device or batch size")
+        if next(self.model.parameters()).device != d0:
             raise FusionError("cell: module and input live on different devices")
-        env = {"in": (s0, s1), "state": [None] * self._n_states, "planes": {}, "tmp": {}, "out": None}
+        env = {"in": (s0, s1), "state": [None] * self._n_states,
+               "planes": {("pre", i): p for i, p in enumerate(planes) if p is not None}, "tmp": {}, "out": None}
         for _, _, run in self._plan:
             run(env)
         fastpath._bump("cell")

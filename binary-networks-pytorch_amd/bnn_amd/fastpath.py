@@ -31,6 +31,7 @@ from __future__ import annotations
 import os
 import threading
 import warnings
+import weakref
 from dataclasses import dataclass
 from typing import Optional
 
@@ -252,6 +253,29 @@ def _replica_packed_weight(layer, master, plan: Plan, fresh: bool = False) -> hi
 BLOCK_KEY, OP_KEY, CELL_KEY = TIER_KEYS = ("_bnn_auto_block", "_bnn_auto_op", "_bnn_auto_cell")
 
 
+# ``model.__dict__`` key under which the explicit whole-network executors built for a model (batsnet.FusedBATSNetwork) are
+# remembered, weakly, so that ``invalidate(model)`` reaches them
+WATCH_KEY = "_bnn_watchers"
+
+
+class _Watchers:
+    """Weak set of the executors to mark stale; a copied or pickled model starts with none."""
+
+    def __init__(self) -> None:
+        self.refs = weakref.WeakSet()
+
+    def __deepcopy__(self, memo) -> "_Watchers":
+        return _Watchers()
+
+    def __reduce__(self):
+        return (_Watchers, ())
+
+
+def watch(model: nn.Module, executor) -> None:
+    """``invalidate(model)`` (or of a module that contains it) will call ``executor.mark_stale()``."""
+    model.__dict__.setdefault(WATCH_KEY, _Watchers()).refs.add(executor)
+
+
 def drop_executor(m: nn.Module) -> None:
     """Drop the fused executor ``m`` itself dispatches to (not those of its sub-modules): derived data goes with a
     ``train()`` <-> ``eval()`` switch."""
@@ -271,6 +295,8 @@ def invalidate(module: nn.Module, executors: bool = True) -> int:
         m.__dict__.pop("_bnn_packed_replicas", None)
         if executors:       # (an executor that re-derives ITSELF (refresh) passes False: it may be that very object)
             drop_executor(m)
+            for ex in tuple(getattr(m.__dict__.get(WATCH_KEY), "refs", ())):
+                ex.mark_stale()
     from .tails import drop_derived                 # folded BatchNorms / transposed head weights of the per-layer tails
     drop_derived(module)
     return n

@@ -258,6 +258,61 @@ def bn_act_pack_s2(x: torch.Tensor, bn_scale=None, bn_shift=None, relu: bool = F
     return tuple(PackedAct(P[k], M[k], (N, C, H // 2, W // 2), bool(relu)) for k in range(2))
 
 
+_STEM3X3_MAX_ELEMS = (1 << 31) - 1      # fp32 elements of x or y one stem3x3 launch covers (capi.hip: kMaxElems)
+
+
+def stem3x3_bn_relu_pack(x: torch.Tensor, w: torch.Tensor, bn_scale: torch.Tensor, bn_shift: torch.Tensor, pack_scales,
+                         pack_shifts, out_f32: bool = True):
+    """The real-valued stem of a BATS CIFAR network with the binarisation of its ``K`` consumers in one launch
+    (``bnn_hip_stem3x3_bn_relu_pack_f32``): ``y = relu(bn(conv3x3(x)))`` for ``x`` ``[N, 3, H, W]``, ``w`` ``[O, 3, 3, 3]``
+    (stride 1, padding 1, no bias) and the folded BatchNorm ``bn_scale`` / ``bn_shift`` ``[O]``; ``pack_scales`` /
+    ``pack_shifts`` are ``[K, O]`` (or sequences of ``K`` vectors), ``1 <= K <= 4``.  Returns ``(y | None, [K PackedAct])``
+    where set ``k`` holds the bits of ``bn_act_pack_multi(y, pack_scales, pack_shifts)[k]``; ``out_f32=False``: ``y`` is
+    not written.  A batch whose ``x`` or ``y`` would reach 2^31 elements is cut into several launches."""
+    x = _require_cuda_f32(x, "stem input")
+    w = _require_cuda_f32(w.detach(), "stem weight")
+    if x.dim() != 4 or x.shape[1] != 3 or w.dim() != 4 or tuple(w.shape[1:]) != (3, 3, 3):
+        raise native.NativeError(f"bnn_amd: stem3x3 expects x [N,3,H,W] and w [O,3,3,3], got {tuple(x.shape)} and "
+                                 f"{tuple(w.shape)}")
+    N, _, H, W = x.shape
+    O = w.shape[0]
+    bn_scale, bn_shift = _per_channel(bn_scale, O, "bn_scale"), _per_channel(bn_shift, O, "bn_shift")
+
+    def table(v, what):
+        v = torch.stack([_per_channel(e, O, what) for e in v]) if isinstance(v, (list, tuple)) else v
+        v = _require_cuda_f32(v.detach(), what)
+        if v.dim() != 2 or v.shape[1] != O:
+            raise native.NativeError(f"bnn_amd: {what} must be [K, {O}]")
+        return v
+    a, b = table(pack_scales, "pack_scales"), table(pack_shifts, "pack_shifts")
+    K = a.shape[0]
+    if not 1 <= K <= 4 or b.shape[0] != K:
+        raise native.NativeError(f"bnn_amd: stem3x3 takes 1..4 affines, got {K} / {b.shape[0]}")
+    lib = native.require()
+    cw64 = (O + 63) // 64
+    step = max(1, min(N, _STEM3X3_MAX_ELEMS // (max(O, 3) * H * W)))
+    with torch.cuda.device(x.device):
+        y = torch.empty((N, O, H, W), dtype=torch.float32, device=x.device) if out_f32 else None
+        parts = []
+        for n0 in range(0, N, step):            # (one launch unless the batch is cut: a plane set is [n, cw64, H, W])
+            n = min(step, N - n0)
+            P = torch.empty((K, n, cw64, H, W), dtype=torch.int64, device=x.device)
+            M = torch.empty_like(P)
+            native.check(lib.bnn_hip_stem3x3_bn_relu_pack_f32(
+                x[n0:n0 + n].data_ptr(), w.data_ptr(), bn_scale.data_ptr(), bn_shift.data_ptr(), a.data_ptr(), b.data_ptr(),
+                n, O, H, W, K, P.data_ptr(), M.data_ptr(), None if y is None else y[n0:n0 + n].data_ptr(),
+                _stream(x.device)), "bnn_hip_stem3x3_bn_relu_pack_f32")
+            parts.append((P, M))
+        if len(parts) == 1:
+            P, M = parts[0]
+        elif parts:
+            P, M = torch.cat([p for p, _ in parts], 1), torch.cat([m for _, m in parts], 1)
+        else:
+            P = torch.empty((K, 0, cw64, H, W), dtype=torch.int64, device=x.device)
+            M = torch.empty_like(P)
+    return y, [PackedAct(P[k], M[k], (N, O, H, W), False) for k in range(K)]
+
+
 def avgpool_pack(x: torch.Tensor, k: int, nonneg: bool = False) -> PackedAct:
     """``AvgPool2d(k, k, ceil_mode=True, count_include_pad=False)`` + sign, fused
     (shortcut branch of bnn/models/resnet.py:128-133).  ``nonneg``: the caller knows ``x >= 0``

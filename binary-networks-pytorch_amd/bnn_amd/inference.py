@@ -15,6 +15,8 @@ The implementation lives in five modules (round 5: this file used to hold all of
                                                                             are one class, ``_TierFusion``)
     cellops.py    FusedCellOp, FusedCell                                    a BATS cell operation in two launches; a
                                                                             whole cell with its adds and its concat in them
+    batsnet.py    FusedBATSNetwork                                          a whole BATS network: stem kernel, planes packed
+                                                                            once per tensor for all cells, head, HIP graph
 
 ``from bnn_amd.inference import FusedResNet`` etc. keep working; module-level state (``_LIBRARY_TAILS`` ...) is read
 through to the module that owns it.
@@ -25,6 +27,7 @@ from . import dispatch as _dispatch
 from . import executor as _executor
 from . import pipeline as _pipeline
 from . import tails as _tails
+from .batsnet import FusedBATSNetwork  # noqa: F401
 from .cellops import FusedCell, FusedCellOp  # noqa: F401
 from .dispatch import (AutoFusion, BlockFusion, CellFusion, OpFusion, auto_block_forward,  # noqa: F401
                        auto_cell_forward, auto_forward, auto_fusion, auto_op_forward, install_auto_fusion,

@@ -139,6 +139,7 @@ _PROTOTYPES = {
     "bnn_hip_bn_act_pack_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "bnn_hip_bn_act_pack_multi_f32": (_i, [_view_p, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "bnn_hip_bn_act_pack_s2_f32": (_i, [_view_p, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "bnn_hip_stem3x3_bn_relu_pack_f32": (_i, [_vp] * 6 + [_i] * 5 + [_vp] * 4),
     "bnn_hip_avgpool_pack_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "bnn_hip_avgpool2_bn_pack2_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "bnn_hip_orpool_packed": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),

@@ -124,6 +124,11 @@ int launch_bn_act_pack_multi(const float* x, int c_off, int c_tot, int N, int C,
                              const float* shift, int relu, uint64_t* P, uint64_t* M, hipStream_t stream);
 int launch_bn_act_pack_s2(const float* x, int c_off, int c_tot, int N, int C, int H, int W, const float* bn_a,
                           const float* bn_b, int relu, uint64_t* P, uint64_t* M, hipStream_t stream);
+// bats_stem.hip: Conv2d(3, O, 3, padding 1) -> folded BatchNorm -> ReLU and K plane sets [K][N][cw64][H][W] of its output
+// (pk_a / pk_b [K][O]) in one launch; y (fp32 [N, O, H, W]) may be null
+int launch_stem3x3_bn_relu_pack(const float* x, const float* w, const float* bn_s, const float* bn_t, const float* pk_a,
+                                const float* pk_b, int N, int O, int H, int W, int K, uint64_t* P, uint64_t* M, float* y,
+                                hipStream_t stream);
 int launch_avgpool_pack(const float* x, int N, int C, int H, int W, int k, uint64_t* P, uint64_t* M,
                         hipStream_t stream);
 int launch_avgpool2_bn_pack2(const float* x, int N, int C, int H, int W, const float* a1, const float* b1, int relu1,

@@ -385,6 +385,22 @@ int bnn_hip_bn_act_pack_s2_f32(const bnn_hip_f32_view* x, int N, int C, int H, i
                                     static_cast<hipStream_t>(stream));
 }
 
+int bnn_hip_stem3x3_bn_relu_pack_f32(const float* x, const float* w, const float* bn_scale, const float* bn_shift,
+                                     const float* pack_scale, const float* pack_shift, int N, int O, int H, int W, int K,
+                                     uint64_t* P, uint64_t* M, float* y, void* stream) {
+  if (!w || !bn_scale || !bn_shift || !pack_scale || !pack_shift || K < 1 || K > 4) return BNN_HIP_ERR_INVALID_ARG;
+  const int st = check_pack(x, 4, N, O, H, W, P, M);     // (the planes are those of the O output channels)
+  if (st != BNN_HIP_OK) return st;
+  if (mulc(N, O, H, W) > kMaxElems || mulc(N, 3, H, W) > kMaxElems) return BNN_HIP_ERR_TOO_LARGE;
+  if (!aligned(w, 4) || !aligned(bn_scale, 4) || !aligned(bn_shift, 4) || !aligned(pack_scale, 4) ||
+      !aligned(pack_shift, 4) || (y && !aligned(y, 4)))
+    return BNN_HIP_ERR_INVALID_ARG;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_stem3x3_bn_relu_pack(x, w, bn_scale, bn_shift, pack_scale, pack_shift, N, O, H, W, K, P, M, y,
+                                          static_cast<hipStream_t>(stream));
+}
+
 int bnn_hip_avgpool_pack_f32(const float* x, int N, int C, int H, int W, int k, uint64_t* P,
                              uint64_t* M, void* stream) {
   if (!x || !P || !M || N <= 0 || C <= 0 || H <= 0 || W <= 0 || k <= 0) return BNN_HIP_ERR_INVALID_ARG;

@@ -67,7 +67,8 @@ extern "C" {
  * convolutions: additive entry points of ABI 15, no struct or signature changed); + bnn_hip_bconv2d_grouped_fused (the
  * same convolution with PReLU, channel shuffle and skip connection in its launch: additive too);
  * + bnn_hip_f32_view, bnn_hip_bn_act_pack_multi_f32, bnn_hip_bn_act_pack_s2_f32, bnn_hip_bconv2d_grouped_node (a whole
- * BATS cell as fused launches: additive as well).
+ * BATS cell as fused launches: additive as well); + bnn_hip_stem3x3_bn_relu_pack_f32 (the real-valued stem of a BATS
+ * CIFAR network with the sign planes of its consumers in one launch: additive too).
  * ABI 14 (round 5): + bnn_hip_stem7x7_wgrad_f32 / bnn_hip_stem7x7_wgrad_workspace_bytes (weight gradient of the stem
  * convolution: the training backward of that layer); + bnn_hip_avgpool2x2_backward_f32, bnn_hip_xnor_grad_pack_weight_f32; + bnn_hip_avgpool_fc_ws_f32 / bnn_hip_avgpool_fc_workspace_bytes (the head as two streaming launches
  * through a workspace); + bnn_hip_stem7x7_conv_f32 (the stem's convolution alone: the training forward); the table of bnn_hip_sign_thresholds_f32 holds FOUR words per channel (was two) and kmax < 2^20.
@@ -548,6 +549,19 @@ int bnn_hip_bconv2d_grouped_node(const bnn_hip_conv_desc* d, int groups, const u
                                  const float* post_scale, const float* prelu, int shuffle_groups,
                                  const bnn_hip_f32_view* residual, const bnn_hip_f32_view* addend, float* out,
                                  int out_c_offset, int out_c_total, void* stream);
+
+/* ---- The real-valued stem of a BATS CIFAR network with the binarisation of its consumers (additive, ABI 15). ----
+ * Conv2d(3, O, 3, stride 1, padding 1, no bias) -> folded BatchNorm -> ReLU (bnn/models/bats.py:118-122), and K plane
+ * sets of the result, one per ReLUConvBN that reads it (bats_ops.py:78-105), in one launch:
+ *     acc = 0;  over (c, kh, kw) in that order:  acc = fmaf(x[n,c,y+kh-1,x+kw-1], w[o,c,kh,kw], acc)   (padding: x = 0)
+ *     v   = fmaxf(fmaf(acc, bn_scale[o], bn_shift[o]), 0)
+ *     plane set k = the bits of bnn_hip_bn_act_pack_multi_f32 on v with pack_scale[k][o] / pack_shift[k][o], relu = 0
+ * x: [N,3,H,W]; w: [O,3,3,3]; pack_scale / pack_shift: [K][O], 1 <= K <= 4; P / M: [K][N][ceil(O/64)][H][W] uint64
+ * (8-byte aligned).  y: fp32 [N,O,H,W] receives v, or NULL: v is not written.  N*O*H*W and N*3*H*W stay below 2^31
+ * (BNN_HIP_ERR_TOO_LARGE: split the batch).                                                                            */
+int bnn_hip_stem3x3_bn_relu_pack_f32(const float* x, const float* w, const float* bn_scale, const float* bn_shift,
+                                     const float* pack_scale, const float* pack_shift, int N, int O, int H, int W, int K,
+                                     uint64_t* P, uint64_t* M, float* y, void* stream);
 
 /* Binary fully-connected layer: x packed as [B][ceil(F/64)] planes (pack_act with
  * H=W=1, i.e. [B][ceil(F/64)] words), weight packed with KH=KW=1.  out: float32 [B,O].                         */

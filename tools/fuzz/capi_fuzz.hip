@@ -102,6 +102,13 @@ int launch_bn_act_pack_s2(const float* x, int c_off, int c_tot, int N, int C, in
   ++g_reached; check_view_planes(x, c_off, c_tot, N, C, H, W, P, M);
   REQUIRE(H % 2 == 0 && W % 2 == 0 && (a == nullptr) == (b == nullptr)); return BNN_HIP_OK;
 }
+int launch_stem3x3_bn_relu_pack(const float* x, const float* w, const float* s, const float* t, const float* a, const float* b,
+                                int N, int O, int H, int W, int K, uint64_t* P, uint64_t* M, float* y, hipStream_t) {
+  ++g_reached; check_planes(x, N, O, H, W, P, M, 4);
+  REQUIRE(w && s && t && a && b && K >= 1 && K <= 4 && (!y || al(y, 4)));
+  REQUIRE((long long)N * O * H * W <= (1LL << 31) - 1 && 3LL * N * H * W <= (1LL << 31) - 1);
+  return BNN_HIP_OK;
+}
 int launch_avgpool_pack(const float* x, int N, int C, int H, int W, int k, uint64_t* P, uint64_t* M, hipStream_t) {
   ++g_reached; REQUIRE(x && P && M && N > 0 && C > 0 && H > 0 && W > 0 && k > 0 && al(P, 8) && al(M, 8)); return BNN_HIP_OK;
 }
@@ -533,7 +540,7 @@ int main(int argc, char** argv) {
   for (long it = 0; it < iters; ++it) {
     ++g_calls;
     int st = 0;
-    switch (rnd() % 53) {
+    switch (rnd() % 54) {
       case 0: { bnn_hip_conv_desc d = pick_desc();
         st = bnn_hip_bconv2d(rnd() % 16 ? &d : nullptr, pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<uint32_t>(),
                              pick_ptr<uint32_t>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), stream);
@@ -763,6 +770,11 @@ int main(int argc, char** argv) {
         st = bnn_hip_bconv_grouped_grad_weight_f32(dp, G, pick_ptr<float>(), pick_ptr<uint64_t>(),
                                                    pick_ptr<uint64_t>(), pick_ptr<float>(), rnd() % 4 ? sp : pick_int(), stream);
         break; }
+      case 53: st = bnn_hip_stem3x3_bn_relu_pack_f32(pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(),
+                                                     pick_ptr<float>(), pick_ptr<float>(), pick_int(), pick_int(), pick_int(),
+                                                     pick_int(), rnd() % 4 ? 1 + (int)(rnd() % 4) : pick_int(),
+                                                     pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<float>(), stream);
+        break;
       default: { bnn_hip_conv_desc d = pick_desc();
         (void)bnn_hip_shortcut_fold_supported(rnd() % 16 ? &d : nullptr, pick_int());
         st = bnn_hip_blinear(pick_int(), pick_int(), pick_int(), pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<uint32_t>(),
