@@ -7,6 +7,9 @@ preprocessors only take ``sign(BatchNorm(.))`` of.  ``FusedBATSNetwork(net)`` pl
 * the real-valued CIFAR stem (``Conv2d(3, 3C, 3, padding=1)`` -> BatchNorm -> ReLU) is ONE launch that leaves the sign
   planes of all its ``ReLUConvBN`` consumers and, only if somebody reads it, the fp32 tensor
   (``hipops.stem3x3_bn_relu_pack``, csrc/bats_stem.hip);
+* the two real-valued ImageNet stems are one launch each: ``stem0`` with its 112 x 112 intermediate in LDS
+  (``hipops.stem_s2x2``), ``stem1`` with the sign planes of its ``ReLUConvBN`` consumers (``hipops.gconv3x3s2_bn_pack``;
+  csrc/bats_stem_in.hip); ``FUSE_IMAGENET_STEMS = False`` keeps them as modules;
 * every other tensor between cells is packed once, for all the ``ReLUConvBN`` that read it (``bn_act_pack_multi``), and
   the planes are handed to the cells (``FusedCell.forward(s0, s1, planes=...)``);
 * global pooling + a real-valued classifier is the head kernel (``hipops.avgpool_fc``);
@@ -28,8 +31,10 @@ from .executor import FusionError, _is_float_layer, _is_float_layer_linear, fold
 NETWORKS = {"BATSNetworkCIFAR": ("stem",), "BATSNetworkImageNet": ("stem0", "stem1")}
 # kernel launches (native.launch_count()) per step kind; the other kinds are torch calls, or modules that dispatch
 # themselves.  The head is two streaming launches through a workspace (bnn_hip_avgpool_fc_ws_f32).
-LAUNCHES = {"stem3x3": 1, "pack_handoff": 1, "pack": 1, "pack_s2": 1, "pack_multi": 1, "dense": 1, "grouped_node": 1,
+LAUNCHES = {"stem3x3": 1, "stem_s2x2": 1, "stem_s2_pack": 1, "pack_handoff": 1, "pack": 1, "pack_s2": 1, "pack_multi": 1, "dense": 1, "grouped_node": 1,
             "avgpool_fc": 2}
+# the fused plan of the real-valued ImageNet stems (read at refresh()); False: stem0 / stem1 run as modules
+FUSE_IMAGENET_STEMS = True
 # widest classifier input the two-launch head covers: 64 bytes of LDS per feature (csrc/tail.hip: avgpool_fc_ws_supported)
 _HEAD_MAX_FEATURES = (160 * 1024 - 1024) // 64
 
@@ -48,7 +53,7 @@ class FusedBATSNetwork(_Executor):
     unrecognised raise ``FusionError``.
 
     ``steps`` lists the plan as ``(kind, detail)``: ``stem3x3`` (``sets`` plane sets, ``y``: whether the fp32 tensor is
-    written) or ``module`` (a stem, pooling or classifier that runs by calling the module and so takes whatever path its
+    written), ``stem_s2x2`` + ``stem_s2_pack`` (the ImageNet stems; ``sets`` / ``y`` / ``consumers`` of ``stem1``) or ``module`` (a stem, pooling or classifier that runs by calling the module and so takes whatever path its
     layers dispatch to); ``pack_handoff`` (one ``bn_act_pack_multi`` of a stem or cell output ``of`` for its ``sets``
     ``ReLUConvBN`` ``consumers``, given as ``(cell, input)``); the steps of every cell with ``cell`` in the detail (without
     the ``pack`` of a preprocessor whose planes are handed over); ``avgpool_fc``.  ``LAUNCHES`` maps the kinds
@@ -88,6 +93,37 @@ class FusedBATSNetwork(_Executor):
                 or bn.num_features != conv.out_channels or not 1 <= n_sets <= MAX_PACK_SETS):
             return None
         return conv, bn
+
+    def _stems_s2(self, stem0: nn.Module, stem1: nn.Module):
+        """``(conv0, bn0, conv1, bn1, conv2, bn2, inplace)`` when the ImageNet stems are what ``stem_s2x2`` and
+        ``gconv3x3s2_bn_pack`` compute (``inplace``: the ReLU at the head of ``stem1`` rewrites ``stem0``'s output), else
+        None: they run as modules."""
+        kinds0, kinds1 = (nn.Conv2d, nn.BatchNorm2d, nn.ReLU, nn.Conv2d, nn.BatchNorm2d), (nn.ReLU, nn.Conv2d, nn.BatchNorm2d)
+        if not (FUSE_IMAGENET_STEMS and isinstance(stem0, nn.Sequential) and isinstance(stem1, nn.Sequential)
+                and len(stem0) == len(kinds0) and len(stem1) == len(kinds1)):
+            return None
+        for mod, kind in list(zip(stem0, kinds0)) + list(zip(stem1, kinds1)):
+            if not (isinstance(mod, kind) if kind is nn.Conv2d else type(mod) is kind):
+                return None
+        conv0, bn0, _, conv1, bn1 = stem0
+        relu, conv2, bn2 = stem1
+        for conv, bn in ((conv0, bn0), (conv1, bn1), (conv2, bn2)):
+            if not (_is_float_layer(conv) and tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (2, 2)
+                    and tuple(conv.padding) == (1, 1) and tuple(conv.dilation) == (1, 1) and conv.padding_mode == "zeros"
+                    and conv.weight.dtype == torch.float32 and conv.bias is None):
+                return None
+            if (bn.running_mean is None or bn.running_var is None or bn.running_var.dtype != torch.float32
+                    or bn.num_features != conv.out_channels):
+                return None
+        if not (conv0.in_channels == 3 and conv0.groups == 1 and conv1.in_channels == conv0.out_channels
+                and conv2.in_channels == conv1.out_channels):
+            return None
+        # what the kernels cover (BNN_HIP_ERR_UNSUPPORTED otherwise): a group's input channels in LDS, groups / words in grid.y
+        if (conv1.in_channels // conv1.groups > native.STEM_S2X2_MAX_GROUP_CHANNELS or conv1.groups > 65535
+                or conv2.in_channels // conv2.groups > native.GCONV3X3S2_MAX_GROUP_CHANNELS
+                or (conv2.out_channels + 63) // 64 > 65535):
+            return None
+        return conv0, bn0, conv1, bn1, conv2, bn2, bool(relu.inplace)
 
     def _head(self, pool: nn.Module, fc: nn.Module):
         """The pooling window the head kernel needs (None: any map, an int k: a k x k map), or False: modules."""
@@ -154,7 +190,31 @@ class FusedBATSNetwork(_Executor):
         # -- the stems
         rcb, a, b, f32 = handoff(0)
         fused_stem = self._stem3x3(getattr(m, stems[0]), len(rcb)) if S == 1 else None
-        if fused_stem is not None:
+        fused_s2 = self._stems_s2(m.stem0, m.stem1) if stems == NETWORKS["BATSNetworkImageNet"] else None
+        if fused_s2 is not None:
+            conv0, bn0, conv1, bn1, conv2, bn2, inplace = fused_s2
+            (s1, t1), (s2, t2), (s3, t3) = fold_bn(bn0), fold_bn(bn1), fold_bn(bn2)
+
+            # stem1's in-place ReLU rewrites s0 before any cell reads it: the cells then see relu(s0), written directly
+            def run_stem0(env, s1=s1, t1=t1, s2=s2, t2=t2):
+                env["t"][0] = hipops.stem_s2x2(env["x"], conv0.weight, s1, t1, conv1.weight, s2, t2, conv1.groups,
+                                               relu_out=inplace)
+            add("stem_s2x2", {"relu_out": inplace}, run_stem0)
+            rcb, a, b, f32 = handoff(1)
+            packs = 1 <= len(rcb) <= MAX_PACK_SETS       # (more consumers: fp32 only, plan_pack binarises)
+            f32 = f32 or not packs
+
+            def run_stem1(env, s3=s3, t3=t3, a=a if packs else None, b=b if packs else None, rcb=rcb, f32=f32):
+                y, sets = hipops.gconv3x3s2_bn_pack(env["t"][0], conv2.weight, s3, t3, conv2.groups, a, b,
+                                                    relu_in=not inplace, out_f32=f32)
+                env["t"][1] = y
+                env["planes"].update(zip(rcb, sets))
+            add("stem_s2_pack", {"sets": len(rcb) if packs else 0, "y": f32, "consumers": list(rcb) if packs else []},
+                run_stem1)
+            plan_pack(0)
+            if not packs:
+                plan_pack(1)
+        elif fused_stem is not None:
             conv, bn = fused_stem
             s, t = fold_bn(bn)
 

@@ -208,6 +208,15 @@ def _view_struct(t: torch.Tensor, what: str):
     return native.F32View(base.data_ptr(), c_off, c_total), base
 
 
+def _affine_table(v, n: int, what: str) -> torch.Tensor:
+    """``K`` per-channel affine vectors as one fp32 ``[K, n]`` tensor on the device (a sequence of vectors is stacked)."""
+    v = torch.stack([_per_channel(e, n, what) for e in v]) if isinstance(v, (list, tuple)) else v
+    v = _require_cuda_f32(v.detach(), what)
+    if v.dim() != 2 or v.shape[1] != n:
+        raise native.NativeError(f"bnn_amd: {what} must be [K, {n}]")
+    return v
+
+
 def bn_act_pack_multi(x: torch.Tensor, bn_scales, bn_shifts, relu: bool = False) -> list:
     """``K`` plane sets ``sign(bn_k(x))`` from ONE read of ``x`` (``bnn_hip_bn_act_pack_multi_f32``, ``1 <= K <= 4``):
     ``bn_scales`` / ``bn_shifts`` are ``[K, C]`` (or sequences of ``K`` vectors).  ``x`` may be a channel slice of a wider
@@ -215,14 +224,7 @@ def bn_act_pack_multi(x: torch.Tensor, bn_scales, bn_shifts, relu: bool = False)
     ``bn_act_pack(x.contiguous(), scale_k, shift_k, relu)``."""
     view, _keep = _view_struct(x, "activation")
     N, C, H, W = x.shape
-
-    def table(v, what):
-        v = torch.stack([_per_channel(e, C, what) for e in v]) if isinstance(v, (list, tuple)) else v
-        v = _require_cuda_f32(v.detach(), what)
-        if v.dim() != 2 or v.shape[1] != C:
-            raise native.NativeError(f"bnn_amd: {what} must be [K, {C}]")
-        return v
-    a, b = table(bn_scales, "bn_scales"), table(bn_shifts, "bn_shifts")
+    a, b = _affine_table(bn_scales, C, "bn_scales"), _affine_table(bn_shifts, C, "bn_shifts")
     K = a.shape[0]
     if not 1 <= K <= 4 or b.shape[0] != K:
         raise native.NativeError(f"bnn_amd: bn_act_pack_multi takes 1..4 affines, got {K} / {b.shape[0]}")
@@ -277,14 +279,7 @@ def stem3x3_bn_relu_pack(x: torch.Tensor, w: torch.Tensor, bn_scale: torch.Tenso
     N, _, H, W = x.shape
     O = w.shape[0]
     bn_scale, bn_shift = _per_channel(bn_scale, O, "bn_scale"), _per_channel(bn_shift, O, "bn_shift")
-
-    def table(v, what):
-        v = torch.stack([_per_channel(e, O, what) for e in v]) if isinstance(v, (list, tuple)) else v
-        v = _require_cuda_f32(v.detach(), what)
-        if v.dim() != 2 or v.shape[1] != O:
-            raise native.NativeError(f"bnn_amd: {what} must be [K, {O}]")
-        return v
-    a, b = table(pack_scales, "pack_scales"), table(pack_shifts, "pack_shifts")
+    a, b = _affine_table(pack_scales, O, "pack_scales"), _affine_table(pack_shifts, O, "pack_shifts")
     K = a.shape[0]
     if not 1 <= K <= 4 or b.shape[0] != K:
         raise native.NativeError(f"bnn_amd: stem3x3 takes 1..4 affines, got {K} / {b.shape[0]}")
@@ -311,6 +306,108 @@ def stem3x3_bn_relu_pack(x: torch.Tensor, w: torch.Tensor, bn_scale: torch.Tenso
             P = torch.empty((K, 0, cw64, H, W), dtype=torch.int64, device=x.device)
             M = torch.empty_like(P)
     return y, [PackedAct(P[k], M[k], (N, O, H, W), False) for k in range(K)]
+
+
+STEM_S2_TILE = native.STEM_S2_TILE      # (rows, columns) of output pixels one workgroup of the two kernels below owns
+_STEM_S2_MAX_ELEMS = (1 << 31) - 1      # fp32 elements of the input or output one launch of them covers (capi.hip: kMaxElems)
+
+
+def _half(v: int) -> int:
+    """Output extent of a 3x3 / stride 2 / padding 1 convolution."""
+    return (v + 1) // 2
+
+
+def _grouped_w(w: torch.Tensor, c_in: int, groups: int, what: str) -> torch.Tensor:
+    w = _require_cuda_f32(w.detach(), what)
+    if (groups < 1 or c_in % groups or w.dim() != 4 or w.shape[0] % groups
+            or tuple(w.shape[1:]) != (c_in // groups, 3, 3)):
+        raise native.NativeError(f"bnn_amd: {what} must be [O, {c_in}/groups, 3, 3] with groups dividing both channel "
+                                 f"counts, got {tuple(w.shape)} and groups = {groups}")
+    return w
+
+
+def stem_s2x2(x: torch.Tensor, w1: torch.Tensor, s1: torch.Tensor, t1: torch.Tensor, w2: torch.Tensor, s2: torch.Tensor,
+              t2: torch.Tensor, groups: int, relu_out: bool = False) -> torch.Tensor:
+    """``stem0`` of a BATS ImageNet network in one launch (``bnn_hip_stem_s2x2_f32``): ``Conv2d(3, C1, 3, stride 2, pad
+    1)`` -> BatchNorm ``s1`` / ``t1`` -> ReLU -> ``Conv2d(C1, C, 3, stride 2, pad 1, groups)`` -> BatchNorm ``s2`` / ``t2``,
+    and a ReLU on the way out when ``relu_out``.  ``x`` ``[N, 3, H, W]``, ``w1`` ``[C1, 3, 3, 3]``, ``w2``
+    ``[C, C1 / groups, 3, 3]``, no biases; returns fp32 ``[N, C, ceil(ceil(H/2)/2), ceil(ceil(W/2)/2)]``.  The intermediate
+    never reaches memory.  A batch whose input or output would reach 2^31 elements is cut into several launches."""
+    x = _require_cuda_f32(x, "stem input")
+    w1 = _require_cuda_f32(w1.detach(), "stem weight")
+    if x.dim() != 4 or x.shape[1] != 3 or w1.dim() != 4 or tuple(w1.shape[1:]) != (3, 3, 3):
+        raise native.NativeError(f"bnn_amd: stem_s2x2 expects x [N,3,H,W] and w1 [C1,3,3,3], got {tuple(x.shape)} and "
+                                 f"{tuple(w1.shape)}")
+    N, _, H, W = x.shape
+    C1 = w1.shape[0]
+    w2 = _grouped_w(w2, C1, groups, "second stem weight")
+    C = w2.shape[0]
+    s1, t1 = _per_channel(s1, C1, "s1"), _per_channel(t1, C1, "t1")
+    s2, t2 = _per_channel(s2, C, "s2"), _per_channel(t2, C, "t2")
+    lib = native.require()
+    H2, W2 = _half(_half(H)), _half(_half(W))
+    step = max(1, min(N, _STEM_S2_MAX_ELEMS // max(3 * H * W, C * H2 * W2, 1)))
+    with torch.cuda.device(x.device):
+        y = torch.empty((N, C, H2, W2), dtype=torch.float32, device=x.device)
+        for n0 in range(0, N if H * W else 0, step):
+            n = min(step, N - n0)
+            native.check(lib.bnn_hip_stem_s2x2_f32(
+                x[n0:n0 + n].data_ptr(), w1.data_ptr(), s1.data_ptr(), t1.data_ptr(), w2.data_ptr(), s2.data_ptr(),
+                t2.data_ptr(), n, C1, C, groups, H, W, int(bool(relu_out)), y[n0:n0 + n].data_ptr(), _stream(x.device)),
+                "bnn_hip_stem_s2x2_f32")
+    return y
+
+
+def gconv3x3s2_bn_pack(x: torch.Tensor, w: torch.Tensor, bn_scale: torch.Tensor, bn_shift: torch.Tensor, groups: int,
+                       pack_scales=None, pack_shifts=None, relu_in: bool = False, out_f32: bool = True):
+    """``stem1`` of a BATS ImageNet network with the binarisation of its ``K`` consumers in one launch
+    (``bnn_hip_gconv3x3s2_bn_pack_f32``): ``y = bn(conv3x3(relu(x) if relu_in else x))`` for ``x`` ``[N, C, H, W]``, ``w``
+    ``[O, C / groups, 3, 3]`` (stride 2, padding 1, no bias) and the folded BatchNorm ``bn_scale`` / ``bn_shift`` ``[O]``;
+    ``pack_scales`` / ``pack_shifts`` are ``[K, O]`` (or sequences of ``K`` vectors), ``0 <= K <= 4`` (None: ``K = 0``).
+    Returns ``(y | None, [K PackedAct])`` where set ``k`` holds the bits of ``bn_act_pack_multi(y, pack_scales,
+    pack_shifts)[k]``; ``out_f32=False`` (``K >= 1`` only): ``y`` is not written.  A batch whose ``x`` or ``y`` would reach
+    2^31 elements is cut into several launches."""
+    x = _require_cuda_f32(x, "activation")
+    if x.dim() != 4:
+        raise native.NativeError(f"bnn_amd: gconv3x3s2_bn_pack expects NCHW, got shape {tuple(x.shape)}")
+    N, C, H, W = x.shape
+    w = _grouped_w(w, C, groups, "weight")
+    O = w.shape[0]
+    bn_scale, bn_shift = _per_channel(bn_scale, O, "bn_scale"), _per_channel(bn_shift, O, "bn_shift")
+    if (pack_scales is None) != (pack_shifts is None):
+        raise native.NativeError("bnn_amd: gconv3x3s2_bn_pack takes pack_scales and pack_shifts together")
+    none = pack_scales is None or len(pack_scales) == 0
+    a, b = (None, None) if none else (_affine_table(pack_scales, O, "pack_scales"),
+                                      _affine_table(pack_shifts, O, "pack_shifts"))
+    K = 0 if none else a.shape[0]
+    if K > 4 or (K and b.shape[0] != K):
+        raise native.NativeError(f"bnn_amd: gconv3x3s2_bn_pack takes 0..4 affines, got {K}")
+    if K == 0 and not out_f32:
+        raise native.NativeError("bnn_amd: gconv3x3s2_bn_pack without affines must write the fp32 output")
+    lib = native.require()
+    Ho, Wo = _half(H), _half(W)
+    cw64 = (O + 63) // 64
+    step = max(1, min(N, _STEM_S2_MAX_ELEMS // max(C * H * W, O * Ho * Wo, 1)))
+    with torch.cuda.device(x.device):
+        y = torch.empty((N, O, Ho, Wo), dtype=torch.float32, device=x.device) if out_f32 else None
+        parts = []
+        for n0 in range(0, N if H * W else 0, step):   # (one launch unless the batch is cut: a plane set is [n, cw64, Ho, Wo])
+            n = min(step, N - n0)
+            P = torch.empty((K, n, cw64, Ho, Wo), dtype=torch.int64, device=x.device)
+            M = torch.empty_like(P)
+            native.check(lib.bnn_hip_gconv3x3s2_bn_pack_f32(
+                x[n0:n0 + n].data_ptr(), w.data_ptr(), bn_scale.data_ptr(), bn_shift.data_ptr(), _ptr(a), _ptr(b), n, C, O,
+                groups, H, W, int(bool(relu_in)), K, P.data_ptr() if K else None, M.data_ptr() if K else None,
+                None if y is None else y[n0:n0 + n].data_ptr(), _stream(x.device)), "bnn_hip_gconv3x3s2_bn_pack_f32")
+            parts.append((P, M))
+        if len(parts) == 1:
+            P, M = parts[0]
+        elif parts:
+            P, M = torch.cat([p for p, _ in parts], 1), torch.cat([m for _, m in parts], 1)
+        else:
+            P = torch.empty((K, 0, cw64, Ho, Wo), dtype=torch.int64, device=x.device)
+            M = torch.empty_like(P)
+    return y, [PackedAct(P[k], M[k], (N, O, Ho, Wo), False) for k in range(K)]
 
 
 def avgpool_pack(x: torch.Tensor, k: int, nonneg: bool = False) -> PackedAct:

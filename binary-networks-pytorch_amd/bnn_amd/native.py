@@ -25,6 +25,9 @@ HBLOCK_CHANNEL_LANES = 128
 STEM_EXACT_FP32 = 1
 STEM_FP16 = 4
 ABI_VERSION = 15
+STEM_S2_TILE = (4, 16)                  # BNN_HIP_STEM_S2_TILE_H / _W: output pixels per workgroup of the ImageNet stem kernels
+STEM_S2X2_MAX_GROUP_CHANNELS = 32       # BNN_HIP_STEM_S2X2_MAX_GROUP_CHANNELS
+GCONV3X3S2_MAX_GROUP_CHANNELS = 40      # BNN_HIP_GCONV3X3S2_MAX_GROUP_CHANNELS
 DTYPE_F32 = 0
 DTYPE_F16 = 1
 
@@ -140,6 +143,8 @@ _PROTOTYPES = {
     "bnn_hip_bn_act_pack_multi_f32": (_i, [_view_p, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "bnn_hip_bn_act_pack_s2_f32": (_i, [_view_p, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "bnn_hip_stem3x3_bn_relu_pack_f32": (_i, [_vp] * 6 + [_i] * 5 + [_vp] * 4),
+    "bnn_hip_stem_s2x2_f32": (_i, [_vp] * 7 + [_i] * 7 + [_vp] * 2),
+    "bnn_hip_gconv3x3s2_bn_pack_f32": (_i, [_vp] * 6 + [_i] * 8 + [_vp] * 4),
     "bnn_hip_avgpool_pack_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "bnn_hip_avgpool2_bn_pack2_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "bnn_hip_orpool_packed": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),

@@ -129,6 +129,14 @@ int launch_bn_act_pack_s2(const float* x, int c_off, int c_tot, int N, int C, in
 int launch_stem3x3_bn_relu_pack(const float* x, const float* w, const float* bn_s, const float* bn_t, const float* pk_a,
                                 const float* pk_b, int N, int O, int H, int W, int K, uint64_t* P, uint64_t* M, float* y,
                                 hipStream_t stream);
+// bats_stem_in.hip: the two ImageNet stems.  stem0 (conv 3x3 / 2 -> BN -> ReLU -> grouped conv 3x3 / 2 -> BN [-> ReLU]) with
+// its intermediate in LDS; stem1 ([ReLU ->] grouped conv 3x3 / 2 -> BN) with K (0..4) plane sets [K][N][cw64][Ho][Wo] of its
+// output, y (fp32 [N, O, Ho, Wo]) null only when K >= 1
+int launch_stem_s2x2(const float* x, const float* w1, const float* s1, const float* t1, const float* w2, const float* s2,
+                     const float* t2, int N, int C1, int C, int G, int H, int W, int relu_out, float* y, hipStream_t stream);
+int launch_gconv3x3s2_bn_pack(const float* x, const float* w, const float* bn_s, const float* bn_t, const float* pk_a,
+                              const float* pk_b, int N, int C, int O, int G, int H, int W, int relu_in, int K, uint64_t* P,
+                              uint64_t* M, float* y, hipStream_t stream);
 int launch_avgpool_pack(const float* x, int N, int C, int H, int W, int k, uint64_t* P, uint64_t* M,
                         hipStream_t stream);
 int launch_avgpool2_bn_pack2(const float* x, int N, int C, int H, int W, const float* a1, const float* b1, int relu1,

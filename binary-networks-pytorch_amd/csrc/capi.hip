@@ -401,6 +401,49 @@ int bnn_hip_stem3x3_bn_relu_pack_f32(const float* x, const float* w, const float
                                           static_cast<hipStream_t>(stream));
 }
 
+int bnn_hip_stem_s2x2_f32(const float* x, const float* w1, const float* s1, const float* t1, const float* w2,
+                          const float* s2, const float* t2, int N, int C1, int C, int G, int H, int W, int relu_out,
+                          float* y, void* stream) {
+  if (!x || !w1 || !s1 || !t1 || !w2 || !s2 || !t2 || !y) return BNN_HIP_ERR_INVALID_ARG;
+  if (N <= 0 || C1 <= 0 || C <= 0 || G <= 0 || H <= 0 || W <= 0) return BNN_HIP_ERR_INVALID_ARG;
+  if (C1 % G != 0 || C % G != 0) return BNN_HIP_ERR_INVALID_ARG;
+  if (!aligned(x, 4) || !aligned(w1, 4) || !aligned(s1, 4) || !aligned(t1, 4) || !aligned(w2, 4) || !aligned(s2, 4) ||
+      !aligned(t2, 4) || !aligned(y, 4))
+    return BNN_HIP_ERR_INVALID_ARG;
+  const int H2 = out_dim(out_dim(H, 3, 2, 1, 1), 3, 2, 1, 1), W2 = out_dim(out_dim(W, 3, 2, 1, 1), 3, 2, 1, 1);
+  if (mulc(N, 3, H, W) > kMaxElems || mulc(N, C, H2, W2) > kMaxElems || mulc(C, C1 / G, 9) > kMaxElems ||
+      mulc(C1, 27) > kMaxElems)
+    return BNN_HIP_ERR_TOO_LARGE;
+  if (C1 / G > BNN_HIP_STEM_S2X2_MAX_GROUP_CHANNELS || G > 65535) return BNN_HIP_ERR_UNSUPPORTED;   // LDS tile, grid.y
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_stem_s2x2(x, w1, s1, t1, w2, s2, t2, N, C1, C, G, H, W, relu_out != 0, y,
+                               static_cast<hipStream_t>(stream));
+}
+
+int bnn_hip_gconv3x3s2_bn_pack_f32(const float* x, const float* w, const float* bn_scale, const float* bn_shift,
+                                   const float* pack_scale, const float* pack_shift, int N, int C, int O, int G, int H,
+                                   int W, int relu_in, int K, uint64_t* P, uint64_t* M, float* y, void* stream) {
+  if (!x || !w || !bn_scale || !bn_shift || K < 0 || K > 4) return BNN_HIP_ERR_INVALID_ARG;
+  if (K == 0 ? !y : (!pack_scale || !pack_shift || !P || !M)) return BNN_HIP_ERR_INVALID_ARG;
+  if (N <= 0 || C <= 0 || O <= 0 || G <= 0 || H <= 0 || W <= 0) return BNN_HIP_ERR_INVALID_ARG;
+  if (C % G != 0 || O % G != 0) return BNN_HIP_ERR_INVALID_ARG;
+  if (!aligned(x, 4) || !aligned(w, 4) || !aligned(bn_scale, 4) || !aligned(bn_shift, 4) || (y && !aligned(y, 4)))
+    return BNN_HIP_ERR_INVALID_ARG;
+  if (K > 0 && (!aligned(pack_scale, 4) || !aligned(pack_shift, 4) || !aligned(P, 8) || !aligned(M, 8)))
+    return BNN_HIP_ERR_INVALID_ARG;
+  const int Ho = out_dim(H, 3, 2, 1, 1), Wo = out_dim(W, 3, 2, 1, 1);
+  if (mulc(N, C, H, W) > kMaxElems || mulc(N, O, Ho, Wo) > kMaxElems || mulc(O, C / G, 9) > kMaxElems)
+    return BNN_HIP_ERR_TOO_LARGE;
+  if (C / G > BNN_HIP_GCONV3X3S2_MAX_GROUP_CHANNELS || ((long long)O + 63) / 64 > 65535)   // LDS tile, grid.y
+    return BNN_HIP_ERR_UNSUPPORTED;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_gconv3x3s2_bn_pack(x, w, bn_scale, bn_shift, K ? pack_scale : nullptr, K ? pack_shift : nullptr, N, C, O,
+                                        G, H, W, relu_in != 0, K, K ? P : nullptr, K ? M : nullptr, y,
+                                        static_cast<hipStream_t>(stream));
+}
+
 int bnn_hip_avgpool_pack_f32(const float* x, int N, int C, int H, int W, int k, uint64_t* P,
                              uint64_t* M, void* stream) {
   if (!x || !P || !M || N <= 0 || C <= 0 || H <= 0 || W <= 0 || k <= 0) return BNN_HIP_ERR_INVALID_ARG;

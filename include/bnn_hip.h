@@ -563,6 +563,42 @@ int bnn_hip_stem3x3_bn_relu_pack_f32(const float* x, const float* w, const float
                                      const float* pack_scale, const float* pack_shift, int N, int O, int H, int W, int K,
                                      uint64_t* P, uint64_t* M, float* y, void* stream);
 
+/* ---- The two real-valued stems of a BATS ImageNet network, one launch each (additive, ABI 15). ----
+ * bnn/models/bats.py:161-172.  With H1 = (H + 1) / 2, H2 = (H1 + 1) / 2 (W alike), Cig = (input channels) / G and
+ * Cog = (output channels) / G per group, g = o / Cog; every convolution is 3x3, stride 2, padding 1, without bias, and a
+ * tap outside its input contributes nothing:
+ *
+ * bnn_hip_stem_s2x2_f32 — stem0: Conv2d(3, C1) -> BatchNorm -> ReLU -> Conv2d(C1, C, groups G) -> BatchNorm [-> ReLU]
+ *     acc1 = 0;  over (ci, kh, kw) in that order:  acc1 = fmaf(x[n,ci,2p+kh-1,2q+kw-1], w1[c,ci,kh,kw], acc1)
+ *     y1[n,c,p,q] = fmaxf(fmaf(acc1, s1[c], t1[c]), 0)                                   on the H1 x W1 map
+ *     acc2 = 0;  over (j, kh, kw) in that order:   acc2 = fmaf(y1[n,g*Cig+j,2p+kh-1,2q+kw-1], w2[o,j,kh,kw], acc2)
+ *     y[n,o,p,q]  = fmaf(acc2, s2[o], t2[o]), then fmaxf(., 0) when relu_out               on the H2 x W2 map
+ *   A tap of the second convolution outside the H1 x W1 map is padding (zero), not the max(t1, 0) the first convolution
+ *   would produce there.  y1 is never written to memory.  x: [N,3,H,W]; w1: [C1,3,3,3]; s1 / t1: [C1]; w2: [C,C1/G,3,3];
+ *   s2 / t2: [C]; y: [N,C,H2,W2].  G divides C1 and C (else INVALID_ARG); C1 / G <= BNN_HIP_STEM_S2X2_MAX_GROUP_CHANNELS and
+ *   G <= 65535 (else UNSUPPORTED); N*3*H*W and N*C*H2*W2 stay below 2^31 (TOO_LARGE: split the batch).
+ *
+ * bnn_hip_gconv3x3s2_bn_pack_f32 — stem1: [ReLU ->] Conv2d(C, O, groups G) -> BatchNorm, and the sign planes of K consumers
+ *     x' = relu_in ? fmaxf(x, 0) : x
+ *     acc = 0;  over (j, kh, kw) in that order:  acc = fmaf(x'[n,g*Cig+j,2p+kh-1,2q+kw-1], w[o,j,kh,kw], acc)
+ *     v   = fmaf(acc, bn_scale[o], bn_shift[o])                                           on the H1 x W1 map
+ *     plane set k = the bits of bnn_hip_bn_act_pack_multi_f32 on v with pack_scale[k][o] / pack_shift[k][o], relu = 0
+ *   x: [N,C,H,W]; w: [O,C/G,3,3]; pack_scale / pack_shift: [K][O], 0 <= K <= 4; P / M: [K][N][ceil(O/64)][H1][W1] uint64
+ *   (8-byte aligned; unused when K == 0).  y: fp32 [N,O,H1,W1] receives v, or NULL (only when K >= 1): v is not written.
+ *   G divides C and O (else INVALID_ARG); C / G <= BNN_HIP_GCONV3X3S2_MAX_GROUP_CHANNELS and ceil(O / 64) <= 65535 (else
+ *   UNSUPPORTED); N*C*H*W and N*O*H1*W1 stay below 2^31 (TOO_LARGE).
+ * Both kernels work on BNN_HIP_STEM_S2_TILE_H x BNN_HIP_STEM_S2_TILE_W tiles of output pixels; any H, W >= 1 is covered. */
+#define BNN_HIP_STEM_S2_TILE_H 4
+#define BNN_HIP_STEM_S2_TILE_W 16
+#define BNN_HIP_STEM_S2X2_MAX_GROUP_CHANNELS 32
+#define BNN_HIP_GCONV3X3S2_MAX_GROUP_CHANNELS 40
+int bnn_hip_stem_s2x2_f32(const float* x, const float* w1, const float* s1, const float* t1, const float* w2,
+                          const float* s2, const float* t2, int N, int C1, int C, int G, int H, int W, int relu_out,
+                          float* y, void* stream);
+int bnn_hip_gconv3x3s2_bn_pack_f32(const float* x, const float* w, const float* bn_scale, const float* bn_shift,
+                                   const float* pack_scale, const float* pack_shift, int N, int C, int O, int G, int H,
+                                   int W, int relu_in, int K, uint64_t* P, uint64_t* M, float* y, void* stream);
+
 /* Binary fully-connected layer: x packed as [B][ceil(F/64)] planes (pack_act with
  * H=W=1, i.e. [B][ceil(F/64)] words), weight packed with KH=KW=1.  out: float32 [B,O].                         */
 int bnn_hip_blinear(int B, int F, int O,

@@ -109,6 +109,30 @@ int launch_stem3x3_bn_relu_pack(const float* x, const float* w, const float* s, 
   REQUIRE((long long)N * O * H * W <= (1LL << 31) - 1 && 3LL * N * H * W <= (1LL << 31) - 1);
   return BNN_HIP_OK;
 }
+// csrc/bats_stem_in.hip: the groups divide the channels, a group's input channels fit the LDS tile, the groups / plane
+// words fit grid.y, every tensor stays below 2^31 elements, and the planes exist exactly when K >= 1
+int launch_stem_s2x2(const float* x, const float* w1, const float* s1, const float* t1, const float* w2, const float* s2,
+                     const float* t2, int N, int C1, int C, int G, int H, int W, int relu_out, float* y, hipStream_t) {
+  ++g_reached;
+  REQUIRE(x && w1 && s1 && t1 && w2 && s2 && t2 && y && al(x, 4) && al(w1, 4) && al(w2, 4) && al(y, 4));
+  REQUIRE(N > 0 && C1 > 0 && C > 0 && G > 0 && H > 0 && W > 0 && C1 % G == 0 && C % G == 0 && (relu_out == 0 || relu_out == 1));
+  REQUIRE(C1 / G <= BNN_HIP_STEM_S2X2_MAX_GROUP_CHANNELS && G <= 65535);
+  const long long H2 = ((long long)H + 3) / 4, W2 = ((long long)W + 3) / 4;      // ceil(ceil(H / 2) / 2)
+  REQUIRE(3LL * N * H * W <= (1LL << 31) - 1 && (long long)N * C * H2 * W2 <= (1LL << 31) - 1);
+  return BNN_HIP_OK;
+}
+int launch_gconv3x3s2_bn_pack(const float* x, const float* w, const float* s, const float* t, const float* a, const float* b,
+                              int N, int C, int O, int G, int H, int W, int relu_in, int K, uint64_t* P, uint64_t* M, float* y,
+                              hipStream_t) {
+  ++g_reached;
+  REQUIRE(x && w && s && t && al(x, 4) && al(w, 4) && (!y || al(y, 4)) && K >= 0 && K <= 4 && (relu_in == 0 || relu_in == 1));
+  REQUIRE(K == 0 ? (y && !a && !b && !P && !M) : (a && b && P && M && al(P, 8) && al(M, 8)));
+  REQUIRE(N > 0 && C > 0 && O > 0 && G > 0 && H > 0 && W > 0 && C % G == 0 && O % G == 0);
+  REQUIRE(C / G <= BNN_HIP_GCONV3X3S2_MAX_GROUP_CHANNELS && (O + 63) / 64 <= 65535);
+  const long long Ho = ((long long)H + 1) / 2, Wo = ((long long)W + 1) / 2;
+  REQUIRE((long long)N * C * H * W <= (1LL << 31) - 1 && (long long)N * O * Ho * Wo <= (1LL << 31) - 1);
+  return BNN_HIP_OK;
+}
 int launch_avgpool_pack(const float* x, int N, int C, int H, int W, int k, uint64_t* P, uint64_t* M, hipStream_t) {
   ++g_reached; REQUIRE(x && P && M && N > 0 && C > 0 && H > 0 && W > 0 && k > 0 && al(P, 8) && al(M, 8)); return BNN_HIP_OK;
 }
@@ -540,7 +564,7 @@ int main(int argc, char** argv) {
   for (long it = 0; it < iters; ++it) {
     ++g_calls;
     int st = 0;
-    switch (rnd() % 54) {
+    switch (rnd() % 56) {
       case 0: { bnn_hip_conv_desc d = pick_desc();
         st = bnn_hip_bconv2d(rnd() % 16 ? &d : nullptr, pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<uint32_t>(),
                              pick_ptr<uint32_t>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), stream);
@@ -775,6 +799,17 @@ int main(int argc, char** argv) {
                                                      pick_int(), rnd() % 4 ? 1 + (int)(rnd() % 4) : pick_int(),
                                                      pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<float>(), stream);
         break;
+      case 54: { const int C1 = pick_int(), C = (rnd() % 2 && C1 > 0 && C1 < (1 << 20)) ? 2 * C1 : pick_int();
+        st = bnn_hip_stem_s2x2_f32(pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(),
+                                   pick_ptr<float>(), pick_ptr<float>(), pick_int(), C1, C, pick_groups(C1, C), pick_int(),
+                                   pick_int(), (int)(rnd() % 3), pick_ptr<float>(), stream);
+        break; }
+      case 55: { const int C = pick_int(), O = rnd() % 2 ? C : pick_int();
+        st = bnn_hip_gconv3x3s2_bn_pack_f32(pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(),
+                                            pick_ptr<float>(), pick_ptr<float>(), pick_int(), C, O, pick_groups(C, O), pick_int(),
+                                            pick_int(), (int)(rnd() % 3), rnd() % 4 ? (int)(rnd() % 5) : pick_int(),
+                                            pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<float>(), stream);
+        break; }
       default: { bnn_hip_conv_desc d = pick_desc();
         (void)bnn_hip_shortcut_fold_supported(rnd() % 16 ? &d : nullptr, pick_int());
         st = bnn_hip_blinear(pick_int(), pick_int(), pick_int(), pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<uint32_t>(),
