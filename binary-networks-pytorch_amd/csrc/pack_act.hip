@@ -325,9 +325,11 @@ int launch_bn_act_pack_s2(const float* x, int c_off, int c_tot, int N, int C, in
 }
 
 // AvgPool2d(k, stride=k, ceil_mode=True, count_include_pad=False) + sign() in one pass: the
-// shortcut branch of a down-sampling stage (bnn/models/resnet.py:128-133).  The sign of an
-// average is the sign of the sum, so the divisor never matters and clipped windows at the
-// ragged edge need no special case beyond skipping out-of-image taps.
+// shortcut branch of a down-sampling stage (bnn/models/resnet.py:128-133).  The planes are those
+// of the AVERAGE, s / count over the in-image taps of the window, not of the sum s: the two
+// differ where the average underflows to zero (one 2^-149 among zeros: s > 0, s / 4 == 0, and the
+// reference's sign is 0).  Clipped windows at the ragged edge skip their out-of-image taps and
+// divide by the taps they kept.
 // One thread = one output pixel x one 32-channel word.
 __global__ __launch_bounds__(256) void avgpool_pack_kernel(const float* __restrict__ x, int C,
                                                            int H, int W, int k, int Ho, int Wo,
@@ -347,6 +349,7 @@ __global__ __launch_bounds__(256) void avgpool_pack_kernel(const float* __restri
     if (c >= C) break;
     const float* xc = x + ((size_t)n * C + c) * H * W;
     float s = 0.0f;
+    int cnt = 0;
     for (int dy = 0; dy < k; ++dy) {
       const int iy = oy * k + dy;
       if (iy >= H) break;
@@ -354,10 +357,12 @@ __global__ __launch_bounds__(256) void avgpool_pack_kernel(const float* __restri
         const int ix = ox * k + dx;
         if (ix >= W) break;
         s += xc[(size_t)iy * W + ix];
+        ++cnt;
       }
     }
-    pw |= (is_pos(s) ? 1u : 0u) << b;
-    mw |= (is_neg(s) ? 1u : 0u) << b;
+    const float t = s / (float)cnt;  // (IEEE division: hipcc's default for fp32)
+    pw |= (is_pos(t) ? 1u : 0u) << b;
+    mw |= (is_neg(t) ? 1u : 0u) << b;
   }
   const size_t o = ((((size_t)n * (cw32 >> 1) + (word >> 1)) * hw + r) << 1) + (word & 1);
   P[o] = pw;
@@ -365,11 +370,14 @@ __global__ __launch_bounds__(256) void avgpool_pack_kernel(const float* __restri
 }
 
 // The same shortcut input when the tensor is NON-NEGATIVE (a ReLU output — every ResNet stage transition) and its
-// sign planes already exist: an average of non-negative values is positive iff one of them is, so
+// sign planes already exist: an average of non-negative values is positive iff one of them is (unless it underflows,
+// below), so
 //     sign(AvgPool_k(x)) = OR over the k x k window of the P plane,   M = 0,
 // computed from 2 bits per element instead of re-reading the fp32 tensor (206 MB -> 6.4 MB for the 64-channel
-// 56x56 stage at batch 256: 38 us -> launch-bound).  Exact for finite inputs (a sum of non-negative floats is
-// positive iff a term is); a NaN element makes the reference's average NaN (sign 0) while the OR ignores it.
+// 56x56 stage at batch 256: 38 us -> launch-bound).  Exact for finite inputs whose window average does not underflow to
+// zero (a sum of non-negative floats is positive iff a term is, but the planes hold no magnitudes: a window whose sum is
+// below count * 2^-150 averages to 0 in the reference and still ORs to 1); a NaN element makes the reference's average
+// NaN (sign 0) while the OR ignores it.
 __global__ __launch_bounds__(256) void orpool_packed_kernel(const uint64_t* __restrict__ P, int H, int W, int k,
                                                             int Ho, int Wo, long long nwords,
                                                             uint64_t* __restrict__ outP,
@@ -427,8 +435,8 @@ __global__ __launch_bounds__(256) void avgpool2_pack_kernel(const float* __restr
     const float* row = x + (((size_t)n * C + c) * H + 2 * oy) * W + 4 * t;
     const float4 u = *reinterpret_cast<const float4*>(row);
     const float4 v = *reinterpret_cast<const float4*>(row + W);
-    const float s0 = ((u.x + u.y) + v.x) + v.y;
-    const float s1 = ((u.z + u.w) + v.z) + v.w;
+    const float s0 = (((u.x + u.y) + v.x) + v.y) * 0.25f;  // the average: x / 4 and x * 0.25f are the same float
+    const float s1 = (((u.z + u.w) + v.z) + v.w) * 0.25f;
     pw0 |= (is_pos(s0) ? 1u : 0u) << b;
     mw0 |= (is_neg(s0) ? 1u : 0u) << b;
     pw1 |= (is_pos(s1) ? 1u : 0u) << b;
@@ -461,7 +469,7 @@ __global__ __launch_bounds__(256) void avgpool2_pack_f2_kernel(const float* __re
     if (word * 32 + b >= C) break;
     const float2 u = *reinterpret_cast<const float2*>(base + b * cstride);
     const float2 v = *reinterpret_cast<const float2*>(base + b * cstride + W);
-    const float s = ((u.x + u.y) + v.x) + v.y;
+    const float s = (((u.x + u.y) + v.x) + v.y) * 0.25f;
     pw |= (is_pos(s) ? 1u : 0u) << b;
     mw |= (is_neg(s) ? 1u : 0u) << b;
   }

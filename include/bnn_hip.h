@@ -254,7 +254,9 @@ int bnn_hip_pack_act_f16(const void* x, int N, int C, int H, int W,
 /* AvgPool2d(kernel=k, stride=k, ceil_mode=True, count_include_pad=False) followed by
  * sign(): the shortcut branch of a down-sampling residual stage
  * (bnn/models/resnet.py:128-133: AvgPool2d -> binary conv1x1 -> BN).  Output planes have
- * ceil(H/k) x ceil(W/k) pixels.                                                    */
+ * ceil(H/k) x ceil(W/k) pixels.  The planes are those of the average (the window summed row by
+ * row in fp32, divided by its in-image taps), so an average that underflows to zero sets no bit,
+ * as in the reference and in bnn_hip_avgpool2_bn_pack2_f32.                          */
 int bnn_hip_avgpool_pack_f32(const float* x, int N, int C, int H, int W, int k,
                              uint64_t* P, uint64_t* M, void* stream);
 
@@ -270,7 +272,9 @@ int bnn_hip_avgpool2_bn_pack2_f32(const float* x, int N, int C, int H, int W, co
  * non-negative values is positive iff one of them is, so sign(AvgPool_k(x)) is the OR of the P plane over each
  * k x k window (ceil mode: windows are clipped at the border) — 2 bits per element read instead of 32.
  * P: [N,ceil(C/64),H,W]; out_P / out_M: [N,ceil(C/64),ceil(H/k),ceil(W/k)], out_M is written as 0.
- * Exact for finite inputs; the caller vouches for x >= 0 (as with BNN_HIP_FLAG_ACT_NONNEG).            */
+ * Exact for finite inputs whose window average does not underflow to zero (the planes hold no magnitudes: a window of
+ * zeros and one 2^-149 averages to 0 in the reference and ORs to 1); the caller vouches for x >= 0 (as with
+ * BNN_HIP_FLAG_ACT_NONNEG).                                                                              */
 int bnn_hip_orpool_packed(const uint64_t* P, int N, int C, int H, int W, int k,
                           uint64_t* out_P, uint64_t* out_M, void* stream);
 

@@ -378,3 +378,68 @@ void orc_epilogue(const int32_t* dot, int N, int O, int HoWo, const float* alpha
         out[idx] = v;
       }
 }
+
+/* ------------------------------------------------------------------------------------ */
+/* Root oracle of the activation-plane producers (csrc/pack_act.hip, csrc/pack_ste.hip):  */
+/* the fp32 value whose sign the kernels pack, in float32 with an explicit fmaf (this     */
+/* file is built with -ffp-contract=off, so `x * a + b` below would NOT be one).          */
+/* ------------------------------------------------------------------------------------ */
+
+/* Eval-mode BatchNorm folded to one multiply-add per channel, then the optional ReLU of a
+ * pre-activation block (bnn/models/layers/res_block.py:148, hierarchical_block.py:39):
+ *   v = a ? fmaf(x, a[c], b[c]) : x ;  relu: v = v < 0 ? 0 : v   (NaN stays NaN)           */
+void orc_bn_act(const float* x, int N, int C, int HW, const float* a, const float* b, int relu,
+                float* out) {
+  for (int n = 0; n < N; ++n)
+    for (int c = 0; c < C; ++c)
+      for (int i = 0; i < HW; ++i) {
+        const size_t idx = ((size_t)n * C + c) * HW + i;
+        float v = a ? fmaf(x[idx], a[c], b[c]) : x[idx];
+        if (relu) v = (v < 0.0f) ? 0.0f : v;
+        out[idx] = v;
+      }
+}
+
+/* AvgPool2d(2, 2) on even images in ATen's order (include/bnn_hip.h,
+ * bnn_hip_avgpool2_bn_pack2_f32): the window summed row by row, then scaled:
+ *   t = (((x00 + x01) + x10) + x11) * 0.25f                                               */
+void orc_avgpool2(const float* x, int N, int C, int H, int W, float* out) {
+  const int Ho = H / 2, Wo = W / 2;
+  for (int nc = 0; nc < N * C; ++nc)
+    for (int oy = 0; oy < Ho; ++oy)
+      for (int ox = 0; ox < Wo; ++ox) {
+        const float* r0 = x + ((size_t)nc * H + 2 * oy) * W + 2 * ox;
+        const float* r1 = r0 + W;
+        out[((size_t)nc * Ho + oy) * Wo + ox] = (((r0[0] + r0[1]) + r1[0]) + r1[1]) * 0.25f;
+      }
+}
+
+/* Tail of the real-valued stem (bnn/models/resnet.py:150-153: bn1 -> relu -> maxpool; relu and
+ * max commute): v = a ? fmaf(x, a[c], b[c]) : x per tap, the maximum over the k x k window with
+ * padding taps ignored (nn.MaxPool2d), then the optional ReLU.  No NaN handling is stated: the
+ * callers keep NaN out of the windows.                                                      */
+void orc_bn_maxpool(const float* x, int N, int C, int H, int W, const float* a, const float* b,
+                    int relu, int k, int stride, int pad, float* out) {
+  const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
+  for (int n = 0; n < N; ++n)
+    for (int c = 0; c < C; ++c) {
+      const float* xc = x + ((size_t)n * C + c) * H * W;
+      for (int oy = 0; oy < Ho; ++oy)
+        for (int ox = 0; ox < Wo; ++ox) {
+          float m = -INFINITY;
+          for (int dy = 0; dy < k; ++dy) {
+            const int iy = oy * stride - pad + dy;
+            if (iy < 0 || iy >= H) continue;
+            for (int dx = 0; dx < k; ++dx) {
+              const int ix = ox * stride - pad + dx;
+              if (ix < 0 || ix >= W) continue;
+              const float xv = xc[(size_t)iy * W + ix];
+              const float v = a ? fmaf(xv, a[c], b[c]) : xv;
+              if (v > m) m = v;
+            }
+          }
+          if (relu) m = (m < 0.0f) ? 0.0f : m;
+          out[(((size_t)n * C + c) * Ho + oy) * Wo + ox] = m;
+        }
+    }
+}

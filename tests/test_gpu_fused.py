@@ -168,7 +168,9 @@ def test_preactivation_epilogue_bit_exact(name, sw):
 @pytest.mark.parametrize("shape,relu,bn", [((2, 64, 14, 14), True, True), ((1, 70, 9, 7), False, True),
                                             ((3, 200, 5, 5), True, False), ((2, 128, 8, 6), False, False)])
 def test_bn_act_pack_matches_sign_of_affine(shape, relu, bn):
-    """sign(act(bn(x))) in one pass == the torch sequence bn -> act -> sign the reference runs."""
+    """sign(act(bn(x))) in one pass == the torch sequence bn -> act -> sign the reference runs.  (Against float64, on
+    single-workgroup shapes: the bit-for-bit comparison with the float32 fmaf oracle, on every vector width, alignment and
+    special value, is tests/test_gpu_pack_family.py::test_bn_act_pack_streaming.)"""
     C = shape[1]
     x = gen.normal(gen.seed_of("bnpack", shape), shape)
     a = ((0.5 + gen.uniform(1, (C,))) * np.where(np.arange(C) % 4 == 0, -1, 1)).astype(np.float32) if bn else None
