@@ -122,10 +122,15 @@ __global__ __launch_bounds__(64, MINW) void bconv_sgpr_kernel(
         if (fullb) prefetch_residual<NACC, EP, true>(g, px, ob * kOCB + ps * NACC, epi, resv);
         else prefetch_residual<NACC, EP>(g, px, ob * kOCB + ps * NACC, epi, resv);
       }
-      // the folded shortcut values of the pass.  Single-chunk kernels: BEFORE the popcount loop, whose weight stream needs
-      // the scalar registers (8 values wait in VGPRs); multi-chunk kernels (16 or 32 values, a register file at its
-      // occupancy step): after it
-      if constexpr (DS && !MULTI) shortcut_values<NACC>(g, ob * kOCB + ps * NACC, sc, dsr, ds_nz, resv);
+      // the folded shortcut values of the pass: a full block streams the 1x1 weights like the 3x3 ones (shortcut_values_full),
+      // a ragged one takes the guarded form — ONE wave-uniform branch.  Single-chunk kernels: BEFORE the popcount loop (8
+      // values wait in VGPRs; the two weight streams follow each other through the same scalar registers); multi-chunk
+      // kernels (16 or 32 values, a register file at its occupancy step): after the chunk loop, when the field's
+      // registers and the main stream's are free, inside the `fullb` branch of the epilogue below
+      if constexpr (DS && !MULTI) {
+        if (fullb) shortcut_values_full<NACC>(g, ob * kOCB + ps * NACC, sc, dsr, ds_nz, resv);
+        else shortcut_values<NACC>(g, opaque_s(ob * kOCB + ps * NACC), sc, dsr, ds_nz, resv);  // (opaque: see the epilogue below)
+      }
       // two-instruction sign test: the pass's comparands as wave-uniform buffer loads (bconv_core.h: midt2_shift_in)
       [[maybe_unused]] int midt_a[NACC];
       if constexpr (MIDT2) {
@@ -165,7 +170,6 @@ __global__ __launch_bounds__(64, MINW) void bconv_sgpr_kernel(
       // the first if, on every wave — and spilled to VGPR lanes (215 v_readlane + 123 v_writelane in the 512->512 kernel).
       constexpr bool RES_LATE_FETCH = !DS && !RES_EARLY && !RES_ALL;
       const int o0 = ob * kOCB + ps * NACC;
-      if constexpr (DS && MULTI) shortcut_values<NACC>(g, o0, sc, dsr, ds_nz, resv);
       [[maybe_unused]] int negnz = NN ? -nz : nz;  // EP_MIDT (see its epilogue): dot = +-2*count + negnz
 #if defined(__HIP_DEVICE_COMPILE__)
       if constexpr (EP == EP_MIDT) asm("" : "+v"(negnz));
@@ -198,6 +202,7 @@ __global__ __launch_bounds__(64, MINW) void bconv_sgpr_kernel(
         });
       } else if (fullb) {
         if constexpr (RES_LATE_FETCH) prefetch_residual<NACC, EP, true>(g, px, o0, epi, resv);
+        if constexpr (DS && MULTI) shortcut_values_full<NACC>(g, o0, sc, dsr, ds_nz, resv);
         if constexpr (SEEDED) {
           epilogue<NACC, EP, true, true>(g, px, o0, acc, resv, epi, pbits, mbits, 0, NN ? 2.0f : -2.0f,
                                          NN ? -(float)nz : (float)nz);
@@ -207,12 +212,15 @@ __global__ __launch_bounds__(64, MINW) void bconv_sgpr_kernel(
         }
       } else {
         if constexpr (RES_LATE_FETCH) prefetch_residual<NACC, EP>(g, px, o0, epi, resv);
+        // (DS: the guarded side's channel index is opaque up to here, or its 32 per-channel predicates and addresses are
+        // computed at the common dominator and spilled to VGPR lanes in front of the branch, on every wave: see above)
+        if constexpr (DS && MULTI) shortcut_values<NACC>(g, opaque_s(o0), sc, dsr, ds_nz, resv);
         if constexpr (SEEDED) {
 #pragma unroll
           for (int j = 0; j < NACC; ++j) acc[j] -= (int)kCountSeed;
         }
         to_dot();
-        epilogue<NACC, EP>(g, px, o0, acc, resv, epi, pbits, mbits, negnz, NN ? 2.0f : -2.0f);
+        epilogue<NACC, EP>(g, px, DS ? opaque_s(o0) : o0, acc, resv, epi, pbits, mbits, negnz, NN ? 2.0f : -2.0f);
       }
     };
     if constexpr (RES_ALL) {

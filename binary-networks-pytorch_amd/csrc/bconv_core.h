@@ -102,6 +102,14 @@ __device__ __forceinline__ int popc_acc_s(uint32_t x, int acc) {
 #endif
 }
 
+// A wave-uniform value the compiler must not look through: what is computed from it stays in the basic block that asks for it.
+__device__ __forceinline__ int opaque_s(int x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+s"(x));
+#endif
+  return x;
+}
+
 // WB consecutive weight words, loaded with one s_load_dwordx16.
 template <int WB>
 struct alignas(WB * 4) WBlock {
@@ -677,6 +685,18 @@ __device__ __forceinline__ void store_packed_part(const Geo& g, const Pix& px, i
 // with the float operations of the 1x1 convolution's own epilogue (EP_DS) — the fp32 shortcut tensor (103 MB at
 // ResNet-18 layer2, batch 256, written once and read once) and the 1x1 launch disappear.  The shortcut input is the
 // sign plane of an AvgPool of ReLU outputs: non-negative, P plane only, [N, ceil(C/64), Ho, Wo] uint64.
+// Two forms of the arithmetic, chosen per 32-channel block by ONE wave-uniform branch (the one the epilogue takes anyway):
+//   full block (o0 + NACC <= O: every block of ResNet-18) — shortcut_values_full(): the 1x1 weights W[o * CW + i] of a
+//     pass are one contiguous run and go through stream_weights() like the 3x3 ones (x16 / x8 scalar blocks requested one
+//     block ahead, v_and + v_bcnt per word, counts seeded with kCountSeed), alpha / a / b come as aligned scalar pairs
+//     into v_pk_fma_f32 as in epilogue<.., FULL>: straight-line code, no guard, no scalar load and no wait per channel;
+//   ragged last block — shortcut_values(): every channel guarded, its weights and constants fetched by scalar loads.
+// Both give the same float per channel (shown at shortcut_values_full_cw).  Single-chunk kernels compute a pass's 8 values
+// BEFORE its popcount loop (the two weight streams follow each other through the same scalar registers); multi-chunk
+// kernels compute 16 or 32 values AFTER the chunk loop, when the field's vector registers and the main stream's 64 scalar
+// registers are free.  The guarded side reads its channel index through opaque_s(): otherwise the compiler computes that
+// side's 32 per-channel predicates and addresses in front of the branch, on every wave, and spills them to VGPR lanes
+// (the 32-value kernel held 1204 v_readlane / v_writelane that way; the counts before and after are in CHANGELOG.md).
 #define BNN_DS_PARAMS                                                                             \
   const uint32_t *__restrict__ dsP, const uint32_t *__restrict__ dsW, const float *__restrict__ ds_alpha, \
       const float *__restrict__ ds_a, const float *__restrict__ ds_b
@@ -729,32 +749,7 @@ __device__ __forceinline__ int load_shortcut_field(const Geo& g, const Pix& px, 
   return nz;
 }
 
-// The shortcut values of channels o0 .. o0+NACC-1 (wave-uniform weights and constants: scalar loads).
-template <int NACC, int CW>
-__device__ __forceinline__ void shortcut_values_cw(const Geo& g, int o0, const ShortcutArgs& d, const uint32_t (&dsr)[8],
-                                                   int nz, float (&resv)[NACC]) {
-#pragma unroll
-  for (int j = 0; j < NACC; ++j) {
-    if (j % 4 == 0) __builtin_amdgcn_sched_barrier(0);  // four channels' weights and constants in scalar registers at a time
-    const int o = o0 + j;
-    float r = 0.0f;
-    if (o < g.O) {
-      int agree = 0;
-#pragma unroll
-      for (int i = 0; i < CW; ++i) agree += __builtin_popcount(d.W[(size_t)o * CW + i] & dsr[i]);
-      const float dot = (float)(2 * agree - nz);           // non-negative input: dot = 2 * agreements - non-zeros
-      r = fmaf(fmaf(d.alpha[o], dot, 0.0f), d.a[o], d.b[o]);  // EP_DS: alpha * dot (no bias), then the folded BatchNorm
-    }
-    resv[j] = r;
-  }
-}
-template <int NACC>
-__device__ __forceinline__ void shortcut_values(const Geo& g, int o0, const ShortcutArgs& d, const uint32_t (&dsr)[8],
-                                                int nz, float (&resv)[NACC]) {
-  if (g.ds_cw == 2) shortcut_values_cw<NACC, 2>(g, o0, d, dsr, nz, resv);
-  else if (g.ds_cw == 4) shortcut_values_cw<NACC, 4>(g, o0, d, dsr, nz, resv);
-  else shortcut_values_cw<NACC, 8>(g, o0, d, dsr, nz, resv);
-}
+// (shortcut_values*: below the weight stream they use.)
 
 // ---------------------------------------------------------------------------------
 // Tiled kernel, weights streamed through SGPRs (scalar cache).  Best when all waves in
@@ -934,6 +929,75 @@ __device__ __forceinline__ void stream_weights_wz(const uint32_t* __restrict__ w
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (b + 1 < NB) { cur = nxt; zcur = znxt; }
   });
+}
+
+// The shortcut values of channels o0 .. o0+NACC-1 of a FULL block (o0 + NACC <= O, wave-uniform, chosen by the caller):
+// the 1x1 convolution is a weight run like any other — NACC x CW contiguous words from W[o0 * CW] — so it goes through
+// stream_weights(): x16/x8 scalar blocks requested one block ahead, one v_and + v_bcnt per word, no guard, no scalar
+// load and no wait per channel.  The constants come as in epilogue<.., FULL>: (o, o+1) as aligned scalar pairs into
+// v_pk_fma_f32.
+// Same float as the guarded form below, per channel.  The chains start from kCountSeed, so cnt is the bit pattern of the
+// float 2^23 + agree (agree <= 32 * CW), and
+//     c   = cnt - 2^23          = agree            exact
+//     dot = fma(c, 2, -nz)      = 2 * agree - nz   exact: every operand and the result are integers below 2^10,
+// which is the value (float)(2 * agree - nz) has; a zero result is +0 in both forms (an exact zero sum rounds to +0, and
+// for nz == 0 it is +0 + -0 = +0).  Then the EP_DS operations in their order: fma(fma(alpha, dot, 0), a, b).
+template <int NACC, int CW>
+__device__ __forceinline__ void shortcut_values_full_cw(int o0, const ShortcutArgs& d, const uint32_t (&dsr)[8], int nz,
+                                                        float (&resv)[NACC]) {
+  static_assert(NACC % 2 == 0 && (NACC * CW) % 16 == 0, "channel pairs; whole, aligned x16 pieces");
+  using f2 = __attribute__((ext_vector_type(2))) float;
+  uint32_t p[CW];
+#pragma unroll
+  for (int i = 0; i < CW; ++i) p[i] = dsr[i];
+  int cnt[NACC];  // (USEED: every chain starts from the scalar seed)
+  // (two words per channel: one chain — an even and an odd one would cost an add per channel)
+  stream_weights<CW, NACC, true, true, CW == 2>(d.W + (size_t)o0 * CW, p, p, cnt, (int)kCountSeed);
+  const float doff = -(float)nz;
+#pragma unroll
+  for (int j = 0; j < NACC; j += 2) {
+    const int o = o0 + j;
+    const f2 c = f2{__int_as_float(cnt[j]), __int_as_float(cnt[j + 1])} - f2{8388608.0f, 8388608.0f};
+    const f2 dot = __builtin_elementwise_fma(c, f2{2.0f, 2.0f}, f2{doff, doff});
+    const f2 t = __builtin_elementwise_fma(f2{d.alpha[o], d.alpha[o + 1]}, dot, f2{0.0f, 0.0f});
+    const f2 r = __builtin_elementwise_fma(t, f2{d.a[o], d.a[o + 1]}, f2{d.b[o], d.b[o + 1]});
+    resv[j] = r.x;
+    resv[j + 1] = r.y;
+  }
+}
+template <int NACC>
+__device__ __forceinline__ void shortcut_values_full(const Geo& g, int o0, const ShortcutArgs& d, const uint32_t (&dsr)[8],
+                                                     int nz, float (&resv)[NACC]) {
+  if (g.ds_cw == 2) shortcut_values_full_cw<NACC, 2>(o0, d, dsr, nz, resv);
+  else if (g.ds_cw == 4) shortcut_values_full_cw<NACC, 4>(o0, d, dsr, nz, resv);
+  else shortcut_values_full_cw<NACC, 8>(o0, d, dsr, nz, resv);
+}
+
+// The same for a ragged last block (o0 + NACC > O): channels past O give 0, every existing one is guarded.
+template <int NACC, int CW>
+__device__ __forceinline__ void shortcut_values_cw(const Geo& g, int o0, const ShortcutArgs& d, const uint32_t (&dsr)[8],
+                                                   int nz, float (&resv)[NACC]) {
+#pragma unroll
+  for (int j = 0; j < NACC; ++j) {
+    if (j % 4 == 0) __builtin_amdgcn_sched_barrier(0);  // four channels' weights and constants in scalar registers at a time
+    const int o = o0 + j;
+    float r = 0.0f;
+    if (o < g.O) {
+      int agree = 0;
+#pragma unroll
+      for (int i = 0; i < CW; ++i) agree += __builtin_popcount(d.W[(size_t)o * CW + i] & dsr[i]);
+      const float dot = (float)(2 * agree - nz);           // non-negative input: dot = 2 * agreements - non-zeros
+      r = fmaf(fmaf(d.alpha[o], dot, 0.0f), d.a[o], d.b[o]);  // EP_DS: alpha * dot (no bias), then the folded BatchNorm
+    }
+    resv[j] = r;
+  }
+}
+template <int NACC>
+__device__ __forceinline__ void shortcut_values(const Geo& g, int o0, const ShortcutArgs& d, const uint32_t (&dsr)[8],
+                                                int nz, float (&resv)[NACC]) {
+  if (g.ds_cw == 2) shortcut_values_cw<NACC, 2>(g, o0, d, dsr, nz, resv);
+  else if (g.ds_cw == 4) shortcut_values_cw<NACC, 4>(g, o0, d, dsr, nz, resv);
+  else shortcut_values_cw<NACC, 8>(g, o0, d, dsr, nz, resv);
 }
 
 // ---------------------------------------------------------------------------------
