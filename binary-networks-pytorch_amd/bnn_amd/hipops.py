@@ -1410,6 +1410,34 @@ def pack_act_ste(x: torch.Tensor) -> SavedAct:
     return SavedAct(a, T, (N, C, H, W))
 
 
+def _ste_planes(x: torch.Tensor, what: str):
+    """What the three-plane producers share: the fp32 NCHW check of ``x`` and empty ``P`` / ``M`` / ``T``."""
+    x = _require_cuda_f32(x, "activation")
+    if x.dim() != 4:
+        raise native.NativeError(f"bnn_amd: {what} expects NCHW, got shape {tuple(x.shape)}")
+    N, C, H, W = x.shape
+    a = empty_packed(N, C, H, W, x.device)
+    return x, SavedAct(a, torch.empty_like(a.P), (N, C, H, W))
+
+
+def bn_act_pack_ste(x: torch.Tensor, bn_scale=None, bn_shift=None) -> SavedAct:
+    """``pack_act_ste(fma(x, scale[c], shift[c]))`` in one pass over ``x``, the affine result never written
+    (``bnn_hip_bn_act_pack_ste_f32``).  Both constants or neither; neither: the bits of ``pack_act_ste(x)``."""
+    if (bn_scale is None) != (bn_shift is None):
+        raise native.NativeError("bnn_amd: bn_act_pack_ste takes bn_scale and bn_shift together")
+    x, sv = _ste_planes(x, "bn_act_pack_ste")
+    N, C, H, W = x.shape
+    bn_scale = _per_channel(bn_scale, C, "bn_scale")
+    bn_shift = _per_channel(bn_shift, C, "bn_shift")
+    lib = native.require()
+    if N:
+        with torch.cuda.device(x.device):
+            native.check(lib.bnn_hip_bn_act_pack_ste_f32(
+                x.data_ptr(), N, C, H, W, _ptr(bn_scale), _ptr(bn_shift), sv.sign.P.data_ptr(), sv.sign.M.data_ptr(),
+                sv.T.data_ptr(), _stream(x.device)), "bnn_hip_bn_act_pack_ste_f32")
+    return sv
+
+
 def _grad_shapes(g: torch.Tensor, x, stride: int):
     N, C, H, W = x.shape
     O = g.shape[1]
@@ -1652,6 +1680,84 @@ def bn_train_backward(gy: torch.Tensor, y: Optional[torch.Tensor], x: torch.Tens
             dx.data_ptr(), _ptr(dres), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), _stream(x.device)),
             "bnn_hip_bn_train_backward_f32")
     return dx, dgamma, dbeta, dres
+
+
+def bn_train_pack_ste(x: torch.Tensor, gamma, beta, running_mean, running_var, momentum: float, eps: float):
+    """``pack_act_ste(batch_norm(x, training=True))`` without writing the normalised tensor
+    (``bnn_hip_bn_train_pack_ste_f32``: the statistics kernels of ``bn_train_forward``, then BatchNorm + sign + STE mask
+    as three bit planes).  Updates the running statistics like ``bn_train_forward``.  Returns ``(SavedAct, save_mean,
+    save_invstd, scale, shift)`` — ``scale`` / ``shift`` are what the planes were made with."""
+    x, sv = _ste_planes(x, "bn_train_pack_ste")
+    N, C, H, W = x.shape
+    gamma = _per_channel(gamma, C, "BatchNorm weight")
+    beta = _per_channel(beta, C, "BatchNorm bias")
+    running_mean = _per_channel(running_mean, C, "running_mean")
+    running_var = _per_channel(running_var, C, "running_var")
+    lib = native.require()
+    with torch.cuda.device(x.device):
+        mean, invstd, ws = _bn_train_buffers(lib, x)
+        scale, shift = torch.empty_like(mean), torch.empty_like(mean)
+        native.check(lib.bnn_hip_bn_train_pack_ste_f32(
+            x.data_ptr(), N, C, H, W, _ptr(gamma), _ptr(beta), float(eps), float(momentum), _ptr(running_mean),
+            _ptr(running_var), sv.sign.P.data_ptr(), sv.sign.M.data_ptr(), sv.T.data_ptr(), mean.data_ptr(),
+            invstd.data_ptr(), scale.data_ptr(), shift.data_ptr(), ws.data_ptr(), _stream(x.device)),
+            "bnn_hip_bn_train_pack_ste_f32")
+    return sv, mean, invstd, scale, shift
+
+
+def bn_train_backward_add(gy: torch.Tensor, x: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor, gamma,
+                          addend: Optional[torch.Tensor] = None):
+    """``bn_train_backward`` (no fused ReLU) with ``dx += addend`` in the dx kernel (``bnn_hip_bn_train_backward_add_f32``):
+    ``(dx, dgamma, dbeta)``.  ``addend=None``: the bits of ``bn_train_backward``."""
+    gy = _require_cuda_f32(gy, "grad_output")
+    x = _require_cuda_f32(x, "BatchNorm input")
+    if x.dim() != 4 or gy.shape != x.shape:
+        raise native.NativeError(f"bnn_amd: bn_train_backward_add: grad_output {tuple(gy.shape)} does not belong to the "
+                                 f"NCHW input {tuple(x.shape)}")
+    if addend is not None:
+        addend = _require_cuda_f32(addend, "addend")
+        if addend.shape != x.shape:
+            raise native.NativeError("bnn_amd: addend shape differs from the BatchNorm input's")
+    lib = native.require()
+    N, C, H, W = x.shape
+    with torch.cuda.device(x.device):
+        dx = torch.empty_like(x)
+        dgamma, dbeta, ws = _bn_train_buffers(lib, x)
+        native.check(lib.bnn_hip_bn_train_backward_add_f32(
+            gy.data_ptr(), None, x.data_ptr(), mean.data_ptr(), invstd.data_ptr(), _ptr(gamma), _ptr(addend), N, C, H * W,
+            dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), _stream(x.device)),
+            "bnn_hip_bn_train_backward_add_f32")
+    return dx, dgamma, dbeta
+
+
+def prelu_shuffle_backward(gy: torch.Tensor, z: torch.Tensor, slope: torch.Tensor, shuffle_groups: int = 1,
+                           inplace: bool = False):
+    """Backward of ``channel_shuffle(prelu(z, slope), shuffle_groups)`` (``bnn_hip_prelu_shuffle_backward_f32``):
+    ``gy`` in the output's channel order, ``z`` in the convolution's -> ``(gz, dslope)``, ``dslope`` shaped like
+    ``slope`` (1 or O values).  Deterministic.  ``inplace``: ``gz`` overwrites ``z``."""
+    gy = _require_cuda_f32(gy, "grad_output")
+    z = _require_cuda_f32(z, "pre-activation")
+    if z.dim() != 4 or gy.shape != z.shape:
+        raise native.NativeError(f"bnn_amd: prelu_shuffle_backward: grad_output {tuple(gy.shape)} does not belong to the "
+                                 f"NCHW pre-activation {tuple(z.shape)}")
+    N, O, H, W = z.shape
+    slope = _require_cuda_f32(slope.detach(), "PReLU slope").reshape(-1)
+    shuffle_groups = int(shuffle_groups)
+    if slope.numel() not in (1, O):
+        raise native.NativeError(f"bnn_amd: PReLU slope must have 1 or {O} entries, got {slope.numel()}")
+    if shuffle_groups < 1 or O % shuffle_groups:
+        raise native.NativeError(f"bnn_amd: shuffle_groups={shuffle_groups} does not divide the {O} channels")
+    lib = native.require()
+    with torch.cuda.device(z.device):
+        gz = z if inplace else torch.empty_like(z)
+        dslope = torch.zeros_like(slope)
+        if z.numel():
+            nbytes = int(lib.bnn_hip_prelu_shuffle_backward_workspace_bytes(N, O, H * W))
+            ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=z.device)
+            native.check(lib.bnn_hip_prelu_shuffle_backward_f32(
+                gy.data_ptr(), z.data_ptr(), slope.data_ptr(), slope.numel(), N, O, H * W, shuffle_groups, gz.data_ptr(),
+                dslope.data_ptr(), ws.data_ptr(), nbytes, _stream(z.device)), "bnn_hip_prelu_shuffle_backward_f32")
+    return gz, dslope
 
 
 def bn_relu_maxpool_train_forward(x: torch.Tensor, gamma, beta, running_mean, running_var, momentum: float, eps: float):

@@ -10,7 +10,8 @@ fixtures generated from the reference.  Every operation has the form
     y = [x +] channel_shuffle(PReLU(conv(BatchNorm(x))), 4)          # skip only at stride 1; ReLUConvBN: no shuffle
 
 and, evaluated for inference on a HIP device, first offers itself to the cell-operation executor
-(``bnn_amd/dispatch.py: OpFusion`` -> ``bnn_amd/cellops.py: FusedCellOp``).
+(``bnn_amd/dispatch.py: OpFusion`` -> ``bnn_amd/cellops.py: FusedCellOp``); in ``train()`` mode under autograd, with
+``training.CELL_OPS`` on, to the training executor (``bnn_amd/training.py: cell_op_train`` -> ``CellOpTrainFn``).
 """
 from __future__ import annotations
 
@@ -63,6 +64,12 @@ class _CellOp(nn.Module):
             y = _fused(self, x)
             if y is not None:
                 return y
+        if self.training and torch.is_grad_enabled():
+            from .. import training                 # (training imports hipops; this package stays importable alone)
+            if training.CELL_OPS:       # read at every call; None: the rule of training.cell_op_train declined
+                y = training.cell_op_train(self, x)
+                if y is not None:
+                    return y
         return self._forward(x)
 
     def _forward(self, x: torch.Tensor) -> torch.Tensor:

@@ -139,6 +139,7 @@ _PROTOTYPES = {
     "bnn_hip_pack_act_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "bnn_hip_pack_act_f16": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "bnn_hip_pack_act_ste_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "bnn_hip_bn_act_pack_ste_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bnn_hip_bn_act_pack_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "bnn_hip_bn_act_pack_multi_f32": (_i, [_view_p, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "bnn_hip_bn_act_pack_s2_f32": (_i, [_view_p, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
@@ -191,6 +192,10 @@ _PROTOTYPES = {
     "bnn_hip_bn_train_workspace_bytes": (_sz, [_i, _i, _i]),
     "bnn_hip_bn_train_forward_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _f, _f] + [_vp] * 7),
     "bnn_hip_bn_train_backward_f32": (_i, [_vp] * 6 + [_i, _i, _i] + [_vp] * 6),
+    "bnn_hip_bn_train_backward_add_f32": (_i, [_vp] * 7 + [_i, _i, _i] + [_vp] * 5),
+    "bnn_hip_bn_train_pack_ste_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _f, _f] + [_vp] * 11),
+    "bnn_hip_prelu_shuffle_backward_workspace_bytes": (_sz, [_i, _i, _i]),
+    "bnn_hip_prelu_shuffle_backward_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "bnn_hip_bn_relu_maxpool_train_forward_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _f, _f] + [_vp] * 8),
     "bnn_hip_bn_relu_maxpool_train_backward_f32": (_i, [_vp] * 7 + [_i, _i, _i, _i] + [_vp] * 5),
     "bnn_hip_hblock_supported": (_i, [_hblock_p]),

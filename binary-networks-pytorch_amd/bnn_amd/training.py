@@ -412,6 +412,152 @@ def conv2d_train(layer: nn.Module, x: torch.Tensor, plan, packed) -> torch.Tenso
     return out
 
 
+# ---- a whole BATS cell operation in a training step -----------------------------------------------------------------
+# SepConv / DilConv / ReLUConvBN (bnn_amd/models/bats_ops.py) evaluate  y = [x +] channel_shuffle(PReLU(conv(sign(bn(x)))), 4)
+# in train() mode as six steps (the library's BatchNorm, pack_act_ste, the convolution, torch PReLU, the shuffle's
+# .contiguous() copy, torch add), and autograd keeps the BatchNorm output u and the convolution output z alive, each as
+# large as the activation.  `CellOpTrainFn` is the whole operation as one autograd function:
+#   forward :  batch statistics (csrc/bn_train.hip)  ->  BatchNorm + sign + STE mask as three bit planes, u never written
+#              (csrc/pack_ste.hip)  ->  the fused convolution launch of the inference path (PReLU, shuffle, skip in its
+#              epilogue)
+#   kept    :  x (an input of the graph anyway), the three planes, mean / invstd, and the parameters — not u, z or y
+#   backward:  z recomputed by the un-fused convolution launch on the kept planes and packed weight (the same bits the
+#              epilogue saw)  ->  PReLU + shuffle backward (csrc/prelu_bwd.hip)  ->  the gradient kernels of the binary
+#              convolution, as BinaryConv2dTrainFusedFn uses them  ->  BatchNorm backward with the skip's gradient added
+#              in its dx kernel.
+# Off by default (its speed against the per-layer path is recorded in profiles/cellops_train_bench.jsonl; the default is
+# a later decision); BNN_AMD_TRAIN_CELL_OPS=1 or `training.CELL_OPS = True` turns it on — read at every call.
+CELL_OPS = os.environ.get("BNN_AMD_TRAIN_CELL_OPS", "0") == "1"
+
+CELL_OP_SHUFFLE = {"SepConv": 4, "DilConv": 4, "ReLUConvBN": 1}    # channel_shuffle(., 4) in SepConv / DilConv.forward
+
+
+def _cell_conv(planes, packed, conf, prelu=None, residual=None):
+    """The convolution launch of a cell operation on bit planes: with ``prelu`` / ``residual`` the fused forward, with
+    neither the pre-activation value ``z`` its epilogue starts from."""
+    groups, stride, padding, dilation, shuffle = conf
+    if groups != 1:
+        if prelu is None and residual is None:
+            return hipops.bconv2d_grouped(planes, packed, None, None, stride, padding, dilation)
+        return hipops.bconv2d_grouped_fused(planes, packed, None, None, stride, padding, dilation, prelu=prelu,
+                                            shuffle_groups=shuffle, residual=residual)
+    return hipops.bconv2d_fused(planes, packed, stride=stride, padding=padding, dilation=dilation, prelu=prelu,
+                                residual=residual, residual_after_act=True)[0]
+
+
+class CellOpTrainFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, slope, bn, conf, packed, add_skip, wconf):
+        x = x.contiguous()      # (see BNActFn.forward: what is saved is what the kernels ran on)
+        sv, mean, invstd, _, _ = hipops.bn_train_pack_ste(x, gamma, beta, bn.running_mean, bn.running_var, _momentum(bn),
+                                                          bn.eps)
+        _stats_written(bn)
+        O = w.shape[0]
+        slopes = slope.detach().reshape(-1)
+        y = _cell_conv(sv.sign, packed, conf, prelu=slopes.expand(O) if slopes.numel() == 1 else slopes,
+                       residual=x if add_skip else None)
+        # (the output is NOT saved: Cell.forward applies drop_path to it in place)
+        ctx.save_for_backward(x, sv.sign.P, sv.sign.M, sv.T, mean, invstd, w, gamma, slope)
+        ctx.packed, ctx.conf, ctx.add_skip, ctx.wconf = packed, conf, add_skip, wconf
+        global _saved_bytes
+        _saved_bytes += sv.nbytes()
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, P, M, T, mean, invstd, w, gamma, slope = ctx.saved_tensors
+        groups, stride, padding, dilation, shuffle = ctx.conf
+        center, compute_alpha = ctx.wconf
+        need_x, need_w, need_gamma, need_beta, need_slope = ctx.needs_input_grad[:5]
+        g = g.contiguous()
+        saved = hipops.SavedAct(hipops.PackedAct(P, M, tuple(x.shape)), T, tuple(x.shape))
+        z = _cell_conv(saved.sign, ctx.packed, ctx.conf)           # scratch: overwritten by gz, dies in here
+        gz, gslope = hipops.prelu_shuffle_backward(g, z, slope, shuffle, inplace=True)
+        need_u = need_x or need_gamma or need_beta
+        gu = gwhat = None
+        if groups != 1:
+            geom = (groups, stride, padding, dilation)
+            if need_u:
+                gu = hipops.bconv_grouped_grad_input(gz, saved, hipops.xnor_what(w, center, compute_alpha), *geom)
+            if need_w:
+                gwhat = hipops.bconv_grouped_grad_weight(gz, saved, w.shape, *geom, reduce=False)
+        else:
+            if need_u:
+                gpacked, alpha = hipops.xnor_grad_pack_weight(w, center, compute_alpha)
+                gu = hipops.bconv_grad_input(gz, saved, gpacked, alpha, w.shape[2], stride[0])
+            if need_w:
+                gwhat = hipops.bconv_grad_weight(gz, saved, w.shape[2], stride[0], reduce=False)
+        gw = None
+        if need_w:
+            if gwhat.shape[0] > 16:         # (see BinaryConv2dTrainFusedFn.backward)
+                gwhat = gwhat.sum(0)
+            gw = hipops.xnor_weight_backward(w, gwhat, center, compute_alpha)
+        dx = dgamma = dbeta = None
+        if need_u:
+            dx, dgamma, dbeta = hipops.bn_train_backward_add(gu, x, mean, invstd, gamma, g if ctx.add_skip else None)
+        return (dx if need_x else None, gw, dgamma if need_gamma else None, dbeta if need_beta else None,
+                gslope.reshape(slope.shape) if need_slope else None, None, None, None, None, None)
+
+
+def _no_hooks(*modules) -> bool:
+    return not any(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks
+                   for m in modules)
+
+
+def cell_op_train(op: nn.Module, x: torch.Tensor):
+    """``op(x)`` of a ``SepConv`` / ``DilConv`` / ``ReLUConvBN`` in train() mode as ``CellOpTrainFn``, or None — the
+    caller then runs the per-layer path — unless: the switches are on and autograd is recording without autocast; ``op.op``
+    is ``Sequential(BatchNorm2d, binary Conv2d, PReLU)`` with the BatchNorm under the rule of ``bn_act_applies``; the
+    recipe is BasicInputBinarizer + XNORWeightBinarizer without a post scale, no bias, zero padding given as numbers; the
+    gradient kernels cover the geometry; fp32 NCHW on a HIP device with more than one value per channel; nothing carries
+    a hook (it would not fire); and the conditions of the fused weight hook in ``conv2d_train`` hold."""
+    from . import fastpath
+    shuffle = CELL_OP_SHUFFLE.get(type(op).__name__)
+    seq = getattr(op, "op", None)
+    if not (CELL_OPS and ENABLED and BINARY_GRADS and FUSED_WEIGHT_HOOK and shuffle is not None and op.training
+            and torch.is_grad_enabled() and not torch.is_autocast_enabled()
+            and isinstance(seq, nn.Sequential) and len(seq) == 3):
+        return None
+    bn, conv, act = seq
+    if not (type(bn) is nn.BatchNorm2d and bn.training and bn.track_running_stats and bn.running_mean is not None
+            and bn.running_var is not None and isinstance(conv, nn.Conv2d) and hasattr(conv, "activation_pre_process")
+            and type(act) is nn.PReLU):
+        return None
+    plan = fastpath._recognise(conv, conv.out_channels)
+    if plan is None or not plan.ste or plan.scale is not None or conv.bias is not None \
+            or isinstance(conv.padding, str) or conv.padding_mode != "zeros":
+        return None
+    w, C, O, groups = conv.weight, conv.in_channels, conv.out_channels, int(conv.groups)
+    stride, padding, dilation = tuple(conv.stride), tuple(conv.padding), tuple(conv.dilation)
+    grouped = shuffle != 1
+    if grouped != (groups != 1) or O % shuffle or bn.num_features != C or act.weight.numel() not in (1, O) \
+            or getattr(op, "stride", None) != stride[0] or stride[0] != stride[1] \
+            or not isinstance(getattr(op, "skip", None), bool):
+        return None
+    if not grouped and (getattr(op, "C_in", None) != C or getattr(op, "C_out", None) != O):
+        return None
+    if not (w.dim() == 4 and w.is_contiguous() and w.shape[2] * w.shape[3] <= 1024):        # (conv2d_train's rule)
+        return None
+    if not _no_hooks(op, seq, bn, conv, act, conv.activation_pre_process, conv.weight_pre_process,
+                     conv.activation_post_process):
+        return None
+    tensors = [x, w, act.weight, bn.running_mean, bn.running_var] + [t for t in (bn.weight, bn.bias) if t is not None]
+    if not (x.dim() == 4 and x.shape[1] == C and x.numel() > C
+            and all(t.is_cuda and t.device == x.device and t.dtype == torch.float32 for t in tensors)):
+        return None
+    supported = hipops.grouped_grad_supported(x.shape, w.shape, groups, stride, padding, dilation) if grouped \
+        else hipops.grad_supported(x.shape, w.shape, stride, padding, dilation)
+    if not supported:
+        return None
+    add_skip = op.skip and stride[0] == 1 and (grouped or C == O)
+    packed = fastpath.packed_weight(conv, plan, sync=False, fresh=True)
+    y = CellOpTrainFn.apply(x, w, bn.weight, bn.bias, act.weight, bn, (groups, stride, padding, dilation, shuffle), packed,
+                            add_skip, (bool(plan.center), bool(plan.compute_alpha)))
+    fastpath._bump("cell_op_train")
+    return y
+
+
 def make_ddp(model: nn.Module, device: torch.device | None = None, **kw) -> nn.Module:
     """Wrap ``model`` for one-process-per-GPU data-parallel training (RCCL when on GPU, gloo on CPU).
     ``torch.distributed`` must be initialised.  Gradient buckets default to 64 MB: xGMI rings are

@@ -225,6 +225,41 @@ __global__ __launch_bounds__(bnt::NT) void bn_bwd_dx_kernel(const float* __restr
   }
 }
 
+// The same dx plus an addend: dx = k * (g - mb - (x - mean) * kg) + addend.  The backward of a BATS cell operation
+// y = x + f(bn(x)) hands the skip's gradient in here, so that it needs no add pass of its own (bnn_hip_bn_train_backward_add_f32).
+// A kernel of its own: the instantiations above stay what they were.
+template <int VEC, bool RELU>
+__global__ __launch_bounds__(bnt::NT) void bn_bwd_dx_add_kernel(const float* __restrict__ gy, const float* __restrict__ y,
+                                                                const float* __restrict__ x, const float* __restrict__ mean,
+                                                                const float* __restrict__ coef,
+                                                                const float* __restrict__ addend, float* __restrict__ dx,
+                                                                long long units, int C, int upr) {
+  const long long u = (long long)blockIdx.x * bnt::NT + threadIdx.x;
+  if (u >= units) return;
+  const int c = (int)((u / upr) % C);
+  const float mu = mean[c], k = coef[3 * c], mb = coef[3 * c + 1], kg = coef[3 * c + 2];
+  const size_t i0 = (size_t)u * VEC;
+  if constexpr (VEC == 4) {
+    float4 g = *reinterpret_cast<const float4*>(gy + i0);
+    const float4 xv = *reinterpret_cast<const float4*>(x + i0);
+    const float4 av = *reinterpret_cast<const float4*>(addend + i0);
+    if constexpr (RELU) {
+      const float4 yv = *reinterpret_cast<const float4*>(y + i0);
+      g.x = yv.x > 0.f ? g.x : 0.f; g.y = yv.y > 0.f ? g.y : 0.f; g.z = yv.z > 0.f ? g.z : 0.f; g.w = yv.w > 0.f ? g.w : 0.f;
+    }
+    float4 d;
+    d.x = k * (g.x - mb - (xv.x - mu) * kg) + av.x;
+    d.y = k * (g.y - mb - (xv.y - mu) * kg) + av.y;
+    d.z = k * (g.z - mb - (xv.z - mu) * kg) + av.z;
+    d.w = k * (g.w - mb - (xv.w - mu) * kg) + av.w;
+    *reinterpret_cast<float4*>(dx + i0) = d;
+  } else {
+    float g = gy[i0];
+    if constexpr (RELU) g = y[i0] > 0.f ? g : 0.f;
+    dx[i0] = k * (g - mb - (x[i0] - mu) * kg) + addend[i0];
+  }
+}
+
 // ------------------------------------------------------------------------------------------------- stem tail
 // bn1 -> relu -> maxpool(3, stride 2, pad 1) of the reference's ResNet stem (bnn/models/resnet.py:150-153) in training
 // mode.  The library evaluates it as BatchNorm (3 passes over the 822 MB conv output at batch 256), ReLU, max-pool
@@ -660,6 +695,34 @@ int launch_bn_relu_pool_bwd(const float* gy, const float* p, const unsigned char
   else
     hipLaunchKernelGGL(bn_pool_bwd_dx_kernel<1>, grid, dim3(bnt::NT), 0, s, gy, p, code, x, mean, work, dx, rows, C, H, W, Hp,
                        Wp, lpr_shift);
+  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+}
+
+// statistics -> mean, invstd, scale, shift (caller's [C] buffers) and the running statistics: the finalize step of
+// launch_bn_apply alone, for a consumer that applies scale / shift itself (pack_ste.hip: bn_pack_ste_kernel)
+int launch_bn_finalize(const double* partial, int splits, const float* gamma, const float* beta, int N, int C, int HW,
+                       float eps, float momentum, float* rm, float* rv, float* mean_out, float* invstd_out, float* scale_out,
+                       float* shift_out, hipStream_t s) {
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, s, partial, splits, C,
+                     (double)N * HW, gamma, beta, eps, momentum, rm, rv, mean_out, invstd_out, scale_out, shift_out);
+  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+}
+
+// launch_bn_bwd_dx with dx += addend (non-null; no dres)
+int launch_bn_bwd_dx_add(const float* gy, const float* y, const float* x, const float* mean, const float* invstd,
+                         const float* gamma, const double* partial, int splits, const float* addend, float* dx,
+                         float* dgamma, float* dbeta, int N, int C, int HW, float* work, hipStream_t s) {
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, s, partial, splits, C,
+                     (double)N * HW, gamma, invstd, dgamma, dbeta, work);
+  const bool v4 = vec4(gy, y, x, dx, HW) && vec4(addend, nullptr, nullptr, nullptr, HW);
+  const int vec = v4 ? 4 : 1;
+  const long long units = (long long)N * C * HW / vec;
+  const dim3 grid((unsigned)((units + bnt::NT - 1) / bnt::NT));
+  const int upr = HW / vec;
+#define BNN_DXA(V_, R_)   hipLaunchKernelGGL((bn_bwd_dx_add_kernel<V_, R_>), grid, dim3(bnt::NT), 0, s, gy, y, x, mean, work, addend, dx, units, C, upr)
+  if (v4) { if (y) BNN_DXA(4, true); else BNN_DXA(4, false); }
+  else { if (y) BNN_DXA(1, true); else BNN_DXA(1, false); }
+#undef BNN_DXA
   return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
 }
 

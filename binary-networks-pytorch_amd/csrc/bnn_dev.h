@@ -179,6 +179,9 @@ int launch_wgrad(const float* g, const void* xin, const void* xin2, int x_planes
                  int C, int H, int W, int ks, int stride, hipStream_t s);
 int launch_pack_ste(const float* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M, uint64_t* T,
                     hipStream_t stream);
+// the same planes of fmaf(x, bn_a[c], bn_b[c]) (bn_a == bn_b == null: of x), u never written
+int launch_bn_pack_ste(const float* x, int N, int C, int H, int W, const float* bn_a, const float* bn_b, uint64_t* P,
+                       uint64_t* M, uint64_t* T, hipStream_t stream);
 int launch_pack_weight(const float* w, int O, int C, int KH, int KW, int center, int compute_alpha,
                        const bnn_hip_wlayout& L, uint32_t* wbits, uint32_t* wnz, float* alpha,
                        int32_t* zero_flag, hipStream_t stream);
@@ -256,6 +259,15 @@ int launch_bn_bwd_reduce(const float* gy, const float* y, const float* x, const 
 int launch_bn_bwd_dx(const float* gy, const float* y, const float* x, const float* mean, const float* invstd,
                      const float* gamma, const double* partial, int splits, float* dx, float* dres, float* dgamma,
                      float* dbeta, int N, int C, int HW, float* work, hipStream_t s);
+int launch_bn_finalize(const double* partial, int splits, const float* gamma, const float* beta, int N, int C, int HW,
+                       float eps, float momentum, float* rm, float* rv, float* mean_out, float* invstd_out, float* scale_out,
+                       float* shift_out, hipStream_t s);
+int launch_bn_bwd_dx_add(const float* gy, const float* y, const float* x, const float* mean, const float* invstd,
+                         const float* gamma, const double* partial, int splits, const float* addend, float* dx,
+                         float* dgamma, float* dbeta, int N, int C, int HW, float* work, hipStream_t s);
+// prelu_bwd.hip: backward of channel_shuffle(PReLU(z), sg); `partial`: O * splits doubles, splits = bn_train_splits(N, O, HW)
+int launch_prelu_shuffle_bwd(const float* gy, const float* z, const float* slope, int slope_count, int N, int O, int HW,
+                             int sg, int splits, float* gz, float* dslope, double* partial, hipStream_t s);
 int launch_bn_relu_pool_fwd(const float* x, const double* partial, int splits, const float* gamma, const float* beta,
                             float* p, unsigned char* code, int N, int C, int H, int W, float eps, float momentum, float* rm,
                             float* rv, float* mean_out, float* invstd_out, float* work, hipStream_t s);

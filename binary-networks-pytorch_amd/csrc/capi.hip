@@ -662,6 +662,17 @@ int bnn_hip_pack_act_ste_f32(const float* x, int N, int C, int H, int W, uint64_
   return bnn::launch_pack_ste(x, N, C, H, W, P, M, T, static_cast<hipStream_t>(stream));
 }
 
+int bnn_hip_bn_act_pack_ste_f32(const float* x, int N, int C, int H, int W, const float* bn_scale, const float* bn_shift,
+                                uint64_t* P, uint64_t* M, uint64_t* T, void* stream) {
+  if (!T || (bn_scale == nullptr) != (bn_shift == nullptr)) return BNN_HIP_ERR_INVALID_ARG;
+  const int st = check_pack(x, 4, N, C, H, W, P, M);
+  if (st != BNN_HIP_OK) return st;
+  if (!aligned(T, 8) || !aligned(bn_scale, 4) || !aligned(bn_shift, 4)) return BNN_HIP_ERR_INVALID_ARG;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_bn_pack_ste(x, N, C, H, W, bn_scale, bn_shift, P, M, T, static_cast<hipStream_t>(stream));
+}
+
 int bnn_hip_bconv_grad_weight_splits(int N, int O, int C, int ksize) {
   return (N > 0 && O > 0 && C > 0 && grad_ks_ok(ksize)) ? bnn::grad_wgrad_splits(N, O, C, ksize)
                                                          : BNN_HIP_ERR_INVALID_ARG;
@@ -1081,6 +1092,32 @@ int bnn_hip_bn_train_forward_f32(const float* x, int N, int C, int HW, const flo
                               running_var, save_mean, save_invstd, ws.work, static_cast<hipStream_t>(stream));
 }
 
+int bnn_hip_bn_train_pack_ste_f32(const float* x, int N, int C, int H, int W, const float* gamma, const float* beta,
+                                  float eps, float momentum, float* running_mean, float* running_var, uint64_t* P,
+                                  uint64_t* M, uint64_t* T, float* save_mean, float* save_invstd, float* scale, float* shift,
+                                  void* workspace, void* stream) {
+  if (!T || !save_mean || !save_invstd || !scale || !shift || !workspace) return BNN_HIP_ERR_INVALID_ARG;
+  const int stp = check_pack(x, 4, N, C, H, W, P, M);
+  if (stp != BNN_HIP_OK) return stp;
+  const int HW = checked_hw(H, W);
+  const int st = check_bn(N, C, HW);
+  if (st != BNN_HIP_OK) return st;
+  if ((running_mean == nullptr) != (running_var == nullptr) || !(eps >= 0.0f)) return BNN_HIP_ERR_INVALID_ARG;
+  if (!aligned(T, 8) || !aligned(scale, 4) || !aligned(shift, 4) || !aligned(save_mean, 4) || !aligned(save_invstd, 4) ||
+      !aligned(workspace, 8))
+    return BNN_HIP_ERR_INVALID_ARG;
+  const BnWorkspace ws = bn_workspace(N, C, HW, workspace);
+  g_launches.fetch_add(3, std::memory_order_relaxed);
+  BNN_RANGE();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int st2 = bnn::launch_bn_stats(x, N, C, HW, ws.splits, ws.partial, s);
+  if (st2 != BNN_HIP_OK) return st2;
+  st2 = bnn::launch_bn_finalize(ws.partial, ws.splits, gamma, beta, N, C, HW, eps, momentum, running_mean, running_var,
+                                save_mean, save_invstd, scale, shift, s);
+  if (st2 != BNN_HIP_OK) return st2;
+  return bnn::launch_bn_pack_ste(x, N, C, H, W, scale, shift, P, M, T, s);
+}
+
 int bnn_hip_bn_act_f32(const float* x, int N, int C, int HW, const float* scale, const float* shift, const float* residual,
                        int relu, float* y, void* stream) {
   if (!x || !y || !scale || !shift) return BNN_HIP_ERR_INVALID_ARG;
@@ -1110,6 +1147,51 @@ int bnn_hip_bn_train_backward_f32(const float* gy, const float* y, const float* 
   if (st2 != BNN_HIP_OK) return st2;
   return bnn::launch_bn_bwd_dx(gy, y, x, save_mean, save_invstd, gamma, ws.partial, ws.splits, dx, dres, dgamma, dbeta, N, C,
                                HW, ws.work, static_cast<hipStream_t>(stream));
+}
+
+int bnn_hip_bn_train_backward_add_f32(const float* gy, const float* y, const float* x, const float* save_mean,
+                                      const float* save_invstd, const float* gamma, const float* addend, int N, int C,
+                                      int HW, float* dx, float* dgamma, float* dbeta, void* workspace, void* stream) {
+  if (!addend)    // no skip: the existing backward, bit for bit
+    return bnn_hip_bn_train_backward_f32(gy, y, x, save_mean, save_invstd, gamma, N, C, HW, dx, nullptr, dgamma, dbeta,
+                                         workspace, stream);
+  if (!gy || !x || !save_mean || !save_invstd || !dx || !workspace) return BNN_HIP_ERR_INVALID_ARG;
+  const int st = check_bn(N, C, HW);
+  if (st != BNN_HIP_OK) return st;
+  if (!aligned(gy, 4) || !aligned(x, 4) || !aligned(dx, 4) || (y && !aligned(y, 4)) || !aligned(addend, 4) ||
+      !aligned(workspace, 8))
+    return BNN_HIP_ERR_INVALID_ARG;
+  const BnWorkspace ws = bn_workspace(N, C, HW, workspace);
+  g_launches.fetch_add(3, std::memory_order_relaxed);
+  BNN_RANGE();
+  const int st2 = bnn::launch_bn_bwd_reduce(gy, y, x, save_mean, save_invstd, N, C, HW, ws.splits, ws.partial,
+                                            static_cast<hipStream_t>(stream));
+  if (st2 != BNN_HIP_OK) return st2;
+  return bnn::launch_bn_bwd_dx_add(gy, y, x, save_mean, save_invstd, gamma, ws.partial, ws.splits, addend, dx, dgamma, dbeta,
+                                   N, C, HW, ws.work, static_cast<hipStream_t>(stream));
+}
+
+// ---- backward of channel_shuffle(PReLU(z), shuffle_groups): csrc/prelu_bwd.hip
+size_t bnn_hip_prelu_shuffle_backward_workspace_bytes(int N, int O, int HW) {
+  return check_bn(N, O, HW) == BNN_HIP_OK ? (size_t)O * bnn::bn_train_splits(N, O, HW) * sizeof(double) : 0;
+}
+
+int bnn_hip_prelu_shuffle_backward_f32(const float* gy, const float* z, const float* slope, int slope_count, int N, int O,
+                                       int HW, int shuffle_groups, float* gz, float* dslope, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+  if (!gy || !z || !slope || !gz || !dslope || !workspace) return BNN_HIP_ERR_INVALID_ARG;
+  const int st = check_bn(N, O, HW);
+  if (st != BNN_HIP_OK) return st;
+  if ((slope_count != 1 && slope_count != O) || shuffle_groups <= 0 || O % shuffle_groups != 0) return BNN_HIP_ERR_INVALID_ARG;
+  if (gz == gy) return BNN_HIP_ERR_INVALID_ARG;   // (gz may be z: same index read and written by one thread; gy is read shuffled)
+  if (!aligned(gy, 4) || !aligned(z, 4) || !aligned(slope, 4) || !aligned(gz, 4) || !aligned(dslope, 4) || !aligned(workspace, 8))
+    return BNN_HIP_ERR_INVALID_ARG;
+  const int splits = bnn::bn_train_splits(N, O, HW);
+  if (workspace_bytes < (size_t)O * splits * sizeof(double)) return BNN_HIP_ERR_INVALID_ARG;
+  g_launches.fetch_add(2, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_prelu_shuffle_bwd(gy, z, slope, slope_count, N, O, HW, shuffle_groups, splits, gz, dslope,
+                                       static_cast<double*>(workspace), static_cast<hipStream_t>(stream));
 }
 
 int bnn_hip_bn_relu_maxpool_train_forward_f32(const float* x, int N, int C, int H, int W, const float* gamma,

@@ -61,7 +61,11 @@
 extern "C" {
 #endif
 
-/* ABI 15 (round 6): + bnn_hip_hblock_{supported,layout_of,pack_weights,forward} (the hierarchical block in one launch);
+/* Additive entry points of ABI 15 for the training step of a BATS cell operation (no struct or signature changed):
+ * + bnn_hip_bn_act_pack_ste_f32, bnn_hip_bn_train_pack_ste_f32 (BatchNorm + sign + straight-through mask as three bit
+ * planes, the normalised tensor never written); + bnn_hip_prelu_shuffle_backward_f32 / _workspace_bytes (backward of
+ * channel_shuffle(PReLU(.))); + bnn_hip_bn_train_backward_add_f32 (the BatchNorm backward with the skip's gradient added).
+ * ABI 15 (round 6): + bnn_hip_hblock_{supported,layout_of,pack_weights,forward} (the hierarchical block in one launch);
  * + bnn_hip_avgpool2_bn_pack2_f32 (the pool in front of a pre-activation stage + both sign planes it feeds);
  * + bnn_hip_grouped_weight_layout, bnn_hip_pack_weight_grouped_f32, bnn_hip_bconv2d_grouped (grouped / depthwise
  * convolutions: additive entry points of ABI 15, no struct or signature changed); + bnn_hip_bconv2d_grouped_fused (the
@@ -414,6 +418,11 @@ int bnn_hip_bconv_grad_weight_f32(const float* g, const float* x, float* partial
  * (input gradient) resp. P and M (weight gradient).  Results are bit-identical to the fp32-x entry points.            */
 int bnn_hip_pack_act_ste_f32(const float* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M, uint64_t* T,
                              void* stream);
+/* The same three planes of u = fmaf(x, bn_scale[c], bn_shift[c]) — the expression of bnn_hip_bn_act_pack_f32 and of the
+ * apply pass of bnn_hip_bn_train_forward_f32, so the bits of bnn_hip_pack_act_ste_f32 on their output — in one pass over
+ * x, u never written.  bn_scale / bn_shift: fp32 [C], both or neither; both NULL: the bits of bnn_hip_pack_act_ste_f32.  */
+int bnn_hip_bn_act_pack_ste_f32(const float* x, int N, int C, int H, int W, const float* bn_scale, const float* bn_shift,
+                                uint64_t* P, uint64_t* M, uint64_t* T, void* stream);
 int bnn_hip_bconv_grad_input_packed_f32(const float* g, const float* alpha, const void* packed_w, const uint64_t* T,
                                         float* gx, int N, int O, int C, int H, int W, int ksize, int stride,
                                         void* stream);
@@ -787,6 +796,38 @@ int bnn_hip_bn_train_forward_f32(const float* x, int N, int C, int HW, const flo
 int bnn_hip_bn_train_backward_f32(const float* gy, const float* y, const float* x, const float* save_mean,
                                   const float* save_invstd, const float* gamma, int N, int C, int HW, float* dx,
                                   float* dres, float* dgamma, float* dbeta, void* workspace, void* stream);
+
+/* The same backward with an addend:  dx = gamma * invstd * (g - dbeta / m - xhat * dgamma / m) + addend.  The backward
+ * of y = x + f(batch_norm_train(x)) passes the skip's gradient (gy of the whole operation) as `addend`, fp32 [N, C, HW],
+ * and needs no add pass of its own.  dgamma / dbeta: the bits of bnn_hip_bn_train_backward_f32.  addend == NULL: that
+ * entry point itself (dres NULL), bit for bit.  No dres here.  Same workspace.                                       */
+int bnn_hip_bn_train_backward_add_f32(const float* gy, const float* y, const float* x, const float* save_mean,
+                                      const float* save_invstd, const float* gamma, const float* addend, int N, int C,
+                                      int HW, float* dx, float* dgamma, float* dbeta, void* workspace, void* stream);
+
+/* Training-mode BatchNorm2d in front of a binary convolution (the BATS cell operations, bnn/models/layers/bats_ops.py:
+ * 78-173: BatchNorm2d -> binary Conv2d): the statistics and running-statistics update of bnn_hip_bn_train_forward_f32
+ * (same kernels: save_mean, save_invstd and the running buffers get the same bits), then the three bit planes of
+ * bnn_hip_bn_act_pack_ste_f32 with scale = gamma * invstd, shift = beta - mean * scale — the normalised tensor is never
+ * written.  scale / shift: fp32 [C], outputs (what the planes were made with).  gamma / beta may be NULL.  Workspace:
+ * bnn_hip_bn_train_workspace_bytes(N, C, H * W).  Three launches, no synchronisation.                                */
+int bnn_hip_bn_train_pack_ste_f32(const float* x, int N, int C, int H, int W, const float* gamma, const float* beta,
+                                  float eps, float momentum, float* running_mean, float* running_var, uint64_t* P,
+                                  uint64_t* M, uint64_t* T, float* save_mean, float* save_invstd, float* scale, float* shift,
+                                  void* workspace, void* stream);
+
+/* Backward of  y = channel_shuffle(PReLU(z), shuffle_groups)  (the tail of a BATS cell operation; the forward is the
+ * epilogue of bnn_hip_bconv2d_grouped_fused / bnn_hip_bconv2d_fused).  gy: fp32 [N, O, HW] in the OUTPUT's (shuffled)
+ * channel order; z, gz: fp32 [N, O, HW] in the convolution's order; slope: slope_count (1 or O) floats:
+ *     gz[n,o,:] = z > 0 ? g : slope[o] * g      g = gy[n, (o % (O / sg)) * sg + o / (O / sg), :]     (z == +-0: slope branch)
+ *     dslope[o] = sum over n, pixels with !(z > 0) of g * z          (slope_count == 1: one value, summed over o as well)
+ * torch.nn.PReLU's convention.  The sums are accumulated in double through per-(channel, image split) partials added in a
+ * fixed order: no atomics, the same bits on every run.  gz may be z (in place), not gy.  workspace:
+ * bnn_hip_prelu_shuffle_backward_workspace_bytes(N, O, HW) bytes, 8-byte aligned.  Two launches.                      */
+size_t bnn_hip_prelu_shuffle_backward_workspace_bytes(int N, int O, int HW);
+int bnn_hip_prelu_shuffle_backward_f32(const float* gy, const float* z, const float* slope, int slope_count, int N, int O,
+                                       int HW, int shuffle_groups, float* gz, float* dslope, void* workspace,
+                                       size_t workspace_bytes, void* stream);
 
 /* Eval-mode BatchNorm2d with folded constants, fused with what follows it in the reference's residual blocks:
  *     y = relu?( fmaf(x, scale[c], shift[c]) (+ residual) )     bnn/models/layers/res_block.py:40-56 under .eval()

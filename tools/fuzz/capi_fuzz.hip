@@ -324,6 +324,11 @@ int launch_dgrad(const float* g, const float* alpha, const void* packed, const v
 int launch_pack_ste(const float* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M, uint64_t* T, hipStream_t) {
   ++g_reached; check_planes(x, N, C, H, W, P, M, 4); REQUIRE(T && al(T, 8)); return BNN_HIP_OK;
 }
+int launch_bn_pack_ste(const float* x, int N, int C, int H, int W, const float* a, const float* b, uint64_t* P, uint64_t* M,
+                       uint64_t* T, hipStream_t) {
+  ++g_reached; check_planes(x, N, C, H, W, P, M, 4); REQUIRE(T && al(T, 8) && (a == nullptr) == (b == nullptr) && al(a, 4) && al(b, 4));
+  return BNN_HIP_OK;
+}
 int grad_wgrad_splits(int N, int O, int C, int ks) { REQUIRE(N > 0 && O > 0 && C > 0 && (ks == 1 || ks == 3)); return 1; }
 int launch_wgrad(const float* g, const void* x, const void* x2, int planes, float* part, int, int N, int O, int C, int H,
                  int W, int ks, int stride, hipStream_t) {
@@ -383,6 +388,26 @@ int launch_bn_bwd_dx(const float* gy, const float*, const float* x, const float*
                      const double* partial, int S, float* dx, float*, float*, float*, int N, int C, int HW, float* work,
                      hipStream_t) {
   ++g_reached; check_bn_args(N, C, HW); REQUIRE(gy && x && m && is && partial && dx && work && S >= 1); return BNN_HIP_OK;
+}
+int launch_bn_finalize(const double* partial, int S, const float*, const float*, int N, int C, int HW, float eps, float,
+                       float* rm, float* rv, float* mo, float* io, float* sc, float* sh, hipStream_t) {
+  ++g_reached; check_bn_args(N, C, HW);
+  REQUIRE(partial && mo && io && sc && sh && S >= 1 && S <= N && eps >= 0.0f && (rm == nullptr) == (rv == nullptr));
+  return BNN_HIP_OK;
+}
+int launch_bn_bwd_dx_add(const float* gy, const float* y, const float* x, const float* m, const float* is, const float*,
+                         const double* partial, int S, const float* addend, float* dx, float*, float*, int N, int C, int HW,
+                         float* work, hipStream_t) {
+  ++g_reached; check_bn_args(N, C, HW);
+  REQUIRE(gy && x && m && is && partial && addend && dx && work && S >= 1 && al(addend, 4) && al(dx, 4) && al(y, 4));
+  return BNN_HIP_OK;
+}
+int launch_prelu_shuffle_bwd(const float* gy, const float* z, const float* slope, int count, int N, int O, int HW, int sg,
+                             int S, float* gz, float* dslope, double* partial, hipStream_t) {
+  ++g_reached; check_bn_args(N, O, HW);
+  REQUIRE(gy && z && slope && gz && dslope && partial && gz != gy && (count == 1 || count == O) && sg >= 1 && O % sg == 0);
+  REQUIRE(S == bn_train_splits(N, O, HW) && (long long)N * HW <= (1LL << 31) - 1 && al(partial, 8) && al(gy, 4) && al(z, 4) && al(gz, 4));
+  return BNN_HIP_OK;
 }
 int launch_bn_relu_pool_fwd(const float* x, const double* partial, int S, const float*, const float*, float* p, unsigned char* code,
                             int N, int C, int H, int W, float eps, float, float* rm, float* rv, float* mo, float* io, float* work,
@@ -564,7 +589,7 @@ int main(int argc, char** argv) {
   for (long it = 0; it < iters; ++it) {
     ++g_calls;
     int st = 0;
-    switch (rnd() % 56) {
+    switch (rnd() % 60) {
       case 0: { bnn_hip_conv_desc d = pick_desc();
         st = bnn_hip_bconv2d(rnd() % 16 ? &d : nullptr, pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<uint32_t>(),
                              pick_ptr<uint32_t>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), stream);
@@ -809,6 +834,29 @@ int main(int argc, char** argv) {
                                             pick_ptr<float>(), pick_ptr<float>(), pick_int(), C, O, pick_groups(C, O), pick_int(),
                                             pick_int(), (int)(rnd() % 3), rnd() % 4 ? (int)(rnd() % 5) : pick_int(),
                                             pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<float>(), stream);
+        break; }
+      case 56: st = bnn_hip_bn_act_pack_ste_f32(pick_ptr<float>(), pick_int(), pick_int(), pick_int(), pick_int(), pick_ptr<float>(),
+                                                pick_ptr<float>(), pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<uint64_t>(),
+                                                stream); break;
+      case 57: st = bnn_hip_bn_train_pack_ste_f32(pick_ptr<float>(), pick_int(), pick_int(), pick_int(), pick_int(), pick_ptr<float>(),
+                                                  pick_ptr<float>(), (float)(pick_int() % 3) * 1e-5f, 0.1f, pick_ptr<float>(),
+                                                  pick_ptr<float>(), pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<uint64_t>(),
+                                                  pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(),
+                                                  pick_ptr<double>(), stream); break;
+      case 58: st = bnn_hip_bn_train_backward_add_f32(pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(),
+                                                      pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), pick_int(), pick_int(),
+                                                      pick_int(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(),
+                                                      pick_ptr<double>(), stream); break;
+      case 59: { const int N = pick_int(), O = pick_int(), HW = pick_int();
+        const int sgs[] = {1, 1, 2, 4, 12};
+        const int sg = rnd() % 8 ? sgs[rnd() % 5] : pick_int();
+        const size_t need = bnn_hip_prelu_shuffle_backward_workspace_bytes(N, O, HW);
+        if (need > ((size_t)1 << 40)) broken("prelu backward workspace size");
+        float* gz = pick_ptr<float>();
+        st = bnn_hip_prelu_shuffle_backward_f32(rnd() % 8 ? pick_ptr<float>() : gz, rnd() % 4 ? pick_ptr<float>() : gz,
+                                                pick_ptr<float>(), rnd() % 3 ? (rnd() % 2 ? 1 : O) : pick_int(), N, O, HW, sg, gz,
+                                                pick_ptr<float>(), pick_ptr<double>(),
+                                                rnd() % 4 ? need : (size_t)(rnd() % 4096), stream);
         break; }
       default: { bnn_hip_conv_desc d = pick_desc();
         (void)bnn_hip_shortcut_fold_supported(rnd() % 16 ? &d : nullptr, pick_int());
