@@ -42,7 +42,7 @@ from . import hipops, native
 
 _stats_lock = threading.Lock()
 _stats = {"conv2d": 0, "conv1d": 0, "linear": 0, "weight_packs": 0, "conv2d_train": 0, "cell_op": 0, "cell": 0,
-          "cell_op_train": 0}
+          "cell_op_train": 0, "reduce_train": 0}
 
 
 def stats() -> dict:

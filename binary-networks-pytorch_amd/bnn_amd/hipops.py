@@ -1438,6 +1438,38 @@ def bn_act_pack_ste(x: torch.Tensor, bn_scale=None, bn_shift=None) -> SavedAct:
     return sv
 
 
+def _ste_planes_s2(x: torch.Tensor, what: str):
+    """``_ste_planes`` for the two pixel lattices of ``FactorizedReduce``: ``P`` / ``M`` / ``T`` as ``[2, N, cw64, H/2,
+    W/2]`` tensors (phase-major, what one launch writes) and the two ``SavedAct`` that view them."""
+    x = _require_cuda_f32(x, "activation")
+    if x.dim() != 4 or x.shape[2] % 2 or x.shape[3] % 2:
+        raise native.NativeError(f"bnn_amd: {what} expects NCHW with even H and W, got shape {tuple(x.shape)}")
+    N, C, H, W = x.shape
+    shape = (N, C, H // 2, W // 2)
+    P = torch.empty((2, N, (C + 63) // 64, H // 2, W // 2), dtype=torch.int64, device=x.device)
+    M, T = torch.empty_like(P), torch.empty_like(P)
+    return x, (P, M, T), tuple(SavedAct(PackedAct(P[k], M[k], shape), T[k], shape) for k in range(2))
+
+
+def bn_act_pack_ste_s2(x: torch.Tensor, bn_scale=None, bn_shift=None):
+    """``(bn_act_pack_ste(x[:, :, ::2, ::2]), bn_act_pack_ste(x[:, :, 1::2, 1::2]))`` — the three planes of the two pixel
+    lattices ``FactorizedReduce`` reads — in one pass over ``x`` (``bnn_hip_bn_act_pack_ste_s2_f32``; H and W even).
+    Both constants or neither."""
+    if (bn_scale is None) != (bn_shift is None):
+        raise native.NativeError("bnn_amd: bn_act_pack_ste_s2 takes bn_scale and bn_shift together")
+    x, (P, M, T), phases = _ste_planes_s2(x, "bn_act_pack_ste_s2")
+    N, C, H, W = x.shape
+    bn_scale = _per_channel(bn_scale, C, "bn_scale")
+    bn_shift = _per_channel(bn_shift, C, "bn_shift")
+    lib = native.require()
+    if N:
+        with torch.cuda.device(x.device):
+            native.check(lib.bnn_hip_bn_act_pack_ste_s2_f32(
+                x.data_ptr(), N, C, H, W, _ptr(bn_scale), _ptr(bn_shift), P.data_ptr(), M.data_ptr(), T.data_ptr(),
+                _stream(x.device)), "bnn_hip_bn_act_pack_ste_s2_f32")
+    return phases
+
+
 def _grad_shapes(g: torch.Tensor, x, stride: int):
     N, C, H, W = x.shape
     O = g.shape[1]
@@ -1727,6 +1759,54 @@ def bn_train_backward_add(gy: torch.Tensor, x: torch.Tensor, mean: torch.Tensor,
             gy.data_ptr(), None, x.data_ptr(), mean.data_ptr(), invstd.data_ptr(), _ptr(gamma), _ptr(addend), N, C, H * W,
             dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), _stream(x.device)),
             "bnn_hip_bn_train_backward_add_f32")
+    return dx, dgamma, dbeta
+
+
+def bn_train_pack_ste_s2(x: torch.Tensor, gamma, beta, running_mean, running_var, momentum: float, eps: float):
+    """``bn_train_pack_ste`` for ``FactorizedReduce`` (``bnn_hip_bn_train_pack_ste_s2_f32``): the same statistics over all
+    of ``x`` and the same running-statistics update, then the planes of ``bn_act_pack_ste_s2``.  Returns ``((SavedAct,
+    SavedAct), save_mean, save_invstd, scale, shift)``."""
+    x, (P, M, T), phases = _ste_planes_s2(x, "bn_train_pack_ste_s2")
+    N, C, H, W = x.shape
+    gamma = _per_channel(gamma, C, "BatchNorm weight")
+    beta = _per_channel(beta, C, "BatchNorm bias")
+    running_mean = _per_channel(running_mean, C, "running_mean")
+    running_var = _per_channel(running_var, C, "running_var")
+    lib = native.require()
+    with torch.cuda.device(x.device):
+        mean, invstd, ws = _bn_train_buffers(lib, x)
+        scale, shift = torch.empty_like(mean), torch.empty_like(mean)
+        native.check(lib.bnn_hip_bn_train_pack_ste_s2_f32(
+            x.data_ptr(), N, C, H, W, _ptr(gamma), _ptr(beta), float(eps), float(momentum), _ptr(running_mean),
+            _ptr(running_var), P.data_ptr(), M.data_ptr(), T.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
+            scale.data_ptr(), shift.data_ptr(), ws.data_ptr(), _stream(x.device)), "bnn_hip_bn_train_pack_ste_s2_f32")
+    return phases, mean, invstd, scale, shift
+
+
+def bn_train_backward_s2(g0: torch.Tensor, g1: torch.Tensor, x: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor,
+                         gamma):
+    """Backward of training-mode BatchNorm for a gradient that lives on the two pixel lattices of ``FactorizedReduce``
+    (``bnn_hip_bn_train_backward_s2_f32``): ``g0[n, c, i, j]`` at ``(2i, 2j)``, ``g1`` at ``(2i+1, 2j+1)``, zero
+    elsewhere -> ``(dx, dgamma, dbeta)`` with the full-resolution ``dx`` written in one pass."""
+    g0 = _require_cuda_f32(g0, "grad_output")
+    g1 = _require_cuda_f32(g1, "grad_output")
+    x = _require_cuda_f32(x, "BatchNorm input")
+    if x.dim() != 4 or x.shape[2] % 2 or x.shape[3] % 2:
+        raise native.NativeError(f"bnn_amd: bn_train_backward_s2 expects NCHW with even H and W, got {tuple(x.shape)}")
+    N, C, H, W = x.shape
+    if tuple(g0.shape) != (N, C, H // 2, W // 2) or g1.shape != g0.shape:
+        raise native.NativeError(f"bnn_amd: bn_train_backward_s2: grad_outputs {tuple(g0.shape)} / {tuple(g1.shape)} do not "
+                                 f"belong to the NCHW input {tuple(x.shape)}")
+    if x.data_ptr() % 8:        # (a view one float into its storage: the kernels move rows as float2)
+        x = x.clone()
+    lib = native.require()
+    with torch.cuda.device(x.device):
+        dx = torch.empty_like(x)
+        dgamma, dbeta, ws = _bn_train_buffers(lib, x)
+        native.check(lib.bnn_hip_bn_train_backward_s2_f32(
+            g0.data_ptr(), g1.data_ptr(), x.data_ptr(), mean.data_ptr(), invstd.data_ptr(), _ptr(gamma), N, C, H, W,
+            dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), _stream(x.device)),
+            "bnn_hip_bn_train_backward_s2_f32")
     return dx, dgamma, dbeta
 
 

@@ -11,7 +11,8 @@ fixtures generated from the reference.  Every operation has the form
 
 and, evaluated for inference on a HIP device, first offers itself to the cell-operation executor
 (``bnn_amd/dispatch.py: OpFusion`` -> ``bnn_amd/cellops.py: FusedCellOp``); in ``train()`` mode under autograd, with
-``training.CELL_OPS`` on, to the training executor (``bnn_amd/training.py: cell_op_train`` -> ``CellOpTrainFn``).
+``training.CELL_OPS`` on, to the training executor (``bnn_amd/training.py: cell_op_train`` -> ``CellOpTrainFn``;
+``FactorizedReduce``: ``reduce_train`` -> ``ReduceTrainFn``).
 """
 from __future__ import annotations
 
@@ -133,6 +134,12 @@ class FactorizedReduce(nn.Module):
         self.bn = nn.BatchNorm2d(C_in, affine=affine)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.training and torch.is_grad_enabled():
+            from .. import training                 # (see _CellOp.forward)
+            if training.CELL_OPS:       # read at every call; None: the rule of training.reduce_train declined
+                y = training.reduce_train(self, x)
+                if y is not None:
+                    return y
         x = self.bn(x)
         out = torch.cat([self.conv_1(x), self.conv_2(x[:, :, 1:, 1:])], dim=1)
         return self.activation(out)

@@ -142,6 +142,7 @@ _PROTOTYPES = {
     "bnn_hip_bn_act_pack_ste_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bnn_hip_bn_act_pack_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "bnn_hip_bn_act_pack_multi_f32": (_i, [_view_p, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "bnn_hip_bn_act_pack_ste_s2_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bnn_hip_bn_act_pack_s2_f32": (_i, [_view_p, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "bnn_hip_stem3x3_bn_relu_pack_f32": (_i, [_vp] * 6 + [_i] * 5 + [_vp] * 4),
     "bnn_hip_stem_s2x2_f32": (_i, [_vp] * 7 + [_i] * 7 + [_vp] * 2),
@@ -194,6 +195,8 @@ _PROTOTYPES = {
     "bnn_hip_bn_train_backward_f32": (_i, [_vp] * 6 + [_i, _i, _i] + [_vp] * 6),
     "bnn_hip_bn_train_backward_add_f32": (_i, [_vp] * 7 + [_i, _i, _i] + [_vp] * 5),
     "bnn_hip_bn_train_pack_ste_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _f, _f] + [_vp] * 11),
+    "bnn_hip_bn_train_pack_ste_s2_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _f, _f] + [_vp] * 11),
+    "bnn_hip_bn_train_backward_s2_f32": (_i, [_vp] * 6 + [_i, _i, _i, _i] + [_vp] * 5),
     "bnn_hip_prelu_shuffle_backward_workspace_bytes": (_sz, [_i, _i, _i]),
     "bnn_hip_prelu_shuffle_backward_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "bnn_hip_bn_relu_maxpool_train_forward_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _f, _f] + [_vp] * 8),

@@ -558,6 +558,139 @@ def cell_op_train(op: nn.Module, x: torch.Tensor):
     return y
 
 
+# ---- FactorizedReduce in a training step -----------------------------------------------------------------------------
+# y = PReLU(cat(conv_1(sign(bn(x))), conv_2(sign(bn(x)[:, :, 1:, 1:]))))  with two 1x1 / stride-2 convolutions reads
+# bn(x) at the pixels (2i, 2j) and (2i+1, 2j+1) only.  `ReduceTrainFn` is the module as one autograd function, behind the
+# same switch as the cell operations (CELL_OPS):
+#   forward :  batch statistics over all of x  ->  BatchNorm + sign + STE mask of the two lattices as bit planes at half
+#              resolution (csrc/pack_ste.hip: bn_pack_ste_s2_kernel), u never written  ->  two dense 1x1 STRIDE-1
+#              launches on the phase planes, each with its half of the PReLU slopes, stored into its half of y
+#   kept    :  x, the two triples of planes, mean / invstd, the parameters — not u, the convolution outputs or y
+#   backward:  z recomputed by the un-fused launches  ->  PReLU backward on the whole of g  ->  ONE copy of gz that makes
+#              its two channel halves contiguous (the gradient kernels take contiguous tensors)  ->  per phase the 1x1
+#              stride-1 gradient kernels of csrc/grad.hip, as CellOpTrainFn uses them  ->  BatchNorm backward from the two
+#              lattice gradients (csrc/bn_train.hip: bn_bwd_s2_reduce_kernel, bn_bwd_dx_s2_kernel), dx written once.
+class ReduceTrainFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w1, w2, gamma, beta, slope, bn, packed, wconf):
+        x = x.contiguous()      # (see BNActFn.forward: what is saved is what the kernels ran on)
+        phases, mean, invstd, _, _ = hipops.bn_train_pack_ste_s2(x, gamma, beta, bn.running_mean, bn.running_var,
+                                                                 _momentum(bn), bn.eps)
+        _stats_written(bn)
+        N, _, H, W = x.shape
+        half = w1.shape[0]
+        slopes = slope.detach().reshape(-1)
+        if slopes.numel() == 1:
+            slopes = slopes.expand(2 * half)
+        y = torch.empty((N, 2 * half, H // 2, W // 2), dtype=torch.float32, device=x.device)
+        for k in range(2):      # torch.cat in place, as cellops._Reduce.conv
+            hipops.bconv2d_fused(phases[k].sign, packed[k], prelu=slopes[k * half:(k + 1) * half], out=y,
+                                 out_c_offset=k * half)
+        # (the output is NOT saved: Cell.forward applies drop_path to it in place)
+        ctx.save_for_backward(x, phases[0].sign.P, phases[0].sign.M, phases[0].T, phases[1].sign.P, phases[1].sign.M,
+                              phases[1].T, mean, invstd, w1, w2, gamma, slope)
+        ctx.packed, ctx.wconf = packed, wconf
+        global _saved_bytes
+        _saved_bytes += phases[0].nbytes() + phases[1].nbytes()
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, P0, M0, T0, P1, M1, T1, mean, invstd, w1, w2, gamma, slope = ctx.saved_tensors
+        need_x, need_w1, need_w2, need_gamma, need_beta, need_slope = ctx.needs_input_grad[:6]
+        g = g.contiguous()
+        N, C, H, W = x.shape
+        shape = (N, C, H // 2, W // 2)
+        saved = [hipops.SavedAct(hipops.PackedAct(P, M, shape), T, shape) for P, M, T in ((P0, M0, T0), (P1, M1, T1))]
+        ws, half = (w1, w2), w1.shape[0]
+        z = torch.empty_like(g)                                    # scratch: overwritten by gz, dies in here
+        for k in range(2):
+            hipops.bconv2d_fused(saved[k].sign, ctx.packed[k], out=z, out_c_offset=k * half)
+        gz, gslope = hipops.prelu_shuffle_backward(g, z, slope, 1, inplace=True)
+        # the one extra pass over g: [N, 2, half, Ho, Wo] -> [2, N, half, Ho, Wo], each half contiguous
+        gzk = gz.view(N, 2, half, shape[2], shape[3]).transpose(0, 1).contiguous()
+        need_u = need_x or need_gamma or need_beta
+        gu, gw = [None, None], [None, None]
+        for k, need_w in enumerate((need_w1, need_w2)):
+            center, compute_alpha = ctx.wconf[k]
+            if need_u:
+                gpacked, alpha = hipops.xnor_grad_pack_weight(ws[k], center, compute_alpha)
+                gu[k] = hipops.bconv_grad_input(gzk[k], saved[k], gpacked, alpha, 1, 1)
+            if need_w:
+                gwhat = hipops.bconv_grad_weight(gzk[k], saved[k], 1, 1, reduce=False)
+                if gwhat.shape[0] > 16:         # (see BinaryConv2dTrainFusedFn.backward)
+                    gwhat = gwhat.sum(0)
+                gw[k] = hipops.xnor_weight_backward(ws[k], gwhat, center, compute_alpha)
+        dx = dgamma = dbeta = None
+        if need_u:
+            dx, dgamma, dbeta = hipops.bn_train_backward_s2(gu[0], gu[1], x, mean, invstd, gamma)
+        return (dx if need_x else None, gw[0], gw[1], dgamma if need_gamma else None, dbeta if need_beta else None,
+                gslope.reshape(slope.shape) if need_slope else None, None, None, None)
+
+
+def reduce_train(m: nn.Module, x: torch.Tensor):
+    """``m(x)`` of a ``FactorizedReduce`` in train() mode as ``ReduceTrainFn``, or None — the caller then runs the module's
+    own forward — unless: the switches are on and autograd is recording without autocast; the module is ``bn`` /
+    ``conv_1`` / ``conv_2`` / ``activation`` as ``cellops._Reduce`` recognises it, the BatchNorm under the rule of
+    ``cell_op_train``; both convolutions are binary 1x1 / stride 2 / padding 0 / ``groups == 1`` over the BatchNorm's
+    channels with the recipe BasicInputBinarizer + XNORWeightBinarizer, no post scale and no bias, and the weight rule of
+    ``conv2d_train``; nothing carries a hook (it would not fire); fp32 NCHW on one HIP device with even ``H`` and ``W`` and
+    more than one value per channel; the 1x1 stride-1 gradient kernels cover the half-resolution geometry; and a phase
+    holds an even number of plane words (the second phase's planes are then 16-byte aligned, as the convolution launch
+    requires)."""
+    from . import fastpath
+    if not (CELL_OPS and ENABLED and BINARY_GRADS and FUSED_WEIGHT_HOOK and type(m).__name__ == "FactorizedReduce"
+            and m.training and torch.is_grad_enabled() and not torch.is_autocast_enabled()):
+        return None
+    bn, act = getattr(m, "bn", None), getattr(m, "activation", None)
+    seqs = [getattr(m, n, None) for n in ("conv_1", "conv_2")]
+    if not (type(bn) is nn.BatchNorm2d and bn.training and bn.track_running_stats and bn.running_mean is not None
+            and bn.running_var is not None and type(act) is nn.PReLU
+            and all(isinstance(s, nn.Sequential) and len(s) == 1 for s in seqs)):
+        return None
+    convs = [s[0] for s in seqs]
+    C, half = bn.num_features, getattr(convs[0], "out_channels", None)
+    plans = []
+    for conv in convs:
+        if not (isinstance(conv, nn.Conv2d) and hasattr(conv, "activation_pre_process")):
+            return None
+        plan = fastpath._recognise(conv, conv.out_channels)
+        if plan is None or not plan.ste or plan.scale is not None or conv.bias is not None \
+                or isinstance(conv.padding, str) or conv.padding_mode != "zeros":
+            return None
+        if (conv.in_channels != C or conv.out_channels != half or conv.groups != 1 or tuple(conv.kernel_size) != (1, 1)
+                or tuple(conv.stride) != (2, 2) or tuple(conv.padding) != (0, 0) or tuple(conv.dilation) != (1, 1)):
+            return None
+        w = conv.weight
+        if not (w.dim() == 4 and w.is_contiguous() and w.shape[2] * w.shape[3] <= 1024):    # (conv2d_train's rule)
+            return None
+        plans.append(plan)
+    if act.weight.numel() not in (1, 2 * half):
+        return None
+    hooked = [m, bn, act] + seqs + convs + [h for c in convs for h in (c.activation_pre_process, c.weight_pre_process,
+                                                                        c.activation_post_process)]
+    if not _no_hooks(*hooked):
+        return None
+    tensors = [x, convs[0].weight, convs[1].weight, act.weight, bn.running_mean, bn.running_var] \
+        + [t for t in (bn.weight, bn.bias) if t is not None]
+    if not (x.dim() == 4 and x.shape[1] == C and x.numel() > C and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
+            and all(t.is_cuda and t.device == x.device and t.dtype == torch.float32 for t in tensors)):
+        return None
+    N, _, H, W = x.shape
+    if not hipops.grad_supported((N, C, H // 2, W // 2), (half, C, 1, 1), (1, 1), (0, 0), (1, 1)):
+        return None
+    # the planes of both phases are ONE phase-major allocation (what the pack launch writes) and the convolution launch
+    # takes 16-byte aligned planes: phase 1 starts N * cw64 * H/2 * W/2 words of 8 bytes behind phase 0
+    if (N * ((C + 63) // 64) * (H // 2) * (W // 2)) % 2:
+        return None
+    packed = tuple(fastpath.packed_weight(c, p, sync=False, fresh=True) for c, p in zip(convs, plans))
+    y = ReduceTrainFn.apply(x, convs[0].weight, convs[1].weight, bn.weight, bn.bias, act.weight, bn, packed,
+                            tuple((bool(p.center), bool(p.compute_alpha)) for p in plans))
+    fastpath._bump("reduce_train")
+    return y
+
+
 def make_ddp(model: nn.Module, device: torch.device | None = None, **kw) -> nn.Module:
     """Wrap ``model`` for one-process-per-GPU data-parallel training (RCCL when on GPU, gloo on CPU).
     ``torch.distributed`` must be initialised.  Gradient buckets default to 64 MB: xGMI rings are

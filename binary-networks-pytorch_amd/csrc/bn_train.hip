@@ -726,4 +726,126 @@ int launch_bn_bwd_dx_add(const float* gy, const float* y, const float* x, const 
   return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
 }
 
+// ------------------------------------------------------------------------------------------------- FactorizedReduce
+// BatchNorm backward behind the two 1x1 stride-2 convolutions of FactorizedReduce (bnn/models/layers/bats_ops.py:204-206):
+// the incoming gradient lives on two pixel lattices only — g0[i, j] at (2i, 2j), g1[i, j] at (2i+1, 2j+1), both
+// [N, C, H/2, W/2] — and is zero at every other pixel (bnn_hip_bn_train_backward_s2_f32).  The statistics of the forward
+// are over ALL of x, so `count` stays N * H * W.
+//
+// partial[c][s] = (sum g, sum g * xhat) over the lattice pixels of the images of split s.  x is read at those pixels only
+// (rows 2i and 2i+1: every line of x is still fetched).  Split rule, double accumulation and fixed order of
+// bn_bwd_reduce_kernel.  OP = output pixels per step: 2 (float4 of x, float2 of g) or 1.
+template <int OP>
+__global__ __launch_bounds__(bnt::NT) void bn_bwd_s2_reduce_kernel(const float* __restrict__ g0, const float* __restrict__ g1,
+                                                                   const float* __restrict__ x,
+                                                                   const float* __restrict__ mean,
+                                                                   const float* __restrict__ invstd, int N, int C, int Ho,
+                                                                   int Wo, int per, double* __restrict__ partial) {
+  const int c = blockIdx.x, s = blockIdx.y, S = gridDim.y;
+  const int n0 = s * per, n1 = min(N, n0 + per);
+  const int W = 2 * Wo;
+  const int upr = Wo / OP;                        // units per output row
+  const int upi = Ho * upr;                       // per image
+  const int total = (n1 - n0) * upi;
+  const size_t HWo = (size_t)Ho * Wo;
+  const float mu = mean[c], is = invstd[c];
+  double a = 0.0, b = 0.0;
+  for (int idx = threadIdx.x; idx < total; idx += bnt::NT) {
+    const int dn = idx / upi, r = idx - dn * upi;
+    const int i = r / upr, ju = r - i * upr;
+    const size_t plane = (size_t)(n0 + dn) * C + c;
+    const size_t go = plane * HWo + (size_t)i * Wo + (size_t)ju * OP;
+    const float* xr = x + plane * 4 * HWo + (size_t)(2 * i) * W + (size_t)ju * 2 * OP;
+    if constexpr (OP == 2) {
+      const float2 p0 = *reinterpret_cast<const float2*>(g0 + go), p1 = *reinterpret_cast<const float2*>(g1 + go);
+      const float4 r0 = *reinterpret_cast<const float4*>(xr), r1 = *reinterpret_cast<const float4*>(xr + W);
+      a += (double)p0.x + (double)p0.y + (double)p1.x + (double)p1.y;
+      b += (double)p0.x * ((r0.x - mu) * is) + (double)p0.y * ((r0.z - mu) * is) + (double)p1.x * ((r1.y - mu) * is) +
+           (double)p1.y * ((r1.w - mu) * is);
+    } else {
+      const float p0 = g0[go], p1 = g1[go];
+      a += (double)p0 + (double)p1;
+      b += (double)p0 * ((xr[0] - mu) * is) + (double)p1 * ((xr[W + 1] - mu) * is);
+    }
+  }
+  block_sum2(a, b);
+  if (threadIdx.x == 0) {
+    partial[((size_t)c * S + s) * 2 + 0] = a;
+    partial[((size_t)c * S + s) * 2 + 1] = b;
+  }
+}
+
+// dx = k * (g - mb - (x - mean) * kg) over the full-resolution tensor, every element written exactly once: a thread owns
+// a 2-row block (the mapping of avgpool2_bwd_kernel) — VEC = 4: two output pixels, two float4 rows; VEC = 2: one output
+// pixel, two float2 rows — and places g0 at the even / even, g1 at the odd / odd position of it, 0 at the other two.
+template <int VEC>
+__global__ __launch_bounds__(bnt::NT) void bn_bwd_dx_s2_kernel(const float* __restrict__ g0, const float* __restrict__ g1,
+                                                               const float* __restrict__ x, const float* __restrict__ mean,
+                                                               const float* __restrict__ coef, float* __restrict__ dx,
+                                                               long long units, int C, int Ho, int Wo) {
+  const long long u = (long long)blockIdx.x * bnt::NT + threadIdx.x;
+  if (u >= units) return;
+  constexpr int OP = VEC / 2;
+  const int upr = Wo / OP;
+  const long long row = u / upr;                  // (n * C + c) * Ho + i
+  const int ju = (int)(u - row * upr);
+  const long long plane = row / Ho;               // n * C + c
+  const int i = (int)(row - plane * Ho), c = (int)(plane % C);
+  const float mu = mean[c], k = coef[3 * c], mb = coef[3 * c + 1], kg = coef[3 * c + 2];
+  const size_t go = (size_t)row * Wo + (size_t)ju * OP;
+  const size_t W = (size_t)2 * Wo;
+  const size_t xo = ((size_t)plane * 2 * Ho + (size_t)2 * i) * W + (size_t)ju * VEC;
+  if constexpr (VEC == 4) {
+    const float2 p0 = *reinterpret_cast<const float2*>(g0 + go), p1 = *reinterpret_cast<const float2*>(g1 + go);
+    const float4 r0 = *reinterpret_cast<const float4*>(x + xo), r1 = *reinterpret_cast<const float4*>(x + xo + W);
+    float4 d0, d1;
+    d0.x = k * (p0.x - mb - (r0.x - mu) * kg);
+    d0.y = k * (0.0f - mb - (r0.y - mu) * kg);
+    d0.z = k * (p0.y - mb - (r0.z - mu) * kg);
+    d0.w = k * (0.0f - mb - (r0.w - mu) * kg);
+    d1.x = k * (0.0f - mb - (r1.x - mu) * kg);
+    d1.y = k * (p1.x - mb - (r1.y - mu) * kg);
+    d1.z = k * (0.0f - mb - (r1.z - mu) * kg);
+    d1.w = k * (p1.y - mb - (r1.w - mu) * kg);
+    *reinterpret_cast<float4*>(dx + xo) = d0;
+    *reinterpret_cast<float4*>(dx + xo + W) = d1;
+  } else {
+    const float p0 = g0[go], p1 = g1[go];
+    const float2 r0 = *reinterpret_cast<const float2*>(x + xo), r1 = *reinterpret_cast<const float2*>(x + xo + W);
+    float2 d0, d1;
+    d0.x = k * (p0 - mb - (r0.x - mu) * kg);
+    d0.y = k * (0.0f - mb - (r0.y - mu) * kg);
+    d1.x = k * (0.0f - mb - (r1.x - mu) * kg);
+    d1.y = k * (p1 - mb - (r1.y - mu) * kg);
+    *reinterpret_cast<float2*>(dx + xo) = d0;
+    *reinterpret_cast<float2*>(dx + xo + W) = d1;
+  }
+}
+
+// reduce + finalize (count = N * H * W: the statistics were taken over all of x) + dx.  H and W even, x and dx 8-byte
+// aligned (capi.hip has checked both).  The wide forms need W % 4 == 0, x / dx 16-byte and g0 / g1 8-byte aligned.
+int launch_bn_bwd_s2(const float* g0, const float* g1, const float* x, const float* mean, const float* invstd,
+                     const float* gamma, int N, int C, int H, int W, int splits, double* partial, float* work, float* dx,
+                     float* dgamma, float* dbeta, hipStream_t s) {
+  const int Ho = H / 2, Wo = W / 2;
+  const int per = (N + splits - 1) / splits;
+  auto al = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
+  const bool g2 = W % 4 == 0 && al(g0, 8) && al(g1, 8);
+  const dim3 rgrid((unsigned)C, (unsigned)splits);
+  if (g2 && al(x, 16))
+    hipLaunchKernelGGL(bn_bwd_s2_reduce_kernel<2>, rgrid, dim3(bnt::NT), 0, s, g0, g1, x, mean, invstd, N, C, Ho, Wo, per, partial);
+  else
+    hipLaunchKernelGGL(bn_bwd_s2_reduce_kernel<1>, rgrid, dim3(bnt::NT), 0, s, g0, g1, x, mean, invstd, N, C, Ho, Wo, per, partial);
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, s, partial, splits, C,
+                     (double)N * H * W, gamma, invstd, dgamma, dbeta, work);
+  const bool v4 = g2 && al(x, 16) && al(dx, 16);
+  const long long units = (long long)N * C * Ho * (v4 ? Wo / 2 : Wo);
+  const dim3 grid((unsigned)((units + bnt::NT - 1) / bnt::NT));
+  if (v4)
+    hipLaunchKernelGGL(bn_bwd_dx_s2_kernel<4>, grid, dim3(bnt::NT), 0, s, g0, g1, x, mean, work, dx, units, C, Ho, Wo);
+  else
+    hipLaunchKernelGGL(bn_bwd_dx_s2_kernel<2>, grid, dim3(bnt::NT), 0, s, g0, g1, x, mean, work, dx, units, C, Ho, Wo);
+  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+}
+
 }  // namespace bnn

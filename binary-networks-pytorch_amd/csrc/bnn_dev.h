@@ -182,6 +182,9 @@ int launch_pack_ste(const float* x, int N, int C, int H, int W, uint64_t* P, uin
 // the same planes of fmaf(x, bn_a[c], bn_b[c]) (bn_a == bn_b == null: of x), u never written
 int launch_bn_pack_ste(const float* x, int N, int C, int H, int W, const float* bn_a, const float* bn_b, uint64_t* P,
                        uint64_t* M, uint64_t* T, hipStream_t stream);
+// the same planes of the pixel lattices (2i, 2j) and (2i+1, 2j+1) only: [2][N][cw64][H/2][W/2] each (H, W even)
+int launch_bn_pack_ste_s2(const float* x, int N, int C, int H, int W, const float* bn_a, const float* bn_b, uint64_t* P,
+                          uint64_t* M, uint64_t* T, hipStream_t stream);
 int launch_pack_weight(const float* w, int O, int C, int KH, int KW, int center, int compute_alpha,
                        const bnn_hip_wlayout& L, uint32_t* wbits, uint32_t* wnz, float* alpha,
                        int32_t* zero_flag, hipStream_t stream);
@@ -265,6 +268,10 @@ int launch_bn_finalize(const double* partial, int splits, const float* gamma, co
 int launch_bn_bwd_dx_add(const float* gy, const float* y, const float* x, const float* mean, const float* invstd,
                          const float* gamma, const double* partial, int splits, const float* addend, float* dx,
                          float* dgamma, float* dbeta, int N, int C, int HW, float* work, hipStream_t s);
+// BatchNorm backward of a gradient that lives on those two lattices (g0, g1: [N, C, H/2, W/2]); reduce + finalize + dx
+int launch_bn_bwd_s2(const float* g0, const float* g1, const float* x, const float* mean, const float* invstd,
+                     const float* gamma, int N, int C, int H, int W, int splits, double* partial, float* work, float* dx,
+                     float* dgamma, float* dbeta, hipStream_t s);
 // prelu_bwd.hip: backward of channel_shuffle(PReLU(z), sg); `partial`: O * splits doubles, splits = bn_train_splits(N, O, HW)
 int launch_prelu_shuffle_bwd(const float* gy, const float* z, const float* slope, int slope_count, int N, int O, int HW,
                              int sg, int splits, float* gz, float* dslope, double* partial, hipStream_t s);

@@ -203,6 +203,9 @@ int check_pack(const void* x, size_t x_align, int N, int C, int H, int W, const 
   return BNN_HIP_OK;
 }
 
+// The two pixel lattices (2i, 2j) and (2i+1, 2j+1) of FactorizedReduce cover an image only when H and W are even.
+int check_lattice(int H, int W) { return (H % 2 != 0 || W % 2 != 0) ? BNN_HIP_ERR_INVALID_ARG : BNN_HIP_OK; }
+
 // A channel-slice view (bnn_hip_f32_view) of C channels: pointer, window, and the whole [N, c_total, H, W] tensor within
 // `max_elems`.  *c_off / *c_tot receive the window with c_total == 0 resolved to C.
 int check_view(const bnn_hip_f32_view* v, int N, int C, long long hw, long long max_elems, int* c_off, int* c_tot) {
@@ -375,7 +378,7 @@ int bnn_hip_bn_act_pack_s2_f32(const bnn_hip_f32_view* x, int N, int C, int H, i
   if (!x || (bn_scale == nullptr) != (bn_shift == nullptr)) return BNN_HIP_ERR_INVALID_ARG;
   const int st = check_pack(x->p, 4, N, C, H, W, P, M);
   if (st != BNN_HIP_OK) return st;
-  if (H % 2 != 0 || W % 2 != 0) return BNN_HIP_ERR_INVALID_ARG;
+  if (check_lattice(H, W) != BNN_HIP_OK) return BNN_HIP_ERR_INVALID_ARG;
   int c_off = 0, c_tot = 0;
   const int sv = check_view(x, N, C, mulc(H, W), kSat, &c_off, &c_tot);
   if (sv != BNN_HIP_OK) return sv;
@@ -671,6 +674,18 @@ int bnn_hip_bn_act_pack_ste_f32(const float* x, int N, int C, int H, int W, cons
   g_launches.fetch_add(1, std::memory_order_relaxed);
   BNN_RANGE();
   return bnn::launch_bn_pack_ste(x, N, C, H, W, bn_scale, bn_shift, P, M, T, static_cast<hipStream_t>(stream));
+}
+
+int bnn_hip_bn_act_pack_ste_s2_f32(const float* x, int N, int C, int H, int W, const float* bn_scale, const float* bn_shift,
+                                   uint64_t* P, uint64_t* M, uint64_t* T, void* stream) {
+  if (!T || (bn_scale == nullptr) != (bn_shift == nullptr)) return BNN_HIP_ERR_INVALID_ARG;
+  const int st = check_pack(x, 4, N, C, H, W, P, M);
+  if (st != BNN_HIP_OK) return st;
+  if (check_lattice(H, W) != BNN_HIP_OK) return BNN_HIP_ERR_INVALID_ARG;
+  if (!aligned(T, 8) || !aligned(bn_scale, 4) || !aligned(bn_shift, 4)) return BNN_HIP_ERR_INVALID_ARG;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_bn_pack_ste_s2(x, N, C, H, W, bn_scale, bn_shift, P, M, T, static_cast<hipStream_t>(stream));
 }
 
 int bnn_hip_bconv_grad_weight_splits(int N, int O, int C, int ksize) {
@@ -1118,6 +1133,33 @@ int bnn_hip_bn_train_pack_ste_f32(const float* x, int N, int C, int H, int W, co
   return bnn::launch_bn_pack_ste(x, N, C, H, W, scale, shift, P, M, T, s);
 }
 
+int bnn_hip_bn_train_pack_ste_s2_f32(const float* x, int N, int C, int H, int W, const float* gamma, const float* beta,
+                                     float eps, float momentum, float* running_mean, float* running_var, uint64_t* P,
+                                     uint64_t* M, uint64_t* T, float* save_mean, float* save_invstd, float* scale,
+                                     float* shift, void* workspace, void* stream) {
+  if (!T || !save_mean || !save_invstd || !scale || !shift || !workspace) return BNN_HIP_ERR_INVALID_ARG;
+  const int stp = check_pack(x, 4, N, C, H, W, P, M);
+  if (stp != BNN_HIP_OK) return stp;
+  if (check_lattice(H, W) != BNN_HIP_OK) return BNN_HIP_ERR_INVALID_ARG;
+  const int HW = checked_hw(H, W);
+  const int st = check_bn(N, C, HW);
+  if (st != BNN_HIP_OK) return st;
+  if ((running_mean == nullptr) != (running_var == nullptr) || !(eps >= 0.0f)) return BNN_HIP_ERR_INVALID_ARG;
+  if (!aligned(T, 8) || !aligned(scale, 4) || !aligned(shift, 4) || !aligned(save_mean, 4) || !aligned(save_invstd, 4) ||
+      !aligned(workspace, 8))
+    return BNN_HIP_ERR_INVALID_ARG;
+  const BnWorkspace ws = bn_workspace(N, C, HW, workspace);
+  g_launches.fetch_add(3, std::memory_order_relaxed);
+  BNN_RANGE();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int st2 = bnn::launch_bn_stats(x, N, C, HW, ws.splits, ws.partial, s);
+  if (st2 != BNN_HIP_OK) return st2;
+  st2 = bnn::launch_bn_finalize(ws.partial, ws.splits, gamma, beta, N, C, HW, eps, momentum, running_mean, running_var,
+                                save_mean, save_invstd, scale, shift, s);
+  if (st2 != BNN_HIP_OK) return st2;
+  return bnn::launch_bn_pack_ste_s2(x, N, C, H, W, scale, shift, P, M, T, s);
+}
+
 int bnn_hip_bn_act_f32(const float* x, int N, int C, int HW, const float* scale, const float* shift, const float* residual,
                        int relu, float* y, void* stream) {
   if (!x || !y || !scale || !shift) return BNN_HIP_ERR_INVALID_ARG;
@@ -1169,6 +1211,24 @@ int bnn_hip_bn_train_backward_add_f32(const float* gy, const float* y, const flo
   if (st2 != BNN_HIP_OK) return st2;
   return bnn::launch_bn_bwd_dx_add(gy, y, x, save_mean, save_invstd, gamma, ws.partial, ws.splits, addend, dx, dgamma, dbeta,
                                    N, C, HW, ws.work, static_cast<hipStream_t>(stream));
+}
+
+int bnn_hip_bn_train_backward_s2_f32(const float* g0, const float* g1, const float* x, const float* save_mean,
+                                     const float* save_invstd, const float* gamma, int N, int C, int H, int W, float* dx,
+                                     float* dgamma, float* dbeta, void* workspace, void* stream) {
+  if (!g0 || !g1 || !x || !save_mean || !save_invstd || !dx || !workspace || H <= 0 || W <= 0) return BNN_HIP_ERR_INVALID_ARG;
+  if (check_lattice(H, W) != BNN_HIP_OK) return BNN_HIP_ERR_INVALID_ARG;
+  const int HW = checked_hw(H, W);
+  const int st = check_bn(N, C, HW);
+  if (st != BNN_HIP_OK) return st;
+  // (x and dx are read and written as rows of float2 at least: W is even, so 8-byte bases keep every row aligned)
+  if (!aligned(g0, 4) || !aligned(g1, 4) || !aligned(x, 8) || !aligned(dx, 8) || !aligned(workspace, 8))
+    return BNN_HIP_ERR_INVALID_ARG;
+  const BnWorkspace ws = bn_workspace(N, C, HW, workspace);
+  g_launches.fetch_add(3, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_bn_bwd_s2(g0, g1, x, save_mean, save_invstd, gamma, N, C, H, W, ws.splits, ws.partial, ws.work, dx,
+                               dgamma, dbeta, static_cast<hipStream_t>(stream));
 }
 
 // ---- backward of channel_shuffle(PReLU(z), shuffle_groups): csrc/prelu_bwd.hip

@@ -127,4 +127,62 @@ int launch_bn_pack_ste(const float* x, int N, int C, int H, int W, const float* 
   return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
 }
 
+// The three planes of the two pixel lattices FactorizedReduce reads (bnn/models/layers/bats_ops.py:204-206): phase 0 =
+// u[2i, 2j], phase 1 = u[2i+1, 2j+1], u = fmaf(x, a[c], b[c]) as above — the training forward of that module
+// (bnn_hip_bn_act_pack_ste_s2_f32 / bnn_hip_bn_train_pack_ste_s2_f32).  Thread mapping of pack_act_s2_kernel
+// (pack_act.hip): one thread = one output pixel of one 64-channel word, two loads per channel (rows 2i and 2i+1 of the
+// plane: every line of x is fetched once), three words per phase out.  Each plane is [2][N][cw64][H/2][W/2]; the ragged
+// last word as above.  Plain loads: the backward reads x again.
+__global__ __launch_bounds__(256) void bn_pack_ste_s2_kernel(const float* __restrict__ x, int C, int W, int Ho, int Wo,
+                                                             long long npix, int cw64, const float* __restrict__ bn_a,
+                                                             const float* __restrict__ bn_b, uint64_t* __restrict__ P,
+                                                             uint64_t* __restrict__ M, uint64_t* __restrict__ T,
+                                                             size_t set_stride) {
+  const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (q >= npix) return;
+  const int g = blockIdx.y;
+  const int HWo = Ho * Wo;
+  const size_t HW = (size_t)4 * HWo;
+  const int n = (int)(q / HWo);
+  const int r = (int)(q - (long long)n * HWo);
+  const int i = r / Wo, j = r - i * Wo;
+  const float* xb = x + ((size_t)n * C) * HW + (size_t)(2 * i) * W + 2 * j;
+  uint32_t pw[2][2] = {{0u, 0u}, {0u, 0u}}, mw[2][2] = {{0u, 0u}, {0u, 0u}}, tw[2][2] = {{0u, 0u}, {0u, 0u}};  // [phase][half]
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int c0 = g * 64 + h * 32;
+    for (int b = 0; b < 32 && c0 + b < C; ++b) {
+      const float* xc = xb + (size_t)(c0 + b) * HW;
+      const float v[2] = {xc[0], xc[W + 1]};
+      const float ca = bn_a ? bn_a[c0 + b] : 1.0f, cb = bn_a ? bn_b[c0 + b] : 0.0f;
+#pragma unroll
+      for (int ph = 0; ph < 2; ++ph) {
+        const float u = bn_a ? fmaf(v[ph], ca, cb) : v[ph];
+        pw[ph][h] |= (is_pos(u) ? 1u : 0u) << b;
+        mw[ph][h] |= (is_neg(u) ? 1u : 0u) << b;
+        tw[ph][h] |= (fabsf(u) < 1.0f ? 1u : 0u) << b;
+      }
+    }
+  }
+  const size_t o = ((size_t)n * cw64 + g) * HWo + r;
+#pragma unroll
+  for (int ph = 0; ph < 2; ++ph) {
+    P[ph * set_stride + o] = (uint64_t)pw[ph][0] | ((uint64_t)pw[ph][1] << 32);
+    M[ph * set_stride + o] = (uint64_t)mw[ph][0] | ((uint64_t)mw[ph][1] << 32);
+    T[ph * set_stride + o] = (uint64_t)tw[ph][0] | ((uint64_t)tw[ph][1] << 32);
+  }
+}
+
+// H and W even (capi.hip has checked that).
+int launch_bn_pack_ste_s2(const float* x, int N, int C, int H, int W, const float* bn_a, const float* bn_b, uint64_t* P,
+                          uint64_t* M, uint64_t* T, hipStream_t stream) {
+  const int Ho = H / 2, Wo = W / 2;
+  const long long npix = (long long)N * Ho * Wo;
+  const int cw64 = (C + 63) / 64;
+  const dim3 grid((unsigned)((npix + 255) / 256), (unsigned)cw64);
+  hipLaunchKernelGGL(bn_pack_ste_s2_kernel, grid, dim3(256), 0, stream, x, C, W, Ho, Wo, npix, cw64, bn_a, bn_b, P, M, T,
+                     (size_t)npix * cw64);
+  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+}
+
 }  // namespace bnn

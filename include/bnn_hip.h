@@ -61,7 +61,10 @@
 extern "C" {
 #endif
 
-/* Additive entry points of ABI 15 for the training step of a BATS cell operation (no struct or signature changed):
+/* Additive entry points of ABI 15 for the training step of FactorizedReduce (no struct or signature changed):
+ * + bnn_hip_bn_act_pack_ste_s2_f32, bnn_hip_bn_train_pack_ste_s2_f32 (the three bit planes of the two pixel lattices its
+ * convolutions read); + bnn_hip_bn_train_backward_s2_f32 (the BatchNorm backward of a gradient that lives on those lattices).
+ * Additive entry points of ABI 15 for the training step of a BATS cell operation (no struct or signature changed):
  * + bnn_hip_bn_act_pack_ste_f32, bnn_hip_bn_train_pack_ste_f32 (BatchNorm + sign + straight-through mask as three bit
  * planes, the normalised tensor never written); + bnn_hip_prelu_shuffle_backward_f32 / _workspace_bytes (backward of
  * channel_shuffle(PReLU(.))); + bnn_hip_bn_train_backward_add_f32 (the BatchNorm backward with the skip's gradient added).
@@ -423,6 +426,13 @@ int bnn_hip_pack_act_ste_f32(const float* x, int N, int C, int H, int W, uint64_
  * x, u never written.  bn_scale / bn_shift: fp32 [C], both or neither; both NULL: the bits of bnn_hip_pack_act_ste_f32.  */
 int bnn_hip_bn_act_pack_ste_f32(const float* x, int N, int C, int H, int W, const float* bn_scale, const float* bn_shift,
                                 uint64_t* P, uint64_t* M, uint64_t* T, void* stream);
+/* The same three planes on the two pixel lattices FactorizedReduce reads (bnn/models/layers/bats_ops.py:204-206): phase 0
+ * = u[2i, 2j], phase 1 = u[2i+1, 2j+1].  P, M, T: uint64 [2][N][ceil(C/64)][H/2][W/2] each (phase-major), 8-byte
+ * aligned — per phase the bits of bnn_hip_bn_act_pack_ste_f32 on a contiguous copy of x[:, :, ::2, ::2] resp.
+ * x[:, :, 1::2, 1::2]; P and M are the planes of bnn_hip_bn_act_pack_s2_f32 (relu = 0).  Pixels off the lattices are not
+ * read.  H and W must be even (INVALID_ARG otherwise).  One launch.                                                  */
+int bnn_hip_bn_act_pack_ste_s2_f32(const float* x, int N, int C, int H, int W, const float* bn_scale, const float* bn_shift,
+                                   uint64_t* P, uint64_t* M, uint64_t* T, void* stream);
 int bnn_hip_bconv_grad_input_packed_f32(const float* g, const float* alpha, const void* packed_w, const uint64_t* T,
                                         float* gx, int N, int O, int C, int H, int W, int ksize, int stride,
                                         void* stream);
@@ -815,6 +825,26 @@ int bnn_hip_bn_train_pack_ste_f32(const float* x, int N, int C, int H, int W, co
                                   float eps, float momentum, float* running_mean, float* running_var, uint64_t* P,
                                   uint64_t* M, uint64_t* T, float* save_mean, float* save_invstd, float* scale, float* shift,
                                   void* workspace, void* stream);
+
+/* Training-mode BatchNorm2d in front of the two 1x1 stride-2 convolutions of FactorizedReduce (bnn/models/layers/
+ * bats_ops.py:190-209).  forward: the statistics and running-statistics update of bnn_hip_bn_train_pack_ste_f32 (same
+ * launchers: save_mean, save_invstd and the running buffers get the same bits — the statistics are over ALL of x), then the
+ * planes of bnn_hip_bn_act_pack_ste_s2_f32 with the scale / shift it returns.  Workspace: bnn_hip_bn_train_workspace_bytes(
+ * N, C, H * W).  Three launches.
+ * backward: the gradient with respect to u arrives on the lattices only — g0[n, c, i, j] at pixel (2i, 2j), g1 at
+ * (2i+1, 2j+1), fp32 [N, C, H/2, W/2] each — and is zero elsewhere: dbeta = sum g, dgamma = sum g * xhat over the
+ * lattice pixels, dx = gamma * invstd * (g - dbeta / m - xhat * dgamma / m) at EVERY pixel of [N, C, H, W], m = N * H * W.
+ * x is read for the sums at the lattice pixels only; dx is written exactly once per element (no clearing pass).  Sums in
+ * double through per-(channel, image split) partials added in a fixed order: no atomics, the same bits on every run.
+ * x, dx: 8-byte aligned (rows are moved as float2, or float4 where W % 4 == 0 and they are 16-byte aligned); gamma,
+ * dgamma, dbeta may be NULL.  H and W even.  Same workspace.  Three launches, no synchronisation.                      */
+int bnn_hip_bn_train_pack_ste_s2_f32(const float* x, int N, int C, int H, int W, const float* gamma, const float* beta,
+                                     float eps, float momentum, float* running_mean, float* running_var, uint64_t* P,
+                                     uint64_t* M, uint64_t* T, float* save_mean, float* save_invstd, float* scale,
+                                     float* shift, void* workspace, void* stream);
+int bnn_hip_bn_train_backward_s2_f32(const float* g0, const float* g1, const float* x, const float* save_mean,
+                                     const float* save_invstd, const float* gamma, int N, int C, int H, int W, float* dx,
+                                     float* dgamma, float* dbeta, void* workspace, void* stream);
 
 /* Backward of  y = channel_shuffle(PReLU(z), shuffle_groups)  (the tail of a BATS cell operation; the forward is the
  * epilogue of bnn_hip_bconv2d_grouped_fused / bnn_hip_bconv2d_fused).  gy: fp32 [N, O, HW] in the OUTPUT's (shuffled)

@@ -329,6 +329,12 @@ int launch_bn_pack_ste(const float* x, int N, int C, int H, int W, const float* 
   ++g_reached; check_planes(x, N, C, H, W, P, M, 4); REQUIRE(T && al(T, 8) && (a == nullptr) == (b == nullptr) && al(a, 4) && al(b, 4));
   return BNN_HIP_OK;
 }
+int launch_bn_pack_ste_s2(const float* x, int N, int C, int H, int W, const float* a, const float* b, uint64_t* P, uint64_t* M,
+                          uint64_t* T, hipStream_t) {
+  ++g_reached; check_planes(x, N, C, H, W, P, M, 4);
+  REQUIRE(H % 2 == 0 && W % 2 == 0 && T && al(T, 8) && (a == nullptr) == (b == nullptr) && al(a, 4) && al(b, 4));
+  return BNN_HIP_OK;
+}
 int grad_wgrad_splits(int N, int O, int C, int ks) { REQUIRE(N > 0 && O > 0 && C > 0 && (ks == 1 || ks == 3)); return 1; }
 int launch_wgrad(const float* g, const void* x, const void* x2, int planes, float* part, int, int N, int O, int C, int H,
                  int W, int ks, int stride, hipStream_t) {
@@ -400,6 +406,14 @@ int launch_bn_bwd_dx_add(const float* gy, const float* y, const float* x, const 
                          float* work, hipStream_t) {
   ++g_reached; check_bn_args(N, C, HW);
   REQUIRE(gy && x && m && is && partial && addend && dx && work && S >= 1 && al(addend, 4) && al(dx, 4) && al(y, 4));
+  return BNN_HIP_OK;
+}
+// csrc/bn_train.hip, FactorizedReduce: rows of x and dx move as float2 at least, so even H / W and 8-byte bases
+int launch_bn_bwd_s2(const float* g0, const float* g1, const float* x, const float* m, const float* is, const float*, int N,
+                     int C, int H, int W, int S, double* partial, float* work, float* dx, float*, float*, hipStream_t) {
+  ++g_reached; REQUIRE(H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && (long long)H * W <= 0x7fffffffLL); check_bn_args(N, C, H * W);
+  REQUIRE(g0 && g1 && x && m && is && partial && work && dx && S >= 1 && S <= N && (long long)N * H * W <= (1LL << 31) - 1);
+  REQUIRE(al(g0, 4) && al(g1, 4) && al(x, 8) && al(dx, 8) && al(partial, 8));
   return BNN_HIP_OK;
 }
 int launch_prelu_shuffle_bwd(const float* gy, const float* z, const float* slope, int count, int N, int O, int HW, int sg,
@@ -589,7 +603,7 @@ int main(int argc, char** argv) {
   for (long it = 0; it < iters; ++it) {
     ++g_calls;
     int st = 0;
-    switch (rnd() % 60) {
+    switch (rnd() % 64) {
       case 0: { bnn_hip_conv_desc d = pick_desc();
         st = bnn_hip_bconv2d(rnd() % 16 ? &d : nullptr, pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<uint32_t>(),
                              pick_ptr<uint32_t>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), stream);
@@ -857,6 +871,21 @@ int main(int argc, char** argv) {
                                                 pick_ptr<float>(), rnd() % 3 ? (rnd() % 2 ? 1 : O) : pick_int(), N, O, HW, sg, gz,
                                                 pick_ptr<float>(), pick_ptr<double>(),
                                                 rnd() % 4 ? need : (size_t)(rnd() % 4096), stream);
+        break; }
+      case 60: { const int H = rnd() % 4 ? 2 * (int)(1 + rnd() % 16) : pick_int(), W = rnd() % 4 ? 2 * (int)(1 + rnd() % 16) : pick_int();
+        st = bnn_hip_bn_act_pack_ste_s2_f32(pick_ptr<float>(), pick_int(), pick_int(), H, W, pick_ptr<float>(), pick_ptr<float>(),
+                                            pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), stream);
+        break; }
+      case 61: { const int H = rnd() % 4 ? 2 * (int)(1 + rnd() % 16) : pick_int(), W = rnd() % 4 ? 2 * (int)(1 + rnd() % 16) : pick_int();
+        st = bnn_hip_bn_train_pack_ste_s2_f32(pick_ptr<float>(), pick_int(), pick_int(), H, W, pick_ptr<float>(), pick_ptr<float>(),
+                                              (float)(pick_int() % 3) * 1e-5f, 0.1f, pick_ptr<float>(), pick_ptr<float>(),
+                                              pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<float>(),
+                                              pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<double>(), stream);
+        break; }
+      case 62: { const int H = rnd() % 4 ? 2 * (int)(1 + rnd() % 16) : pick_int(), W = rnd() % 4 ? 2 * (int)(1 + rnd() % 16) : pick_int();
+        st = bnn_hip_bn_train_backward_s2_f32(pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(),
+                                              pick_ptr<float>(), pick_ptr<float>(), pick_int(), pick_int(), H, W, pick_ptr<float>(),
+                                              pick_ptr<float>(), pick_ptr<float>(), pick_ptr<double>(), stream);
         break; }
       default: { bnn_hip_conv_desc d = pick_desc();
         (void)bnn_hip_shortcut_fold_supported(rnd() % 16 ? &d : nullptr, pick_int());
