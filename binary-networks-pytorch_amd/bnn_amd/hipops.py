@@ -1010,27 +1010,18 @@ def bconv2d_direct(x: torch.Tensor, w: PackedWeight, bias: Optional[torch.Tensor
     return out
 
 
-def bconv2d_fused(a: PackedAct, w: PackedWeight, *, bias=None, post_scale=None, bn_scale=None,
-                  bn_shift=None, residual=None, prelu=None, relu=False, out_f32=True,
-                  out_packed=False, stride=1, padding=0, dilation=1, force_generic=False,
-                  weights: Optional[str] = None, residual_after_act: bool = False,
-                  pack_before_residual: bool = False, pack_scale=None, pack_shift=None,
-                  pack_relu: bool = False, out: Optional[torch.Tensor] = None, out_c_offset: int = 0,
-                  throughput: bool = False, sign_thresholds: Optional[torch.Tensor] = None,
-                  shortcut: Optional[tuple] = None):
-    """Binary convolution + fused epilogue (see ``bnn_hip_epilogue``): returns
-    ``(y_fp32 | None, PackedAct(sign(p)) | None)``.
-
-    ``shortcut = (PackedAct, PackedWeight, bn_scale, bn_shift)``: the down-sampling block's shortcut branch folded into
-    this launch (``bnn_hip_epilogue.sc_*``): the residual is ``BN(conv1x1(packed))`` computed in the kernel instead of
-    an fp32 tensor; see ``shortcut_fold_supported``.
-
-    ``out``: write the fp32 result into channels ``[out_c_offset, out_c_offset + O)`` of this
-    preallocated ``[N, C_total, Ho, Wo]`` tensor (``torch.cat`` in place); ``residual`` then has
-    ``C_total`` channels too.  The remaining keyword arguments are the pre-activation switches of
-    ``BNN_HIP_EPI_*`` (include/bnn_hip.h); ``throughput``: ``BNN_HIP_FLAG_THROUGHPUT`` (several batches in flight)."""
-    _ungrouped(w, "bconv2d_fused")
-    lib = native.require()
+def _fused_launches(a: PackedAct, w: PackedWeight, what: str, *, bias=None, post_scale=None, bn_scale=None,
+                    bn_shift=None, residual=None, prelu=None, relu=False, out_f32=True,
+                    out_packed=False, stride=1, padding=0, dilation=1, force_generic=False,
+                    weights: Optional[str] = None, residual_after_act: bool = False,
+                    pack_before_residual: bool = False, pack_scale=None, pack_shift=None,
+                    pack_relu: bool = False, out: Optional[torch.Tensor] = None, out_c_offset: int = 0,
+                    throughput: bool = False, sign_thresholds: Optional[torch.Tensor] = None,
+                    shortcut: Optional[tuple] = None):
+    """Everything ``bconv2d_fused`` does short of launching (shared with ``bconv2d_route``): checks the arguments,
+    allocates the outputs and returns ``(y, pk, nonneg, launches)`` where ``launches`` yields one
+    ``(descriptor, epilogue, n0, n1)`` per launch of the batch."""
+    _ungrouped(w, what)
     d = _desc(a.shape, w.shape, stride, padding, dilation, _flags(w, force_generic, weights, a, throughput))
     ho, wo = conv_out_hw(d.H, d.W, d.KH, d.KW, stride, padding, dilation)
     dev = a.P.device
@@ -1075,8 +1066,10 @@ def bconv2d_fused(a: PackedAct, w: PackedWeight, *, bias=None, post_scale=None, 
         y = out if out is not None else (
             torch.empty((d.N, d.O, ho, wo), dtype=torch.float32, device=dev) if out_f32 else None)
         pk = empty_packed(d.N, d.O, ho, wo, dev) if out_packed else None
-        # one launch addresses < 2^31 elements: split the batch when a tensor is larger (like bconv2d)
-        step = fused_launch_images(d.N, d.C, d.H, d.W, d.O, (d.KH, d.KW), stride, padding, dilation, c_total)
+    # one launch addresses < 2^31 elements: split the batch when a tensor is larger (like bconv2d)
+    step = fused_launch_images(d.N, d.C, d.H, d.W, d.O, (d.KH, d.KW), stride, padding, dilation, c_total)
+
+    def launches():
         for n0, n1, dd in _desc_slices(d, step):
             e = native.Epilogue(w.alpha.data_ptr(), _ptr(bias), _ptr(post_scale), _ptr(bn_scale),
                                 _ptr(bn_shift), None if residual is None else residual[n0:n1].data_ptr(),
@@ -1088,15 +1081,71 @@ def bconv2d_fused(a: PackedAct, w: PackedWeight, *, bias=None, post_scale=None, 
                                 _ptr(sign_thresholds),
                                 *((sa.P[n0:n1].data_ptr(), sw.wbits.data_ptr(), sw.alpha.data_ptr(), sbn_a.data_ptr(),
                                    sbn_b.data_ptr(), sa.shape[1], sc_in_hw) if shortcut is not None else ()))
+            yield dd, e, n0, n1
+
+    # mirrors the kernel's rule for leaving the M plane at zero
+    late = residual is not None and residual_after_act
+    nonneg = bool(pack_relu) or (bool(relu) and prelu is None and pack_scale is None
+                                 and (not late or pack_before_residual))
+    return y, pk, nonneg, launches()
+
+
+def bconv2d_fused(a: PackedAct, w: PackedWeight, **kw):
+    """Binary convolution + fused epilogue (see ``bnn_hip_epilogue``): returns
+    ``(y_fp32 | None, PackedAct(sign(p)) | None)``.
+
+    Keyword arguments (all optional): ``bias, post_scale, bn_scale, bn_shift, residual, prelu, relu=False, out_f32=True,
+    out_packed=False, stride=1, padding=0, dilation=1, force_generic=False, weights=None, residual_after_act=False,
+    pack_before_residual=False, pack_scale, pack_shift, pack_relu=False, out, out_c_offset=0, throughput=False,
+    sign_thresholds, shortcut``.
+
+    ``shortcut = (PackedAct, PackedWeight, bn_scale, bn_shift)``: the down-sampling block's shortcut branch folded into
+    this launch (``bnn_hip_epilogue.sc_*``): the residual is ``BN(conv1x1(packed))`` computed in the kernel instead of
+    an fp32 tensor; see ``shortcut_fold_supported``.
+
+    ``out``: write the fp32 result into channels ``[out_c_offset, out_c_offset + O)`` of this
+    preallocated ``[N, C_total, Ho, Wo]`` tensor (``torch.cat`` in place); ``residual`` then has
+    ``C_total`` channels too.  The remaining keyword arguments are the pre-activation switches of
+    ``BNN_HIP_EPI_*`` (include/bnn_hip.h); ``throughput``: ``BNN_HIP_FLAG_THROUGHPUT`` (several batches in flight)."""
+    lib = native.require()
+    y, pk, nonneg, launches = _fused_launches(a, w, "bconv2d_fused", **kw)
+    dev = a.P.device
+    with torch.cuda.device(dev):
+        for dd, e, n0, n1 in launches:
             native.check(lib.bnn_hip_bconv2d_fused(ctypes.byref(dd), a.P[n0:n1].data_ptr(), a.M[n0:n1].data_ptr(),
                                                    w.wbits.data_ptr(), w.wnz.data_ptr(),
                                                    ctypes.byref(e), _stream(dev)),
                          "bnn_hip_bconv2d_fused")
-    if pk is not None:  # mirrors the kernel's rule for leaving the M plane at zero
-        late = residual is not None and residual_after_act
-        pk.nonneg = bool(pack_relu) or (bool(relu) and prelu is None and pack_scale is None
-                                        and (not late or pack_before_residual))
+    if pk is not None:
+        pk.nonneg = nonneg
     return y, pk
+
+
+def bconv2d_route(a: PackedAct, w: PackedWeight, *, fused: bool = True, raw_dot: bool = False, **kw) -> dict:
+    """Which kernel ``bconv2d_fused(a, w, **kw)`` runs (``bnn_hip_bconv2d_route``: the launch ladder itself answers,
+    nothing is launched) as a dict of the fields of ``bnn_hip_conv_route``; of the first launch when the batch is split.
+    ``fused=False``: of ``bconv2d(a, w, **kw)`` instead (``bias, post_scale, stride, padding, dilation, force_generic,
+    raw_dot, weights``)."""
+    lib = native.require()
+    r = native.ConvRoute()
+    if fused:
+        if raw_dot:
+            raise ValueError("raw_dot belongs to bconv2d: fused=False")
+        _, _, _, launches = _fused_launches(a, w, "bconv2d_route", **kw)
+        dd, e, _, _ = next(launches)
+        native.check(lib.bnn_hip_bconv2d_route(ctypes.byref(dd), ctypes.byref(e), ctypes.byref(r)), "bnn_hip_bconv2d_route")
+        return r.as_dict()
+    _ungrouped(w, "bconv2d_route")
+    kw.pop("bias", None), kw.pop("post_scale", None)      # (the drop-in kernel takes them or not: one route)
+    d = _desc(a.shape, w.shape, kw.pop("stride", 1), kw.pop("padding", 0), kw.pop("dilation", 1),
+              _flags(w, kw.pop("force_generic", False), kw.pop("weights", None), a))
+    if kw:
+        raise TypeError(f"bconv2d_route(fused=False): unexpected arguments {sorted(kw)}")
+    if raw_dot:
+        native.check(lib.bnn_hip_bconv2d_dot_route(ctypes.byref(d), ctypes.byref(r)), "bnn_hip_bconv2d_dot_route")
+    else:
+        native.check(lib.bnn_hip_bconv2d_route(ctypes.byref(d), None, ctypes.byref(r)), "bnn_hip_bconv2d_route")
+    return r.as_dict()
 
 
 @dataclass

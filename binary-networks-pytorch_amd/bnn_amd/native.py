@@ -24,7 +24,7 @@ FLAG_THROUGHPUT = 64
 HBLOCK_CHANNEL_LANES = 128
 STEM_EXACT_FP32 = 1
 STEM_FP16 = 4
-ABI_VERSION = 15
+ABI_VERSION = 16
 STEM_S2_TILE = (4, 16)                  # BNN_HIP_STEM_S2_TILE_H / _W: output pixels per workgroup of the ImageNet stem kernels
 STEM_S2X2_MAX_GROUP_CHANNELS = 32       # BNN_HIP_STEM_S2X2_MAX_GROUP_CHANNELS
 GCONV3X3S2_MAX_GROUP_CHANNELS = 40      # BNN_HIP_GCONV3X3S2_MAX_GROUP_CHANNELS
@@ -98,6 +98,25 @@ class Epilogue(ctypes.Structure):
                 ("sc_C", ctypes.c_int32), ("sc_in_hw", ctypes.c_int32)]
 
 
+class ConvRoute(ctypes.Structure):
+    """``bnn_hip_conv_route``: the kernel the launch ladder of ``csrc/bconv.hip`` picks for a convolution."""
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "tiled", "kh", "kw", "cwc", "nchunk", "profile", "nonneg", "weight_zeros", "multi", "pieces", "blocks_per_wave",
+        "shortcut_fold", "site", "reserved")] + [("waves", ctypes.c_int64)]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
+# bnn_hip_conv_route.profile (BNN_HIP_ROUTE_EP_*) and .site (BNN_HIP_SITE_*), by name
+ROUTE_PROFILES = {"PLAIN": 0, "RUNTIME": 1, "MID": 2, "OUT": 3, "DS": 4, "LAST": 5, "HB": 6, "HB3": 7, "MIDT": 8, "OUTP": 9}
+ROUTE_SITE_NAMES = ("SINGLE_OBW", "SINGLE_SPLIT", "SINGLE_FOLD", "SINGLE", "MULTI4_SPLIT4", "MULTI4_SPLIT2_FOLD",
+                    "MULTI4_SPLIT2", "MULTI4_FOLD", "MULTI4", "CHUNKS_FOLD", "CHUNKS", "WZ_SINGLE", "WZ_CHUNKS",
+                    "GENERIC_WZ", "GENERIC")
+ROUTE_SITES = len(ROUTE_SITE_NAMES)     # BNN_HIP_ROUTE_SITES
+SITE = {n: i for i, n in enumerate(ROUTE_SITE_NAMES)}
+
+
 class F32View(ctypes.Structure):
     """``bnn_hip_f32_view``: channels ``[c_offset, c_offset + C)`` of a contiguous fp32 ``[N, c_total, H, W]`` tensor."""
     _fields_ = [("p", ctypes.c_void_p), ("c_offset", ctypes.c_int32), ("c_total", ctypes.c_int32)]
@@ -169,6 +188,8 @@ _PROTOTYPES = {
     "bnn_hip_bconv2d_grouped_node": (_i, [_conv_p, _i] + [_vp] * 8 + [_i, _view_p, _view_p, _vp, _i, _i, _vp]),
     "bnn_hip_bconv2d_fused": (_i, [_conv_p] + [_vp] * 4 + [ctypes.POINTER(Epilogue), _vp]),
     "bnn_hip_shortcut_fold_supported": (_i, [_conv_p, _i]),
+    "bnn_hip_bconv2d_route": (_i, [_conv_p, ctypes.POINTER(Epilogue), ctypes.POINTER(ConvRoute)]),
+    "bnn_hip_bconv2d_dot_route": (_i, [_conv_p, ctypes.POINTER(ConvRoute)]),
     "bnn_hip_bconv2d_dot": (_i, [_conv_p] + [_vp] * 6),
     "bnn_hip_blinear": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "bnn_hip_conv_workspace_bytes": (_sz, [_conv_p]),

@@ -360,11 +360,64 @@ __global__ __launch_bounds__(64) void bconv_generic_kernel(
 #define BNN_NN_MULTI_MINW 1
 #endif
 
+// ---- one ladder for the launch and for the route query (bnn_hip_bconv2d_route) -------------------------------------
+// Every launch statement below goes through launch_site(), which first writes down WHAT it is about to launch — from
+// the template arguments of the very kernel it names — and then launches it unless the call is a dry run.  The query
+// therefore cannot drift from the launch: there is no second copy of a threshold or of a profile mask to keep in step.
+static_assert(BNN_HIP_ROUTE_EP_PLAIN == EP_PLAIN && BNN_HIP_ROUTE_EP_RUNTIME == EP_RUNTIME &&
+              BNN_HIP_ROUTE_EP_MID == EP_MID && BNN_HIP_ROUTE_EP_OUT == EP_OUT && BNN_HIP_ROUTE_EP_DS == EP_DS &&
+              BNN_HIP_ROUTE_EP_LAST == EP_LAST && BNN_HIP_ROUTE_EP_HB == EP_HB && BNN_HIP_ROUTE_EP_HB3 == EP_HB3 &&
+              BNN_HIP_ROUTE_EP_MIDT == EP_MIDT && BNN_HIP_ROUTE_EP_OUTP == EP_OUTP,
+              "include/bnn_hip.h mirrors the epilogue profiles of bconv_core.h");
+
+struct RouteCtx {
+  bnn_hip_conv_route* out;  // null: nobody asked
+  bool dry;                 // true: describe only
+};
+
+// One instantiation of bconv_sgpr_kernel: its description and its launch, from ONE template argument list.
+template <int KH, int KW, int CWC, int EP, int MINW, int PASSES, bool MULTI, bool GSPLIT = false, bool NN = false,
+          bool WZ = false, int OBW = 1, bool DS = false>
+struct SgprKernel {
+  static void describe(const ConvP& p, bnn_hip_conv_route* r) {
+    r->tiled = 1; r->kh = KH; r->kw = KW; r->cwc = CWC; r->nchunk = p.nchunk; r->profile = EP; r->nonneg = NN;
+    r->weight_zeros = WZ; r->multi = MULTI; r->pieces = GSPLIT ? PASSES : 1; r->blocks_per_wave = OBW;
+    r->shortcut_fold = DS;
+  }
+  static void launch(const ConvP& p, const Geo& g, dim3 grid, hipStream_t s) {
+    hipLaunchKernelGGL((bconv_sgpr_kernel<KH, KW, CWC, EP, MINW, PASSES, MULTI, GSPLIT, NN, WZ, OBW, DS>), grid,
+                       dim3(kWave), 0, s, p.P, p.M, p.W, p.Z, BNN_EPI_ACTUALS, BNN_DS_ACTUALS, g);
+  }
+};
+template <bool WZ>
+struct GenericKernel {
+  static void describe(const ConvP& p, bnn_hip_conv_route* r) {
+    r->tiled = 0; r->kh = p.KH; r->kw = p.KW; r->cwc = p.cwc; r->nchunk = p.nchunk; r->profile = EP_RUNTIME;
+    r->nonneg = 0; r->weight_zeros = WZ; r->multi = 0; r->pieces = 1; r->blocks_per_wave = 1; r->shortcut_fold = 0;
+  }
+  static void launch(const ConvP& p, const Geo& g, dim3 grid, hipStream_t s) {
+    hipLaunchKernelGGL((bconv_generic_kernel<WZ>), grid, dim3(kWave), 0, s, p.P, p.M, p.W, p.Z, BNN_EPI_ACTUALS, g);
+  }
+};
+
+template <class K>
+static void launch_site(int site, const ConvP& p, const Geo& g, dim3 grid, hipStream_t s, const RouteCtx& rc) {
+  if (rc.out) {
+    K::describe(p, rc.out);
+    rc.out->site = site;
+    rc.out->reserved = 0;
+    rc.out->waves = (int64_t)grid.x * grid.y;
+  }
+  if (!rc.dry) K::launch(p, g, grid, s);
+}
+// BNN_LAUNCH(site, grid, template arguments of bconv_sgpr_kernel...)
+#define BNN_LAUNCH(SITE_, GRID_, ...) launch_site<SgprKernel<__VA_ARGS__>>(SITE_, p, g, GRID_, s, rc)
+
 // NN: the caller vouches for an all-zero M plane (BNN_HIP_FLAG_ACT_NONNEG); 3x3 kernels only.
 // split_ok: the multi-chunk kernels may split a 32-channel block over two waves (lower latency of ONE batch; with
 // several batches in flight — BNN_HIP_FLAG_THROUGHPUT — the unsplit kernel's single field load per block wins).
 template <int KH, int KW, int CWC, int EP, bool NN>
-static void launch_sgpr_t(const ConvP& p, const Geo& g, bool split_ok, hipStream_t s) {
+static void launch_sgpr_t(const ConvP& p, const Geo& g, bool split_ok, hipStream_t s, const RouteCtx& rc) {
   const dim3 grid((unsigned)(8 * g.tiles_per_xcd) * oblocks(p));  // see the XCD note in the kernel
   constexpr bool k3 = KH * KW > 1;
   constexpr int P1 = k3 ? BNN_SGPR_PASSES : 1, PM = k3 ? BNN_SGPR_PASSES_MULTI : 1;
@@ -376,8 +429,7 @@ static void launch_sgpr_t(const ConvP& p, const Geo& g, bool split_ok, hipStream
     if constexpr (EP == EP_PLAIN) {
       if (oblocks(p) >= BNN_SGPR_OBW) {
         const dim3 grid2((unsigned)(8 * g.tiles_per_xcd) * ((oblocks(p) + BNN_SGPR_OBW - 1) / BNN_SGPR_OBW));
-        hipLaunchKernelGGL((bconv_sgpr_kernel<KH, KW, CWC, EP, 1, P1, false, false, NN, false, BNN_SGPR_OBW>), grid2,
-                           dim3(kWave), 0, s, p.P, p.M, p.W, p.Z, BNN_EPI_ACTUALS, BNN_DS_ACTUALS, g);
+        BNN_LAUNCH(BNN_HIP_SITE_SINGLE_OBW, grid2, KH, KW, CWC, EP, 1, P1, false, false, NN, false, BNN_SGPR_OBW);
         return;
       }
     }
@@ -388,8 +440,7 @@ static void launch_sgpr_t(const ConvP& p, const Geo& g, bool split_ok, hipStream
     if constexpr (EP == EP_MID || EP == EP_MIDT) {
       if (split_ok && (long long)grid.x <= BNN_SINGLE_GSPLIT_MAX_WAVES) {
         const dim3 grid2(grid.x * BNN_SINGLE_GSPLIT);
-        hipLaunchKernelGGL((bconv_sgpr_kernel<KH, KW, CWC, EP, 1, BNN_SINGLE_GSPLIT, false, true, NN>), grid2,
-                           dim3(kWave), 0, s, p.P, p.M, p.W, p.Z, BNN_EPI_ACTUALS, BNN_DS_ACTUALS, g);
+        BNN_LAUNCH(BNN_HIP_SITE_SINGLE_SPLIT, grid2, KH, KW, CWC, EP, 1, BNN_SINGLE_GSPLIT, false, true, NN);
         return;
       }
     }
@@ -398,13 +449,11 @@ static void launch_sgpr_t(const ConvP& p, const Geo& g, bool split_ok, hipStream
     constexpr int MW1 = (NN && CWC == 4 && EP == EP_OUT) ? BNN_OUT4_MINW : 1;
     if constexpr (EP == EP_OUT && NN) {
       if (p.ds_P) {  // the block's shortcut convolution folded in (ds_fold_applies() vouches for the shape)
-        hipLaunchKernelGGL((bconv_sgpr_kernel<KH, KW, CWC, EP, MW1, P1, false, false, NN, false, 1, true>), grid,
-                           dim3(kWave), 0, s, p.P, p.M, p.W, p.Z, BNN_EPI_ACTUALS, BNN_DS_ACTUALS, g);
+        BNN_LAUNCH(BNN_HIP_SITE_SINGLE_FOLD, grid, KH, KW, CWC, EP, MW1, P1, false, false, NN, false, 1, true);
         return;
       }
     }
-    hipLaunchKernelGGL((bconv_sgpr_kernel<KH, KW, CWC, EP, MW1, P1, false, false, NN>), grid,
-                       dim3(kWave), 0, s, p.P, p.M, p.W, p.Z, BNN_EPI_ACTUALS, BNN_DS_ACTUALS, g);
+    BNN_LAUNCH(BNN_HIP_SITE_SINGLE, grid, KH, KW, CWC, EP, MW1, P1, false, false, NN);
     return;
   }
   if constexpr (k3 && CWC == 4) {  // the only shape class with several chunks of a large field
@@ -425,104 +474,91 @@ static void launch_sgpr_t(const ConvP& p, const Geo& g, bool split_ok, hipStream
       if constexpr (EP == EP_MID || EP == EP_MIDT) {
         if (split_ok && (long long)grid.x * BNN_MULTI_GSPLIT <= BNN_GSPLIT4_MAX_WAVES) {
           const dim3 grid4(grid.x * 4);
-          hipLaunchKernelGGL((bconv_sgpr_kernel<KH, KW, CWC, EP, MW, 4, true, true, NN>), grid4, dim3(kWave), 0, s, p.P,
-                             p.M, p.W, p.Z, BNN_EPI_ACTUALS, BNN_DS_ACTUALS, g);
+          BNN_LAUNCH(BNN_HIP_SITE_MULTI4_SPLIT4, grid4, KH, KW, CWC, EP, MW, 4, true, true, NN);
           return;
         }
       }
       const dim3 grid2(grid.x * BNN_MULTI_GSPLIT);
       if constexpr (EP == EP_OUT && NN) {
         if (p.ds_P) {
-          hipLaunchKernelGGL(
-              (bconv_sgpr_kernel<KH, KW, CWC, EP, MW, BNN_MULTI_GSPLIT, true, true, NN, false, 1, true>), grid2,
-              dim3(kWave), 0, s, p.P, p.M, p.W, p.Z, BNN_EPI_ACTUALS, BNN_DS_ACTUALS, g);
+          BNN_LAUNCH(BNN_HIP_SITE_MULTI4_SPLIT2_FOLD, grid2, KH, KW, CWC, EP, MW, BNN_MULTI_GSPLIT, true, true, NN, false,
+                     1, true);
           return;
         }
       }
-      hipLaunchKernelGGL(
-          (bconv_sgpr_kernel<KH, KW, CWC, EP, MW, BNN_MULTI_GSPLIT, true, true, NN>), grid2,
-          dim3(kWave), 0, s, p.P, p.M, p.W, p.Z, BNN_EPI_ACTUALS, BNN_DS_ACTUALS, g);
+      BNN_LAUNCH(BNN_HIP_SITE_MULTI4_SPLIT2, grid2, KH, KW, CWC, EP, MW, BNN_MULTI_GSPLIT, true, true, NN);
       return;
     }
 #endif
     if constexpr (EP == EP_OUT && NN) {
       if (p.ds_P) {
-        hipLaunchKernelGGL((bconv_sgpr_kernel<KH, KW, CWC, EP, MW, PM, true, false, NN, false, 1, true>), grid,
-                           dim3(kWave), 0, s, p.P, p.M, p.W, p.Z, BNN_EPI_ACTUALS, BNN_DS_ACTUALS, g);
+        BNN_LAUNCH(BNN_HIP_SITE_MULTI4_FOLD, grid, KH, KW, CWC, EP, MW, PM, true, false, NN, false, 1, true);
         return;
       }
     }
-    hipLaunchKernelGGL((bconv_sgpr_kernel<KH, KW, CWC, EP, MW, PM, true, false, NN>), grid,
-                       dim3(kWave), 0, s, p.P, p.M, p.W, p.Z, BNN_EPI_ACTUALS, BNN_DS_ACTUALS, g);
+    BNN_LAUNCH(BNN_HIP_SITE_MULTI4, grid, KH, KW, CWC, EP, MW, PM, true, false, NN);
     return;
   }
   if constexpr (EP == EP_OUT && NN) {
     if (p.ds_P) {
-      hipLaunchKernelGGL((bconv_sgpr_kernel<KH, KW, CWC, EP, 1, PM, true, false, NN, false, 1, true>), grid,
-                         dim3(kWave), 0, s, p.P, p.M, p.W, p.Z, BNN_EPI_ACTUALS, BNN_DS_ACTUALS, g);
+      BNN_LAUNCH(BNN_HIP_SITE_CHUNKS_FOLD, grid, KH, KW, CWC, EP, 1, PM, true, false, NN, false, 1, true);
       return;
     }
   }
-  hipLaunchKernelGGL((bconv_sgpr_kernel<KH, KW, CWC, EP, 1, PM, true, false, NN>), grid,
-                     dim3(kWave), 0, s, p.P, p.M, p.W, p.Z, BNN_EPI_ACTUALS, BNN_DS_ACTUALS, g);
+  BNN_LAUNCH(BNN_HIP_SITE_CHUNKS, grid, KH, KW, CWC, EP, 1, PM, true, false, NN);
 }
 
 template <int KH, int KW, int CWC, int EP>
-static void launch_sgpr_e(const ConvP& p, const Geo& g, bool nn, bool split_ok, hipStream_t s) {
+static void launch_sgpr_e(const ConvP& p, const Geo& g, bool nn, bool split_ok, hipStream_t s, const RouteCtx& rc) {
   if constexpr (KH * KW > 1) {
-    if (nn) return launch_sgpr_t<KH, KW, CWC, EP, true>(p, g, split_ok, s);
+    if (nn) return launch_sgpr_t<KH, KW, CWC, EP, true>(p, g, split_ok, s, rc);
   }
-  launch_sgpr_t<KH, KW, CWC, EP, false>(p, g, split_ok, s);
+  launch_sgpr_t<KH, KW, CWC, EP, false>(p, g, split_ok, s, rc);
 }
 
 // Zero-weight variant (BNN_HIP_FLAG_WEIGHT_ZEROS): two-plane field, 4 passes of 8 channels, run-time epilogue.
 template <int KH, int KW, int CWC, int EP>
-static void launch_sgpr_wz(const ConvP& p, const Geo& g, hipStream_t s) {
+static void launch_sgpr_wz(const ConvP& p, const Geo& g, hipStream_t s, const RouteCtx& rc) {
   const dim3 grid((unsigned)(8 * g.tiles_per_xcd) * oblocks(p));
   if (KH * KW > 1 && p.nchunk == 1)
-    hipLaunchKernelGGL((bconv_sgpr_kernel<KH, KW, CWC, EP, 1, 4, false, false, false, true>), grid,
-                       dim3(kWave), 0, s, p.P, p.M, p.W, p.Z, BNN_EPI_ACTUALS, BNN_DS_ACTUALS, g);
+    BNN_LAUNCH(BNN_HIP_SITE_WZ_SINGLE, grid, KH, KW, CWC, EP, 1, 4, false, false, false, true);
   else
-    hipLaunchKernelGGL((bconv_sgpr_kernel<KH, KW, CWC, EP, 1, 4, true, false, false, true>), grid,
-                       dim3(kWave), 0, s, p.P, p.M, p.W, p.Z, BNN_EPI_ACTUALS, BNN_DS_ACTUALS, g);
+    BNN_LAUNCH(BNN_HIP_SITE_WZ_CHUNKS, grid, KH, KW, CWC, EP, 1, 4, true, false, false, true);
 }
 
 // PROFILES: whether the compile-time epilogue profiles exist for this shape (3x3 only).
 template <int KH, int KW, int CWC, bool PROFILES>
-static void launch_sgpr(const ConvP& p, int flags, hipStream_t s) {
+static void launch_sgpr(const ConvP& p, int flags, hipStream_t s, const RouteCtx& rc) {
   const Geo g = make_geo(p);
   const bool nn = (flags & BNN_HIP_FLAG_ACT_NONNEG) != 0;
   const bool so = (flags & BNN_HIP_FLAG_THROUGHPUT) == 0;
   // (the int32 "raw" output is a run-time switch: EP_PLAIN keeps its counts in float form and cannot serve it)
   const bool fused = (g.flags & (EF_BN | EF_RES | EF_RELU | EF_PRELU | EF_PACK | EF_RAW)) != 0;
   if (flags & BNN_HIP_FLAG_WEIGHT_ZEROS) {
-    if (fused) launch_sgpr_wz<KH, KW, CWC, EP_RUNTIME>(p, g, s);
-    else launch_sgpr_wz<KH, KW, CWC, EP_PLAIN>(p, g, s);
+    if (fused) launch_sgpr_wz<KH, KW, CWC, EP_RUNTIME>(p, g, s, rc);
+    else launch_sgpr_wz<KH, KW, CWC, EP_PLAIN>(p, g, s, rc);
     return;
   }
   if constexpr (PROFILES) {
-    if (g.flags == kFlagsMid && p.thr) return launch_sgpr_e<KH, KW, CWC, EP_MIDT>(p, g, nn, so, s);
-    if (g.flags == kFlagsMid) return launch_sgpr_e<KH, KW, CWC, EP_MID>(p, g, nn, so, s);
-    if (g.flags == kFlagsOut) return launch_sgpr_e<KH, KW, CWC, EP_OUT>(p, g, nn, so, s);
-    if (g.flags == kFlagsOutP) return launch_sgpr_e<KH, KW, CWC, EP_OUTP>(p, g, nn, so, s);
-    if (g.flags == kFlagsLast) return launch_sgpr_e<KH, KW, CWC, EP_LAST>(p, g, nn, so, s);
-    if (g.flags == kFlagsHb) return launch_sgpr_e<KH, KW, CWC, EP_HB>(p, g, nn, so, s);
-    if (g.flags == kFlagsHb3) return launch_sgpr_e<KH, KW, CWC, EP_HB3>(p, g, nn, so, s);
+    if (g.flags == kFlagsMid && p.thr) return launch_sgpr_e<KH, KW, CWC, EP_MIDT>(p, g, nn, so, s, rc);
+    if (g.flags == kFlagsMid) return launch_sgpr_e<KH, KW, CWC, EP_MID>(p, g, nn, so, s, rc);
+    if (g.flags == kFlagsOut) return launch_sgpr_e<KH, KW, CWC, EP_OUT>(p, g, nn, so, s, rc);
+    if (g.flags == kFlagsOutP) return launch_sgpr_e<KH, KW, CWC, EP_OUTP>(p, g, nn, so, s, rc);
+    if (g.flags == kFlagsLast) return launch_sgpr_e<KH, KW, CWC, EP_LAST>(p, g, nn, so, s, rc);
+    if (g.flags == kFlagsHb) return launch_sgpr_e<KH, KW, CWC, EP_HB>(p, g, nn, so, s, rc);
+    if (g.flags == kFlagsHb3) return launch_sgpr_e<KH, KW, CWC, EP_HB3>(p, g, nn, so, s, rc);
   } else {
-    if (g.flags == kFlagsDs) return launch_sgpr_e<KH, KW, CWC, EP_DS>(p, g, nn, so, s);
+    if (g.flags == kFlagsDs) return launch_sgpr_e<KH, KW, CWC, EP_DS>(p, g, nn, so, s, rc);
   }
-  if (fused) launch_sgpr_e<KH, KW, CWC, EP_RUNTIME>(p, g, nn, so, s);
-  else launch_sgpr_e<KH, KW, CWC, EP_PLAIN>(p, g, nn, so, s);
+  if (fused) launch_sgpr_e<KH, KW, CWC, EP_RUNTIME>(p, g, nn, so, s, rc);
+  else launch_sgpr_e<KH, KW, CWC, EP_PLAIN>(p, g, nn, so, s, rc);
 }
+#undef BNN_LAUNCH
 
-static void launch_generic(const ConvP& p, bool wz, hipStream_t s) {
+static void launch_generic(const ConvP& p, bool wz, hipStream_t s, const RouteCtx& rc) {
   const dim3 grid((p.npix + kWave - 1) / kWave, oblocks(p));
-  if (wz)
-    hipLaunchKernelGGL((bconv_generic_kernel<true>), grid, dim3(kWave), 0, s, p.P, p.M, p.W, p.Z,
-                       BNN_EPI_ACTUALS, make_geo(p));
-  else
-    hipLaunchKernelGGL((bconv_generic_kernel<false>), grid, dim3(kWave), 0, s, p.P, p.M, p.W, p.Z,
-                       BNN_EPI_ACTUALS, make_geo(p));
+  if (wz) launch_site<GenericKernel<true>>(BNN_HIP_SITE_GENERIC_WZ, p, make_geo(p), grid, s, rc);
+  else launch_site<GenericKernel<false>>(BNN_HIP_SITE_GENERIC, p, make_geo(p), grid, s, rc);
 }
 
 // Chunk width is a pure function of the weight geometry (shared with pack_weight).
@@ -556,7 +592,8 @@ bool ds_fold_applies(const ConvP& p, int flags) {
   return make_geo(q).flags == kFlagsOut;
 }
 
-int launch_bconv(const ConvP& p, int flags, hipStream_t s) {
+int launch_bconv(const ConvP& p, int flags, hipStream_t s, bnn_hip_conv_route* route, bool dry) {
+  const RouteCtx rc{route, dry};
   const bool wz = (flags & BNN_HIP_FLAG_WEIGHT_ZEROS) != 0;
   const bool generic = (flags & BNN_HIP_FLAG_FORCE_GENERIC) || p.dh != 1 || p.dw != 1 || !small_indices(p);
   bool done = false;
@@ -564,13 +601,14 @@ int launch_bconv(const ConvP& p, int flags, hipStream_t s) {
     done = true;
 #define BNN_PICK(KH_, KW_, C_, PROF_)                           \
   if (p.KH == KH_ && p.KW == KW_ && p.cwc == C_) {              \
-    launch_sgpr<KH_, KW_, C_, PROF_>(p, flags, s);              \
+    launch_sgpr<KH_, KW_, C_, PROF_>(p, flags, s, rc);          \
   } else
     BNN_PICK(3, 3, 4, true) BNN_PICK(3, 3, 2, true) BNN_PICK(1, 1, 16, false)
     BNN_PICK(1, 1, 8, false) BNN_PICK(1, 1, 4, false) BNN_PICK(1, 1, 2, false) { done = false; }
 #undef BNN_PICK
   }
-  if (!done) launch_generic(p, wz, s);
+  if (!done) launch_generic(p, wz, s, rc);
+  if (dry) return BNN_HIP_OK;  // (nothing was launched: no HIP call either — the query runs on a host without a device)
   return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
 }
 

@@ -189,7 +189,9 @@ int launch_pack_weight(const float* w, int O, int C, int KH, int KW, int center,
                        const bnn_hip_wlayout& L, uint32_t* wbits, uint32_t* wnz, float* alpha,
                        int32_t* zero_flag, hipStream_t stream);
 bool ds_fold_applies(const ConvP& p, int flags);
-int launch_bconv(const ConvP& p, int flags, hipStream_t s);
+// route != null: the kernel the ladder picks is described there (include/bnn_hip.h, bnn_hip_conv_route); dry: nothing is
+// launched and no HIP function is called (bnn_hip_bconv2d_route: the query IS the launch ladder)
+int launch_bconv(const ConvP& p, int flags, hipStream_t s, bnn_hip_conv_route* route = nullptr, bool dry = false);
 // grouped / depthwise convolutions: pack_weight.hip (the windowed layout, L from bnn_hip_grouped_weight_layout) and
 // bconv_grouped.hip (p.C = all input channels, p.W / p.Z in that layout with S words per tap)
 int launch_pack_weight_grouped(const float* w, int O, int Cg, int groups, int center, int compute_alpha,

@@ -105,9 +105,10 @@ void fill_geometry(const bnn_hip_conv_desc* d, int Ho, int Wo, bnn::ConvP* p) {
   if (p->c_tot == 0) { p->c_off = 0; p->c_tot = d->O; }
 }
 
-// Shared tail of every conv entry point: fills the geometry part of `p` and launches.
-int run_conv(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const uint32_t* wbits,
-             const uint32_t* wnz, bnn::ConvP p, void* stream) {
+// The validator of every dense conv entry point (and of the route query): fills the geometry and operand part of `p`.
+int check_conv(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const uint32_t* wbits,
+               const uint32_t* wnz, bnn::ConvP* pp) {
+  bnn::ConvP& p = *pp;
   int Ho = 0, Wo = 0;
   const int st = check_desc(d, &Ho, &Wo);
   if (st != BNN_HIP_OK) return st;
@@ -134,10 +135,29 @@ int run_conv(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, c
     if (p.ds_inW > 0 && ((p.ds_inH + 1) / 2 != Ho || (p.ds_inW + 1) / 2 != Wo)) return BNN_HIP_ERR_INVALID_ARG;
     if (p.ds_inW > 0 && mulc(d->N, ((long long)p.ds_C + 63) / 64, p.ds_inH, p.ds_inW) > kMaxPlaneWords) return BNN_HIP_ERR_TOO_LARGE;
   }
+  return BNN_HIP_OK;
+}
+
+// Shared tail of every conv entry point: validates, fills the geometry part of `p` and launches.
+int run_conv(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const uint32_t* wbits,
+             const uint32_t* wnz, bnn::ConvP p, void* stream) {
+  const int st = check_conv(d, P, M, wbits, wnz, &p);
+  if (st != BNN_HIP_OK) return st;
   g_launches.fetch_add(1, std::memory_order_relaxed);
   Range range(p.raw ? "bnn_hip_bconv2d_dot" : p.ds_P ? "bnn_hip_bconv2d_fused+shortcut"
               : (p.bn_a || p.res || p.outP || p.relu || p.prelu) ? "bnn_hip_bconv2d_fused" : "bnn_hip_bconv2d");
   return bnn::launch_bconv(p, d->flags, static_cast<hipStream_t>(stream));
+}
+
+// Shared tail of the route queries: the same validator, then the launch ladder as a dry run.  The packed operands are
+// not part of a query: an aligned host word stands in for them (never read — nothing is launched).
+int route_conv(const bnn_hip_conv_desc* d, bnn::ConvP p, bnn_hip_conv_route* out) {
+  alignas(16) static const uint64_t operand[2] = {0, 0};
+  if (!out) return BNN_HIP_ERR_INVALID_ARG;
+  const uint32_t* const w = reinterpret_cast<const uint32_t*>(operand);
+  const int st = check_conv(d, operand, operand, w, w, &p);
+  if (st != BNN_HIP_OK) return st;
+  return bnn::launch_bconv(p, d->flags, nullptr, out, /*dry=*/true);
 }
 
 // Grouped convolutions (include/bnn_hip.h, bnn_hip_grouped_weight_layout): S = the most 32-bit activation words one
@@ -175,6 +195,35 @@ bnn::ConvP empty_convp() {
   bnn::ConvP p;
   std::memset(&p, 0, sizeof(p));
   return p;
+}
+
+// The epilogue part of a ConvP from a bnn_hip_epilogue (bnn_hip_bconv2d_fused and its route query).
+int epilogue_convp(const bnn_hip_epilogue* e, bnn::ConvP* pp) {
+  if (!e) return BNN_HIP_ERR_INVALID_ARG;
+  bnn::ConvP& p = *pp;
+  p.alpha = e->alpha; p.bias = e->bias; p.scale = e->post_scale;
+  p.bn_a = e->bn_scale; p.bn_b = e->bn_shift; p.res = e->residual; p.prelu = e->prelu;
+  p.relu = e->relu != 0;
+  p.out = e->out_f32;
+  p.outP = reinterpret_cast<uint32_t*>(e->out_P);
+  p.outM = reinterpret_cast<uint32_t*>(e->out_M);
+  p.pack_a = e->pack_scale; p.pack_b = e->pack_shift;
+  p.thr = e->sign_thresholds;
+  if (p.thr && !aligned(p.thr, 4)) return BNN_HIP_ERR_INVALID_ARG;
+  p.eflags = e->flags;
+  p.c_off = e->out_c_offset; p.c_tot = e->out_c_total;
+  if (e->sc_P || e->sc_wbits || e->sc_alpha || e->sc_bn_scale || e->sc_bn_shift) {
+    if (!e->sc_P) return BNN_HIP_ERR_INVALID_ARG;
+    p.ds_P = reinterpret_cast<const uint32_t*>(e->sc_P);
+    p.ds_W = e->sc_wbits; p.ds_alpha = e->sc_alpha; p.ds_a = e->sc_bn_scale; p.ds_b = e->sc_bn_shift;
+    p.ds_C = e->sc_C;
+    if (e->sc_in_hw != 0) {      // un-pooled shortcut plane: (H << 16) | W of it; the kernel ORs the 2 x 2 windows
+      p.ds_inH = (int)((uint32_t)e->sc_in_hw >> 16);
+      p.ds_inW = (int)((uint32_t)e->sc_in_hw & 0xFFFFu);
+      if (p.ds_inH <= 0 || p.ds_inW <= 0) return BNN_HIP_ERR_INVALID_ARG;
+    }
+  }
+  return BNN_HIP_OK;
 }
 
 // A weight layout of `words` 32-bit words per output channel and tap, read in chunks of `cwc` words (which divides it).
@@ -888,31 +937,28 @@ int bnn_hip_bconv2d_grouped_node(const bnn_hip_conv_desc* d, int groups, const u
 int bnn_hip_bconv2d_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M,
                           const uint32_t* wbits, const uint32_t* wnz, const bnn_hip_epilogue* e,
                           void* stream) {
-  if (!e) return BNN_HIP_ERR_INVALID_ARG;
   bnn::ConvP p = empty_convp();
-  p.alpha = e->alpha; p.bias = e->bias; p.scale = e->post_scale;
-  p.bn_a = e->bn_scale; p.bn_b = e->bn_shift; p.res = e->residual; p.prelu = e->prelu;
-  p.relu = e->relu != 0;
-  p.out = e->out_f32;
-  p.outP = reinterpret_cast<uint32_t*>(e->out_P);
-  p.outM = reinterpret_cast<uint32_t*>(e->out_M);
-  p.pack_a = e->pack_scale; p.pack_b = e->pack_shift;
-  p.thr = e->sign_thresholds;
-  if (p.thr && !aligned(p.thr, 4)) return BNN_HIP_ERR_INVALID_ARG;
-  p.eflags = e->flags;
-  p.c_off = e->out_c_offset; p.c_tot = e->out_c_total;
-  if (e->sc_P || e->sc_wbits || e->sc_alpha || e->sc_bn_scale || e->sc_bn_shift) {
-    if (!e->sc_P) return BNN_HIP_ERR_INVALID_ARG;
-    p.ds_P = reinterpret_cast<const uint32_t*>(e->sc_P);
-    p.ds_W = e->sc_wbits; p.ds_alpha = e->sc_alpha; p.ds_a = e->sc_bn_scale; p.ds_b = e->sc_bn_shift;
-    p.ds_C = e->sc_C;
-    if (e->sc_in_hw != 0) {      // un-pooled shortcut plane: (H << 16) | W of it; the kernel ORs the 2 x 2 windows
-      p.ds_inH = (int)((uint32_t)e->sc_in_hw >> 16);
-      p.ds_inW = (int)((uint32_t)e->sc_in_hw & 0xFFFFu);
-      if (p.ds_inH <= 0 || p.ds_inW <= 0) return BNN_HIP_ERR_INVALID_ARG;
-    }
-  }
+  const int st = epilogue_convp(e, &p);
+  if (st != BNN_HIP_OK) return st;
   return run_conv(d, P, M, wbits, wnz, p, stream);
+}
+
+int bnn_hip_bconv2d_route(const bnn_hip_conv_desc* d, const bnn_hip_epilogue* e, bnn_hip_conv_route* out) {
+  bnn::ConvP p = empty_convp();
+  if (e) {
+    const int st = epilogue_convp(e, &p);
+    if (st != BNN_HIP_OK) return st;
+  } else {  // bnn_hip_bconv2d: alpha -> fp32 (any non-null values: only compared with null)
+    p.alpha = reinterpret_cast<const float*>(&p);
+    p.out = &p;
+  }
+  return route_conv(d, p, out);
+}
+
+int bnn_hip_bconv2d_dot_route(const bnn_hip_conv_desc* d, bnn_hip_conv_route* out) {
+  bnn::ConvP p = empty_convp();
+  p.raw = true; p.out = &p;
+  return route_conv(d, p, out);
 }
 
 int bnn_hip_shortcut_fold_supported(const bnn_hip_conv_desc* d, int sc_C) {

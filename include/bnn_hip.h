@@ -61,7 +61,9 @@
 extern "C" {
 #endif
 
-/* Additive entry points of ABI 15 for the training step of FactorizedReduce (no struct or signature changed):
+/* ABI 16: + bnn_hip_bconv2d_route, bnn_hip_bconv2d_dot_route and bnn_hip_conv_route (which kernel a convolution runs:
+ * host-only queries answered by the launch ladder itself; no other struct or signature changed).
+ * Additive entry points of ABI 15 for the training step of FactorizedReduce (no struct or signature changed):
  * + bnn_hip_bn_act_pack_ste_s2_f32, bnn_hip_bn_train_pack_ste_s2_f32 (the three bit planes of the two pixel lattices its
  * convolutions read); + bnn_hip_bn_train_backward_s2_f32 (the BatchNorm backward of a gradient that lives on those lattices).
  * Additive entry points of ABI 15 for the training step of a BATS cell operation (no struct or signature changed):
@@ -86,7 +88,7 @@ extern "C" {
  * bnn_hip_bn_relu_maxpool_train_{forward,backward}_f32, bnn_hip_xnor_weight_{forward,backward}_f32;
  * - BNN_HIP_STEM_STAGED and BNN_HIP_FLAG_WEIGHTS_LDS (those kernels are test-only now: csrc/legacy/);
  * stem tensors capped at the 32-bit buffer-descriptor range; size arithmetic of all validators saturating.          */
-#define BNN_HIP_ABI_VERSION 15
+#define BNN_HIP_ABI_VERSION 16
 #define BNN_HIP_OCB 32 /* output channels per weight block (padding granularity of O) */
 
 typedef enum bnn_hip_status {
@@ -458,6 +460,66 @@ int bnn_hip_bconv2d_fused(const bnn_hip_conv_desc* d,
  * sc_*) for this convolution — 3x3 tiled kernels on non-negative activations (BNN_HIP_FLAG_ACT_NONNEG) without zero
  * weights, epilogue = BatchNorm + shortcut + ReLU -> fp32 + sign planes, sc_C in {64, 128, 256}; 0 otherwise.       */
 int bnn_hip_shortcut_fold_supported(const bnn_hip_conv_desc* d, int sc_C);
+
+/* ---- Which kernel a convolution runs (ABI 16): the route of bnn_hip_bconv2d / _fused / _dot, for tests. ----
+ * The launch ladder of csrc/bconv.hip picks one instantiation per call from the kernel size, the chunk width, the
+ * epilogue, the flags and the size of the grid.  The route query walks THAT ladder (the same statements, with the
+ * launch itself skipped) and reports where it ends, so that a test can assert which kernel it is about to check.    */
+enum {                          /* bnn_hip_conv_route.profile: the epilogue the kernel was compiled for */
+  BNN_HIP_ROUTE_EP_PLAIN = 0,   /* alpha [, bias] [, post-scale] -> fp32                                */
+  BNN_HIP_ROUTE_EP_RUNTIME = 1, /* anything, decided at run time (also every shape-generic launch)      */
+  BNN_HIP_ROUTE_EP_MID = 2,     /* BN + ReLU -> planes                                                  */
+  BNN_HIP_ROUTE_EP_OUT = 3,     /* BN + residual + ReLU -> fp32 + planes                                */
+  BNN_HIP_ROUTE_EP_DS = 4,      /* BN -> fp32 (1x1 shortcut convolution)                                */
+  BNN_HIP_ROUTE_EP_LAST = 5,    /* BN + residual + ReLU -> fp32                                         */
+  BNN_HIP_ROUTE_EP_HB = 6,      /* hierarchical-block stages 1, 2                                       */
+  BNN_HIP_ROUTE_EP_HB3 = 7,     /* hierarchical-block stage 3                                           */
+  BNN_HIP_ROUTE_EP_MIDT = 8,    /* EP_MID through the integer sign thresholds                           */
+  BNN_HIP_ROUTE_EP_OUTP = 9     /* BN + residual + ReLU -> planes                                       */
+};
+enum {                          /* bnn_hip_conv_route.site: the launch statement of the ladder, in source order */
+  BNN_HIP_SITE_SINGLE_OBW = 0,      /* single-chunk 3x3, EP_PLAIN, several 32-channel blocks per wave           */
+  BNN_HIP_SITE_SINGLE_SPLIT = 1,    /* single-chunk 3x3 split into pieces (compiled out: BNN_SINGLE_GSPLIT == 1) */
+  BNN_HIP_SITE_SINGLE_FOLD = 2,     /* single-chunk 3x3 with the folded shortcut                                */
+  BNN_HIP_SITE_SINGLE = 3,          /* single-chunk 3x3                                                         */
+  BNN_HIP_SITE_MULTI4_SPLIT4 = 4,   /* multi-chunk 3x3 of chunk width 4, four pieces per block                  */
+  BNN_HIP_SITE_MULTI4_SPLIT2_FOLD = 5, /* ... two pieces, folded shortcut                                      */
+  BNN_HIP_SITE_MULTI4_SPLIT2 = 6,   /* ... two pieces                                                           */
+  BNN_HIP_SITE_MULTI4_FOLD = 7,     /* ... unsplit, folded shortcut                                             */
+  BNN_HIP_SITE_MULTI4 = 8,          /* ... unsplit                                                              */
+  BNN_HIP_SITE_CHUNKS_FOLD = 9,     /* multi-chunk 3x3 of chunk width 2 with the folded shortcut                */
+  BNN_HIP_SITE_CHUNKS = 10,         /* multi-chunk 3x3 of chunk width 2, and every 1x1                          */
+  BNN_HIP_SITE_WZ_SINGLE = 11,      /* zero-weight kernel, single-chunk 3x3                                     */
+  BNN_HIP_SITE_WZ_CHUNKS = 12,      /* zero-weight kernel, everything else                                      */
+  BNN_HIP_SITE_GENERIC_WZ = 13,     /* shape-generic kernel honouring zero weights                              */
+  BNN_HIP_SITE_GENERIC = 14,        /* shape-generic kernel                                                     */
+  BNN_HIP_ROUTE_SITES = 15          /* number of launch statements                                              */
+};
+typedef struct bnn_hip_conv_route {
+  int32_t tiled;           /* 1: bconv_sgpr_kernel; 0: the shape-generic bconv_generic_kernel                    */
+  int32_t kh, kw;          /* kernel size the kernel was compiled for (generic: of the descriptor)               */
+  int32_t cwc, nchunk;     /* 32-bit words per chunk of input channels, chunks (bnn_hip_weight_layout)           */
+  int32_t profile;         /* BNN_HIP_ROUTE_EP_*                                                                 */
+  int32_t nonneg;          /* 1: the P-only kernel (BNN_HIP_FLAG_ACT_NONNEG honoured; never for 1x1 or generic)   */
+  int32_t weight_zeros;    /* 1: the kernel reads the wnz mask                                                   */
+  int32_t multi;           /* 1: the kernel walks chunks (every 1x1 kernel does, also over one chunk)            */
+  int32_t pieces;          /* waves that share one 32-channel block: 1, 2 or 4                                   */
+  int32_t blocks_per_wave; /* 32-channel blocks one wave produces                                                */
+  int32_t shortcut_fold;   /* 1: the kernel computes the folded shortcut convolution (bnn_hip_epilogue sc_*)      */
+  int32_t site;            /* BNN_HIP_SITE_*                                                                     */
+  int32_t reserved;        /* 0                                                                                  */
+  int64_t waves;           /* workgroups (of one wave) of the launch                                             */
+} bnn_hip_conv_route;
+
+/* HOST: the route bnn_hip_bconv2d_fused(d, ..., e, ...) takes, or with e == NULL the route of bnn_hip_bconv2d(d, ...)
+ * with any alpha / bias / post_scale.  Validates d and *e through the validator of those entry points (same status
+ * codes, including BNN_HIP_ERR_UNSUPPORTED for a shortcut fold the shape does not take); the packed operands P, M,
+ * wbits and wnz are not arguments and count as valid.  Launches nothing, calls no HIP function and reads through no
+ * pointer of *e: those are only compared with NULL (and checked for alignment), so any non-null value describes "given".
+ * *out is written only on BNN_HIP_OK.                                                                               */
+int bnn_hip_bconv2d_route(const bnn_hip_conv_desc* d, const bnn_hip_epilogue* e, bnn_hip_conv_route* out);
+/* HOST: the same for bnn_hip_bconv2d_dot(d, ...).                                                                    */
+int bnn_hip_bconv2d_dot_route(const bnn_hip_conv_desc* d, bnn_hip_conv_route* out);
 
 /* Same traversal, raw integer result: dot[n,o,y,x] (int32) — the bit-exact target
  * of the popcount path against the emulated-integer oracle.                        */

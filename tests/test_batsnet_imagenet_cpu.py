@@ -39,7 +39,7 @@ def test_header_binding_and_library_agree_on_the_symbols(symbol, count):
     assert fn.restype is ctypes.c_int and len(fn.argtypes) == len(params) == count
     for p, t in zip(params, fn.argtypes):          # pointers are bound as pointers, ints as ints, in the header's order
         assert (t is ctypes.c_void_p) == ("*" in p) and (t is ctypes.c_int) == (p.startswith("int ")), (p, t)
-    assert native.require().bnn_hip_abi_version() == native.ABI_VERSION == 15      # additive entry points
+    assert native.require().bnn_hip_abi_version() == native.ABI_VERSION == 16      # additive entry points
 
 
 def test_python_constants_are_the_headers():

@@ -26,6 +26,7 @@ def test_library_exports_every_declared_symbol():
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/bnn_hip.h but not exported"
     assert set(native.EXPORTED_SYMBOLS) == set(syms)
+    assert {"bnn_hip_bconv2d_route", "bnn_hip_bconv2d_dot_route"} <= set(syms)
     # every exported symbol carries its prototype on the loaded library (an undeclared one passes pointers as C ints)
     loaded, text = native.require(), open(os.path.join(ROOT, "include", "bnn_hip.h")).read()
     for s in native.EXPORTED_SYMBOLS:
@@ -71,7 +72,7 @@ def test_capi_validators_survive_an_argument_fuzz_under_asan_and_ubsan():
 
 def test_require_loads_and_reports_abi():
     lib = native.require()
-    assert lib.bnn_hip_abi_version() == native.ABI_VERSION == 15
+    assert lib.bnn_hip_abi_version() == native.ABI_VERSION == 16
     assert lib.bnn_hip_status_string(0) == b"ok"
     assert b"invalid" in lib.bnn_hip_status_string(-1)
     assert isinstance(native.launch_count(), int)
@@ -98,7 +99,8 @@ def test_ctypes_structs_have_the_layout_of_the_c_header(tmp_path):
     by the folded-shortcut fields in ABI 11) would otherwise shift every pointer behind it silently."""
     import subprocess
     structs = {"bnn_hip_conv_desc": native.ConvDesc, "bnn_hip_epilogue": native.Epilogue,
-               "bnn_hip_wlayout": native.WLayout, "bnn_hip_fly_plan": native.FlyPlan}
+               "bnn_hip_wlayout": native.WLayout, "bnn_hip_fly_plan": native.FlyPlan,
+               "bnn_hip_conv_route": native.ConvRoute}
     lines = []
     for cname, cls in structs.items():
         lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))

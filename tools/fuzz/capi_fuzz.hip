@@ -46,8 +46,10 @@ static void check_convp(const ConvP& p) {
   REQUIRE((long long)p.N * ctot * p.Ho * p.Wo <= kConvElems);
   REQUIRE((long long)p.N * p.Ho * p.Wo * ((p.O + 63) / 64) <= kPlaneWords);
 }
-int launch_bconv(const ConvP& p, int flags, hipStream_t) {
+int launch_bconv(const ConvP& p, int flags, hipStream_t, bnn_hip_conv_route* route, bool dry) {
   ++g_reached;
+  REQUIRE(dry == (route != nullptr));  // the entry points launch without a route; the queries ask for one and launch nothing
+  if (route) { std::memset(route, 0, sizeof(*route)); route->site = BNN_HIP_ROUTE_SITES - 1; route->waves = 1; }
   check_convp(p);
   REQUIRE((long long)p.N * p.H * p.Wd * ((p.C + 63) / 64) <= kPlaneWords);
   REQUIRE(p.P && p.M && p.W && al(p.P, 16) && al(p.M, 16) && al(p.W, 16));
@@ -889,6 +891,22 @@ int main(int argc, char** argv) {
         break; }
       default: { bnn_hip_conv_desc d = pick_desc();
         (void)bnn_hip_shortcut_fold_supported(rnd() % 16 ? &d : nullptr, pick_int());
+        { // the route queries: the validator of bnn_hip_bconv2d_fused / _dot on a descriptor and an epilogue alone
+          bnn_hip_epilogue e; std::memset(&e, 0, sizeof(e));
+          e.alpha = pick_ptr<float>(); e.bn_scale = pick_ptr<float>(); e.bn_shift = pick_ptr<float>(); e.residual = pick_ptr<float>();
+          e.relu = pick_int(); e.flags = (int)(rnd() % 8); e.out_f32 = pick_ptr<float>(); e.out_P = pick_ptr<uint64_t>();
+          e.out_M = pick_ptr<uint64_t>(); e.out_c_offset = pick_int(); e.out_c_total = pick_int();
+          e.sign_thresholds = pick_ptr<int32_t>();
+          if (rnd() % 3 == 0) { e.sc_P = pick_ptr<uint64_t>(); e.sc_wbits = pick_ptr<uint32_t>(); e.sc_alpha = pick_ptr<float>();
+                                e.sc_bn_scale = pick_ptr<float>(); e.sc_bn_shift = pick_ptr<float>(); e.sc_C = pick_int(); }
+          bnn_hip_conv_route r; std::memset(&r, 0x5A, sizeof(r));
+          const int sr = bnn_hip_bconv2d_route(rnd() % 16 ? &d : nullptr, rnd() % 4 ? &e : nullptr, rnd() % 16 ? &r : nullptr);
+          if (!status_ok(sr)) broken("route status");
+          if (sr == BNN_HIP_OK && (r.site < 0 || r.site >= BNN_HIP_ROUTE_SITES || r.waves <= 0)) broken("route of an accepted call");
+          const int sd = bnn_hip_bconv2d_dot_route(rnd() % 16 ? &d : nullptr, rnd() % 16 ? &r : nullptr);
+          if (!status_ok(sd)) broken("dot route status");
+          digest = (digest ^ (uint64_t)(uint32_t)sr ^ ((uint64_t)(uint32_t)sd << 32)) * 0x100000001B3ull;
+        }
         st = bnn_hip_blinear(pick_int(), pick_int(), pick_int(), pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<uint32_t>(),
                              pick_ptr<uint32_t>(), pick_int(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(),
                              pick_ptr<float>(), stream);
