@@ -1552,16 +1552,21 @@ def bconv_grad_input(g: torch.Tensor, x, packed: torch.Tensor, alpha: torch.Tens
     return gx
 
 
-def bconv_grad_weight(g: torch.Tensor, x, ksize: int = 3, stride: int = 1, reduce: bool = True) -> torch.Tensor:
+def bconv_grad_weight(g: torch.Tensor, x, ksize: int = 3, stride: int = 1, reduce: bool = True,
+                      splits: Optional[int] = None) -> torch.Tensor:
     """dL/dWhat [O,C,k,k] of the binary 3x3/p1 or 1x1/p0 conv: correlation of g with sign(x).  ``x``: the fp32 input, or
     its ``SavedAct`` (the sign planes are all this kernel needs of it) — same bits either way.  ``reduce=False``: the
-    kernel's split-K partial slabs ``[splits, O, C, k, k]`` as they are (``xnor_weight_backward`` adds them itself)."""
+    kernel's split-K partial slabs ``[splits, O, C, k, k]`` as they are (``xnor_weight_backward`` adds them itself).
+    ``splits=None``: the library's choice (``bnn_hip_bconv_grad_weight_splits``); a value of the caller's goes to the entry
+    point as it is, which refuses one that is not ``ceil(N / ceil(N / splits))``."""
     g = _require_cuda_f32(g, "grad_output")
     if not isinstance(x, SavedAct):
         x = _require_cuda_f32(x, "input")
     lib = native.require()
     N, O, C, H, W = _grad_shapes(g, x, stride)
-    splits = int(lib.bnn_hip_bconv_grad_weight_splits(N, O, C, ksize))
+    splits = int(lib.bnn_hip_bconv_grad_weight_splits(N, O, C, ksize)) if splits is None else int(splits)
+    if splits < 1 or splits > N:                     # (before `part` is sized by it)
+        native.check(native.ERR_INVALID_ARG, "bnn_hip_bconv_grad_weight_f32")
     with torch.cuda.device(g.device):
         part = torch.empty((splits, O, C, ksize, ksize), dtype=torch.float32, device=g.device)
         if isinstance(x, SavedAct):
@@ -1652,19 +1657,21 @@ def bconv_grouped_grad_weight(g: torch.Tensor, saved: "SavedAct", w_shape, group
         return part[0] if splits == 1 else part.sum(0)
 
 
-def xnor_what(w: torch.Tensor, center: bool, compute_alpha: bool) -> torch.Tensor:
+def xnor_what(w: torch.Tensor, center: bool, compute_alpha: bool, return_alpha: bool = False):
     """``XNORWeightBinarizer.forward`` value (bnn/ops.py:129-140) in one kernel: ``sign(Wc) * alpha`` as an fp32 tensor
-    (no autograd graph).  Same centring / alpha reductions as ``pack_weight``."""
+    (no autograd graph).  Same centring / alpha reductions as ``pack_weight``.  ``return_alpha``: ``(What, alpha[O])``, the
+    kernel's own per-channel scale (1 without ``compute_alpha``)."""
     w = _require_cuda_f32(w.detach(), "weight")
     lib = native.require()
     O, C = w.shape[0], w.shape[1]
     kh, kw = (w.shape[2], w.shape[3]) if w.dim() == 4 else (1, 1)
     with torch.cuda.device(w.device):
         what = torch.empty_like(w)
+        alpha = torch.empty(O, dtype=torch.float32, device=w.device) if return_alpha else None
         native.check(lib.bnn_hip_xnor_weight_forward_f32(w.data_ptr(), O, C, kh, kw, int(center), int(compute_alpha),
-                                                         what.data_ptr(), None, _stream(w.device)),
+                                                         what.data_ptr(), _ptr(alpha), _stream(w.device)),
                      "bnn_hip_xnor_weight_forward_f32")
-    return what
+    return (what, alpha) if return_alpha else what
 
 
 def xnor_weight_backward(w: torch.Tensor, dwhat: torch.Tensor, center: bool, compute_alpha: bool) -> torch.Tensor:

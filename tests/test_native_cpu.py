@@ -168,6 +168,18 @@ def test_argument_validation_without_touching_the_gpu():
     assert lib.bnn_hip_bconv_grad_input_f32(16, 16, 16, 16, 16, 2, 64, 64, 8, 8, 3, 3, None) == -2   # stride 3
     assert lib.bnn_hip_bconv_grad_input_f32(16, 16, 16, 16, 16, 2, 64, 64, 8, 8, 1, 2, None) == -2   # strided 1x1
     assert lib.bnn_hip_bconv_grad_weight_f32(None, 16, 16, 1, 2, 64, 64, 8, 8, 3, 1, None) == -1
+    # a caller's image split (hipops.bconv_grad_weight(..., splits=)) is refused before any launch unless it is
+    # ceil(N / ceil(N / splits)): more slabs than images, N = 5 in 4 (per = 2 gives 3), none
+    for fp32 in (True, False):
+        def wgrad(splits, N, fp32=fp32):
+            if fp32:
+                return lib.bnn_hip_bconv_grad_weight_f32(16, 16, 16, splits, N, 64, 64, 8, 8, 3, 1, None)
+            return lib.bnn_hip_bconv_grad_weight_packed_f32(16, 16, 16, 16, splits, N, 64, 64, 8, 8, 3, 1, None)
+        assert wgrad(6, 5) == -1 and wgrad(4, 5) == -1 and wgrad(0, 5) == -1 and wgrad(-1, 5) == -1
+        assert wgrad(6, 7) == -1 and wgrad(5, 7) == -1
+    # the library's own choice: ~1024 workgroups, then evened out; 20 images on a 512 x 512 layer run 3 per workgroup
+    assert lib.bnn_hip_bconv_grad_weight_splits(20, 512, 512, 3) == 7
+    assert lib.bnn_hip_bconv_grad_weight_splits(5, 64, 64, 3) == 5
     # stem convolution of a training step: forward argument checks; backward workspace arithmetic and support rule
     assert lib.bnn_hip_stem7x7_conv_f32(None, 16, 1, 8, 8, 0, 16, None) == -1
     assert lib.bnn_hip_stem7x7_conv_f32(16, 16, 1, 8, 8, 2, 16, None) == -1                 # unknown flag
