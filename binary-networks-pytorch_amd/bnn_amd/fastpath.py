@@ -10,8 +10,11 @@ A layer takes the HIP path when ALL of the following hold (otherwise the torch c
 * input and weight are both float32 or both float16 (a ``.half()`` model: bit planes straight from the fp16
   tensor, fp32 arithmetic inside, output rounded to fp16 once) on the same HIP device
 * autograd is not recording (``torch.no_grad()`` / inference); when it IS recording, ``Conv2d`` takes the
-  training variant (HIP forward, fp32 library backward with the straight-through estimator:
-  ``bnn_amd/training.py``), ``Conv1d``/``Linear`` fall back to the composition
+  training variant (HIP forward, binary-aware HIP gradient kernels or the library's fp32 backward with the
+  straight-through estimator: ``bnn_amd/training.py``); ``Linear`` takes its own training variant under
+  ``training.LINEAR`` (``BNN_AMD_TRAIN_LINEAR=1``, off by default: one HIP launch forward that keeps three bit planes
+  of the input, bf16 x 3 matrix-core gradients from the weight pack and the planes: ``csrc/blinear.hip``) and the
+  composition otherwise; ``Conv1d`` under autograd stays on the composition
 * ``padding_mode == 'zeros'``, numeric padding, and either ``groups == 1`` or — ``Conv2d`` / ``Conv1d`` under inference,
   ``Conv2d`` under autograd only with ``training.GROUPED`` — ``groups > 1`` (grouped and depthwise layers: ``pack_act``
   + ``bnn_hip_bconv2d_grouped``, two launches; the ResNet executors keep declining them, and so does the training
@@ -42,7 +45,7 @@ from . import hipops, native
 
 _stats_lock = threading.Lock()
 _stats = {"conv2d": 0, "conv1d": 0, "linear": 0, "weight_packs": 0, "conv2d_train": 0, "cell_op": 0, "cell": 0,
-          "cell_op_train": 0, "reduce_train": 0}
+          "cell_op_train": 0, "reduce_train": 0, "linear_train": 0}
 
 
 def stats() -> dict:
@@ -169,6 +172,23 @@ def plan_linear(layer, x: torch.Tensor) -> Optional[Plan]:
         return None
     plan = _recognise(layer, layer.out_features)
     return plan if plan is not None and _eligible(layer, x, plan) else None
+
+
+def plan_linear_train(layer, x: torch.Tensor) -> Optional[Plan]:
+    """Plan for a training-mode forward of a ``Linear`` (only consulted when ``plan_linear`` declined), under
+    ``training.LINEAR`` (read at every call; off by default): recognised hooks with the hard-tanh STE, fp32 weight and
+    input on one HIP device, autograd recording without autocast, no hooks on ``weight_pre_process`` (they would not
+    fire)."""
+    from . import training
+    if not training.LINEAR or x.dim() < 1 or torch.is_autocast_enabled():
+        return None
+    plan = _recognise(layer, layer.out_features)
+    if plan is None or not plan.ste or not _eligible_train(layer, x):
+        return None
+    wpre = layer.weight_pre_process
+    if wpre._forward_hooks or wpre._forward_pre_hooks:
+        return None
+    return plan
 
 
 def packed_weight(layer, plan: Plan, sync: bool = True, fresh: bool = False) -> hipops.PackedWeight:
@@ -350,11 +370,20 @@ def conv1d(layer, x: torch.Tensor, plan: Plan) -> torch.Tensor:
 
 
 def linear(layer, x: torch.Tensor, plan: Plan) -> torch.Tensor:
-    """``Linear`` as a 1x1 convolution over 1x1 images (bnn/layers/linear.py:22-27)."""
+    """``Linear`` (bnn/layers/linear.py:22-27): the row-major XNOR GEMM kernel where it was measured not slower, else a
+    1x1 convolution over 1x1 images (``hipops.linear``) — the same bits."""
     native.require()
     pw = packed_weight(layer, plan)
-    lead = x.shape[:-1]
-    x2 = x.reshape(-1, x.shape[-1])
-    out = hipops.bconv2d_direct(x2[:, :, None, None], pw, _f32(layer.bias), _f32(plan.scale))
+    out = hipops.linear(x, pw, _f32(layer.bias), _f32(plan.scale))
     _bump("linear")
-    return out.reshape(*lead, layer.out_features).to(x.dtype)
+    return out.to(x.dtype)
+
+
+def linear_train(layer, x: torch.Tensor, plan: Plan) -> torch.Tensor:
+    """Same forward under autograd (``training.linear_train``): one HIP launch forward that keeps three bit planes of the
+    input, the binary-aware HIP gradient kernels backward."""
+    from . import training
+    native.require()
+    out = training.linear_train(layer, x, plan, packed_weight(layer, plan, sync=False, fresh=True))
+    _bump("linear_train")
+    return out

@@ -1695,6 +1695,157 @@ def xnor_weight_backward(w: torch.Tensor, dwhat: torch.Tensor, center: bool, com
     return dw
 
 
+# ---- Linear as GEMM-shaped kernels (csrc/blinear.hip): forward from the float input, gradients from bits ---------------
+_LINEAR_MAX_ELEMS = (1 << 30) - 1       # M * F and M * O of one launch (include/bnn_hip.h)
+
+
+def _linear_rows(M: int, F: int, O: int) -> int:
+    """Rows per launch of the Linear kernels."""
+    return max(1, min(M, _LINEAR_MAX_ELEMS // max(F, O)))
+
+
+def _linear_weight(w: PackedWeight, what: str) -> Tuple[int, int]:
+    _ungrouped(w, what)
+    if tuple(w.shape[2:]) != (1, 1):
+        raise native.NativeError(f"bnn_amd: {what} takes the pack of an [O, F] weight, got {tuple(w.shape)}")
+    return int(w.shape[0]), int(w.shape[1])
+
+
+def _linear_planes(M: int, F: int, device) -> "SavedAct":
+    a = empty_packed(M, F, 1, 1, device)
+    return SavedAct(a, torch.empty_like(a.P), (M, F, 1, 1))
+
+
+def blinear_direct(x: torch.Tensor, w: PackedWeight, bias: Optional[torch.Tensor] = None,
+                   post_scale: Optional[torch.Tensor] = None, want_planes: bool = False, lds_words: int = 0):
+    """``Linear.forward`` of the reference (bnn/layers/linear.py:22-27) in ONE launch of the row-major kernel
+    (``bnn_hip_blinear_direct``): fp32 or fp16 ``[..., F]`` in, fp32 ``[..., O]`` out, ``sign(x)`` taken inside — the bits
+    of ``bconv2d_direct`` on ``M`` images of 1 x 1 pixels.  ``want_planes``: returns ``(out, SavedAct)`` with the three bit
+    planes of ``pack_act_ste`` (shape ``(M, F, 1, 1)``, ``M`` the flattened leading dimensions) from the same pass over
+    ``x``.  ``lds_words``: the kernel's LDS pass over ``F`` in 32-bit words per row (0: its default; tests force it)."""
+    O, F = _linear_weight(w, "blinear_direct")
+    x = _require_cuda_act(x)
+    if x.dim() < 1 or x.shape[-1] != F:
+        raise native.NativeError(f"bnn_amd: blinear_direct expects [..., {F}], got shape {tuple(x.shape)}")
+    lib = native.require()
+    lead = tuple(x.shape[:-1])
+    x2 = x.reshape(-1, F)
+    M = x2.shape[0]
+    dev = x.device
+    bias = _per_channel(bias, O, "bias")
+    post_scale = _per_channel(post_scale, O, "post_scale")
+    with torch.cuda.device(dev):
+        out = torch.empty((M, O), dtype=torch.float32, device=dev)
+        sv = _linear_planes(M, F, dev) if want_planes else None
+        dtype = native.DTYPE_F16 if x.dtype == torch.float16 else native.DTYPE_F32
+        step = _linear_rows(M, F, O)
+        for m0 in range(0, M, step):
+            m1 = min(M, m0 + step)
+            pl = [None, None, None] if sv is None else [t[m0:m1].data_ptr() for t in (sv.sign.P, sv.sign.M, sv.T)]
+            native.check(lib.bnn_hip_blinear_direct(
+                m1 - m0, F, O, x2[m0:m1].data_ptr(), dtype, w.wbits.data_ptr(), w.wnz.data_ptr(), int(w.has_zero),
+                w.alpha.data_ptr(), _ptr(bias), _ptr(post_scale), out[m0:m1].data_ptr(), *pl, int(lds_words), _stream(dev)),
+                "bnn_hip_blinear_direct")
+    out = out.reshape(*lead, O)
+    return (out, sv) if want_planes else out
+
+
+def _linear_grad_shapes(g: torch.Tensor, saved: "SavedAct", O: Optional[int] = None):
+    M, F = int(saved.shape[0]), int(saved.shape[1])
+    if tuple(saved.shape[2:]) != (1, 1) or g.dim() < 1 or (O is not None and g.shape[-1] != O) or g.numel() != M * g.shape[-1]:
+        raise native.NativeError(f"bnn_amd: grad_output {tuple(g.shape)} does not belong to the planes of a "
+                                 f"{tuple(saved.shape[:2])} input")
+    return M, F, int(g.shape[-1])
+
+
+def blinear_grad_input(g: torch.Tensor, saved: "SavedAct", w: PackedWeight) -> torch.Tensor:
+    """dL/dx ``[M, F]`` of the binary Linear incl. the hard-tanh STE mask: ``(sum_o g alpha sign(Wc)) * 1[|x| < 1]``, from
+    the forward's own weight pack (sign bits and zero mask) and the mask plane of ``saved``."""
+    O, F = _linear_weight(w, "blinear_grad_input")
+    g = _require_cuda_f32(g, "grad_output")
+    M, F2, _ = _linear_grad_shapes(g, saved, O)
+    if F2 != F:
+        raise native.NativeError(f"bnn_amd: planes of {F2} features against a weight of {F}")
+    g = g.reshape(M, O)
+    lib = native.require()
+    with torch.cuda.device(g.device):
+        gx = torch.empty((M, F), dtype=torch.float32, device=g.device)
+        step = _linear_rows(M, F, O)
+        for m0 in range(0, M, step):
+            m1 = min(M, m0 + step)
+            native.check(lib.bnn_hip_blinear_grad_input_f32(
+                g[m0:m1].data_ptr(), w.alpha.data_ptr(), w.wbits.data_ptr(), w.wnz.data_ptr(), saved.T[m0:m1].data_ptr(),
+                gx[m0:m1].data_ptr(), m1 - m0, O, F, _stream(g.device)), "bnn_hip_blinear_grad_input_f32")
+    return gx
+
+
+def blinear_grad_weight_splits(M: int, O: int, F: int) -> int:
+    """The default row split of ``blinear_grad_weight`` (``bnn_hip_blinear_grad_weight_splits``)."""
+    s = int(native.require().bnn_hip_blinear_grad_weight_splits(M, O, F))
+    if s < 1:
+        native.check(s, "bnn_hip_blinear_grad_weight_splits")
+    return s
+
+
+def blinear_grad_weight(g: torch.Tensor, saved: "SavedAct", reduce: bool = True,
+                        splits: Optional[int] = None) -> torch.Tensor:
+    """dL/dWhat ``[O, F]`` of the binary Linear: ``sum_m g[m, o] sign(x)[m, f]`` from the sign planes of ``saved``.
+    ``reduce=False``: the kernel's partial slabs ``[splits, O, F]`` as they are (``xnor_weight_backward`` adds them itself).
+    ``splits=None``: the library's choice; a value of the caller's goes to the entry point as it is, which refuses one that
+    is not ``ceil(M / ceil(M / splits))``."""
+    g = _require_cuda_f32(g, "grad_output")
+    M, F, O = _linear_grad_shapes(g, saved)
+    g = g.reshape(M, O)
+    lib = native.require()
+    step = _linear_rows(M, F, O) if splits is None else M      # (a caller's split is one launch: the entry point judges it)
+    parts = []
+    with torch.cuda.device(g.device):
+        for m0 in range(0, M, step):
+            m1 = min(M, m0 + step)
+            sp = blinear_grad_weight_splits(m1 - m0, O, F) if splits is None else int(splits)
+            if sp < 1 or sp > m1 - m0:                 # (before `part` is sized by it)
+                native.check(native.ERR_INVALID_ARG, "bnn_hip_blinear_grad_weight_f32")
+            part = torch.empty((sp, O, F), dtype=torch.float32, device=g.device)
+            native.check(lib.bnn_hip_blinear_grad_weight_f32(
+                g[m0:m1].data_ptr(), saved.sign.P[m0:m1].data_ptr(), saved.sign.M[m0:m1].data_ptr(), part.data_ptr(), sp,
+                m1 - m0, O, F, _stream(g.device)), "bnn_hip_blinear_grad_weight_f32")
+            parts.append(part)
+    part = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+    if not reduce:
+        return part
+    return part[0] if part.shape[0] == 1 else part.sum(0)
+
+
+_BLINEAR_MIN_ROWS = 4096
+
+
+def blinear_preferred(M: int, F: int, O: int) -> bool:
+    """Whether ``linear`` runs the row-major kernel for this shape: where tools/bench_linear.py measured it not slower than
+    the 1x1-image route (profiles/linear_bench.jsonl; DESIGN.md section 4, "Linear").  Measured on an MI355X, blinear / conv
+    in us: every shape of 4096 rows and more wins (4096 x 768 -> 3072: 75 / 110; 8192 x 1024 -> 1024: 76 / 124; 16384 and
+    32768 rows: 0.27-0.41 of the conv route's time; 50176 x 768 -> 3072: 648 / 1469; 50176 x 3072 -> 768: 718 / 2501), the
+    small batches lose or tie (32 x 4096 -> 4096: 96 / 42; 1024 x 1024 -> 1024: 43.6 / 39.6; 256 x 512 -> 1000: 26.5 / 26.3:
+    a workgroup owns 64 rows, so few rows are few workgroups, each binarising its rows again for its share of the output
+    channels) and stay on the conv route; nothing between 1024 and 4096 rows was measured, so the threshold is the smallest
+    measured win."""
+    return M >= _BLINEAR_MIN_ROWS
+
+
+def linear(x: torch.Tensor, w: PackedWeight, bias: Optional[torch.Tensor] = None,
+           post_scale: Optional[torch.Tensor] = None, route: Optional[str] = None) -> torch.Tensor:
+    """``Linear.forward`` on ``[..., F]``: the row-major kernel (``blinear_direct``) where ``blinear_preferred`` says so,
+    else ``bconv2d_direct`` on 1 x 1 images — the same bits either way.  ``route``: ``None`` picks per shape; ``"blinear"``
+    / ``"conv"`` force one (tools, tests)."""
+    if route not in (None, "blinear", "conv"):
+        raise ValueError("route must be None, 'blinear' or 'conv'")
+    O, F = int(w.shape[0]), int(w.shape[1])
+    lead = tuple(x.shape[:-1])
+    x2 = x.reshape(-1, x.shape[-1])
+    if route == "blinear" or (route is None and x2.shape[0] > 0 and blinear_preferred(x2.shape[0], F, O)):
+        return blinear_direct(x2, w, bias, post_scale).reshape(*lead, O)
+    return bconv2d_direct(x2[:, :, None, None], w, bias, post_scale).reshape(*lead, O)
+
+
 def bn_act(x: torch.Tensor, bn_scale: torch.Tensor, bn_shift: torch.Tensor, relu: bool = False,
            residual: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``relu?(fma(x, scale[c], shift[c]) (+ residual))``: eval-mode BatchNorm with folded constants + the residual add +

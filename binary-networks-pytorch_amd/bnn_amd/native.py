@@ -192,6 +192,10 @@ _PROTOTYPES = {
     "bnn_hip_bconv2d_dot_route": (_i, [_conv_p, ctypes.POINTER(ConvRoute)]),
     "bnn_hip_bconv2d_dot": (_i, [_conv_p] + [_vp] * 6),
     "bnn_hip_blinear": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "bnn_hip_blinear_direct": (_i, [_i, _i, _i, _vp, _i, _vp, _vp, _i] + [_vp] * 7 + [_i, _vp]),
+    "bnn_hip_blinear_grad_input_f32": (_i, [_vp] * 6 + [_i, _i, _i, _vp]),
+    "bnn_hip_blinear_grad_weight_splits": (_i, [_i, _i, _i]),
+    "bnn_hip_blinear_grad_weight_f32": (_i, [_vp] * 4 + [_i, _i, _i, _i, _vp]),
     "bnn_hip_conv_workspace_bytes": (_sz, [_conv_p]),
     "bnn_hip_bconv2d_f32": (_i, [_conv_p] + [_vp] * 9),
     "bnn_hip_bconv2d_direct_plan": (_i, [_conv_p, ctypes.POINTER(FlyPlan)]),

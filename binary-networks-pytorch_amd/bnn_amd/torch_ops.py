@@ -15,7 +15,9 @@ path must (the layers' torch composition is what runs on CPU, not these ops).
 
 ``binary_conv2d`` has an autograd formula (``bnn_amd/training.py``: straight-through estimator for the
 input, the reference's XNOR weight binarizer differentiated by torch for the weight), so it can also
-stand in a training graph.
+stand in a training graph.  ``binary_linear`` has one too, on the kernels of ``csrc/blinear.hip`` (bf16 x 3
+matrix-core gradients from the weight pack and the bit planes, the fused weight hook), independent of
+``training.LINEAR``.
 """
 from __future__ import annotations
 
@@ -162,18 +164,53 @@ binary_conv2d.register_autograd(_conv_backward, setup_context=_conv_setup)
 @torch.library.custom_op(f"{_NS}::binary_linear", mutates_args=(), device_types="cuda")
 def binary_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
                   post_scale: Optional[torch.Tensor], center_weights: bool, compute_alpha: bool) -> torch.Tensor:
-    """``bnn.layers.Linear.forward`` (bnn/layers/linear.py:22-27) as a 1x1 convolution over 1x1 images."""
+    """``bnn.layers.Linear.forward`` (bnn/layers/linear.py:22-27): ``hipops.linear`` (the row-major kernel or a 1x1
+    convolution over 1x1 images, the same bits)."""
     _need_gpu(x, weight, bias, post_scale)
     pw = _packed(weight, center_weights, compute_alpha)
-    lead = x.shape[:-1]
-    x2 = x.reshape(-1, x.shape[-1])
-    out = hipops.bconv2d_direct(x2[:, :, None, None], pw, bias, post_scale)
-    return out.reshape(*lead, weight.shape[0])
+    return hipops.linear(x, pw, bias, post_scale)
 
 
 @binary_linear.register_fake
 def _(x, weight, bias, post_scale, center_weights, compute_alpha):
     return x.new_empty((*x.shape[:-1], weight.shape[0]), dtype=torch.float32)
+
+
+def _linear_setup(ctx, inputs, output):
+    x, weight, bias, post_scale, center, compute_alpha = inputs
+    ctx.save_for_backward(x, weight, post_scale, bias)
+    ctx.conf = (center, compute_alpha)
+
+
+def _linear_backward(ctx, g):
+    """The gradients of ``training.BinaryLinearTrainFn`` on the same kernels (csrc/blinear.hip); the operator has one
+    output, so the three bit planes are made here from the saved ``x``."""
+    x, weight, post_scale, bias = ctx.saved_tensors
+    center, compute_alpha = ctx.conf
+    pw = _packed(weight, center, compute_alpha)
+    O, F = weight.shape
+    g = g.reshape(-1, O).contiguous()
+    gs = None
+    if post_scale is not None:
+        if ctx.needs_input_grad[3]:      # d out / d post_scale = the pre-scale output, recomputed (see _conv_backward)
+            pre = hipops.linear(x, pw, bias, None).reshape(-1, O)
+            gs = (g * pre).sum(0).reshape(post_scale.shape)
+        g = g * post_scale.reshape(1, -1)
+    saved = hipops.pack_act_ste(x.reshape(-1, F).float()[:, :, None, None])
+    gx = gw = gb = None
+    if ctx.needs_input_grad[0]:
+        gx = hipops.blinear_grad_input(g, saved, pw).reshape(x.shape).to(x.dtype)
+    if ctx.needs_input_grad[1]:
+        gwhat = hipops.blinear_grad_weight(g, saved, reduce=False)
+        if gwhat.shape[0] > 16:
+            gwhat = gwhat.sum(0)
+        gw = hipops.xnor_weight_backward(weight.float(), gwhat, center, compute_alpha).to(weight.dtype)
+    if bias is not None and ctx.needs_input_grad[2]:
+        gb = g.sum(0).to(bias.dtype)
+    return gx, gw, gb, gs, None, None
+
+
+binary_linear.register_autograd(_linear_backward, setup_context=_linear_setup)
 
 
 OPS = ("pack_sign", "binary_conv2d", "binary_linear")

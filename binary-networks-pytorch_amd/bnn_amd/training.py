@@ -412,6 +412,69 @@ def conv2d_train(layer: nn.Module, x: torch.Tensor, plan, packed) -> torch.Tenso
     return out
 
 
+# ---- a binary Linear in a training step -----------------------------------------------------------------------------
+# `F.linear(sign(x), What)` under autograd is sign(x) materialised in fp32, a library fp32 GEMM, and the fp32 x and fp32
+# sign(x) kept alive.  `BinaryLinearTrainFn` is the layer as one autograd function on the kernels of csrc/blinear.hip:
+#   forward :  ONE launch (bnn_hip_blinear_direct) that also writes the three bit planes of x — all that is kept of it
+#   backward:  input gradient from the forward's weight pack and the mask plane, weight gradient from the sign planes as
+#              partial slabs (both bf16 x 3 on the matrix cores), the slabs through the fused weight hook
+# Off by default (its speed against the library's GEMMs is recorded in profiles/linear_bench.jsonl; the default is a later
+# decision); BNN_AMD_TRAIN_LINEAR=1 or `training.LINEAR = True` turns it on — read at every call
+# (fastpath.plan_linear_train).
+LINEAR = os.environ.get("BNN_AMD_TRAIN_LINEAR", "0") == "1"
+
+
+class BinaryLinearTrainFn(torch.autograd.Function):
+    """``wconf = (center, compute_alpha)``: ``w`` is the LATENT weight and the XNORWeightBinarizer is inside (as in
+    ``BinaryConv2dTrainFusedFn``); ``wconf = None``: ``w`` is ``What = weight_pre_process(W)``, made under autograd by the
+    caller."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, packed, wconf):
+        out, sv = hipops.blinear_direct(x, packed, bias, None, want_planes=True)
+        ctx.save_for_backward(sv.sign.P, sv.sign.M, sv.T, w)
+        ctx.packed, ctx.wconf, ctx.x_shape, ctx.has_bias = packed, wconf, tuple(x.shape), bias is not None
+        global _saved_bytes
+        _saved_bytes += sv.nbytes()
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        P, M, T, w = ctx.saved_tensors
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        shape = (P.shape[0], ctx.x_shape[-1], 1, 1)
+        saved = hipops.SavedAct(hipops.PackedAct(P, M, shape), T, shape)
+        g = g.reshape(-1, g.shape[-1]).contiguous()
+        gx = gw = gb = None
+        if need_x:
+            gx = hipops.blinear_grad_input(g, saved, ctx.packed).reshape(ctx.x_shape)      # STE mask fused
+        if need_w:
+            gwhat = hipops.blinear_grad_weight(g, saved, reduce=False)
+            if ctx.wconf is None:
+                gw = gwhat[0] if gwhat.shape[0] == 1 else gwhat.sum(0)
+            else:
+                if gwhat.shape[0] > 16:         # (see BinaryConv2dTrainFusedFn.backward)
+                    gwhat = gwhat.sum(0)
+                gw = hipops.xnor_weight_backward(w, gwhat, *ctx.wconf)
+        if need_b:
+            gb = g.sum(0)
+        return gx, gw, gb, None, None
+
+
+def linear_train(layer: nn.Module, x: torch.Tensor, plan, packed) -> torch.Tensor:
+    """``bnn.layers.Linear.forward`` with autograd recording (``fastpath.plan_linear_train`` admitted the layer)."""
+    w = layer.weight
+    if FUSED_WEIGHT_HOOK and w.dim() == 2 and w.is_contiguous():
+        out = BinaryLinearTrainFn.apply(x, w, layer.bias, packed, (bool(plan.center), bool(plan.compute_alpha)))
+    else:
+        w_hat = layer.weight_pre_process(w)                 # autograd edge to W (sign STE, alpha)
+        out = BinaryLinearTrainFn.apply(x, w_hat, layer.bias, packed, None)
+    if plan.scale is not None:                              # BasicScaleBinarizer (bnn/ops.py:200-202)
+        out = out * plan.scale
+    return out
+
+
 # ---- a whole BATS cell operation in a training step -----------------------------------------------------------------
 # SepConv / DilConv / ReLUConvBN (bnn_amd/models/bats_ops.py) evaluate  y = [x +] channel_shuffle(PReLU(conv(sign(bn(x)))), 4)
 # in train() mode as six steps (the library's BatchNorm, pack_act_ste, the convolution, torch PReLU, the shuffle's

@@ -221,6 +221,17 @@ int launch_grouped_wgrad(const GroupedGradP& q, const float* g, const uint64_t* 
 bool fly_supported(const ConvP& p);
 int fly_default_plan(const ConvP& p, int flags, bnn_hip_fly_plan* plan);
 int launch_bconv_fly(const ConvP& p, const void* x, int x_half, int flags, const bnn_hip_fly_plan* plan, hipStream_t s);
+// blinear.hip: the fully-connected layer on a row-major [M, F] input.  Forward from the float input (fp16 when x_half) in one
+// launch, P / Mn / T (all or none) receive the three bit planes [M][ceil(F/64)]; lds_words: 32-bit words per row of one LDS
+// pass over F (0 = default).  Gradients from the forward's weight pack and the planes (bf16 x 3 MFMA).
+int launch_blinear_fwd(const void* x, int x_half, const uint32_t* wbits, const uint32_t* wnz, int weight_zeros,
+                       const float* alpha, const float* bias, const float* scale, float* out, uint64_t* P, uint64_t* Mn,
+                       uint64_t* T, int M, int F, int O, int lds_words, hipStream_t s);
+int launch_blinear_dgrad(const float* g, const float* alpha, const uint32_t* wbits, const uint32_t* wnz, const uint64_t* T,
+                         float* gx, int M, int O, int F, hipStream_t s);
+int blinear_wgrad_splits(int M, int O, int F);
+int launch_blinear_wgrad(const float* g, const uint64_t* P, const uint64_t* Mn, float* part, int splits, int M, int O, int F,
+                         hipStream_t s);
 // hblock.hip: the hierarchical block in one launch
 bool hblock_supported(const bnn_hip_hblock_desc* d);
 int hblock_layout(int C_in, int planes, bnn_hip_hblock_layout* L);

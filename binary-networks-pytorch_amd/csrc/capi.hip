@@ -1004,6 +1004,65 @@ int bnn_hip_blinear(int B, int F, int O, const uint64_t* P, const uint64_t* M, c
   return bnn_hip_bconv2d(&d, P, M, wbits, wnz, alpha, bias, post_scale, out, stream);
 }
 
+// Entry contract of the GEMM-shaped Linear kernels (csrc/blinear.hip): positive sizes, M * F and M * O below 2^30 per launch
+// (the caller splits M), a weight whose 1x1 pack layout exists.
+static int check_linear(int M, int F, int O) {
+  if (M <= 0 || F <= 0 || O <= 0) return BNN_HIP_ERR_INVALID_ARG;
+  if (mulc(M, F) > kMaxConvElems || mulc(M, O) > kMaxConvElems) return BNN_HIP_ERR_TOO_LARGE;
+  bnn_hip_wlayout L;
+  return bnn_hip_weight_layout(O, F, 1, 1, &L);
+}
+
+int bnn_hip_blinear_direct(int M, int F, int O, const void* x, int x_dtype, const uint32_t* wbits, const uint32_t* wnz,
+                           int weight_zeros, const float* alpha, const float* bias, const float* post_scale, float* out,
+                           uint64_t* P, uint64_t* Mn, uint64_t* T, int lds_words, void* stream) {
+  if (!x || !wbits || !alpha || !out || lds_words < 0) return BNN_HIP_ERR_INVALID_ARG;
+  if (x_dtype != BNN_HIP_DTYPE_F32 && x_dtype != BNN_HIP_DTYPE_F16) return BNN_HIP_ERR_INVALID_ARG;
+  if (weight_zeros && !wnz) return BNN_HIP_ERR_INVALID_ARG;
+  if ((P == nullptr) != (Mn == nullptr) || (P == nullptr) != (T == nullptr)) return BNN_HIP_ERR_INVALID_ARG;
+  if (!aligned(x, x_dtype == BNN_HIP_DTYPE_F16 ? 2 : 4) || !aligned(wbits, 16) || !aligned(wnz, 16) || !aligned(alpha, 4) ||
+      !aligned(bias, 4) || !aligned(post_scale, 4) || !aligned(out, 4) || !aligned(P, 8) || !aligned(Mn, 8) || !aligned(T, 8))
+    return BNN_HIP_ERR_INVALID_ARG;
+  const int st = check_linear(M, F, O);
+  if (st != BNN_HIP_OK) return st;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_blinear_fwd(x, x_dtype == BNN_HIP_DTYPE_F16, wbits, wnz, weight_zeros != 0, alpha, bias, post_scale, out,
+                                 P, Mn, T, M, F, O, lds_words, static_cast<hipStream_t>(stream));
+}
+
+int bnn_hip_blinear_grad_input_f32(const float* g, const float* alpha, const uint32_t* wbits, const uint32_t* wnz,
+                                   const uint64_t* T, float* gx, int M, int O, int F, void* stream) {
+  if (!g || !alpha || !wbits || !wnz || !T || !gx) return BNN_HIP_ERR_INVALID_ARG;
+  if (!aligned(g, 4) || !aligned(alpha, 4) || !aligned(wbits, 16) || !aligned(wnz, 16) || !aligned(T, 8) || !aligned(gx, 4))
+    return BNN_HIP_ERR_INVALID_ARG;
+  const int st = check_linear(M, F, O);
+  if (st != BNN_HIP_OK) return st;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_blinear_dgrad(g, alpha, wbits, wnz, T, gx, M, O, F, static_cast<hipStream_t>(stream));
+}
+
+int bnn_hip_blinear_grad_weight_splits(int M, int O, int F) {
+  return check_linear(M, F, O) == BNN_HIP_OK ? bnn::blinear_wgrad_splits(M, O, F) : BNN_HIP_ERR_INVALID_ARG;
+}
+
+int bnn_hip_blinear_grad_weight_f32(const float* g, const uint64_t* P, const uint64_t* Mn, float* partial, int splits, int M,
+                                    int O, int F, void* stream) {
+  if (!g || !P || !Mn || !partial || !aligned(g, 4) || !aligned(P, 8) || !aligned(Mn, 8) || !aligned(partial, 4))
+    return BNN_HIP_ERR_INVALID_ARG;
+  const int st = check_linear(M, F, O);
+  if (st != BNN_HIP_OK) return st;
+  // the rule of bnn_hip_bconv_grad_weight_f32, checked here (a host-side decision): every split holds ceil(M / splits) rows,
+  // the last one what is left, none is empty
+  if (splits < 1 || splits > M) return BNN_HIP_ERR_INVALID_ARG;
+  const int per = (M + splits - 1) / splits;
+  if ((M + per - 1) / per != splits) return BNN_HIP_ERR_INVALID_ARG;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_blinear_wgrad(g, P, Mn, partial, splits, M, O, F, static_cast<hipStream_t>(stream));
+}
+
 // Geometry part of a ConvP for the one-launch layer (no packed operands).
 static int fly_convp(const bnn_hip_conv_desc* d, bnn::ConvP* out) {
   int Ho = 0, Wo = 0;

@@ -63,6 +63,8 @@ extern "C" {
 
 /* ABI 16: + bnn_hip_bconv2d_route, bnn_hip_bconv2d_dot_route and bnn_hip_conv_route (which kernel a convolution runs:
  * host-only queries answered by the launch ladder itself; no other struct or signature changed).
+ * Additive entry points of ABI 16 for the fully-connected layer (no struct or signature changed): + bnn_hip_blinear_direct,
+ * bnn_hip_blinear_grad_input_f32, bnn_hip_blinear_grad_weight_f32, bnn_hip_blinear_grad_weight_splits (csrc/blinear.hip).
  * Additive entry points of ABI 15 for the training step of FactorizedReduce (no struct or signature changed):
  * + bnn_hip_bn_act_pack_ste_s2_f32, bnn_hip_bn_train_pack_ste_s2_f32 (the three bit planes of the two pixel lattices its
  * convolutions read); + bnn_hip_bn_train_backward_s2_f32 (the BatchNorm backward of a gradient that lives on those lattices).
@@ -691,6 +693,41 @@ int bnn_hip_blinear(int B, int F, int O,
                     const uint32_t* wbits, const uint32_t* wnz, int weight_zeros,
                     const float* alpha, const float* bias, const float* post_scale,
                     float* out, void* stream);
+
+/* ---- Linear as GEMM-shaped kernels (additive, ABI 16): bnn.layers.Linear.forward (bnn/layers/linear.py:22-27) from the
+ * FLOAT input in one launch, and its two gradients under the straight-through estimator (bnn/ops.py:68-73).  Leading
+ * dimensions are flattened by the caller: x is row-major [M, F].  The weight is the 1x1 pack of bnn_hip_pack_weight_f32
+ * (O, F, 1, 1).  Sizes: M, F, O > 0; M * F and M * O below 2^30 per launch (BNN_HIP_ERR_TOO_LARGE: split M); more than
+ * 65535 * 256 features or 65535 * 64 output channels: BNN_HIP_ERR_UNSUPPORTED.
+ *
+ *   bnn_hip_blinear_direct          out[m,o] = fmaf(alpha[o], dot(sign(x[m,:]), sign(Wc[o,:])), bias[o]) [* post_scale[o]]:
+ *                                   the bits of bnn_hip_bconv2d_direct / bnn_hip_blinear on the same operands.  x: fp32
+ *                                   (4-byte aligned) or fp16 (2-byte aligned), x_dtype = BNN_HIP_DTYPE_*; wbits / wnz
+ *                                   16-byte aligned, wnz may be NULL unless weight_zeros; bias / post_scale may be NULL;
+ *                                   out fp32 [M,O].  P, Mn, T: all NULL, or all three 8-byte aligned [M][ceil(F/64)]
+ *                                   words that receive x > 0, x < 0 and |x| < 1 — the planes of bnn_hip_pack_act_ste_f32
+ *                                   with H = W = 1, pad bits of the last word 0 — from the same pass over x.
+ *                                   lds_words: 32-bit words per row that one LDS pass over F holds (rounded down to the
+ *                                   pack's chunk, at least one chunk); 0 = the default (128).  Same bits for any value.
+ *   bnn_hip_blinear_grad_input_f32  gx[m,f] = 1[|x[m,f]| < 1] * sum_o g[m,o] alpha[o] sign(Wc)[o,f]; g fp32 [M,O], alpha
+ *                                   [O], wbits AND wnz of the forward's pack (16-byte aligned), T the mask plane of
+ *                                   the forward (8-byte aligned), gx fp32 [M,F].  g' = alpha g is rounded once in fp32 and
+ *                                   split into three bf16 terms; v_mfma_f32_16x16x32_bf16, fp32 accumulation.
+ *   bnn_hip_blinear_grad_weight_f32 partial[s,o,f] = sum over the rows m of split s of g[m,o] sign(x)[m,f] from the P / Mn
+ *                                   planes (8-byte aligned); partial fp32 [splits,O,F].  Split s holds rows
+ *                                   [s * per, min(M, (s+1) * per)), per = ceil(M / splits); a `splits` outside 1..M or
+ *                                   with ceil(M / per) != splits is BNN_HIP_ERR_INVALID_ARG (the rule of
+ *                                   bnn_hip_bconv_grad_weight_f32).  bnn_hip_blinear_grad_weight_splits returns the default
+ *                                   (a valid one), or BNN_HIP_ERR_INVALID_ARG for sizes the kernels reject.  The slabs go to
+ *                                   bnn_hip_xnor_weight_backward_f32 as they are.                                          */
+int bnn_hip_blinear_direct(int M, int F, int O, const void* x, int x_dtype, const uint32_t* wbits, const uint32_t* wnz,
+                           int weight_zeros, const float* alpha, const float* bias, const float* post_scale, float* out,
+                           uint64_t* P, uint64_t* Mn, uint64_t* T, int lds_words, void* stream);
+int bnn_hip_blinear_grad_input_f32(const float* g, const float* alpha, const uint32_t* wbits, const uint32_t* wnz,
+                                   const uint64_t* T, float* gx, int M, int O, int F, void* stream);
+int bnn_hip_blinear_grad_weight_splits(int M, int O, int F);
+int bnn_hip_blinear_grad_weight_f32(const float* g, const uint64_t* P, const uint64_t* Mn, float* partial, int splits, int M,
+                                    int O, int F, void* stream);
 
 /* ---- The LAYER in one launch (ABI 10): bnn.layers.Conv2d.forward (bnn/layers/conv.py:90-97) from the float
  * activation tensor to the float output, sign(x) (bnn/ops.py:63-66,151-152) computed ON THE FLY inside the

@@ -343,6 +343,33 @@ int launch_wgrad(const float* g, const void* x, const void* x2, int planes, floa
   ++g_reached; REQUIRE(g && x && part && (!planes || (x2 && al(x, 8) && al(x2, 8)))); check_grad(N, O, C, H, W, ks, stride);
   return BNN_HIP_OK;
 }
+static void check_linear(int M, int F, int O) {
+  REQUIRE(M > 0 && F > 0 && O > 0 && (long long)M * F <= (1LL << 30) - 1 && (long long)M * O <= (1LL << 30) - 1);
+  REQUIRE(((long long)O + 31) / 32 * 32 * (2 * (((long long)F + 63) / 64)) <= (1LL << 31) - 1);
+}
+int launch_blinear_fwd(const void* x, int x_half, const uint32_t* wb, const uint32_t* wz, int zeros, const float* alpha,
+                       const float* bias, const float* scale, float* out, uint64_t* P, uint64_t* Mn, uint64_t* T, int M, int F,
+                       int O, int lds_words, hipStream_t) {
+  ++g_reached; check_linear(M, F, O);
+  REQUIRE(x && wb && alpha && out && al(x, x_half ? 2 : 4) && al(wb, 16) && al(wz, 16) && (!zeros || wz) && al(bias, 4) &&
+          al(scale, 4) && al(out, 4) && lds_words >= 0);
+  REQUIRE((P == nullptr) == (Mn == nullptr) && (P == nullptr) == (T == nullptr) && al(P, 8) && al(Mn, 8) && al(T, 8));
+  return BNN_HIP_OK;
+}
+int launch_blinear_dgrad(const float* g, const float* alpha, const uint32_t* wb, const uint32_t* wz, const uint64_t* T,
+                         float* gx, int M, int O, int F, hipStream_t) {
+  ++g_reached; check_linear(M, F, O);
+  REQUIRE(g && alpha && wb && wz && T && gx && al(wb, 16) && al(wz, 16) && al(T, 8) && al(g, 4) && al(gx, 4));
+  return BNN_HIP_OK;
+}
+int blinear_wgrad_splits(int M, int O, int F) { check_linear(M, F, O); return 1; }
+int launch_blinear_wgrad(const float* g, const uint64_t* P, const uint64_t* Mn, float* part, int splits, int M, int O, int F,
+                         hipStream_t) {
+  ++g_reached; check_linear(M, F, O);
+  REQUIRE(g && P && Mn && part && al(P, 8) && al(Mn, 8) && al(g, 4) && al(part, 4));
+  REQUIRE(splits >= 1 && splits <= M && (M + (M + splits - 1) / splits - 1) / ((M + splits - 1) / splits) == splits);
+  return BNN_HIP_OK;
+}
 int launch_pack_weight(const float* w, int O, int C, int KH, int KW, int, int, const bnn_hip_wlayout& L, uint32_t* wb,
                        uint32_t* wz, float* alpha, int32_t* flag, hipStream_t) {
   ++g_reached;
@@ -910,6 +937,23 @@ int main(int argc, char** argv) {
         st = bnn_hip_blinear(pick_int(), pick_int(), pick_int(), pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<uint32_t>(),
                              pick_ptr<uint32_t>(), pick_int(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(),
                              pick_ptr<float>(), stream);
+        { // the GEMM-shaped Linear entry points (csrc/blinear.hip)
+          const int s1 = bnn_hip_blinear_direct(pick_int(), pick_int(), pick_int(), pick_ptr<float>(), (int)(rnd() % 3),
+                                                pick_ptr<uint32_t>(), pick_ptr<uint32_t>(), pick_int(), pick_ptr<float>(),
+                                                pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<uint64_t>(),
+                                                pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), rnd() % 4 ? (int)(rnd() % 200) : pick_int(),
+                                                stream);
+          const int s2 = bnn_hip_blinear_grad_input_f32(pick_ptr<float>(), pick_ptr<float>(), pick_ptr<uint32_t>(),
+                                                        pick_ptr<uint32_t>(), pick_ptr<uint64_t>(), pick_ptr<float>(), pick_int(),
+                                                        pick_int(), pick_int(), stream);
+          const int M = pick_int(), O = pick_int(), F = pick_int();
+          const int sp = bnn_hip_blinear_grad_weight_splits(M, O, F);
+          if (sp != BNN_HIP_ERR_INVALID_ARG && (sp < 1 || sp > M)) broken("default split of the Linear weight gradient");
+          const int s3 = bnn_hip_blinear_grad_weight_f32(pick_ptr<float>(), pick_ptr<uint64_t>(), pick_ptr<uint64_t>(),
+                                                         pick_ptr<float>(), rnd() % 2 ? sp : pick_int(), M, O, F, stream);
+          if (!status_ok(s1) || !status_ok(s2) || !status_ok(s3)) broken("blinear status");
+          digest = (digest ^ (uint64_t)(uint32_t)s1 ^ ((uint64_t)(uint32_t)s2 << 16) ^ ((uint64_t)(uint32_t)s3 << 32)) * 0x100000001B3ull;
+        }
         break; }
     }
     if (!status_ok(st)) { std::fprintf(stderr, "unknown status %d\n", st); return 2; }
