@@ -185,10 +185,7 @@ def plan_linear_train(layer, x: torch.Tensor) -> Optional[Plan]:
     plan = _recognise(layer, layer.out_features)
     if plan is None or not plan.ste or not _eligible_train(layer, x):
         return None
-    wpre = layer.weight_pre_process
-    if wpre._forward_hooks or wpre._forward_pre_hooks:
-        return None
-    return plan
+    return plan if training._no_hooks(layer.weight_pre_process, backward=False) else None
 
 
 def packed_weight(layer, plan: Plan, sync: bool = True, fresh: bool = False) -> hipops.PackedWeight:

@@ -16,8 +16,8 @@ path must (the layers' torch composition is what runs on CPU, not these ops).
 ``binary_conv2d`` has an autograd formula (``bnn_amd/training.py``: straight-through estimator for the
 input, the reference's XNOR weight binarizer differentiated by torch for the weight), so it can also
 stand in a training graph.  ``binary_linear`` has one too, on the kernels of ``csrc/blinear.hip`` (bf16 x 3
-matrix-core gradients from the weight pack and the bit planes, the fused weight hook), independent of
-``training.LINEAR``.
+matrix-core gradients from the weight pack and the bit planes, the fused weight hook:
+``training.blinear_backward``), independent of ``training.LINEAR``.
 """
 from __future__ import annotations
 
@@ -28,7 +28,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from . import hipops, native
+from . import hipops, native, training
 
 _NS = "bnn_amd"
 
@@ -183,8 +183,9 @@ def _linear_setup(ctx, inputs, output):
 
 
 def _linear_backward(ctx, g):
-    """The gradients of ``training.BinaryLinearTrainFn`` on the same kernels (csrc/blinear.hip); the operator has one
-    output, so the three bit planes are made here from the saved ``x``."""
+    """``training.blinear_backward`` — the gradients of ``training.BinaryLinearTrainFn`` with the fused weight hook — and
+    what is the operator's own: it has one output, so the three bit planes are made here from the saved ``x``; the
+    ``post_scale`` gradient; the casts back to the inputs' dtypes."""
     x, weight, post_scale, bias = ctx.saved_tensors
     center, compute_alpha = ctx.conf
     pw = _packed(weight, center, compute_alpha)
@@ -197,17 +198,10 @@ def _linear_backward(ctx, g):
             gs = (g * pre).sum(0).reshape(post_scale.shape)
         g = g * post_scale.reshape(1, -1)
     saved = hipops.pack_act_ste(x.reshape(-1, F).float()[:, :, None, None])
-    gx = gw = gb = None
-    if ctx.needs_input_grad[0]:
-        gx = hipops.blinear_grad_input(g, saved, pw).reshape(x.shape).to(x.dtype)
-    if ctx.needs_input_grad[1]:
-        gwhat = hipops.blinear_grad_weight(g, saved, reduce=False)
-        if gwhat.shape[0] > 16:
-            gwhat = gwhat.sum(0)
-        gw = hipops.xnor_weight_backward(weight.float(), gwhat, center, compute_alpha).to(weight.dtype)
-    if bias is not None and ctx.needs_input_grad[2]:
-        gb = g.sum(0).to(bias.dtype)
-    return gx, gw, gb, gs, None, None
+    gx, gw = training.blinear_backward(g, saved, pw, weight.float(), (center, compute_alpha), *ctx.needs_input_grad[:2])
+    gb = g.sum(0).to(bias.dtype) if bias is not None and ctx.needs_input_grad[2] else None
+    return (None if gx is None else gx.reshape(x.shape).to(x.dtype), None if gw is None else gw.to(weight.dtype), gb, gs,
+            None, None)
 
 
 binary_linear.register_autograd(_linear_backward, setup_context=_linear_setup)

@@ -22,11 +22,28 @@ forward (``fastpath.packed_weight(..., fresh=True)``).  The forward is ONE launc
 autograd keeps alive; the gradient kernels read the planes (``bnn_hip_bconv_grad_*_packed_f32``) and return the same
 bits as from the fp32 tensor.
 
-Grouped and depthwise layers (``groups > 1``: the BATS cells' ``SepConv`` / ``DilConv``) take the same two autograd
-functions under ``GROUPED``: ``pack_act_ste`` + ``bnn_hip_bconv2d_grouped`` forward, and — where
+Grouped and depthwise layers (``groups > 1``: the BATS cells' ``SepConv`` / ``DilConv``) take the same autograd
+function under ``GROUPED``: ``pack_act_ste`` + ``bnn_hip_bconv2d_grouped`` forward, and — where
 ``hipops.grouped_grad_supported`` says so — the fp32 VALU gradient kernels of ``csrc/grad_grouped.hip`` on the three bit
 planes, which are then ALL that is kept of the input; other grouped geometries keep the fp32 ``x`` for
 ``aten::convolution_backward`` with ``groups``.
+
+The backward of a binary layer is written ONCE and every autograd function of this module calls it
+(``BinaryConv2dTrainFn``, ``CellOpTrainFn``, both phases of ``ReduceTrainFn``; ``BinaryLinearTrainFn`` and the operator
+``torch.ops.bnn_amd.binary_linear`` for a ``Linear``):
+
+    _bconv_backward / blinear_backward(g, kept input, weight, ..., wconf) -> (gx, gw)
+        sign fragments of the weight (dense) or the fp32 What (grouped; a Linear reads the forward's pack)
+        -> the input-gradient kernel, STE mask fused
+        -> the weight-gradient kernel's split-K slabs
+        -> ``_weight_grad_from_slabs``: more than 16 slabs added first, then ``xnor_weight_backward``
+
+``wconf = (center, compute_alpha)``: the weight is the LATENT one and the XNORWeightBinarizer is inside (the fused weight
+hook, ``FUSED_WEIGHT_HOOK``); ``wconf = None``: the weight is ``What = weight_pre_process(W)``, made under autograd by the
+caller, and the slabs are summed into dL/dWhat.  What a forward keeps of its input as bit planes goes through ``_keep`` /
+``_kept`` (which also counts ``saved_input_bytes``), and the rules by which ``cell_op_train`` / ``reduce_train`` /
+``conv2d_train`` / ``linear_train`` / ``bn_act_applies`` admit a module are the named predicates ``_batch_stat_bn``,
+``_fusable_binary_conv``, ``_fused_weight_hook``, ``_f32_on_one_device`` and ``_no_hooks``.
 
 Data-parallel training is ordinary ``DistributedDataParallel`` over RCCL (backend ``"nccl"``), one
 process per GPU: the binary layers are ``nn.Module``s with ordinary fp32 Parameters, so gradient
@@ -71,8 +88,71 @@ def saved_input_bytes(reset: bool = False) -> int:
 GROUPED = os.environ.get("BNN_AMD_TRAIN_GROUPED", "0") == "1"
 
 
+def _keep(ctx, acts, *tensors, nbytes: int = 0) -> None:
+    """Save the bit planes of the ``SavedAct``s ``acts`` and then ``tensors`` on ``ctx`` for ``_kept``, and count the
+    planes' bytes (plus ``nbytes``: an fp32 input kept in their place) into ``saved_input_bytes``."""
+    global _saved_bytes
+    ctx.save_for_backward(*[t for sv in acts for t in (sv.sign.P, sv.sign.M, sv.T)], *tensors)
+    ctx.act_shapes = [tuple(sv.shape) for sv in acts]
+    _saved_bytes += nbytes + sum(sv.nbytes() for sv in acts)
+
+
+def _kept(ctx):
+    """``(acts, tensors)`` as ``_keep`` was given them."""
+    ts, shapes = ctx.saved_tensors, ctx.act_shapes
+    acts = [hipops.SavedAct(hipops.PackedAct(ts[3 * i], ts[3 * i + 1], shape), ts[3 * i + 2], shape)
+            for i, shape in enumerate(shapes)]
+    return acts, ts[3 * len(shapes):]
+
+
+def _weight_grad_from_slabs(w, slabs, wconf):
+    """dL/dW of the latent weight ``w`` from the split-K slabs ``[splits, *w.shape]`` of dL/dWhat, through the fused
+    weight hook."""
+    # up to 16 slabs are added inside the hook's kernel (one workgroup per output channel walks them), the hundreds of a
+    # 64-channel layer by the library's parallel reduction
+    if slabs.shape[0] > 16:
+        slabs = slabs.sum(0)
+    return hipops.xnor_weight_backward(w, slabs, *wconf)
+
+
+def _bconv_backward(g, x, w, geom, need_x, need_w, wconf):
+    """``(gx, gw)`` of one binary convolution on the binary-aware kernels.  ``x``: the kept input (fp32, or its
+    ``SavedAct``; a grouped layer keeps planes only); ``geom = (groups, stride, padding, dilation)`` picks the dense or the
+    grouped kernels; ``wconf``: module docstring (``gw`` is dL/dW with it, dL/dWhat without)."""
+    groups, stride = geom[0], geom[1]
+    latent = wconf is not None
+    gx = gw = None
+    if groups != 1:
+        if need_x:      # the grouped kernel reads the fp32 What (wave-uniform per group), not sign fragments
+            gx = hipops.bconv_grouped_grad_input(g, x, hipops.xnor_what(w, *wconf) if latent else w, *geom)  # STE mask fused
+        if need_w:
+            gw = hipops.bconv_grouped_grad_weight(g, x, w.shape, *geom, reduce=not latent)
+    else:
+        if need_x:      # (latent: one launch, the same bytes)
+            packed, alpha = hipops.xnor_grad_pack_weight(w, *wconf) if latent else hipops.grad_pack_weight(w)
+            gx = hipops.bconv_grad_input(g, x, packed, alpha, w.shape[2], stride[0])               # STE mask fused
+        if need_w:
+            gw = hipops.bconv_grad_weight(g, x, w.shape[2], stride[0], reduce=not latent)
+    if need_w and latent:
+        gw = _weight_grad_from_slabs(w, gw, wconf)
+    return gx, gw
+
+
+def blinear_backward(g, saved, packed, w, wconf, need_x, need_w):
+    """``(gx, gw)`` of one binary ``Linear``: ``g`` as ``[M, O]``, ``saved`` the planes of the ``[M, F]`` input, ``packed``
+    the forward's weight pack; ``gx`` is ``[M, F]``.  ``wconf``: module docstring."""
+    gx = gw = None
+    if need_x:
+        gx = hipops.blinear_grad_input(g, saved, packed)                                           # STE mask fused
+    if need_w:
+        gw = hipops.blinear_grad_weight(g, saved, reduce=wconf is None)
+        if wconf is not None:
+            gw = _weight_grad_from_slabs(w, gw, wconf)
+    return gx, gw
+
+
 def _forward_and_keep(ctx, x, w, bias, layer, packed):
-    """Forward of both autograd functions, and what they keep of ``x`` for the backward (``w``: the tensor saved next to
+    """Forward of ``BinaryConv2dTrainFn``, and what it keeps of ``x`` for the backward (``w``: the tensor saved next to
     it).  Dense layer: ONE launch, the fp32 ``x`` kept — or, ``PACKED_STATE``, its three bit planes where the gradient
     kernels cover the geometry.  Grouped layer: the planes are made first (the forward reads the sign planes) and are
     ALL that is kept where the grouped gradient kernels cover the geometry; otherwise the fp32 ``x`` for the library's
@@ -92,32 +172,11 @@ def _forward_and_keep(ctx, x, w, bias, layer, packed):
             # reference's autograd keeps alive until the backward)
             sv = hipops.pack_act_ste(x)
     if planes:
-        ctx.save_for_backward(sv.sign.P, sv.sign.M, sv.T, w)
-        ctx.x_shape = tuple(x.shape)
-        kept = sv.nbytes()
+        _keep(ctx, [sv], w)
     else:
-        ctx.save_for_backward(x, w)
-        ctx.x_shape = None
-        kept = x.numel() * x.element_size()
-    global _saved_bytes
-    _saved_bytes += kept
+        _keep(ctx, [], x, w, nbytes=x.numel() * x.element_size())
     ctx.groups = groups
     return out, (stride, padding, dilation)
-
-
-def _kept_input(ctx):
-    """``(x, w)`` of ``_forward_and_keep``: ``x`` is the fp32 input or the ``SavedAct`` of its planes."""
-    if ctx.x_shape is None:
-        return ctx.saved_tensors
-    P, M, T, w = ctx.saved_tensors
-    return hipops.SavedAct(hipops.PackedAct(P, M, ctx.x_shape), T, ctx.x_shape), w
-
-
-def _binary_grads(ctx, x, w_shape, stride, padding, dilation) -> bool:
-    """Whether the backward runs on the binary-aware kernels: always when only the planes were kept, else for a dense
-    layer they cover (a grouped layer that kept its fp32 input takes the library's backward)."""
-    return ctx.x_shape is not None or (
-        ctx.groups == 1 and BINARY_GRADS and hipops.grad_supported(x.shape, w_shape, stride, padding, dilation))
 
 
 def _library_backward(ctx, g, x, w_hat, conf, need):
@@ -132,36 +191,33 @@ def _library_backward(ctx, g, x, w_hat, conf, need):
 
 
 class BinaryConv2dTrainFn(torch.autograd.Function):
+    """``wconf``: module docstring (``w`` is the latent weight with it, ``What`` without)."""
+
     @staticmethod
-    def forward(ctx, x, w_hat, bias, layer, plan, packed):
-        out, (stride, padding, dilation) = _forward_and_keep(ctx, x, w_hat, bias, layer, packed)
+    def forward(ctx, x, w, bias, layer, packed, wconf):
+        out, (stride, padding, dilation) = _forward_and_keep(ctx, x, w, bias, layer, packed)
         ctx.conf = (stride, padding, dilation, bias is not None, None if bias is None else tuple(bias.shape))
+        ctx.wconf = wconf
         return out
 
     @staticmethod
     def backward(ctx, g):
         stride, padding, dilation, has_bias, bias_shape = ctx.conf
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]
-        x, w_hat = _kept_input(ctx)
+        acts, rest = _kept(ctx)
+        x, w = (acts[0], rest[0]) if acts else rest     # x: the fp32 input, or the SavedAct of its planes
+        wconf = ctx.wconf
         g = g.contiguous()
-        if _binary_grads(ctx, x, w_hat.shape, stride, padding, dilation):
-            gx = gw = gb = None
-            if ctx.groups != 1:
-                geom = (ctx.groups, stride, padding, dilation)
-                if need_x:
-                    gx = hipops.bconv_grouped_grad_input(g, x, w_hat, *geom)                # STE mask fused
-                if need_w:
-                    gw = hipops.bconv_grouped_grad_weight(g, x, w_hat.shape, *geom)
-            else:
-                if need_x:
-                    packed, alpha = hipops.grad_pack_weight(w_hat)
-                    gx = hipops.bconv_grad_input(g, x, packed, alpha, w_hat.shape[2], stride[0])   # STE mask fused
-                if need_w:
-                    gw = hipops.bconv_grad_weight(g, x, w_hat.shape[2], stride[0])
-            if need_b:
-                gb = g.sum(dim=(0, 2, 3))
-            return gx, gw, gb, None, None, None
-        gx, gw, gb = _library_backward(ctx, g, x, w_hat, ctx.conf, (need_x, need_w, need_b))
+        # the binary-aware kernels: always when only the planes were kept, else for a dense layer they cover (a grouped
+        # layer that kept its fp32 input takes the library's backward)
+        if acts or (ctx.groups == 1 and BINARY_GRADS and hipops.grad_supported(x.shape, w.shape, stride, padding, dilation)):
+            gx, gw = _bconv_backward(g, x, w, (ctx.groups, stride, padding, dilation), need_x, need_w, wconf)
+            gb = g.sum(dim=(0, 2, 3)) if need_b else None
+        else:
+            what = w if wconf is None else hipops.xnor_what(w, *wconf)
+            gx, gw, gb = _library_backward(ctx, g, x, what, ctx.conf, (need_x, need_w, need_b))
+            if need_w and wconf is not None:
+                gw = _weight_grad_from_slabs(w, gw[None], wconf)        # (one slab)
         return (gx if need_x else None, gw if need_w else None, gb if need_b else None, None, None, None)
 
 
@@ -215,16 +271,31 @@ def _momentum(bn: nn.BatchNorm2d) -> float:
     return float(bn.momentum)
 
 
+def _no_hooks(*modules, backward: bool = True) -> bool:
+    """None of ``modules`` (``None`` entries skipped) carries a forward or forward-pre hook — nor, ``backward``, a
+    backward or backward-pre hook: a fused op that stands in for the modules would not fire them."""
+    return not any(m._forward_hooks or m._forward_pre_hooks or (backward and (m._backward_hooks or m._backward_pre_hooks))
+                   for m in modules if m is not None)
+
+
+def _f32_on_one_device(x: torch.Tensor, *tensors) -> bool:
+    """``x`` and ``tensors`` are fp32 on the HIP device of ``x``."""
+    return all(t.is_cuda and t.device == x.device and t.dtype == torch.float32 for t in (x, *tensors))
+
+
+def _batch_stat_bn(bn) -> bool:
+    """A stock ``nn.BatchNorm2d`` (no subclass) in training mode that normalises with batch statistics and has both
+    running statistics for the kernels to update."""
+    return (type(bn) is nn.BatchNorm2d and bn.training and bn.track_running_stats and bn.running_mean is not None
+            and bn.running_var is not None)
+
+
 def bn_act_applies(bn: nn.Module, act, x: torch.Tensor) -> bool:
-    """The fused op stands in for ``act(bn(x) [+ identity])`` iff: training mode with batch statistics, a stock
-    ``nn.BatchNorm2d`` with running statistics, ``act`` None or a stock ``nn.ReLU``, fp32 NCHW on a HIP device, autograd
-    recording, and no forward hooks on either module (they would not fire)."""
-    return (FUSED_BN and ENABLED and type(bn) is nn.BatchNorm2d and bn.training and bn.track_running_stats
-            and bn.running_mean is not None and (act is None or type(act) is nn.ReLU)
-            and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and torch.is_grad_enabled()
-            and (bn.weight is None or bn.weight.dtype == torch.float32)
-            and not bn._forward_hooks and not bn._forward_pre_hooks
-            and (act is None or (not act._forward_hooks and not act._forward_pre_hooks)))
+    """The fused op stands in for ``act(bn(x) [+ identity])`` iff: ``_batch_stat_bn``, ``act`` None or a stock
+    ``nn.ReLU``, fp32 NCHW on a HIP device, autograd recording, and no forward hooks on either module."""
+    return (FUSED_BN and ENABLED and _batch_stat_bn(bn) and (act is None or type(act) is nn.ReLU)
+            and _f32_on_one_device(x) and x.dim() == 4 and torch.is_grad_enabled()
+            and (bn.weight is None or bn.weight.dtype == torch.float32) and _no_hooks(bn, act, backward=False))
 
 
 def bn_act(x: torch.Tensor, bn: nn.BatchNorm2d, act=None, residual=None) -> torch.Tensor:
@@ -294,10 +365,8 @@ def stem_conv_applies(conv: nn.Module, x: torch.Tensor) -> bool:
             and conv.in_channels == 3 and conv.out_channels == 64 and tuple(conv.kernel_size) == (7, 7)
             and tuple(conv.stride) == (2, 2) and tuple(conv.padding) == (3, 3) and tuple(conv.dilation) == (1, 1)
             and conv.groups == 1 and conv.bias is None and conv.padding_mode == "zeros"
-            and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()
-            and conv.weight.dtype == torch.float32 and torch.is_grad_enabled()
-            and not conv._forward_hooks and not conv._forward_pre_hooks and not conv._backward_hooks
-            and not conv._backward_pre_hooks          # (they would not fire on the fused path)
+            and _f32_on_one_device(x) and x.dim() == 4 and x.is_contiguous()
+            and conv.weight.dtype == torch.float32 and torch.is_grad_enabled() and _no_hooks(conv)
             and not torch.is_autocast_enabled())      # (under AMP the reference's conv returns fp16: the module itself)
 
 
@@ -314,7 +383,7 @@ def stem_tail(x: torch.Tensor, bn: nn.Module, act: nn.Module, pool: nn.Module) -
     if (bn_act_applies(bn, act, x) and act is not None and type(pool) is nn.MaxPool2d
             and pool.kernel_size in (3, (3, 3)) and pool.stride in (2, (2, 2)) and pool.padding in (1, (1, 1))
             and pool.dilation in (1, (1, 1)) and not pool.ceil_mode and not pool.return_indices
-            and not pool._forward_hooks and not pool._forward_pre_hooks):
+            and _no_hooks(pool, backward=False)):
         return StemTailFn.apply(x, bn.weight, bn.bias, bn)[0]
     return pool(bn_act(x, bn, act))
 
@@ -339,9 +408,9 @@ def shortcut_pool(x: torch.Tensor, pool: nn.Module) -> torch.Tensor:
     a HIP device under autograd, else the module itself."""
     if (FUSED_SHORTCUT_POOL and ENABLED and type(pool) is nn.AvgPool2d and pool.kernel_size in (2, (2, 2))
             and pool.stride in (2, (2, 2)) and pool.padding in (0, (0, 0)) and pool.divisor_override is None
-            and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
+            and _f32_on_one_device(x) and x.dim() == 4 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
             and torch.is_grad_enabled() and x.requires_grad
-            and not pool._forward_hooks and not pool._forward_pre_hooks and not pool._backward_hooks):
+            and _no_hooks(pool, backward=False) and not pool._backward_hooks):   # (backward-pre hooks were never asked)
         return AvgPool2x2Fn.apply(x)
     return pool(x)
 
@@ -352,62 +421,24 @@ def shortcut_pool(x: torch.Tensor, pool: nn.Module) -> torch.Tensor:
 FUSED_WEIGHT_HOOK = os.environ.get("BNN_AMD_TRAIN_FUSED_WEIGHT_HOOK", "1") == "1"
 
 
-class BinaryConv2dTrainFusedFn(torch.autograd.Function):
-    """``BinaryConv2dTrainFn`` with the XNORWeightBinarizer inside: inputs are x and the LATENT weight W."""
-
-    @staticmethod
-    def forward(ctx, x, w, bias, layer, plan, packed):
-        out, (stride, padding, dilation) = _forward_and_keep(ctx, x, w, bias, layer, packed)
-        ctx.conf = (stride, padding, dilation, bias is not None, None if bias is None else tuple(bias.shape),
-                    bool(plan.center), bool(plan.compute_alpha))
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        stride, padding, dilation, has_bias, bias_shape, center, compute_alpha = ctx.conf
-        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]
-        x, w = _kept_input(ctx)
-        g = g.contiguous()
-        gx = gwhat = gb = None
-        if _binary_grads(ctx, x, w.shape, stride, padding, dilation):
-            if ctx.groups != 1:
-                geom = (ctx.groups, stride, padding, dilation)
-                if need_x:      # the grouped kernel reads the fp32 What (wave-uniform per group), not sign fragments
-                    gx = hipops.bconv_grouped_grad_input(g, x, hipops.xnor_what(w, center, compute_alpha), *geom)
-                if need_w:
-                    gwhat = hipops.bconv_grouped_grad_weight(g, x, w.shape, *geom, reduce=False)
-            else:
-                if need_x:
-                    packed, alpha = hipops.xnor_grad_pack_weight(w, center, compute_alpha)   # (one launch, the same bytes)
-                    gx = hipops.bconv_grad_input(g, x, packed, alpha, w.shape[2], stride[0])       # STE mask fused
-                if need_w:
-                    gwhat = hipops.bconv_grad_weight(g, x, w.shape[2], stride[0], reduce=False)
-            # the split-K slabs: up to 16 are added inside the hook's kernel (one workgroup per output channel walks them),
-            # the hundreds of a 64-channel layer by the library's parallel reduction
-            if need_w and gwhat.shape[0] > 16:
-                gwhat = gwhat.sum(0)
-            if need_b:
-                gb = g.sum(dim=(0, 2, 3))
-        else:
-            gx, gwhat, gb = _library_backward(ctx, g, x, hipops.xnor_what(w, center, compute_alpha), ctx.conf[:5],
-                                              (need_x, need_w, need_b))
-        gw = hipops.xnor_weight_backward(w, gwhat, center, compute_alpha) if need_w else None
-        return (gx if need_x else None, gw, gb if need_b else None, None, None, None)
+def _fused_weight_hook(layer: nn.Module, rank: int, backward_hooks: bool) -> bool:
+    """The two kernels can stand in for ``layer.weight_pre_process`` (an XNORWeightBinarizer, by the layer's plan): the
+    switch is on, the weight is contiguous of ``rank`` 4 (``Conv2d``; at most 1024 taps) or 2 (``Linear``), and the
+    binarizer carries no forward hook — ``backward_hooks``: nor a backward hook (the per-layer functions never asked)."""
+    w = layer.weight
+    return (FUSED_WEIGHT_HOOK and w.dim() == rank and w.is_contiguous() and (rank == 2 or w.shape[2] * w.shape[3] <= 1024)
+            and _no_hooks(layer.weight_pre_process, backward=backward_hooks))
 
 
 def conv2d_train(layer: nn.Module, x: torch.Tensor, plan, packed) -> torch.Tensor:
     """``bnn.layers.Conv2d.forward`` with autograd recording: HIP forward; binary-aware HIP backward where the gradient
     kernels cover the layer (dense or — ``GROUPED`` — grouped), the library's otherwise."""
-    w = layer.weight
-    if (FUSED_WEIGHT_HOOK and w.dim() == 4 and w.is_contiguous() and w.shape[2] * w.shape[3] <= 1024
-            and not layer.weight_pre_process._forward_hooks and not layer.weight_pre_process._forward_pre_hooks):
-        out = BinaryConv2dTrainFusedFn.apply(x, w, layer.bias, layer, plan, packed)
-        if plan.scale is not None:                          # BasicScaleBinarizer (bnn/ops.py:200-202)
-            out = out * plan.scale
-        return out
-    w_hat = layer.weight_pre_process(layer.weight)          # autograd edge to W (sign STE, alpha)
-    out = BinaryConv2dTrainFn.apply(x, w_hat, layer.bias, layer, plan, packed)
-    if plan.scale is not None:                              # BasicScaleBinarizer (bnn/ops.py:200-202)
+    if _fused_weight_hook(layer, 4, backward_hooks=False):
+        w, wconf = layer.weight, (bool(plan.center), bool(plan.compute_alpha))
+    else:
+        w, wconf = layer.weight_pre_process(layer.weight), None     # autograd edge to W (sign STE, alpha)
+    out = BinaryConv2dTrainFn.apply(x, w, layer.bias, layer, packed, wconf)
+    if plan.scale is not None:                                      # BasicScaleBinarizer (bnn/ops.py:200-202)
         out = out * plan.scale
     return out
 
@@ -425,52 +456,34 @@ LINEAR = os.environ.get("BNN_AMD_TRAIN_LINEAR", "0") == "1"
 
 
 class BinaryLinearTrainFn(torch.autograd.Function):
-    """``wconf = (center, compute_alpha)``: ``w`` is the LATENT weight and the XNORWeightBinarizer is inside (as in
-    ``BinaryConv2dTrainFusedFn``); ``wconf = None``: ``w`` is ``What = weight_pre_process(W)``, made under autograd by the
-    caller."""
+    """``wconf``: module docstring (``w`` is the latent weight with it, ``What`` without)."""
 
     @staticmethod
     def forward(ctx, x, w, bias, packed, wconf):
         out, sv = hipops.blinear_direct(x, packed, bias, None, want_planes=True)
-        ctx.save_for_backward(sv.sign.P, sv.sign.M, sv.T, w)
+        _keep(ctx, [sv], w)
         ctx.packed, ctx.wconf, ctx.x_shape, ctx.has_bias = packed, wconf, tuple(x.shape), bias is not None
-        global _saved_bytes
-        _saved_bytes += sv.nbytes()
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        P, M, T, w = ctx.saved_tensors
+        (saved,), (w,) = _kept(ctx)
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
-        shape = (P.shape[0], ctx.x_shape[-1], 1, 1)
-        saved = hipops.SavedAct(hipops.PackedAct(P, M, shape), T, shape)
         g = g.reshape(-1, g.shape[-1]).contiguous()
-        gx = gw = gb = None
-        if need_x:
-            gx = hipops.blinear_grad_input(g, saved, ctx.packed).reshape(ctx.x_shape)      # STE mask fused
-        if need_w:
-            gwhat = hipops.blinear_grad_weight(g, saved, reduce=False)
-            if ctx.wconf is None:
-                gw = gwhat[0] if gwhat.shape[0] == 1 else gwhat.sum(0)
-            else:
-                if gwhat.shape[0] > 16:         # (see BinaryConv2dTrainFusedFn.backward)
-                    gwhat = gwhat.sum(0)
-                gw = hipops.xnor_weight_backward(w, gwhat, *ctx.wconf)
-        if need_b:
-            gb = g.sum(0)
-        return gx, gw, gb, None, None
+        gx, gw = blinear_backward(g, saved, ctx.packed, w, ctx.wconf, need_x, need_w)
+        return (gx.reshape(ctx.x_shape) if need_x else None, gw, g.sum(0) if need_b else None, None, None)
 
 
 def linear_train(layer: nn.Module, x: torch.Tensor, plan, packed) -> torch.Tensor:
-    """``bnn.layers.Linear.forward`` with autograd recording (``fastpath.plan_linear_train`` admitted the layer)."""
-    w = layer.weight
-    if FUSED_WEIGHT_HOOK and w.dim() == 2 and w.is_contiguous():
-        out = BinaryLinearTrainFn.apply(x, w, layer.bias, packed, (bool(plan.center), bool(plan.compute_alpha)))
+    """``bnn.layers.Linear.forward`` with autograd recording (``fastpath.plan_linear_train`` admitted the layer, and
+    with it ``weight_pre_process`` as one without forward hooks)."""
+    if _fused_weight_hook(layer, 2, backward_hooks=False):
+        w, wconf = layer.weight, (bool(plan.center), bool(plan.compute_alpha))
     else:
-        w_hat = layer.weight_pre_process(w)                 # autograd edge to W (sign STE, alpha)
-        out = BinaryLinearTrainFn.apply(x, w_hat, layer.bias, packed, None)
-    if plan.scale is not None:                              # BasicScaleBinarizer (bnn/ops.py:200-202)
+        w, wconf = layer.weight_pre_process(layer.weight), None     # autograd edge to W (sign STE, alpha)
+    out = BinaryLinearTrainFn.apply(x, w, layer.bias, packed, wconf)
+    if plan.scale is not None:                                      # BasicScaleBinarizer (bnn/ops.py:200-202)
         out = out * plan.scale
     return out
 
@@ -486,7 +499,7 @@ def linear_train(layer: nn.Module, x: torch.Tensor, plan, packed) -> torch.Tenso
 #   kept    :  x (an input of the graph anyway), the three planes, mean / invstd, and the parameters — not u, z or y
 #   backward:  z recomputed by the un-fused convolution launch on the kept planes and packed weight (the same bits the
 #              epilogue saw)  ->  PReLU + shuffle backward (csrc/prelu_bwd.hip)  ->  the gradient kernels of the binary
-#              convolution, as BinaryConv2dTrainFusedFn uses them  ->  BatchNorm backward with the skip's gradient added
+#              convolution (_bconv_backward)  ->  BatchNorm backward with the skip's gradient added
 #              in its dx kernel.
 # Off by default (its speed against the per-layer path is recorded in profiles/cellops_train_bench.jsonl; the default is
 # a later decision); BNN_AMD_TRAIN_CELL_OPS=1 or `training.CELL_OPS = True` turns it on — read at every call.
@@ -520,42 +533,21 @@ class CellOpTrainFn(torch.autograd.Function):
         y = _cell_conv(sv.sign, packed, conf, prelu=slopes.expand(O) if slopes.numel() == 1 else slopes,
                        residual=x if add_skip else None)
         # (the output is NOT saved: Cell.forward applies drop_path to it in place)
-        ctx.save_for_backward(x, sv.sign.P, sv.sign.M, sv.T, mean, invstd, w, gamma, slope)
+        _keep(ctx, [sv], x, mean, invstd, w, gamma, slope)
         ctx.packed, ctx.conf, ctx.add_skip, ctx.wconf = packed, conf, add_skip, wconf
-        global _saved_bytes
-        _saved_bytes += sv.nbytes()
         return y
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        x, P, M, T, mean, invstd, w, gamma, slope = ctx.saved_tensors
-        groups, stride, padding, dilation, shuffle = ctx.conf
-        center, compute_alpha = ctx.wconf
+        (saved,), (x, mean, invstd, w, gamma, slope) = _kept(ctx)
+        shuffle = ctx.conf[4]
         need_x, need_w, need_gamma, need_beta, need_slope = ctx.needs_input_grad[:5]
         g = g.contiguous()
-        saved = hipops.SavedAct(hipops.PackedAct(P, M, tuple(x.shape)), T, tuple(x.shape))
         z = _cell_conv(saved.sign, ctx.packed, ctx.conf)           # scratch: overwritten by gz, dies in here
         gz, gslope = hipops.prelu_shuffle_backward(g, z, slope, shuffle, inplace=True)
         need_u = need_x or need_gamma or need_beta
-        gu = gwhat = None
-        if groups != 1:
-            geom = (groups, stride, padding, dilation)
-            if need_u:
-                gu = hipops.bconv_grouped_grad_input(gz, saved, hipops.xnor_what(w, center, compute_alpha), *geom)
-            if need_w:
-                gwhat = hipops.bconv_grouped_grad_weight(gz, saved, w.shape, *geom, reduce=False)
-        else:
-            if need_u:
-                gpacked, alpha = hipops.xnor_grad_pack_weight(w, center, compute_alpha)
-                gu = hipops.bconv_grad_input(gz, saved, gpacked, alpha, w.shape[2], stride[0])
-            if need_w:
-                gwhat = hipops.bconv_grad_weight(gz, saved, w.shape[2], stride[0], reduce=False)
-        gw = None
-        if need_w:
-            if gwhat.shape[0] > 16:         # (see BinaryConv2dTrainFusedFn.backward)
-                gwhat = gwhat.sum(0)
-            gw = hipops.xnor_weight_backward(w, gwhat, center, compute_alpha)
+        gu, gw = _bconv_backward(gz, saved, w, ctx.conf[:4], need_u, need_w, ctx.wconf)
         dx = dgamma = dbeta = None
         if need_u:
             dx, dgamma, dbeta = hipops.bn_train_backward_add(gu, x, mean, invstd, gamma, g if ctx.add_skip else None)
@@ -563,33 +555,40 @@ class CellOpTrainFn(torch.autograd.Function):
                 gslope.reshape(slope.shape) if need_slope else None, None, None, None, None, None)
 
 
-def _no_hooks(*modules) -> bool:
-    return not any(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks
-                   for m in modules)
+def _fusable_binary_conv(conv: nn.Module, plan) -> bool:
+    """``conv`` with its ``fastpath._recognise`` ``plan`` can sit inside a fused training op: recognised hooks whose input
+    binarizer has the hard-tanh STE (``plan.ste``: BasicInputBinarizer), no post scale, no bias, zero padding given as
+    numbers."""
+    return (plan is not None and plan.ste and plan.scale is None and conv.bias is None
+            and not isinstance(conv.padding, str) and conv.padding_mode == "zeros")
+
+
+def _binary_conv_plan(conv):
+    """The plan of ``conv`` when it is a binary ``Conv2d`` under ``_fusable_binary_conv`` and ``_fused_weight_hook``
+    (backward hooks included: nothing of a fused op fires), else None."""
+    if not (isinstance(conv, nn.Conv2d) and hasattr(conv, "activation_pre_process")):
+        return None
+    from . import fastpath
+    plan = fastpath._recognise(conv, conv.out_channels)
+    return plan if _fusable_binary_conv(conv, plan) and _fused_weight_hook(conv, 4, backward_hooks=True) else None
 
 
 def cell_op_train(op: nn.Module, x: torch.Tensor):
     """``op(x)`` of a ``SepConv`` / ``DilConv`` / ``ReLUConvBN`` in train() mode as ``CellOpTrainFn``, or None — the
     caller then runs the per-layer path — unless: the switches are on and autograd is recording without autocast; ``op.op``
-    is ``Sequential(BatchNorm2d, binary Conv2d, PReLU)`` with the BatchNorm under the rule of ``bn_act_applies``; the
-    recipe is BasicInputBinarizer + XNORWeightBinarizer without a post scale, no bias, zero padding given as numbers; the
-    gradient kernels cover the geometry; fp32 NCHW on a HIP device with more than one value per channel; nothing carries
-    a hook (it would not fire); and the conditions of the fused weight hook in ``conv2d_train`` hold."""
+    is ``Sequential(BatchNorm2d, binary Conv2d, PReLU)`` with ``_batch_stat_bn`` and ``_binary_conv_plan``; ``_no_hooks``
+    on everything; the geometry is the operation's own and the gradient kernels cover it; ``_f32_on_one_device``, NCHW
+    with more than one value per channel."""
     from . import fastpath
     shuffle = CELL_OP_SHUFFLE.get(type(op).__name__)
     seq = getattr(op, "op", None)
-    if not (CELL_OPS and ENABLED and BINARY_GRADS and FUSED_WEIGHT_HOOK and shuffle is not None and op.training
+    if not (CELL_OPS and ENABLED and BINARY_GRADS and shuffle is not None and op.training
             and torch.is_grad_enabled() and not torch.is_autocast_enabled()
             and isinstance(seq, nn.Sequential) and len(seq) == 3):
         return None
     bn, conv, act = seq
-    if not (type(bn) is nn.BatchNorm2d and bn.training and bn.track_running_stats and bn.running_mean is not None
-            and bn.running_var is not None and isinstance(conv, nn.Conv2d) and hasattr(conv, "activation_pre_process")
-            and type(act) is nn.PReLU):
-        return None
-    plan = fastpath._recognise(conv, conv.out_channels)
-    if plan is None or not plan.ste or plan.scale is not None or conv.bias is not None \
-            or isinstance(conv.padding, str) or conv.padding_mode != "zeros":
+    plan = _binary_conv_plan(conv) if _batch_stat_bn(bn) and type(act) is nn.PReLU else None
+    if plan is None or not _no_hooks(op, seq, bn, conv, act, conv.activation_pre_process, conv.activation_post_process):
         return None
     w, C, O, groups = conv.weight, conv.in_channels, conv.out_channels, int(conv.groups)
     stride, padding, dilation = tuple(conv.stride), tuple(conv.padding), tuple(conv.dilation)
@@ -600,14 +599,9 @@ def cell_op_train(op: nn.Module, x: torch.Tensor):
         return None
     if not grouped and (getattr(op, "C_in", None) != C or getattr(op, "C_out", None) != O):
         return None
-    if not (w.dim() == 4 and w.is_contiguous() and w.shape[2] * w.shape[3] <= 1024):        # (conv2d_train's rule)
-        return None
-    if not _no_hooks(op, seq, bn, conv, act, conv.activation_pre_process, conv.weight_pre_process,
-                     conv.activation_post_process):
-        return None
-    tensors = [x, w, act.weight, bn.running_mean, bn.running_var] + [t for t in (bn.weight, bn.bias) if t is not None]
+    affine = [t for t in (bn.weight, bn.bias) if t is not None]
     if not (x.dim() == 4 and x.shape[1] == C and x.numel() > C
-            and all(t.is_cuda and t.device == x.device and t.dtype == torch.float32 for t in tensors)):
+            and _f32_on_one_device(x, w, act.weight, bn.running_mean, bn.running_var, *affine)):
         return None
     supported = hipops.grouped_grad_supported(x.shape, w.shape, groups, stride, padding, dilation) if grouped \
         else hipops.grad_supported(x.shape, w.shape, stride, padding, dilation)
@@ -631,7 +625,7 @@ def cell_op_train(op: nn.Module, x: torch.Tensor):
 #   kept    :  x, the two triples of planes, mean / invstd, the parameters — not u, the convolution outputs or y
 #   backward:  z recomputed by the un-fused launches  ->  PReLU backward on the whole of g  ->  ONE copy of gz that makes
 #              its two channel halves contiguous (the gradient kernels take contiguous tensors)  ->  per phase the 1x1
-#              stride-1 gradient kernels of csrc/grad.hip, as CellOpTrainFn uses them  ->  BatchNorm backward from the two
+#              stride-1 gradient kernels of csrc/grad.hip (_bconv_backward)  ->  BatchNorm backward from the two
 #              lattice gradients (csrc/bn_train.hip: bn_bwd_s2_reduce_kernel, bn_bwd_dx_s2_kernel), dx written once.
 class ReduceTrainFn(torch.autograd.Function):
     @staticmethod
@@ -650,95 +644,70 @@ class ReduceTrainFn(torch.autograd.Function):
             hipops.bconv2d_fused(phases[k].sign, packed[k], prelu=slopes[k * half:(k + 1) * half], out=y,
                                  out_c_offset=k * half)
         # (the output is NOT saved: Cell.forward applies drop_path to it in place)
-        ctx.save_for_backward(x, phases[0].sign.P, phases[0].sign.M, phases[0].T, phases[1].sign.P, phases[1].sign.M,
-                              phases[1].T, mean, invstd, w1, w2, gamma, slope)
+        _keep(ctx, phases, x, mean, invstd, w1, w2, gamma, slope)
         ctx.packed, ctx.wconf = packed, wconf
-        global _saved_bytes
-        _saved_bytes += phases[0].nbytes() + phases[1].nbytes()
         return y
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        x, P0, M0, T0, P1, M1, T1, mean, invstd, w1, w2, gamma, slope = ctx.saved_tensors
+        saved, (x, mean, invstd, w1, w2, gamma, slope) = _kept(ctx)
         need_x, need_w1, need_w2, need_gamma, need_beta, need_slope = ctx.needs_input_grad[:6]
         g = g.contiguous()
-        N, C, H, W = x.shape
-        shape = (N, C, H // 2, W // 2)
-        saved = [hipops.SavedAct(hipops.PackedAct(P, M, shape), T, shape) for P, M, T in ((P0, M0, T0), (P1, M1, T1))]
-        ws, half = (w1, w2), w1.shape[0]
+        N, half = x.shape[0], w1.shape[0]
         z = torch.empty_like(g)                                    # scratch: overwritten by gz, dies in here
         for k in range(2):
             hipops.bconv2d_fused(saved[k].sign, ctx.packed[k], out=z, out_c_offset=k * half)
         gz, gslope = hipops.prelu_shuffle_backward(g, z, slope, 1, inplace=True)
         # the one extra pass over g: [N, 2, half, Ho, Wo] -> [2, N, half, Ho, Wo], each half contiguous
-        gzk = gz.view(N, 2, half, shape[2], shape[3]).transpose(0, 1).contiguous()
+        gzk = gz.view(N, 2, half, *gz.shape[2:]).transpose(0, 1).contiguous()
         need_u = need_x or need_gamma or need_beta
-        gu, gw = [None, None], [None, None]
-        for k, need_w in enumerate((need_w1, need_w2)):
-            center, compute_alpha = ctx.wconf[k]
-            if need_u:
-                gpacked, alpha = hipops.xnor_grad_pack_weight(ws[k], center, compute_alpha)
-                gu[k] = hipops.bconv_grad_input(gzk[k], saved[k], gpacked, alpha, 1, 1)
-            if need_w:
-                gwhat = hipops.bconv_grad_weight(gzk[k], saved[k], 1, 1, reduce=False)
-                if gwhat.shape[0] > 16:         # (see BinaryConv2dTrainFusedFn.backward)
-                    gwhat = gwhat.sum(0)
-                gw[k] = hipops.xnor_weight_backward(ws[k], gwhat, center, compute_alpha)
+        geom = (1, (1, 1), (0, 0), (1, 1))                         # the phases are dense 1x1 stride-1 convolutions
+        (gu0, gw0), (gu1, gw1) = (_bconv_backward(gzk[k], saved[k], w, geom, need_u, need_w, ctx.wconf[k])
+                                  for k, (w, need_w) in enumerate(((w1, need_w1), (w2, need_w2))))
         dx = dgamma = dbeta = None
         if need_u:
-            dx, dgamma, dbeta = hipops.bn_train_backward_s2(gu[0], gu[1], x, mean, invstd, gamma)
-        return (dx if need_x else None, gw[0], gw[1], dgamma if need_gamma else None, dbeta if need_beta else None,
+            dx, dgamma, dbeta = hipops.bn_train_backward_s2(gu0, gu1, x, mean, invstd, gamma)
+        return (dx if need_x else None, gw0, gw1, dgamma if need_gamma else None, dbeta if need_beta else None,
                 gslope.reshape(slope.shape) if need_slope else None, None, None, None)
 
 
 def reduce_train(m: nn.Module, x: torch.Tensor):
     """``m(x)`` of a ``FactorizedReduce`` in train() mode as ``ReduceTrainFn``, or None — the caller then runs the module's
     own forward — unless: the switches are on and autograd is recording without autocast; the module is ``bn`` /
-    ``conv_1`` / ``conv_2`` / ``activation`` as ``cellops._Reduce`` recognises it, the BatchNorm under the rule of
-    ``cell_op_train``; both convolutions are binary 1x1 / stride 2 / padding 0 / ``groups == 1`` over the BatchNorm's
-    channels with the recipe BasicInputBinarizer + XNORWeightBinarizer, no post scale and no bias, and the weight rule of
-    ``conv2d_train``; nothing carries a hook (it would not fire); fp32 NCHW on one HIP device with even ``H`` and ``W`` and
+    ``conv_1`` / ``conv_2`` / ``activation`` as ``cellops._Reduce`` recognises it, with ``_batch_stat_bn`` and, for both
+    convolutions, ``_binary_conv_plan``; both are 1x1 / stride 2 / padding 0 / ``groups == 1`` over the BatchNorm's
+    channels; ``_no_hooks`` on everything; ``_f32_on_one_device``, NCHW with even ``H`` and ``W`` and
     more than one value per channel; the 1x1 stride-1 gradient kernels cover the half-resolution geometry; and a phase
     holds an even number of plane words (the second phase's planes are then 16-byte aligned, as the convolution launch
     requires)."""
     from . import fastpath
-    if not (CELL_OPS and ENABLED and BINARY_GRADS and FUSED_WEIGHT_HOOK and type(m).__name__ == "FactorizedReduce"
+    if not (CELL_OPS and ENABLED and BINARY_GRADS and type(m).__name__ == "FactorizedReduce"
             and m.training and torch.is_grad_enabled() and not torch.is_autocast_enabled()):
         return None
     bn, act = getattr(m, "bn", None), getattr(m, "activation", None)
     seqs = [getattr(m, n, None) for n in ("conv_1", "conv_2")]
-    if not (type(bn) is nn.BatchNorm2d and bn.training and bn.track_running_stats and bn.running_mean is not None
-            and bn.running_var is not None and type(act) is nn.PReLU
+    if not (_batch_stat_bn(bn) and type(act) is nn.PReLU
             and all(isinstance(s, nn.Sequential) and len(s) == 1 for s in seqs)):
         return None
     convs = [s[0] for s in seqs]
     C, half = bn.num_features, getattr(convs[0], "out_channels", None)
-    plans = []
+    plans = [_binary_conv_plan(conv) for conv in convs]
+    if any(p is None for p in plans):
+        return None
     for conv in convs:
-        if not (isinstance(conv, nn.Conv2d) and hasattr(conv, "activation_pre_process")):
-            return None
-        plan = fastpath._recognise(conv, conv.out_channels)
-        if plan is None or not plan.ste or plan.scale is not None or conv.bias is not None \
-                or isinstance(conv.padding, str) or conv.padding_mode != "zeros":
-            return None
         if (conv.in_channels != C or conv.out_channels != half or conv.groups != 1 or tuple(conv.kernel_size) != (1, 1)
                 or tuple(conv.stride) != (2, 2) or tuple(conv.padding) != (0, 0) or tuple(conv.dilation) != (1, 1)):
             return None
-        w = conv.weight
-        if not (w.dim() == 4 and w.is_contiguous() and w.shape[2] * w.shape[3] <= 1024):    # (conv2d_train's rule)
-            return None
-        plans.append(plan)
     if act.weight.numel() not in (1, 2 * half):
         return None
-    hooked = [m, bn, act] + seqs + convs + [h for c in convs for h in (c.activation_pre_process, c.weight_pre_process,
-                                                                        c.activation_post_process)]
-    if not _no_hooks(*hooked):
+    if not _no_hooks(m, bn, act, *seqs, *convs, *[h for c in convs for h in (c.activation_pre_process,
+                                                                             c.activation_post_process)]):
         return None
-    tensors = [x, convs[0].weight, convs[1].weight, act.weight, bn.running_mean, bn.running_var] \
-        + [t for t in (bn.weight, bn.bias) if t is not None]
+    affine = [t for t in (bn.weight, bn.bias) if t is not None]
     if not (x.dim() == 4 and x.shape[1] == C and x.numel() > C and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
-            and all(t.is_cuda and t.device == x.device and t.dtype == torch.float32 for t in tensors)):
+            and _f32_on_one_device(x, convs[0].weight, convs[1].weight, act.weight, bn.running_mean, bn.running_var,
+                                   *affine)):
         return None
     N, _, H, W = x.shape
     if not hipops.grad_supported((N, C, H // 2, W // 2), (half, C, 1, 1), (1, 1), (0, 0), (1, 1)):

@@ -102,6 +102,119 @@ def test_each_decline_rule_falls_through(cell_ops_on):
     assert training.cell_op_train(nn.Sequential(m), x) is None                 # not a cell operation
 
 
+def _binary(m, **recipe):
+    return binarise(m, **recipe).train()
+
+
+def _conv(k=3, bias=False, **recipe):
+    return _binary(nn.Conv2d(8, 8, k, padding=k // 2, bias=bias), **recipe)
+
+
+def _with(m, change):
+    """``m`` after ``change(m)`` (a hook registered, an attribute replaced)."""
+    change(m)
+    return m
+
+
+def _hook(kind, pick=lambda m: m):
+    register = {"forward": lambda m: m.register_forward_hook(lambda mod, i, o: None),
+                "forward_pre": lambda m: m.register_forward_pre_hook(lambda mod, i: None),
+                "backward": lambda m: m.register_full_backward_hook(lambda mod, gi, go: None),
+                "backward_pre": lambda m: m.register_full_backward_pre_hook(lambda mod, go: None)}[kind]
+    return lambda m: register(pick(m))
+
+
+def _transposed_weight(m):
+    m.weight = nn.Parameter(m.weight.detach().transpose(-1, -2))        # same shape (square), other strides
+
+
+def _padding_same(m):
+    m.padding = "same"
+
+
+def _no_running_var(m):
+    m.running_var = None
+
+
+def _wpre(m):
+    return m.weight_pre_process
+
+
+def _fusable(conv):
+    return training._fusable_binary_conv(conv, fastpath._recognise(conv, conv.out_channels))
+
+
+# (rule, what it is asked, its answer): one row per reason to decline, and the plain module each was derived from
+ADMISSION = [
+    ("bn: plain", lambda: training._batch_stat_bn(nn.BatchNorm2d(8)), True),
+    ("bn: not affine", lambda: training._batch_stat_bn(nn.BatchNorm2d(8, affine=False)), True),
+    ("bn: a subclass", lambda: training._batch_stat_bn(nn.SyncBatchNorm(8)), False),
+    ("bn: no running statistics", lambda: training._batch_stat_bn(nn.BatchNorm2d(8, track_running_stats=False)), False),
+    ("bn: one running statistic", lambda: training._batch_stat_bn(_with(nn.BatchNorm2d(8), _no_running_var)), False),
+    ("bn: eval mode", lambda: training._batch_stat_bn(nn.BatchNorm2d(8).eval()), False),
+    ("bn: not a BatchNorm", lambda: training._batch_stat_bn(None), False),
+    ("conv: plain", lambda: _fusable(_conv()), True),
+    ("conv: bias", lambda: _fusable(_conv(bias=True)), False),
+    ("conv: post scale", lambda: _fusable(_conv(post=BasicScaleBinarizer)), False),
+    ("conv: AdvancedInputBinarizer", lambda: _fusable(_conv(pre=AdvancedInputBinarizer)), False),
+    ("conv: string padding", lambda: _fusable(_with(_conv(), _padding_same)), False),
+    ("conv: not recognised", lambda: training._fusable_binary_conv(_conv(), None), False),
+    ("hook: plain conv", lambda: training._fused_weight_hook(_conv(), 4, backward_hooks=True), True),
+    ("hook: 32 x 32 taps", lambda: training._fused_weight_hook(_conv(k=32), 4, backward_hooks=True), True),
+    ("hook: non-contiguous weight", lambda: training._fused_weight_hook(_with(_conv(), _transposed_weight), 4, True), False),
+    ("hook: kh * kw > 1024", lambda: training._fused_weight_hook(_conv(k=33), 4, backward_hooks=True), False),
+    ("hook: a Linear asked as a Conv2d", lambda: training._fused_weight_hook(_binary(nn.Linear(8, 8)), 4, True), False),
+    ("hook: plain Linear", lambda: training._fused_weight_hook(_binary(nn.Linear(8, 8)), 2, backward_hooks=False), True),
+    ("hook: non-contiguous Linear weight",
+     lambda: training._fused_weight_hook(_with(_binary(nn.Linear(8, 8)), _transposed_weight), 2, False), False),
+    ("hook: forward hook on the binarizer, per-layer site",
+     lambda: training._fused_weight_hook(_with(_conv(), _hook("forward", _wpre)), 4, backward_hooks=False), False),
+    ("hook: forward-pre hook on the binarizer, fused-op site",
+     lambda: training._fused_weight_hook(_with(_conv(), _hook("forward_pre", _wpre)), 4, backward_hooks=True), False),
+    ("hook: backward hook on the binarizer, fused-op site",
+     lambda: training._fused_weight_hook(_with(_conv(), _hook("backward", _wpre)), 4, backward_hooks=True), False),
+    ("hook: backward hook on the binarizer, per-layer site (never asked there)",
+     lambda: training._fused_weight_hook(_with(_conv(), _hook("backward", _wpre)), 4, backward_hooks=False), True),
+    ("no_hooks: plain, and None skipped", lambda: training._no_hooks(nn.ReLU(), None, nn.BatchNorm2d(8)), True),
+    ("no_hooks: forward", lambda: training._no_hooks(nn.ReLU(), _with(nn.ReLU(), _hook("forward"))), False),
+    ("no_hooks: forward, forward-only site",
+     lambda: training._no_hooks(_with(nn.ReLU(), _hook("forward")), backward=False), False),
+    ("no_hooks: forward-pre", lambda: training._no_hooks(_with(nn.ReLU(), _hook("forward_pre")), backward=False), False),
+    ("no_hooks: backward", lambda: training._no_hooks(_with(nn.ReLU(), _hook("backward"))), False),
+    ("no_hooks: backward-pre", lambda: training._no_hooks(_with(nn.ReLU(), _hook("backward_pre"))), False),
+    ("no_hooks: backward, forward-only site",
+     lambda: training._no_hooks(_with(nn.ReLU(), _hook("backward")), backward=False), True),
+    ("device: a CPU tensor", lambda: training._f32_on_one_device(torch.zeros(2)), False),
+    ("device: a CPU tensor among the others",
+     lambda: training._f32_on_one_device(torch.zeros(2, device="meta"), torch.zeros(2)), False),
+]
+
+
+@pytest.mark.parametrize("name,ask,answer", ADMISSION, ids=[r[0] for r in ADMISSION])
+def test_each_admission_rule_answers_on_its_own(name, ask, answer):
+    """Through ``cell_op_train`` / ``reduce_train`` every decline on a CPU module ends in the same None (the device rule
+    declines last); asked directly, each rule shows its own answer.  No native call is made."""
+    launches = native.launch_count()
+    assert ask() is answer
+    assert native.launch_count() == launches
+
+
+def test_the_fused_weight_hook_rule_follows_its_switch(monkeypatch):
+    conv = _conv()
+    assert training._fused_weight_hook(conv, 4, backward_hooks=True)
+    monkeypatch.setattr(training, "FUSED_WEIGHT_HOOK", False)
+    assert not training._fused_weight_hook(conv, 4, backward_hooks=True)
+    assert training._binary_conv_plan(conv) is None
+
+
+def test_the_plan_of_a_fusable_convolution():
+    plan = training._binary_conv_plan(_conv())
+    assert plan is not None and plan.ste and plan.scale is None
+    assert training._binary_conv_plan(nn.Conv2d(8, 8, 3)) is None                       # not a binary layer
+    assert training._binary_conv_plan(_conv(bias=True)) is None
+    assert training._binary_conv_plan(_with(_conv(), _hook("backward", _wpre))) is None
+
+
 def test_master_switches_turn_the_path_off(monkeypatch):
     case = CELL_CASES[0]
     m, x = build(case), torch.from_numpy(case.input())

@@ -221,6 +221,19 @@ def test_training_forward_and_gradients_match_the_composition(linear_flag, lead,
         assert torch.allclose(gp1[n], gp0[n], **_tol(gp0[n])), n
 
 
+@pytest.mark.parametrize("fused", [True, False], ids=["fused_hook", "torch_hook"])
+def test_training_gradients_with_and_without_the_fused_weight_hook(linear_flag, monkeypatch, fused):
+    """``training.FUSED_WEIGHT_HOOK`` off: ``What = weight_pre_process(W)`` is made by torch under autograd and the weight
+    gradient kernel's slabs are summed into dL/dWhat instead of feeding ``xnor_weight_backward``.  65 rows: one full
+    64-row workgroup and a tail."""
+    hook_kernel = []
+    real = hipops.xnor_weight_backward
+    monkeypatch.setattr(hipops, "xnor_weight_backward", lambda *a: hook_kernel.append(1) or real(*a))
+    monkeypatch.setattr(training, "FUSED_WEIGHT_HOOK", fused)
+    test_training_forward_and_gradients_match_the_composition(None, (65,), 70, 33, True, False, False)
+    assert len(hook_kernel) == (1 if fused else 0)
+
+
 # ---- dispatch -----------------------------------------------------------------------------------------------------------
 def test_flag_moves_a_linear_onto_the_hip_path_and_keeps_three_bits_per_element():
     layer = _layer(70, 33, True, False, False, seed=3)

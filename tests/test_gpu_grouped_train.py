@@ -228,6 +228,23 @@ def test_layer_with_the_library_backward_forced(grouped_on, case):
     check_layer(case, binary_grads=False)
 
 
+# depthwise, a ragged batch (three images), every pixel of the 5 x 5 image within one tap of the border
+DW_SMALL = GroupedCase("dw16_n3_5x5", 3, 16, 5, 5, 16, 16, 3, 3, pad=(1, 1))
+
+
+@pytest.mark.parametrize("fused", [True, False], ids=["fused_hook", "torch_hook"])
+def test_layer_with_and_without_the_fused_weight_hook(grouped_on, monkeypatch, fused):
+    """``training.FUSED_WEIGHT_HOOK`` off: ``What = weight_pre_process(W)`` is made by torch under autograd and the grouped
+    gradient kernels return dL/dWhat (slabs summed) instead of feeding ``xnor_weight_backward``."""
+    hook_kernel = []
+    real = hipops.xnor_weight_backward
+    monkeypatch.setattr(hipops, "xnor_weight_backward", lambda *a: hook_kernel.append(1) or real(*a))
+    monkeypatch.setattr(training, "FUSED_WEIGHT_HOOK", fused)
+    assert supported(DW_SMALL)
+    check_layer(DW_SMALL, binary_grads=True)
+    assert len(hook_kernel) == (1 if fused else 0)
+
+
 def test_the_switch_is_off_by_default_and_read_at_every_call(monkeypatch):
     assert training.GROUPED is (os.environ.get("BNN_AMD_TRAIN_GROUPED", "0") == "1")      # off unless the environment asks
     case = GROUPED_CASES[1]

@@ -84,6 +84,22 @@ def test_training_forward_and_gradients_match_composition(C, O, k, stride, pad, 
         assert torch.allclose(gp1[n], gp0[n], rtol=1e-3, atol=1e-4 * float(gp0[n].abs().max()) + 1e-7), n
 
 
+def test_more_than_16_weight_gradient_slabs_are_summed_before_the_fused_weight_hook():
+    """18 images are 18 split-K slabs (one per image at this size): more than the 16 the hook's kernel adds itself.  Same
+    comparison and tolerances as ``test_training_forward_and_gradients_match_composition``."""
+    N, C, O = 18, 64, 40
+    assert native.require().bnn_hip_bconv_grad_weight_splits(N, O, C, 3) > 16
+    layer = _layer(C, O, 3, 1, 1, False, False, True, seed=77)
+    x = (gen.normal(7, (N, C, 6, 5)) * 0.8).astype(np.float32)
+    g = gen.normal(8, (N, O, 6, 5))
+    y1, gx1, gp1 = _grads(layer, x, g, enabled=True)
+    y0, gx0, gp0 = _grads(layer, x, g, enabled=False)
+    assert torch.allclose(y1, y0, rtol=1e-4, atol=1e-5 * float(y0.abs().max()))
+    assert torch.allclose(gx1, gx0, rtol=1e-4, atol=1e-5 * float(gx0.abs().max()))
+    w1, w0 = gp1["weight"], gp0["weight"]
+    assert torch.allclose(w1, w0, rtol=1e-3, atol=1e-4 * float(w0.abs().max()) + 1e-7)
+
+
 def test_inference_and_training_forwards_agree_and_repack_after_optimizer_step():
     layer = _layer(64, 64, 3, 1, 1, False, False, False, seed=9)
     x = dev(gen.normal(3, (2, 64, 8, 8)))
