@@ -15,6 +15,9 @@ A layer takes the HIP path when ALL of the following hold (otherwise the torch c
   ``training.LINEAR`` (``BNN_AMD_TRAIN_LINEAR=1``, off by default: one HIP launch forward that keeps three bit planes
   of the input, bf16 x 3 matrix-core gradients from the weight pack and the planes: ``csrc/blinear.hip``) and the
   composition otherwise; ``Conv1d`` under autograd stays on the composition
+* a ``Conv2d`` whose weight hook is the identity (binary activations, real weights: step 0 of the two-stage recipe) takes
+  a path of its own under ``REAL_WEIGHTS`` (``BNN_AMD_REAL_WEIGHTS=1``, off by default): ``csrc/sconv.hip`` forward, in a
+  training step ``training.SignConvTrainFn``; ``Linear``, ``Conv1d``, grouped layers and fp16 keep the composition
 * ``padding_mode == 'zeros'``, numeric padding, and either ``groups == 1`` or — ``Conv2d`` / ``Conv1d`` under inference,
   ``Conv2d`` under autograd only with ``training.GROUPED`` — ``groups > 1`` (grouped and depthwise layers: ``pack_act``
   + ``bnn_hip_bconv2d_grouped``, two launches; the ResNet executors keep declining them, and so does the training
@@ -45,7 +48,15 @@ from . import hipops, native
 
 _stats_lock = threading.Lock()
 _stats = {"conv2d": 0, "conv1d": 0, "linear": 0, "weight_packs": 0, "conv2d_train": 0, "cell_op": 0, "cell": 0,
-          "cell_op_train": 0, "reduce_train": 0, "linear_train": 0}
+          "cell_op_train": 0, "reduce_train": 0, "linear_train": 0, "conv2d_real": 0, "conv2d_real_train": 0}
+
+# Binary activations with REAL weights (step 0 of the reference's two-stage recipe, examples/recepies/imagenet-baseline.yaml:
+# ``weight: nn.Identity``) on the HIP path: ``Conv2d`` layers whose weight hook is the identity take csrc/sconv.hip (one
+# launch from the fp32 input, three bf16 matrix-core products per weight) instead of the torch composition, in ``eval()``
+# and in a training step.  Off by default (its speed against the composition is recorded in profiles/sconv_bench.jsonl;
+# the default is a later decision); BNN_AMD_REAL_WEIGHTS=1 or ``fastpath.REAL_WEIGHTS = True`` turns it on — read at
+# every call (``plan_conv2d_real`` / ``plan_conv2d_real_train``).  With it off nothing here runs.
+REAL_WEIGHTS = os.environ.get("BNN_AMD_REAL_WEIGHTS", "0") == "1"
 
 
 def stats() -> dict:
@@ -78,6 +89,13 @@ class Plan:
     ste: bool = True               # the input hook's backward is the hard-tanh STE (training fast path allowed)
 
 
+@dataclass
+class RealPlan:
+    """Plan of a layer with binary activations and a real-valued weight (``_recognise_real``)."""
+    scale: Optional[torch.Tensor]  # BasicScaleBinarizer.alpha or None
+    ste: bool = True               # the input hook's backward is the hard-tanh STE (training fast path allowed)
+
+
 _HOOK_MODULES = ("bnn_amd.ops", "bnn_amd.bconfig", "bnn.ops", "bnn.bconfig")
 
 
@@ -88,25 +106,54 @@ def _is(obj, name: str) -> bool:
     return t.__name__ == name and t.__module__ in _HOOK_MODULES
 
 
-def _recognise(layer: nn.Module, out_channels: int) -> Optional[Plan]:
-    pre = layer.activation_pre_process
-    wpre = layer.weight_pre_process
-    post = layer.activation_post_process
-    basic = _is(pre, "BasicInputBinarizer")
+def _input_hook(pre) -> Optional[bool]:
+    """``True``: ``BasicInputBinarizer``; ``False``: an input hook whose VALUE is ``sign(x)`` too (inference only);
+    ``None``: anything else."""
+    if _is(pre, "BasicInputBinarizer"):
+        return True
     # AdvancedInputBinarizer (bnn/ops.py:167-177) returns sign(f(t*x)); with the default f = tanh and t > 0
     # that IS sign(x), only its gradient differs — so inference may take the same kernels, training may not
     advanced = (_is(pre, "AdvancedInputBinarizer") and getattr(pre, "derivative_funct", None) is torch.tanh
                 and isinstance(getattr(pre, "t", None), (int, float)) and pre.t > 0)
-    if not (basic or advanced) or not _is(wpre, "XNORWeightBinarizer"):
-        return None
+    return False if advanced else None
+
+
+def _post_scale(post, out_channels: int):
+    """``(recognised, scale)`` of the post hook: ``Identity``, or a per-output-channel ``BasicScaleBinarizer``."""
     if _is(post, "Identity"):
-        scale = None
-    elif _is(post, "BasicScaleBinarizer") and post.alpha.numel() == out_channels \
+        return True, None
+    if _is(post, "BasicScaleBinarizer") and post.alpha.numel() == out_channels \
             and post.alpha.dim() >= 2 and post.alpha.shape[1] == out_channels:
-        scale = post.alpha
-    else:
+        return True, post.alpha
+    return False, None
+
+
+def _recognise(layer: nn.Module, out_channels: int) -> Optional[Plan]:
+    wpre = layer.weight_pre_process
+    basic = _input_hook(layer.activation_pre_process)
+    if basic is None or not _is(wpre, "XNORWeightBinarizer"):
+        return None
+    ok, scale = _post_scale(layer.activation_post_process, out_channels)
+    if not ok:
         return None
     return Plan(bool(wpre.center_weights), bool(wpre.compute_alpha), scale, ste=basic)
+
+
+def _recognise_real(layer: nn.Module, out_channels: int) -> Optional[RealPlan]:
+    """The hooks of a layer that binarises its activations only: the input hooks of ``_recognise``, a weight hook that is
+    exactly ``torch.nn.Identity`` or this package's / the reference's ``Identity`` with no forward hooks on it (a fused
+    launch would not fire them), and the post hooks of ``_recognise``.  ``_recognise`` returns ``None`` for these layers,
+    so the fused executors keep declining them."""
+    wpre = layer.weight_pre_process
+    basic = _input_hook(layer.activation_pre_process)
+    if basic is None:
+        return None
+    if not (type(wpre) is nn.Identity or _is(wpre, "Identity")) or wpre._forward_hooks or wpre._forward_pre_hooks:
+        return None
+    ok, scale = _post_scale(layer.activation_post_process, out_channels)
+    if not ok:
+        return None
+    return RealPlan(scale, ste=basic)
 
 
 def _eligible(layer: nn.Module, x: torch.Tensor, plan: Plan) -> bool:
@@ -157,6 +204,33 @@ def plan_conv2d_train(layer, x: torch.Tensor) -> Optional[Plan]:
     if x.dim() != 4 or not (_numeric_padding(layer) or (training.GROUPED and _grouped_numeric_padding(layer))):
         return None
     plan = _recognise(layer, layer.out_channels)
+    return plan if plan is not None and plan.ste and _eligible_train(layer, x) else None
+
+
+def _real_applies(layer, x: torch.Tensor) -> Optional[RealPlan]:
+    """What both real-weight plans ask: the switch, a dense zero-padded ``Conv2d`` with the recognised hooks, fp32 without
+    autocast, a geometry of ``hipops.sconv_supported``."""
+    if not REAL_WEIGHTS or x.dim() != 4 or not _numeric_padding(layer) or torch.is_autocast_enabled():
+        return None
+    if x.dtype != torch.float32 or layer.weight.dtype != torch.float32:
+        return None
+    plan = _recognise_real(layer, layer.out_channels)
+    if plan is None or not hipops.sconv_supported(x.shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation):
+        return None
+    return plan
+
+
+def plan_conv2d_real(layer, x: torch.Tensor) -> Optional[RealPlan]:
+    """Plan for the inference forward of a layer with binary activations and real weights (consulted when both XNOR plans
+    declined; ``REAL_WEIGHTS``, read at every call)."""
+    plan = _real_applies(layer, x)
+    return plan if plan is not None and _eligible(layer, x, plan) else None
+
+
+def plan_conv2d_real_train(layer, x: torch.Tensor) -> Optional[RealPlan]:
+    """The same for a training-mode forward (only consulted when ``plan_conv2d_real`` declined): the input hook's
+    backward must be the hard-tanh STE."""
+    plan = _real_applies(layer, x)
     return plan if plan is not None and plan.ste and _eligible_train(layer, x) else None
 
 
@@ -310,6 +384,8 @@ def invalidate(module: nn.Module, executors: bool = True) -> int:
     for m in module.modules():
         if m.__dict__.pop("_bnn_packed", None) is not None:
             n += 1
+        if m.__dict__.pop(REAL_KEY, None) is not None:
+            n += 1
         m.__dict__.pop("_bnn_packed_replicas", None)
         if executors:       # (an executor that re-derives ITSELF (refresh) passes False: it may be that very object)
             drop_executor(m)
@@ -348,6 +424,43 @@ def conv2d_train(layer, x: torch.Tensor, plan: Plan) -> torch.Tensor:
     native.require()
     out = training.conv2d_train(layer, x, plan, packed_weight(layer, plan, sync=False, fresh=True))
     _bump("conv2d_train")
+    return out
+
+
+# ``layer.__dict__`` key of the cached weight fragments of a real-weight layer (``real_packed_weight``)
+REAL_KEY = "_bnn_packed_real"
+
+
+def real_packed_weight(layer) -> hipops.SconvWeight:
+    """Cached ``hipops.sconv_pack_weight(layer.weight)``, the way ``packed_weight`` caches: keyed on the weight's storage
+    pointer, version counter and a recipe tag of its own; dropped by ``invalidate()`` and by ``train()`` / ``eval()``;
+    never trusted under ``BNN_AMD_STRICT_WEIGHTS=1``."""
+    w = layer.weight
+    key = (w.data_ptr(), w._version, str(w.device), tuple(w.shape), "sconv")
+    cached = layer.__dict__.get(REAL_KEY)
+    if cached is not None and cached[0] == key and not strict_weights():
+        return cached[1]
+    pw = hipops.sconv_pack_weight(w)
+    layer.__dict__[REAL_KEY] = (key, pw)
+    _bump("weight_packs")
+    return pw
+
+
+def conv2d_real(layer, x: torch.Tensor, plan: RealPlan) -> torch.Tensor:
+    """HIP evaluation of ``bnn.layers.Conv2d.forward`` for a layer with an identity weight hook: one launch, bias and
+    scale in its epilogue (csrc/sconv.hip)."""
+    native.require()
+    out = hipops.sconv2d(x, real_packed_weight(layer), layer.bias, plan.scale, layer.stride, layer.padding)
+    _bump("conv2d_real")
+    return out
+
+
+def conv2d_real_train(layer, x: torch.Tensor, plan: RealPlan) -> torch.Tensor:
+    """Same forward under autograd (``training.sconv2d_train``); the weight is re-packed on every forward."""
+    from . import training
+    native.require()
+    out = training.sconv2d_train(layer, x, plan)
+    _bump("conv2d_real_train")
     return out
 
 

@@ -1404,6 +1404,60 @@ def grad_supported(x_shape, w_shape, stride, padding, dilation) -> bool:
     return k == (1, 1) and _pair(stride) == (1, 1) and _pair(padding) == (0, 0)
 
 
+def sconv_supported(x_shape, w_shape, stride, padding, dilation) -> bool:
+    """Shapes the real-weight convolution kernel (csrc/sconv.hip) covers: exactly those of ``grad_supported``, whose
+    weight-gradient kernel its training step uses (3x3 / stride 1 or 2 / padding 1 and 1x1 / stride 1 / padding 0,
+    dilation 1, ``groups == 1``, input width <= 64)."""
+    return len(x_shape) == 4 and len(w_shape) == 4 and x_shape[1] == w_shape[1] \
+        and grad_supported(x_shape, w_shape, stride, padding, dilation)
+
+
+@dataclass
+class SconvWeight:
+    """A real-valued weight ``[O,C,k,k]`` as the MFMA fragments of ``bnn_hip_sconv2d_f32`` (three bf16 terms per weight
+    and one exponent per output channel: include/bnn_hip.h)."""
+    data: torch.Tensor                  # uint8 [bnn_hip_sconv2d_weight_pack_bytes(O, C, k)]
+    shape: Tuple[int, int, int, int]    # (O, C, k, k)
+
+
+def sconv_pack_weight(w: torch.Tensor) -> SconvWeight:
+    """``bnn_hip_sconv2d_pack_weight_f32``: ``W [O,C,k,k]`` fp32 (k = 3 or 1) -> ``SconvWeight``."""
+    w = _require_cuda_f32(w.detach(), "weight")
+    if w.dim() != 4 or w.shape[2] != w.shape[3]:
+        raise native.NativeError(f"bnn_amd: sconv_pack_weight expects [O,C,k,k], got shape {tuple(w.shape)}")
+    lib = native.require()
+    O, C, k = w.shape[0], w.shape[1], w.shape[2]
+    with torch.cuda.device(w.device):
+        packed = torch.empty(int(lib.bnn_hip_sconv2d_weight_pack_bytes(O, C, k)), dtype=torch.uint8, device=w.device)
+        native.check(lib.bnn_hip_sconv2d_pack_weight_f32(w.data_ptr(), O, C, k, packed.data_ptr(), _stream(w.device)),
+                     "bnn_hip_sconv2d_pack_weight_f32")
+    return SconvWeight(packed, (O, C, k, k))
+
+
+def sconv2d(x: torch.Tensor, packed: SconvWeight, bias=None, post_scale=None, stride=1, padding=None) -> torch.Tensor:
+    """``(conv2d(s(x), W) + bias[o]) * post_scale[o]`` in one launch from the fp32 NCHW ``x`` (``bnn_hip_sconv2d_f32``):
+    ``s(x)`` = +1 / -1 / 0 for x > 0 / x < 0 / anything else.  ``padding`` must be ``k // 2`` (``None``: that).  A geometry
+    outside ``sconv_supported`` raises (``BNN_HIP_ERR_UNSUPPORTED``)."""
+    x = _require_cuda_f32(x, "activation")
+    O, C, k, _ = packed.shape
+    if x.dim() != 4 or x.shape[1] != C:
+        raise native.NativeError(f"bnn_amd: sconv2d: input {tuple(x.shape)} does not match the weight {packed.shape}")
+    st = _pair(stride)
+    if st[0] != st[1] or (padding is not None and _pair(padding) != (k // 2, k // 2)):
+        native.check(native.ERR_UNSUPPORTED, "bnn_hip_sconv2d_f32")
+    bias = _per_channel(bias, O, "bias")
+    post_scale = _per_channel(post_scale, O, "post_scale")
+    lib = native.require()
+    N, _, H, W = x.shape
+    with torch.cuda.device(x.device):
+        y = torch.empty((N, O, (H - 1) // st[0] + 1, (W - 1) // st[0] + 1), dtype=torch.float32, device=x.device)
+        if N:
+            native.check(lib.bnn_hip_sconv2d_f32(x.data_ptr(), packed.data.data_ptr(), _ptr(bias), _ptr(post_scale),
+                                                 y.data_ptr(), N, O, C, H, W, k, st[0], _stream(x.device)),
+                         "bnn_hip_sconv2d_f32")
+    return y
+
+
 def _grad_pack(w: torch.Tensor, what: str, symbol: str, *switches):
     """The two packers of the input-gradient kernel's weight: ``[O,C,k,k]`` fp32 -> (sign fragments, alpha[O]) through the
     entry point ``symbol(w, O, C, k, *switches, packed, alpha, stream)``."""

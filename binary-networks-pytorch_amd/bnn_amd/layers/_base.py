@@ -39,6 +39,7 @@ class BinaryLayerMixin:
         if bool(mode) != self.training:
             self.__dict__.pop("_bnn_packed", None)
             self.__dict__.pop("_bnn_packed_replicas", None)
+            self.__dict__.pop("_bnn_packed_real", None)
         return super().train(mode)
 
     def _replicate_for_data_parallel(self):
@@ -50,6 +51,7 @@ class BinaryLayerMixin:
         replica = super()._replicate_for_data_parallel()
         replica.__dict__["_bnn_master"] = self.__dict__.get("_bnn_master", self)
         replica.__dict__.pop("_bnn_packed", None)       # (device 0's entry, copied with __dict__)
+        replica.__dict__.pop("_bnn_packed_real", None)
         return replica
 
     @classmethod

@@ -9,6 +9,9 @@
 * the **composition path**: ``post(conv(pre(x), wpre(W), b), x)`` out of torch ops — training,
   CPU tensors, or hook combinations outside the accelerated path.  This is the reference's own
   formulation (``bnn/layers/conv.py:90-97``).
+
+Under ``fastpath.REAL_WEIGHTS`` a ``Conv2d`` whose weight hook is the identity (binary activations, real weights) takes a
+third implementation, ``fastpath.conv2d_real`` / ``conv2d_real_train`` (``csrc/sconv.hip``), where it applies.
 """
 from __future__ import annotations
 
@@ -51,6 +54,13 @@ class Conv2d(BinaryLayerMixin, nn.Conv2d):
         plan = fastpath.plan_conv2d_train(self, input)
         if plan is not None:
             return fastpath.conv2d_train(self, input, plan)
+        if fastpath.REAL_WEIGHTS:   # identity weight hook: binary activations, real weights (csrc/sconv.hip)
+            plan = fastpath.plan_conv2d_real(self, input)
+            if plan is not None:
+                return fastpath.conv2d_real(self, input, plan)
+            plan = fastpath.plan_conv2d_real_train(self, input)
+            if plan is not None:
+                return fastpath.conv2d_real_train(self, input, plan)
         x = self.activation_pre_process(input)
         out = self._conv_forward(x, self.weight_pre_process(self.weight), self.bias)
         return self.activation_post_process(out, input)

@@ -443,6 +443,49 @@ def conv2d_train(layer: nn.Module, x: torch.Tensor, plan, packed) -> torch.Tenso
     return out
 
 
+# ---- binary activations, real weights, in a training step ------------------------------------------------------------
+# Step 0 of the reference's two-stage recipe (``weight: nn.Identity``): ``conv2d(sign(x), W, b)`` under autograd is sign(x)
+# materialised in fp32, the library's fp32 convolution, and the fp32 x and fp32 sign(x) kept alive.  ``SignConvTrainFn`` is
+# the layer as one autograd function (``fastpath.REAL_WEIGHTS``):
+#   forward :  the weight fragments (re-packed on every forward) and ONE launch of csrc/sconv.hip; keeps x and W
+#   backward:  gW = sum g sign(x): the weight-gradient kernel of csrc/grad.hip, which is the layer's whole dL/dW (the
+#              weight hook is the identity); gx = the library's input gradient + the hard-tanh STE mask (g W has two real
+#              operands and no ternary one: the three-term trick does not apply); gb = the sum of g.
+class SignConvTrainFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, bias, stride):
+        out = hipops.sconv2d(x, hipops.sconv_pack_weight(w), bias, None, stride)
+        ctx.save_for_backward(x, w)
+        ctx.stride, ctx.has_bias = int(stride), bias is not None
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        k, st = w.shape[2], ctx.stride
+        g = g.contiguous()
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.ops.aten.convolution_backward(g, x, w, None, [st, st], [k // 2, k // 2], [1, 1], False, [0, 0], 1,
+                                                     [True, False, False])[0]
+            gx = gx.masked_fill(x.abs() >= 1, 0)                    # hard-tanh STE (bnn/ops.py:68-73)
+        if ctx.needs_input_grad[1]:
+            gw = hipops.bconv_grad_weight(g, x, k, st, reduce=True)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            gb = g.sum((0, 2, 3))
+        return gx, gw, gb, None
+
+
+def sconv2d_train(layer: nn.Module, x: torch.Tensor, plan) -> torch.Tensor:
+    """``bnn.layers.Conv2d.forward`` of a layer with an identity weight hook, autograd recording (``fastpath.
+    plan_conv2d_real_train`` admitted it: dense, fp32, a geometry of ``hipops.sconv_supported``)."""
+    out = SignConvTrainFn.apply(x, layer.weight, layer.bias, layer.stride[0])
+    if plan.scale is not None:                                      # BasicScaleBinarizer (bnn/ops.py:200-202)
+        out = out * plan.scale
+    return out
+
+
 # ---- a binary Linear in a training step -----------------------------------------------------------------------------
 # `F.linear(sign(x), What)` under autograd is sign(x) materialised in fp32, a library fp32 GEMM, and the fp32 x and fp32
 # sign(x) kept alive.  `BinaryLinearTrainFn` is the layer as one autograd function on the kernels of csrc/blinear.hip:

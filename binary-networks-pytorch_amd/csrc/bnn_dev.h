@@ -177,6 +177,11 @@ int launch_dgrad(const float* g, const float* alpha, const void* packed, const v
 int grad_wgrad_splits(int N, int O, int C, int ks);
 int launch_wgrad(const float* g, const void* xin, const void* xin2, int x_planes, float* part, int splits, int N, int O,
                  int C, int H, int W, int ks, int stride, hipStream_t s);
+// sconv.hip: forward of a convolution with binary activations and REAL weights (three bf16 terms per weight)
+size_t sconv_weight_pack_bytes(int O, int C, int ks);
+int launch_sconv_pack_weight(const float* w, int O, int C, int ks, void* packed, hipStream_t s);
+int launch_sconv(const float* x, const void* packed, const float* bias, const float* scale, float* y, int N, int O,
+                 int C, int H, int W, int ks, int stride, hipStream_t s);
 int launch_pack_ste(const float* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M, uint64_t* T,
                     hipStream_t stream);
 // the same planes of fmaf(x, bn_a[c], bn_b[c]) (bn_a == bn_b == null: of x), u never written

@@ -703,6 +703,52 @@ int bnn_hip_bconv_grad_input_packed_f32(const float* g, const float* alpha, cons
   return bnn::launch_dgrad(g, alpha, packed, T, 1, gx, N, O, C, H, W, ksize, stride, static_cast<hipStream_t>(stream));
 }
 
+// Entry contract of the real-weight convolution (csrc/sconv.hip): the geometry of check_grad_shape (3x3 / stride 1 or 2
+// and 1x1 / stride 1, input rows of at most 64 pixels), and x [N,C,H,W] and y [N,O,Ho,Wo] inside the 32-bit range of a
+// sized buffer descriptor (kMaxDescBytes).
+static int check_sconv_shape(int N, int O, int C, int H, int W, int ksize, int stride) {
+  const int st = check_grad_shape(N, O, C, H, W, ksize, stride);
+  if (st != BNN_HIP_OK) return st;
+  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+  if (mulc(mulc(N, C, H, W), 4) > kMaxDescBytes || mulc(mulc(N, O, Ho, Wo), 4) > kMaxDescBytes) return BNN_HIP_ERR_TOO_LARGE;
+  return BNN_HIP_OK;
+}
+
+// fragments of the packed weight stay addressable by a 32-bit element index (as the other weight layouts)
+static int check_sconv_weight(int O, int C, int ksize) {
+  if (O <= 0 || C <= 0) return BNN_HIP_ERR_INVALID_ARG;
+  if (!grad_ks_ok(ksize)) return BNN_HIP_ERR_UNSUPPORTED;
+  if (mulc(((long long)C + 31) / 32, ksize * ksize, ((long long)O + 15) / 16, 3 * 64 * 8) > kMaxElems) return BNN_HIP_ERR_TOO_LARGE;
+  return BNN_HIP_OK;
+}
+
+size_t bnn_hip_sconv2d_weight_pack_bytes(int O, int C, int ksize) {
+  return check_sconv_weight(O, C, ksize) == BNN_HIP_OK ? bnn::sconv_weight_pack_bytes(O, C, ksize) : 0;
+}
+
+int bnn_hip_sconv2d_pack_weight_f32(const float* w, int O, int C, int ksize, void* packed, void* stream) {
+  if (!w || !packed) return BNN_HIP_ERR_INVALID_ARG;
+  const int st = check_sconv_weight(O, C, ksize);
+  if (st != BNN_HIP_OK) return st;
+  if (!aligned(packed, 16) || !aligned(w, 4)) return BNN_HIP_ERR_INVALID_ARG;
+  g_launches.fetch_add(2, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_sconv_pack_weight(w, O, C, ksize, packed, static_cast<hipStream_t>(stream));
+}
+
+int bnn_hip_sconv2d_f32(const float* x, const void* packed, const float* bias, const float* post_scale, float* y, int N,
+                        int O, int C, int H, int W, int ksize, int stride, void* stream) {
+  if (!x || !packed || !y) return BNN_HIP_ERR_INVALID_ARG;
+  int st = check_sconv_shape(N, O, C, H, W, ksize, stride);
+  if (st == BNN_HIP_OK) st = check_sconv_weight(O, C, ksize);
+  if (st != BNN_HIP_OK) return st;
+  if (!aligned(packed, 16) || !aligned(x, 4) || !aligned(y, 4) || !aligned(bias, 4) || !aligned(post_scale, 4))
+    return BNN_HIP_ERR_INVALID_ARG;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_sconv(x, packed, bias, post_scale, y, N, O, C, H, W, ksize, stride, static_cast<hipStream_t>(stream));
+}
+
 int bnn_hip_pack_act_ste_f32(const float* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M, uint64_t* T,
                              void* stream) {
   if (!T) return BNN_HIP_ERR_INVALID_ARG;

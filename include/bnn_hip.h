@@ -61,7 +61,9 @@
 extern "C" {
 #endif
 
-/* ABI 16: + bnn_hip_bconv2d_route, bnn_hip_bconv2d_dot_route and bnn_hip_conv_route (which kernel a convolution runs:
+/* Additive entry points of ABI 16 for the convolution with binary activations and real weights (no struct or signature
+ * changed): + bnn_hip_sconv2d_weight_pack_bytes, bnn_hip_sconv2d_pack_weight_f32, bnn_hip_sconv2d_f32 (csrc/sconv.hip).
+ * ABI 16: + bnn_hip_bconv2d_route, bnn_hip_bconv2d_dot_route and bnn_hip_conv_route (which kernel a convolution runs:
  * host-only queries answered by the launch ladder itself; no other struct or signature changed).
  * Additive entry points of ABI 16 for the fully-connected layer (no struct or signature changed): + bnn_hip_blinear_direct,
  * bnn_hip_blinear_grad_input_f32, bnn_hip_blinear_grad_weight_f32, bnn_hip_blinear_grad_weight_splits (csrc/blinear.hip).
@@ -417,6 +419,38 @@ int bnn_hip_bconv_grad_input_f32(const float* g, const float* alpha, const void*
 int bnn_hip_bconv_grad_weight_splits(int N, int O, int C, int ksize);
 int bnn_hip_bconv_grad_weight_f32(const float* g, const float* x, float* partial, int splits,
                                   int N, int O, int C, int H, int W, int ksize, int stride, void* stream);
+
+/* ---- binary activations, REAL weights (additive entry points of ABI 16, no struct or signature changed): step 0 of
+ * the reference's two-stage recipe (examples/recepies/imagenet-baseline.yaml: weight: nn.Identity), the layer
+ * bnn/layers/conv.py:90-97 evaluates as conv2d(sign(x), W, b) * alpha in fp32.  One launch from the fp32 NCHW input:
+ *
+ *   bnn_hip_sconv2d_f32   y[n,o,p] = (sum_{c,tap} s(x)[n,c,p*stride + tap - ksize/2] * W[o,c,tap] + bias[o]) * post_scale[o]
+ *
+ * s(x) = +1 for x > 0, -1 for x < 0, 0 otherwise (+-0, NaN, the zero padding: the predicate of the bit planes).  A GEMM
+ * with one operand exactly {-1,0,+1} and one real operand split into three bf16 terms: three v_mfma_f32_16x16x32_bf16
+ * per product, every product exact, fp32 accumulation (the rounding class of an fp32 convolution).
+ * Geometry: that of the gradient kernels above — ksize 3 (padding 1, stride 1 or 2) or 1 (padding 0, stride 1),
+ * dilation 1, groups 1, W <= 64, any N, C, O.  Anything else: BNN_HIP_ERR_UNSUPPORTED (the caller keeps its fp32 path).
+ * x: float32 [N,C,H,W]; y: float32 [N,O,Ho,Wo], Ho = (H-1)/stride + 1; bias, post_scale: float32 [O], each may be NULL
+ * (no add / no multiply).
+ *
+ *   bnn_hip_sconv2d_pack_weight_f32   W [O,C,k,k] fp32 -> `packed` (bnn_hip_sconv2d_weight_pack_bytes(O, C, k) bytes,
+ *                                     16-byte aligned); two launches; once per weight update.
+ *
+ * Byte layout of `packed`, CB = ceil(C/32), OS = ceil(O/16), T = k*k:
+ *   Wp[cb][tap][os][term][lane][e]  bf16 (2 bytes), term 0/1/2 = hi/mid/lo, lane < 64, e < 8: one 16-byte MFMA B
+ *                                   fragment per lane
+ *       = term(W[o = 16 os + (lane & 15)][c = 32 cb + 8 (lane >> 4) + e][tap] * 2^kexp[o]);  0 for o >= O or c >= C
+ *   kexp[16 OS]                     int32 at byte offset CB*T*OS*3*1024; 0 for o >= O
+ * hi = the upper 16 bits of the fp32 value (truncation to bf16), mid the same of (value - hi), lo of (value - hi - mid),
+ * each difference in fp32 (exact).  kexp[o] = 1 - exponent of the largest |W[o,:,:,:]| if that lies in (0, 1) — the
+ * scaled row's largest magnitude is then in [1, 2) — and 0 otherwise; the kernel multiplies its accumulator by
+ * 2^-kexp[o].  bf16 terms of the unscaled weight could not hold what lies below 2^-133: with the row exponent
+ * hi + mid + lo == W * 2^kexp exactly for every finite weight within 2^-100 of its row's largest, subnormals included. */
+size_t bnn_hip_sconv2d_weight_pack_bytes(int O, int C, int ksize);
+int bnn_hip_sconv2d_pack_weight_f32(const float* w, int O, int C, int ksize, void* packed, void* stream);
+int bnn_hip_sconv2d_f32(const float* x, const void* packed, const float* bias, const float* post_scale, float* y, int N,
+                        int O, int C, int H, int W, int ksize, int stride, void* stream);
 
 /* ABI 12: the same two gradients from 3 BITS per input element instead of the fp32 tensor — what a training step has
  * to keep of x between forward and backward (the reference's autograd keeps the fp32 x and the fp32 sign(x),

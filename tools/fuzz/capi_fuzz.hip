@@ -323,6 +323,22 @@ int launch_dgrad(const float* g, const float* alpha, const void* packed, const v
   ++g_reached; REQUIRE(g && alpha && packed && x && gx && al(x, planes ? 8 : 4)); check_grad(N, O, C, H, W, ks, stride);
   return BNN_HIP_OK;
 }
+static void check_sconv_w(int O, int C, int ks) {
+  REQUIRE(O > 0 && C > 0 && (ks == 1 || ks == 3));
+  REQUIRE(((long long)C + 31) / 32 * ks * ks * (((long long)O + 15) / 16) * 3 * 64 * 8 <= (1LL << 31) - 1);
+}
+size_t sconv_weight_pack_bytes(int O, int C, int ks) { check_sconv_w(O, C, ks); return 16; }
+int launch_sconv_pack_weight(const float* w, int O, int C, int ks, void* packed, hipStream_t) {
+  ++g_reached; REQUIRE(w && packed && al(packed, 16) && al(w, 4)); check_sconv_w(O, C, ks); return BNN_HIP_OK;
+}
+int launch_sconv(const float* x, const void* packed, const float* bias, const float* scale, float* y, int N, int O, int C,
+                 int H, int W, int ks, int stride, hipStream_t) {
+  ++g_reached; REQUIRE(x && packed && y && al(packed, 16) && al(x, 4) && al(y, 4) && al(bias, 4) && al(scale, 4));
+  check_grad(N, O, C, H, W, ks, stride); check_sconv_w(O, C, ks);
+  REQUIRE(ks == 3 || stride == 1);
+  REQUIRE((long long)N * C * H * W * 4 <= kDesc && (long long)N * O * ((H - 1) / stride + 1) * ((W - 1) / stride + 1) * 4 <= kDesc);
+  return BNN_HIP_OK;
+}
 int launch_pack_ste(const float* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M, uint64_t* T, hipStream_t) {
   ++g_reached; check_planes(x, N, C, H, W, P, M, 4); REQUIRE(T && al(T, 8)); return BNN_HIP_OK;
 }
@@ -937,6 +953,16 @@ int main(int argc, char** argv) {
         st = bnn_hip_blinear(pick_int(), pick_int(), pick_int(), pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<uint32_t>(),
                              pick_ptr<uint32_t>(), pick_int(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(),
                              pick_ptr<float>(), stream);
+        { // the convolution with real weights (csrc/sconv.hip)
+          const int O = pick_int(), C = pick_int(), ks = (int)(rnd() % 5);
+          if (bnn_hip_sconv2d_weight_pack_bytes(O, C, ks) > ((size_t)1 << 40)) broken("sconv weight pack size");
+          const int s1 = bnn_hip_sconv2d_pack_weight_f32(pick_ptr<float>(), O, C, ks, pick_ptr<char>(), stream);
+          const int s2 = bnn_hip_sconv2d_f32(pick_ptr<float>(), pick_ptr<char>(), pick_ptr<float>(), pick_ptr<float>(),
+                                             pick_ptr<float>(), pick_int(), pick_int(), pick_int(), pick_int(), pick_int(),
+                                             (int)(rnd() % 5), (int)(rnd() % 4), stream);
+          if (!status_ok(s1) || !status_ok(s2)) broken("sconv status");
+          digest = (digest ^ (uint64_t)(uint32_t)s1 ^ ((uint64_t)(uint32_t)s2 << 32)) * 0x100000001B3ull;
+        }
         { // the GEMM-shaped Linear entry points (csrc/blinear.hip)
           const int s1 = bnn_hip_blinear_direct(pick_int(), pick_int(), pick_int(), pick_ptr<float>(), (int)(rnd() % 3),
                                                 pick_ptr<uint32_t>(), pick_ptr<uint32_t>(), pick_int(), pick_ptr<float>(),
