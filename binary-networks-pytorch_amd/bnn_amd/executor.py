@@ -259,6 +259,11 @@ def _activation(act: nn.Module):
     raise FusionError(f"unsupported activation {type(act).__name__}")
 
 
+# HIP graphs (and side streams / events) of executors that were garbage-collected while the calling thread was capturing
+# a HIP graph of its own: kept alive until the next executor is built outside a capture (``FusedResNet.__del__``)
+_PARKED: list = []
+
+
 class FusedResNet(nn.Module):
     """Inference executor for ``bnn_amd.models.ResNet`` built from ``BasicBlock`` (ResNet-18/34),
     ``Bottleneck`` (ResNet-50/101/152: mixed 1x1 / 3x3 binary convolutions), ``PreBasicBlock`` (the
@@ -269,6 +274,8 @@ class FusedResNet(nn.Module):
                  int_thresholds: bool = True, skip_dead_f32: bool = True, fold_shortcut: bool = True,
                  fuse_hblock: bool = True) -> None:
         super().__init__()
+        if _PARKED and not torch.cuda.is_current_stream_capturing():
+            _PARKED.clear()
         # a hierarchical block as ONE launch (bnn_hip_hblock_forward) instead of a packing pass + three convolutions
         self.fuse_hblock = fuse_hblock and os.environ.get("BNN_AMD_FUSE_HBLOCK", "1") != "0"   # ("0": launch by launch, for A/B profiles)
         # the last conv of a block writes no fp32 tensor when the next block consumes sign planes only
@@ -289,6 +296,19 @@ class FusedResNet(nn.Module):
         self._graph = None
         self._split = collections.OrderedDict()   # (input shape, stream) -> _Split (forward_fresh)
         self.refresh()
+
+    def __del__(self):
+        # The executor is in a reference cycle with the model it wraps (the model's dispatch state holds the executor), so
+        # it dies in whichever garbage collection finds it — possibly one that runs while the CALLER captures a HIP graph of
+        # its own around a later ``net(x)``.  Destroying a graph is not an operation a capture admits (the HIP runtime
+        # aborted the process there), so inside a capture the HIP objects are handed to ``_PARKED`` instead.
+        try:
+            held = [self.__dict__.get("_graph")] + [sp.graph for sp in self.__dict__.get("_split", {}).values()]
+            held = [g for g in held if g is not None]
+            if held and torch.cuda.is_current_stream_capturing():
+                _PARKED.append((held, dict(self.__dict__.get("_side", {}))))
+        except Exception:       # interpreter shutdown: nothing to protect any more
+            pass
 
     def _conv(self, conv, bn, act) -> _Conv:
         plan = _plan_of(conv)

@@ -17,7 +17,9 @@ A layer takes the HIP path when ALL of the following hold (otherwise the torch c
   composition otherwise; ``Conv1d`` under autograd stays on the composition
 * a ``Conv2d`` whose weight hook is the identity (binary activations, real weights: step 0 of the two-stage recipe) takes
   a path of its own under ``REAL_WEIGHTS`` (``BNN_AMD_REAL_WEIGHTS=1``, off by default): ``csrc/sconv.hip`` forward, in a
-  training step ``training.SignConvTrainFn``; ``Linear``, ``Conv1d``, grouped layers and fp16 keep the composition
+  training step ``training.SignConvTrainFn``; a ``Linear`` with these hooks takes ``csrc/slinear.hip`` under the same
+  switch (one launch on the row-major input at every ``M``; ``training.SignLinearTrainFn`` in a training step, which
+  keeps three bit planes of the input); ``Conv1d``, grouped layers and fp16 keep the composition
 * ``padding_mode == 'zeros'``, numeric padding, and either ``groups == 1`` or — ``Conv2d`` / ``Conv1d`` under inference,
   ``Conv2d`` under autograd only with ``training.GROUPED`` — ``groups > 1`` (grouped and depthwise layers: ``pack_act``
   + ``bnn_hip_bconv2d_grouped``, two launches; the ResNet executors keep declining them, and so does the training
@@ -48,7 +50,8 @@ from . import hipops, native
 
 _stats_lock = threading.Lock()
 _stats = {"conv2d": 0, "conv1d": 0, "linear": 0, "weight_packs": 0, "conv2d_train": 0, "cell_op": 0, "cell": 0,
-          "cell_op_train": 0, "reduce_train": 0, "linear_train": 0, "conv2d_real": 0, "conv2d_real_train": 0}
+          "cell_op_train": 0, "reduce_train": 0, "linear_train": 0, "conv2d_real": 0, "conv2d_real_train": 0,
+          "linear_real": 0, "linear_real_train": 0}
 
 # Binary activations with REAL weights (step 0 of the reference's two-stage recipe, examples/recepies/imagenet-baseline.yaml:
 # ``weight: nn.Identity``) on the HIP path: ``Conv2d`` layers whose weight hook is the identity take csrc/sconv.hip (one
@@ -231,6 +234,29 @@ def plan_conv2d_real_train(layer, x: torch.Tensor) -> Optional[RealPlan]:
     """The same for a training-mode forward (only consulted when ``plan_conv2d_real`` declined): the input hook's
     backward must be the hard-tanh STE."""
     plan = _real_applies(layer, x)
+    return plan if plan is not None and plan.ste and _eligible_train(layer, x) else None
+
+
+def _real_linear_applies(layer, x: torch.Tensor) -> Optional[RealPlan]:
+    """What both real-weight plans of a ``Linear`` ask: the switch, the recognised hooks, fp32 without autocast."""
+    if not REAL_WEIGHTS or x.dim() < 1 or torch.is_autocast_enabled():
+        return None
+    if x.dtype != torch.float32 or layer.weight.dtype != torch.float32:
+        return None
+    return _recognise_real(layer, layer.out_features)
+
+
+def plan_linear_real(layer, x: torch.Tensor) -> Optional[RealPlan]:
+    """Plan for the inference forward of a ``Linear`` with binary activations and real weights (consulted when both XNOR
+    plans declined; ``REAL_WEIGHTS``, read at every call)."""
+    plan = _real_linear_applies(layer, x)
+    return plan if plan is not None and _eligible(layer, x, plan) else None
+
+
+def plan_linear_real_train(layer, x: torch.Tensor) -> Optional[RealPlan]:
+    """The same for a training-mode forward (only consulted when ``plan_linear_real`` declined): the input hook's
+    backward must be the hard-tanh STE."""
+    plan = _real_linear_applies(layer, x)
     return plan if plan is not None and plan.ste and _eligible_train(layer, x) else None
 
 
@@ -432,7 +458,8 @@ REAL_KEY = "_bnn_packed_real"
 
 
 def real_packed_weight(layer) -> hipops.SconvWeight:
-    """Cached ``hipops.sconv_pack_weight(layer.weight)``, the way ``packed_weight`` caches: keyed on the weight's storage
+    """Cached ``hipops.sconv_pack_weight(layer.weight)`` (``slinear_pack_weight`` for the 2-D weight of a ``Linear``: the
+    ``ksize = 1`` pack), the way ``packed_weight`` caches: keyed on the weight's storage
     pointer, version counter and a recipe tag of its own; dropped by ``invalidate()`` and by ``train()`` / ``eval()``;
     never trusted under ``BNN_AMD_STRICT_WEIGHTS=1``."""
     w = layer.weight
@@ -440,7 +467,7 @@ def real_packed_weight(layer) -> hipops.SconvWeight:
     cached = layer.__dict__.get(REAL_KEY)
     if cached is not None and cached[0] == key and not strict_weights():
         return cached[1]
-    pw = hipops.sconv_pack_weight(w)
+    pw = hipops.slinear_pack_weight(w) if w.dim() == 2 else hipops.sconv_pack_weight(w)
     layer.__dict__[REAL_KEY] = (key, pw)
     _bump("weight_packs")
     return pw
@@ -461,6 +488,25 @@ def conv2d_real_train(layer, x: torch.Tensor, plan: RealPlan) -> torch.Tensor:
     native.require()
     out = training.sconv2d_train(layer, x, plan)
     _bump("conv2d_real_train")
+    return out
+
+
+def linear_real(layer, x: torch.Tensor, plan: RealPlan) -> torch.Tensor:
+    """HIP evaluation of ``bnn.layers.Linear.forward`` for a layer with an identity weight hook: one launch on the
+    row-major input, bias and scale in its epilogue (csrc/slinear.hip)."""
+    native.require()
+    scale = None if plan.scale is None else plan.scale.reshape(-1)
+    out = hipops.slinear(x, real_packed_weight(layer), layer.bias, scale)
+    _bump("linear_real")
+    return out
+
+
+def linear_real_train(layer, x: torch.Tensor, plan: RealPlan) -> torch.Tensor:
+    """Same forward under autograd (``training.slinear_train``); the weight is re-packed on every forward."""
+    from . import training
+    native.require()
+    out = training.slinear_train(layer, x, plan)
+    _bump("linear_real_train")
     return out
 
 

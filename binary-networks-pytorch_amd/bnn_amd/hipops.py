@@ -1870,6 +1870,65 @@ def blinear_grad_weight(g: torch.Tensor, saved: "SavedAct", reduce: bool = True,
     return part[0] if part.shape[0] == 1 else part.sum(0)
 
 
+# ---- Linear with binary activations and real weights (csrc/slinear.hip) -----------------------------------------------
+def slinear_pack_weight(w: torch.Tensor) -> SconvWeight:
+    """``W [O,F]`` fp32 -> the ``ksize = 1`` pack of ``sconv_pack_weight`` (shape ``(O, F, 1, 1)``): what ``slinear`` reads."""
+    if w.dim() != 2:
+        raise native.NativeError(f"bnn_amd: slinear_pack_weight expects [O,F], got shape {tuple(w.shape)}")
+    return sconv_pack_weight(w.detach().reshape(w.shape[0], w.shape[1], 1, 1))
+
+
+def slinear(x: torch.Tensor, packed: SconvWeight, bias=None, post_scale=None, want_planes: bool = False):
+    """``(s(x) @ W.T + bias[o]) * post_scale[o]`` in one launch of the row-major kernel (``bnn_hip_slinear_f32``): fp32
+    ``[..., F]`` in, fp32 ``[..., O]`` out, ``s(x)`` = +1 / -1 / 0 for x > 0 / x < 0 / anything else taken inside.
+    ``want_planes``: returns ``(out, SavedAct)`` with the three bit planes of ``pack_act_ste`` (shape ``(M, F, 1, 1)``,
+    ``M`` the flattened leading dimensions) from the same pass over ``x``."""
+    x = _require_cuda_f32(x, "activation")
+    O, F = int(packed.shape[0]), int(packed.shape[1])
+    if tuple(packed.shape[2:]) != (1, 1):
+        raise native.NativeError(f"bnn_amd: slinear takes the pack of an [O, F] weight, got {tuple(packed.shape)}")
+    if x.dim() < 1 or x.shape[-1] != F:
+        raise native.NativeError(f"bnn_amd: slinear expects [..., {F}], got shape {tuple(x.shape)}")
+    bias = _per_channel(bias, O, "bias")
+    post_scale = _per_channel(post_scale, O, "post_scale")
+    lib = native.require()
+    lead = tuple(x.shape[:-1])
+    x2 = x.reshape(-1, F)
+    M = x2.shape[0]
+    dev = x.device
+    with torch.cuda.device(dev):
+        out = torch.empty((M, O), dtype=torch.float32, device=dev)
+        sv = _linear_planes(M, F, dev) if want_planes else None
+        step = _linear_rows(M, F, O)
+        for m0 in range(0, M, step):
+            m1 = min(M, m0 + step)
+            pl = [None, None, None] if sv is None else [t[m0:m1].data_ptr() for t in (sv.sign.P, sv.sign.M, sv.T)]
+            native.check(lib.bnn_hip_slinear_f32(m1 - m0, F, O, x2[m0:m1].data_ptr(), packed.data.data_ptr(), _ptr(bias),
+                                                 _ptr(post_scale), out[m0:m1].data_ptr(), *pl, _stream(dev)),
+                         "bnn_hip_slinear_f32")
+    out = out.reshape(*lead, O)
+    return (out, sv) if want_planes else out
+
+
+def ste_mask_(gx: torch.Tensor, saved: "SavedAct") -> torch.Tensor:
+    """The hard-tanh straight-through mask in place (``bnn_hip_ste_mask_f32``): ``gx[m, f]`` becomes ``+0.0`` where the
+    ``T`` plane of ``saved`` (shape ``(M, F, 1, 1)``) says ``|x| >= 1``.  ``gx``: contiguous fp32 with ``M * F`` elements."""
+    M, F = int(saved.shape[0]), int(saved.shape[1])
+    if (not gx.is_cuda or gx.dtype != torch.float32 or not gx.is_contiguous() or tuple(saved.shape[2:]) != (1, 1)
+            or gx.numel() != M * F or gx.dim() < 1 or gx.shape[-1] != F):
+        raise native.NativeError(f"bnn_amd: ste_mask_ expects a contiguous fp32 HIP tensor [..., {F}] of {M} rows, got "
+                                 f"{tuple(gx.shape)} {gx.dtype} on {gx.device}")
+    lib = native.require()
+    g2 = gx.view(M, F)
+    with torch.cuda.device(gx.device):
+        step = _linear_rows(M, F, 1)
+        for m0 in range(0, M, step):
+            m1 = min(M, m0 + step)
+            native.check(lib.bnn_hip_ste_mask_f32(g2[m0:m1].data_ptr(), saved.T[m0:m1].data_ptr(), m1 - m0, F,
+                                                  _stream(gx.device)), "bnn_hip_ste_mask_f32")
+    return gx
+
+
 _BLINEAR_MIN_ROWS = 4096
 
 

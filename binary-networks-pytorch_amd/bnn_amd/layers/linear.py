@@ -32,6 +32,12 @@ class Linear(BinaryLayerMixin, nn.Linear):
         plan = fastpath.plan_linear_train(self, input)
         if plan is not None:
             return fastpath.linear_train(self, input, plan)
+        plan = fastpath.plan_linear_real(self, input)
+        if plan is not None:
+            return fastpath.linear_real(self, input, plan)
+        plan = fastpath.plan_linear_real_train(self, input)
+        if plan is not None:
+            return fastpath.linear_real_train(self, input, plan)
         x = self.activation_pre_process(input)
         out = F.linear(x, self.weight_pre_process(self.weight), self.bias)
         return self.activation_post_process(out, input)

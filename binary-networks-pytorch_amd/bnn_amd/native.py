@@ -206,6 +206,8 @@ _PROTOTYPES = {
     "bnn_hip_sconv2d_weight_pack_bytes": (_sz, [_i, _i, _i]),
     "bnn_hip_sconv2d_pack_weight_f32": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "bnn_hip_sconv2d_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "bnn_hip_slinear_f32": (_i, [_i, _i, _i] + [_vp] * 9),
+    "bnn_hip_ste_mask_f32": (_i, [_vp, _vp, _i, _i, _vp]),
     "bnn_hip_bconv_grad_input_f32": (_i, [_vp] * 5 + [_i] * 7 + [_vp]),
     "bnn_hip_bconv_grad_input_packed_f32": (_i, [_vp] * 5 + [_i] * 7 + [_vp]),
     "bnn_hip_bconv_grad_weight_splits": (_i, [_i, _i, _i, _i]),

@@ -486,6 +486,44 @@ def sconv2d_train(layer: nn.Module, x: torch.Tensor, plan) -> torch.Tensor:
     return out
 
 
+# The ``Linear`` twin (csrc/slinear.hip), under the same switch:
+#   forward :  the weight fragments (re-packed on every forward) and ONE launch that also writes the three bit planes of
+#              x — all that is kept of it, with W
+#   backward:  gx = the library's g W, then the hard-tanh STE mask in place from the T plane (bnn_hip_ste_mask_f32);
+#              gW = sum_m g sign(x) from the sign planes (the weight-gradient kernel of csrc/blinear.hip), the layer's
+#              whole dL/dW; gb = the sum of g.
+class SignLinearTrainFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, bias):
+        out, sv = hipops.slinear(x, hipops.slinear_pack_weight(w), bias, None, want_planes=True)
+        _keep(ctx, [sv], w)
+        ctx.x_shape, ctx.has_bias = tuple(x.shape), bias is not None
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        (saved,), (w,) = _kept(ctx)
+        g = g.reshape(-1, g.shape[-1]).contiguous()
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = hipops.ste_mask_(torch.mm(g, w), saved).reshape(ctx.x_shape)   # hard-tanh STE (bnn/ops.py:68-73)
+        if ctx.needs_input_grad[1]:
+            gw = hipops.blinear_grad_weight(g, saved, reduce=True)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            gb = g.sum(0)
+        return gx, gw, gb
+
+
+def slinear_train(layer: nn.Module, x: torch.Tensor, plan) -> torch.Tensor:
+    """``bnn.layers.Linear.forward`` of a layer with an identity weight hook, autograd recording (``fastpath.
+    plan_linear_real_train`` admitted it: fp32 on one HIP device, recognised hooks)."""
+    out = SignLinearTrainFn.apply(x, layer.weight, layer.bias)
+    if plan.scale is not None:                                      # BasicScaleBinarizer (bnn/ops.py:200-202)
+        out = out * plan.scale
+    return out
+
+
 # ---- a binary Linear in a training step -----------------------------------------------------------------------------
 # `F.linear(sign(x), What)` under autograd is sign(x) materialised in fp32, a library fp32 GEMM, and the fp32 x and fp32
 # sign(x) kept alive.  `BinaryLinearTrainFn` is the layer as one autograd function on the kernels of csrc/blinear.hip:

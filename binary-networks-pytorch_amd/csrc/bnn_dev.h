@@ -182,6 +182,12 @@ size_t sconv_weight_pack_bytes(int O, int C, int ks);
 int launch_sconv_pack_weight(const float* w, int O, int C, int ks, void* packed, hipStream_t s);
 int launch_sconv(const float* x, const void* packed, const float* bias, const float* scale, float* y, int N, int O,
                  int C, int H, int W, int ks, int stride, hipStream_t s);
+// slinear.hip: the same layer as a GEMM on a row-major [M, F] input (the ksize = 1 pack of sconv.hip); P / Mn / T (all or
+// none) receive the three bit planes [M][ceil(F/64)].  launch_ste_mask: gx[m,f] = T bit ? gx[m,f] : +0 in place.
+int slinear_block_channels(int O);
+int launch_slinear(const float* x, const void* packed, const float* bias, const float* scale, float* out, uint64_t* P,
+                   uint64_t* Mn, uint64_t* T, int M, int F, int O, hipStream_t s);
+int launch_ste_mask(float* gx, const uint64_t* T, int M, int F, hipStream_t s);
 int launch_pack_ste(const float* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M, uint64_t* T,
                     hipStream_t stream);
 // the same planes of fmaf(x, bn_a[c], bn_b[c]) (bn_a == bn_b == null: of x), u never written

@@ -1109,6 +1109,33 @@ int bnn_hip_blinear_grad_weight_f32(const float* g, const uint64_t* P, const uin
   return bnn::launch_blinear_wgrad(g, P, Mn, partial, splits, M, O, F, static_cast<hipStream_t>(stream));
 }
 
+// Linear with binary activations and real weights (csrc/slinear.hip): the sizes of check_linear, the weight that of
+// check_sconv_weight with ksize = 1.
+int bnn_hip_slinear_f32(int M, int F, int O, const float* x, const void* packed, const float* bias, const float* post_scale,
+                        float* out, uint64_t* P, uint64_t* Mn, uint64_t* T, void* stream) {
+  if (!x || !packed || !out) return BNN_HIP_ERR_INVALID_ARG;
+  if ((P == nullptr) != (Mn == nullptr) || (P == nullptr) != (T == nullptr)) return BNN_HIP_ERR_INVALID_ARG;
+  int st = check_linear(M, F, O);
+  if (st == BNN_HIP_OK) st = check_sconv_weight(O, F, 1);
+  if (st != BNN_HIP_OK) return st;
+  if (!aligned(packed, 16) || !aligned(x, 4) || !aligned(out, 4) || !aligned(bias, 4) || !aligned(post_scale, 4) ||
+      !aligned(P, 8) || !aligned(Mn, 8) || !aligned(T, 8))
+    return BNN_HIP_ERR_INVALID_ARG;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_slinear(x, packed, bias, post_scale, out, P, Mn, T, M, F, O, static_cast<hipStream_t>(stream));
+}
+
+int bnn_hip_ste_mask_f32(float* gx, const uint64_t* T, int M, int F, void* stream) {
+  if (!gx || !T) return BNN_HIP_ERR_INVALID_ARG;
+  if (M <= 0 || F <= 0) return BNN_HIP_ERR_INVALID_ARG;
+  if (mulc(M, F) > kMaxConvElems) return BNN_HIP_ERR_TOO_LARGE;
+  if (!aligned(gx, 4) || !aligned(T, 8)) return BNN_HIP_ERR_INVALID_ARG;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_ste_mask(gx, T, M, F, static_cast<hipStream_t>(stream));
+}
+
 // Geometry part of a ConvP for the one-launch layer (no packed operands).
 static int fly_convp(const bnn_hip_conv_desc* d, bnn::ConvP* out) {
   int Ho = 0, Wo = 0;

@@ -61,7 +61,9 @@
 extern "C" {
 #endif
 
-/* Additive entry points of ABI 16 for the convolution with binary activations and real weights (no struct or signature
+/* Additive entry points of ABI 16 for the Linear with binary activations and real weights (no struct or signature
+ * changed): + bnn_hip_slinear_f32, bnn_hip_ste_mask_f32 (csrc/slinear.hip).
+ * Additive entry points of ABI 16 for the convolution with binary activations and real weights (no struct or signature
  * changed): + bnn_hip_sconv2d_weight_pack_bytes, bnn_hip_sconv2d_pack_weight_f32, bnn_hip_sconv2d_f32 (csrc/sconv.hip).
  * ABI 16: + bnn_hip_bconv2d_route, bnn_hip_bconv2d_dot_route and bnn_hip_conv_route (which kernel a convolution runs:
  * host-only queries answered by the launch ladder itself; no other struct or signature changed).
@@ -762,6 +764,29 @@ int bnn_hip_blinear_grad_input_f32(const float* g, const float* alpha, const uin
 int bnn_hip_blinear_grad_weight_splits(int M, int O, int F);
 int bnn_hip_blinear_grad_weight_f32(const float* g, const uint64_t* P, const uint64_t* Mn, float* partial, int splits, int M,
                                     int O, int F, void* stream);
+
+/* ---- Linear with binary activations and REAL weights (additive entry points of ABI 16, no struct or signature changed):
+ * the fully-connected layer of step 0 of the two-stage recipe, bnn/layers/linear.py:22-27 with weight: nn.Identity, which
+ * the reference evaluates as F.linear(sign(x), W, b) * alpha in fp32.  One launch from the fp32 row-major input:
+ *
+ *   bnn_hip_slinear_f32   out[m,o] = (sum_f s(x[m,f]) * W[o,f] + bias[o]) * post_scale[o]
+ *
+ * s(x) and the arithmetic are those of bnn_hip_sconv2d_f32: +1 / -1 / 0 for x > 0 / x < 0 / anything else, the weight
+ * split into three bf16 terms, three v_mfma_f32_16x16x32_bf16 per product, fp32 accumulation, then * 2^-kexp[o], + bias[o],
+ * * post_scale[o] in that order.  Leading dimensions are flattened by the caller.
+ * x: float32 [M,F] row-major (4-byte aligned: any F); packed: bnn_hip_sconv2d_pack_weight_f32(W.view(O,F,1,1), O, F, 1),
+ * 16-byte aligned; bias, post_scale: float32 [O], each may be NULL (no add / no multiply); out: float32 [M,O].
+ * P, Mn, T: all NULL, or all three 8-byte aligned [M][ceil(F/64)] words that receive x > 0, x < 0 and |x| < 1 — the planes
+ * of bnn_hip_pack_act_ste_f32 with H = W = 1, pad bits of the last word 0 — from the same pass over x (a mix of NULL and
+ * non-NULL: BNN_HIP_ERR_INVALID_ARG).  Sizes: M, F, O > 0 (BNN_HIP_ERR_INVALID_ARG); M * F and M * O below 2^30 per launch
+ * (BNN_HIP_ERR_TOO_LARGE: split M).
+ *
+ *   bnn_hip_ste_mask_f32  gx[m,f] = T bit (m,f) ? gx[m,f] : +0.0f   in place: the hard-tanh straight-through mask on an
+ *                         input gradient [M,F] (4-byte aligned) from the mask plane T [M][ceil(F/64)] (8-byte aligned);
+ *                         M, F > 0, M * F below 2^30.                                                                  */
+int bnn_hip_slinear_f32(int M, int F, int O, const float* x, const void* packed, const float* bias, const float* post_scale,
+                        float* out, uint64_t* P, uint64_t* Mn, uint64_t* T, void* stream);
+int bnn_hip_ste_mask_f32(float* gx, const uint64_t* T, int M, int F, void* stream);
 
 /* ---- The LAYER in one launch (ABI 10): bnn.layers.Conv2d.forward (bnn/layers/conv.py:90-97) from the float
  * activation tensor to the float output, sign(x) (bnn/ops.py:63-66,151-152) computed ON THE FLY inside the

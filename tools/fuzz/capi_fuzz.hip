@@ -386,6 +386,18 @@ int launch_blinear_wgrad(const float* g, const uint64_t* P, const uint64_t* Mn, 
   REQUIRE(splits >= 1 && splits <= M && (M + (M + splits - 1) / splits - 1) / ((M + splits - 1) / splits) == splits);
   return BNN_HIP_OK;
 }
+int slinear_block_channels(int O) { REQUIRE(O > 0); return O > 64 ? 128 : 64; }
+int launch_slinear(const float* x, const void* packed, const float* bias, const float* scale, float* out, uint64_t* P,
+                   uint64_t* Mn, uint64_t* T, int M, int F, int O, hipStream_t) {
+  ++g_reached; check_linear(M, F, O); check_sconv_w(O, F, 1);
+  REQUIRE(x && packed && out && al(packed, 16) && al(x, 4) && al(out, 4) && al(bias, 4) && al(scale, 4));
+  REQUIRE((P == nullptr) == (Mn == nullptr) && (P == nullptr) == (T == nullptr) && al(P, 8) && al(Mn, 8) && al(T, 8));
+  return BNN_HIP_OK;
+}
+int launch_ste_mask(float* gx, const uint64_t* T, int M, int F, hipStream_t) {
+  ++g_reached; REQUIRE(gx && T && al(gx, 4) && al(T, 8) && M > 0 && F > 0 && (long long)M * F <= (1LL << 30) - 1);
+  return BNN_HIP_OK;
+}
 int launch_pack_weight(const float* w, int O, int C, int KH, int KW, int, int, const bnn_hip_wlayout& L, uint32_t* wb,
                        uint32_t* wz, float* alpha, int32_t* flag, hipStream_t) {
   ++g_reached;
@@ -979,6 +991,14 @@ int main(int argc, char** argv) {
                                                          pick_ptr<float>(), rnd() % 2 ? sp : pick_int(), M, O, F, stream);
           if (!status_ok(s1) || !status_ok(s2) || !status_ok(s3)) broken("blinear status");
           digest = (digest ^ (uint64_t)(uint32_t)s1 ^ ((uint64_t)(uint32_t)s2 << 16) ^ ((uint64_t)(uint32_t)s3 << 32)) * 0x100000001B3ull;
+        }
+        { // the Linear with real weights and the mask kernel (csrc/slinear.hip)
+          const int s1 = bnn_hip_slinear_f32(pick_int(), pick_int(), pick_int(), pick_ptr<float>(), pick_ptr<char>(),
+                                             pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<uint64_t>(),
+                                             pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), stream);
+          const int s2 = bnn_hip_ste_mask_f32(pick_ptr<float>(), pick_ptr<uint64_t>(), pick_int(), pick_int(), stream);
+          if (!status_ok(s1) || !status_ok(s2)) broken("slinear status");
+          digest = (digest ^ (uint64_t)(uint32_t)s1 ^ ((uint64_t)(uint32_t)s2 << 32)) * 0x100000001B3ull;
         }
         break; }
     }
