@@ -112,6 +112,28 @@ class _Conv:
     name: str = ""
     throughput: bool = False   # BNN_HIP_FLAG_THROUGHPUT: several batches in flight (PipelinedInference)
     thr: Optional[torch.Tensor] = None   # integer sign thresholds of a BN + ReLU -> planes-only epilogue
+    w8: Optional[torch.Tensor] = None    # int8 MFMA pack of the weight (csrc/bconv_mfma.hip), built with the plan
+    mfma: dict = field(default_factory=dict)   # (geometry, epilogue) -> this launch runs on the int8 matrix cores
+
+    def _on_matrix_cores(self, act: hipops.PackedAct, residual, out_f32: bool, out_packed: bool, thr, epi) -> bool:
+        """The admission of one launch to the MFMA convolution: the table of ``fastpath`` (shapes that measured faster)
+        and the kernel's own query, asked once per geometry.  The pre-activation switches and the folded shortcut
+        (``epi``) stay on the popcount kernels."""
+        if self.w8 is None or epi:
+            return False
+        key = (tuple(act.shape), act.nonneg, residual is not None, out_f32, out_packed, thr is not None)
+        ok = self.mfma.get(key)
+        if ok is None:
+            lay = self.layer
+            stride = lay.stride[0] if isinstance(lay.stride, (tuple, list)) else lay.stride
+            ok = self.mfma[key] = (
+                fastpath.mfma_conv_admitted(act.shape[1], lay.out_channels, act.shape[2], stride, False)
+                and hipops.bconv2d_mfma_supported(
+                    act.shape, self.weight, nonneg=act.nonneg, bias=lay.bias is not None,
+                    post_scale=self.plan.scale is not None, bn=self.bn_scale is not None, residual=residual is not None,
+                    prelu=self.prelu is not None, relu=self.relu, out_f32=out_f32, out_packed=out_packed,
+                    stride=lay.stride, padding=lay.padding, dilation=lay.dilation, sign_thresholds=thr is not None))
+        return ok
 
     def run(self, act: hipops.PackedAct, *, residual=None, out_f32: bool, out_packed: bool, **epi):
         """``epi``: the pre-activation switches of ``hipops.bconv2d_fused`` (late residual, pack affine, ...)."""
@@ -120,11 +142,13 @@ class _Conv:
             _TAP(self.name, act)
         # BN + ReLU -> planes only (conv1 of a BasicBlock): the sign bit is an integer compare of the dot
         thr = self.thr if (out_packed and not out_f32 and residual is None and not epi) else None
-        return hipops.bconv2d_fused(
-            act, self.weight, bias=lay.bias, post_scale=self.plan.scale, bn_scale=self.bn_scale,
-            bn_shift=self.bn_shift, residual=residual, prelu=self.prelu, relu=self.relu,
-            out_f32=out_f32, out_packed=out_packed, stride=lay.stride, padding=lay.padding,
-            dilation=lay.dilation, throughput=self.throughput, sign_thresholds=thr, **epi)
+        args = dict(bias=lay.bias, post_scale=self.plan.scale, bn_scale=self.bn_scale,
+                    bn_shift=self.bn_shift, residual=residual, prelu=self.prelu, relu=self.relu,
+                    out_f32=out_f32, out_packed=out_packed, stride=lay.stride, padding=lay.padding,
+                    dilation=lay.dilation, throughput=self.throughput, sign_thresholds=thr, **epi)
+        if self._on_matrix_cores(act, residual, out_f32, out_packed, thr, epi):
+            return hipops.bconv2d_mfma_fused(act, self.weight, self.w8, **args)
+        return hipops.bconv2d_fused(act, self.weight, **args)
 
 
 def _plan_of(conv: nn.Module) -> fastpath.Plan:
@@ -321,7 +345,10 @@ class FusedResNet(nn.Module):
         if (self.int_thresholds and scale is not None and relu and prelu is None and conv.bias is None
                 and plan.scale is None and not pw.has_zero):
             thr = hipops.sign_thresholds(pw, scale, shift)
-        return _Conv(conv, plan, pw, scale, shift, relu, prelu, self._names.get(id(conv), ""), self.throughput_mode, thr)
+        # the int8 form of a 3x3 weight, when the switch admits any launch at all (None: no such form for this weight)
+        w8 = hipops.pack_weight_i8(pw) if fastpath.MFMA_CONV != "0" and tuple(pw.shape[2:]) == (3, 3) else None
+        return _Conv(conv, plan, pw, scale, shift, relu, prelu, self._names.get(id(conv), ""), self.throughput_mode, thr,
+                     w8)
 
     @staticmethod
     def _sign_through(act: nn.Module):

@@ -61,6 +61,34 @@ _stats = {"conv2d": 0, "conv1d": 0, "linear": 0, "weight_packs": 0, "conv2d_trai
 # every call (``plan_conv2d_real`` / ``plan_conv2d_real_train``).  With it off nothing here runs.
 REAL_WEIGHTS = os.environ.get("BNN_AMD_REAL_WEIGHTS", "0") == "1"
 
+# The dense 3x3 convolutions of the fused ResNet executor on the int8 matrix cores (csrc/bconv_mfma.hip: the same integer
+# dot from v_mfma_i32_16x16x64_i8, the same float epilogue, the same bits) instead of the XNOR-popcount kernels.
+# BNN_AMD_MFMA_CONV: "1" (default) — the launches listed in MFMA_CONV_SHAPES; "0" — none, the popcount launches as
+# before; "all" — every launch bnn_hip_bconv2d_mfma_supported takes (for measuring a new shape).  Read when an executor
+# plans its layers (``FusedResNet.refresh``), never during a graph capture.
+MFMA_CONV = os.environ.get("BNN_AMD_MFMA_CONV", "1")
+# The admission rule, in one place: (C, O, H of the input, stride, folded shortcut) -> (popcount us, MFMA us) of that
+# launch in a kernel trace of one ResNet-18 forward at batch 256 on MI355X, one batch in flight
+# (profiles/mfma_conv_kernel_roofline.md).  A shape is listed only where the MFMA launch measured faster.
+MFMA_CONV_SHAPES = {
+    (128, 128, 28, 1, False): ((51.9, 37.8), (58.6, 45.2)),   # layer2.1.conv1, layer2.1.conv2
+    (128, 256, 28, 2, False): ((30.3, 26.2),),                # layer3.0.conv1
+    (256, 256, 14, 1, False): ((54.9, 33.4), (56.9, 38.9)),   # layer3.1.conv1, layer3.1.conv2
+    (256, 512, 14, 2, False): ((33.6, 23.8),),                # layer4.0.conv1
+    (512, 512, 7, 1, False): ((60.6, 32.0), (63.3, 39.2)),    # layer4.1.conv1, layer4.1.conv2
+    # measured slower or level, left on the popcount kernels:
+    #   (64, 64, 56, 1, False)   layer1.*.conv1 51.6 -> 49.2, 51.2 -> 48.0 but layer1.*.conv2 81.2 -> 86.2, 63.3 -> 69.6
+    #                            (the fp32 residual and output streams: 54 us of HBM time, not hidden behind the MFMAs)
+    #   (64, 128, 56, 2, False)  layer2.0.conv1 28.9 -> 30.0
+    # not built: the folded shortcut (layer2.0 / 3.0 / 4.0 conv2) — bnn_hip_bconv2d_mfma_supported says no
+}
+
+
+def mfma_conv_admitted(C: int, O: int, H: int, stride: int, fold: bool) -> bool:
+    if MFMA_CONV == "0":
+        return False
+    return MFMA_CONV == "all" or (C, O, H, stride, fold) in MFMA_CONV_SHAPES
+
 
 def stats() -> dict:
     """Counters of HIP-path invocations (tests use them to prove which path ran)."""

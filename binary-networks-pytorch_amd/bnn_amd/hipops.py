@@ -1121,6 +1121,60 @@ def bconv2d_fused(a: PackedAct, w: PackedWeight, **kw):
     return y, pk
 
 
+def pack_weight_i8(w: PackedWeight) -> Optional[torch.Tensor]:
+    """The int8 MFMA-fragment form of a packed 3x3 weight (``bnn_hip_pack_weight_i8``, layout: include/bnn_hip.h), or
+    ``None`` where there is none (not 3x3, C or O no multiple of 64, a grouped pack).  One launch; ``w.alpha`` is used
+    unchanged beside it."""
+    lib = native.require()
+    if w.windowed or w.groups != 1:
+        return None
+    O, C, KH, KW = w.shape
+    nbytes = int(lib.bnn_hip_weight_i8_bytes(O, C, KH, KW))
+    if nbytes == 0:
+        return None
+    dev = w.wbits.device
+    with torch.cuda.device(dev):
+        w8 = torch.empty(nbytes, dtype=torch.int8, device=dev)
+        native.check(lib.bnn_hip_pack_weight_i8(w.wbits.data_ptr(), w.wnz.data_ptr(), O, C, KH, KW, w8.data_ptr(),
+                                                _stream(dev)), "bnn_hip_pack_weight_i8")
+    return w8
+
+
+def bconv2d_mfma_supported(a_shape, w: PackedWeight, *, nonneg: bool = False, bias=False, post_scale=False, bn=False,
+                           residual=False, prelu=False, relu=False, out_f32=True, out_packed=False, stride=1, padding=0,
+                           dilation=1, sign_thresholds=False, shortcut=False, epi_flags: int = 0, pack_affine=False,
+                           out_c_total: int = 0) -> bool:
+    """Whether ``bconv2d_mfma_fused`` takes a launch of this geometry and epilogue (``bnn_hip_bconv2d_mfma_supported``:
+    host only, nothing is launched or allocated).  The epilogue is given by what it contains (truth values), not by
+    tensors: an aligned stand-in pointer takes the place of each operand that is present."""
+    lib = native.require()
+    if w.windowed or w.groups != 1:
+        return False
+    d = _desc(tuple(a_shape), w.shape, stride, padding, dilation, native.FLAG_ACT_NONNEG if nonneg else 0)
+    p = 0x10000   # never dereferenced
+    on = lambda v: p if v else None
+    e = native.Epilogue(p, on(bias), on(post_scale), on(bn), on(bn), on(residual), on(prelu), int(bool(relu)), epi_flags,
+                        on(out_f32), on(out_packed), on(out_packed), on(pack_affine), on(pack_affine), 0, out_c_total,
+                        on(sign_thresholds), *((p, p, p, p, p, 64, 0) if shortcut else ()))
+    return bool(lib.bnn_hip_bconv2d_mfma_supported(ctypes.byref(d), ctypes.byref(e)))
+
+
+def bconv2d_mfma_fused(a: PackedAct, w: PackedWeight, w8: torch.Tensor, **kw):
+    """``bconv2d_fused`` with the dot on ``v_mfma_i32_16x16x64_i8`` (``bnn_hip_bconv2d_mfma_fused``): same arguments, same
+    bits.  ``w8 = pack_weight_i8(w)``.  Raises where ``bconv2d_mfma_supported`` says no."""
+    lib = native.require()
+    y, pk, nonneg, launches = _fused_launches(a, w, "bconv2d_mfma_fused", **kw)
+    dev = a.P.device
+    with torch.cuda.device(dev):
+        for dd, e, n0, n1 in launches:
+            native.check(lib.bnn_hip_bconv2d_mfma_fused(ctypes.byref(dd), a.P[n0:n1].data_ptr(), a.M[n0:n1].data_ptr(),
+                                                        w8.data_ptr(), ctypes.byref(e), _stream(dev)),
+                         "bnn_hip_bconv2d_mfma_fused")
+    if pk is not None:
+        pk.nonneg = nonneg
+    return y, pk
+
+
 def bconv2d_route(a: PackedAct, w: PackedWeight, *, fused: bool = True, raw_dot: bool = False, **kw) -> dict:
     """Which kernel ``bconv2d_fused(a, w, **kw)`` runs (``bnn_hip_bconv2d_route``: the launch ladder itself answers,
     nothing is launched) as a dict of the fields of ``bnn_hip_conv_route``; of the first launch when the batch is split.

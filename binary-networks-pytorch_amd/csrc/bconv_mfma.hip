@@ -1,0 +1,359 @@
+// bconv_mfma.hip — the dense 3x3 binary convolution as an implicit GEMM on v_mfma_i32_16x16x64_i8.
+//
+// Same arithmetic as bconv.hip (bnn/layers/conv.py:90-97): the integer dot of sign(x) in {-1,0,+1} with sign(W) in
+// {-1,0,+1} over the 3x3 window.  Both operands are exact in int8 and the int32 accumulation of at most 9 C <= 2^20
+// products of magnitude <= 1 is exact, so the accumulator IS the popcount kernels' dot; it then enters
+// bconv_core.h: epilogue<>() — the same float operations in the same order — and the results are the same bits.
+//
+// GEMM view: rows = output channels (operand A: the int8 weight pack, straight from global / L2 into registers), columns
+// = output pixels (operand B: int8 activations from LDS), k = (64-channel group, tap, channel in the group).
+//   workgroup (4 waves) = TP consecutive output pixels (linear index over N x Ho x Wo: a tile may span rows and images)
+//                         x TO output channels, TP x TO = 256 x 64 or 128 x 128; one wave = 64 pixels x 64 channels
+//                         = 4 x 4 MFMA tiles of 16 x 16, 64 int32 accumulators per lane
+//   per 64-channel group: the sign-plane words of every input pixel the tile touches — one contiguous run of the linear
+//                         input index n H W + y W + x, its neighbours one row up and down included — are expanded once
+//                         into LDS as 64 int8 per pixel (P bit -> 0x01, M bit -> 0xFF; P and M are exclusive).  The nine
+//                         taps are shifted 16-byte reads of that patch; a tap in the zero padding (or in the neighbouring
+//                         row / image, where the shifted index lands) reads a row of zero bytes instead.
+//   per k-step (one tap of one group): 4 ds_read_b128 + 4 global_load_dwordx4 feed 16 MFMAs.
+// The k order inside a fragment is the kernel's own choice (integer sums do not depend on it): byte e of lane l is
+// channel 16 (l >> 4) + e of the group in BOTH operands.  What the hardware fixes is that lane l holds row / column
+// l & 15 of A / B and that D has column l & 15 and rows 4 (l >> 4) + r in register r.
+// Epilogue: the accumulators go through LDS, 32 channels at a time, to lane = pixel; from there on it is the popcount
+// kernels' straight-line epilogue (coalesced NCHW stores, one 32-channel plane word per lane).
+#include "bconv_core.h"
+
+namespace bnn {
+
+namespace {
+
+using i32x4 = __attribute__((ext_vector_type(4))) int;
+
+constexpr int kMfmaThreads = 256;
+constexpr int kAccStride = 68;  // int32 per channel row of the transpose buffer: 4 rows apart = 16 banks apart
+constexpr int kAccBytes = 4 * 32 * kAccStride * 4;  // four waves x 32 channels
+constexpr int kMaxLds = 64 * 1024;
+constexpr int kPatchSlots = 4;  // patch pixels per thread (1024 pixels = the LDS limit): the plane words of the next group wait in registers
+
+struct MfmaGeo {
+  int tp;          // output pixels per workgroup: 256 (four waves side by side) or 128 (two by two)
+  int groups;      // C / 64
+  int ihw;         // H * W
+  int patch_cap;   // pixels of the LDS patch (the zero row sits behind them)
+  int nn;          // M plane all zero
+  int n_in;        // N * H * W
+  uint32_t m_ihw;  // fast_div by ihw
+  int s_ihw;
+};
+
+// 4 bits -> 4 bytes of 0 / 1: bit i lands at 8 i  (0x00204081 = 1 + 2^7 + 2^14 + 2^21; both factors below 2^24)
+__device__ __forceinline__ uint32_t spread4(uint32_t word, int sh) {
+  return __umul24((word >> sh) & 15u, 0x00204081u) & 0x01010101u;
+}
+__device__ __forceinline__ uint32_t expand4(uint32_t pw, uint32_t mw, int sh, bool nn) {
+  const uint32_t p = spread4(pw, sh);
+  if (nn) return p;
+  return p | (spread4(mw, sh) * 0xFFu);  // bytes of 0 / 1 times 255: no carry between bytes
+}
+
+// linear input index of the window centre of output pixel q (monotone in q)
+__device__ __forceinline__ int centre_of(const Geo& g, const MfmaGeo& mg, int q, int* oy, int* ox) {
+  const int hw = g.Ho * g.Wo;
+  const int n = (int)fast_div((uint32_t)q, g.m_hw, g.s_hw);
+  const int r = q - n * hw;
+  *oy = (int)fast_div((uint32_t)r, g.m_wo, g.s_wo);
+  *ox = r - *oy * g.Wo;
+  return n * mg.ihw + *oy * g.sh * g.Wd + *ox * g.sw;
+}
+
+template <int EP>
+__global__ __launch_bounds__(kMfmaThreads) void bconv_mfma_kernel(const uint32_t* __restrict__ P,
+                                                                  const uint32_t* __restrict__ M,
+                                                                  const int8_t* __restrict__ W8, BNN_EPI_PARAMS,
+                                                                  const Geo g, const MfmaGeo mg) {
+  BNN_EPI_INIT;
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  // (wave-uniform by construction; said so, the per-channel constants of the epilogue stay on the scalar path)
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lrow = lane & 15, lgrp = lane >> 4;
+  const int pwaves = mg.tp >> 6;                 // waves along the pixels: 4 or 2
+  const int wave_pix = (wave % pwaves) * 64;     // first pixel of this wave inside the tile
+  const int wave_ch = (wave / pwaves) * 64;      // first channel of this wave inside the workgroup's channels
+  const int q0 = blockIdx.x * mg.tp;
+  const int o_wave = blockIdx.y * (64 * (4 / pwaves)) + wave_ch;
+
+  // the tile's run of input pixels
+  int ty, tx;
+  const int c_first = centre_of(g, mg, q0, &ty, &tx);
+  const int c_last = centre_of(g, mg, min(q0 + mg.tp, g.npix) - 1, &ty, &tx);
+  const int l_lo = max(c_first - g.Wd - 1, 0);
+  const int patch_len = min(min(c_last + g.Wd + 1, mg.n_in - 1) - l_lo + 1, mg.patch_cap);
+  const int zero_idx = mg.patch_cap;
+
+  // this lane's four B columns (pixels 16 pt + lrow of the wave): patch index of the window centre, valid taps
+  int base[4];
+  uint32_t okm[4];
+#pragma unroll
+  for (int pt = 0; pt < 4; ++pt) {
+    const int q = min(q0 + wave_pix + 16 * pt + lrow, g.npix - 1);
+    int oy, ox;
+    base[pt] = centre_of(g, mg, q, &oy, &ox) - l_lo;
+    uint32_t m = 0u;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      const int iy = oy * g.sh - 1 + t / 3, ix = ox * g.sw - 1 + t % 3;
+      const bool ok = (unsigned)iy < (unsigned)g.H && (unsigned)ix < (unsigned)g.Wd;
+      m |= (ok ? 1u : 0u) << t;
+    }
+    okm[pt] = m;
+  }
+
+  i32x4 acc[4][4];
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+    for (int pt = 0; pt < 4; ++pt) acc[ct][pt] = i32x4{0, 0, 0, 0};
+
+  if (tid < 4) reinterpret_cast<uint4*>(lds + (size_t)zero_idx * 64)[tid] = uint4{0u, 0u, 0u, 0u};
+
+  const bool nn = mg.nn != 0;
+  const uint2* P2 = reinterpret_cast<const uint2*>(P);
+  const uint2* M2 = reinterpret_cast<const uint2*>(M);
+  // A fragments of this wave: [o / 64][group][tap][16-channel tile][lane][16 bytes]
+  const int8_t* wbase = W8 + (size_t)(o_wave >> 6) * mg.groups * (9 * 4096) + lane * 16;
+
+  // Software pipeline.  A fragments: k-step k + 2 (contiguous behind k and k + 1, across groups too) is requested before
+  // the MFMAs of k-step k — three register sets in rotation, and nine taps per group bring the rotation back to its
+  // start.  B fragments: the next tap's, within a group.  Plane words: the next group's are requested into registers
+  // before the current group's MFMAs and expanded into the patch behind them.
+  const int ksteps = mg.groups * 9;
+  auto a_load = [&](i32x4 (&dst)[4], int k) {
+    const int8_t* src = wbase + (size_t)min(k, ksteps - 1) * 4096;  // (past the end: the last k-step's again, never used)
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) dst[ct] = *reinterpret_cast<const i32x4*>(src + ct * 1024);
+  };
+  auto b_frag = [&](int pt, int t) -> i32x4 {
+    const int off = (t / 3 - 1) * g.Wd + (t % 3 - 1);
+    const int idx = ((okm[pt] >> t) & 1u) ? min(base[pt] + off, zero_idx) : zero_idx;
+    return *reinterpret_cast<const i32x4*>(lds + (size_t)idx * 64 + lgrp * 16);
+  };
+  // patch pixels tid, tid + 256, ... (patch_cap <= kPatchSlots * 256: choose_tile)
+  unsigned wi0[kPatchSlots];
+  uint2 pv[kPatchSlots], mv[kPatchSlots];
+#pragma unroll
+  for (int sl = 0; sl < kPatchSlots; ++sl) {
+    const int L = l_lo + min(tid + sl * kMfmaThreads, patch_len - 1);
+    const int n = (int)fast_div((uint32_t)L, mg.m_ihw, mg.s_ihw);
+    wi0[sl] = (unsigned)(n * mg.groups * mg.ihw + (L - n * mg.ihw));  // uint64 words, group 0
+    pv[sl] = uint2{0u, 0u};
+    mv[sl] = uint2{0u, 0u};
+  }
+  auto request = [&](int gi) {
+#pragma unroll
+    for (int sl = 0; sl < kPatchSlots; ++sl)
+      if (sl * kMfmaThreads < patch_len) {  // (wave-uniform; lanes past the end re-read the last pixel)
+        pv[sl] = P2[wi0[sl] + (unsigned)(gi * mg.ihw)];
+        if (!nn) mv[sl] = M2[wi0[sl] + (unsigned)(gi * mg.ihw)];
+      }
+  };
+  auto expand = [&]() {
+#pragma unroll
+    for (int sl = 0; sl < kPatchSlots; ++sl) {
+      const int i = tid + sl * kMfmaThreads;
+      if (i < patch_len) {
+        uint4* dst = reinterpret_cast<uint4*>(lds + (size_t)i * 64);
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+          const uint32_t pw = h < 2 ? pv[sl].x : pv[sl].y, mw = h < 2 ? mv[sl].x : mv[sl].y;
+          const int s0 = 16 * (h & 1);
+          dst[h] = uint4{expand4(pw, mw, s0, nn), expand4(pw, mw, s0 + 4, nn), expand4(pw, mw, s0 + 8, nn),
+                         expand4(pw, mw, s0 + 12, nn)};
+        }
+      }
+    }
+  };
+
+  request(0);
+  i32x4 a_buf[3][4];
+  a_load(a_buf[0], 0);
+  a_load(a_buf[1], 1);
+#pragma unroll 1
+  for (int gi = 0; gi < mg.groups; ++gi) {
+    __syncthreads();  // the previous group's reads of the patch are done
+    expand();
+    __syncthreads();
+    if (gi + 1 < mg.groups) request(gi + 1);
+    i32x4 b_cur[4];
+#pragma unroll
+    for (int pt = 0; pt < 4; ++pt) b_cur[pt] = b_frag(pt, 0);
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      i32x4 b_nxt[4];
+      a_load(a_buf[(t + 2) % 3], gi * 9 + t + 2);
+      if (t < 8) {
+#pragma unroll
+        for (int pt = 0; pt < 4; ++pt) b_nxt[pt] = b_frag(pt, t + 1);
+      }
+      __builtin_amdgcn_sched_barrier(0);  // keep the requests in front of the MFMAs they hide behind
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+        for (int pt = 0; pt < 4; ++pt)
+          acc[ct][pt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_buf[t % 3][ct], b_cur[pt], acc[ct][pt], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      if (t < 8) {
+#pragma unroll
+        for (int pt = 0; pt < 4; ++pt) b_cur[pt] = b_nxt[pt];
+      }
+    }
+  }
+
+  // ---- epilogue: lane = pixel, 32 channels at a time through LDS ----
+  const Pix px = decode_pixel<true>(g, q0 + wave_pix + lane);
+  int* tbuf = reinterpret_cast<int*>(lds) + wave * (32 * kAccStride);
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int o0 = o_wave + 32 * h;
+    float resv[32];
+    prefetch_residual<32, EP, true>(g, px, o0, epi, resv);
+    __syncthreads();  // the patch (h = 0) / the first half's values (h = 1) have been read
+#pragma unroll
+    for (int c2 = 0; c2 < 2; ++c2)
+#pragma unroll
+      for (int pt = 0; pt < 4; ++pt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          tbuf[(16 * c2 + 4 * lgrp + r) * kAccStride + 16 * pt + lrow] = acc[2 * h + c2][pt][r];
+    __syncthreads();
+    int dot[32];
+#pragma unroll
+    for (int j = 0; j < 32; ++j) dot[j] = tbuf[j * kAccStride + lane];
+    uint32_t pbits = 0u, mbits = 0u;
+    // EP_MIDT: bit = (dot >= T) ^ flip, written as dot * 1 + 0 >= T
+    epilogue<32, EP, true>(g, px, o0, dot, resv, epi, pbits, mbits, 0, 1.0f, 0.0f);
+    uint32_t xorw = 0u;
+    if constexpr (EP == EP_MIDT) xorw = (uint32_t)epi.thr[kThrStride * o0 + 1];
+    store_packed(g, px, o0 >> 5, pbits, mbits, epi, true, xorw);
+  }
+}
+
+// wbits / wnz (bnn_hip_pack_weight_f32) -> int8 A fragments (include/bnn_hip.h: bnn_hip_pack_weight_i8).  One thread per
+// four bytes.
+__global__ __launch_bounds__(256) void pack_weight_i8_kernel(const uint32_t* __restrict__ wbits,
+                                                             const uint32_t* __restrict__ wnz, int O, int taps,
+                                                             int cw32, int cwc, uint32_t* __restrict__ w8) {
+  const int groups = cw32 >> 1, nchunk = cw32 / cwc, per_o = taps * cwc;
+  const size_t total = (size_t)O * groups * taps * 16;  // dwords
+  const size_t d = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (d >= total) return;
+  const int e4 = (int)(d & 3), lane = (int)((d >> 2) & 63), ct = (int)((d >> 8) & 3);
+  size_t rest = d >> 10;
+  const int t = (int)(rest % taps);
+  rest /= taps;
+  const int gi = (int)(rest % groups), ob64 = (int)(rest / groups);
+  const int o = 64 * ob64 + 16 * ct + (lane & 15);
+  const int c0 = 64 * gi + 16 * (lane >> 4) + 4 * e4;  // four consecutive input channels, inside one 32-bit word
+  const int cw_abs = c0 >> 5, ch = cw_abs / cwc, cw = cw_abs - ch * cwc;
+  const size_t wi = ((size_t)((o >> 5) * nchunk + ch) * kOCB + (o & 31)) * per_o + t * cwc + cw;
+  const uint32_t b = wbits[wi] >> (c0 & 31), z = wnz[wi] >> (c0 & 31);
+  uint32_t v = 0u;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint32_t byte = ((z >> k) & 1u) ? (((b >> k) & 1u) ? 0x01u : 0xFFu) : 0u;
+    v |= byte << (8 * k);
+  }
+  w8[d] = v;
+}
+
+// Input pixels between the window centres of the first and the last pixel of any run of `tp` output pixels, at most:
+// (tp - 1) steps of `s`, plus what a change of row and a change of image add beyond such a step.
+long long centre_span(const ConvP& p, int tp) {
+  const long long s = p.sw, k = tp - 1, hw = (long long)p.Ho * p.Wo;
+  const long long row_extra = (long long)p.sh * p.Wd - (long long)p.Wo * s;
+  const long long img_extra = (long long)p.H * p.Wd - (long long)p.Ho * p.sh * p.Wd;
+  return k * s + (k + p.Wo - 1) / p.Wo * (row_extra > 0 ? row_extra : 0) + (k + hw - 1) / hw * (img_extra > 0 ? img_extra : 0);
+}
+
+size_t lds_bytes_of(int patch_cap) {
+  const size_t patch = (size_t)(patch_cap + 1) * 64;
+  return patch > (size_t)kAccBytes ? patch : (size_t)kAccBytes;
+}
+
+// The tile of a launch: 256 pixels x 64 channels where only 64 channels exist or the patch of 128 pixels would not be
+// smaller anyway; 128 x 128 (half the weight traffic per pixel) otherwise.  0: no tile fits the LDS.
+int choose_tile(const ConvP& p, int* patch_cap) {
+  const int order[2] = {(p.O % 128 == 0 && p.C >= 128) ? 128 : 256, (p.O % 128 == 0 && p.C >= 128) ? 256 : 128};
+  for (int tp : order) {
+    if (tp == 128 && p.O % 128 != 0) continue;
+    const long long cap = centre_span(p, tp) + 2LL * p.Wd + 3;
+    if (cap <= kPatchSlots * kMfmaThreads && lds_bytes_of((int)cap) <= (size_t)kMaxLds) {
+      *patch_cap = (int)cap;
+      return tp;
+    }
+  }
+  return 0;
+}
+
+template <int EP>
+void launch_ep(const ConvP& p, const Geo& g, const MfmaGeo& mg, const void* w8, dim3 grid, size_t ldsb, hipStream_t s) {
+  hipLaunchKernelGGL((bconv_mfma_kernel<EP>), grid, dim3(kMfmaThreads), ldsb, s, p.P, p.M,
+                     static_cast<const int8_t*>(w8), BNN_EPI_ACTUALS, g, mg);
+}
+
+}  // namespace
+
+size_t weight_i8_bytes(int O, int C, int KH, int KW) {
+  if (O <= 0 || C <= 0 || KH != 3 || KW != 3 || O % 64 != 0 || C % 64 != 0) return 0;
+  return (size_t)O * (size_t)C * 9;
+}
+
+int launch_pack_weight_i8(const uint32_t* wbits, const uint32_t* wnz, const bnn_hip_wlayout& L, int O, void* w8,
+                          hipStream_t s) {
+  const size_t dwords = (size_t)O * (L.cw32 >> 1) * L.taps * 16;
+  hipLaunchKernelGGL(pack_weight_i8_kernel, dim3((unsigned)((dwords + 255) / 256)), dim3(256), 0, s, wbits, wnz, O, L.taps,
+                     L.cw32, L.cwc, static_cast<uint32_t*>(w8));
+  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+}
+
+// What the kernel covers, stated once (capi.hip asks here for the launch and for bnn_hip_bconv2d_mfma_supported).
+bool mfma_conv_applies(const ConvP& p, int flags) {
+  if (flags & BNN_HIP_FLAG_FORCE_GENERIC) return false;
+  if (p.KH != 3 || p.KW != 3 || p.ph != 1 || p.pw != 1 || p.dh != 1 || p.dw != 1) return false;
+  if (p.sh != p.sw || (p.sh != 1 && p.sh != 2)) return false;
+  if (p.C % 64 != 0 || p.O % 64 != 0 || !small_indices(p)) return false;
+  if (p.raw || p.prelu || p.pack_a || p.pack_b || p.eflags != 0 || p.ds_P) return false;
+  if (p.c_off != 0 || p.c_tot != p.O) return false;
+  if ((long long)p.N * p.H * p.Wd >= (1ll << 30)) return false;
+  int cap = 0;
+  return choose_tile(p, &cap) != 0;
+}
+
+int launch_bconv_mfma(const ConvP& p, int flags, const void* w8, hipStream_t s) {
+  int cap = 0;
+  const int tp = choose_tile(p, &cap);
+  if (!mfma_conv_applies(p, flags) || tp == 0) return BNN_HIP_ERR_UNSUPPORTED;
+  const Geo g = make_geo(p);
+  MfmaGeo mg;
+  mg.tp = tp;
+  mg.groups = p.C / 64;
+  mg.ihw = p.H * p.Wd;
+  mg.patch_cap = cap;
+  mg.nn = (flags & BNN_HIP_FLAG_ACT_NONNEG) ? 1 : 0;
+  mg.n_in = p.N * p.H * p.Wd;
+  div_magic((uint32_t)mg.ihw, mg.m_ihw, mg.s_ihw);
+  const dim3 grid((unsigned)((p.npix + tp - 1) / tp), (unsigned)(p.O / (tp == 256 ? 64 : 128)));
+  const size_t ldsb = lds_bytes_of(cap);
+  const int f = g.flags;
+  const bool fused = (f & (EF_BN | EF_RES | EF_RELU | EF_PACK)) != 0;
+  if (f == kFlagsMid && p.thr) launch_ep<EP_MIDT>(p, g, mg, w8, grid, ldsb, s);
+  else if (f == kFlagsMid) launch_ep<EP_MID>(p, g, mg, w8, grid, ldsb, s);
+  else if (f == kFlagsOut) launch_ep<EP_OUT>(p, g, mg, w8, grid, ldsb, s);
+  else if (f == kFlagsOutP) launch_ep<EP_OUTP>(p, g, mg, w8, grid, ldsb, s);
+  else if (f == kFlagsLast) launch_ep<EP_LAST>(p, g, mg, w8, grid, ldsb, s);
+  else if (fused) launch_ep<EP_RUNTIME>(p, g, mg, w8, grid, ldsb, s);
+  else launch_ep<EP_PLAIN>(p, g, mg, w8, grid, ldsb, s);
+  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+}
+
+}  // namespace bnn

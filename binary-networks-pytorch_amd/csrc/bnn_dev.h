@@ -203,6 +203,13 @@ bool ds_fold_applies(const ConvP& p, int flags);
 // route != null: the kernel the ladder picks is described there (include/bnn_hip.h, bnn_hip_conv_route); dry: nothing is
 // launched and no HIP function is called (bnn_hip_bconv2d_route: the query IS the launch ladder)
 int launch_bconv(const ConvP& p, int flags, hipStream_t s, bnn_hip_conv_route* route = nullptr, bool dry = false);
+// bconv_mfma.hip: the dense 3x3 convolution on v_mfma_i32_16x16x64_i8.  weight_i8_bytes: size of the int8 pack, 0 where
+// there is none; mfma_conv_applies: what the kernel covers (p from capi.hip's check_conv).
+size_t weight_i8_bytes(int O, int C, int KH, int KW);
+int launch_pack_weight_i8(const uint32_t* wbits, const uint32_t* wnz, const bnn_hip_wlayout& L, int O, void* w8,
+                          hipStream_t s);
+bool mfma_conv_applies(const ConvP& p, int flags);
+int launch_bconv_mfma(const ConvP& p, int flags, const void* w8, hipStream_t s);
 // grouped / depthwise convolutions: pack_weight.hip (the windowed layout, L from bnn_hip_grouped_weight_layout) and
 // bconv_grouped.hip (p.C = all input channels, p.W / p.Z in that layout with S words per tap)
 int launch_pack_weight_grouped(const float* w, int O, int Cg, int groups, int center, int compute_alpha,

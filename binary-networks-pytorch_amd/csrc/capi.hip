@@ -1020,6 +1020,48 @@ int bnn_hip_shortcut_fold_supported(const bnn_hip_conv_desc* d, int sc_C) {
   return bnn::ds_fold_applies(p, d->flags) ? 1 : 0;
 }
 
+// ---- the dense 3x3 convolution on the int8 matrix cores (csrc/bconv_mfma.hip) ----
+size_t bnn_hip_weight_i8_bytes(int O, int C, int KH, int KW) { return bnn::weight_i8_bytes(O, C, KH, KW); }
+
+int bnn_hip_pack_weight_i8(const uint32_t* wbits, const uint32_t* wnz, int O, int C, int KH, int KW, void* w8,
+                           void* stream) {
+  if (!wbits || !wnz || !w8) return BNN_HIP_ERR_INVALID_ARG;
+  bnn_hip_wlayout L;
+  const int st = bnn_hip_weight_layout(O, C, KH, KW, &L);
+  if (st != BNN_HIP_OK) return st;
+  if (bnn::weight_i8_bytes(O, C, KH, KW) == 0) return BNN_HIP_ERR_UNSUPPORTED;
+  if (!aligned(wbits, 16) || !aligned(wnz, 16) || !aligned(w8, 16)) return BNN_HIP_ERR_INVALID_ARG;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_pack_weight_i8(wbits, wnz, L, O, w8, static_cast<hipStream_t>(stream));
+}
+
+int bnn_hip_bconv2d_mfma_supported(const bnn_hip_conv_desc* d, const bnn_hip_epilogue* e) {
+  alignas(16) static const uint64_t operand[2] = {0, 0};  // stands in for the packed operands (never read)
+  bnn::ConvP p = empty_convp();
+  if (epilogue_convp(e, &p) != BNN_HIP_OK) return 0;
+  const uint32_t* const w = reinterpret_cast<const uint32_t*>(operand);
+  if (check_conv(d, operand, operand, w, w, &p) != BNN_HIP_OK) return 0;
+  if (p.out && !aligned(p.out, 4)) return 0;
+  return bnn::mfma_conv_applies(p, d->flags) ? 1 : 0;
+}
+
+int bnn_hip_bconv2d_mfma_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const void* w8,
+                               const bnn_hip_epilogue* e, void* stream) {
+  bnn::ConvP p = empty_convp();
+  int st = epilogue_convp(e, &p);
+  if (st != BNN_HIP_OK) return st;
+  if (!w8 || !aligned(w8, 16)) return BNN_HIP_ERR_INVALID_ARG;
+  // (the int8 pack stands in for wbits / wnz in the shared validator: non-null and 16-byte aligned like them)
+  st = check_conv(d, P, M, static_cast<const uint32_t*>(w8), static_cast<const uint32_t*>(w8), &p);
+  if (st != BNN_HIP_OK) return st;
+  if (p.out && !aligned(p.out, 4)) return BNN_HIP_ERR_INVALID_ARG;
+  if (!bnn::mfma_conv_applies(p, d->flags)) return BNN_HIP_ERR_UNSUPPORTED;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_bconv_mfma(p, d->flags, w8, static_cast<hipStream_t>(stream));
+}
+
 int bnn_hip_sign_thresholds_f32(const float* alpha, const float* bias, const float* post_scale, const float* bn_scale,
                                 const float* bn_shift, int O, int kmax, int32_t* thresholds, void* stream) {
   // (kmax < 2^20: the two-instruction form of the test biases its counts by 2^20 > kmax / 2, bconv_core.h kMidtBias)

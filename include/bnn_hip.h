@@ -499,6 +499,37 @@ int bnn_hip_bconv2d_fused(const bnn_hip_conv_desc* d,
  * weights, epilogue = BatchNorm + shortcut + ReLU -> fp32 + sign planes, sc_C in {64, 128, 256}; 0 otherwise.       */
 int bnn_hip_shortcut_fold_supported(const bnn_hip_conv_desc* d, int sc_C);
 
+/* ---- The dense 3x3 convolution on the int8 matrix cores (additive entry points of ABI 16, no struct or signature
+ * changed; csrc/bconv_mfma.hip).  The same layer as bnn_hip_bconv2d_fused on the same sign planes, the dot taken by
+ * v_mfma_i32_16x16x64_i8 instead of XNOR + popcount: operands in {-1,0,+1} are exact in int8 and the int32 accumulation
+ * of at most 9 C such products is exact, so the integer dot — and, through the same float epilogue, every output bit —
+ * equals bnn_hip_bconv2d_fused's.  About four times the popcount rate of the int ALU.
+ *
+ * Covered (bnn_hip_bconv2d_mfma_supported == 1): KH = KW = 3, padding 1, dilation 1, stride 1 or 2 (both directions
+ * alike), C % 64 == 0, O % 64 == 0, sizes within the limits of the tiled popcount kernels, an image row narrow enough
+ * for the kernel's LDS patch (64 KB: W up to ~380 at stride 1); epilogue: alpha [, bias] [, post_scale] [, BatchNorm]
+ * [, residual] [, ReLU] -> fp32 and / or sign planes, sign_thresholds honoured as in bnn_hip_bconv2d_fused.  Not covered
+ * (BNN_HIP_ERR_UNSUPPORTED, nothing launched): PReLU, the BNN_HIP_EPI_* flags, pack_scale / pack_shift, a channel window
+ * (out_c_total != O), the folded shortcut (sc_*), BNN_HIP_FLAG_FORCE_GENERIC.  BNN_HIP_FLAG_ACT_NONNEG is honoured (M is
+ * not read); the zero weights of the pack are always honoured, with or without BNN_HIP_FLAG_WEIGHT_ZEROS.
+ *
+ * bnn_hip_pack_weight_i8: wbits / wnz of bnn_hip_pack_weight_f32 -> `w8`, bnn_hip_weight_i8_bytes(O, C, KH, KW) = 9 O C
+ * bytes (0: no int8 pack for this weight shape), 16-byte aligned; once per weight version.  alpha is used unchanged.
+ * Byte layout, G = C / 64:
+ *   w8[o / 64][g][tap][ct][lane][e]   int8, g < G, tap = 3 ky + kx, ct < 4, lane < 64, e < 16: one 16-byte MFMA operand
+ *                                     fragment per lane, 4 KB per (64 output channels, group, tap)
+ *       = sign(W[o = 64 (o / 64) + 16 ct + (lane & 15)][c = 64 g + 16 (lane >> 4) + e][tap])   as +1 / -1 / 0
+ * (wnz bit ? (wbits bit ? +1 : -1) : 0).  The kernel expands the activation planes with the same channel order inside a
+ * fragment; the sum over a fragment does not depend on that order, only on both operands sharing it.                 */
+size_t bnn_hip_weight_i8_bytes(int O, int C, int KH, int KW);
+int bnn_hip_pack_weight_i8(const uint32_t* wbits, const uint32_t* wnz, int O, int C, int KH, int KW, void* w8,
+                           void* stream);
+/* HOST: 1 when bnn_hip_bconv2d_mfma_fused() takes this convolution with this epilogue, 0 otherwise (invalid arguments
+ * included).                                                                                                          */
+int bnn_hip_bconv2d_mfma_supported(const bnn_hip_conv_desc* d, const bnn_hip_epilogue* epi);
+int bnn_hip_bconv2d_mfma_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const void* w8,
+                               const bnn_hip_epilogue* epi, void* stream);
+
 /* ---- Which kernel a convolution runs (ABI 16): the route of bnn_hip_bconv2d / _fused / _dot, for tests. ----
  * The launch ladder of csrc/bconv.hip picks one instantiation per call from the kernel size, the chunk width, the
  * epilogue, the flags and the size of the grid.  The route query walks THAT ladder (the same statements, with the

@@ -63,6 +63,32 @@ int launch_bconv(const ConvP& p, int flags, hipStream_t, bnn_hip_conv_route* rou
   return BNN_HIP_OK;
 }
 bool ds_fold_applies(const ConvP& p, int flags) { return p.KH == 3 && p.KW == 3 && (flags & BNN_HIP_FLAG_ACT_NONNEG); }
+// the int8 matrix-core convolution (csrc/bconv_mfma.hip)
+size_t weight_i8_bytes(int O, int C, int KH, int KW) {
+  return (O > 0 && C > 0 && KH == 3 && KW == 3 && O % 64 == 0 && C % 64 == 0) ? (size_t)O * (size_t)C * 9 : 0;
+}
+int launch_pack_weight_i8(const uint32_t* wbits, const uint32_t* wnz, const bnn_hip_wlayout& L, int O, void* w8, hipStream_t) {
+  ++g_reached;
+  REQUIRE(wbits && wnz && w8 && al(wbits, 16) && al(wnz, 16) && al(w8, 16));
+  REQUIRE(O > 0 && O % 64 == 0 && L.taps == 9 && L.cw32 > 0 && L.cw32 % 2 == 0 && L.cwc * L.nchunk == L.cw32 && L.o_pad == O);
+  return BNN_HIP_OK;
+}
+bool mfma_conv_applies(const ConvP& p, int) {
+  check_convp(p);
+  return p.KH == 3 && p.KW == 3 && p.C % 64 == 0 && p.O % 64 == 0 && !p.ds_P && !p.prelu && p.c_tot == p.O;
+}
+int launch_bconv_mfma(const ConvP& p, int flags, const void* w8, hipStream_t) {
+  ++g_reached;
+  check_convp(p);
+  REQUIRE(mfma_conv_applies(p, flags));
+  REQUIRE((long long)p.N * p.H * p.Wd * ((p.C + 63) / 64) <= kPlaneWords);
+  REQUIRE(p.P && p.M && w8 && al(p.P, 16) && al(p.M, 16) && al(w8, 16) && p.alpha);
+  REQUIRE(p.out || (p.outP && p.outM));
+  REQUIRE((p.bn_a == nullptr) == (p.bn_b == nullptr) && (p.outP == nullptr) == (p.outM == nullptr));
+  REQUIRE(!p.outP || (al(p.outP, 8) && al(p.outM, 8)));
+  REQUIRE(!p.out || al(p.out, 4));
+  return BNN_HIP_OK;
+}
 bool fly_supported(const ConvP& p) { return p.KH * p.KW <= 49; }
 int fly_default_plan(const ConvP& p, int, bnn_hip_fly_plan* plan) {
   check_convp(p);
@@ -961,6 +987,19 @@ int main(int argc, char** argv) {
           const int sd = bnn_hip_bconv2d_dot_route(rnd() % 16 ? &d : nullptr, rnd() % 16 ? &r : nullptr);
           if (!status_ok(sd)) broken("dot route status");
           digest = (digest ^ (uint64_t)(uint32_t)sr ^ ((uint64_t)(uint32_t)sd << 32)) * 0x100000001B3ull;
+          // the int8 matrix-core convolution on the same descriptor and epilogue (csrc/bconv_mfma.hip)
+          if (rnd() % 2) { d.KH = d.KW = 3; d.pad_h = d.pad_w = d.dil_h = d.dil_w = 1; d.stride_h = d.stride_w = 1 + (int)(rnd() % 2); }
+          if (rnd() % 2) { d.C = 64 * (1 + (int)(rnd() % 8)); d.O = 64 * (1 + (int)(rnd() % 8)); }
+          const bnn_hip_conv_desc* dp = rnd() % 16 ? &d : nullptr;
+          const bnn_hip_epilogue* ep = rnd() % 16 ? &e : nullptr;
+          const int sup = bnn_hip_bconv2d_mfma_supported(dp, ep);
+          if (sup != 0 && sup != 1) broken("mfma supported");
+          const int sm = bnn_hip_bconv2d_mfma_fused(dp, pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<char>(), ep, stream);
+          if (!status_ok(sm) || (sm == BNN_HIP_OK && !sup)) broken("mfma conv launched where the query said no");
+          if (bnn_hip_weight_i8_bytes(d.O, d.C, d.KH, d.KW) > ((size_t)1 << 62)) broken("int8 weight pack size");
+          const int sp8 = bnn_hip_pack_weight_i8(pick_ptr<uint32_t>(), pick_ptr<uint32_t>(), d.O, d.C, d.KH, d.KW, pick_ptr<char>(), stream);
+          if (!status_ok(sp8)) broken("int8 weight pack status");
+          digest = (digest ^ (uint64_t)(uint32_t)sm ^ ((uint64_t)(uint32_t)sp8 << 32) ^ (uint64_t)sup) * 0x100000001B3ull;
         }
         st = bnn_hip_blinear(pick_int(), pick_int(), pick_int(), pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<uint32_t>(),
                              pick_ptr<uint32_t>(), pick_int(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(),
