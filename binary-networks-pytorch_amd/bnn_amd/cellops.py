@@ -11,6 +11,9 @@ three fp32 passes over HBM (x read by the pack, x read as the skip, y written) i
 path — torch BatchNorm, ``pack_act``, the grouped kernel, torch PReLU, the ``.contiguous()`` shuffle copy, torch add —
 stays what every call outside ``eval()`` / ``no_grad()`` runs.
 
+``FusedFactorizedConv(module)`` does the same for ``FactorizedConv`` (``'conv_7x1_1x7'``): two dense binary convolutions
+with only a sign between them, run as ``bn_act_pack`` and one launch that keeps that sign in LDS (csrc/fconv.hip).
+
 ``FusedCell(cell)`` evaluates a whole ``Cell`` (reference: ``bnn/models/bats.py:9-83``) the same way: every state is
 binarised once for all the operations that read it (``bn_act_pack_multi``), a node ``s = op1(h1) + op2(h2)`` is the
 second operation's launch adding the first one's result in its epilogue (``bnn_hip_bconv2d_grouped_node``), and that
@@ -196,6 +199,130 @@ class FusedCellOp(_Executor):
         y = self.conv(self.pack(x), x)
         fastpath._bump("cell_op")
         return y
+
+
+class FusedFactorizedConv(_Executor):
+    """Inference executor of a BATS ``FactorizedConv`` (reference: ``bats_ops.py:55-75``, ``'conv_7x1_1x7'``)
+
+        y = [x +] channel_shuffle(PReLU(conv_Kx1(sign(BN(PReLU(conv_1xK(sign(BN(x)))))))), 4)     # skip at stride 1
+
+    as ``bn_act_pack`` and ONE launch (``hipops.fconv_fused``, csrc/fconv.hip) that keeps the tensor between the two
+    convolutions in LDS as bit planes: two launches and three fp32 passes over HBM (x read by the pack, x read as the
+    skip, y written).  Where ``hipops.fconv_supported`` or ``fastpath.fconv_admitted`` says no, the same bits come from
+    the launches the library had before: ``bconv2d_fused`` of the 1 x K layer (planes only), ``bconv2d_fused`` of the
+    K x 1 layer, torch's shuffle and add.
+
+    Recognition is by structure, like ``FusedCellOp``: the class NAME must be ``FactorizedConv`` and ``module.op`` the
+    six modules of the reference with both convolutions binary, dense and of exactly the constructor's geometry, so an
+    instance of the reference's own class, handed over explicitly, works.  Derived data (the two folded BatchNorms, the
+    two packed weights, the slope vectors) is keyed on the identity, storage and version of every parameter and buffer;
+    writes through ``.data`` need ``refresh()`` (or ``fastpath.invalidate(module)``)."""
+    takes = "factorized conv: the input must be a float32 NCHW tensor"
+
+    def _recognise(self) -> None:
+        m = self.model
+        kind = type(m).__name__
+        if kind != "FactorizedConv":
+            raise FusionError(f"{kind} is not a BATS FactorizedConv")
+        op = getattr(m, "op", None)
+        kinds = (nn.BatchNorm2d, nn.Conv2d, nn.PReLU, nn.BatchNorm2d, nn.Conv2d, nn.PReLU)
+        if not (isinstance(op, nn.Sequential) and len(op) == 6 and all(isinstance(a, b) for a, b in zip(op, kinds))):
+            raise FusionError("FactorizedConv.op is not Sequential(BatchNorm2d, Conv2d, PReLU, BatchNorm2d, Conv2d, PReLU)")
+        bn1, c1, a1, bn2, c2, a2 = op
+        if m.training:
+            raise FusionError("FusedFactorizedConv is inference-only: call .eval() first")
+        self._plans = [_binary_plan(c, "factorized conv") for c in (c1, c2)]
+        for bn in (bn1, bn2):
+            if bn.running_mean is None or bn.running_var is None:
+                raise FusionError("factorized conv: BatchNorm2d without running statistics normalises with batch statistics")
+            if bn.running_var.dtype != torch.float32:
+                raise FusionError("factorized conv: only float32 modules are covered")
+        stride = getattr(m, "stride", None)
+        if not isinstance(stride, int) or isinstance(stride, bool) or stride < 1:
+            raise FusionError(f"factorized conv: stride={stride!r} is not a positive int")
+        if not isinstance(getattr(m, "skip", None), bool):
+            raise FusionError("factorized conv: FactorizedConv.skip is not a bool")
+        C, K = c1.in_channels, c1.kernel_size[1]
+        want = [((1, K), (1, stride), (0, K // 2)), ((K, 1), (stride, 1), (K // 2, 0))]
+        for c, (ks, st, pd) in zip((c1, c2), want):
+            if (isinstance(c.padding, str) or c.padding_mode != "zeros" or c.groups != 1 or tuple(c.dilation) != (1, 1)
+                    or c.in_channels != C or c.out_channels != C or K % 2 == 0
+                    or (tuple(c.kernel_size), tuple(c.stride), tuple(c.padding)) != (ks, st, pd)):
+                raise FusionError("factorized conv: the convolutions are not dense C -> C, (1, K) / (1, s) / (0, K//2) then "
+                                  "(K, 1) / (s, 1) / (K//2, 0)")
+        if C % SHUFFLE_GROUPS or any(bn.num_features != C for bn in (bn1, bn2)) \
+                or any(a.weight.numel() not in (1, C) for a in (a1, a2)):
+            raise FusionError(f"factorized conv: widths do not fit ({C} channels, a multiple of {SHUFFLE_GROUPS})")
+        self.C, self.K, self.stride = C, K, stride
+        self.add_skip = m.skip and stride == 1
+
+    def refresh(self) -> None:
+        """Re-derive everything from the module's current parameters and buffers."""
+        self._sig = None
+        self._recognise()
+        bn1, c1, a1, bn2, c2, a2 = self.model.op
+        fastpath.invalidate(self.model, executors=False)
+        self.bn_a, self.bn_b = fold_bn(bn1)
+        self.mid_a, self.mid_b = fold_bn(bn2)
+        self._stage = [dict(bias=fastpath._f32(c.bias), post_scale=fastpath._f32(p.scale), prelu=_prelu_slopes(a, self.C))
+                       for c, p, a in ((c1, self._plans[0], a1), (c2, self._plans[1], a2))]
+        self._weights = None
+        self._fused = {}        # input shape -> whether the one-launch kernel takes it
+        if c1.weight.is_cuda:
+            native.require()
+            self._weights = [fastpath.packed_weight(c, p) for c, p in zip((c1, c2), self._plans)]
+        self._sig = param_signature(self.model)
+
+    def pack(self, x: torch.Tensor) -> hipops.PackedAct:
+        """``sign(BatchNorm(x))`` as bit planes (``bn_act_pack``)."""
+        return hipops.bn_act_pack(x, self.bn_a, self.bn_b, relu=False)
+
+    def takes_fused(self, shape) -> bool:
+        """Whether an input of this shape runs the one-launch kernel: it exists for the geometry
+        (``hipops.fconv_supported``) and did not measure slower than the per-layer launches
+        (``fastpath.fconv_admitted``)."""
+        shape = tuple(shape)
+        ok = self._fused.get(shape)
+        if ok is None:
+            N, C, H, W = shape
+            ok = self._fused[shape] = bool(fastpath.fconv_admitted(C, H, W, self.stride)
+                                           and hipops.fconv_supported(N, C, H, W, self.K, self.stride))
+        return ok
+
+    def conv(self, planes: hipops.PackedAct, x: torch.Tensor) -> torch.Tensor:
+        """Everything behind the first BatchNorm in one launch (``hipops.fconv_fused``)."""
+        s1, s2 = self._stage
+        return hipops.fconv_fused(planes, self._weights[0], self._weights[1], self.mid_a, self.mid_b, stride=self.stride,
+                                  bias1=s1["bias"], post_scale1=s1["post_scale"], prelu1=s1["prelu"], bias2=s2["bias"],
+                                  post_scale2=s2["post_scale"], prelu2=s2["prelu"], shuffle_groups=SHUFFLE_GROUPS,
+                                  residual=x if self.add_skip else None)
+
+    def composition(self, planes: hipops.PackedAct, x: torch.Tensor) -> torch.Tensor:
+        """The same bits from two ``bconv2d_fused`` launches (the tensor between them as bit planes in global memory),
+        torch's shuffle copy and torch's add: what runs where the one-launch kernel does not."""
+        s, K = self.stride, self.K
+        _, t = hipops.bconv2d_fused(planes, self._weights[0], stride=(1, s), padding=(0, K // 2), pack_scale=self.mid_a,
+                                    pack_shift=self.mid_b, out_f32=False, out_packed=True, **self._stage[0])
+        y, _ = hipops.bconv2d_fused(t, self._weights[1], stride=(s, 1), padding=(K // 2, 0), **self._stage[1])
+        n, c, h, w = y.shape
+        y = y.reshape(n, SHUFFLE_GROUPS, c // SHUFFLE_GROUPS, h, w).transpose(1, 2).reshape(n, c, h, w)
+        return x + y if self.add_skip else y.contiguous()
+
+    @torch.no_grad()
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        self._check_inputs(x)
+        if not self._unchanged():
+            self.refresh()
+        if self._weights is None or self._weights[0].alpha.device != x.device:
+            raise FusionError("factorized conv: module and input live on different devices")
+        if x.shape[1] != self.C:
+            raise FusionError(f"factorized conv: the input has {x.shape[1]} channels, the module {self.C}")
+        planes = self.pack(x)
+        if self.takes_fused(x.shape):
+            y = self.conv(planes, x)
+            fastpath._bump("fconv")
+            return y
+        return self.composition(planes, x)
 
 
 def _stride_of(op: nn.Module) -> int:

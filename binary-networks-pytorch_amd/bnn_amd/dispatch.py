@@ -1,8 +1,8 @@
 """What ``model(x)`` and ``block(x)`` dispatch to by themselves — the drop-in tiers: ``AutoFusion`` (whole model:
 the fused executor, as eager launches / stem launch + HIP graph / two halves in flight), the three tiers of a module that
 fuses itself, stated once in ``_TierFusion`` — ``BlockFusion`` (one residual block), ``OpFusion`` (one BATS cell
-operation), ``CellFusion`` (one whole BATS cell) — and ``install_auto_fusion`` (the same dispatch for ResNets of other
-packages, from ``prepare_binary_model``).
+operation; ``FactorizedFusion`` for ``FactorizedConv``), ``CellFusion`` (one whole BATS cell) — and
+``install_auto_fusion`` (the same dispatch for ResNets of other packages, from ``prepare_binary_model``).
 Reference call being served: ``outputs = net(inputs)`` (examples/cifar10.py:71,140-149)."""
 from __future__ import annotations
 
@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from . import fastpath, native
 from . import tails as _tails
-from .cellops import FusedCell, FusedCellOp
+from .cellops import FusedCell, FusedCellOp, FusedFactorizedConv
 from .executor import (FusedBlocks, FusedResNet, FusionError, inner_hooks, is_native_model, param_signature,
                        resnet_shaped, tap_binary_inputs)
 from .pipeline import TwoHalves
@@ -150,6 +150,14 @@ class OpFusion(_TierFusion):
     build = FusedCellOp
 
 
+class FactorizedFusion(_TierFusion):
+    """``OpFusion`` for ``FactorizedConv`` (``'conv_7x1_1x7'``): the operation evaluates itself as
+    ``FusedFactorizedConv(op)`` — ``bn_act_pack`` and one launch for both convolutions with the sign between them in
+    LDS, PReLU, channel shuffle and skip in its epilogue — instead of about a dozen launches and fp32 passes."""
+    key = fastpath.OP_KEY
+    build = FusedFactorizedConv
+
+
 _NO_CELL_FUSION = 0
 
 
@@ -185,6 +193,11 @@ def auto_block_forward(block: nn.Module, x: torch.Tensor) -> Optional[torch.Tens
 def auto_op_forward(op: nn.Module, x: torch.Tensor) -> Optional[torch.Tensor]:
     """Called at the top of the cell operations' ``forward``: the fused result, or None -> its own forward."""
     return OpFusion.of(op).run(op, x)
+
+
+def auto_fconv_forward(op: nn.Module, x: torch.Tensor) -> Optional[torch.Tensor]:
+    """Called at the top of ``FactorizedConv.forward``: the fused result, or None -> its own forward."""
+    return FactorizedFusion.of(op).run(op, x)
 
 
 def auto_cell_forward(cell: nn.Module, s0: torch.Tensor, s1: torch.Tensor) -> Optional[torch.Tensor]:

@@ -51,7 +51,7 @@ from . import hipops, native
 _stats_lock = threading.Lock()
 _stats = {"conv2d": 0, "conv1d": 0, "linear": 0, "weight_packs": 0, "conv2d_train": 0, "cell_op": 0, "cell": 0,
           "cell_op_train": 0, "reduce_train": 0, "linear_train": 0, "conv2d_real": 0, "conv2d_real_train": 0,
-          "linear_real": 0, "linear_real_train": 0}
+          "linear_real": 0, "linear_real_train": 0, "fconv": 0}
 
 # Binary activations with REAL weights (step 0 of the reference's two-stage recipe, examples/recepies/imagenet-baseline.yaml:
 # ``weight: nn.Identity``) on the HIP path: ``Conv2d`` layers whose weight hook is the identity take csrc/sconv.hip (one
@@ -88,6 +88,20 @@ def mfma_conv_admitted(C: int, O: int, H: int, stride: int, fold: bool) -> bool:
     if MFMA_CONV == "0":
         return False
     return MFMA_CONV == "all" or (C, O, H, stride, fold) in MFMA_CONV_SHAPES
+
+
+# The one-launch FactorizedConv kernel (csrc/fconv.hip) against the per-layer path of the same module, batch 256 on
+# MI355X (tools/bench_fconv.py -> profiles/fconv_bench.jsonl).  The admission rule, in one place: a shape (C, H, W,
+# stride) whose fused executor measured SLOWER than the per-layer path is listed here with its (per-layer us, fused us)
+# and takes the launches the library had before (``cellops.FusedFactorizedConv.composition``: the same bits).
+FCONV_DECLINED_SHAPES = {
+    # none: per-layer -> fused us at batch 256 was 460 -> 104 (48, 32, 32, 1), 427 -> 91 (96, 16, 16, 1), 479 -> 91
+    # (192, 8, 8, 1), 513 -> 95 (96, 32, 32, 2), 488 -> 87 (192, 16, 16, 2), 648 -> 166 (80, 28, 28, 1)
+}
+
+
+def fconv_admitted(C: int, H: int, W: int, stride: int) -> bool:
+    return (C, H, W, stride) not in FCONV_DECLINED_SHAPES
 
 
 def stats() -> dict:

@@ -943,6 +943,77 @@ def bconv2d_grouped_node(a: PackedAct, w: PackedWeight, bias: Optional[torch.Ten
     return out
 
 
+def _fconv_desc(N: int, C: int, H: int, W: int, K: int, stride: int, weight_zeros: bool = False) -> native.FconvDesc:
+    return native.FconvDesc(N, C, H, W, K, stride, native.FLAG_WEIGHT_ZEROS if weight_zeros else 0, 0)
+
+
+def fconv_supported(N: int, C: int, H: int, W: int, K: int, stride: int) -> bool:
+    """Whether ``fconv_fused`` has a kernel for this geometry (``bnn_hip_fconv_supported``: ``K`` in 1 / 3 / 5 / 7,
+    stride 1 or 2, ``K`` rows of the intermediate bit planes within a workgroup's LDS); asked per launch of a batch
+    that ``fconv_fused`` would split."""
+    lib = native.require()
+    step = _fconv_launch_images(N, C, H, W, stride)
+    return bool(lib.bnn_hip_fconv_supported(ctypes.byref(_fconv_desc(min(N, step) or 1, C, H, W, K, stride))))
+
+
+def _fconv_launch_images(N: int, C: int, H: int, W: int, stride: int) -> int:
+    ho, wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    return _launch_images(N, C, C, C, 2 * H * W * ((C + 63) // 64), ho * wo)
+
+
+def fconv_fused(a: PackedAct, w1: PackedWeight, w2: PackedWeight, mid_scale: torch.Tensor, mid_shift: torch.Tensor, *,
+                stride: int = 1, bias1=None, post_scale1=None, prelu1=None, bias2=None, post_scale2=None, prelu2=None,
+                shuffle_groups: int = 1, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The BATS ``FactorizedConv`` behind its first BatchNorm in ONE launch (``bnn_hip_fconv_fused``): ``a`` holds
+    ``sign(BatchNorm(x))``, ``w1`` / ``w2`` are the ``pack_weight`` of its ``[C, C, 1, K]`` and ``[C, C, K, 1]`` weights,
+    ``mid_scale`` / ``mid_shift`` the folded BatchNorm between them; the rest per stage (``[C]`` each, optional).  The
+    result ``[N, C, (H-1)//s + 1, (W-1)//s + 1]`` holds the bits of ``bconv2d_fused`` (1 x K, ``prelu1``,
+    ``pack_scale`` / ``pack_shift``, planes only) -> ``bconv2d_fused`` (K x 1, ``prelu2``) -> ``channel_shuffle`` ->
+    ``residual + .``; the tensor between the convolutions stays in LDS as bit planes.  ``NativeError`` where
+    ``fconv_supported`` says no."""
+    _ungrouped(w1, "fconv_fused")
+    _ungrouped(w2, "fconv_fused")
+    lib = native.require()
+    N, C, H, W = a.shape
+    K = w1.shape[3]
+    if tuple(w1.shape) != (C, C, 1, K) or tuple(w2.shape) != (C, C, K, 1):
+        raise native.NativeError(f"bnn_amd: fconv_fused takes [C, C, 1, K] and [C, C, K, 1] weights over the input's {C} "
+                                 f"channels, got {tuple(w1.shape)} and {tuple(w2.shape)}")
+    stride, shuffle_groups = int(stride), int(shuffle_groups)
+    if stride < 1:
+        raise native.NativeError(f"bnn_amd: stride={stride}")
+    if shuffle_groups < 1 or C % shuffle_groups:
+        raise native.NativeError(f"bnn_amd: shuffle_groups={shuffle_groups} does not divide the {C} channels")
+    ho, wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    dev = a.P.device
+    mid_scale = _per_channel(mid_scale, C, "mid_scale")
+    mid_shift = _per_channel(mid_shift, C, "mid_shift")
+    consts = [[_per_channel(t, C, what) for t, what in ((b, "bias"), (s, "post_scale"), (p, "prelu"))]
+              for b, s, p in ((bias1, post_scale1, prelu1), (bias2, post_scale2, prelu2))]
+    stages = [native.FconvStage(w.alpha.data_ptr(), *map(_ptr, c)) for w, c in zip((w1, w2), consts)]
+    if residual is not None:
+        residual = _require_cuda_f32(residual, "residual")
+        if tuple(residual.shape) != (N, C, ho, wo):
+            raise native.NativeError(f"bnn_amd: residual shape {tuple(residual.shape)} != output")
+    d = _fconv_desc(N, C, H, W, K, stride, w1.has_zero or w2.has_zero)
+    with torch.cuda.device(dev):
+        out = torch.empty((N, C, ho, wo), dtype=torch.float32, device=dev)
+        if N == 0:
+            return out
+        step = _fconv_launch_images(N, C, H, W, stride)
+        for n0 in range(0, N, step):
+            n1 = min(N, n0 + step)
+            dd = native.FconvDesc.from_buffer_copy(d)
+            dd.N = n1 - n0
+            native.check(lib.bnn_hip_fconv_fused(
+                ctypes.byref(dd), a.P[n0:n1].data_ptr(), a.M[n0:n1].data_ptr(), w1.wbits.data_ptr(), w1.wnz.data_ptr(),
+                ctypes.byref(stages[0]), w2.wbits.data_ptr(), w2.wnz.data_ptr(), ctypes.byref(stages[1]),
+                mid_scale.data_ptr(), mid_shift.data_ptr(), shuffle_groups,
+                None if residual is None else residual[n0:n1].data_ptr(), out[n0:n1].data_ptr(), _stream(dev)),
+                "bnn_hip_fconv_fused")
+    return out
+
+
 def direct_plan(x_shape, w: PackedWeight, stride=1, padding=0, dilation=1) -> Optional[native.FlyPlan]:
     """The band plan ``bconv2d_direct`` would use for this geometry, or None where the one-launch layer does not
     apply (include/bnn_hip.h: bnn_hip_bconv2d_direct_plan)."""

@@ -13,7 +13,7 @@ The implementation lives in five modules (round 5: this file used to hold all of
                   CellFusion, AutoFusion, auto_fusion, auto_forward,        / ``model(x)`` dispatch to by themselves (the
                   install_auto_fusion, optimize_for_inference               drop-in tiers; the three self-fusing ones
                                                                             are one class, ``_TierFusion``)
-    cellops.py    FusedCellOp, FusedCell                                    a BATS cell operation in two launches; a
+    cellops.py    FusedCellOp, FusedFactorizedConv, FusedCell               a BATS cell operation in two launches; a
                                                                             whole cell with its adds and its concat in them
     batsnet.py    FusedBATSNetwork                                          a whole BATS network: stem kernel, planes packed
                                                                             once per tensor for all cells, head, HIP graph
@@ -28,9 +28,10 @@ from . import executor as _executor
 from . import pipeline as _pipeline
 from . import tails as _tails
 from .batsnet import FusedBATSNetwork  # noqa: F401
-from .cellops import FusedCell, FusedCellOp  # noqa: F401
-from .dispatch import (AutoFusion, BlockFusion, CellFusion, OpFusion, auto_block_forward,  # noqa: F401
-                       auto_cell_forward, auto_forward, auto_fusion, auto_op_forward, install_auto_fusion,
+from .cellops import FusedCell, FusedCellOp, FusedFactorizedConv  # noqa: F401
+from .dispatch import (AutoFusion, BlockFusion, CellFusion, FactorizedFusion, OpFusion,  # noqa: F401
+                       auto_block_forward, auto_cell_forward, auto_fconv_forward, auto_forward, auto_fusion,
+                       auto_op_forward, install_auto_fusion,
                        no_cell_fusion, no_model_fusion, optimize_for_inference, uninstall_auto_fusion)
 from .executor import (FusedBlocks, FusedResNet, FusionError, fold_bn, is_native_model, resnet_shaped,  # noqa: F401
                        tap_binary_inputs)

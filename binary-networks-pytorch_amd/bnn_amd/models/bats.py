@@ -14,7 +14,7 @@ from typing import List, Optional, Tuple
 import torch
 import torch.nn as nn
 
-from .bats_ops import OPS, FactorizedReduce, Genotype, ReLUConvBN, drop_path
+from .bats_ops import ALL_OPS, FactorizedReduce, Genotype, ReLUConvBN, drop_path
 
 
 def _fused(cell, s0, s1):
@@ -52,7 +52,7 @@ class Cell(nn.Module):
         self._ops = nn.ModuleList()
         for name, index in zip(op_names, indices):
             stride = 2 if reduction and index < 2 else 1
-            self._ops += [OPS[name](C, stride, True, True, groups)]
+            self._ops += [ALL_OPS[name](C, stride, True, True, groups)]
         self._indices = indices
 
     def train(self, mode: bool = True):

@@ -1,6 +1,6 @@
 """The BATS cell operations built on grouped binary convolutions (``bnn/models/layers/bats_ops.py``):
-``SepConv``, ``DilConv`` and ``ReLUConvBN``, and what a cell needs around them — ``FactorizedReduce``, ``Zero``,
-``drop_path``, ``Genotype`` / ``PRIMITIVES`` / ``OPS``.
+``SepConv``, ``DilConv`` and ``ReLUConvBN``, the dense ``FactorizedConv``, and what a cell needs around them —
+``FactorizedReduce``, ``Zero``, ``drop_path``, ``Genotype`` / ``PRIMITIVES`` / ``OPS`` / ``EXTENDED_OPS`` / ``ALL_OPS``.
 
 Plain float ``nn.Module`` graphs, like ``blocks.py``: the ``nn.Conv2d`` inside becomes a binary layer only after
 ``prepare_binary_model``.  Constructor signatures, attribute names and forward order equal the reference's, so
@@ -108,6 +108,42 @@ class ReLUConvBN(_CellOp):
         return x + y if self.skip and self.stride == 1 and self.C_in == self.C_out else y
 
 
+class FactorizedConv(nn.Module):
+    """BN - dense 1 x K conv, stride (1, s) - PReLU - BN - dense K x 1 conv, stride (s, 1) - PReLU, channel shuffle, skip
+    at stride 1   (reference: ``bats_ops.py:55-75``, the ``'conv_7x1_1x7'`` primitive).  Evaluated for inference on a HIP
+    device it first offers itself to its executor (``bnn_amd/dispatch.py: FactorizedFusion`` ->
+    ``bnn_amd/cellops.py: FusedFactorizedConv``: both convolutions in one launch, the sign between them in LDS); in
+    training mode and under autograd its two layers take their per-layer paths."""
+
+    def __init__(self, C: int, kernel_size: int, stride: int, affine: bool = True, skip: bool = False) -> None:
+        super().__init__()
+        self.skip = skip or True        # (the reference's expression, as in _CellOp)
+        self.stride = stride
+        self.op = nn.Sequential(
+            nn.BatchNorm2d(C, affine=affine),
+            nn.Conv2d(C, C, (1, kernel_size), stride=(1, stride), padding=(0, kernel_size // 2), bias=False),
+            nn.PReLU(num_parameters=C),
+            nn.BatchNorm2d(C, affine=affine),
+            nn.Conv2d(C, C, (kernel_size, 1), stride=(stride, 1), padding=(kernel_size // 2, 0), bias=False),
+            nn.PReLU(num_parameters=C))
+
+    def train(self, mode: bool = True):
+        # train() <-> eval(): the executor's derived data goes with the mode (_CellOp.train)
+        if bool(mode) != self.training:
+            from ..fastpath import drop_executor
+            drop_executor(self)
+        return super().train(mode)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if not self.training and x.is_cuda and not torch.is_grad_enabled():
+            from ..inference import auto_fconv_forward      # (inference imports this package)
+            y = auto_fconv_forward(self, x)
+            if y is not None:
+                return y
+        y = channel_shuffle(self.op(x), 4)
+        return x + y if self.skip and self.stride == 1 else y
+
+
 class Zero(nn.Module):
     """The ``none`` primitive: zeros of the input's shape, ``H`` and ``W`` floor-divided by the stride   (reference:
     ``bats_ops.py:176-187``; fp32 there whatever the input's dtype, the same here)."""
@@ -158,8 +194,9 @@ def drop_path(x: torch.Tensor, drop_prob: float) -> torch.Tensor:
     return x
 
 
-# primitive name -> constructor(C, stride, affine, skip, groups)   (reference: ``bats_ops.py:41-52``; its 'sep_conv_7x7'
-# and 'conv_7x1_1x7' / FactorizedConv entries are not provided: DESIGN.md section 7)
+# primitive name -> constructor(C, stride, affine, skip, groups)   (reference: ``bats_ops.py:41-52``).  OPS holds the
+# eight names of PRIMITIVES, the search space; the reference's table has two more that no entry of PRIMITIVES names,
+# 'sep_conv_7x7' and 'conv_7x1_1x7': EXTENDED_OPS.  A genotype may name any of the ten: Cell._compile reads ALL_OPS.
 OPS = {
     "none": lambda C, stride, affine, skip, groups: Zero(stride),
     "avg_pool_3x3": lambda C, stride, affine, skip, groups: nn.AvgPool2d(3, stride=stride, padding=1,
@@ -176,3 +213,11 @@ OPS = {
     "dil_conv_5x5": lambda C, stride, affine, skip, groups: DilConv(C, C, 5, stride, 4, 2, affine=affine, skip=skip,
                                                                     groups=groups),
 }
+
+EXTENDED_OPS = {
+    "sep_conv_7x7": lambda C, stride, affine, skip, groups: SepConv(C, C, 7, stride, 3, affine=affine, skip=skip,
+                                                                    groups=groups),
+    "conv_7x1_1x7": lambda C, stride, affine, skip, groups: FactorizedConv(C, 7, stride, affine=affine, skip=skip),
+}
+
+ALL_OPS = {**OPS, **EXTENDED_OPS}

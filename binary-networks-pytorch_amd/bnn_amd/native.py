@@ -117,6 +117,16 @@ ROUTE_SITES = len(ROUTE_SITE_NAMES)     # BNN_HIP_ROUTE_SITES
 SITE = {n: i for i, n in enumerate(ROUTE_SITE_NAMES)}
 
 
+class FconvDesc(ctypes.Structure):
+    """``bnn_hip_fconv_desc``: geometry of a FactorizedConv (1 x K stride (1, s), then K x 1 stride (s, 1))."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("N", "C", "H", "W", "K", "stride", "flags", "reserved")]
+
+
+class FconvStage(ctypes.Structure):
+    """``bnn_hip_fconv_stage``: the per-channel constants behind one of its two convolutions."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("alpha", "bias", "post_scale", "prelu")]
+
+
 class F32View(ctypes.Structure):
     """``bnn_hip_f32_view``: channels ``[c_offset, c_offset + C)`` of a contiguous fp32 ``[N, c_total, H, W]`` tensor."""
     _fields_ = [("p", ctypes.c_void_p), ("c_offset", ctypes.c_int32), ("c_total", ctypes.c_int32)]
@@ -144,6 +154,8 @@ _conv_p = ctypes.POINTER(ConvDesc)
 _hblock_p = ctypes.POINTER(HBlockDesc)
 _wlayout_p = ctypes.POINTER(WLayout)
 _view_p = ctypes.POINTER(F32View)
+_fconv_p = ctypes.POINTER(FconvDesc)
+_fstage_p = ctypes.POINTER(FconvStage)
 
 # Every symbol include/bnn_hip.h declares: name -> (restype, argtypes).  load() resolves and declares from this table,
 # so a symbol cannot be exported without its prototype (an undeclared one would pass 64-bit pointers as C ints).
@@ -186,6 +198,8 @@ _PROTOTYPES = {
     "bnn_hip_bconv2d_grouped": (_i, [_conv_p, _i] + [_vp] * 9),
     "bnn_hip_bconv2d_grouped_fused": (_i, [_conv_p, _i] + [_vp] * 8 + [_i] + [_vp] * 3),
     "bnn_hip_bconv2d_grouped_node": (_i, [_conv_p, _i] + [_vp] * 8 + [_i, _view_p, _view_p, _vp, _i, _i, _vp]),
+    "bnn_hip_fconv_supported": (_i, [_fconv_p]),
+    "bnn_hip_fconv_fused": (_i, [_fconv_p, _vp, _vp, _vp, _vp, _fstage_p, _vp, _vp, _fstage_p, _vp, _vp, _i, _vp, _vp, _vp]),
     "bnn_hip_bconv2d_fused": (_i, [_conv_p] + [_vp] * 4 + [ctypes.POINTER(Epilogue), _vp]),
     "bnn_hip_shortcut_fold_supported": (_i, [_conv_p, _i]),
     "bnn_hip_weight_i8_bytes": (_sz, [_i, _i, _i, _i]),

@@ -273,6 +273,25 @@ bool hblock_cl_ds_supported(const bnn_hip_hblock_desc* d);
 int launch_hblock_cl_ds(const bnn_hip_hblock_desc* d, const uint64_t* inP, const uint32_t* W, const float* Kc,
                         const uint64_t* dsP, const uint64_t* dsM, const uint32_t* dsW, const float* dsA, float* out,
                         uint64_t* outP, hipStream_t stream);
+// fconv.hip: the BATS FactorizedConv (1 x K then K x 1 dense binary convolutions) in one launch, the tensor between
+// them as bit planes in LDS.  Operands of a call that passed capi.hip's checks.
+struct FconvP {
+  const uint64_t* P;
+  const uint64_t* M;
+  const uint32_t* W1;
+  const uint32_t* Z1;   // null unless wz
+  const uint32_t* W2;
+  const uint32_t* Z2;
+  bnn_hip_fconv_stage s1, s2;
+  const float* mid_a;
+  const float* mid_b;
+  const float* res;     // or null
+  float* out;
+  int N, C, H, W, K, stride, shuffle_groups;
+  bool wz;              // honour the zero masks Z1 / Z2
+};
+bool fconv_supported(int C, int H, int W, int K, int stride);
+int launch_fconv(const FconvP& p, hipStream_t s);
 // xnor_train.hip: XNORWeightBinarizer under autograd, value and backward
 int launch_xnor_grad_pack(const float* w, int O, int C, int ks, int center, int compute_alpha, void* packed, float* alpha,
                           hipStream_t s);

@@ -333,6 +333,18 @@ int check_grouped(const bnn_hip_conv_desc* d, int groups, const uint64_t* P, con
   return BNN_HIP_OK;
 }
 
+// Sizes of a FactorizedConv descriptor (csrc/fconv.hip): positive extents, a stride, and every tensor of the launch
+// inside the convolution kernels' 32-bit byte offsets.  What the kernel covers beyond that is bnn::fconv_supported().
+int check_fconv_desc(const bnn_hip_fconv_desc* d) {
+  if (d->N <= 0 || d->C <= 0 || d->H <= 0 || d->W <= 0 || d->K <= 0 || d->stride <= 0) return BNN_HIP_ERR_INVALID_ARG;
+  const long long cw64 = ((long long)d->C + 63) / 64;
+  const long long Ho = ((long long)d->H - 1) / d->stride + 1, Wo = ((long long)d->W - 1) / d->stride + 1;
+  if (mulc(d->N, d->H, d->W, cw64) > kMaxPlaneWords) return BNN_HIP_ERR_TOO_LARGE;
+  if (mulc(d->N, d->C, Ho, Wo) > kMaxConvElems) return BNN_HIP_ERR_TOO_LARGE;
+  if (mulc(((long long)d->C + 31) / 32 * 32, d->K, 2 * cw64) > kMaxElems) return BNN_HIP_ERR_TOO_LARGE;
+  return BNN_HIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -943,6 +955,45 @@ int bnn_hip_bconv2d_grouped_fused(const bnn_hip_conv_desc* d, int groups, const 
   g_launches.fetch_add(1, std::memory_order_relaxed);
   BNN_RANGE();
   return bnn::launch_bconv_grouped_cell(p, groups, S, shuffle_groups, static_cast<hipStream_t>(stream));
+}
+
+int bnn_hip_fconv_supported(const bnn_hip_fconv_desc* d) {
+  return (d && check_fconv_desc(d) == BNN_HIP_OK && bnn::fconv_supported(d->C, d->H, d->W, d->K, d->stride)) ? 1 : 0;
+}
+
+int bnn_hip_fconv_fused(const bnn_hip_fconv_desc* d, const uint64_t* P, const uint64_t* M, const uint32_t* w1bits,
+                        const uint32_t* w1nz, const bnn_hip_fconv_stage* s1, const uint32_t* w2bits, const uint32_t* w2nz,
+                        const bnn_hip_fconv_stage* s2, const float* mid_scale, const float* mid_shift, int shuffle_groups,
+                        const float* residual, float* out, void* stream) {
+  if (!d) return BNN_HIP_ERR_INVALID_ARG;
+  const int st = check_fconv_desc(d);
+  if (st != BNN_HIP_OK) return st;
+  if (!P || !M || !w1bits || !w2bits || !s1 || !s2 || !s1->alpha || !s2->alpha || !mid_scale || !mid_shift || !out)
+    return BNN_HIP_ERR_INVALID_ARG;
+  const bool wz = (d->flags & BNN_HIP_FLAG_WEIGHT_ZEROS) != 0;
+  if (wz && (!w1nz || !w2nz)) return BNN_HIP_ERR_INVALID_ARG;
+  if (!aligned(P, 16) || !aligned(M, 16) || !aligned(w1bits, 16) || !aligned(w2bits, 16) || !aligned(s1->alpha, 4) ||
+      !aligned(s2->alpha, 4) || !aligned(out, 4) || !aligned(mid_scale, 4) || !aligned(mid_shift, 4))
+    return BNN_HIP_ERR_INVALID_ARG;
+  if (wz && (!aligned(w1nz, 16) || !aligned(w2nz, 16))) return BNN_HIP_ERR_INVALID_ARG;
+  for (const bnn_hip_fconv_stage* s : {s1, s2})
+    if (!aligned(s->bias, 4) || !aligned(s->post_scale, 4) || !aligned(s->prelu, 4)) return BNN_HIP_ERR_INVALID_ARG;
+  if (shuffle_groups < 1 || d->C % shuffle_groups != 0) return BNN_HIP_ERR_INVALID_ARG;
+  if (residual) {  // read and written through independent pointers, on other planes under the shuffle: no overlap
+    const int Ho = (d->H - 1) / d->stride + 1, Wo = (d->W - 1) / d->stride + 1;
+    const uintptr_t r = reinterpret_cast<uintptr_t>(residual), o = reinterpret_cast<uintptr_t>(out);
+    const uintptr_t bytes = (uintptr_t)mulc(d->N, d->C, Ho, Wo) * 4;   // (check_fconv_desc: below 2^32)
+    if (!aligned(residual, 4) || (r < o + bytes && o < r + bytes)) return BNN_HIP_ERR_INVALID_ARG;
+  }
+  if (!bnn::fconv_supported(d->C, d->H, d->W, d->K, d->stride)) return BNN_HIP_ERR_UNSUPPORTED;
+  bnn::FconvP p{};
+  p.P = P; p.M = M; p.W1 = w1bits; p.Z1 = wz ? w1nz : nullptr; p.W2 = w2bits; p.Z2 = wz ? w2nz : nullptr;
+  p.s1 = *s1; p.s2 = *s2; p.mid_a = mid_scale; p.mid_b = mid_shift; p.res = residual; p.out = out;
+  p.N = d->N; p.C = d->C; p.H = d->H; p.W = d->W; p.K = d->K; p.stride = d->stride; p.shuffle_groups = shuffle_groups;
+  p.wz = wz;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_fconv(p, static_cast<hipStream_t>(stream));
 }
 
 int bnn_hip_bconv2d_grouped_node(const bnn_hip_conv_desc* d, int groups, const uint64_t* P, const uint64_t* M,

@@ -61,7 +61,9 @@
 extern "C" {
 #endif
 
-/* Additive entry points of ABI 16 for the Linear with binary activations and real weights (no struct or signature
+/* Additive entry points of ABI 16 for the BATS FactorizedConv (no struct or signature changed): + bnn_hip_fconv_desc,
+ * bnn_hip_fconv_stage, bnn_hip_fconv_supported, bnn_hip_fconv_fused (csrc/fconv.hip).
+ * Additive entry points of ABI 16 for the Linear with binary activations and real weights (no struct or signature
  * changed): + bnn_hip_slinear_f32, bnn_hip_ste_mask_f32 (csrc/slinear.hip).
  * Additive entry points of ABI 16 for the convolution with binary activations and real weights (no struct or signature
  * changed): + bnn_hip_sconv2d_weight_pack_bytes, bnn_hip_sconv2d_pack_weight_f32, bnn_hip_sconv2d_f32 (csrc/sconv.hip).
@@ -703,6 +705,52 @@ int bnn_hip_bconv2d_grouped_node(const bnn_hip_conv_desc* d, int groups, const u
                                  const float* post_scale, const float* prelu, int shuffle_groups,
                                  const bnn_hip_f32_view* residual, const bnn_hip_f32_view* addend, float* out,
                                  int out_c_offset, int out_c_total, void* stream);
+
+/* ---- The BATS FactorizedConv ('conv_7x1_1x7', bnn/models/layers/bats_ops.py:55-75) in one launch: additive entry points
+ * of ABI 16 (csrc/fconv.hip). ----
+ *     y = [x +] channel_shuffle(PReLU(conv_Kx1(sign(BatchNorm(PReLU(conv_1xK(sign(BatchNorm(x)))))))), 4)
+ * Two dense binary convolutions over C channels: [C,C,1,K] with stride (1, s) and padding (0, K/2), then [C,C,K,1] with
+ * stride (s, 1) and padding (K/2, 0).  With Wm = (W-1)/s + 1, Ho = (H-1)/s + 1, Wo = Wm, every float operation rounded on
+ * its own:
+ *     dot1[n,m,y,xm] = zero-aware XNOR dot over (c, kx) of planes[n,c,y, s*xm + kx - K/2] and w1[m,c,0,kx]   (outside the image: 0)
+ *     v = fmaf(alpha1[m], dot1, bias1 ? bias1[m] : 0);  v *= post_scale1[m] (if given);  v = v >= 0 ? v : prelu1[m]*v (if given)
+ *     p = fmaf(v, mid_scale[m], mid_shift[m]);          t[n,m,y,xm] = (p > 0) - (p < 0)        (NaN, +-0 -> 0: the planes' predicate)
+ *     dot2[n,o,yo,xo] = zero-aware dot over (m, ky) of t[n,m, s*yo + ky - K/2, xo] and w2[o,m,ky,0]   (rows outside the image: 0)
+ *     v = fmaf(alpha2[o], dot2, bias2 ? bias2[o] : 0);  v *= post_scale2[o] (if given);  v = v >= 0 ? v : prelu2[o]*v (if given)
+ *     o' = (o % (C/sg)) * sg + o / (C/sg)     (sg = shuffle_groups; 1: o' = o)
+ *     out[n,o',yo,xo] = residual ? residual[n,o',yo,xo] + v : v
+ * The bits of: bnn_hip_bconv2d_fused of the 1 x K layer (prelu, pack_scale / pack_shift = mid_scale / mid_shift, planes
+ * only), bnn_hip_bconv2d_fused of the K x 1 layer (prelu), then shuffle and add as separate fp32 passes.  t is kept in LDS
+ * as two bit planes: it is never written to global memory, and no fp32 intermediate exists.
+ * P / M: bnn_hip_bn_act_pack_f32 planes [N, ceil(C/64), H, W]; w1bits / w1nz and w2bits / w2nz: bnn_hip_pack_weight_f32 of
+ * the two weights (wnz may be NULL unless BNN_HIP_FLAG_WEIGHT_ZEROS is set in d->flags: then both masks are honoured);
+ * s1 / s2: the per-channel constants of the two stages (alpha [o_pad] from the weight pack, the rest [C] or NULL);
+ * mid_scale / mid_shift: the folded BatchNorm between the convolutions, [C]; residual, out: float32 [N, C, Ho, Wo], not
+ * overlapping.  Planes and weight words 16-byte aligned, fp32 tensors 4.
+ * Covered (bnn_hip_fconv_supported, HOST: 1 / 0): K in {1, 3, 5, 7}, stride in {1, 2}, and
+ * 2 * ceil(C/64) * K * Wm * 8 bytes (K rows of t) within the 64 KB of LDS a workgroup takes: a workgroup computes a band
+ * of output rows of one image — the whole image where 2 * ceil(C/64) * (s*(Ho-1) + K) * Wm * 8 bytes fit — and the
+ * s*(rows-1) + K rows of t under it.  Anything else: BNN_HIP_ERR_UNSUPPORTED (the composition above is the fallback).
+ * Null or misaligned pointers, non-positive sizes, shuffle_groups < 1 or not dividing C: BNN_HIP_ERR_INVALID_ARG; planes
+ * of 2^29 words or an fp32 tensor of 2^30 elements and more: BNN_HIP_ERR_TOO_LARGE (split the batch).                  */
+typedef struct bnn_hip_fconv_desc {
+  int32_t N, C, H, W;   /* input [N,C,H,W]                                       */
+  int32_t K;            /* kernel extent of both convolutions                    */
+  int32_t stride;       /* (1, s) then (s, 1)                                    */
+  int32_t flags;        /* BNN_HIP_FLAG_WEIGHT_ZEROS                             */
+  int32_t reserved;     /* 0                                                     */
+} bnn_hip_fconv_desc;
+typedef struct bnn_hip_fconv_stage {
+  const float* alpha;      /* [o_pad]                                            */
+  const float* bias;       /* [C] or NULL                                        */
+  const float* post_scale; /* [C] or NULL                                        */
+  const float* prelu;      /* [C] or NULL                                        */
+} bnn_hip_fconv_stage;
+int bnn_hip_fconv_supported(const bnn_hip_fconv_desc* d);
+int bnn_hip_fconv_fused(const bnn_hip_fconv_desc* d, const uint64_t* P, const uint64_t* M, const uint32_t* w1bits,
+                        const uint32_t* w1nz, const bnn_hip_fconv_stage* s1, const uint32_t* w2bits, const uint32_t* w2nz,
+                        const bnn_hip_fconv_stage* s2, const float* mid_scale, const float* mid_shift, int shuffle_groups,
+                        const float* residual, float* out, void* stream);
 
 /* ---- The real-valued stem of a BATS CIFAR network with the binarisation of its consumers (additive, ABI 15). ----
  * Conv2d(3, O, 3, stride 1, padding 1, no bias) -> folded BatchNorm -> ReLU (bnn/models/bats.py:118-122), and K plane

@@ -627,6 +627,29 @@ int launch_grouped_wgrad(const GroupedGradP& q, const float* g, const uint64_t* 
   REQUIRE(g && P && M && part && al(g, 4) && al(P, 8) && al(M, 8) && al(part, 4) && splits >= 1 && splits <= q.N && splits <= 65535);
   return BNN_HIP_OK;
 }
+// the FactorizedConv launch (csrc/fconv.hip): a geometry the stub's own statement of the kernel's coverage accepts, every
+// tensor inside the 32-bit byte offsets, the two fp32 tensors disjoint
+bool fconv_supported(int C, int H, int W, int K, int stride) {
+  if (C <= 0 || H <= 0 || W <= 0 || K < 1 || K > 7 || K % 2 == 0 || (stride != 1 && stride != 2)) return false;
+  return 2LL * ((C + 63) / 64) * K * ((W - 1) / stride + 1) * 8 <= 64 * 1024;
+}
+int launch_fconv(const FconvP& p, hipStream_t) {
+  ++g_reached;
+  REQUIRE(p.N > 0 && fconv_supported(p.C, p.H, p.W, p.K, p.stride));
+  const long long Ho = (p.H - 1) / p.stride + 1, Wo = (p.W - 1) / p.stride + 1;
+  REQUIRE((long long)p.N * p.H * p.W * ((p.C + 63) / 64) <= kPlaneWords && (long long)p.N * p.C * Ho * Wo <= kConvElems);
+  REQUIRE(p.P && p.M && p.W1 && p.W2 && p.out && al(p.P, 16) && al(p.M, 16) && al(p.W1, 16) && al(p.W2, 16) && al(p.out, 4));
+  REQUIRE(p.wz ? (p.Z1 && p.Z2 && al(p.Z1, 16) && al(p.Z2, 16)) : (!p.Z1 && !p.Z2));
+  REQUIRE(p.s1.alpha && p.s2.alpha && p.mid_a && p.mid_b && al(p.s1.alpha, 4) && al(p.s2.alpha, 4) && al(p.mid_a, 4) && al(p.mid_b, 4));
+  for (const bnn_hip_fconv_stage* st : {&p.s1, &p.s2}) REQUIRE(al(st->bias, 4) && al(st->post_scale, 4) && al(st->prelu, 4));
+  REQUIRE(p.shuffle_groups >= 1 && p.C % p.shuffle_groups == 0);
+  if (p.res) {
+    const uintptr_t r = reinterpret_cast<uintptr_t>(p.res), o = reinterpret_cast<uintptr_t>(p.out);
+    const uintptr_t bytes = (uintptr_t)((long long)p.N * p.C * Ho * Wo) * 4;
+    REQUIRE(al(p.res, 4) && (r >= o + bytes || o >= r + bytes));
+  }
+  return BNN_HIP_OK;
+}
 int launch_probe_int_alu(int mode, int iters, double* r, double*, hipStream_t) { REQUIRE(iters > 0 && r); (void)mode; return BNN_HIP_OK; }
 int launch_probe_clock(int it, double* mhz, double*, hipStream_t) { REQUIRE(it > 0 && mhz); return BNN_HIP_OK; }
 }  // namespace bnn
@@ -972,6 +995,26 @@ int main(int argc, char** argv) {
         break; }
       default: { bnn_hip_conv_desc d = pick_desc();
         (void)bnn_hip_shortcut_fold_supported(rnd() % 16 ? &d : nullptr, pick_int());
+        { // the FactorizedConv entry points: mostly a plausible geometry, sometimes anything
+          bnn_hip_fconv_desc fd;
+          fd.N = pick_int(); fd.C = pick_int(); fd.H = pick_int(); fd.W = pick_int(); fd.K = pick_int(); fd.stride = pick_int();
+          fd.flags = (int)(rnd() % 4); fd.reserved = 0;
+          if (rnd() % 2) { fd.K = 1 + 2 * (int)(rnd() % 4); fd.stride = 1 + (int)(rnd() % 2); }
+          if (rnd() % 2) { fd.C = 16 * (1 + (int)(rnd() % 16)); }
+          const int sup = bnn_hip_fconv_supported(rnd() % 16 ? &fd : nullptr);
+          if (sup != 0 && sup != 1) broken("fconv_supported");
+          bnn_hip_fconv_stage s1{pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>()};
+          bnn_hip_fconv_stage s2{pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>()};
+          const int sgs[] = {1, 1, 2, 4};
+          float* fout = pick_ptr<float>();
+          const float* fres = rnd() % 3 == 0 ? nullptr : rnd() % 4 == 0 ? fout : reinterpret_cast<const float*>(0x7fff0000fff0ull);
+          const int sf = bnn_hip_fconv_fused(rnd() % 16 ? &fd : nullptr, pick_ptr<uint64_t>(), pick_ptr<uint64_t>(),
+                                             pick_ptr<uint32_t>(), pick_ptr<uint32_t>(), rnd() % 16 ? &s1 : nullptr,
+                                             pick_ptr<uint32_t>(), pick_ptr<uint32_t>(), rnd() % 16 ? &s2 : nullptr,
+                                             pick_ptr<float>(), pick_ptr<float>(), rnd() % 8 ? sgs[rnd() % 4] : pick_int(), fres,
+                                             fout, stream);
+          if (!status_ok(sf)) broken("fconv status");
+        }
         { // the route queries: the validator of bnn_hip_bconv2d_fused / _dot on a descriptor and an epilogue alone
           bnn_hip_epilogue e; std::memset(&e, 0, sizeof(e));
           e.alpha = pick_ptr<float>(); e.bn_scale = pick_ptr<float>(); e.bn_shift = pick_ptr<float>(); e.residual = pick_ptr<float>();
