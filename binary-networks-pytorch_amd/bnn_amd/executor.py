@@ -114,6 +114,8 @@ class _Conv:
     thr: Optional[torch.Tensor] = None   # integer sign thresholds of a BN + ReLU -> planes-only epilogue
     w8: Optional[torch.Tensor] = None    # int8 MFMA pack of the weight (csrc/bconv_mfma.hip), built with the plan
     mfma: dict = field(default_factory=dict)   # (geometry, epilogue) -> this launch runs on the int8 matrix cores
+    sc_w8: Optional[torch.Tensor] = None  # a block's shortcut convolution: int8 pack of its 1x1 weight (built with the plan)
+    mfma_fold: dict = field(default_factory=dict)   # geometry -> this launch, with its shortcut folded in, does too
 
     def _on_matrix_cores(self, act: hipops.PackedAct, residual, out_f32: bool, out_packed: bool, thr, epi) -> bool:
         """The admission of one launch to the MFMA convolution: the table of ``fastpath`` (shapes that measured faster)
@@ -135,8 +137,31 @@ class _Conv:
                     stride=lay.stride, padding=lay.padding, dilation=lay.dilation, sign_thresholds=thr is not None))
         return ok
 
-    def run(self, act: hipops.PackedAct, *, residual=None, out_f32: bool, out_packed: bool, **epi):
-        """``epi``: the pre-activation switches of ``hipops.bconv2d_fused`` (late residual, pack affine, ...)."""
+    def _fold_on_matrix_cores(self, act: hipops.PackedAct, out_f32: bool, out_packed: bool, epi, sc_w8) -> bool:
+        """The same for a launch with the block's shortcut folded in (``epi`` is exactly the shortcut): the table of
+        ``fastpath.MFMA_FOLD_SHAPES`` and ``bnn_hip_bconv2d_mfma_fold_supported``, asked once per geometry."""
+        if self.w8 is None or sc_w8 is None or set(epi) != {"shortcut"} or not (out_f32 and out_packed):
+            return False
+        sa = epi["shortcut"][0]
+        key = (tuple(act.shape), act.nonneg, tuple(sa.shape), self.throughput)
+        ok = self.mfma_fold.get(key)
+        if ok is None:
+            lay = self.layer
+            pooled = tuple(sa.shape[2:]) == tuple(hipops.conv_out_hw(act.shape[2], act.shape[3], 3, 3, lay.stride,
+                                                                     lay.padding, lay.dilation))
+            ok = self.mfma_fold[key] = bool(
+                lay.bias is None and self.plan.scale is None and self.bn_scale is not None and self.relu
+                and self.prelu is None and tuple(lay.kernel_size) == (3, 3)
+                and fastpath.mfma_fold_admitted(act.shape[1], lay.out_channels, act.shape[2], sa.shape[1])
+                and hipops.bconv2d_mfma_fold_supported(
+                    act.shape, self.weight, sa.shape[1], nonneg=act.nonneg, stride=lay.stride, padding=lay.padding,
+                    dilation=lay.dilation, unpooled_hw=None if pooled else tuple(sa.shape[2:]),
+                    throughput=self.throughput))
+        return ok
+
+    def run(self, act: hipops.PackedAct, *, residual=None, out_f32: bool, out_packed: bool, shortcut_w8=None, **epi):
+        """``epi``: the pre-activation switches of ``hipops.bconv2d_fused`` (late residual, pack affine, ...);
+        ``shortcut_w8``: the int8 pack of the weight in ``epi["shortcut"]``, where there is one."""
         lay = self.layer
         if _TAP is not None:
             _TAP(self.name, act)
@@ -148,6 +173,8 @@ class _Conv:
                     dilation=lay.dilation, throughput=self.throughput, sign_thresholds=thr, **epi)
         if self._on_matrix_cores(act, residual, out_f32, out_packed, thr, epi):
             return hipops.bconv2d_mfma_fused(act, self.weight, self.w8, **args)
+        if residual is None and self._fold_on_matrix_cores(act, out_f32, out_packed, epi, shortcut_w8):
+            return hipops.bconv2d_mfma_fold_fused(act, self.weight, self.w8, shortcut_w8, **args)
         return hipops.bconv2d_fused(act, self.weight, **args)
 
 
@@ -496,6 +523,9 @@ class FusedResNet(nn.Module):
                               "count_include_pad=False)")
         entry.ds = self._conv(conv, bn, None)
         entry.pool = k
+        # the int8 form of the shortcut weight, for the fold on the matrix cores (None: no such form, or switched off)
+        if fastpath.MFMA_CONV != "0" and fastpath.MFMA_FOLD != "0":
+            entry.ds.sc_w8 = hipops.pack_shortcut_weight_i8(entry.ds.weight)
 
     @torch.no_grad()
     def _forward_impl(self, x: torch.Tensor) -> torch.Tensor:
@@ -607,7 +637,7 @@ class FusedResNet(nn.Module):
             dead_f32 = (self.skip_dead_f32 and nxt is not None and nxt.kind == "post" and nxt.ds is not None
                         and (nxt.pool <= 1 or (c2.relu and c2.prelu is None)))
             if fold is not None:
-                t, packed = c2.run(packed, out_f32=True, out_packed=True, shortcut=fold)
+                t, packed = c2.run(packed, out_f32=True, out_packed=True, shortcut=fold, shortcut_w8=b.ds.sc_w8)
             else:
                 t, packed = c2.run(packed, residual=idn, out_f32=not dead_f32, out_packed=i != last)
         return t

@@ -80,7 +80,8 @@ MFMA_CONV_SHAPES = {
     #   (64, 64, 56, 1, False)   layer1.*.conv1 51.6 -> 49.2, 51.2 -> 48.0 but layer1.*.conv2 81.2 -> 86.2, 63.3 -> 69.6
     #                            (the fp32 residual and output streams: 54 us of HBM time, not hidden behind the MFMAs)
     #   (64, 128, 56, 2, False)  layer2.0.conv1 28.9 -> 30.0
-    # not built: the folded shortcut (layer2.0 / 3.0 / 4.0 conv2) — bnn_hip_bconv2d_mfma_supported says no
+    # the folded shortcut (layer2.0 / 3.0 / 4.0 conv2) has a launch and a table of its own: MFMA_FOLD_SHAPES below
+    # (bnn_hip_bconv2d_mfma_supported keeps saying no to it)
 }
 
 
@@ -88,6 +89,26 @@ def mfma_conv_admitted(C: int, O: int, H: int, stride: int, fold: bool) -> bool:
     if MFMA_CONV == "0":
         return False
     return MFMA_CONV == "all" or (C, O, H, stride, fold) in MFMA_CONV_SHAPES
+
+
+# The same for the last convolution of a down-sampling block with its shortcut folded in (csrc/bconv_mfma.hip, the DS form:
+# both dots on the matrix cores, bnn_hip_bconv2d_mfma_fold_fused) instead of the popcount fold.
+# BNN_AMD_MFMA_FOLD: "1" (default) — the launches listed in MFMA_FOLD_SHAPES; "0" — none: exactly the launches of before;
+# "all" — every launch bnn_hip_bconv2d_mfma_fold_supported takes.  BNN_AMD_MFMA_CONV=0 turns this off too.
+MFMA_FOLD = os.environ.get("BNN_AMD_MFMA_FOLD", "1")
+# (C, O, H of the input, channels of the shortcut input) -> (popcount us, MFMA us) in the same kind of trace
+# (profiles/mfma_fold_kernel_roofline.md).  A shape is listed only where the fold launch measured faster.
+MFMA_FOLD_SHAPES = {           # (means of two traces each; both MFMA values lie below both popcount values)
+    (128, 128, 28, 64): (71.0, 61.2),     # layer2.0.conv2 + shortcut
+    (256, 256, 14, 128): (66.0, 50.3),    # layer3.0.conv2 + shortcut
+    (512, 512, 7, 256): (71.8, 45.3),     # layer4.0.conv2 + shortcut
+}
+
+
+def mfma_fold_admitted(C: int, O: int, H: int, sc_C: int) -> bool:
+    if MFMA_CONV == "0" or MFMA_FOLD == "0":
+        return False
+    return MFMA_FOLD == "all" or (C, O, H, sc_C) in MFMA_FOLD_SHAPES
 
 
 # The one-launch FactorizedConv kernel (csrc/fconv.hip) against the per-layer path of the same module, batch 256 on

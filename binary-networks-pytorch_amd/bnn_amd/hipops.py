@@ -1246,6 +1246,65 @@ def bconv2d_mfma_fused(a: PackedAct, w: PackedWeight, w8: torch.Tensor, **kw):
     return y, pk
 
 
+def pack_shortcut_weight_i8(sw: PackedWeight) -> Optional[torch.Tensor]:
+    """The int8 MFMA-fragment form of a shortcut's packed 1x1 weight (``bnn_hip_pack_shortcut_weight_i8``, layout:
+    include/bnn_hip.h), or ``None`` where there is none (not 1x1, zero weights, O no multiple of 64, C not 64 / 128 / 256,
+    a grouped pack).  One launch; ``sw.alpha`` is used unchanged beside it."""
+    lib = native.require()
+    if sw.windowed or sw.groups != 1 or sw.has_zero:
+        return None
+    O, C, KH, KW = sw.shape
+    if (KH, KW) != (1, 1):
+        return None
+    nbytes = int(lib.bnn_hip_shortcut_weight_i8_bytes(O, C))
+    if nbytes == 0:
+        return None
+    dev = sw.wbits.device
+    with torch.cuda.device(dev):
+        w8 = torch.empty(nbytes, dtype=torch.int8, device=dev)
+        native.check(lib.bnn_hip_pack_shortcut_weight_i8(sw.wbits.data_ptr(), O, C, w8.data_ptr(), _stream(dev)),
+                     "bnn_hip_pack_shortcut_weight_i8")
+    return w8
+
+
+def bconv2d_mfma_fold_supported(a_shape, w: PackedWeight, sc_channels: int, *, nonneg: bool = True, stride=1, padding=1,
+                                dilation=1, unpooled_hw: Optional[Tuple[int, int]] = None, throughput: bool = False) -> bool:
+    """Whether ``bconv2d_mfma_fold_fused`` takes this convolution with a folded shortcut of ``sc_channels`` input channels
+    (``bnn_hip_bconv2d_mfma_fold_supported``: host only).  The epilogue is the one the fold belongs to: BatchNorm +
+    shortcut + ReLU -> fp32 + sign planes.  ``unpooled_hw``: the shortcut plane comes un-pooled at this size."""
+    lib = native.require()
+    if w.windowed or w.groups != 1:
+        return False
+    flags = (native.FLAG_ACT_NONNEG if nonneg else 0) | (native.FLAG_WEIGHT_ZEROS if w.has_zero else 0) | \
+        (native.FLAG_THROUGHPUT if throughput else 0)
+    d = _desc(tuple(a_shape), w.shape, stride, padding, dilation, flags)
+    p = 0x10000   # never dereferenced
+    hw = 0 if unpooled_hw is None else (int(unpooled_hw[0]) << 16) | int(unpooled_hw[1])
+    e = native.Epilogue(p, None, None, p, p, None, None, 1, 0, p, p, p, None, None, 0, 0, None,
+                        p, None, p, p, p, int(sc_channels), hw)
+    return bool(lib.bnn_hip_bconv2d_mfma_fold_supported(ctypes.byref(d), ctypes.byref(e)))
+
+
+def bconv2d_mfma_fold_fused(a: PackedAct, w: PackedWeight, w8: torch.Tensor, sc_w8: torch.Tensor, **kw):
+    """``bconv2d_fused(a, w, ..., shortcut=(sa, sw, bn_a, bn_b))`` with both dots on ``v_mfma_i32_16x16x64_i8``
+    (``bnn_hip_bconv2d_mfma_fold_fused``): same arguments, same bits.  ``w8 = pack_weight_i8(w)``,
+    ``sc_w8 = pack_shortcut_weight_i8(sw)``.  Raises where ``bconv2d_mfma_fold_supported`` says no."""
+    lib = native.require()
+    if kw.get("shortcut") is None:
+        raise native.NativeError("bnn_amd: bconv2d_mfma_fold_fused needs shortcut=(PackedAct, PackedWeight, bn_a, bn_b)")
+    y, pk, nonneg, launches = _fused_launches(a, w, "bconv2d_mfma_fold_fused", **kw)
+    dev = a.P.device
+    with torch.cuda.device(dev):
+        for dd, e, n0, n1 in launches:
+            native.check(lib.bnn_hip_bconv2d_mfma_fold_fused(ctypes.byref(dd), a.P[n0:n1].data_ptr(),
+                                                             a.M[n0:n1].data_ptr(), w8.data_ptr(), sc_w8.data_ptr(),
+                                                             ctypes.byref(e), _stream(dev)),
+                         "bnn_hip_bconv2d_mfma_fold_fused")
+    if pk is not None:
+        pk.nonneg = nonneg
+    return y, pk
+
+
 def bconv2d_route(a: PackedAct, w: PackedWeight, *, fused: bool = True, raw_dot: bool = False, **kw) -> dict:
     """Which kernel ``bconv2d_fused(a, w, **kw)`` runs (``bnn_hip_bconv2d_route``: the launch ladder itself answers,
     nothing is launched) as a dict of the fields of ``bnn_hip_conv_route``; of the first launch when the batch is split.

@@ -34,6 +34,12 @@ constexpr int kAccStride = 68;  // int32 per channel row of the transpose buffer
 constexpr int kAccBytes = 4 * 32 * kAccStride * 4;  // four waves x 32 channels
 constexpr int kMaxLds = 64 * 1024;
 constexpr int kPatchSlots = 4;  // patch pixels per thread (1024 pixels = the LDS limit): the plane words of the next group wait in registers
+// Folded shortcut (DS): the shortcut's dots wait in LDS behind the patch / transpose buffer while the main loop runs, as
+// int16 (|dot| <= 256), one row of 64 channels per pixel of a wave.  72 int16 = 36 dwords per row: a lane's four
+// ds_read_b128 of a half land 4 banks apart from its neighbour's, eight lanes cover the 32 banks.
+constexpr int kParkStride = 72;
+constexpr int kParkBytes = 4 * 64 * kParkStride * 2;  // four waves x 64 pixels
+constexpr int kMaxLdsFold = 80 * 1024;  // two workgroups in the CU's 160 KB
 
 struct MfmaGeo {
   int tp;          // output pixels per workgroup: 256 (four waves side by side) or 128 (two by two)
@@ -44,6 +50,16 @@ struct MfmaGeo {
   int n_in;        // N * H * W
   uint32_t m_ihw;  // fast_div by ihw
   int s_ihw;
+  int park_off;    // DS: byte offset of the parked shortcut dots in the LDS
+};
+
+// The folded shortcut convolution (bconv_core.h: ShortcutArgs) with its weight as int8 A fragments.
+struct ShortcutArgs8 {
+  const uint32_t* P;
+  const int8_t* W8;  // [o / 64][group][16-channel tile][lane][16 bytes] (include/bnn_hip.h: bnn_hip_pack_shortcut_weight_i8)
+  const float* alpha;
+  const float* a;
+  const float* b;
 };
 
 // 4 bits -> 4 bytes of 0 / 1: bit i lands at 8 i  (0x00204081 = 1 + 2^7 + 2^14 + 2^21; both factors below 2^24)
@@ -66,12 +82,27 @@ __device__ __forceinline__ int centre_of(const Geo& g, const MfmaGeo& mg, int q,
   return n * mg.ihw + *oy * g.sh * g.Wd + *ox * g.sw;
 }
 
-template <int EP>
+// DS: the block's shortcut convolution folded in (EP_OUT only).  The residual of channel o at a pixel is
+//     r = fmaf(fmaf(alpha_ds[o], (float)dot1x1, 0), a_ds[o], b_ds[o])
+// — the float operations of the popcount fold (bconv_core.h: shortcut_values_cw) on the same integer.  The 1, 2 or 4
+// k-steps of the 1x1 convolution run FIRST, through the same A / B pipeline into `acc`: B = the OR-pooled P plane of the
+// tile's own output pixels expanded into the (still unused) patch, A = the shortcut's int8 pack.  Their result is parked
+// in LDS as int16 in the layout the epilogue reads (lane = pixel, 32 channels = four ds_read_b128), `acc` starts again
+// from zero and the main loop runs unchanged: no register lives across it, and the epilogue gains only the conversion.
+// (The shortcut's pointers travel behind the geometry: the kernel arguments of the plain form keep their places.)
+template <int EP, bool DS = false>
 __global__ __launch_bounds__(kMfmaThreads) void bconv_mfma_kernel(const uint32_t* __restrict__ P,
                                                                   const uint32_t* __restrict__ M,
                                                                   const int8_t* __restrict__ W8, BNN_EPI_PARAMS,
-                                                                  const Geo g, const MfmaGeo mg) {
+                                                                  const Geo g, const MfmaGeo mg,
+                                                                  const uint32_t* __restrict__ dsP,
+                                                                  const int8_t* __restrict__ dsW8,
+                                                                  const float* __restrict__ ds_alpha,
+                                                                  const float* __restrict__ ds_a,
+                                                                  const float* __restrict__ ds_b) {
+  static_assert(!DS || EP == EP_OUT, "the fold belongs to BN + residual + ReLU -> fp32 + planes");
   BNN_EPI_INIT;
+  [[maybe_unused]] const ShortcutArgs8 sc{dsP, dsW8, ds_alpha, ds_a, ds_b};
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   // (wave-uniform by construction; said so, the per-channel constants of the epilogue stay on the scalar path)
@@ -176,11 +207,97 @@ __global__ __launch_bounds__(kMfmaThreads) void bconv_mfma_kernel(const uint32_t
 
   request(0);
   i32x4 a_buf[3][4];
+  if constexpr (DS) {
+    const int sg = g.ds_cw >> 1;  // 64-channel groups of the shortcut input = its k-steps: 1, 2 or 4
+    // the shortcut plane words of tile pixel `tid` (threads past the tile hold a clamped copy and write nothing)
+    uint2 scw[4];
+    {
+      const int q = min(q0 + tid, g.npix - 1), hw = g.Ho * g.Wo;
+      const int n = (int)fast_div((uint32_t)q, g.m_hw, g.s_hw), r = q - n * hw;
+      const int oy = (int)fast_div((uint32_t)r, g.m_wo, g.s_wo), ox = r - oy * g.Wo;
+      const uint2* S2 = reinterpret_cast<const uint2*>(sc.P);
+      if (g.ds_w > 0) {  // un-pooled plane: OR of the 2 x 2 window, clipped at odd edges (load_shortcut_field)
+        const unsigned shw = (unsigned)(g.ds_h * g.ds_w);
+        const int y0 = 2 * oy, x0 = 2 * ox;
+        const bool x1 = x0 + 1 < g.ds_w, y1 = y0 + 1 < g.ds_h;
+        const unsigned b0 = (unsigned)n * (unsigned)sg * shw + (unsigned)(y0 * g.ds_w + x0);
+        static_for<4>([&](auto GI) {
+          constexpr int gi = GI;
+          uint2 v{0u, 0u};
+          if (gi < sg) {
+            const unsigned b = b0 + (unsigned)gi * shw;
+            v = S2[b];
+            const uint2 a = S2[x1 ? b + 1 : b], c = S2[y1 ? b + (unsigned)g.ds_w : b],
+                        e = S2[(x1 && y1) ? b + (unsigned)g.ds_w + 1 : b];
+            v.x |= a.x | c.x | e.x;
+            v.y |= a.y | c.y | e.y;
+          }
+          scw[gi] = v;
+        });
+      } else {
+        const unsigned b0 = (unsigned)n * (unsigned)sg * (unsigned)hw + (unsigned)r;
+        static_for<4>([&](auto GI) {
+          constexpr int gi = GI;
+          scw[gi] = gi < sg ? S2[b0 + (unsigned)(gi * hw)] : uint2{0u, 0u};
+        });
+      }
+    }
+    const int8_t* sbase = sc.W8 + (size_t)(o_wave >> 6) * sg * 4096 + lane * 16;
+    auto sa_load = [&](i32x4 (&dst)[4], int k) {
+      const int8_t* src = sbase + (size_t)min(k, sg - 1) * 4096;  // (past the end: the last k-step's again, never used)
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) dst[ct] = *reinterpret_cast<const i32x4*>(src + ct * 1024);
+    };
+    sa_load(a_buf[0], 0);
+    sa_load(a_buf[1], 1);
+    static_for<4>([&](auto K) {
+      constexpr int k = K;
+      if (k < sg) {  // (wave-uniform)
+        if (k > 0) __syncthreads();  // the previous group's reads are done
+        if (tid < mg.tp) {
+          uint4* dst = reinterpret_cast<uint4*>(lds + (size_t)tid * 64);
+#pragma unroll
+          for (int h = 0; h < 4; ++h) {
+            const uint32_t pw = h < 2 ? scw[k].x : scw[k].y;
+            const int s0 = 16 * (h & 1);
+            dst[h] = uint4{expand4(pw, 0u, s0, true), expand4(pw, 0u, s0 + 4, true), expand4(pw, 0u, s0 + 8, true),
+                           expand4(pw, 0u, s0 + 12, true)};
+          }
+        }
+        __syncthreads();
+        sa_load(a_buf[(k + 2) % 3], k + 2);
+        i32x4 b_sc[4];
+#pragma unroll
+        for (int pt = 0; pt < 4; ++pt)
+          b_sc[pt] = *reinterpret_cast<const i32x4*>(lds + (size_t)(wave_pix + 16 * pt + lrow) * 64 + lgrp * 16);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+          for (int pt = 0; pt < 4; ++pt)
+            acc[ct][pt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_buf[k % 3][ct], b_sc[pt], acc[ct][pt], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    });
+  }
   a_load(a_buf[0], 0);
   a_load(a_buf[1], 1);
+  if constexpr (DS) {
+    // park the shortcut dots (this wave's 64 pixels x 64 channels; only this wave reads them back, in the epilogue)
+    short* park = reinterpret_cast<short*>(lds + mg.park_off) + wave * (64 * kParkStride);
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+      for (int pt = 0; pt < 4; ++pt) {
+        const i32x4 v = acc[ct][pt];
+        *reinterpret_cast<uint2*>(park + (16 * pt + lrow) * kParkStride + 16 * ct + 4 * lgrp) =
+            uint2{((uint32_t)v[0] & 0xFFFFu) | ((uint32_t)v[1] << 16), ((uint32_t)v[2] & 0xFFFFu) | ((uint32_t)v[3] << 16)};
+        acc[ct][pt] = i32x4{0, 0, 0, 0};
+      }
+  }
 #pragma unroll 1
   for (int gi = 0; gi < mg.groups; ++gi) {
-    __syncthreads();  // the previous group's reads of the patch are done
+    __syncthreads();  // the previous group's reads of the patch (gi = 0, DS: of the shortcut operand) are done
     expand();
     __syncthreads();
     if (gi + 1 < mg.groups) request(gi + 1);
@@ -216,7 +333,28 @@ __global__ __launch_bounds__(kMfmaThreads) void bconv_mfma_kernel(const uint32_t
   for (int h = 0; h < 2; ++h) {
     const int o0 = o_wave + 32 * h;
     float resv[32];
-    prefetch_residual<32, EP, true>(g, px, o0, epi, resv);
+    if constexpr (DS) {
+      using f2 = __attribute__((ext_vector_type(2))) float;
+      const uint4* pr = reinterpret_cast<const uint4*>(reinterpret_cast<const short*>(lds + mg.park_off) +
+                                                       wave * (64 * kParkStride) + lane * kParkStride + 32 * h);
+      uint32_t w[16];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const uint4 v = pr[i];
+        w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+      }
+#pragma unroll
+      for (int j = 0; j < 32; j += 2) {
+        const int o = o0 + j;
+        const f2 d = f2{(float)((int)(w[j >> 1] << 16) >> 16), (float)((int)w[j >> 1] >> 16)};
+        const f2 t = __builtin_elementwise_fma(f2{sc.alpha[o], sc.alpha[o + 1]}, d, f2{0.0f, 0.0f});
+        const f2 r = __builtin_elementwise_fma(t, f2{sc.a[o], sc.a[o + 1]}, f2{sc.b[o], sc.b[o + 1]});
+        resv[j] = r.x;
+        resv[j + 1] = r.y;
+      }
+    } else {
+      prefetch_residual<32, EP, true>(g, px, o0, epi, resv);
+    }
     __syncthreads();  // the patch (h = 0) / the first half's values (h = 1) have been read
 #pragma unroll
     for (int c2 = 0; c2 < 2; ++c2)
@@ -239,7 +377,7 @@ __global__ __launch_bounds__(kMfmaThreads) void bconv_mfma_kernel(const uint32_t
 }
 
 // wbits / wnz (bnn_hip_pack_weight_f32) -> int8 A fragments (include/bnn_hip.h: bnn_hip_pack_weight_i8).  One thread per
-// four bytes.
+// four bytes.  wnz == null: no zero weights (the folded shortcut's 1x1 weight: taps = 1).
 __global__ __launch_bounds__(256) void pack_weight_i8_kernel(const uint32_t* __restrict__ wbits,
                                                              const uint32_t* __restrict__ wnz, int O, int taps,
                                                              int cw32, int cwc, uint32_t* __restrict__ w8) {
@@ -256,7 +394,7 @@ __global__ __launch_bounds__(256) void pack_weight_i8_kernel(const uint32_t* __r
   const int c0 = 64 * gi + 16 * (lane >> 4) + 4 * e4;  // four consecutive input channels, inside one 32-bit word
   const int cw_abs = c0 >> 5, ch = cw_abs / cwc, cw = cw_abs - ch * cwc;
   const size_t wi = ((size_t)((o >> 5) * nchunk + ch) * kOCB + (o & 31)) * per_o + t * cwc + cw;
-  const uint32_t b = wbits[wi] >> (c0 & 31), z = wnz[wi] >> (c0 & 31);
+  const uint32_t b = wbits[wi] >> (c0 & 31), z = wnz ? wnz[wi] >> (c0 & 31) : 15u;
   uint32_t v = 0u;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -282,12 +420,15 @@ size_t lds_bytes_of(int patch_cap) {
 
 // The tile of a launch: 256 pixels x 64 channels where only 64 channels exist or the patch of 128 pixels would not be
 // smaller anyway; 128 x 128 (half the weight traffic per pixel) otherwise.  0: no tile fits the LDS.
-int choose_tile(const ConvP& p, int* patch_cap) {
+// `park`: LDS the launch needs behind the patch (the folded shortcut's parked dots); such a launch may ask for more than
+// the default 64 KB, up to half the CU's LDS: two workgroups per CU either way.
+int choose_tile(const ConvP& p, int* patch_cap, size_t park = 0) {
+  const size_t lds_max = park ? (size_t)kMaxLdsFold : (size_t)kMaxLds;
   const int order[2] = {(p.O % 128 == 0 && p.C >= 128) ? 128 : 256, (p.O % 128 == 0 && p.C >= 128) ? 256 : 128};
   for (int tp : order) {
     if (tp == 128 && p.O % 128 != 0) continue;
     const long long cap = centre_span(p, tp) + 2LL * p.Wd + 3;
-    if (cap <= kPatchSlots * kMfmaThreads && lds_bytes_of((int)cap) <= (size_t)kMaxLds) {
+    if (cap <= kPatchSlots * kMfmaThreads && lds_bytes_of((int)cap) + park <= lds_max) {
       *patch_cap = (int)cap;
       return tp;
     }
@@ -298,7 +439,9 @@ int choose_tile(const ConvP& p, int* patch_cap) {
 template <int EP>
 void launch_ep(const ConvP& p, const Geo& g, const MfmaGeo& mg, const void* w8, dim3 grid, size_t ldsb, hipStream_t s) {
   hipLaunchKernelGGL((bconv_mfma_kernel<EP>), grid, dim3(kMfmaThreads), ldsb, s, p.P, p.M,
-                     static_cast<const int8_t*>(w8), BNN_EPI_ACTUALS, g, mg);
+                     static_cast<const int8_t*>(w8), BNN_EPI_ACTUALS, g, mg, static_cast<const uint32_t*>(nullptr),
+                     static_cast<const int8_t*>(nullptr), static_cast<const float*>(nullptr),
+                     static_cast<const float*>(nullptr), static_cast<const float*>(nullptr));
 }
 
 }  // namespace
@@ -316,24 +459,52 @@ int launch_pack_weight_i8(const uint32_t* wbits, const uint32_t* wnz, const bnn_
   return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
 }
 
-// What the kernel covers, stated once (capi.hip asks here for the launch and for bnn_hip_bconv2d_mfma_supported).
-bool mfma_conv_applies(const ConvP& p, int flags) {
+size_t shortcut_weight_i8_bytes(int O, int C) {
+  if (O <= 0 || O % 64 != 0 || (C != 64 && C != 128 && C != 256)) return 0;
+  return (size_t)O * (size_t)C;
+}
+
+int launch_pack_shortcut_weight_i8(const uint32_t* wbits, int O, int C, void* w8, hipStream_t s) {
+  // the dense layout of a 1x1 weight of these widths is [o][C / 32] words: one chunk (bnn_hip_weight_layout)
+  const int cw32 = C / 32;
+  const size_t dwords = (size_t)O * (cw32 >> 1) * 16;
+  hipLaunchKernelGGL(pack_weight_i8_kernel, dim3((unsigned)((dwords + 255) / 256)), dim3(256), 0, s, wbits,
+                     static_cast<const uint32_t*>(nullptr), O, 1, cw32, cw32, static_cast<uint32_t*>(w8));
+  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+}
+
+namespace {
+// The dense rule both forms share; `park`: choose_tile.
+bool mfma_dense_rule(const ConvP& p, int flags, size_t park) {
   if (flags & BNN_HIP_FLAG_FORCE_GENERIC) return false;
   if (p.KH != 3 || p.KW != 3 || p.ph != 1 || p.pw != 1 || p.dh != 1 || p.dw != 1) return false;
   if (p.sh != p.sw || (p.sh != 1 && p.sh != 2)) return false;
   if (p.C % 64 != 0 || p.O % 64 != 0 || !small_indices(p)) return false;
-  if (p.raw || p.prelu || p.pack_a || p.pack_b || p.eflags != 0 || p.ds_P) return false;
+  if (p.raw || p.prelu || p.pack_a || p.pack_b || p.eflags != 0) return false;
   if (p.c_off != 0 || p.c_tot != p.O) return false;
   if ((long long)p.N * p.H * p.Wd >= (1ll << 30)) return false;
   int cap = 0;
-  return choose_tile(p, &cap) != 0;
+  return choose_tile(p, &cap, park) != 0;
+}
+}  // namespace
+
+// What the kernel covers, stated once (capi.hip asks here for the launch and for bnn_hip_bconv2d_mfma_supported).
+bool mfma_conv_applies(const ConvP& p, int flags) { return !p.ds_P && mfma_dense_rule(p, flags, 0); }
+
+// The same for the folded-shortcut form (bnn_hip_bconv2d_mfma_fold_supported): the dense rule; BN + shortcut + ReLU ->
+// fp32 + sign planes (kFlagsOut) and nothing else; non-negative activations (the shortcut operand is a P plane); no zero
+// weights (the shortcut pack has none); a shortcut of 64, 128 or 256 channels (1, 2 or 4 k-steps); the patch and the
+// parked dots within half the CU's LDS.
+bool mfma_fold_applies(const ConvP& p, int flags) {
+  if (!p.ds_P || p.res || p.thr) return false;
+  if (!(flags & BNN_HIP_FLAG_ACT_NONNEG) || (flags & BNN_HIP_FLAG_WEIGHT_ZEROS)) return false;
+  if (shortcut_weight_i8_bytes(p.O, p.ds_C) == 0) return false;
+  if (make_geo(p).flags != kFlagsOut) return false;
+  return mfma_dense_rule(p, flags, (size_t)kParkBytes);
 }
 
-int launch_bconv_mfma(const ConvP& p, int flags, const void* w8, hipStream_t s) {
-  int cap = 0;
-  const int tp = choose_tile(p, &cap);
-  if (!mfma_conv_applies(p, flags) || tp == 0) return BNN_HIP_ERR_UNSUPPORTED;
-  const Geo g = make_geo(p);
+namespace {
+MfmaGeo make_mfma_geo(const ConvP& p, int flags, int tp, int cap) {
   MfmaGeo mg;
   mg.tp = tp;
   mg.groups = p.C / 64;
@@ -342,6 +513,34 @@ int launch_bconv_mfma(const ConvP& p, int flags, const void* w8, hipStream_t s) 
   mg.nn = (flags & BNN_HIP_FLAG_ACT_NONNEG) ? 1 : 0;
   mg.n_in = p.N * p.H * p.Wd;
   div_magic((uint32_t)mg.ihw, mg.m_ihw, mg.s_ihw);
+  mg.park_off = (int)lds_bytes_of(cap);
+  return mg;
+}
+}  // namespace
+
+int launch_bconv_mfma_fold(const ConvP& p, int flags, const void* w8, const void* sc_w8, hipStream_t s) {
+  int cap = 0;
+  const int tp = choose_tile(p, &cap, (size_t)kParkBytes);
+  if (!mfma_fold_applies(p, flags) || tp == 0) return BNN_HIP_ERR_UNSUPPORTED;
+  const Geo g = make_geo(p);
+  const MfmaGeo mg = make_mfma_geo(p, flags, tp, cap);
+  const dim3 grid((unsigned)((p.npix + tp - 1) / tp), (unsigned)(p.O / (tp == 256 ? 64 : 128)));
+  const size_t ldsb = lds_bytes_of(cap) + (size_t)kParkBytes;  // above the 64 KB default
+  auto kern = bconv_mfma_kernel<EP_OUT, true>;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          kMaxDynamicLds) != hipSuccess)
+    return BNN_HIP_ERR_LAUNCH;
+  hipLaunchKernelGGL(kern, grid, dim3(kMfmaThreads), ldsb, s, p.P, p.M, static_cast<const int8_t*>(w8), BNN_EPI_ACTUALS, g,
+                     mg, p.ds_P, static_cast<const int8_t*>(sc_w8), p.ds_alpha, p.ds_a, p.ds_b);
+  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+}
+
+int launch_bconv_mfma(const ConvP& p, int flags, const void* w8, hipStream_t s) {
+  int cap = 0;
+  const int tp = choose_tile(p, &cap);
+  if (!mfma_conv_applies(p, flags) || tp == 0) return BNN_HIP_ERR_UNSUPPORTED;
+  const Geo g = make_geo(p);
+  const MfmaGeo mg = make_mfma_geo(p, flags, tp, cap);
   const dim3 grid((unsigned)((p.npix + tp - 1) / tp), (unsigned)(p.O / (tp == 256 ? 64 : 128)));
   const size_t ldsb = lds_bytes_of(cap);
   const int f = g.flags;

@@ -1113,6 +1113,46 @@ int bnn_hip_bconv2d_mfma_fused(const bnn_hip_conv_desc* d, const uint64_t* P, co
   return bnn::launch_bconv_mfma(p, d->flags, w8, static_cast<hipStream_t>(stream));
 }
 
+// ---- the same with the shortcut convolution folded in ----
+size_t bnn_hip_shortcut_weight_i8_bytes(int O, int C) { return bnn::shortcut_weight_i8_bytes(O, C); }
+
+int bnn_hip_pack_shortcut_weight_i8(const uint32_t* wbits, int O, int C, void* sc_w8, void* stream) {
+  if (!wbits || !sc_w8 || O <= 0 || C <= 0) return BNN_HIP_ERR_INVALID_ARG;
+  if (bnn::shortcut_weight_i8_bytes(O, C) == 0) return BNN_HIP_ERR_UNSUPPORTED;
+  if (!aligned(wbits, 16) || !aligned(sc_w8, 16)) return BNN_HIP_ERR_INVALID_ARG;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_pack_shortcut_weight_i8(wbits, O, C, sc_w8, static_cast<hipStream_t>(stream));
+}
+
+int bnn_hip_bconv2d_mfma_fold_supported(const bnn_hip_conv_desc* d, const bnn_hip_epilogue* e) {
+  alignas(16) static const uint64_t operand[2] = {0, 0};  // stands in for the packed operands (never read)
+  bnn::ConvP p = empty_convp();
+  if (epilogue_convp(e, &p) != BNN_HIP_OK || !p.ds_P) return 0;
+  const uint32_t* const w = reinterpret_cast<const uint32_t*>(operand);
+  p.ds_W = w;  // (the shortcut's int8 pack stands in for sc_wbits in the shared validator)
+  if (check_conv(d, operand, operand, w, w, &p) != BNN_HIP_OK) return 0;
+  if (p.out && !aligned(p.out, 4)) return 0;
+  return bnn::mfma_fold_applies(p, d->flags) ? 1 : 0;
+}
+
+int bnn_hip_bconv2d_mfma_fold_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const void* w8,
+                                    const void* sc_w8, const bnn_hip_epilogue* e, void* stream) {
+  bnn::ConvP p = empty_convp();
+  int st = epilogue_convp(e, &p);
+  if (st != BNN_HIP_OK) return st;
+  if (!w8 || !aligned(w8, 16) || !sc_w8 || !aligned(sc_w8, 16)) return BNN_HIP_ERR_INVALID_ARG;
+  if (!p.ds_P) return BNN_HIP_ERR_UNSUPPORTED;
+  p.ds_W = static_cast<const uint32_t*>(sc_w8);  // (stands in for sc_wbits in the shared validator, like w8 for wbits)
+  st = check_conv(d, P, M, static_cast<const uint32_t*>(w8), static_cast<const uint32_t*>(w8), &p);
+  if (st != BNN_HIP_OK) return st;
+  if (p.out && !aligned(p.out, 4)) return BNN_HIP_ERR_INVALID_ARG;
+  if (!bnn::mfma_fold_applies(p, d->flags)) return BNN_HIP_ERR_UNSUPPORTED;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_bconv_mfma_fold(p, d->flags, w8, sc_w8, static_cast<hipStream_t>(stream));
+}
+
 int bnn_hip_sign_thresholds_f32(const float* alpha, const float* bias, const float* post_scale, const float* bn_scale,
                                 const float* bn_shift, int O, int kmax, int32_t* thresholds, void* stream) {
   // (kmax < 2^20: the two-instruction form of the test biases its counts by 2^20 > kmax / 2, bconv_core.h kMidtBias)

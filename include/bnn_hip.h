@@ -532,6 +532,31 @@ int bnn_hip_bconv2d_mfma_supported(const bnn_hip_conv_desc* d, const bnn_hip_epi
 int bnn_hip_bconv2d_mfma_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const void* w8,
                                const bnn_hip_epilogue* epi, void* stream);
 
+/* ---- The same with the block's shortcut convolution folded in (additive entry points of ABI 16).  The launch of
+ * bnn_hip_bconv2d_fused with epi->sc_* set (BatchNorm + shortcut + ReLU -> fp32 + sign planes), both dots on
+ * v_mfma_i32_16x16x64_i8: the shortcut's 1x1 dot runs first through the same pipeline (operand B: the P plane sc_P at the
+ * output pixels, OR-pooled in the kernel when sc_in_hw != 0), waits in LDS as int16 and enters the epilogue as
+ *     r = fmaf(fmaf(sc_alpha[o], (float)dot, 0), sc_bn_scale[o], sc_bn_shift[o])
+ * — the float operations of the popcount fold on the same integer, so every output bit equals bnn_hip_bconv2d_fused's.
+ * epi->sc_wbits is not read (it may be NULL): the shortcut weight comes as `sc_w8`.
+ *
+ * Covered (bnn_hip_bconv2d_mfma_fold_supported == 1): what bnn_hip_bconv2d_mfma_supported covers, and: sc_* present;
+ * epilogue exactly alpha, BatchNorm, ReLU, out_f32 and out_P / out_M (no bias, post_scale, residual, sign_thresholds);
+ * BNN_HIP_FLAG_ACT_NONNEG; no BNN_HIP_FLAG_WEIGHT_ZEROS (the shortcut pack has no zero weights); sc_C in {64, 128,
+ * 256}; the LDS patch plus 36 KB of parked shortcut dots within 80 KB (two workgroups per CU).
+ *
+ * bnn_hip_pack_shortcut_weight_i8: wbits of the 1x1 weight [O, C, 1, 1] (bnn_hip_pack_weight_f32; bit ? +1 : -1, no
+ * zeros) -> `sc_w8`, bnn_hip_shortcut_weight_i8_bytes(O, C) = O C bytes (0: O % 64 != 0 or C not in {64, 128, 256}),
+ * 16-byte aligned.  Byte layout, G = C / 64 — bnn_hip_pack_weight_i8's with one tap:
+ *   sc_w8[o / 64][g][ct][lane][e]   int8, g < G, ct < 4, lane < 64, e < 16
+ *       = W[o = 64 (o / 64) + 16 ct + (lane & 15)][c = 64 g + 16 (lane >> 4) + e]   as +1 / -1                        */
+size_t bnn_hip_shortcut_weight_i8_bytes(int O, int C);
+int bnn_hip_pack_shortcut_weight_i8(const uint32_t* wbits, int O, int C, void* sc_w8, void* stream);
+/* HOST: 1 when bnn_hip_bconv2d_mfma_fold_fused() takes this convolution with this epilogue, 0 otherwise.            */
+int bnn_hip_bconv2d_mfma_fold_supported(const bnn_hip_conv_desc* d, const bnn_hip_epilogue* epi);
+int bnn_hip_bconv2d_mfma_fold_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const void* w8,
+                                    const void* sc_w8, const bnn_hip_epilogue* epi, void* stream);
+
 /* ---- Which kernel a convolution runs (ABI 16): the route of bnn_hip_bconv2d / _fused / _dot, for tests. ----
  * The launch ladder of csrc/bconv.hip picks one instantiation per call from the kernel size, the chunk width, the
  * epilogue, the flags and the size of the grid.  The route query walks THAT ladder (the same statements, with the

@@ -89,6 +89,32 @@ int launch_bconv_mfma(const ConvP& p, int flags, const void* w8, hipStream_t) {
   REQUIRE(!p.out || al(p.out, 4));
   return BNN_HIP_OK;
 }
+// the same with the shortcut convolution folded in
+size_t shortcut_weight_i8_bytes(int O, int C) {
+  return (O > 0 && O % 64 == 0 && (C == 64 || C == 128 || C == 256)) ? (size_t)O * (size_t)C : 0;
+}
+int launch_pack_shortcut_weight_i8(const uint32_t* wbits, int O, int C, void* w8, hipStream_t) {
+  ++g_reached;
+  REQUIRE(wbits && w8 && al(wbits, 16) && al(w8, 16) && shortcut_weight_i8_bytes(O, C) != 0);
+  return BNN_HIP_OK;
+}
+bool mfma_fold_applies(const ConvP& p, int flags) {
+  check_convp(p);
+  return p.KH == 3 && p.KW == 3 && p.C % 64 == 0 && p.O % 64 == 0 && p.ds_P && !p.res && !p.prelu && p.c_tot == p.O &&
+         (flags & BNN_HIP_FLAG_ACT_NONNEG) && shortcut_weight_i8_bytes(p.O, p.ds_C) != 0;
+}
+int launch_bconv_mfma_fold(const ConvP& p, int flags, const void* w8, const void* sc_w8, hipStream_t) {
+  ++g_reached;
+  check_convp(p);
+  REQUIRE(mfma_fold_applies(p, flags));
+  REQUIRE((long long)p.N * p.H * p.Wd * ((p.C + 63) / 64) <= kPlaneWords);
+  REQUIRE(p.P && p.M && w8 && sc_w8 && al(p.P, 16) && al(p.M, 16) && al(w8, 16) && al(sc_w8, 16) && p.alpha);
+  REQUIRE(p.ds_P && al(p.ds_P, 8) && p.ds_alpha && p.ds_a && p.ds_b);
+  REQUIRE(p.ds_inW == 0 || ((p.ds_inH + 1) / 2 == p.Ho && (p.ds_inW + 1) / 2 == p.Wo));
+  REQUIRE(!p.outP || (al(p.outP, 8) && al(p.outM, 8)));
+  REQUIRE(!p.out || al(p.out, 4));
+  return BNN_HIP_OK;
+}
 bool fly_supported(const ConvP& p) { return p.KH * p.KW <= 49; }
 int fly_default_plan(const ConvP& p, int, bnn_hip_fly_plan* plan) {
   check_convp(p);
@@ -1043,6 +1069,17 @@ int main(int argc, char** argv) {
           const int sp8 = bnn_hip_pack_weight_i8(pick_ptr<uint32_t>(), pick_ptr<uint32_t>(), d.O, d.C, d.KH, d.KW, pick_ptr<char>(), stream);
           if (!status_ok(sp8)) broken("int8 weight pack status");
           digest = (digest ^ (uint64_t)(uint32_t)sm ^ ((uint64_t)(uint32_t)sp8 << 32) ^ (uint64_t)sup) * 0x100000001B3ull;
+          // and its folded-shortcut form
+          const int fsup = bnn_hip_bconv2d_mfma_fold_supported(dp, ep);
+          if (fsup != 0 && fsup != 1) broken("mfma fold supported");
+          const int sf = bnn_hip_bconv2d_mfma_fold_fused(dp, pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<char>(),
+                                                         pick_ptr<char>(), ep, stream);
+          if (!status_ok(sf) || (sf == BNN_HIP_OK && !fsup)) broken("mfma fold launched where the query said no");
+          const int sc_c = rnd() % 4 ? 64 << (rnd() % 3) : pick_int();
+          if (bnn_hip_shortcut_weight_i8_bytes(d.O, sc_c) > ((size_t)1 << 62)) broken("int8 shortcut pack size");
+          const int sps = bnn_hip_pack_shortcut_weight_i8(pick_ptr<uint32_t>(), d.O, sc_c, pick_ptr<char>(), stream);
+          if (!status_ok(sps)) broken("int8 shortcut pack status");
+          digest = (digest ^ (uint64_t)(uint32_t)sf ^ ((uint64_t)(uint32_t)sps << 32) ^ (uint64_t)fsup) * 0x100000001B3ull;
         }
         st = bnn_hip_blinear(pick_int(), pick_int(), pick_int(), pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<uint32_t>(),
                              pick_ptr<uint32_t>(), pick_int(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(),
