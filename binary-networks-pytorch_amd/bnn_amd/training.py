@@ -292,9 +292,10 @@ def _batch_stat_bn(bn) -> bool:
 
 def bn_act_applies(bn: nn.Module, act, x: torch.Tensor) -> bool:
     """The fused op stands in for ``act(bn(x) [+ identity])`` iff: ``_batch_stat_bn``, ``act`` None or a stock
-    ``nn.ReLU``, fp32 NCHW on a HIP device, autograd recording, and no forward hooks on either module."""
+    ``nn.ReLU``, fp32 NCHW on a HIP device with more than one value per channel (with one, the module raises "Expected
+    more than 1 value per channel": it must get to), autograd recording, and no forward hooks on either module."""
     return (FUSED_BN and ENABLED and _batch_stat_bn(bn) and (act is None or type(act) is nn.ReLU)
-            and _f32_on_one_device(x) and x.dim() == 4 and torch.is_grad_enabled()
+            and _f32_on_one_device(x) and x.dim() == 4 and x.numel() > x.shape[1] and torch.is_grad_enabled()
             and (bn.weight is None or bn.weight.dtype == torch.float32) and _no_hooks(bn, act, backward=False))
 
 
