@@ -7,8 +7,19 @@ A layer takes the HIP path when ALL of the following hold (otherwise the torch c
   ``tanh``, whose value is also ``sign(x)``) / ``XNORWeightBinarizer`` / (``Identity`` or a
   per-output-channel ``BasicScaleBinarizer``)      (reference: ``examples/cifar10.py:65-69``,
   ``test/test_layers.py:17-21``)
-* input and weight are both float32 or both float16 (a ``.half()`` model: bit planes straight from the fp16
-  tensor, fp32 arithmetic inside, output rounded to fp16 once) on the same HIP device
+* on the same HIP device, input and weight are
+  - both float32, or
+  - both float16 (a ``.half()`` model: bit planes straight from the fp16 tensor, fp32 arithmetic inside, output rounded
+    to fp16 once), or — inference only, ``lowp_dtype`` —
+  - both bfloat16 (a ``.bfloat16()`` model), or
+  - a 16-bit input of the autocast dtype with a float32 weight under ``torch.autocast("cuda", dtype=float16 | bfloat16)``
+    (what every binary layer behind the first one sees there).  These two return a tensor of that 16-bit dtype ``D`` with
+    the reference's own rounding points: the weight is ``weight_pre_process(weight).to(D)`` (its sign bits, its zeros and
+    ``alpha[o] = max |What_D[o]|``: ``lowp_packed_weight``), the bias is rounded to ``D``, the result
+    ``fmaf(alpha, dot, bias)`` is rounded to ``D`` and, with a ``BasicScaleBinarizer``, multiplied and rounded again
+    (``hipops.round_lowp``; the one-launch kernel stores the 16 bits itself: ``LOWP_STORE_DECLINED_SHAPES``).  A float32
+    input under autocast still returns float32; a 16-bit input with a float32 weight and no autocast reaches the
+    composition; the fused executors and the real-weight path keep declining 16 bits
 * autograd is not recording (``torch.no_grad()`` / inference); when it IS recording, ``Conv2d`` takes the
   training variant (HIP forward, binary-aware HIP gradient kernels or the library's fp32 backward with the
   straight-through estimator: ``bnn_amd/training.py``); ``Linear`` takes its own training variant under
@@ -125,6 +136,22 @@ def fconv_admitted(C: int, H: int, W: int, stride: int) -> bool:
     return (C, H, W, stride) not in FCONV_DECLINED_SHAPES
 
 
+# The 16-bit store inside the one-launch layer kernel (``hipops.bconv2d_direct(out_dtype=D)``: 2 bytes of traffic per output
+# element) against the same kernel's fp32 store followed by ``hipops.round_lowp`` (10 bytes), batch 256 on MI355X
+# (tools/bench_lowp.py -> profiles/lowp_bench.jsonl).  The admission rule, in one place: a shape (D, C, O, H, W, kernel,
+# stride) where the 16-bit store measured SLOWER is listed here with its (fp32 store + round_lowp us, 16-bit store us) and
+# takes the former: the same bits.
+LOWP_STORE_DECLINED_SHAPES = {
+    # none: fp32 store + round_lowp -> 16-bit store, us at batch 256, bf16 / fp16: 187.6 -> 88.4 / 185.8 -> 87.0 (64, 64, 56, 56,
+    # 3, 1), 130.2 -> 78.5 / 130.4 -> 81.2 (128, 128, 28, 28, 3, 1), 112.9 -> 84.5 / 111.4 -> 82.4 (256, 256, 14, 14, 3, 1),
+    # 102.1 -> 75.2 / 101.4 -> 75.8 (512, 512, 7, 7, 3, 1), 110.5 -> 60.5 / 108.3 -> 60.1 (64, 128, 56, 56, 3, 2)
+}
+
+
+def lowp_store_admitted(D: torch.dtype, C: int, O: int, H: int, W: int, kernel: int, stride: int) -> bool:
+    return (D, C, O, H, W, kernel, stride) not in LOWP_STORE_DECLINED_SHAPES
+
+
 def stats() -> dict:
     """Counters of HIP-path invocations (tests use them to prove which path ran)."""
     with _stats_lock:
@@ -222,11 +249,30 @@ def _recognise_real(layer: nn.Module, out_channels: int) -> Optional[RealPlan]:
     return RealPlan(scale, ste=basic)
 
 
+_LOWP = (torch.float16, torch.bfloat16)
+
+
+def lowp_dtype(layer: nn.Module, x: torch.Tensor) -> Optional[torch.dtype]:
+    """The 16-bit dtype ``D`` a layer computes in on the HIP path, or ``None``: the two admission cases beyond fp32 and
+    ``.half()`` (module docstring).  (1) a bf16 model: input and weight both bfloat16 — under autocast only if its dtype is
+    bfloat16 too, where the casts are no-ops; (2) autocast: a float32 weight and an input of the autocast dtype, float16 or
+    bfloat16.  Looks at devices and dtypes only; ``_eligible`` adds "autograd is not recording"."""
+    w = layer.weight
+    if not (x.is_cuda and w.is_cuda and x.device == w.device) or x.dtype not in _LOWP:
+        return None
+    cast = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else None
+    if w.dtype == torch.bfloat16:
+        return torch.bfloat16 if x.dtype == torch.bfloat16 and cast in (None, torch.bfloat16) else None
+    if w.dtype == torch.float32:
+        return x.dtype if cast == x.dtype else None
+    return None
+
+
 def _eligible(layer: nn.Module, x: torch.Tensor, plan: Plan) -> bool:
     w = layer.weight
     if not (x.is_cuda and w.is_cuda and x.device == w.device):
         return False
-    if x.dtype != w.dtype or x.dtype not in (torch.float32, torch.float16):
+    if (x.dtype != w.dtype or x.dtype not in (torch.float32, torch.float16)) and lowp_dtype(layer, x) is None:
         return False
     if torch.is_grad_enabled():
         needs = x.requires_grad or w.requires_grad
@@ -473,6 +519,7 @@ def invalidate(module: nn.Module, executors: bool = True) -> int:
     for m in module.modules():
         if m.__dict__.pop("_bnn_packed", None) is not None:
             n += 1
+        n += len(m.__dict__.pop(LOWP_KEY, ()))
         if m.__dict__.pop(REAL_KEY, None) is not None:
             n += 1
         m.__dict__.pop("_bnn_packed_replicas", None)
@@ -485,6 +532,43 @@ def invalidate(module: nn.Module, executors: bool = True) -> int:
     return n
 
 
+# ``layer.__dict__`` key of the packs of the 16-bit cases: {(D, weight dtype): (key, pack, bias)} (``lowp_packed_weight``)
+LOWP_KEY = "_bnn_packed_lowp"
+
+
+def lowp_packed_weight(layer, plan: Plan, D: torch.dtype):
+    """``(pack, bias)`` of a layer that computes in the 16-bit dtype ``D`` (``lowp_dtype``), cached beside the fp32 pack
+    (one entry per ``D`` and case, so a layer called plainly, under autocast and plainly again keeps all its packs):
+
+    * ``What_D = weight_pre_process(weight).to(D)``, by the layer's own hook, in torch on the device — what the reference
+      hands to the convolution: under autocast the fp32 ``alpha * sign(w)`` rounded by the cast, in a 16-bit model the
+      hook's own ``D`` arithmetic.  The pack holds its sign bits and zero mask (``pack_weight`` of the widened tensor
+      without centring) and ``alpha[o] = max |What_D[o]|`` — exact: every non-zero entry of row ``o`` is +-alpha;
+    * the bias rounded to ``D`` as autocast's cast does (a 16-bit model's already is), widened for the fp32 epilogue.
+
+    Keyed like ``packed_weight`` (storage pointer, version, device, shape, recipe, groups) plus the bias's pointer and
+    version; never trusted under ``BNN_AMD_STRICT_WEIGHTS=1``; dropped by ``invalidate()``.  A ``DataParallel`` replica
+    (new storage every forward) packs on every call."""
+    w, b = layer.weight, layer.bias
+    groups = getattr(layer, "groups", 1)
+    case = (D, w.dtype)
+    key = (w.data_ptr(), w._version, str(w.device), tuple(w.shape), plan.center, plan.compute_alpha, groups,
+           None if b is None else (b.data_ptr(), b._version))
+    cache = layer.__dict__.setdefault(LOWP_KEY, {})
+    hit = cache.get(case)
+    if hit is not None and hit[0] == key and not strict_weights():
+        return hit[1], hit[2]
+    with torch.no_grad(), torch.autocast("cuda", enabled=False):
+        what = layer.weight_pre_process(w).detach().to(D)
+        wf = what.float()
+        pw = hipops.pack_weight_grouped(wf, groups, center=False) if groups != 1 else hipops.pack_weight(wf, center=False)
+        pw.alpha[:wf.shape[0]] = wf.abs().flatten(1).amax(1)
+        bias = None if b is None else b.detach().to(D).float()
+    cache[case] = (key, pw, bias)
+    _bump("weight_packs")
+    return pw, bias
+
+
 def _f32(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     """Per-channel constants of a ``.half()`` model, widened (exactly) for the fp32 epilogue."""
     return t if t is None or t.dtype == torch.float32 else t.detach().float()
@@ -493,6 +577,9 @@ def _f32(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
 def conv2d(layer, x: torch.Tensor, plan: Plan) -> torch.Tensor:
     """HIP evaluation of ``bnn.layers.Conv2d.forward`` (bnn/layers/conv.py:90-97)."""
     native.require()
+    D = lowp_dtype(layer, x)
+    if D is not None:
+        return _conv2d_lowp(layer, x, plan, D)
     pw = packed_weight(layer, plan)
     if layer.groups != 1:   # grouped / depthwise: the sign planes, then the grouped kernel (csrc/bconv_grouped.hip)
         out = hipops.bconv2d_grouped(hipops.pack_act(x), pw, _f32(layer.bias), _f32(plan.scale), layer.stride,
@@ -504,6 +591,25 @@ def conv2d(layer, x: torch.Tensor, plan: Plan) -> torch.Tensor:
                                 layer.dilation)
     _bump("conv2d")
     return out.to(x.dtype)
+
+
+def _conv2d_lowp(layer, x: torch.Tensor, plan: Plan, D: torch.dtype) -> torch.Tensor:
+    """``conv2d`` of a layer that computes in the 16-bit dtype ``D``: the same launches on ``lowp_packed_weight``, the
+    result rounded where the reference rounds — by the one-launch kernel's own 16-bit store where it was measured not
+    slower (``lowp_store_admitted``), else and on the grouped kernel by ``hipops.round_lowp`` on the fp32 result."""
+    pw, bias = lowp_packed_weight(layer, plan, D)
+    scale = _f32(plan.scale)
+    geometry = (layer.stride, layer.padding, layer.dilation)
+    if layer.groups != 1:
+        out = hipops.round_lowp(hipops.bconv2d_grouped(hipops.pack_act(x), pw, bias, None, *geometry), scale, D)
+    elif (layer.kernel_size[0] == layer.kernel_size[1] and layer.stride[0] == layer.stride[1] and
+          not lowp_store_admitted(D, x.shape[1], layer.out_channels, x.shape[2], x.shape[3], layer.kernel_size[0],
+                                  layer.stride[0])):
+        out = hipops.round_lowp(hipops.bconv2d_direct(x, pw, bias, None, *geometry), scale, D)
+    else:
+        out = hipops.bconv2d_direct(x, pw, bias, scale, *geometry, out_dtype=D)
+    _bump("conv2d")
+    return out
 
 
 def conv2d_train(layer, x: torch.Tensor, plan: Plan) -> torch.Tensor:
@@ -576,6 +682,16 @@ def linear_real_train(layer, x: torch.Tensor, plan: RealPlan) -> torch.Tensor:
 def conv1d(layer, x: torch.Tensor, plan: Plan) -> torch.Tensor:
     """``Conv1d`` as an ``H == 1`` 2-D convolution (bnn/layers/conv.py:36-43)."""
     native.require()
+    D = lowp_dtype(layer, x)
+    if D is not None:   # a 16-bit layer: the fp32 launches on its own pack, then the reference's two roundings
+        pw, bias = lowp_packed_weight(layer, plan, D)
+        geometry = ((1, layer.stride[0]), (0, layer.padding[0]), (1, layer.dilation[0]))
+        if layer.groups != 1:
+            out = hipops.bconv2d_grouped(hipops.pack_act(x.unsqueeze(2)), pw, bias, None, *geometry)
+        else:
+            out = hipops.bconv2d_direct(x.unsqueeze(2), pw, bias, None, *geometry)
+        _bump("conv1d")
+        return hipops.round_lowp(out.squeeze(2), _f32(plan.scale), D)
     pw = packed_weight(layer, plan)
     if layer.groups != 1:
         out = hipops.bconv2d_grouped(hipops.pack_act(x.unsqueeze(2)), pw, _f32(layer.bias), _f32(plan.scale),
@@ -592,6 +708,12 @@ def linear(layer, x: torch.Tensor, plan: Plan) -> torch.Tensor:
     """``Linear`` (bnn/layers/linear.py:22-27): the row-major XNOR GEMM kernel where it was measured not slower, else a
     1x1 convolution over 1x1 images (``hipops.linear``) — the same bits."""
     native.require()
+    D = lowp_dtype(layer, x)
+    if D is not None:   # a 16-bit layer: the fp32 launch on its own pack, then the reference's two roundings
+        pw, bias = lowp_packed_weight(layer, plan, D)
+        out = hipops.round_lowp(hipops.linear(x, pw, bias, None), _f32(plan.scale), D, channel_dim=-1)
+        _bump("linear")
+        return out
     pw = packed_weight(layer, plan)
     out = hipops.linear(x, pw, _f32(layer.bias), _f32(plan.scale))
     _bump("linear")

@@ -81,9 +81,41 @@ def _require_cuda_f32(t: torch.Tensor, what: str) -> torch.Tensor:
     return t.contiguous()
 
 
+# The 16-bit formats the kernels read (C-ABI input type) and the one-launch layer stores (descriptor flag)
+_LOWP_DTYPE = {torch.float16: native.DTYPE_F16, torch.bfloat16: native.DTYPE_BF16}
+_LOWP_OUT_FLAG = {torch.float16: native.FLAG_OUT_F16, torch.bfloat16: native.FLAG_OUT_BF16}
+
+
+def _act_dtype(x: torch.Tensor) -> int:
+    """``BNN_HIP_DTYPE_*`` of an activation that passed ``_require_cuda_act``."""
+    return _LOWP_DTYPE.get(x.dtype, native.DTYPE_F32)
+
+
+def _check_out_dtype(out_dtype) -> None:
+    if out_dtype is not None and out_dtype not in _LOWP_OUT_FLAG:
+        raise ValueError("out_dtype must be None, torch.float16 or torch.bfloat16")
+
+
+def round_lowp(out: torch.Tensor, post_scale: Optional[torch.Tensor], dtype: torch.dtype,
+               channel_dim: int = 1) -> torch.Tensor:
+    """The two rounding points of the reference layer on a 16-bit tensor, applied with torch to the fp32 result ``out`` of
+    a launch that ran WITHOUT its post-scale: ``r = out.to(dtype)`` (round to nearest even, fp16 overflow -> +-inf), then
+    — ``BasicScaleBinarizer``'s in-place ``x.mul_(alpha)`` — ``r = dtype(float(r) * post_scale[o])``, channels on
+    dimension ``channel_dim``.  What the in-kernel store of ``bconv2d_direct(out_dtype=...)`` computes, for the routes
+    that have no such store."""
+    _check_out_dtype(dtype)
+    r = out.to(dtype)
+    if post_scale is not None:
+        shape = [1] * r.dim()
+        shape[channel_dim] = -1
+        r.mul_(post_scale.detach().float().reshape(shape))
+    return r
+
+
 def _require_cuda_act(x: torch.Tensor) -> torch.Tensor:
-    """An activation the packing kernels read: fp16 stays as it is, everything else must be fp32, on a HIP device."""
-    if x.dtype != torch.float16:
+    """An activation the packing kernels read: fp16 / bf16 stay as they are, everything else must be fp32, on a HIP
+    device."""
+    if x.dtype not in _LOWP_DTYPE:
         return _require_cuda_f32(x, "activation")
     if not x.is_cuda:
         raise native.NativeError(f"bnn_amd: activation must live on a HIP device, got {x.device}")
@@ -144,7 +176,7 @@ def empty_packed(N: int, C: int, H: int, W: int, device) -> PackedAct:
 
 
 def pack_act(x: torch.Tensor) -> PackedAct:
-    """``BasicInputBinarizer`` on device: fp32 (or fp16) NCHW -> bit planes (bnn/ops.py:151-152)."""
+    """``BasicInputBinarizer`` on device: fp32 (or fp16 / bf16) NCHW -> bit planes (bnn/ops.py:151-152)."""
     x = _require_cuda_act(x)
     if x.dim() != 4:
         raise native.NativeError(f"bnn_amd: pack_act expects NCHW, got shape {tuple(x.shape)}")
@@ -154,7 +186,8 @@ def pack_act(x: torch.Tensor) -> PackedAct:
         return empty_packed(0, C, H, W, x.device)
     with torch.cuda.device(x.device):
         a = empty_packed(N, C, H, W, x.device)
-        fn = lib.bnn_hip_pack_act_f16 if x.dtype == torch.float16 else lib.bnn_hip_pack_act_f32
+        fn = {native.DTYPE_F32: lib.bnn_hip_pack_act_f32, native.DTYPE_F16: lib.bnn_hip_pack_act_f16,
+              native.DTYPE_BF16: lib.bnn_hip_pack_act_bf16}[_act_dtype(x)]
         native.check(fn(x.data_ptr(), N, C, H, W, a.P.data_ptr(), a.M.data_ptr(), _stream(x.device)),
                      "bnn_hip_pack_act")
     return a
@@ -1041,15 +1074,20 @@ def _prefers_two_launches(d) -> bool:
 def bconv2d_direct(x: torch.Tensor, w: PackedWeight, bias: Optional[torch.Tensor] = None,
                    post_scale: Optional[torch.Tensor] = None, stride=1, padding=0, dilation=1,
                    plan: Optional[native.FlyPlan] = None, force_generic: bool = False,
-                   route: Optional[str] = None) -> torch.Tensor:
-    """``Conv2d.forward`` of the reference (bnn/layers/conv.py:90-97) in ONE launch: fp32 or fp16 NCHW activations in,
-    fp32 NCHW out, ``sign(x)`` computed on the fly inside the convolution kernel (csrc/bconv_fly.hip) — no packed
+                   route: Optional[str] = None, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """``Conv2d.forward`` of the reference (bnn/layers/conv.py:90-97) in ONE launch: fp32, fp16 or bf16 NCHW activations
+    in, fp32 NCHW out, ``sign(x)`` computed on the fly inside the convolution kernel (csrc/bconv_fly.hip) — no packed
     copy of the activations in HBM.  Geometries the one-launch kernel does not cover (an output row with its halo
     larger than a CU's LDS) take ``pack_act`` + ``bconv2d``; the results are bit-identical either way.
+
+    ``out_dtype`` (``torch.float16`` / ``torch.bfloat16``): the layer of a 16-bit network — a tensor of that type comes
+    back, rounded where the reference rounds (``round_lowp``): by the kernel's own 16-bit store on the one-launch route
+    (BNN_HIP_FLAG_OUT_*), by ``round_lowp`` on the fp32 result of the others.
 
     ``route``: ``None`` picks per shape (``_prefers_two_launches``); ``"direct"`` / ``"packed"`` force one (tools)."""
     if route not in (None, "direct", "packed"):
         raise ValueError("route must be None, 'direct' or 'packed'")
+    _check_out_dtype(out_dtype)
     _ungrouped(w, "bconv2d_direct")
     x = _require_cuda_act(x)
     if x.dim() != 4:
@@ -1060,22 +1098,30 @@ def bconv2d_direct(x: torch.Tensor, w: PackedWeight, bias: Optional[torch.Tensor
     dev = x.device
     bias = _per_channel(bias, d.O, "bias")
     post_scale = _per_channel(post_scale, d.O, "post_scale")
+
+    def two_launches(xs: torch.Tensor) -> torch.Tensor:
+        if out_dtype is None:
+            return bconv2d(pack_act(xs), w, bias, post_scale, stride, padding, dilation, force_generic=force_generic)
+        return round_lowp(bconv2d(pack_act(xs), w, bias, None, stride, padding, dilation, force_generic=force_generic),
+                          post_scale, out_dtype)
+
     if d.N and plan is None and (route == "packed" or (route is None and _prefers_two_launches(d))):
-        return bconv2d(pack_act(x), w, bias, post_scale, stride, padding, dilation, force_generic=force_generic)
+        return two_launches(x)
+    if out_dtype is not None:
+        d.flags |= _LOWP_OUT_FLAG[out_dtype]
     with torch.cuda.device(dev):
-        out = torch.empty((d.N, d.O, ho, wo), dtype=torch.float32, device=dev)
+        out = torch.empty((d.N, d.O, ho, wo), dtype=out_dtype or torch.float32, device=dev)
         if d.N == 0:
             return out
-        step = _launch_images(d.N, d.C, d.O, d.O, d.C * d.H * d.W, ho * wo)   # (the input is fp32 / fp16 elements here)
-        dtype = native.DTYPE_F16 if x.dtype == torch.float16 else native.DTYPE_F32
+        step = _launch_images(d.N, d.C, d.O, d.O, d.C * d.H * d.W, ho * wo)   # (the input is fp32 / 16-bit elements here)
+        dtype = _act_dtype(x)
         for n0, n1, dd in _desc_slices(d, step):
             st = lib.bnn_hip_bconv2d_direct(ctypes.byref(dd), x[n0:n1].data_ptr(), dtype, w.wbits.data_ptr(),
                                             w.wnz.data_ptr(), w.alpha.data_ptr(), _ptr(bias), _ptr(post_scale),
                                             out[n0:n1].data_ptr(), None if plan is None else ctypes.byref(plan),
                                             _stream(dev))
             if st == native.ERR_UNSUPPORTED and plan is None:   # the two-launch form of the same layer
-                out[n0:n1] = bconv2d(pack_act(x[n0:n1]), w, bias, post_scale, stride, padding, dilation,
-                                     force_generic=force_generic)
+                out[n0:n1] = two_launches(x[n0:n1])
                 continue
             native.check(st, "bnn_hip_bconv2d_direct")
     return out
@@ -1957,7 +2003,7 @@ def _linear_planes(M: int, F: int, device) -> "SavedAct":
 def blinear_direct(x: torch.Tensor, w: PackedWeight, bias: Optional[torch.Tensor] = None,
                    post_scale: Optional[torch.Tensor] = None, want_planes: bool = False, lds_words: int = 0):
     """``Linear.forward`` of the reference (bnn/layers/linear.py:22-27) in ONE launch of the row-major kernel
-    (``bnn_hip_blinear_direct``): fp32 or fp16 ``[..., F]`` in, fp32 ``[..., O]`` out, ``sign(x)`` taken inside — the bits
+    (``bnn_hip_blinear_direct``): fp32, fp16 or bf16 ``[..., F]`` in, fp32 ``[..., O]`` out, ``sign(x)`` taken inside — the bits
     of ``bconv2d_direct`` on ``M`` images of 1 x 1 pixels.  ``want_planes``: returns ``(out, SavedAct)`` with the three bit
     planes of ``pack_act_ste`` (shape ``(M, F, 1, 1)``, ``M`` the flattened leading dimensions) from the same pass over
     ``x``.  ``lds_words``: the kernel's LDS pass over ``F`` in 32-bit words per row (0: its default; tests force it)."""
@@ -1975,7 +2021,7 @@ def blinear_direct(x: torch.Tensor, w: PackedWeight, bias: Optional[torch.Tensor
     with torch.cuda.device(dev):
         out = torch.empty((M, O), dtype=torch.float32, device=dev)
         sv = _linear_planes(M, F, dev) if want_planes else None
-        dtype = native.DTYPE_F16 if x.dtype == torch.float16 else native.DTYPE_F32
+        dtype = _act_dtype(x)
         step = _linear_rows(M, F, O)
         for m0 in range(0, M, step):
             m1 = min(M, m0 + step)

@@ -21,6 +21,8 @@ FLAG_WEIGHT_ZEROS = 2
 FLAG_WEIGHTS_SGPR = 4
 FLAG_ACT_NONNEG = 32
 FLAG_THROUGHPUT = 64
+FLAG_OUT_F16 = 256                      # bnn_hip_bconv2d_direct only: the kernel rounds and stores 16-bit floats
+FLAG_OUT_BF16 = 512
 HBLOCK_CHANNEL_LANES = 128
 STEM_EXACT_FP32 = 1
 STEM_FP16 = 4
@@ -30,6 +32,7 @@ STEM_S2X2_MAX_GROUP_CHANNELS = 32       # BNN_HIP_STEM_S2X2_MAX_GROUP_CHANNELS
 GCONV3X3S2_MAX_GROUP_CHANNELS = 40      # BNN_HIP_GCONV3X3S2_MAX_GROUP_CHANNELS
 DTYPE_F32 = 0
 DTYPE_F16 = 1
+DTYPE_BF16 = 2
 
 # status codes of include/bnn_hip.h that Python code compares against (anything else just goes through check())
 OK = 0
@@ -169,6 +172,7 @@ _PROTOTYPES = {
     "bnn_hip_grouped_weight_layout": (_i, [_i, _i, _i, _i, _i, _wlayout_p]),
     "bnn_hip_pack_act_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "bnn_hip_pack_act_f16": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "bnn_hip_pack_act_bf16": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "bnn_hip_pack_act_ste_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "bnn_hip_bn_act_pack_ste_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bnn_hip_bn_act_pack_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),

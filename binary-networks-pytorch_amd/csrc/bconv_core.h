@@ -46,6 +46,9 @@ enum : int {
   EF_PACK_PRE = 1024,   // binarise the value before a late residual
   EF_PACK_AFF = 2048,   // next layer's BatchNorm applied to the value that is binarised
   EF_PACK_RELU = 4096,  // planes of sign(relu(p)): M = 0
+  // the one-launch layer (bconv_fly.hip, epilogue<.., LOWP>): `out` holds 16-bit floats, rounded in the epilogue
+  EF_OUT_F16 = 8192,
+  EF_OUT_BF16 = 16384,
 };
 
 struct EpiArgs {
@@ -372,7 +375,40 @@ __device__ __forceinline__ constexpr int ep_flags(int ep, int runtime) {
 // -+(non-zero inputs of the lane): two packed instructions per channel PAIR, all operands small integers, so exact —
 // instead of add-shift, subtract and v_cvt_f32_i32 per channel.
 constexpr uint32_t kCountSeed = 0x4B000000u;  // 2^23 as fp32
-template <int NACC, int EP, bool FULL = false, bool RAWF = false>
+
+// The 16-bit store of the one-launch layer (EF_OUT_F16 / EF_OUT_BF16): the two rounding points of the reference on a 16-bit
+// tensor.  v -> r = D(v), round to nearest even (v_cvt_f16_f32: overflow gives +-inf; v_cvt_pk_bf16_f32), what
+// Tensor.to(D) does; with a post-scale r = D(float(r) * scale): the reference's in-place `x.mul_(alpha)` on the 16-bit
+// tensor multiplies the widened value in fp32 and rounds again.  One 2-byte store per lane (the element index of a band's
+// first pixel may be odd, so neighbouring lanes are not paired into dwords).
+template <bool BF>
+__device__ __forceinline__ uint16_t round16(float v) {
+  if constexpr (BF) return __builtin_bit_cast(uint16_t, static_cast<__bf16>(v));
+  else return __builtin_bit_cast(uint16_t, static_cast<_Float16>(v));
+}
+template <bool BF>
+__device__ __forceinline__ float widen16(uint16_t r) {
+  if constexpr (BF) return __builtin_bit_cast(float, (uint32_t)r << 16);
+  else return static_cast<float>(__builtin_bit_cast(_Float16, r));
+}
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ void buf_st16(BufRsrc r, unsigned lane_boff, unsigned chan_boff, uint16_t v) {
+  __builtin_amdgcn_raw_buffer_store_b16((short)v, r, (int)lane_boff, (int)chan_boff, 0);
+}
+#else
+__device__ __forceinline__ void buf_st16(BufRsrc, unsigned, unsigned, uint16_t) {}
+#endif
+template <bool BF>
+__device__ __forceinline__ void store16(void* out, unsigned lane_boff, unsigned chan_boff, float v, bool has_scale,
+                                        float scale) {
+  uint16_t r = round16<BF>(v);
+  if (has_scale) r = round16<BF>(widen16<BF>(r) * scale);
+  buf_st16(make_rsrc(out), lane_boff, chan_boff, r);
+}
+
+// LOWP (bconv_fly.hip only): the plain profile honours EF_OUT_F16 / EF_OUT_BF16; without it the bits are never looked at
+// and the kernels of bconv.hip keep their instruction streams.
+template <int NACC, int EP, bool FULL = false, bool RAWF = false, bool LOWP = false>
 __device__ __forceinline__ void epilogue(const Geo& g, const Pix& px, int o0,
                                          const int (&dot)[NACC], const float (&resv)[NACC],
                                          const EpiArgs& e, uint32_t& pbits, uint32_t& mbits,
@@ -407,6 +443,38 @@ __device__ __forceinline__ void epilogue(const Geo& g, const Pix& px, int o0,
   float* outf = static_cast<float*>(e.out);
   if (!FUSED) {  // alpha, optional bias / post-scale, fp32 store: the drop-in Conv2d.forward
     const bool hb = (f & EF_BIAS) != 0, hs = (f & EF_SCALE) != 0;
+    if constexpr (LOWP) {
+      if (f & (EF_OUT_F16 | EF_OUT_BF16)) {  // (wave-uniform) the same v, rounded and stored as 16 bits; byte offsets halve
+        const unsigned lane_off2 = px.out_base * 2u;
+        auto lowp = [&](auto bf) __attribute__((always_inline)) {
+          constexpr bool BF = decltype(bf)::value;
+          if constexpr (FULL && NACC % 2 == 0) {
+#pragma unroll
+            for (int j = 0; j < NACC; j += 2) {
+              const int o = o0 + j;
+              const f2 y = __builtin_elementwise_fma(f2{e.alpha[o], e.alpha[o + 1]}, dot_pair(j),
+                                                     hb ? f2{e.bias[o], e.bias[o + 1]} : f2{0.0f, 0.0f});
+              store16<BF>(e.out, lane_off2, (unsigned)(o + g.c_off) * (unsigned)hw * 2u, y.x, hs, hs ? e.scale[o] : 1.0f);
+              store16<BF>(e.out, lane_off2, (unsigned)(o + 1 + g.c_off) * (unsigned)hw * 2u, y.y, hs,
+                          hs ? e.scale[o + 1] : 1.0f);
+            }
+          } else {
+#pragma unroll
+            for (int j = 0; j < NACC; ++j) {
+              const int o = o0 + j;
+              if (full || o < g.O) {
+                const float y = fmaf(e.alpha[o], (float)dot[j], hb ? e.bias[o] : 0.0f);
+                const float sc = hs ? e.scale[o] : 1.0f;
+                if (live) store16<BF>(e.out, lane_off2, (unsigned)(o + g.c_off) * (unsigned)hw * 2u, y, hs, sc);
+              }
+            }
+          }
+        };
+        if (f & EF_OUT_BF16) lowp(std::true_type{});
+        else lowp(std::false_type{});
+        return;
+      }
+    }
     if constexpr (FULL && NACC % 2 == 0) {  // two channels per v_pk_fma_f32 (see the fused profiles below)
 #pragma unroll
       for (int j = 0; j < NACC; j += 2) {
@@ -1062,6 +1130,8 @@ inline Geo make_geo(const ConvP& p) {
   if (p.res && (p.eflags & BNN_HIP_EPI_RES_AFTER_ACT) && (p.eflags & BNN_HIP_EPI_PACK_BEFORE_RES)) f |= EF_PACK_PRE;
   if (p.pack_a && p.pack_b) f |= EF_PACK_AFF;
   if (p.eflags & BNN_HIP_EPI_PACK_RELU) f |= EF_PACK_RELU;
+  if (p.out16 == BNN_HIP_DTYPE_F16) f |= EF_OUT_F16;
+  if (p.out16 == BNN_HIP_DTYPE_BF16) f |= EF_OUT_BF16;
   g.ds_cw = p.ds_P ? 2 * ((p.ds_C + 63) / 64) : 0;
   g.ds_h = p.ds_P ? p.ds_inH : 0;
   g.ds_w = p.ds_P ? p.ds_inW : 0;

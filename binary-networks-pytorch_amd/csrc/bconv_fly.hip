@@ -1,5 +1,6 @@
-// bconv_fly.hip — the binary convolution LAYER in one launch: fp32 (or fp16) NCHW in -> fp32 NCHW out, with the
-// activations binarised ON THE FLY into LDS.  No packed copy of the input ever reaches HBM.
+// bconv_fly.hip — the binary convolution LAYER in one launch: fp32 (or fp16 / bf16) NCHW in -> fp32 NCHW out (or, for a
+// 16-bit network, fp16 / bf16 out, rounded in the epilogue), with the activations binarised ON THE FLY into LDS.  No packed
+// copy of the input ever reaches HBM.
 //
 // Replaces bnn/layers/conv.py:90-97 (Conv2d.forward) end to end:
 //     sign(x)                         bnn/ops.py:63-66,151-152   -> pack_item(): fp32 -> two bit planes in LDS
@@ -44,7 +45,7 @@ namespace bnn {
 
 struct FlyGeo {
   int C, HW;             // input channels, H * W
-  int in_half;           // input element type: 0 = fp32, 1 = fp16
+  int in_dtype;          // input element type: BNN_HIP_DTYPE_F32 / _F16 / _BF16
   unsigned x_bytes;      // range of the input descriptor
   int nwords;            // 32-channel words per pixel that hold real channels: ceil(C / 32)
   int wpi, gpi;          // PACK items: words per item (min(4, cwc)), items per input pixel group
@@ -253,30 +254,31 @@ __device__ __forceinline__ FlyCtx make_ctx(const FlyGeo& f, const Band& B, unsig
 //   fp32: s = sign bits, z = "sign(x) != 0" bits (shift_in_f32: three VALU instructions per element), P = z & ~s,
 //         M = z & s.  -0.0 and NaN have z = 0, denormals z = 1: the planes of pack_act_kernel bit for bit.
 //   fp16: the class test of the exactly widened value (what pack_act_kernel<__half> does).
+//   bf16: a 16-bit load, a shift left by 16 (the fp32 word of the same value), then the fp32 form.
 // A word at the channel tail re-reads channel C-1 for its missing channels (valid memory, no branches); the caller
 // clears their bits.
-template <bool HALF>
+template <int DT>
 __device__ __forceinline__ void pack_word(BufRsrc rx, unsigned voff, int c0, int C, unsigned chan_bytes,
                                           uint32_t& P, uint32_t& M) {
   uint32_t v[32];
 #pragma unroll
   for (int b = 0; b < 32; ++b) {
     const unsigned so = (unsigned)min(c0 + b, C - 1) * chan_bytes;
-    v[b] = HALF ? buf_ld_u16s(rx, voff, so) : buf_ld_u32s(rx, voff, so);
+    v[b] = DT != BNN_HIP_DTYPE_F32 ? buf_ld_u16s(rx, voff, so) : buf_ld_u32s(rx, voff, so);
   }
   uint32_t s = 0u, z = 0u;
 #pragma unroll
   for (int b = 31; b >= 0; --b) {
-    if constexpr (HALF) {
+    if constexpr (DT == BNN_HIP_DTYPE_F16) {
       const float u = __half2float(__ushort_as_half((unsigned short)v[b]));
       s = shift_in(s, is_pos(u));
       z = shift_in(z, is_neg(u));
     } else {
-      shift_in_f32(s, z, v[b], (uint32_t)kClassNonzero);
+      shift_in_f32(s, z, DT == BNN_HIP_DTYPE_BF16 ? v[b] << 16 : v[b], (uint32_t)kClassNonzero);
     }
   }
-  P = HALF ? s : (z & ~s);
-  M = HALF ? z : (z & s);
+  P = DT == BNN_HIP_DTYPE_F16 ? s : (z & ~s);
+  M = DT == BNN_HIP_DTYPE_F16 ? z : (z & s);
 }
 
 // Pack the next item if one is left (synchronously); false when all items have been handed out.
@@ -299,7 +301,7 @@ __device__ __forceinline__ bool pack_item(const void* __restrict__ x, const Geo&
   }
   const int rowl = (int)fast_div((uint32_t)r, f.m_W, f.s_W);
   const int ix = r - rowl * g.Wd;
-  const unsigned esz = f.in_half ? 2u : 4u;
+  const unsigned esz = f.in_dtype != BNN_HIP_DTYPE_F32 ? 2u : 4u;
 #ifdef BNN_FLY_EXP_SAMEIMG  // experiment: every band reads image 0 (the activations come out of L2 / MALL)
   const unsigned elem = (unsigned)(B.iy_lo * g.Wd + r);
 #else
@@ -318,8 +320,9 @@ __device__ __forceinline__ bool pack_item(const void* __restrict__ x, const Geo&
     const int nch = f.C - (w0 + k) * 32;
     if (nch <= 0) break;  // words past the last channel stay zero
     uint32_t Pw, Mw;
-    if (f.in_half) pack_word<true>(rx, voff, (w0 + k) * 32, f.C, (unsigned)f.HW * 2u, Pw, Mw);
-    else pack_word<false>(rx, voff, (w0 + k) * 32, f.C, (unsigned)f.HW * 4u, Pw, Mw);
+    if (f.in_dtype == BNN_HIP_DTYPE_F16) pack_word<BNN_HIP_DTYPE_F16>(rx, voff, (w0 + k) * 32, f.C, (unsigned)f.HW * 2u, Pw, Mw);
+    else if (f.in_dtype == BNN_HIP_DTYPE_BF16) pack_word<BNN_HIP_DTYPE_BF16>(rx, voff, (w0 + k) * 32, f.C, (unsigned)f.HW * 2u, Pw, Mw);
+    else pack_word<BNN_HIP_DTYPE_F32>(rx, voff, (w0 + k) * 32, f.C, (unsigned)f.HW * 4u, Pw, Mw);
     const uint32_t keep = nch >= 32 ? 0xFFFFFFFFu : ((1u << nch) - 1u);
     Pw &= keep;
     Mw &= keep;
@@ -601,11 +604,11 @@ struct TiledUnit {
       };
       if (fullb) {
         if constexpr (SEEDED) {
-          epilogue<NACC, EP_PLAIN, true, true>(g, px, o0, acc, resv, epi, pbits, mbits, 0, NN ? 2.0f : -2.0f,
+          epilogue<NACC, EP_PLAIN, true, true, true>(g, px, o0, acc, resv, epi, pbits, mbits, 0, NN ? 2.0f : -2.0f,
                                                NN ? -(float)nz : (float)nz);
         } else {
           to_dot();
-          epilogue<NACC, EP_PLAIN, true>(g, px, o0, acc, resv, epi, pbits, mbits);
+          epilogue<NACC, EP_PLAIN, true, false, true>(g, px, o0, acc, resv, epi, pbits, mbits);
         }
       } else {
         if constexpr (SEEDED) {
@@ -613,7 +616,7 @@ struct TiledUnit {
           for (int j = 0; j < NACC; ++j) acc[j] -= (int)kCountSeed;
         }
         to_dot();
-        epilogue<NACC, EP_PLAIN>(g, px, o0, acc, resv, epi, pbits, mbits);
+        epilogue<NACC, EP_PLAIN, false, false, true>(g, px, o0, acc, resv, epi, pbits, mbits);
       }
     }
   }
@@ -707,7 +710,7 @@ __global__ __launch_bounds__(1024) void bconv_fly_generic_kernel(BNN_FLY_PARAMS)
       float resv[kOCB];
 #pragma unroll
       for (int j = 0; j < kOCB; ++j) resv[j] = 0.0f;
-      epilogue<kOCB, EP_PLAIN>(g, px, ob * kOCB, dotv, resv, epi, pbits, mbits);
+      epilogue<kOCB, EP_PLAIN, false, false, true>(g, px, ob * kOCB, dotv, resv, epi, pbits, mbits);
     }
   });
 }
@@ -837,7 +840,7 @@ int launch_tiled(const ConvP& p, const void* x, const Geo& g, const FlyGeo& f, i
 
 // `plan` == nullptr: the default plan.  A caller's plan is validated (LDS budget, ranges) and its derived fields
 // are recomputed; only images_per_band / rows_per_band / waves / blocks_per_unit are taken from it.
-int launch_bconv_fly(const ConvP& p, const void* x, int x_half, int flags, const bnn_hip_fly_plan* user,
+int launch_bconv_fly(const ConvP& p, const void* x, int x_dtype, int flags, const bnn_hip_fly_plan* user,
                      hipStream_t s) {
   bnn_hip_fly_plan plan;
   int st = fly_default_plan(p, flags, &plan);
@@ -872,8 +875,8 @@ int launch_bconv_fly(const ConvP& p, const void* x, int x_half, int flags, const
   const int C = p.C;
   f.C = C;
   f.HW = p.H * p.Wd;
-  f.in_half = x_half ? 1 : 0;
-  f.x_bytes = (unsigned)((long long)p.N * C * p.H * p.Wd * (x_half ? 2 : 4));
+  f.in_dtype = x_dtype;
+  f.x_bytes = (unsigned)((long long)p.N * C * p.H * p.Wd * (x_dtype != BNN_HIP_DTYPE_F32 ? 2 : 4));
   f.nwords = (C + 31) / 32;
   f.cwc = p.cwc;
   f.wpi = std::min(4, p.cwc);

@@ -458,11 +458,17 @@ __global__ __launch_bounds__(256) void blinear_wgrad_kernel(const float* __restr
 }  // namespace blin
 
 // ------------------------------------------------------------------------------------------------- host side
-int launch_blinear_fwd(const void* x, int x_half, const uint32_t* wbits, const uint32_t* wnz, int weight_zeros,
+int launch_blinear_fwd(const void* x, int x_dtype, const uint32_t* wbits, const uint32_t* wnz, int weight_zeros,
                        const float* alpha, const float* bias, const float* scale, float* out, uint64_t* P, uint64_t* Mn,
                        uint64_t* T, int M, int F, int O, int lds_words, hipStream_t s) {
   const int cw32 = 2 * ((F + 63) / 64), cwc = choose_cwc(cw32, 1, 1), nchunk = cw32 / cwc;
-  if (x_half) {
+  if (x_dtype == BNN_HIP_DTYPE_BF16) {  // (float)__bf16 is the exact widening: the same planes
+    return weight_zeros ? blin::launch_fwd_c<__bf16, true>(cwc, x, wbits, wnz, alpha, bias, scale, out, P, Mn, T, M, F, O,
+                                                           nchunk, lds_words, s)
+                        : blin::launch_fwd_c<__bf16, false>(cwc, x, wbits, wnz, alpha, bias, scale, out, P, Mn, T, M, F, O,
+                                                            nchunk, lds_words, s);
+  }
+  if (x_dtype == BNN_HIP_DTYPE_F16) {
     return weight_zeros ? blin::launch_fwd_c<_Float16, true>(cwc, x, wbits, wnz, alpha, bias, scale, out, P, Mn, T, M, F, O,
                                                              nchunk, lds_words, s)
                         : blin::launch_fwd_c<_Float16, false>(cwc, x, wbits, wnz, alpha, bias, scale, out, P, Mn, T, M, F, O,

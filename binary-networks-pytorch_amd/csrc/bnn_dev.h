@@ -79,6 +79,7 @@ struct ConvP {
   int cw32, cwc, nchunk;
   int npix;  // N*Ho*Wo
   int C;     // input channels
+  int out16; // one-launch layer only: `out` holds 16-bit floats, rounded in the epilogue (0 = fp32, BNN_HIP_DTYPE_F16 / _BF16)
   // shortcut convolution folded into this one (bconv_core.h ShortcutArgs): 1x1 / stride 1 over ds_C channels at the
   // OUTPUT resolution, P plane only; null = none
   const uint32_t* ds_P;
@@ -116,6 +117,8 @@ int launch_pack_act(const float* x, int N, int C, int H, int W, uint64_t* P, uin
                     hipStream_t stream);
 int launch_pack_act_f16(const void* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M,
                         hipStream_t stream);
+int launch_pack_act_bf16(const void* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M,
+                         hipStream_t stream);
 int launch_bn_act_pack(const float* x, int N, int C, int H, int W, const float* bn_a, const float* bn_b,
                        int relu, uint64_t* P, uint64_t* M, hipStream_t stream);
 // the same from channels [c_off, c_off + C) of x [N, c_tot, H, W]: K plane sets [K][N][cw64][H][W] for K affines
@@ -239,15 +242,15 @@ int launch_grouped_dgrad(const GroupedGradP& q, const float* g, const float* wha
                          hipStream_t s);
 int launch_grouped_wgrad(const GroupedGradP& q, const float* g, const uint64_t* P, const uint64_t* M, float* part,
                          int splits, hipStream_t s);
-// bconv_fly.hip: the whole layer in one launch, activations (fp32, or fp16 when x_half) binarised on the fly into LDS.
+// bconv_fly.hip: the whole layer in one launch, activations (x_dtype: BNN_HIP_DTYPE_*) binarised on the fly into LDS.
 // p.P / p.M are unused; p.alpha / bias / scale / out as for launch_bconv.  `plan` may be null (default plan).
 bool fly_supported(const ConvP& p);
 int fly_default_plan(const ConvP& p, int flags, bnn_hip_fly_plan* plan);
-int launch_bconv_fly(const ConvP& p, const void* x, int x_half, int flags, const bnn_hip_fly_plan* plan, hipStream_t s);
-// blinear.hip: the fully-connected layer on a row-major [M, F] input.  Forward from the float input (fp16 when x_half) in one
+int launch_bconv_fly(const ConvP& p, const void* x, int x_dtype, int flags, const bnn_hip_fly_plan* plan, hipStream_t s);
+// blinear.hip: the fully-connected layer on a row-major [M, F] input.  Forward from the float input (x_dtype: BNN_HIP_DTYPE_*) in one
 // launch, P / Mn / T (all or none) receive the three bit planes [M][ceil(F/64)]; lds_words: 32-bit words per row of one LDS
 // pass over F (0 = default).  Gradients from the forward's weight pack and the planes (bf16 x 3 MFMA).
-int launch_blinear_fwd(const void* x, int x_half, const uint32_t* wbits, const uint32_t* wnz, int weight_zeros,
+int launch_blinear_fwd(const void* x, int x_dtype, const uint32_t* wbits, const uint32_t* wnz, int weight_zeros,
                        const float* alpha, const float* bias, const float* scale, float* out, uint64_t* P, uint64_t* Mn,
                        uint64_t* T, int M, int F, int O, int lds_words, hipStream_t s);
 int launch_blinear_dgrad(const float* g, const float* alpha, const uint32_t* wbits, const uint32_t* wnz, const uint64_t* T,

@@ -78,6 +78,9 @@ int check_desc(const bnn_hip_conv_desc* d, int* Ho, int* Wo) {
   if (d->stride_h <= 0 || d->stride_w <= 0 || d->pad_h < 0 || d->pad_w < 0 || d->dil_h <= 0 ||
       d->dil_w <= 0)
     return BNN_HIP_ERR_INVALID_ARG;
+  // the 16-bit output store exists in the one-launch layer alone (bnn_hip_bconv2d_direct takes the bits out of the
+  // descriptor it validates): every other entry point rejects them here
+  if (d->flags & (BNN_HIP_FLAG_OUT_F16 | BNN_HIP_FLAG_OUT_BF16)) return BNN_HIP_ERR_INVALID_ARG;
   const int ho = out_dim(d->H, d->KH, d->stride_h, d->pad_h, d->dil_h);
   const int wo = out_dim(d->W, d->KW, d->stride_w, d->pad_w, d->dil_w);
   if (ho <= 0 || wo <= 0) return BNN_HIP_ERR_INVALID_ARG;
@@ -407,6 +410,15 @@ int bnn_hip_pack_act_f16(const void* x, int N, int C, int H, int W, uint64_t* P,
   g_launches.fetch_add(1, std::memory_order_relaxed);
   BNN_RANGE();
   return bnn::launch_pack_act_f16(x, N, C, H, W, P, M, static_cast<hipStream_t>(stream));
+}
+
+int bnn_hip_pack_act_bf16(const void* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M,
+                          void* stream) {
+  const int st = check_pack(x, 2, N, C, H, W, P, M);
+  if (st != BNN_HIP_OK) return st;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_pack_act_bf16(x, N, C, H, W, P, M, static_cast<hipStream_t>(stream));
 }
 
 int bnn_hip_bn_act_pack_f32(const float* x, int N, int C, int H, int W, const float* bn_scale,
@@ -1196,17 +1208,18 @@ int bnn_hip_blinear_direct(int M, int F, int O, const void* x, int x_dtype, cons
                            int weight_zeros, const float* alpha, const float* bias, const float* post_scale, float* out,
                            uint64_t* P, uint64_t* Mn, uint64_t* T, int lds_words, void* stream) {
   if (!x || !wbits || !alpha || !out || lds_words < 0) return BNN_HIP_ERR_INVALID_ARG;
-  if (x_dtype != BNN_HIP_DTYPE_F32 && x_dtype != BNN_HIP_DTYPE_F16) return BNN_HIP_ERR_INVALID_ARG;
+  if (x_dtype != BNN_HIP_DTYPE_F32 && x_dtype != BNN_HIP_DTYPE_F16 && x_dtype != BNN_HIP_DTYPE_BF16)
+    return BNN_HIP_ERR_INVALID_ARG;
   if (weight_zeros && !wnz) return BNN_HIP_ERR_INVALID_ARG;
   if ((P == nullptr) != (Mn == nullptr) || (P == nullptr) != (T == nullptr)) return BNN_HIP_ERR_INVALID_ARG;
-  if (!aligned(x, x_dtype == BNN_HIP_DTYPE_F16 ? 2 : 4) || !aligned(wbits, 16) || !aligned(wnz, 16) || !aligned(alpha, 4) ||
+  if (!aligned(x, x_dtype == BNN_HIP_DTYPE_F32 ? 4 : 2) || !aligned(wbits, 16) || !aligned(wnz, 16) || !aligned(alpha, 4) ||
       !aligned(bias, 4) || !aligned(post_scale, 4) || !aligned(out, 4) || !aligned(P, 8) || !aligned(Mn, 8) || !aligned(T, 8))
     return BNN_HIP_ERR_INVALID_ARG;
   const int st = check_linear(M, F, O);
   if (st != BNN_HIP_OK) return st;
   g_launches.fetch_add(1, std::memory_order_relaxed);
   BNN_RANGE();
-  return bnn::launch_blinear_fwd(x, x_dtype == BNN_HIP_DTYPE_F16, wbits, wnz, weight_zeros != 0, alpha, bias, post_scale, out,
+  return bnn::launch_blinear_fwd(x, x_dtype, wbits, wnz, weight_zeros != 0, alpha, bias, post_scale, out,
                                  P, Mn, T, M, F, O, lds_words, static_cast<hipStream_t>(stream));
 }
 
@@ -1296,17 +1309,25 @@ int bnn_hip_bconv2d_direct(const bnn_hip_conv_desc* d, const void* x, int x_dtyp
                            const uint32_t* wnz, const float* alpha, const float* bias, const float* post_scale,
                            float* out, const bnn_hip_fly_plan* plan, void* stream) {
   if (!d || !x || !wbits || !alpha || !out) return BNN_HIP_ERR_INVALID_ARG;
-  if (x_dtype != BNN_HIP_DTYPE_F32 && x_dtype != BNN_HIP_DTYPE_F16) return BNN_HIP_ERR_INVALID_ARG;
-  if (!aligned(x, x_dtype == BNN_HIP_DTYPE_F16 ? 2 : 4) || !aligned(wbits, 16) || !aligned(out, 4))
+  if (x_dtype != BNN_HIP_DTYPE_F32 && x_dtype != BNN_HIP_DTYPE_F16 && x_dtype != BNN_HIP_DTYPE_BF16)
+    return BNN_HIP_ERR_INVALID_ARG;
+  // the output type travels in the descriptor's flags; the shared validator sees the descriptor without them
+  const int out_bits = d->flags & (BNN_HIP_FLAG_OUT_F16 | BNN_HIP_FLAG_OUT_BF16);
+  if (out_bits == (BNN_HIP_FLAG_OUT_F16 | BNN_HIP_FLAG_OUT_BF16)) return BNN_HIP_ERR_INVALID_ARG;
+  bnn_hip_conv_desc plain = *d;
+  plain.flags &= ~(BNN_HIP_FLAG_OUT_F16 | BNN_HIP_FLAG_OUT_BF16);
+  d = &plain;
+  if (!aligned(x, x_dtype == BNN_HIP_DTYPE_F32 ? 4 : 2) || !aligned(wbits, 16) || !aligned(out, out_bits ? 2 : 4))
     return BNN_HIP_ERR_INVALID_ARG;
   if ((d->flags & BNN_HIP_FLAG_WEIGHT_ZEROS) && !wnz) return BNN_HIP_ERR_INVALID_ARG;
   bnn::ConvP p;
   const int st = fly_convp(d, &p);
   if (st != BNN_HIP_OK) return st;
+  p.out16 = out_bits == BNN_HIP_FLAG_OUT_F16 ? BNN_HIP_DTYPE_F16 : out_bits == BNN_HIP_FLAG_OUT_BF16 ? BNN_HIP_DTYPE_BF16 : 0;
   p.W = wbits; p.Z = wnz; p.alpha = alpha; p.bias = bias; p.scale = post_scale; p.out = out;
   g_launches.fetch_add(1, std::memory_order_relaxed);
   BNN_RANGE();
-  return bnn::launch_bconv_fly(p, x, x_dtype == BNN_HIP_DTYPE_F16, d->flags, plan, static_cast<hipStream_t>(stream));
+  return bnn::launch_bconv_fly(p, x, x_dtype, d->flags, plan, static_cast<hipStream_t>(stream));
 }
 
 static bool direct_applies(const bnn_hip_conv_desc* d) {

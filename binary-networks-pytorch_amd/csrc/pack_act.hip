@@ -18,7 +18,8 @@
 namespace bnn {
 
 // VP consecutive pixels of one channel, loaded with ONE instruction (4..16 bytes per lane).
-// T = float, or __half for `.half()` models (sign() of an fp16 value is the sign of its exact fp32 widening).
+// T = float, or __half / Bf16Bits for 16-bit models and autocast (sign() of a 16-bit value is the sign of its exact fp32
+// widening).
 template <typename T, int VP>
 struct alignas(sizeof(T) * VP) PixVec {
   T v[VP];
@@ -41,6 +42,11 @@ __device__ __forceinline__ V load_once(const V* p) {
 }
 __device__ __forceinline__ float widen(float v) { return v; }
 __device__ __forceinline__ float widen(__half v) { return __half2float(v); }
+// bf16 is the upper half of an fp32 word: the widening is one shift, exact for every value (NaN, +-0, subnormals)
+struct Bf16Bits {
+  uint16_t u;
+};
+__device__ __forceinline__ float widen(Bf16Bits v) { return __uint_as_float((uint32_t)v.u << 16); }
 
 // AFF: v = fmaf(x, bn_a[c], bn_b[c]) first (eval-mode BatchNorm in front of a pre-activation block's
 // binary conv: res_block.py:148, hierarchical_block.py:39); relu != 0: planes of sign(max(v, 0)).
@@ -139,6 +145,11 @@ int launch_pack_act(const float* x, int N, int C, int H, int W, uint64_t* P, uin
 int launch_pack_act_f16(const void* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M,
                         hipStream_t stream) {
   return launch_pack_act_t<__half>(static_cast<const __half*>(x), N, C, H, W, P, M, stream);
+}
+
+int launch_pack_act_bf16(const void* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M,
+                         hipStream_t stream) {
+  return launch_pack_act_t<Bf16Bits>(static_cast<const Bf16Bits*>(x), N, C, H, W, P, M, stream);
 }
 
 int launch_bn_act_pack(const float* x, int N, int C, int H, int W, const float* bn_a, const float* bn_b,

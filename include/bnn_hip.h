@@ -134,6 +134,12 @@ typedef struct bnn_hip_conv_desc {
                                         longer waves — the multi-chunk 3x3 kernels then do not split a
                                         32-channel block over two waves (same results; ResNet-18 b256:
                                         -3 % with one batch in flight, +2 % with two)              */
+/* bnn_hip_bconv2d_direct only (every other entry point answers BNN_HIP_ERR_INVALID_ARG): `out` is a tensor of 16-bit
+ * floats, 2-byte aligned, and the kernel rounds the result itself, where Tensor.to() and the reference's in-place
+ * post-scale on a 16-bit tensor round it:  r = D(fmaf(alpha[o], dot, bias[o]));  with post_scale: r = D(float(r) *
+ * post_scale[o]).  Round to nearest even, fp16 overflow gives +-inf.  At most one of the two.          */
+#define BNN_HIP_FLAG_OUT_F16 256
+#define BNN_HIP_FLAG_OUT_BF16 512
 
 /* Everything that happens to the integer dot after the popcount loop, fused into the conv
  * kernel so that activations can stay bit-packed between binary layers (callers:
@@ -267,6 +273,12 @@ int bnn_hip_pack_act_f32(const float* x, int N, int C, int H, int W,
  * the planes equal those of the widened fp32 tensor bit for bit.                                  */
 int bnn_hip_pack_act_f16(const void* x, int N, int C, int H, int W,
                          uint64_t* P, uint64_t* M, void* stream);
+
+/* Same planes from a bfloat16 tensor (a `.bfloat16()` model, or the activations of a network under bf16 autocast):
+ * x: [N,C,H,W] of 16-bit brain floats, 2-byte aligned.  A bf16 value is the upper half of an fp32 word: the widening
+ * is exact, the planes equal those of the widened fp32 tensor bit for bit.  (Additive entry point of ABI 16.)  */
+int bnn_hip_pack_act_bf16(const void* x, int N, int C, int H, int W,
+                          uint64_t* P, uint64_t* M, void* stream);
 
 /* AvgPool2d(kernel=k, stride=k, ceil_mode=True, count_include_pad=False) followed by
  * sign(): the shortcut branch of a down-sampling residual stage
@@ -842,7 +854,7 @@ int bnn_hip_blinear(int B, int F, int O,
  *
  *   bnn_hip_blinear_direct          out[m,o] = fmaf(alpha[o], dot(sign(x[m,:]), sign(Wc[o,:])), bias[o]) [* post_scale[o]]:
  *                                   the bits of bnn_hip_bconv2d_direct / bnn_hip_blinear on the same operands.  x: fp32
- *                                   (4-byte aligned) or fp16 (2-byte aligned), x_dtype = BNN_HIP_DTYPE_*; wbits / wnz
+ *                                   (4-byte aligned), fp16 or bf16 (2-byte aligned), x_dtype = BNN_HIP_DTYPE_*; wbits / wnz
  *                                   16-byte aligned, wnz may be NULL unless weight_zeros; bias / post_scale may be NULL;
  *                                   out fp32 [M,O].  P, Mn, T: all NULL, or all three 8-byte aligned [M][ceil(F/64)]
  *                                   words that receive x > 0, x < 0 and |x| < 1 — the planes of bnn_hip_pack_act_ste_f32
@@ -898,9 +910,11 @@ int bnn_hip_ste_mask_f32(float* gx, const uint64_t* T, int M, int F, void* strea
  * image with its halo) straight into LDS as two bit planes and convolves it from there — no packed copy of the
  * activations in HBM, no workspace, the input is read once.  Same integers, same float epilogue, same bits as
  * bnn_hip_pack_act_f32 + bnn_hip_bconv2d.
- *   x: [N,C,H,W] contiguous, x_dtype = BNN_HIP_DTYPE_F32 (4-byte aligned) or BNN_HIP_DTYPE_F16 (a `.half()` model:
- *      the planes are those of the exactly widened values; the output stays fp32, the caller rounds it once);
+ *   x: [N,C,H,W] contiguous, x_dtype = BNN_HIP_DTYPE_F32 (4-byte aligned), BNN_HIP_DTYPE_F16 or BNN_HIP_DTYPE_BF16
+ *      (2-byte aligned; a 16-bit model or autocast: the planes are those of the exactly widened values);
  *      N*C*H*W < 2^30 elements per launch.
+ *   out: fp32 [N,O,Ho,Wo], 4-byte aligned — or, with BNN_HIP_FLAG_OUT_F16 / BNN_HIP_FLAG_OUT_BF16 in d->flags, a tensor
+ *      of that 16-bit type, 2-byte aligned, rounded inside the kernel (see the flags).
  *   plan: NULL = bnn_hip_bconv2d_direct_plan()'s choice.  A caller's plan (tests, tuning) supplies
  *      images_per_band / rows_per_band / waves / blocks_per_unit / pack_ahead / fine_head / fine_tail /
  *      producers;
@@ -910,6 +924,7 @@ int bnn_hip_ste_mask_f32(float* gx, const uint64_t* T, int M, int F, void* strea
  * bnn_hip_pack_act_f32 + bnn_hip_bconv2d (what bnn_hip_bconv2d_f32 does by itself) for those.                   */
 #define BNN_HIP_DTYPE_F32 0
 #define BNN_HIP_DTYPE_F16 1
+#define BNN_HIP_DTYPE_BF16 2
 typedef struct bnn_hip_fly_plan {
   int32_t images_per_band;  /* whole images per workgroup (>= 1); > 1 only with rows_per_band == Ho            */
   int32_t rows_per_band;    /* output rows per workgroup: Ho = whole images                                     */

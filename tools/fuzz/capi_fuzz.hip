@@ -121,11 +121,15 @@ int fly_default_plan(const ConvP& p, int, bnn_hip_fly_plan* plan) {
   std::memset(plan, 0, sizeof(*plan));
   return fly_supported(p) ? BNN_HIP_OK : BNN_HIP_ERR_UNSUPPORTED;
 }
-int launch_bconv_fly(const ConvP& p, const void* x, int half, int flags, const bnn_hip_fly_plan*, hipStream_t) {
+int launch_bconv_fly(const ConvP& p, const void* x, int dtype, int flags, const bnn_hip_fly_plan*, hipStream_t) {
   ++g_reached;
   check_convp(p);
-  REQUIRE(x && p.W && p.alpha && p.out && al(x, half ? 2 : 4) && al(p.W, 16) && al(p.out, 4));
+  REQUIRE(dtype == BNN_HIP_DTYPE_F32 || dtype == BNN_HIP_DTYPE_F16 || dtype == BNN_HIP_DTYPE_BF16);
+  const bool half = dtype != BNN_HIP_DTYPE_F32;
+  REQUIRE(p.out16 == 0 || p.out16 == BNN_HIP_DTYPE_F16 || p.out16 == BNN_HIP_DTYPE_BF16);
+  REQUIRE(x && p.W && p.alpha && p.out && al(x, half ? 2 : 4) && al(p.W, 16) && al(p.out, p.out16 ? 2 : 4));
   REQUIRE((long long)p.N * p.C * p.H * p.Wd * (half ? 2 : 4) <= kDesc);
+  REQUIRE(!(flags & (BNN_HIP_FLAG_OUT_F16 | BNN_HIP_FLAG_OUT_BF16)));   // (they travel as p.out16)
   REQUIRE(!(flags & BNN_HIP_FLAG_WEIGHT_ZEROS) || p.Z);
   return BNN_HIP_OK;
 }
@@ -137,6 +141,9 @@ int launch_pack_act(const float* x, int N, int C, int H, int W, uint64_t* P, uin
   ++g_reached; check_planes(x, N, C, H, W, P, M, 4); return BNN_HIP_OK;
 }
 int launch_pack_act_f16(const void* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M, hipStream_t) {
+  ++g_reached; check_planes(x, N, C, H, W, P, M, 2); return BNN_HIP_OK;
+}
+int launch_pack_act_bf16(const void* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M, hipStream_t) {
   ++g_reached; check_planes(x, N, C, H, W, P, M, 2); return BNN_HIP_OK;
 }
 int launch_bn_act_pack(const float* x, int N, int C, int H, int W, const float* a, const float* b, int, uint64_t* P,
@@ -415,11 +422,12 @@ static void check_linear(int M, int F, int O) {
   REQUIRE(M > 0 && F > 0 && O > 0 && (long long)M * F <= (1LL << 30) - 1 && (long long)M * O <= (1LL << 30) - 1);
   REQUIRE(((long long)O + 31) / 32 * 32 * (2 * (((long long)F + 63) / 64)) <= (1LL << 31) - 1);
 }
-int launch_blinear_fwd(const void* x, int x_half, const uint32_t* wb, const uint32_t* wz, int zeros, const float* alpha,
+int launch_blinear_fwd(const void* x, int x_dtype, const uint32_t* wb, const uint32_t* wz, int zeros, const float* alpha,
                        const float* bias, const float* scale, float* out, uint64_t* P, uint64_t* Mn, uint64_t* T, int M, int F,
                        int O, int lds_words, hipStream_t) {
   ++g_reached; check_linear(M, F, O);
-  REQUIRE(x && wb && alpha && out && al(x, x_half ? 2 : 4) && al(wb, 16) && al(wz, 16) && (!zeros || wz) && al(bias, 4) &&
+  REQUIRE(x_dtype == BNN_HIP_DTYPE_F32 || x_dtype == BNN_HIP_DTYPE_F16 || x_dtype == BNN_HIP_DTYPE_BF16);
+  REQUIRE(x && wb && alpha && out && al(x, x_dtype != BNN_HIP_DTYPE_F32 ? 2 : 4) && al(wb, 16) && al(wz, 16) && (!zeros || wz) && al(bias, 4) &&
           al(scale, 4) && al(out, 4) && lds_words >= 0);
   REQUIRE((P == nullptr) == (Mn == nullptr) && (P == nullptr) == (T == nullptr) && al(P, 8) && al(Mn, 8) && al(T, 8));
   return BNN_HIP_OK;
