@@ -2,6 +2,22 @@
 
 torch is used here for what the tier calls plumbing: device memory (caching allocator), the
 current HIP stream and device guards.  All arithmetic happens inside ``libbnn_hip.so``.
+
+Conventions (the C-ABI sees pointers, never strides, so every tensor passes one checker before its ``data_ptr()``):
+
+* an fp32 NCHW activation: ``_nchw`` (device, fp32 — or fp16 / bf16 with ``lowp`` —, rank 4, made contiguous);
+* per-channel constants: ``_per_channel`` (``[K, n]`` tables: ``_affine_table``); a read-only tensor of a known shape
+  (``residual``, ``addend``, gradients, saved statistics): ``_shaped``; both make a strided view contiguous;
+* a tensor the kernel writes in place (running statistics, ``out=``, ``gx`` of ``ste_mask_``): ``_written``, which
+  rejects a strided view — a copy would swallow the update;
+* an opaque buffer of a size the library states (``w8``, ``SconvWeight.data``, gradient weight packs): ``_opaque``;
+* channel slices of a wider tensor, read or written in place: ``channel_view``.
+
+A batch or row range larger than one launch addresses is cut by ``_split`` (descriptors: ``_desc_slices``).  Each wrapper
+computes its own step from the limit of its kernels — ``_MAX_ELEMS`` / ``_MAX_INDEX_FACTOR`` (``_batch_step``),
+``_MAX_DESC_BYTES``, ``_STEM3X3_MAX_ELEMS``, ``_STEM_S2_MAX_ELEMS``, ``_LINEAR_MAX_ELEMS``: module globals, read at call
+time — and only the cutting is shared.  A new wrapper: check every operand with one of the above, compute the step,
+allocate under ``torch.cuda.device``, loop over ``_split`` and hand each status to ``native.check``.
 """
 from __future__ import annotations
 
@@ -43,11 +59,17 @@ def _stem_launch_images(n: int, H: int, W: int, ho: int, wo: int) -> int:
     return max(1, min(n, _MAX_DESC_BYTES // max(12 * H * W, 256 * ho * wo)))
 
 
-def _desc_slices(d: native.ConvDesc, step: int):
-    """``(n0, n1, descriptor of images [n0, n1))`` for each launch of the descriptor's batch cut into ``step`` images."""
-    for n0 in range(0, d.N, step):
-        n1 = min(d.N, n0 + step)
-        dd = native.ConvDesc.from_buffer_copy(d)
+def _split(n: int, step: int):
+    """``(n0, n1)`` for each launch of ``n`` images (or rows) cut into runs of ``step``; nothing for ``n == 0``."""
+    for n0 in range(0, n, step):
+        yield n0, min(n, n0 + step)
+
+
+def _desc_slices(d, step: int):
+    """``(n0, n1, descriptor of images [n0, n1))`` for each launch of the descriptor's batch cut into ``step`` images
+    (``d``: any descriptor structure with an ``N`` field; it is left as it is)."""
+    for n0, n1 in _split(d.N, step):
+        dd = type(d).from_buffer_copy(d)
         dd.N = n1 - n0
         yield n0, n1, dd
 
@@ -73,12 +95,55 @@ def _stream(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
-def _require_cuda_f32(t: torch.Tensor, what: str) -> torch.Tensor:
+def _on_device(t: torch.Tensor, what: str, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     if not t.is_cuda:
         raise native.NativeError(f"bnn_amd: {what} must live on a HIP device, got {t.device}")
-    if t.dtype != torch.float32:
-        raise native.NativeError(f"bnn_amd: {what} must be float32, got {t.dtype}")
+    if t.dtype != dtype:
+        raise native.NativeError(f"bnn_amd: {what} must be {str(dtype)[6:]}, got {t.dtype}")
+    return t
+
+
+def _require_cuda_f32(t: torch.Tensor, what: str) -> torch.Tensor:
+    return _on_device(t, what).contiguous()
+
+
+def _shaped(t: Optional[torch.Tensor], shape, what: str, mismatch: Optional[str] = None,
+            dtype: torch.dtype = torch.float32) -> Optional[torch.Tensor]:
+    """A tensor the kernel only reads (None stays None): on the device, of ``dtype`` and ``shape``, made contiguous (the
+    same object when it is already).  ``mismatch``: the text of the shape error (``{got}``: the shape that came)."""
+    if t is None:
+        return None
+    _on_device(t, what, dtype)
+    if tuple(t.shape) != tuple(shape):
+        raise native.NativeError("bnn_amd: " + (mismatch or "{what} shape {got} != {want}").format(
+            what=what, got=tuple(t.shape), want=tuple(shape)))
     return t.contiguous()
+
+
+def _written(t: Optional[torch.Tensor], shape, what: str, error: Optional[str] = None) -> Optional[torch.Tensor]:
+    """A tensor the kernel writes in place (None stays None): on the device, fp32, of ``shape`` (an int: that many
+    elements in any shape) and contiguous.  A strided view is refused, never copied: the copy would take the update.
+    ``error``: the text of wrappers that had one of their own."""
+    if t is None:
+        return None
+    fits = t.numel() == shape if isinstance(shape, int) else tuple(t.shape) == tuple(shape)
+    if not (t.is_cuda and t.dtype == torch.float32 and fits and t.is_contiguous()):
+        raise native.NativeError("bnn_amd: " + (error or (
+            f"{what} is written in place: it must be a contiguous fp32 HIP tensor of {shape} "
+            f"{'entries' if isinstance(shape, int) else '(its shape)'}, got {tuple(t.shape)} {t.dtype} on {t.device}, "
+            f"strides {t.stride()}")))
+    return t
+
+
+def _opaque(t: torch.Tensor, nbytes: int, what: str, dtype: torch.dtype) -> torch.Tensor:
+    """A buffer whose layout only the library knows: on the device, ``dtype``, contiguous and exactly the ``nbytes`` the
+    library's own ``*_bytes`` function states for it (0: it has no such buffer for this geometry, and the entry point
+    refuses the call before reading any)."""
+    _on_device(t, what, dtype)
+    if not t.is_contiguous() or (nbytes and t.numel() * t.element_size() != int(nbytes)):
+        raise native.NativeError(f"bnn_amd: {what} must be a contiguous buffer of {int(nbytes)} bytes, got "
+                                 f"{t.numel() * t.element_size()} (strides {t.stride()})")
+    return t
 
 
 # The 16-bit formats the kernels read (C-ABI input type) and the one-launch layer stores (descriptor flag)
@@ -120,6 +185,22 @@ def _require_cuda_act(x: torch.Tensor) -> torch.Tensor:
     if not x.is_cuda:
         raise native.NativeError(f"bnn_amd: activation must live on a HIP device, got {x.device}")
     return x.contiguous()
+
+
+def _nchw(x: torch.Tensor, what: str, fn: str, lowp: bool = False) -> torch.Tensor:
+    """An NCHW activation of the wrapper ``fn``: on the device, fp32 (``lowp``: or fp16 / bf16), rank 4, made contiguous."""
+    x = _require_cuda_act(x) if lowp else _require_cuda_f32(x, what)
+    if x.dim() != 4:
+        raise native.NativeError(f"bnn_amd: {fn} expects NCHW, got shape {tuple(x.shape)}")
+    return x
+
+
+def _shuffle_groups(v, channels: int, noun: str) -> int:
+    """``channel_shuffle``'s group count as an int that divides the ``channels`` (``noun``: what the error calls them)."""
+    v = int(v)
+    if v < 1 or channels % v:
+        raise native.NativeError(f"bnn_amd: shuffle_groups={v} does not divide the {channels} {noun}")
+    return v
 
 
 def _per_channel(t: Optional[torch.Tensor], n: int, what: str) -> Optional[torch.Tensor]:
@@ -177,9 +258,7 @@ def empty_packed(N: int, C: int, H: int, W: int, device) -> PackedAct:
 
 def pack_act(x: torch.Tensor) -> PackedAct:
     """``BasicInputBinarizer`` on device: fp32 (or fp16 / bf16) NCHW -> bit planes (bnn/ops.py:151-152)."""
-    x = _require_cuda_act(x)
-    if x.dim() != 4:
-        raise native.NativeError(f"bnn_amd: pack_act expects NCHW, got shape {tuple(x.shape)}")
+    x = _nchw(x, "activation", "pack_act", lowp=True)
     lib = native.require()
     N, C, H, W = x.shape
     if N == 0:  # empty batch: nothing to launch (the reference's conv2d returns an empty tensor too)
@@ -196,9 +275,7 @@ def pack_act(x: torch.Tensor) -> PackedAct:
 def bn_act_pack(x: torch.Tensor, bn_scale=None, bn_shift=None, relu: bool = False) -> PackedAct:
     """``sign(act(bn(x)))`` of an fp32 NCHW tensor in one pass: the input binarisation of a pre-activation
     block (bnn/models/layers/res_block.py:148, hierarchical_block.py:39)."""
-    x = _require_cuda_f32(x, "activation")
-    if x.dim() != 4:
-        raise native.NativeError(f"bnn_amd: bn_act_pack expects NCHW, got shape {tuple(x.shape)}")
+    x = _nchw(x, "activation", "bn_act_pack")
     lib = native.require()
     N, C, H, W = x.shape
     bn_scale = _per_channel(bn_scale, C, "bn_scale")
@@ -293,6 +370,17 @@ def bn_act_pack_s2(x: torch.Tensor, bn_scale=None, bn_shift=None, relu: bool = F
     return tuple(PackedAct(P[k], M[k], (N, C, H // 2, W // 2), bool(relu)) for k in range(2))
 
 
+def _join_plane_sets(parts: list, K: int, plane_shape, device):
+    """``(P, M)`` ``[K, N, cw64, H, W]`` from the ``[K, n, cw64, H, W]`` pairs of each launch of a cut batch: the pair
+    itself for one launch, a concatenation over the batch for several, empty ``[K, 0, *plane_shape]`` planes for none."""
+    if len(parts) == 1:
+        return parts[0]
+    if parts:
+        return torch.cat([p for p, _ in parts], 1), torch.cat([m for _, m in parts], 1)
+    P = torch.empty((K, 0, *plane_shape), dtype=torch.int64, device=device)
+    return P, torch.empty_like(P)
+
+
 _STEM3X3_MAX_ELEMS = (1 << 31) - 1      # fp32 elements of x or y one stem3x3 launch covers (capi.hip: kMaxElems)
 
 
@@ -322,22 +410,15 @@ def stem3x3_bn_relu_pack(x: torch.Tensor, w: torch.Tensor, bn_scale: torch.Tenso
     with torch.cuda.device(x.device):
         y = torch.empty((N, O, H, W), dtype=torch.float32, device=x.device) if out_f32 else None
         parts = []
-        for n0 in range(0, N, step):            # (one launch unless the batch is cut: a plane set is [n, cw64, H, W])
-            n = min(step, N - n0)
-            P = torch.empty((K, n, cw64, H, W), dtype=torch.int64, device=x.device)
+        for n0, n1 in _split(N, step):          # (one launch unless the batch is cut: a plane set is [n, cw64, H, W])
+            P = torch.empty((K, n1 - n0, cw64, H, W), dtype=torch.int64, device=x.device)
             M = torch.empty_like(P)
             native.check(lib.bnn_hip_stem3x3_bn_relu_pack_f32(
-                x[n0:n0 + n].data_ptr(), w.data_ptr(), bn_scale.data_ptr(), bn_shift.data_ptr(), a.data_ptr(), b.data_ptr(),
-                n, O, H, W, K, P.data_ptr(), M.data_ptr(), None if y is None else y[n0:n0 + n].data_ptr(),
+                x[n0:n1].data_ptr(), w.data_ptr(), bn_scale.data_ptr(), bn_shift.data_ptr(), a.data_ptr(), b.data_ptr(),
+                n1 - n0, O, H, W, K, P.data_ptr(), M.data_ptr(), None if y is None else y[n0:n1].data_ptr(),
                 _stream(x.device)), "bnn_hip_stem3x3_bn_relu_pack_f32")
             parts.append((P, M))
-        if len(parts) == 1:
-            P, M = parts[0]
-        elif parts:
-            P, M = torch.cat([p for p, _ in parts], 1), torch.cat([m for _, m in parts], 1)
-        else:
-            P = torch.empty((K, 0, cw64, H, W), dtype=torch.int64, device=x.device)
-            M = torch.empty_like(P)
+        P, M = _join_plane_sets(parts, K, (cw64, H, W), x.device)
     return y, [PackedAct(P[k], M[k], (N, O, H, W), False) for k in range(K)]
 
 
@@ -382,11 +463,10 @@ def stem_s2x2(x: torch.Tensor, w1: torch.Tensor, s1: torch.Tensor, t1: torch.Ten
     step = max(1, min(N, _STEM_S2_MAX_ELEMS // max(3 * H * W, C * H2 * W2, 1)))
     with torch.cuda.device(x.device):
         y = torch.empty((N, C, H2, W2), dtype=torch.float32, device=x.device)
-        for n0 in range(0, N if H * W else 0, step):
-            n = min(step, N - n0)
+        for n0, n1 in _split(N if H * W else 0, step):
             native.check(lib.bnn_hip_stem_s2x2_f32(
-                x[n0:n0 + n].data_ptr(), w1.data_ptr(), s1.data_ptr(), t1.data_ptr(), w2.data_ptr(), s2.data_ptr(),
-                t2.data_ptr(), n, C1, C, groups, H, W, int(bool(relu_out)), y[n0:n0 + n].data_ptr(), _stream(x.device)),
+                x[n0:n1].data_ptr(), w1.data_ptr(), s1.data_ptr(), t1.data_ptr(), w2.data_ptr(), s2.data_ptr(),
+                t2.data_ptr(), n1 - n0, C1, C, groups, H, W, int(bool(relu_out)), y[n0:n1].data_ptr(), _stream(x.device)),
                 "bnn_hip_stem_s2x2_f32")
     return y
 
@@ -400,9 +480,7 @@ def gconv3x3s2_bn_pack(x: torch.Tensor, w: torch.Tensor, bn_scale: torch.Tensor,
     Returns ``(y | None, [K PackedAct])`` where set ``k`` holds the bits of ``bn_act_pack_multi(y, pack_scales,
     pack_shifts)[k]``; ``out_f32=False`` (``K >= 1`` only): ``y`` is not written.  A batch whose ``x`` or ``y`` would reach
     2^31 elements is cut into several launches."""
-    x = _require_cuda_f32(x, "activation")
-    if x.dim() != 4:
-        raise native.NativeError(f"bnn_amd: gconv3x3s2_bn_pack expects NCHW, got shape {tuple(x.shape)}")
+    x = _nchw(x, "activation", "gconv3x3s2_bn_pack")
     N, C, H, W = x.shape
     w = _grouped_w(w, C, groups, "weight")
     O = w.shape[0]
@@ -424,22 +502,15 @@ def gconv3x3s2_bn_pack(x: torch.Tensor, w: torch.Tensor, bn_scale: torch.Tensor,
     with torch.cuda.device(x.device):
         y = torch.empty((N, O, Ho, Wo), dtype=torch.float32, device=x.device) if out_f32 else None
         parts = []
-        for n0 in range(0, N if H * W else 0, step):   # (one launch unless the batch is cut: a plane set is [n, cw64, Ho, Wo])
-            n = min(step, N - n0)
-            P = torch.empty((K, n, cw64, Ho, Wo), dtype=torch.int64, device=x.device)
+        for n0, n1 in _split(N if H * W else 0, step):   # (one launch unless the batch is cut: a plane set is [n, cw64, Ho, Wo])
+            P = torch.empty((K, n1 - n0, cw64, Ho, Wo), dtype=torch.int64, device=x.device)
             M = torch.empty_like(P)
             native.check(lib.bnn_hip_gconv3x3s2_bn_pack_f32(
-                x[n0:n0 + n].data_ptr(), w.data_ptr(), bn_scale.data_ptr(), bn_shift.data_ptr(), _ptr(a), _ptr(b), n, C, O,
+                x[n0:n1].data_ptr(), w.data_ptr(), bn_scale.data_ptr(), bn_shift.data_ptr(), _ptr(a), _ptr(b), n1 - n0, C, O,
                 groups, H, W, int(bool(relu_in)), K, P.data_ptr() if K else None, M.data_ptr() if K else None,
-                None if y is None else y[n0:n0 + n].data_ptr(), _stream(x.device)), "bnn_hip_gconv3x3s2_bn_pack_f32")
+                None if y is None else y[n0:n1].data_ptr(), _stream(x.device)), "bnn_hip_gconv3x3s2_bn_pack_f32")
             parts.append((P, M))
-        if len(parts) == 1:
-            P, M = parts[0]
-        elif parts:
-            P, M = torch.cat([p for p, _ in parts], 1), torch.cat([m for _, m in parts], 1)
-        else:
-            P = torch.empty((K, 0, cw64, Ho, Wo), dtype=torch.int64, device=x.device)
-            M = torch.empty_like(P)
+        P, M = _join_plane_sets(parts, K, (cw64, Ho, Wo), x.device)
     return y, [PackedAct(P[k], M[k], (N, O, Ho, Wo), False) for k in range(K)]
 
 
@@ -447,7 +518,7 @@ def avgpool_pack(x: torch.Tensor, k: int, nonneg: bool = False) -> PackedAct:
     """``AvgPool2d(k, k, ceil_mode=True, count_include_pad=False)`` + sign, fused
     (shortcut branch of bnn/models/resnet.py:128-133).  ``nonneg``: the caller knows ``x >= 0``
     (it is a ReLU output), so the averages are too."""
-    x = _require_cuda_f32(x, "activation")
+    x = _nchw(x, "activation", "avgpool_pack")
     lib = native.require()
     N, C, H, W = x.shape
     ho, wo = (H + k - 1) // k, (W + k - 1) // k
@@ -499,32 +570,28 @@ def stem7x7(x: torch.Tensor, w: torch.Tensor, bn_scale: torch.Tensor, bn_shift: 
     with torch.cuda.device(x.device):
         if out is not None:
             y, pk = out
-            if (y is not None and (tuple(y.shape) != (N, 64, hp, wp) or y.dtype != torch.float32 or y.device != x.device
-                                   or not y.is_contiguous())) or \
+            wrong = "stem7x7: `out` does not belong to this input shape / device"
+            _written(y, (N, 64, hp, wp), "out", wrong)
+            if (y is not None and y.device != x.device) or \
                     (pk is not None and (tuple(pk.shape) != (N, 64, hp, wp) or pk.P.device != x.device)):
-                raise native.NativeError("bnn_amd: stem7x7: `out` does not belong to this input shape / device")
+                raise native.NativeError("bnn_amd: " + wrong)
         else:
             y = torch.empty((N, 64, hp, wp), dtype=torch.float32, device=x.device) if out_f32 else None
             pk = empty_packed(N, 64, hp, wp, x.device) if out_packed else None
         step = _stem_launch_images(N, H, W, hp, wp)   # larger batches go in several launches
         flags = native.STEM_EXACT_FP32 if exact_fp32 else (native.STEM_FP16 if fp16 else 0)
+        symbol, affine = "bnn_hip_stem7x7_bn_relu_pool_pack_f32", ()
         if pack_affine is not None:
             if exact_fp32 or pk is None:
                 raise native.NativeError("bnn_amd: stem7x7(pack_affine=...) needs packed output and is not built for the exact-fp32 stem")
             pa, pb = _per_channel(pack_affine[0], 64, "pack scale"), _per_channel(pack_affine[1], 64, "pack shift")
-        for n0 in range(0, N, step):
-            n1 = min(N, n0 + step)
-            if pack_affine is not None:
-                native.check(lib.bnn_hip_stem7x7_bn_relu_pool_pack_affine_f32(
-                    x[n0:n1].data_ptr(), w.data_ptr(), bn_scale.data_ptr(), bn_shift.data_ptr(), pa.data_ptr(), pb.data_ptr(),
-                    n1 - n0, H, W, flags, None if y is None else y[n0:n1].data_ptr(), pk.P[n0:n1].data_ptr(),
-                    pk.M[n0:n1].data_ptr(), _stream(x.device)), "bnn_hip_stem7x7_bn_relu_pool_pack_affine_f32")
-                continue
-            native.check(lib.bnn_hip_stem7x7_bn_relu_pool_pack_f32(
-                x[n0:n1].data_ptr(), w.data_ptr(), bn_scale.data_ptr(), bn_shift.data_ptr(), n1 - n0, H, W, flags,
+            symbol, affine = "bnn_hip_stem7x7_bn_relu_pool_pack_affine_f32", (pa.data_ptr(), pb.data_ptr())
+        for n0, n1 in _split(N, step):
+            native.check(getattr(lib, symbol)(
+                x[n0:n1].data_ptr(), w.data_ptr(), bn_scale.data_ptr(), bn_shift.data_ptr(), *affine, n1 - n0, H, W, flags,
                 None if y is None else y[n0:n1].data_ptr(),
                 None if pk is None else pk.P[n0:n1].data_ptr(), None if pk is None else pk.M[n0:n1].data_ptr(),
-                _stream(x.device)), "bnn_hip_stem7x7_bn_relu_pool_pack_f32")
+                _stream(x.device)), symbol)
     if pk is not None:
         pk.nonneg = True  # ReLU output
     return y, pk
@@ -544,8 +611,7 @@ def stem7x7_conv(x: torch.Tensor, w: torch.Tensor, fp16: bool = False) -> torch.
     with torch.cuda.device(x.device):
         y = torch.empty((N, 64, hc, wc), dtype=torch.float32, device=x.device)
         step = _stem_launch_images(N, H, W, hc, wc)
-        for n0 in range(0, N, step):
-            n1 = min(N, n0 + step)
+        for n0, n1 in _split(N, step):
             native.check(lib.bnn_hip_stem7x7_conv_f32(x[n0:n1].data_ptr(), w.data_ptr(), n1 - n0, H, W,
                                                       native.STEM_FP16 if fp16 else 0, y[n0:n1].data_ptr(),
                                                       _stream(x.device)), "bnn_hip_stem7x7_conv_f32")
@@ -601,7 +667,7 @@ def avgpool2_bn_pack2(x: torch.Tensor, bn1, relu1: bool, bn2=None, relu2: bool =
     """``AvgPool2d(2, 2)`` of an fp32 NCHW tensor (even H, W) + ``sign(act(bn(.)))`` of the pooled tensor for up to two
     BatchNorm branches in one pass (``bnn_hip_avgpool2_bn_pack2_f32``).  ``bn1`` / ``bn2``: (scale, shift).
     Returns ``(PackedAct 1, PackedAct 2 | None, pooled fp32 | None)``."""
-    x = _require_cuda_f32(x, "activation")
+    x = _nchw(x, "activation", "avgpool2_bn_pack2")
     lib = native.require()
     N, C, H, W = x.shape
     if H % 2 or W % 2:
@@ -677,7 +743,7 @@ def bn_relu_maxpool_pack(x: torch.Tensor, bn_scale=None, bn_shift=None, relu: bo
                          stride: int = 2, pad: int = 1, out_f32: bool = True, out_packed: bool = True):
     """Stem tail in one pass: folded BN -> MaxPool2d(k, stride, pad) -> ReLU, written as fp32
     and/or sign planes (bnn/models/resnet.py:150-153 + the first binary conv's binarizer)."""
-    x = _require_cuda_f32(x, "activation")
+    x = _nchw(x, "activation", "bn_relu_maxpool_pack")
     lib = native.require()
     N, C, H, W = x.shape
     ho, wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
@@ -810,6 +876,11 @@ def _flags(w: PackedWeight, force_generic: bool, weights: Optional[str], a: Opti
     return f
 
 
+def _conv_step(d: native.ConvDesc, stride, padding, dilation, c_total: Optional[int] = None) -> int:
+    """``fused_launch_images`` of a descriptor: one launch addresses < 2^31 elements, a larger batch is split."""
+    return fused_launch_images(d.N, d.C, d.H, d.W, d.O, (d.KH, d.KW), stride, padding, dilation, c_total)
+
+
 def bconv2d(a: PackedAct, w: PackedWeight, bias: Optional[torch.Tensor] = None,
             post_scale: Optional[torch.Tensor] = None, stride=1, padding=0, dilation=1,
             force_generic: bool = False, raw_dot: bool = False,
@@ -825,11 +896,7 @@ def bconv2d(a: PackedAct, w: PackedWeight, bias: Optional[torch.Tensor] = None,
     with torch.cuda.device(dev):
         out = torch.empty((d.N, d.O, ho, wo), dtype=torch.int32 if raw_dot else torch.float32,
                           device=dev)
-        if d.N == 0:
-            return out
-        # one launch addresses < 2^31 elements: split the batch when a tensor is larger
-        step = fused_launch_images(d.N, d.C, d.H, d.W, d.O, (d.KH, d.KW), stride, padding, dilation)
-        for n0, n1, dd in _desc_slices(d, step):
+        for n0, n1, dd in _desc_slices(d, _conv_step(d, stride, padding, dilation)):
             args = (ctypes.byref(dd), a.P[n0:n1].data_ptr(), a.M[n0:n1].data_ptr(),
                     w.wbits.data_ptr(), w.wnz.data_ptr())
             if raw_dot:
@@ -841,32 +908,37 @@ def bconv2d(a: PackedAct, w: PackedWeight, bias: Optional[torch.Tensor] = None,
     return out
 
 
+def _grouped_frame(a: PackedAct, w: PackedWeight, fn: str, stride, padding, dilation, bias, post_scale, prelu=None,
+                   shuffle_groups=1):
+    """What the three grouped wrappers (``fn``: which) share: ``(descriptor over all C input channels, (ho, wo), (bias,
+    post_scale, prelu) checked per output channel, shuffle_groups validated)``."""
+    if not w.windowed:
+        raise native.NativeError(f"bnn_amd: {fn} reads the layout of pack_weight_grouped, not of pack_weight")
+    N, C, H, W = a.shape
+    O, Cg, KH, KW = w.shape
+    if Cg * w.groups != C:
+        raise native.NativeError(f"bnn_amd: grouped weight reads {Cg} x {w.groups} channels, the input has {C}")
+    shuffle_groups = _shuffle_groups(shuffle_groups, O, "output channels")
+    d = _desc(a.shape, (O, C, KH, KW), stride, padding, dilation, 0)
+    consts = tuple(_per_channel(t, O, what) for t, what in ((bias, "bias"), (post_scale, "post_scale"), (prelu, "prelu")))
+    return d, conv_out_hw(H, W, KH, KW, stride, padding, dilation), consts, shuffle_groups
+
+
 def bconv2d_grouped(a: PackedAct, w: PackedWeight, bias: Optional[torch.Tensor] = None,
                     post_scale: Optional[torch.Tensor] = None, stride=1, padding=0, dilation=1,
                     raw_dot: bool = False) -> torch.Tensor:
     """Grouped / depthwise binary convolution on packed operands (``bnn_hip_bconv2d_grouped``): ``a`` holds all C input
     channels, ``w`` comes from ``pack_weight_grouped`` (any ``groups``, 1 included) -> fp32 NCHW, or the int32 dot when
     ``raw_dot``."""
-    if not w.windowed:
-        raise native.NativeError("bnn_amd: bconv2d_grouped reads the layout of pack_weight_grouped, not of pack_weight")
     lib = native.require()
-    N, C, H, W = a.shape
-    O, Cg, KH, KW = w.shape
-    if Cg * w.groups != C:
-        raise native.NativeError(f"bnn_amd: grouped weight reads {Cg} x {w.groups} channels, the input has {C}")
-    d = _desc(a.shape, (O, C, KH, KW), stride, padding, dilation, 0)
-    ho, wo = conv_out_hw(H, W, KH, KW, stride, padding, dilation)
+    d, (ho, wo), (bias, post_scale, _), _ = _grouped_frame(a, w, "bconv2d_grouped", stride, padding, dilation, bias,
+                                                           post_scale)
     dev = a.P.device
-    bias = _per_channel(bias, O, "bias")
-    post_scale = _per_channel(post_scale, O, "post_scale")
     if raw_dot and (bias is not None or post_scale is not None):
         raise ValueError("raw_dot returns the integer dot: no bias / post_scale")
     with torch.cuda.device(dev):
-        out = torch.empty((N, O, ho, wo), dtype=torch.int32 if raw_dot else torch.float32, device=dev)
-        if N == 0:
-            return out
-        step = fused_launch_images(N, C, H, W, O, (KH, KW), stride, padding, dilation)
-        for n0, n1, dd in _desc_slices(d, step):
+        out = torch.empty((d.N, d.O, ho, wo), dtype=torch.int32 if raw_dot else torch.float32, device=dev)
+        for n0, n1, dd in _desc_slices(d, _conv_step(d, stride, padding, dilation)):
             native.check(lib.bnn_hip_bconv2d_grouped(ctypes.byref(dd), w.groups, a.P[n0:n1].data_ptr(),
                                                      a.M[n0:n1].data_ptr(), w.wbits.data_ptr(), w.wnz.data_ptr(),
                                                      None if raw_dot else w.alpha.data_ptr(), _ptr(bias),
@@ -883,33 +955,14 @@ def bconv2d_grouped_fused(a: PackedAct, w: PackedWeight, bias: Optional[torch.Te
     (``bnn_hip_bconv2d_grouped_fused``): per-channel PReLU, ``channel_shuffle(., shuffle_groups)`` as the store index
     and the skip connection ``residual + .`` (fp32 ``[N, O, Ho, Wo]``) -> fp32 NCHW.  With none of the three it returns
     the bits of ``bconv2d_grouped``."""
-    if not w.windowed:
-        raise native.NativeError("bnn_amd: bconv2d_grouped_fused reads the layout of pack_weight_grouped, not of "
-                                 "pack_weight")
     lib = native.require()
-    N, C, H, W = a.shape
-    O, Cg, KH, KW = w.shape
-    if Cg * w.groups != C:
-        raise native.NativeError(f"bnn_amd: grouped weight reads {Cg} x {w.groups} channels, the input has {C}")
-    shuffle_groups = int(shuffle_groups)
-    if shuffle_groups < 1 or O % shuffle_groups:
-        raise native.NativeError(f"bnn_amd: shuffle_groups={shuffle_groups} does not divide the {O} output channels")
-    d = _desc(a.shape, (O, C, KH, KW), stride, padding, dilation, 0)
-    ho, wo = conv_out_hw(H, W, KH, KW, stride, padding, dilation)
+    d, (ho, wo), (bias, post_scale, prelu), shuffle_groups = _grouped_frame(
+        a, w, "bconv2d_grouped_fused", stride, padding, dilation, bias, post_scale, prelu, shuffle_groups)
     dev = a.P.device
-    bias = _per_channel(bias, O, "bias")
-    post_scale = _per_channel(post_scale, O, "post_scale")
-    prelu = _per_channel(prelu, O, "prelu")
-    if residual is not None:
-        residual = _require_cuda_f32(residual, "residual")
-        if tuple(residual.shape) != (N, O, ho, wo):
-            raise native.NativeError(f"bnn_amd: residual shape {tuple(residual.shape)} != output")
+    residual = _shaped(residual, (d.N, d.O, ho, wo), "residual", "residual shape {got} != output")
     with torch.cuda.device(dev):
-        out = torch.empty((N, O, ho, wo), dtype=torch.float32, device=dev)
-        if N == 0:
-            return out
-        step = fused_launch_images(N, C, H, W, O, (KH, KW), stride, padding, dilation)
-        for n0, n1, dd in _desc_slices(d, step):
+        out = torch.empty((d.N, d.O, ho, wo), dtype=torch.float32, device=dev)
+        for n0, n1, dd in _desc_slices(d, _conv_step(d, stride, padding, dilation)):
             native.check(lib.bnn_hip_bconv2d_grouped_fused(
                 ctypes.byref(dd), w.groups, a.P[n0:n1].data_ptr(), a.M[n0:n1].data_ptr(), w.wbits.data_ptr(),
                 w.wnz.data_ptr(), w.alpha.data_ptr(), _ptr(bias), _ptr(post_scale), _ptr(prelu), shuffle_groups,
@@ -929,44 +982,28 @@ def bconv2d_grouped_node(a: PackedAct, w: PackedWeight, bias: Optional[torch.Ten
     (``channel_view``) — ``out`` typically the node's slice of the cell output, which makes ``torch.cat`` disappear.
     ``out`` may not share an element with an operand; slices of ONE tensor with disjoint channels are fine.  Returns
     ``out`` (a new tensor when not given)."""
-    if not w.windowed:
-        raise native.NativeError("bnn_amd: bconv2d_grouped_node reads the layout of pack_weight_grouped, not of "
-                                 "pack_weight")
     lib = native.require()
-    N, C, H, W = a.shape
-    O, Cg, KH, KW = w.shape
-    if Cg * w.groups != C:
-        raise native.NativeError(f"bnn_amd: grouped weight reads {Cg} x {w.groups} channels, the input has {C}")
-    shuffle_groups = int(shuffle_groups)
-    if shuffle_groups < 1 or O % shuffle_groups:
-        raise native.NativeError(f"bnn_amd: shuffle_groups={shuffle_groups} does not divide the {O} output channels")
-    d = _desc(a.shape, (O, C, KH, KW), stride, padding, dilation, 0)
-    ho, wo = conv_out_hw(H, W, KH, KW, stride, padding, dilation)
+    d, (ho, wo), (bias, post_scale, prelu), shuffle_groups = _grouped_frame(
+        a, w, "bconv2d_grouped_node", stride, padding, dilation, bias, post_scale, prelu, shuffle_groups)
     dev = a.P.device
-    bias = _per_channel(bias, O, "bias")
-    post_scale = _per_channel(post_scale, O, "post_scale")
-    prelu = _per_channel(prelu, O, "prelu")
+    shape = (d.N, d.O, ho, wo)
     with torch.cuda.device(dev):
         if out is None:
-            out = torch.empty((N, O, ho, wo), dtype=torch.float32, device=dev)
+            out = torch.empty(shape, dtype=torch.float32, device=dev)
         views = []
         for t, what in ((residual, "residual"), (addend, "addend"), (out, "out")):
-            if t is None:
-                views.append(None)
-                continue
-            if tuple(t.shape) != (N, O, ho, wo):
-                raise native.NativeError(f"bnn_amd: {what} shape {tuple(t.shape)} != output {(N, O, ho, wo)}")
-            views.append(channel_view(t, what))
-        if N == 0:
+            if t is not None and tuple(t.shape) != shape:
+                raise native.NativeError(f"bnn_amd: {what} shape {tuple(t.shape)} != output {shape}")
+            views.append(None if t is None else channel_view(t, what))
+        if d.N == 0:
             return out
         c_max = max(v[2] for v in views if v is not None)
-        step = fused_launch_images(N, C, H, W, O, (KH, KW), stride, padding, dilation, c_max)
 
         def arg(v, n0, n1):
             if v is None:
                 return None
             return native.F32View(v[0][n0:n1].data_ptr(), v[1], v[2])
-        for n0, n1, dd in _desc_slices(d, step):
+        for n0, n1, dd in _desc_slices(d, _conv_step(d, stride, padding, dilation, c_max)):
             r, ad, o = (arg(v, n0, n1) for v in views)
             native.check(lib.bnn_hip_bconv2d_grouped_node(
                 ctypes.byref(dd), w.groups, a.P[n0:n1].data_ptr(), a.M[n0:n1].data_ptr(), w.wbits.data_ptr(),
@@ -1012,11 +1049,10 @@ def fconv_fused(a: PackedAct, w1: PackedWeight, w2: PackedWeight, mid_scale: tor
     if tuple(w1.shape) != (C, C, 1, K) or tuple(w2.shape) != (C, C, K, 1):
         raise native.NativeError(f"bnn_amd: fconv_fused takes [C, C, 1, K] and [C, C, K, 1] weights over the input's {C} "
                                  f"channels, got {tuple(w1.shape)} and {tuple(w2.shape)}")
-    stride, shuffle_groups = int(stride), int(shuffle_groups)
+    stride = int(stride)
     if stride < 1:
         raise native.NativeError(f"bnn_amd: stride={stride}")
-    if shuffle_groups < 1 or C % shuffle_groups:
-        raise native.NativeError(f"bnn_amd: shuffle_groups={shuffle_groups} does not divide the {C} channels")
+    shuffle_groups = _shuffle_groups(shuffle_groups, C, "channels")
     ho, wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     dev = a.P.device
     mid_scale = _per_channel(mid_scale, C, "mid_scale")
@@ -1024,20 +1060,11 @@ def fconv_fused(a: PackedAct, w1: PackedWeight, w2: PackedWeight, mid_scale: tor
     consts = [[_per_channel(t, C, what) for t, what in ((b, "bias"), (s, "post_scale"), (p, "prelu"))]
               for b, s, p in ((bias1, post_scale1, prelu1), (bias2, post_scale2, prelu2))]
     stages = [native.FconvStage(w.alpha.data_ptr(), *map(_ptr, c)) for w, c in zip((w1, w2), consts)]
-    if residual is not None:
-        residual = _require_cuda_f32(residual, "residual")
-        if tuple(residual.shape) != (N, C, ho, wo):
-            raise native.NativeError(f"bnn_amd: residual shape {tuple(residual.shape)} != output")
+    residual = _shaped(residual, (N, C, ho, wo), "residual", "residual shape {got} != output")
     d = _fconv_desc(N, C, H, W, K, stride, w1.has_zero or w2.has_zero)
     with torch.cuda.device(dev):
         out = torch.empty((N, C, ho, wo), dtype=torch.float32, device=dev)
-        if N == 0:
-            return out
-        step = _fconv_launch_images(N, C, H, W, stride)
-        for n0 in range(0, N, step):
-            n1 = min(N, n0 + step)
-            dd = native.FconvDesc.from_buffer_copy(d)
-            dd.N = n1 - n0
+        for n0, n1, dd in _desc_slices(d, _fconv_launch_images(N, C, H, W, stride)):
             native.check(lib.bnn_hip_fconv_fused(
                 ctypes.byref(dd), a.P[n0:n1].data_ptr(), a.M[n0:n1].data_ptr(), w1.wbits.data_ptr(), w1.wnz.data_ptr(),
                 ctypes.byref(stages[0]), w2.wbits.data_ptr(), w2.wnz.data_ptr(), ctypes.byref(stages[1]),
@@ -1089,9 +1116,7 @@ def bconv2d_direct(x: torch.Tensor, w: PackedWeight, bias: Optional[torch.Tensor
         raise ValueError("route must be None, 'direct' or 'packed'")
     _check_out_dtype(out_dtype)
     _ungrouped(w, "bconv2d_direct")
-    x = _require_cuda_act(x)
-    if x.dim() != 4:
-        raise native.NativeError(f"bnn_amd: bconv2d_direct expects NCHW, got shape {tuple(x.shape)}")
+    x = _nchw(x, "activation", "bconv2d_direct", lowp=True)
     lib = native.require()
     d = _desc(tuple(x.shape), w.shape, stride, padding, dilation, _flags(w, force_generic, None))
     ho, wo = conv_out_hw(d.H, d.W, d.KH, d.KW, stride, padding, dilation)
@@ -1151,16 +1176,12 @@ def _fused_launches(a: PackedAct, w: PackedWeight, what: str, *, bias=None, post
     pack_shift = _per_channel(pack_shift, d.O, "pack_shift")
     c_total = d.O
     if out is not None:
-        if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4
-                and out.shape[0] == d.N and tuple(out.shape[2:]) == (ho, wo)
-                and 0 <= out_c_offset and out_c_offset + d.O <= out.shape[1]):
-            raise native.NativeError("bnn_amd: `out` must be a contiguous fp32 [N, C_total, Ho, Wo] tensor "
-                                     "with room for O channels at out_c_offset")
+        wrong = "`out` must be a contiguous fp32 [N, C_total, Ho, Wo] tensor with room for O channels at out_c_offset"
+        if out.dim() != 4 or not 0 <= out_c_offset <= out.shape[1] - d.O:
+            raise native.NativeError("bnn_amd: " + wrong)
         c_total = out.shape[1]
-    if residual is not None:
-        residual = _require_cuda_f32(residual, "residual")
-        if tuple(residual.shape) != (d.N, c_total, ho, wo):
-            raise native.NativeError(f"bnn_amd: residual shape {tuple(residual.shape)} != output")
+        _written(out, (d.N, c_total, ho, wo), "out", wrong)
+    residual = _shaped(residual, (d.N, c_total, ho, wo), "residual", "residual shape {got} != output")
     sc_in_hw = 0
     if shortcut is not None:
         sa, sw, sbn_a, sbn_b = shortcut
@@ -1183,21 +1204,21 @@ def _fused_launches(a: PackedAct, w: PackedWeight, what: str, *, bias=None, post
         y = out if out is not None else (
             torch.empty((d.N, d.O, ho, wo), dtype=torch.float32, device=dev) if out_f32 else None)
         pk = empty_packed(d.N, d.O, ho, wo, dev) if out_packed else None
-    # one launch addresses < 2^31 elements: split the batch when a tensor is larger (like bconv2d)
-    step = fused_launch_images(d.N, d.C, d.H, d.W, d.O, (d.KH, d.KW), stride, padding, dilation, c_total)
+    step = _conv_step(d, stride, padding, dilation, c_total)
 
     def launches():
         for n0, n1, dd in _desc_slices(d, step):
-            e = native.Epilogue(w.alpha.data_ptr(), _ptr(bias), _ptr(post_scale), _ptr(bn_scale),
-                                _ptr(bn_shift), None if residual is None else residual[n0:n1].data_ptr(),
-                                _ptr(prelu), int(bool(relu)), eflags,
-                                None if y is None else y[n0:n1].data_ptr(),
-                                None if pk is None else pk.P[n0:n1].data_ptr(),
-                                None if pk is None else pk.M[n0:n1].data_ptr(), _ptr(pack_scale), _ptr(pack_shift),
-                                out_c_offset if out is not None else 0, c_total if out is not None else 0,
-                                _ptr(sign_thresholds),
-                                *((sa.P[n0:n1].data_ptr(), sw.wbits.data_ptr(), sw.alpha.data_ptr(), sbn_a.data_ptr(),
-                                   sbn_b.data_ptr(), sa.shape[1], sc_in_hw) if shortcut is not None else ()))
+            e = native.Epilogue(
+                alpha=w.alpha.data_ptr(), bias=_ptr(bias), post_scale=_ptr(post_scale), bn_scale=_ptr(bn_scale),
+                bn_shift=_ptr(bn_shift), residual=None if residual is None else residual[n0:n1].data_ptr(),
+                prelu=_ptr(prelu), relu=int(bool(relu)), flags=eflags, out_f32=None if y is None else y[n0:n1].data_ptr(),
+                out_P=None if pk is None else pk.P[n0:n1].data_ptr(), out_M=None if pk is None else pk.M[n0:n1].data_ptr(),
+                pack_scale=_ptr(pack_scale), pack_shift=_ptr(pack_shift),
+                out_c_offset=out_c_offset if out is not None else 0, out_c_total=c_total if out is not None else 0,
+                sign_thresholds=_ptr(sign_thresholds))
+            if shortcut is not None:
+                e.sc_P, e.sc_wbits, e.sc_alpha = sa.P[n0:n1].data_ptr(), sw.wbits.data_ptr(), sw.alpha.data_ptr()
+                e.sc_bn_scale, e.sc_bn_shift, e.sc_C, e.sc_in_hw = sbn_a.data_ptr(), sbn_b.data_ptr(), sa.shape[1], sc_in_hw
             yield dd, e, n0, n1
 
     # mirrors the kernel's rule for leaving the M plane at zero
@@ -1205,6 +1226,21 @@ def _fused_launches(a: PackedAct, w: PackedWeight, what: str, *, bias=None, post
     nonneg = bool(pack_relu) or (bool(relu) and prelu is None and pack_scale is None
                                  and (not late or pack_before_residual))
     return y, pk, nonneg, launches()
+
+
+def _run_fused(symbol: str, a: PackedAct, w: PackedWeight, weight_ptrs: tuple, what: str, **kw):
+    """The launches of the fused convolution ``symbol`` for the wrapper ``what``: ``_fused_launches``, then per launch
+    ``symbol(descriptor, planes of a, *weight_ptrs, epilogue, stream)``, and the ``nonneg`` mark on the output planes."""
+    fn = getattr(native.require(), symbol)
+    y, pk, nonneg, launches = _fused_launches(a, w, what, **kw)
+    dev = a.P.device
+    with torch.cuda.device(dev):
+        for dd, e, n0, n1 in launches:
+            native.check(fn(ctypes.byref(dd), a.P[n0:n1].data_ptr(), a.M[n0:n1].data_ptr(), *weight_ptrs, ctypes.byref(e),
+                            _stream(dev)), symbol)
+    if pk is not None:
+        pk.nonneg = nonneg
+    return y, pk
 
 
 def bconv2d_fused(a: PackedAct, w: PackedWeight, **kw):
@@ -1224,18 +1260,7 @@ def bconv2d_fused(a: PackedAct, w: PackedWeight, **kw):
     preallocated ``[N, C_total, Ho, Wo]`` tensor (``torch.cat`` in place); ``residual`` then has
     ``C_total`` channels too.  The remaining keyword arguments are the pre-activation switches of
     ``BNN_HIP_EPI_*`` (include/bnn_hip.h); ``throughput``: ``BNN_HIP_FLAG_THROUGHPUT`` (several batches in flight)."""
-    lib = native.require()
-    y, pk, nonneg, launches = _fused_launches(a, w, "bconv2d_fused", **kw)
-    dev = a.P.device
-    with torch.cuda.device(dev):
-        for dd, e, n0, n1 in launches:
-            native.check(lib.bnn_hip_bconv2d_fused(ctypes.byref(dd), a.P[n0:n1].data_ptr(), a.M[n0:n1].data_ptr(),
-                                                   w.wbits.data_ptr(), w.wnz.data_ptr(),
-                                                   ctypes.byref(e), _stream(dev)),
-                         "bnn_hip_bconv2d_fused")
-    if pk is not None:
-        pk.nonneg = nonneg
-    return y, pk
+    return _run_fused("bnn_hip_bconv2d_fused", a, w, (w.wbits.data_ptr(), w.wnz.data_ptr()), "bconv2d_fused", **kw)
 
 
 def pack_weight_i8(w: PackedWeight) -> Optional[torch.Tensor]:
@@ -1270,26 +1295,20 @@ def bconv2d_mfma_supported(a_shape, w: PackedWeight, *, nonneg: bool = False, bi
     d = _desc(tuple(a_shape), w.shape, stride, padding, dilation, native.FLAG_ACT_NONNEG if nonneg else 0)
     p = 0x10000   # never dereferenced
     on = lambda v: p if v else None
-    e = native.Epilogue(p, on(bias), on(post_scale), on(bn), on(bn), on(residual), on(prelu), int(bool(relu)), epi_flags,
-                        on(out_f32), on(out_packed), on(out_packed), on(pack_affine), on(pack_affine), 0, out_c_total,
-                        on(sign_thresholds), *((p, p, p, p, p, 64, 0) if shortcut else ()))
+    e = native.Epilogue(alpha=p, bias=on(bias), post_scale=on(post_scale), bn_scale=on(bn), bn_shift=on(bn),
+                        residual=on(residual), prelu=on(prelu), relu=int(bool(relu)), flags=epi_flags, out_f32=on(out_f32),
+                        out_P=on(out_packed), out_M=on(out_packed), pack_scale=on(pack_affine), pack_shift=on(pack_affine),
+                        out_c_total=out_c_total, sign_thresholds=on(sign_thresholds), sc_P=on(shortcut),
+                        sc_wbits=on(shortcut), sc_alpha=on(shortcut), sc_bn_scale=on(shortcut), sc_bn_shift=on(shortcut),
+                        sc_C=64 if shortcut else 0)
     return bool(lib.bnn_hip_bconv2d_mfma_supported(ctypes.byref(d), ctypes.byref(e)))
 
 
 def bconv2d_mfma_fused(a: PackedAct, w: PackedWeight, w8: torch.Tensor, **kw):
     """``bconv2d_fused`` with the dot on ``v_mfma_i32_16x16x64_i8`` (``bnn_hip_bconv2d_mfma_fused``): same arguments, same
     bits.  ``w8 = pack_weight_i8(w)``.  Raises where ``bconv2d_mfma_supported`` says no."""
-    lib = native.require()
-    y, pk, nonneg, launches = _fused_launches(a, w, "bconv2d_mfma_fused", **kw)
-    dev = a.P.device
-    with torch.cuda.device(dev):
-        for dd, e, n0, n1 in launches:
-            native.check(lib.bnn_hip_bconv2d_mfma_fused(ctypes.byref(dd), a.P[n0:n1].data_ptr(), a.M[n0:n1].data_ptr(),
-                                                        w8.data_ptr(), ctypes.byref(e), _stream(dev)),
-                         "bnn_hip_bconv2d_mfma_fused")
-    if pk is not None:
-        pk.nonneg = nonneg
-    return y, pk
+    w8 = _opaque(w8, native.require().bnn_hip_weight_i8_bytes(*w.shape), "w8", torch.int8)
+    return _run_fused("bnn_hip_bconv2d_mfma_fused", a, w, (w8.data_ptr(),), "bconv2d_mfma_fused", **kw)
 
 
 def pack_shortcut_weight_i8(sw: PackedWeight) -> Optional[torch.Tensor]:
@@ -1326,8 +1345,8 @@ def bconv2d_mfma_fold_supported(a_shape, w: PackedWeight, sc_channels: int, *, n
     d = _desc(tuple(a_shape), w.shape, stride, padding, dilation, flags)
     p = 0x10000   # never dereferenced
     hw = 0 if unpooled_hw is None else (int(unpooled_hw[0]) << 16) | int(unpooled_hw[1])
-    e = native.Epilogue(p, None, None, p, p, None, None, 1, 0, p, p, p, None, None, 0, 0, None,
-                        p, None, p, p, p, int(sc_channels), hw)
+    e = native.Epilogue(alpha=p, bn_scale=p, bn_shift=p, relu=1, out_f32=p, out_P=p, out_M=p, sc_P=p, sc_alpha=p,
+                        sc_bn_scale=p, sc_bn_shift=p, sc_C=int(sc_channels), sc_in_hw=hw)
     return bool(lib.bnn_hip_bconv2d_mfma_fold_supported(ctypes.byref(d), ctypes.byref(e)))
 
 
@@ -1338,17 +1357,10 @@ def bconv2d_mfma_fold_fused(a: PackedAct, w: PackedWeight, w8: torch.Tensor, sc_
     lib = native.require()
     if kw.get("shortcut") is None:
         raise native.NativeError("bnn_amd: bconv2d_mfma_fold_fused needs shortcut=(PackedAct, PackedWeight, bn_a, bn_b)")
-    y, pk, nonneg, launches = _fused_launches(a, w, "bconv2d_mfma_fold_fused", **kw)
-    dev = a.P.device
-    with torch.cuda.device(dev):
-        for dd, e, n0, n1 in launches:
-            native.check(lib.bnn_hip_bconv2d_mfma_fold_fused(ctypes.byref(dd), a.P[n0:n1].data_ptr(),
-                                                             a.M[n0:n1].data_ptr(), w8.data_ptr(), sc_w8.data_ptr(),
-                                                             ctypes.byref(e), _stream(dev)),
-                         "bnn_hip_bconv2d_mfma_fold_fused")
-    if pk is not None:
-        pk.nonneg = nonneg
-    return y, pk
+    w8 = _opaque(w8, lib.bnn_hip_weight_i8_bytes(*w.shape), "w8", torch.int8)
+    sc_w8 = _opaque(sc_w8, lib.bnn_hip_shortcut_weight_i8_bytes(*kw["shortcut"][1].shape[:2]), "sc_w8", torch.int8)
+    return _run_fused("bnn_hip_bconv2d_mfma_fold_fused", a, w, (w8.data_ptr(), sc_w8.data_ptr()),
+                      "bconv2d_mfma_fold_fused", **kw)
 
 
 def bconv2d_route(a: PackedAct, w: PackedWeight, *, fused: bool = True, raw_dot: bool = False, **kw) -> dict:
@@ -1475,9 +1487,7 @@ def hblock_forward(a: PackedAct, pack: HBlockPack, residual: torch.Tensor, out_p
     N, c_in, H, W = a.shape
     if not a.nonneg or c_in != pack.c_in:
         raise native.NativeError("bnn_amd: hblock_forward needs non-negative input planes of the block's width")
-    residual = _require_cuda_f32(residual, "residual")
-    if tuple(residual.shape) != (N, pack.planes, H, W):
-        raise native.NativeError(f"bnn_amd: residual shape {tuple(residual.shape)} != block output")
+    residual = _shaped(residual, (N, pack.planes, H, W), "residual", "residual shape {got} != block output")
     if out_packed and not pack.has_next:
         raise native.NativeError("bnn_amd: this HBlockPack holds no next-block BatchNorm")
     dev = a.P.device
@@ -1573,9 +1583,10 @@ def hblock_pool_forward(a: PackedAct, pack: HBlockPack, residual: torch.Tensor, 
     N, c_in, H, W = a.shape
     if not a.nonneg or c_in != pack.c_in or c_in != pack.planes:
         raise native.NativeError("bnn_amd: hblock_pool_forward needs non-negative input planes of a width-preserving block")
-    residual = _require_cuda_f32(residual, "residual")
-    if tuple(residual.shape) != (N, pack.planes, H, W) or H % 2 or W % 2:
-        raise native.NativeError(f"bnn_amd: residual shape {tuple(residual.shape)} != block output (even height and width)")
+    wrong = "residual shape {got} != block output (even height and width)"
+    residual = _shaped(residual, (N, pack.planes, H, W), "residual", wrong)
+    if H % 2 or W % 2:
+        raise native.NativeError("bnn_amd: " + wrong.format(got=tuple(residual.shape)))
     if (pool_consts.dtype != torch.float32 or pool_consts.numel() != 8 * pack.planes or not pool_consts.is_contiguous()
             or pool_consts.device != a.P.device):
         raise native.NativeError("bnn_amd: pool_consts must be the buffer of hblock_pool_consts")
@@ -1678,6 +1689,7 @@ def sconv2d(x: torch.Tensor, packed: SconvWeight, bias=None, post_scale=None, st
     bias = _per_channel(bias, O, "bias")
     post_scale = _per_channel(post_scale, O, "post_scale")
     lib = native.require()
+    _opaque(packed.data, lib.bnn_hip_sconv2d_weight_pack_bytes(O, C, k), "packed weight", torch.uint8)
     N, _, H, W = x.shape
     with torch.cuda.device(x.device):
         y = torch.empty((N, O, (H - 1) // st[0] + 1, (W - 1) // st[0] + 1), dtype=torch.float32, device=x.device)
@@ -1729,9 +1741,7 @@ class SavedAct:
 
 def pack_act_ste(x: torch.Tensor) -> SavedAct:
     """``bnn_hip_pack_act_ste_f32``: one pass over ``x`` -> the three bit planes of ``SavedAct``."""
-    x = _require_cuda_f32(x, "activation")
-    if x.dim() != 4:
-        raise native.NativeError(f"bnn_amd: pack_act_ste expects NCHW, got shape {tuple(x.shape)}")
+    x = _nchw(x, "activation", "pack_act_ste")
     lib = native.require()
     N, C, H, W = x.shape
     with torch.cuda.device(x.device):
@@ -1745,9 +1755,7 @@ def pack_act_ste(x: torch.Tensor) -> SavedAct:
 
 def _ste_planes(x: torch.Tensor, what: str):
     """What the three-plane producers share: the fp32 NCHW check of ``x`` and empty ``P`` / ``M`` / ``T``."""
-    x = _require_cuda_f32(x, "activation")
-    if x.dim() != 4:
-        raise native.NativeError(f"bnn_amd: {what} expects NCHW, got shape {tuple(x.shape)}")
+    x = _nchw(x, "activation", what)
     N, C, H, W = x.shape
     a = empty_packed(N, C, H, W, x.device)
     return x, SavedAct(a, torch.empty_like(a.P), (N, C, H, W))
@@ -1818,21 +1826,17 @@ def bconv_grad_input(g: torch.Tensor, x, packed: torch.Tensor, alpha: torch.Tens
     input, or its ``SavedAct`` (the mask plane is all this kernel needs of it) — same bits either way."""
     g = _require_cuda_f32(g, "grad_output")
     lib = native.require()
-    if isinstance(x, SavedAct):
-        N, O, C, H, W = _grad_shapes(g, x, stride)
-        with torch.cuda.device(g.device):
-            gx = torch.empty((N, C, H, W), dtype=torch.float32, device=g.device)
-            native.check(lib.bnn_hip_bconv_grad_input_packed_f32(
-                g.data_ptr(), alpha.data_ptr(), packed.data_ptr(), x.T.data_ptr(), gx.data_ptr(), N, O, C, H, W, ksize,
-                stride, _stream(g.device)), "bnn_hip_bconv_grad_input_packed_f32")
-        return gx
-    x = _require_cuda_f32(x, "input")
+    saved = isinstance(x, SavedAct)
+    symbol = "bnn_hip_bconv_grad_input_packed_f32" if saved else "bnn_hip_bconv_grad_input_f32"
+    if not saved:
+        x = _require_cuda_f32(x, "input")
     N, O, C, H, W = _grad_shapes(g, x, stride)
+    alpha = _per_channel(alpha, O, "alpha")
+    packed = _opaque(packed, lib.bnn_hip_grad_weight_pack_bytes(O, C, ksize), "packed weight", torch.uint8)
     with torch.cuda.device(g.device):
-        gx = torch.empty_like(x)
-        native.check(lib.bnn_hip_bconv_grad_input_f32(g.data_ptr(), alpha.data_ptr(), packed.data_ptr(),
-                                                      x.data_ptr(), gx.data_ptr(), N, O, C, H, W, ksize, stride,
-                                                      _stream(g.device)), "bnn_hip_bconv_grad_input_f32")
+        gx = torch.empty((N, C, H, W), dtype=torch.float32, device=g.device)
+        native.check(getattr(lib, symbol)(g.data_ptr(), alpha.data_ptr(), packed.data_ptr(), (x.T if saved else x).data_ptr(),
+                                          gx.data_ptr(), N, O, C, H, W, ksize, stride, _stream(g.device)), symbol)
     return gx
 
 
@@ -2022,9 +2026,7 @@ def blinear_direct(x: torch.Tensor, w: PackedWeight, bias: Optional[torch.Tensor
         out = torch.empty((M, O), dtype=torch.float32, device=dev)
         sv = _linear_planes(M, F, dev) if want_planes else None
         dtype = _act_dtype(x)
-        step = _linear_rows(M, F, O)
-        for m0 in range(0, M, step):
-            m1 = min(M, m0 + step)
+        for m0, m1 in _split(M, _linear_rows(M, F, O)):
             pl = [None, None, None] if sv is None else [t[m0:m1].data_ptr() for t in (sv.sign.P, sv.sign.M, sv.T)]
             native.check(lib.bnn_hip_blinear_direct(
                 m1 - m0, F, O, x2[m0:m1].data_ptr(), dtype, w.wbits.data_ptr(), w.wnz.data_ptr(), int(w.has_zero),
@@ -2054,9 +2056,7 @@ def blinear_grad_input(g: torch.Tensor, saved: "SavedAct", w: PackedWeight) -> t
     lib = native.require()
     with torch.cuda.device(g.device):
         gx = torch.empty((M, F), dtype=torch.float32, device=g.device)
-        step = _linear_rows(M, F, O)
-        for m0 in range(0, M, step):
-            m1 = min(M, m0 + step)
+        for m0, m1 in _split(M, _linear_rows(M, F, O)):
             native.check(lib.bnn_hip_blinear_grad_input_f32(
                 g[m0:m1].data_ptr(), w.alpha.data_ptr(), w.wbits.data_ptr(), w.wnz.data_ptr(), saved.T[m0:m1].data_ptr(),
                 gx[m0:m1].data_ptr(), m1 - m0, O, F, _stream(g.device)), "bnn_hip_blinear_grad_input_f32")
@@ -2084,8 +2084,7 @@ def blinear_grad_weight(g: torch.Tensor, saved: "SavedAct", reduce: bool = True,
     step = _linear_rows(M, F, O) if splits is None else M      # (a caller's split is one launch: the entry point judges it)
     parts = []
     with torch.cuda.device(g.device):
-        for m0 in range(0, M, step):
-            m1 = min(M, m0 + step)
+        for m0, m1 in _split(M, step):
             sp = blinear_grad_weight_splits(m1 - m0, O, F) if splits is None else int(splits)
             if sp < 1 or sp > m1 - m0:                 # (before `part` is sized by it)
                 native.check(native.ERR_INVALID_ARG, "bnn_hip_blinear_grad_weight_f32")
@@ -2122,6 +2121,7 @@ def slinear(x: torch.Tensor, packed: SconvWeight, bias=None, post_scale=None, wa
     bias = _per_channel(bias, O, "bias")
     post_scale = _per_channel(post_scale, O, "post_scale")
     lib = native.require()
+    _opaque(packed.data, lib.bnn_hip_sconv2d_weight_pack_bytes(O, F, 1), "packed weight", torch.uint8)
     lead = tuple(x.shape[:-1])
     x2 = x.reshape(-1, F)
     M = x2.shape[0]
@@ -2129,9 +2129,7 @@ def slinear(x: torch.Tensor, packed: SconvWeight, bias=None, post_scale=None, wa
     with torch.cuda.device(dev):
         out = torch.empty((M, O), dtype=torch.float32, device=dev)
         sv = _linear_planes(M, F, dev) if want_planes else None
-        step = _linear_rows(M, F, O)
-        for m0 in range(0, M, step):
-            m1 = min(M, m0 + step)
+        for m0, m1 in _split(M, _linear_rows(M, F, O)):
             pl = [None, None, None] if sv is None else [t[m0:m1].data_ptr() for t in (sv.sign.P, sv.sign.M, sv.T)]
             native.check(lib.bnn_hip_slinear_f32(m1 - m0, F, O, x2[m0:m1].data_ptr(), packed.data.data_ptr(), _ptr(bias),
                                                  _ptr(post_scale), out[m0:m1].data_ptr(), *pl, _stream(dev)),
@@ -2144,16 +2142,14 @@ def ste_mask_(gx: torch.Tensor, saved: "SavedAct") -> torch.Tensor:
     """The hard-tanh straight-through mask in place (``bnn_hip_ste_mask_f32``): ``gx[m, f]`` becomes ``+0.0`` where the
     ``T`` plane of ``saved`` (shape ``(M, F, 1, 1)``) says ``|x| >= 1``.  ``gx``: contiguous fp32 with ``M * F`` elements."""
     M, F = int(saved.shape[0]), int(saved.shape[1])
-    if (not gx.is_cuda or gx.dtype != torch.float32 or not gx.is_contiguous() or tuple(saved.shape[2:]) != (1, 1)
-            or gx.numel() != M * F or gx.dim() < 1 or gx.shape[-1] != F):
-        raise native.NativeError(f"bnn_amd: ste_mask_ expects a contiguous fp32 HIP tensor [..., {F}] of {M} rows, got "
-                                 f"{tuple(gx.shape)} {gx.dtype} on {gx.device}")
+    wrong = f"ste_mask_ expects a contiguous fp32 HIP tensor [..., {F}] of {M} rows, got {tuple(gx.shape)} {gx.dtype} on " \
+            f"{gx.device}"
+    if tuple(saved.shape[2:]) != (1, 1) or gx.dim() < 1 or gx.shape[-1] != F:
+        raise native.NativeError("bnn_amd: " + wrong)
     lib = native.require()
-    g2 = gx.view(M, F)
+    g2 = _written(gx, M * F, "gx", wrong).view(M, F)
     with torch.cuda.device(gx.device):
-        step = _linear_rows(M, F, 1)
-        for m0 in range(0, M, step):
-            m1 = min(M, m0 + step)
+        for m0, m1 in _split(M, _linear_rows(M, F, 1)):
             native.check(lib.bnn_hip_ste_mask_f32(g2[m0:m1].data_ptr(), saved.T[m0:m1].data_ptr(), m1 - m0, F,
                                                   _stream(gx.device)), "bnn_hip_ste_mask_f32")
     return gx
@@ -2194,17 +2190,12 @@ def bn_act(x: torch.Tensor, bn_scale: torch.Tensor, bn_shift: torch.Tensor, relu
     """``relu?(fma(x, scale[c], shift[c]) (+ residual))``: eval-mode BatchNorm with folded constants + the residual add +
     ReLU of a residual block as ONE launch (include/bnn_hip.h: bnn_hip_bn_act_f32) — the tail of the per-layer path; the
     same float operations as the fused convolution epilogue."""
-    x = _require_cuda_f32(x, "BatchNorm input")
-    if x.dim() != 4:
-        raise native.NativeError(f"bnn_amd: bn_act expects NCHW, got shape {tuple(x.shape)}")
+    x = _nchw(x, "BatchNorm input", "bn_act")
     lib = native.require()
     N, C, H, W = x.shape
     bn_scale = _per_channel(bn_scale, C, "bn_scale")
     bn_shift = _per_channel(bn_shift, C, "bn_shift")
-    if residual is not None:
-        residual = _require_cuda_f32(residual, "residual")
-        if residual.shape != x.shape:
-            raise native.NativeError("bnn_amd: residual shape differs from the BatchNorm input's")
+    residual = _shaped(residual, x.shape, "residual", "residual shape differs from the BatchNorm input's")
     with torch.cuda.device(x.device):
         y = torch.empty_like(x)
         if x.numel():
@@ -2222,20 +2213,28 @@ def _bn_train_buffers(lib, x: torch.Tensor):
             torch.empty(int(lib.bnn_hip_bn_train_workspace_bytes(N, C, H * W)), dtype=torch.uint8, device=x.device))
 
 
+def _bn_train_affine(C: int, gamma, beta, running_mean, running_var):
+    """The operands of a training BatchNorm going forward, each optional: ``gamma`` / ``beta`` per channel (read), the
+    running statistics (written in place)."""
+    return (_per_channel(gamma, C, "BatchNorm weight"), _per_channel(beta, C, "BatchNorm bias"),
+            _written(running_mean, C, "running_mean"), _written(running_var, C, "running_var"))
+
+
+def _bn_train_saved(C: int, mean, invstd, gamma):
+    """The operands of a training BatchNorm going back: the forward's saved statistics and the optional ``gamma``."""
+    return _shaped(mean, (C,), "mean"), _shaped(invstd, (C,), "invstd"), _per_channel(gamma, C, "BatchNorm weight")
+
+
 def bn_train_forward(x: torch.Tensor, gamma, beta, running_mean, running_var, momentum: float, eps: float,
                      relu: bool = False, residual: Optional[torch.Tensor] = None):
     """``relu?(batch_norm(x, training=True) (+ residual))`` in three launches (csrc/bn_train.hip).  Updates the running
     statistics in place (unbiased variance, momentum) like ``torch.nn.BatchNorm2d`` in training mode.  Returns
     ``(y, save_mean, save_invstd)``."""
-    x = _require_cuda_f32(x, "BatchNorm input")
-    if x.dim() != 4:
-        raise native.NativeError(f"bnn_amd: bn_train_forward expects NCHW, got shape {tuple(x.shape)}")
+    x = _nchw(x, "BatchNorm input", "bn_train_forward")
     lib = native.require()
     N, C, H, W = x.shape
-    if residual is not None:
-        residual = _require_cuda_f32(residual, "residual")
-        if residual.shape != x.shape:
-            raise native.NativeError("bnn_amd: residual shape differs from the BatchNorm input's")
+    gamma, beta, running_mean, running_var = _bn_train_affine(C, gamma, beta, running_mean, running_var)
+    residual = _shaped(residual, x.shape, "residual", "residual shape differs from the BatchNorm input's")
     with torch.cuda.device(x.device):
         y = torch.empty_like(x)
         mean, invstd, ws = _bn_train_buffers(lib, x)
@@ -2250,9 +2249,11 @@ def bn_train_backward(gy: torch.Tensor, y: Optional[torch.Tensor], x: torch.Tens
                       invstd: torch.Tensor, gamma, want_dres: bool = False):
     """Backward of ``bn_train_forward``: ``(dx, dgamma, dbeta, dres | None)``.  ``y``: the forward's output when a ReLU
     was fused (its mask), else None."""
-    gy = _require_cuda_f32(gy, "grad_output")
+    x = _nchw(x, "BatchNorm input", "bn_train_backward")
+    gy, y = _shaped(gy, x.shape, "grad_output"), _shaped(y, x.shape, "BatchNorm output")
     lib = native.require()
     N, C, H, W = x.shape
+    mean, invstd, gamma = _bn_train_saved(C, mean, invstd, gamma)
     with torch.cuda.device(x.device):
         dx = torch.empty_like(x)
         dres = torch.empty_like(x) if want_dres else None
@@ -2264,27 +2265,30 @@ def bn_train_backward(gy: torch.Tensor, y: Optional[torch.Tensor], x: torch.Tens
     return dx, dgamma, dbeta, dres
 
 
+def _bn_train_pack(symbol: str, x: torch.Tensor, planes, gamma, beta, running_mean, running_var, momentum, eps):
+    """The launch of ``bn_train_pack_ste`` and ``bn_train_pack_ste_s2``: the batch statistics of ``x``, the running
+    statistics' update, and ``planes`` ``(P, M, T)`` filled -> ``(save_mean, save_invstd, scale, shift)``."""
+    N, C, H, W = x.shape
+    gamma, beta, running_mean, running_var = _bn_train_affine(C, gamma, beta, running_mean, running_var)
+    lib = native.require()
+    with torch.cuda.device(x.device):
+        mean, invstd, ws = _bn_train_buffers(lib, x)
+        scale, shift = torch.empty_like(mean), torch.empty_like(mean)
+        native.check(getattr(lib, symbol)(
+            x.data_ptr(), N, C, H, W, _ptr(gamma), _ptr(beta), float(eps), float(momentum), _ptr(running_mean),
+            _ptr(running_var), *(t.data_ptr() for t in planes), mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(),
+            shift.data_ptr(), ws.data_ptr(), _stream(x.device)), symbol)
+    return mean, invstd, scale, shift
+
+
 def bn_train_pack_ste(x: torch.Tensor, gamma, beta, running_mean, running_var, momentum: float, eps: float):
     """``pack_act_ste(batch_norm(x, training=True))`` without writing the normalised tensor
     (``bnn_hip_bn_train_pack_ste_f32``: the statistics kernels of ``bn_train_forward``, then BatchNorm + sign + STE mask
     as three bit planes).  Updates the running statistics like ``bn_train_forward``.  Returns ``(SavedAct, save_mean,
     save_invstd, scale, shift)`` — ``scale`` / ``shift`` are what the planes were made with."""
     x, sv = _ste_planes(x, "bn_train_pack_ste")
-    N, C, H, W = x.shape
-    gamma = _per_channel(gamma, C, "BatchNorm weight")
-    beta = _per_channel(beta, C, "BatchNorm bias")
-    running_mean = _per_channel(running_mean, C, "running_mean")
-    running_var = _per_channel(running_var, C, "running_var")
-    lib = native.require()
-    with torch.cuda.device(x.device):
-        mean, invstd, ws = _bn_train_buffers(lib, x)
-        scale, shift = torch.empty_like(mean), torch.empty_like(mean)
-        native.check(lib.bnn_hip_bn_train_pack_ste_f32(
-            x.data_ptr(), N, C, H, W, _ptr(gamma), _ptr(beta), float(eps), float(momentum), _ptr(running_mean),
-            _ptr(running_var), sv.sign.P.data_ptr(), sv.sign.M.data_ptr(), sv.T.data_ptr(), mean.data_ptr(),
-            invstd.data_ptr(), scale.data_ptr(), shift.data_ptr(), ws.data_ptr(), _stream(x.device)),
-            "bnn_hip_bn_train_pack_ste_f32")
-    return sv, mean, invstd, scale, shift
+    return (sv, *_bn_train_pack("bnn_hip_bn_train_pack_ste_f32", x, (sv.sign.P, sv.sign.M, sv.T), gamma, beta, running_mean,
+                                running_var, momentum, eps))
 
 
 def bn_train_backward_add(gy: torch.Tensor, x: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor, gamma,
@@ -2296,12 +2300,10 @@ def bn_train_backward_add(gy: torch.Tensor, x: torch.Tensor, mean: torch.Tensor,
     if x.dim() != 4 or gy.shape != x.shape:
         raise native.NativeError(f"bnn_amd: bn_train_backward_add: grad_output {tuple(gy.shape)} does not belong to the "
                                  f"NCHW input {tuple(x.shape)}")
-    if addend is not None:
-        addend = _require_cuda_f32(addend, "addend")
-        if addend.shape != x.shape:
-            raise native.NativeError("bnn_amd: addend shape differs from the BatchNorm input's")
+    addend = _shaped(addend, x.shape, "addend", "addend shape differs from the BatchNorm input's")
     lib = native.require()
     N, C, H, W = x.shape
+    mean, invstd, gamma = _bn_train_saved(C, mean, invstd, gamma)
     with torch.cuda.device(x.device):
         dx = torch.empty_like(x)
         dgamma, dbeta, ws = _bn_train_buffers(lib, x)
@@ -2316,21 +2318,9 @@ def bn_train_pack_ste_s2(x: torch.Tensor, gamma, beta, running_mean, running_var
     """``bn_train_pack_ste`` for ``FactorizedReduce`` (``bnn_hip_bn_train_pack_ste_s2_f32``): the same statistics over all
     of ``x`` and the same running-statistics update, then the planes of ``bn_act_pack_ste_s2``.  Returns ``((SavedAct,
     SavedAct), save_mean, save_invstd, scale, shift)``."""
-    x, (P, M, T), phases = _ste_planes_s2(x, "bn_train_pack_ste_s2")
-    N, C, H, W = x.shape
-    gamma = _per_channel(gamma, C, "BatchNorm weight")
-    beta = _per_channel(beta, C, "BatchNorm bias")
-    running_mean = _per_channel(running_mean, C, "running_mean")
-    running_var = _per_channel(running_var, C, "running_var")
-    lib = native.require()
-    with torch.cuda.device(x.device):
-        mean, invstd, ws = _bn_train_buffers(lib, x)
-        scale, shift = torch.empty_like(mean), torch.empty_like(mean)
-        native.check(lib.bnn_hip_bn_train_pack_ste_s2_f32(
-            x.data_ptr(), N, C, H, W, _ptr(gamma), _ptr(beta), float(eps), float(momentum), _ptr(running_mean),
-            _ptr(running_var), P.data_ptr(), M.data_ptr(), T.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-            scale.data_ptr(), shift.data_ptr(), ws.data_ptr(), _stream(x.device)), "bnn_hip_bn_train_pack_ste_s2_f32")
-    return phases, mean, invstd, scale, shift
+    x, planes, phases = _ste_planes_s2(x, "bn_train_pack_ste_s2")
+    return (phases, *_bn_train_pack("bnn_hip_bn_train_pack_ste_s2_f32", x, planes, gamma, beta, running_mean, running_var,
+                                    momentum, eps))
 
 
 def bn_train_backward_s2(g0: torch.Tensor, g1: torch.Tensor, x: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor,
@@ -2349,6 +2339,7 @@ def bn_train_backward_s2(g0: torch.Tensor, g1: torch.Tensor, x: torch.Tensor, me
                                  f"belong to the NCHW input {tuple(x.shape)}")
     if x.data_ptr() % 8:        # (a view one float into its storage: the kernels move rows as float2)
         x = x.clone()
+    mean, invstd, gamma = _bn_train_saved(C, mean, invstd, gamma)
     lib = native.require()
     with torch.cuda.device(x.device):
         dx = torch.empty_like(x)
@@ -2372,11 +2363,9 @@ def prelu_shuffle_backward(gy: torch.Tensor, z: torch.Tensor, slope: torch.Tenso
                                  f"NCHW pre-activation {tuple(z.shape)}")
     N, O, H, W = z.shape
     slope = _require_cuda_f32(slope.detach(), "PReLU slope").reshape(-1)
-    shuffle_groups = int(shuffle_groups)
     if slope.numel() not in (1, O):
         raise native.NativeError(f"bnn_amd: PReLU slope must have 1 or {O} entries, got {slope.numel()}")
-    if shuffle_groups < 1 or O % shuffle_groups:
-        raise native.NativeError(f"bnn_amd: shuffle_groups={shuffle_groups} does not divide the {O} channels")
+    shuffle_groups = _shuffle_groups(shuffle_groups, O, "channels")
     lib = native.require()
     with torch.cuda.device(z.device):
         gz = z if inplace else torch.empty_like(z)
@@ -2393,9 +2382,10 @@ def prelu_shuffle_backward(gy: torch.Tensor, z: torch.Tensor, slope: torch.Tenso
 def bn_relu_maxpool_train_forward(x: torch.Tensor, gamma, beta, running_mean, running_var, momentum: float, eps: float):
     """``maxpool3x3/2/1(relu(batch_norm(x, training=True)))`` without writing the normalised tensor (csrc/bn_train.hip):
     returns ``(pooled, code uint8, save_mean, save_invstd)``; ``code`` = which of the 9 window positions won."""
-    x = _require_cuda_f32(x, "BatchNorm input")
+    x = _nchw(x, "BatchNorm input", "bn_relu_maxpool_train_forward")
     lib = native.require()
     N, C, H, W = x.shape
+    gamma, beta, running_mean, running_var = _bn_train_affine(C, gamma, beta, running_mean, running_var)
     hp, wp = _half_hw(H, W)
     with torch.cuda.device(x.device):
         p = torch.empty((N, C, hp, wp), dtype=torch.float32, device=x.device)
@@ -2411,9 +2401,13 @@ def bn_relu_maxpool_train_forward(x: torch.Tensor, gamma, beta, running_mean, ru
 def bn_relu_maxpool_train_backward(gy: torch.Tensor, p: torch.Tensor, code: torch.Tensor, x: torch.Tensor,
                                    mean: torch.Tensor, invstd: torch.Tensor, gamma):
     """Backward of ``bn_relu_maxpool_train_forward``: ``(dx, dgamma, dbeta)``."""
-    gy = _require_cuda_f32(gy, "grad_output")
+    x = _nchw(x, "BatchNorm input", "bn_relu_maxpool_train_backward")
     lib = native.require()
     N, C, H, W = x.shape
+    pooled = (N, C) + _half_hw(H, W)
+    gy, p = _shaped(gy, pooled, "grad_output"), _shaped(p, pooled, "pooled output")
+    code = _shaped(code, pooled, "code", dtype=torch.uint8)
+    mean, invstd, gamma = _bn_train_saved(C, mean, invstd, gamma)
     with torch.cuda.device(x.device):
         dx = torch.empty_like(x)
         dgamma, dbeta, ws = _bn_train_buffers(lib, x)
