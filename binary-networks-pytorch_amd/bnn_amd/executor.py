@@ -116,13 +116,16 @@ class _Conv:
     mfma: dict = field(default_factory=dict)   # (geometry, epilogue) -> this launch runs on the int8 matrix cores
     sc_w8: Optional[torch.Tensor] = None  # a block's shortcut convolution: int8 pack of its 1x1 weight (built with the plan)
     mfma_fold: dict = field(default_factory=dict)   # geometry -> this launch, with its shortcut folded in, does too
+    w4: Optional[torch.Tensor] = None    # FP4 MFMA pack of the weight (the F4 form of the same kernel), built with the plan
+    f4: dict = field(default_factory=dict)   # the keys of ``mfma`` / ``mfma_fold`` -> that matrix-core launch is the FP4 form
 
-    def _on_matrix_cores(self, act: hipops.PackedAct, residual, out_f32: bool, out_packed: bool, thr, epi) -> bool:
+    def _on_matrix_cores(self, act: hipops.PackedAct, residual, out_f32: bool, out_packed: bool, thr, epi):
         """The admission of one launch to the MFMA convolution: the table of ``fastpath`` (shapes that measured faster)
         and the kernel's own query, asked once per geometry.  The pre-activation switches and the folded shortcut
-        (``epi``) stay on the popcount kernels."""
+        (``epi``) stay on the popcount kernels.  Returns (on the matrix cores, in the FP4 form): an admitted launch asks
+        ``fastpath.mfma_f4_admitted`` and ``bnn_hip_bconv2d_mfma4_supported`` the same way."""
         if self.w8 is None or epi:
-            return False
+            return False, False
         key = (tuple(act.shape), act.nonneg, residual is not None, out_f32, out_packed, thr is not None)
         ok = self.mfma.get(key)
         if ok is None:
@@ -135,13 +138,21 @@ class _Conv:
                     post_scale=self.plan.scale is not None, bn=self.bn_scale is not None, residual=residual is not None,
                     prelu=self.prelu is not None, relu=self.relu, out_f32=out_f32, out_packed=out_packed,
                     stride=lay.stride, padding=lay.padding, dilation=lay.dilation, sign_thresholds=thr is not None))
-        return ok
+            self.f4[key] = bool(
+                ok and self.w4 is not None
+                and fastpath.mfma_f4_admitted((act.shape[1], lay.out_channels, act.shape[2], stride, False))
+                and hipops.bconv2d_mfma4_supported(
+                    act.shape, self.weight, nonneg=act.nonneg, bias=lay.bias is not None,
+                    post_scale=self.plan.scale is not None, bn=self.bn_scale is not None, residual=residual is not None,
+                    prelu=self.prelu is not None, relu=self.relu, out_f32=out_f32, out_packed=out_packed,
+                    stride=lay.stride, padding=lay.padding, dilation=lay.dilation, sign_thresholds=thr is not None))
+        return ok, ok and self.f4[key]
 
-    def _fold_on_matrix_cores(self, act: hipops.PackedAct, out_f32: bool, out_packed: bool, epi, sc_w8) -> bool:
+    def _fold_on_matrix_cores(self, act: hipops.PackedAct, out_f32: bool, out_packed: bool, epi, sc_w8):
         """The same for a launch with the block's shortcut folded in (``epi`` is exactly the shortcut): the table of
         ``fastpath.MFMA_FOLD_SHAPES`` and ``bnn_hip_bconv2d_mfma_fold_supported``, asked once per geometry."""
         if self.w8 is None or sc_w8 is None or set(epi) != {"shortcut"} or not (out_f32 and out_packed):
-            return False
+            return False, False
         sa = epi["shortcut"][0]
         key = (tuple(act.shape), act.nonneg, tuple(sa.shape), self.throughput)
         ok = self.mfma_fold.get(key)
@@ -157,7 +168,14 @@ class _Conv:
                     act.shape, self.weight, sa.shape[1], nonneg=act.nonneg, stride=lay.stride, padding=lay.padding,
                     dilation=lay.dilation, unpooled_hw=None if pooled else tuple(sa.shape[2:]),
                     throughput=self.throughput))
-        return ok
+            self.f4[key] = bool(
+                ok and self.w4 is not None
+                and fastpath.mfma_f4_admitted((act.shape[1], lay.out_channels, act.shape[2], sa.shape[1]))
+                and hipops.bconv2d_mfma4_fold_supported(
+                    act.shape, self.weight, sa.shape[1], nonneg=act.nonneg, stride=lay.stride, padding=lay.padding,
+                    dilation=lay.dilation, unpooled_hw=None if pooled else tuple(sa.shape[2:]),
+                    throughput=self.throughput))
+        return ok, ok and self.f4[key]
 
     def run(self, act: hipops.PackedAct, *, residual=None, out_f32: bool, out_packed: bool, shortcut_w8=None, **epi):
         """``epi``: the pre-activation switches of ``hipops.bconv2d_fused`` (late residual, pack affine, ...);
@@ -171,10 +189,17 @@ class _Conv:
                     bn_shift=self.bn_shift, residual=residual, prelu=self.prelu, relu=self.relu,
                     out_f32=out_f32, out_packed=out_packed, stride=lay.stride, padding=lay.padding,
                     dilation=lay.dilation, throughput=self.throughput, sign_thresholds=thr, **epi)
-        if self._on_matrix_cores(act, residual, out_f32, out_packed, thr, epi):
+        on, f4 = self._on_matrix_cores(act, residual, out_f32, out_packed, thr, epi)
+        if on:
+            if f4:
+                return hipops.bconv2d_mfma4_fused(act, self.weight, self.w4, **args)
             return hipops.bconv2d_mfma_fused(act, self.weight, self.w8, **args)
-        if residual is None and self._fold_on_matrix_cores(act, out_f32, out_packed, epi, shortcut_w8):
-            return hipops.bconv2d_mfma_fold_fused(act, self.weight, self.w8, shortcut_w8, **args)
+        if residual is None:
+            on, f4 = self._fold_on_matrix_cores(act, out_f32, out_packed, epi, shortcut_w8)
+            if on and f4:
+                return hipops.bconv2d_mfma4_fold_fused(act, self.weight, self.w4, shortcut_w8, **args)
+            if on:
+                return hipops.bconv2d_mfma_fold_fused(act, self.weight, self.w8, shortcut_w8, **args)
         return hipops.bconv2d_fused(act, self.weight, **args)
 
 
@@ -374,8 +399,10 @@ class FusedResNet(nn.Module):
             thr = hipops.sign_thresholds(pw, scale, shift)
         # the int8 form of a 3x3 weight, when the switch admits any launch at all (None: no such form for this weight)
         w8 = hipops.pack_weight_i8(pw) if fastpath.MFMA_CONV != "0" and tuple(pw.shape[2:]) == (3, 3) else None
+        # and its FP4 form (None as well where C is no multiple of 128)
+        w4 = hipops.pack_weight_f4(pw) if w8 is not None and fastpath.MFMA_F4 != "0" else None
         return _Conv(conv, plan, pw, scale, shift, relu, prelu, self._names.get(id(conv), ""), self.throughput_mode, thr,
-                     w8)
+                     w8, w4=w4)
 
     @staticmethod
     def _sign_through(act: nn.Module):

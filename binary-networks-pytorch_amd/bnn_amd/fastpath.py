@@ -122,6 +122,34 @@ def mfma_fold_admitted(C: int, O: int, H: int, sc_C: int) -> bool:
     return MFMA_FOLD == "all" or (C, O, H, sc_C) in MFMA_FOLD_SHAPES
 
 
+# A launch already on the matrix cores (admitted above) on the FP4 form of the same kernel (csrc/bconv_mfma.hip, F4:
+# v_mfma_f32_16x16x128_f8f6f4 with E2M1 operands — half the matrix cycles, operand bytes and k-steps, the same bits;
+# bnn_hip_bconv2d_mfma4_fused / _fold_fused) instead of the int8 form.
+# BNN_AMD_MFMA_F4: "1" (default) — the launches listed in MFMA_F4_SHAPES; "0" — none: exactly the launches of before;
+# "all" — every matrix-core launch bnn_hip_bconv2d_mfma4_supported / _fold_supported takes (C % 128 == 0).
+MFMA_F4 = os.environ.get("BNN_AMD_MFMA_F4", "1")
+# The dense key (C, O, H of the input, stride, False) or the fold key (C, O, H of the input, channels of the shortcut
+# input) -> (int8 MFMA us, FP4 us) in the same kind of trace (profiles/mfma_f4_kernel_roofline.md).  A shape is listed
+# only where both FP4 traces lie below both int8 traces by more than the launch's trace-to-trace gap.  (Means of two
+# traces each; a dense key that two launches share holds their sums.)
+MFMA_F4_SHAPES = {
+    (128, 128, 28, 64): (61.6, 53.1),             # layer2.0.conv2 + shortcut
+    (128, 128, 28, 1, False): (86.6, 71.9),       # layer2.1.conv1 39.1 -> 31.1, layer2.1.conv2 47.4 -> 40.8
+    (128, 256, 28, 2, False): (26.8, 21.4),       # layer3.0.conv1
+    (256, 256, 14, 128): (48.8, 39.1),            # layer3.0.conv2 + shortcut
+    (256, 256, 14, 1, False): (73.7, 52.5),       # layer3.1.conv1 34.3 -> 23.9, layer3.1.conv2 39.4 -> 28.7
+    (256, 512, 14, 2, False): (24.4, 17.2),       # layer4.0.conv1
+    (512, 512, 7, 256): (44.5, 32.7),             # layer4.0.conv2 + shortcut
+    (512, 512, 7, 1, False): (74.1, 50.6),        # layer4.1.conv1 32.7 -> 21.3, layer4.1.conv2 41.4 -> 29.3
+}
+
+
+def mfma_f4_admitted(key: tuple) -> bool:
+    if MFMA_F4 == "0":
+        return False
+    return MFMA_F4 == "all" or tuple(key) in MFMA_F4_SHAPES
+
+
 # The one-launch FactorizedConv kernel (csrc/fconv.hip) against the per-layer path of the same module, batch 256 on
 # MI355X (tools/bench_fconv.py -> profiles/fconv_bench.jsonl).  The admission rule, in one place: a shape (C, H, W,
 # stride) whose fused executor measured SLOWER than the per-layer path is listed here with its (per-layer us, fused us)

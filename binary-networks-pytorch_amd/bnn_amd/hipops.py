@@ -1263,23 +1263,36 @@ def bconv2d_fused(a: PackedAct, w: PackedWeight, **kw):
     return _run_fused("bnn_hip_bconv2d_fused", a, w, (w.wbits.data_ptr(), w.wnz.data_ptr()), "bconv2d_fused", **kw)
 
 
-def pack_weight_i8(w: PackedWeight) -> Optional[torch.Tensor]:
-    """The int8 MFMA-fragment form of a packed 3x3 weight (``bnn_hip_pack_weight_i8``, layout: include/bnn_hip.h), or
-    ``None`` where there is none (not 3x3, C or O no multiple of 64, a grouped pack).  One launch; ``w.alpha`` is used
-    unchanged beside it."""
+def _pack_weight_mfma(w: PackedWeight, kind: str) -> Optional[torch.Tensor]:
+    """``bnn_hip_pack_weight_<kind>`` (kind = "i8" or "f4"), or ``None`` where ``bnn_hip_weight_<kind>_bytes`` is 0."""
     lib = native.require()
     if w.windowed or w.groups != 1:
         return None
     O, C, KH, KW = w.shape
-    nbytes = int(lib.bnn_hip_weight_i8_bytes(O, C, KH, KW))
+    nbytes = int(getattr(lib, f"bnn_hip_weight_{kind}_bytes")(O, C, KH, KW))
     if nbytes == 0:
         return None
     dev = w.wbits.device
     with torch.cuda.device(dev):
-        w8 = torch.empty(nbytes, dtype=torch.int8, device=dev)
-        native.check(lib.bnn_hip_pack_weight_i8(w.wbits.data_ptr(), w.wnz.data_ptr(), O, C, KH, KW, w8.data_ptr(),
-                                                _stream(dev)), "bnn_hip_pack_weight_i8")
-    return w8
+        pack = torch.empty(nbytes, dtype=torch.int8, device=dev)
+        native.check(getattr(lib, f"bnn_hip_pack_weight_{kind}")(w.wbits.data_ptr(), w.wnz.data_ptr(), O, C, KH, KW,
+                                                                 pack.data_ptr(), _stream(dev)),
+                     f"bnn_hip_pack_weight_{kind}")
+    return pack
+
+
+def pack_weight_i8(w: PackedWeight) -> Optional[torch.Tensor]:
+    """The int8 MFMA-fragment form of a packed 3x3 weight (``bnn_hip_pack_weight_i8``, layout: include/bnn_hip.h), or
+    ``None`` where there is none (not 3x3, C or O no multiple of 64, a grouped pack).  One launch; ``w.alpha`` is used
+    unchanged beside it."""
+    return _pack_weight_mfma(w, "i8")
+
+
+def pack_weight_f4(w: PackedWeight) -> Optional[torch.Tensor]:
+    """The FP4 (E2M1) MFMA-fragment form of a packed 3x3 weight (``bnn_hip_pack_weight_f4``, layout: include/bnn_hip.h):
+    half the bytes of ``pack_weight_i8``, as an int8 tensor of nibble pairs.  ``None`` where there is none (as
+    ``pack_weight_i8``, or C no multiple of 128)."""
+    return _pack_weight_mfma(w, "f4")
 
 
 def bconv2d_mfma_supported(a_shape, w: PackedWeight, *, nonneg: bool = False, bias=False, post_scale=False, bn=False,
@@ -1289,6 +1302,11 @@ def bconv2d_mfma_supported(a_shape, w: PackedWeight, *, nonneg: bool = False, bi
     """Whether ``bconv2d_mfma_fused`` takes a launch of this geometry and epilogue (``bnn_hip_bconv2d_mfma_supported``:
     host only, nothing is launched or allocated).  The epilogue is given by what it contains (truth values), not by
     tensors: an aligned stand-in pointer takes the place of each operand that is present."""
+    return _mfma_supported("bnn_hip_bconv2d_mfma_supported", **locals())
+
+
+def _mfma_supported(_symbol, a_shape, w, nonneg, bias, post_scale, bn, residual, prelu, relu, out_f32, out_packed, stride,
+                    padding, dilation, sign_thresholds, shortcut, epi_flags, pack_affine, out_c_total) -> bool:
     lib = native.require()
     if w.windowed or w.groups != 1:
         return False
@@ -1301,7 +1319,16 @@ def bconv2d_mfma_supported(a_shape, w: PackedWeight, *, nonneg: bool = False, bi
                         out_c_total=out_c_total, sign_thresholds=on(sign_thresholds), sc_P=on(shortcut),
                         sc_wbits=on(shortcut), sc_alpha=on(shortcut), sc_bn_scale=on(shortcut), sc_bn_shift=on(shortcut),
                         sc_C=64 if shortcut else 0)
-    return bool(lib.bnn_hip_bconv2d_mfma_supported(ctypes.byref(d), ctypes.byref(e)))
+    return bool(getattr(lib, _symbol)(ctypes.byref(d), ctypes.byref(e)))
+
+
+def bconv2d_mfma4_supported(a_shape, w: PackedWeight, *, nonneg: bool = False, bias=False, post_scale=False, bn=False,
+                            residual=False, prelu=False, relu=False, out_f32=True, out_packed=False, stride=1, padding=0,
+                            dilation=1, sign_thresholds=False, shortcut=False, epi_flags: int = 0, pack_affine=False,
+                            out_c_total: int = 0) -> bool:
+    """``bconv2d_mfma_supported`` for the FP4 form (``bnn_hip_bconv2d_mfma4_supported``): the same rule plus whole
+    128-channel groups."""
+    return _mfma_supported("bnn_hip_bconv2d_mfma4_supported", **locals())
 
 
 def bconv2d_mfma_fused(a: PackedAct, w: PackedWeight, w8: torch.Tensor, **kw):
@@ -1309,6 +1336,14 @@ def bconv2d_mfma_fused(a: PackedAct, w: PackedWeight, w8: torch.Tensor, **kw):
     bits.  ``w8 = pack_weight_i8(w)``.  Raises where ``bconv2d_mfma_supported`` says no."""
     w8 = _opaque(w8, native.require().bnn_hip_weight_i8_bytes(*w.shape), "w8", torch.int8)
     return _run_fused("bnn_hip_bconv2d_mfma_fused", a, w, (w8.data_ptr(),), "bconv2d_mfma_fused", **kw)
+
+
+def bconv2d_mfma4_fused(a: PackedAct, w: PackedWeight, w4: torch.Tensor, **kw):
+    """``bconv2d_mfma_fused`` with the dot on ``v_mfma_f32_16x16x128_f8f6f4`` and FP4 operands
+    (``bnn_hip_bconv2d_mfma4_fused``): same arguments, same bits.  ``w4 = pack_weight_f4(w)``.  Raises where
+    ``bconv2d_mfma4_supported`` says no."""
+    w4 = _opaque(w4, native.require().bnn_hip_weight_f4_bytes(*w.shape), "w4", torch.int8)
+    return _run_fused("bnn_hip_bconv2d_mfma4_fused", a, w, (w4.data_ptr(),), "bconv2d_mfma4_fused", **kw)
 
 
 def pack_shortcut_weight_i8(sw: PackedWeight) -> Optional[torch.Tensor]:
@@ -1337,6 +1372,10 @@ def bconv2d_mfma_fold_supported(a_shape, w: PackedWeight, sc_channels: int, *, n
     """Whether ``bconv2d_mfma_fold_fused`` takes this convolution with a folded shortcut of ``sc_channels`` input channels
     (``bnn_hip_bconv2d_mfma_fold_supported``: host only).  The epilogue is the one the fold belongs to: BatchNorm +
     shortcut + ReLU -> fp32 + sign planes.  ``unpooled_hw``: the shortcut plane comes un-pooled at this size."""
+    return _mfma_fold_supported("bnn_hip_bconv2d_mfma_fold_supported", **locals())
+
+
+def _mfma_fold_supported(_symbol, a_shape, w, sc_channels, nonneg, stride, padding, dilation, unpooled_hw, throughput) -> bool:
     lib = native.require()
     if w.windowed or w.groups != 1:
         return False
@@ -1347,20 +1386,39 @@ def bconv2d_mfma_fold_supported(a_shape, w: PackedWeight, sc_channels: int, *, n
     hw = 0 if unpooled_hw is None else (int(unpooled_hw[0]) << 16) | int(unpooled_hw[1])
     e = native.Epilogue(alpha=p, bn_scale=p, bn_shift=p, relu=1, out_f32=p, out_P=p, out_M=p, sc_P=p, sc_alpha=p,
                         sc_bn_scale=p, sc_bn_shift=p, sc_C=int(sc_channels), sc_in_hw=hw)
-    return bool(lib.bnn_hip_bconv2d_mfma_fold_supported(ctypes.byref(d), ctypes.byref(e)))
+    return bool(getattr(lib, _symbol)(ctypes.byref(d), ctypes.byref(e)))
+
+
+def bconv2d_mfma4_fold_supported(a_shape, w: PackedWeight, sc_channels: int, *, nonneg: bool = True, stride=1, padding=1,
+                                 dilation=1, unpooled_hw: Optional[Tuple[int, int]] = None, throughput: bool = False) -> bool:
+    """``bconv2d_mfma_fold_supported`` for the FP4 form (``bnn_hip_bconv2d_mfma4_fold_supported``): the same rule plus
+    whole 128-channel groups."""
+    return _mfma_fold_supported("bnn_hip_bconv2d_mfma4_fold_supported", **locals())
+
+
+def _mfma_fold_fused(kind: str, what: str, a: PackedAct, w: PackedWeight, pack: torch.Tensor, sc_w8: torch.Tensor, **kw):
+    lib = native.require()
+    if kw.get("shortcut") is None:
+        raise native.NativeError(f"bnn_amd: {what} needs shortcut=(PackedAct, PackedWeight, bn_a, bn_b)")
+    name = "w8" if kind == "i8" else "w4"
+    pack = _opaque(pack, getattr(lib, f"bnn_hip_weight_{kind}_bytes")(*w.shape), name, torch.int8)
+    sc_w8 = _opaque(sc_w8, lib.bnn_hip_shortcut_weight_i8_bytes(*kw["shortcut"][1].shape[:2]), "sc_w8", torch.int8)
+    symbol = "bnn_hip_bconv2d_mfma_fold_fused" if kind == "i8" else "bnn_hip_bconv2d_mfma4_fold_fused"
+    return _run_fused(symbol, a, w, (pack.data_ptr(), sc_w8.data_ptr()), what, **kw)
 
 
 def bconv2d_mfma_fold_fused(a: PackedAct, w: PackedWeight, w8: torch.Tensor, sc_w8: torch.Tensor, **kw):
     """``bconv2d_fused(a, w, ..., shortcut=(sa, sw, bn_a, bn_b))`` with both dots on ``v_mfma_i32_16x16x64_i8``
     (``bnn_hip_bconv2d_mfma_fold_fused``): same arguments, same bits.  ``w8 = pack_weight_i8(w)``,
     ``sc_w8 = pack_shortcut_weight_i8(sw)``.  Raises where ``bconv2d_mfma_fold_supported`` says no."""
-    lib = native.require()
-    if kw.get("shortcut") is None:
-        raise native.NativeError("bnn_amd: bconv2d_mfma_fold_fused needs shortcut=(PackedAct, PackedWeight, bn_a, bn_b)")
-    w8 = _opaque(w8, lib.bnn_hip_weight_i8_bytes(*w.shape), "w8", torch.int8)
-    sc_w8 = _opaque(sc_w8, lib.bnn_hip_shortcut_weight_i8_bytes(*kw["shortcut"][1].shape[:2]), "sc_w8", torch.int8)
-    return _run_fused("bnn_hip_bconv2d_mfma_fold_fused", a, w, (w8.data_ptr(), sc_w8.data_ptr()),
-                      "bconv2d_mfma_fold_fused", **kw)
+    return _mfma_fold_fused("i8", "bconv2d_mfma_fold_fused", a, w, w8, sc_w8, **kw)
+
+
+def bconv2d_mfma4_fold_fused(a: PackedAct, w: PackedWeight, w4: torch.Tensor, sc_w8: torch.Tensor, **kw):
+    """``bconv2d_mfma_fold_fused`` with the 3x3 dot on FP4 operands (``bnn_hip_bconv2d_mfma4_fold_fused``; the shortcut's
+    1x1 dot stays on the int8 instruction): same arguments, same bits.  ``w4 = pack_weight_f4(w)``,
+    ``sc_w8 = pack_shortcut_weight_i8(sw)``.  Raises where ``bconv2d_mfma4_fold_supported`` says no."""
+    return _mfma_fold_fused("f4", "bconv2d_mfma4_fold_fused", a, w, w4, sc_w8, **kw)
 
 
 def bconv2d_route(a: PackedAct, w: PackedWeight, *, fused: bool = True, raw_dot: bool = False, **kw) -> dict:

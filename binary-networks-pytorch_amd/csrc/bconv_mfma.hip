@@ -21,13 +21,27 @@
 // l & 15 of A / B and that D has column l & 15 and rows 4 (l >> 4) + r in register r.
 // Epilogue: the accumulators go through LDS, 32 channels at a time, to lane = pixel; from there on it is the popcount
 // kernels' straight-line epilogue (coalesced NCHW stores, one 32-channel plane word per lane).
+//
+// FP4 form (F4, C % 128 == 0): the same kernel on v_mfma_f32_16x16x128_f8f6f4 with E2M1 operands (cbsz:4 blgp:4, no
+// scales): -1, 0 and +1 are exact in E2M1 (0xA, 0x0, 0x2), every product is in {-1, 0, +1} and every partial sum is an
+// integer of magnitude <= 9 C <= 2^20 < 2^24, so every fp32 addition is exact in any order and the accumulator converted
+// to int is the same dot.  A k-step is one tap of a 128-channel group = two consecutive 64-channel plane groups: the same
+// 16 bytes per lane and operand as the int8 form at half the k-steps.  The LDS patch stays 64 bytes per pixel, now 128
+// nibbles (P bit -> 0x2, M bit -> 0xA); nibble e of lane l is channel 32 (l >> 4) + e of the group in BOTH operands, so
+// lane group l >> 4 reads the 16 bytes that come from 32-bit plane word l >> 4 of the group.  Tile choice, pipeline and
+// epilogue are the int8 form's; the folded shortcut's 1x1 prologue stays on the int8 instruction with int32
+// accumulators of its own, dead before the main loop.
 #include "bconv_core.h"
+
+#include <type_traits>
 
 namespace bnn {
 
 namespace {
 
 using i32x4 = __attribute__((ext_vector_type(4))) int;
+using i32x8 = __attribute__((ext_vector_type(8))) int;
+using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int kMfmaThreads = 256;
 constexpr int kAccStride = 68;  // int32 per channel row of the transpose buffer: 4 rows apart = 16 banks apart
@@ -72,6 +86,37 @@ __device__ __forceinline__ uint32_t expand4(uint32_t pw, uint32_t mw, int sh, bo
   return p | (spread4(mw, sh) * 0xFFu);  // bytes of 0 / 1 times 255: no carry between bytes
 }
 
+// FP4: 8 bits -> 8 nibbles, bit i in nibble i.  The bits go two to a byte, and each byte looks its two nibbles up in the
+// four bytes of `lut` (v_perm_b32): 0x22200200 turns a set bit into 0x2, 0x88800800 into 0x8.
+__device__ __forceinline__ uint32_t nibbles8(uint32_t word, int sh, uint32_t lut) {
+  uint32_t t = (word >> sh) & 0xFFu;
+  t = (t | (t << 12)) & 0x000F000Fu;
+  t = (t | (t << 6)) & 0x03030303u;
+  return __builtin_amdgcn_perm(lut, lut, t);
+}
+// P or M set -> 0x2, M set -> 0x8 on top of it: +1 = 0x2, -1 = 0xA (P and M are exclusive)
+__device__ __forceinline__ uint32_t expand8_f4(uint32_t pw, uint32_t mw, int sh, bool nn) {
+  if (nn) return nibbles8(pw, sh, 0x22200200u);
+  return nibbles8(pw | mw, sh, 0x22200200u) | nibbles8(mw, sh, 0x88800800u);
+}
+
+// One k-step of one 16 x 16 tile.  FP4: the operands are the low four of the instruction's eight dwords.
+template <bool F4, class Acc>
+__device__ __forceinline__ Acc mma_step(const i32x4 a, const i32x4 b, const Acc c) {
+  if constexpr (F4) {
+    const i32x8 a8{a[0], a[1], a[2], a[3], 0, 0, 0, 0}, b8{b[0], b[1], b[2], b[3], 0, 0, 0, 0};
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a8, b8, c, 4, 4, 0, 0, 0, 0);
+  } else {
+    return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0);
+  }
+}
+
+template <bool First, class A, class B>
+__device__ __forceinline__ auto& pick(A& a, B& b) {
+  if constexpr (First) return a;
+  else return b;
+}
+
 // linear input index of the window centre of output pixel q (monotone in q)
 __device__ __forceinline__ int centre_of(const Geo& g, const MfmaGeo& mg, int q, int* oy, int* ox) {
   const int hw = g.Ho * g.Wo;
@@ -90,7 +135,8 @@ __device__ __forceinline__ int centre_of(const Geo& g, const MfmaGeo& mg, int q,
 // in LDS as int16 in the layout the epilogue reads (lane = pixel, 32 channels = four ds_read_b128), `acc` starts again
 // from zero and the main loop runs unchanged: no register lives across it, and the epilogue gains only the conversion.
 // (The shortcut's pointers travel behind the geometry: the kernel arguments of the plain form keep their places.)
-template <int EP, bool DS = false>
+// F4: the FP4 form (file comment): W8 is then the FP4 pack of bnn_hip_pack_weight_f4 (the shortcut's stays int8).
+template <int EP, bool DS = false, bool F4 = false>
 __global__ __launch_bounds__(kMfmaThreads) void bconv_mfma_kernel(const uint32_t* __restrict__ P,
                                                                   const uint32_t* __restrict__ M,
                                                                   const int8_t* __restrict__ W8, BNN_EPI_PARAMS,
@@ -140,11 +186,12 @@ __global__ __launch_bounds__(kMfmaThreads) void bconv_mfma_kernel(const uint32_t
     okm[pt] = m;
   }
 
-  i32x4 acc[4][4];
+  using acc_t = std::conditional_t<F4, f32x4, i32x4>;
+  acc_t acc[4][4];
 #pragma unroll
   for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
-    for (int pt = 0; pt < 4; ++pt) acc[ct][pt] = i32x4{0, 0, 0, 0};
+    for (int pt = 0; pt < 4; ++pt) acc[ct][pt] = acc_t{0, 0, 0, 0};
 
   if (tid < 4) reinterpret_cast<uint4*>(lds + (size_t)zero_idx * 64)[tid] = uint4{0u, 0u, 0u, 0u};
 
@@ -152,13 +199,15 @@ __global__ __launch_bounds__(kMfmaThreads) void bconv_mfma_kernel(const uint32_t
   const uint2* P2 = reinterpret_cast<const uint2*>(P);
   const uint2* M2 = reinterpret_cast<const uint2*>(M);
   // A fragments of this wave: [o / 64][group][tap][16-channel tile][lane][16 bytes]
-  const int8_t* wbase = W8 + (size_t)(o_wave >> 6) * mg.groups * (9 * 4096) + lane * 16;
+  // (FP4: [o / 64][128-channel group][tap][16-channel tile][lane][16 bytes], the same 4096 bytes per k-step)
+  const int kgroups = F4 ? mg.groups >> 1 : mg.groups;  // groups of the k loop: 128 or 64 channels
+  const int8_t* wbase = W8 + (size_t)(o_wave >> 6) * kgroups * (9 * 4096) + lane * 16;
 
   // Software pipeline.  A fragments: k-step k + 2 (contiguous behind k and k + 1, across groups too) is requested before
   // the MFMAs of k-step k — three register sets in rotation, and nine taps per group bring the rotation back to its
   // start.  B fragments: the next tap's, within a group.  Plane words: the next group's are requested into registers
   // before the current group's MFMAs and expanded into the patch behind them.
-  const int ksteps = mg.groups * 9;
+  const int ksteps = kgroups * 9;
   auto a_load = [&](i32x4 (&dst)[4], int k) {
     const int8_t* src = wbase + (size_t)min(k, ksteps - 1) * 4096;  // (past the end: the last k-step's again, never used)
 #pragma unroll
@@ -172,6 +221,7 @@ __global__ __launch_bounds__(kMfmaThreads) void bconv_mfma_kernel(const uint32_t
   // patch pixels tid, tid + 256, ... (patch_cap <= kPatchSlots * 256: choose_tile)
   unsigned wi0[kPatchSlots];
   uint2 pv[kPatchSlots], mv[kPatchSlots];
+  [[maybe_unused]] uint2 pv1[F4 ? kPatchSlots : 1], mv1[F4 ? kPatchSlots : 1];  // FP4: the second plane group of the 128
 #pragma unroll
   for (int sl = 0; sl < kPatchSlots; ++sl) {
     const int L = l_lo + min(tid + sl * kMfmaThreads, patch_len - 1);
@@ -179,13 +229,26 @@ __global__ __launch_bounds__(kMfmaThreads) void bconv_mfma_kernel(const uint32_t
     wi0[sl] = (unsigned)(n * mg.groups * mg.ihw + (L - n * mg.ihw));  // uint64 words, group 0
     pv[sl] = uint2{0u, 0u};
     mv[sl] = uint2{0u, 0u};
+    if constexpr (F4) {
+      pv1[sl] = uint2{0u, 0u};
+      mv1[sl] = uint2{0u, 0u};
+    }
   }
   auto request = [&](int gi) {
 #pragma unroll
     for (int sl = 0; sl < kPatchSlots; ++sl)
       if (sl * kMfmaThreads < patch_len) {  // (wave-uniform; lanes past the end re-read the last pixel)
-        pv[sl] = P2[wi0[sl] + (unsigned)(gi * mg.ihw)];
-        if (!nn) mv[sl] = M2[wi0[sl] + (unsigned)(gi * mg.ihw)];
+        if constexpr (F4) {  // plane groups 2 gi and 2 gi + 1
+          pv[sl] = P2[wi0[sl] + (unsigned)(2 * gi * mg.ihw)];
+          pv1[sl] = P2[wi0[sl] + (unsigned)((2 * gi + 1) * mg.ihw)];
+          if (!nn) {
+            mv[sl] = M2[wi0[sl] + (unsigned)(2 * gi * mg.ihw)];
+            mv1[sl] = M2[wi0[sl] + (unsigned)((2 * gi + 1) * mg.ihw)];
+          }
+        } else {
+          pv[sl] = P2[wi0[sl] + (unsigned)(gi * mg.ihw)];
+          if (!nn) mv[sl] = M2[wi0[sl] + (unsigned)(gi * mg.ihw)];
+        }
       }
   };
   auto expand = [&]() {
@@ -194,12 +257,21 @@ __global__ __launch_bounds__(kMfmaThreads) void bconv_mfma_kernel(const uint32_t
       const int i = tid + sl * kMfmaThreads;
       if (i < patch_len) {
         uint4* dst = reinterpret_cast<uint4*>(lds + (size_t)i * 64);
+        if constexpr (F4) {  // 16 bytes per 32-bit plane word of the group
+          const uint32_t pw4[4] = {pv[sl].x, pv[sl].y, pv1[sl].x, pv1[sl].y};
+          const uint32_t mw4[4] = {mv[sl].x, mv[sl].y, mv1[sl].x, mv1[sl].y};
 #pragma unroll
-        for (int h = 0; h < 4; ++h) {
-          const uint32_t pw = h < 2 ? pv[sl].x : pv[sl].y, mw = h < 2 ? mv[sl].x : mv[sl].y;
-          const int s0 = 16 * (h & 1);
-          dst[h] = uint4{expand4(pw, mw, s0, nn), expand4(pw, mw, s0 + 4, nn), expand4(pw, mw, s0 + 8, nn),
-                         expand4(pw, mw, s0 + 12, nn)};
+          for (int h = 0; h < 4; ++h)
+            dst[h] = uint4{expand8_f4(pw4[h], mw4[h], 0, nn), expand8_f4(pw4[h], mw4[h], 8, nn),
+                           expand8_f4(pw4[h], mw4[h], 16, nn), expand8_f4(pw4[h], mw4[h], 24, nn)};
+        } else {
+#pragma unroll
+          for (int h = 0; h < 4; ++h) {
+            const uint32_t pw = h < 2 ? pv[sl].x : pv[sl].y, mw = h < 2 ? mv[sl].x : mv[sl].y;
+            const int s0 = 16 * (h & 1);
+            dst[h] = uint4{expand4(pw, mw, s0, nn), expand4(pw, mw, s0 + 4, nn), expand4(pw, mw, s0 + 8, nn),
+                           expand4(pw, mw, s0 + 12, nn)};
+          }
         }
       }
     }
@@ -207,7 +279,15 @@ __global__ __launch_bounds__(kMfmaThreads) void bconv_mfma_kernel(const uint32_t
 
   request(0);
   i32x4 a_buf[3][4];
+  [[maybe_unused]] i32x4 sc_acc[F4 && DS ? 4 : 1][4];  // FP4: the int8 prologue's own accumulators
   if constexpr (DS) {
+    i32x4(&sacc)[4][4] = pick<F4>(sc_acc, acc);
+    if constexpr (F4) {
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+        for (int pt = 0; pt < 4; ++pt) sacc[ct][pt] = i32x4{0, 0, 0, 0};
+    }
     const int sg = g.ds_cw >> 1;  // 64-channel groups of the shortcut input = its k-steps: 1, 2 or 4
     // the shortcut plane words of tile pixel `tid` (threads past the tile hold a clamped copy and write nothing)
     uint2 scw[4];
@@ -275,7 +355,7 @@ __global__ __launch_bounds__(kMfmaThreads) void bconv_mfma_kernel(const uint32_t
         for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
           for (int pt = 0; pt < 4; ++pt)
-            acc[ct][pt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_buf[k % 3][ct], b_sc[pt], acc[ct][pt], 0, 0, 0);
+            sacc[ct][pt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_buf[k % 3][ct], b_sc[pt], sacc[ct][pt], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
       }
     });
@@ -289,18 +369,18 @@ __global__ __launch_bounds__(kMfmaThreads) void bconv_mfma_kernel(const uint32_t
     for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
       for (int pt = 0; pt < 4; ++pt) {
-        const i32x4 v = acc[ct][pt];
+        const i32x4 v = pick<F4>(sc_acc, acc)[ct][pt];
         *reinterpret_cast<uint2*>(park + (16 * pt + lrow) * kParkStride + 16 * ct + 4 * lgrp) =
             uint2{((uint32_t)v[0] & 0xFFFFu) | ((uint32_t)v[1] << 16), ((uint32_t)v[2] & 0xFFFFu) | ((uint32_t)v[3] << 16)};
-        acc[ct][pt] = i32x4{0, 0, 0, 0};
+        acc[ct][pt] = acc_t{0, 0, 0, 0};
       }
   }
 #pragma unroll 1
-  for (int gi = 0; gi < mg.groups; ++gi) {
+  for (int gi = 0; gi < kgroups; ++gi) {
     __syncthreads();  // the previous group's reads of the patch (gi = 0, DS: of the shortcut operand) are done
     expand();
     __syncthreads();
-    if (gi + 1 < mg.groups) request(gi + 1);
+    if (gi + 1 < kgroups) request(gi + 1);
     i32x4 b_cur[4];
 #pragma unroll
     for (int pt = 0; pt < 4; ++pt) b_cur[pt] = b_frag(pt, 0);
@@ -317,7 +397,7 @@ __global__ __launch_bounds__(kMfmaThreads) void bconv_mfma_kernel(const uint32_t
       for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
         for (int pt = 0; pt < 4; ++pt)
-          acc[ct][pt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_buf[t % 3][ct], b_cur[pt], acc[ct][pt], 0, 0, 0);
+          acc[ct][pt] = mma_step<F4>(a_buf[t % 3][ct], b_cur[pt], acc[ct][pt]);
       __builtin_amdgcn_sched_barrier(0);
       if (t < 8) {
 #pragma unroll
@@ -362,7 +442,7 @@ __global__ __launch_bounds__(kMfmaThreads) void bconv_mfma_kernel(const uint32_t
       for (int pt = 0; pt < 4; ++pt)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          tbuf[(16 * c2 + 4 * lgrp + r) * kAccStride + 16 * pt + lrow] = acc[2 * h + c2][pt][r];
+          tbuf[(16 * c2 + 4 * lgrp + r) * kAccStride + 16 * pt + lrow] = (int)acc[2 * h + c2][pt][r];  // (FP4: exact)
     __syncthreads();
     int dot[32];
 #pragma unroll
@@ -404,6 +484,34 @@ __global__ __launch_bounds__(256) void pack_weight_i8_kernel(const uint32_t* __r
   w8[d] = v;
 }
 
+// wbits / wnz -> FP4 (E2M1) A fragments (include/bnn_hip.h: bnn_hip_pack_weight_f4).  One thread per dword = eight
+// consecutive input channels of one output channel and tap: +1 -> 0x2, -1 -> 0xA, a zero weight -> 0x0.
+__global__ __launch_bounds__(256) void pack_weight_f4_kernel(const uint32_t* __restrict__ wbits,
+                                                             const uint32_t* __restrict__ wnz, int O, int cw32, int cwc,
+                                                             uint32_t* __restrict__ w4) {
+  const int groups = cw32 >> 2, nchunk = cw32 / cwc, per_o = 9 * cwc;
+  const size_t total = (size_t)O * groups * 9 * 16;  // dwords
+  const size_t d = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (d >= total) return;
+  const int e8 = (int)(d & 3), lane = (int)((d >> 2) & 63), ct = (int)((d >> 8) & 3);
+  size_t rest = d >> 10;
+  const int t = (int)(rest % 9);
+  rest /= 9;
+  const int gi = (int)(rest % groups), ob64 = (int)(rest / groups);
+  const int o = 64 * ob64 + 16 * ct + (lane & 15);
+  const int c0 = 128 * gi + 32 * (lane >> 4) + 8 * e8;  // eight consecutive input channels, inside one 32-bit word
+  const int cw_abs = c0 >> 5, ch = cw_abs / cwc, cw = cw_abs - ch * cwc;
+  const size_t wi = ((size_t)((o >> 5) * nchunk + ch) * kOCB + (o & 31)) * per_o + t * cwc + cw;
+  const uint32_t b = wbits[wi] >> (c0 & 31), z = wnz[wi] >> (c0 & 31);
+  uint32_t v = 0u;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const uint32_t nib = ((z >> k) & 1u) ? (((b >> k) & 1u) ? 0x2u : 0xAu) : 0u;
+    v |= nib << (4 * k);
+  }
+  w4[d] = v;
+}
+
 // Input pixels between the window centres of the first and the last pixel of any run of `tp` output pixels, at most:
 // (tp - 1) steps of `s`, plus what a change of row and a change of image add beyond such a step.
 long long centre_span(const ConvP& p, int tp) {
@@ -436,9 +544,9 @@ int choose_tile(const ConvP& p, int* patch_cap, size_t park = 0) {
   return 0;
 }
 
-template <int EP>
+template <int EP, bool F4>
 void launch_ep(const ConvP& p, const Geo& g, const MfmaGeo& mg, const void* w8, dim3 grid, size_t ldsb, hipStream_t s) {
-  hipLaunchKernelGGL((bconv_mfma_kernel<EP>), grid, dim3(kMfmaThreads), ldsb, s, p.P, p.M,
+  hipLaunchKernelGGL((bconv_mfma_kernel<EP, false, F4>), grid, dim3(kMfmaThreads), ldsb, s, p.P, p.M,
                      static_cast<const int8_t*>(w8), BNN_EPI_ACTUALS, g, mg, static_cast<const uint32_t*>(nullptr),
                      static_cast<const int8_t*>(nullptr), static_cast<const float*>(nullptr),
                      static_cast<const float*>(nullptr), static_cast<const float*>(nullptr));
@@ -456,6 +564,19 @@ int launch_pack_weight_i8(const uint32_t* wbits, const uint32_t* wnz, const bnn_
   const size_t dwords = (size_t)O * (L.cw32 >> 1) * L.taps * 16;
   hipLaunchKernelGGL(pack_weight_i8_kernel, dim3((unsigned)((dwords + 255) / 256)), dim3(256), 0, s, wbits, wnz, O, L.taps,
                      L.cw32, L.cwc, static_cast<uint32_t*>(w8));
+  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+}
+
+size_t weight_f4_bytes(int O, int C, int KH, int KW) {
+  if (weight_i8_bytes(O, C, KH, KW) == 0 || C % 128 != 0) return 0;
+  return (size_t)O * (size_t)C * 9 / 2;
+}
+
+int launch_pack_weight_f4(const uint32_t* wbits, const uint32_t* wnz, const bnn_hip_wlayout& L, int O, void* w4,
+                          hipStream_t s) {
+  const size_t dwords = (size_t)O * (L.cw32 >> 2) * 9 * 16;
+  hipLaunchKernelGGL(pack_weight_f4_kernel, dim3((unsigned)((dwords + 255) / 256)), dim3(256), 0, s, wbits, wnz, O, L.cw32,
+                     L.cwc, static_cast<uint32_t*>(w4));
   return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
 }
 
@@ -503,6 +624,11 @@ bool mfma_fold_applies(const ConvP& p, int flags) {
   return mfma_dense_rule(p, flags, (size_t)kParkBytes);
 }
 
+// The FP4 forms (bnn_hip_bconv2d_mfma4_supported / _fold_supported): the dense rule, or the fold rule, plus whole
+// 128-channel groups.
+bool mfma4_conv_applies(const ConvP& p, int flags) { return p.C % 128 == 0 && mfma_conv_applies(p, flags); }
+bool mfma4_fold_applies(const ConvP& p, int flags) { return p.C % 128 == 0 && mfma_fold_applies(p, flags); }
+
 namespace {
 MfmaGeo make_mfma_geo(const ConvP& p, int flags, int tp, int cap) {
   MfmaGeo mg;
@@ -518,15 +644,15 @@ MfmaGeo make_mfma_geo(const ConvP& p, int flags, int tp, int cap) {
 }
 }  // namespace
 
-int launch_bconv_mfma_fold(const ConvP& p, int flags, const void* w8, const void* sc_w8, hipStream_t s) {
+int launch_bconv_mfma_fold(const ConvP& p, int flags, const void* w8, const void* sc_w8, hipStream_t s, bool f4) {
   int cap = 0;
   const int tp = choose_tile(p, &cap, (size_t)kParkBytes);
-  if (!mfma_fold_applies(p, flags) || tp == 0) return BNN_HIP_ERR_UNSUPPORTED;
+  if (!(f4 ? mfma4_fold_applies(p, flags) : mfma_fold_applies(p, flags)) || tp == 0) return BNN_HIP_ERR_UNSUPPORTED;
   const Geo g = make_geo(p);
   const MfmaGeo mg = make_mfma_geo(p, flags, tp, cap);
   const dim3 grid((unsigned)((p.npix + tp - 1) / tp), (unsigned)(p.O / (tp == 256 ? 64 : 128)));
   const size_t ldsb = lds_bytes_of(cap) + (size_t)kParkBytes;  // above the 64 KB default
-  auto kern = bconv_mfma_kernel<EP_OUT, true>;
+  auto kern = f4 ? bconv_mfma_kernel<EP_OUT, true, true> : bconv_mfma_kernel<EP_OUT, true>;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                           kMaxDynamicLds) != hipSuccess)
     return BNN_HIP_ERR_LAUNCH;
@@ -535,23 +661,31 @@ int launch_bconv_mfma_fold(const ConvP& p, int flags, const void* w8, const void
   return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
 }
 
-int launch_bconv_mfma(const ConvP& p, int flags, const void* w8, hipStream_t s) {
+namespace {
+template <bool F4>
+void launch_dense(const ConvP& p, const Geo& g, const MfmaGeo& mg, const void* w8, dim3 grid, size_t ldsb, hipStream_t s) {
+  const int f = g.flags;
+  const bool fused = (f & (EF_BN | EF_RES | EF_RELU | EF_PACK)) != 0;
+  if (f == kFlagsMid && p.thr) launch_ep<EP_MIDT, F4>(p, g, mg, w8, grid, ldsb, s);
+  else if (f == kFlagsMid) launch_ep<EP_MID, F4>(p, g, mg, w8, grid, ldsb, s);
+  else if (f == kFlagsOut) launch_ep<EP_OUT, F4>(p, g, mg, w8, grid, ldsb, s);
+  else if (f == kFlagsOutP) launch_ep<EP_OUTP, F4>(p, g, mg, w8, grid, ldsb, s);
+  else if (f == kFlagsLast) launch_ep<EP_LAST, F4>(p, g, mg, w8, grid, ldsb, s);
+  else if (fused) launch_ep<EP_RUNTIME, F4>(p, g, mg, w8, grid, ldsb, s);
+  else launch_ep<EP_PLAIN, F4>(p, g, mg, w8, grid, ldsb, s);
+}
+}  // namespace
+
+int launch_bconv_mfma(const ConvP& p, int flags, const void* w8, hipStream_t s, bool f4) {
   int cap = 0;
   const int tp = choose_tile(p, &cap);
-  if (!mfma_conv_applies(p, flags) || tp == 0) return BNN_HIP_ERR_UNSUPPORTED;
+  if (!(f4 ? mfma4_conv_applies(p, flags) : mfma_conv_applies(p, flags)) || tp == 0) return BNN_HIP_ERR_UNSUPPORTED;
   const Geo g = make_geo(p);
   const MfmaGeo mg = make_mfma_geo(p, flags, tp, cap);
   const dim3 grid((unsigned)((p.npix + tp - 1) / tp), (unsigned)(p.O / (tp == 256 ? 64 : 128)));
   const size_t ldsb = lds_bytes_of(cap);
-  const int f = g.flags;
-  const bool fused = (f & (EF_BN | EF_RES | EF_RELU | EF_PACK)) != 0;
-  if (f == kFlagsMid && p.thr) launch_ep<EP_MIDT>(p, g, mg, w8, grid, ldsb, s);
-  else if (f == kFlagsMid) launch_ep<EP_MID>(p, g, mg, w8, grid, ldsb, s);
-  else if (f == kFlagsOut) launch_ep<EP_OUT>(p, g, mg, w8, grid, ldsb, s);
-  else if (f == kFlagsOutP) launch_ep<EP_OUTP>(p, g, mg, w8, grid, ldsb, s);
-  else if (f == kFlagsLast) launch_ep<EP_LAST>(p, g, mg, w8, grid, ldsb, s);
-  else if (fused) launch_ep<EP_RUNTIME>(p, g, mg, w8, grid, ldsb, s);
-  else launch_ep<EP_PLAIN>(p, g, mg, w8, grid, ldsb, s);
+  if (f4) launch_dense<true>(p, g, mg, w8, grid, ldsb, s);
+  else launch_dense<false>(p, g, mg, w8, grid, ldsb, s);
   return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
 }
 

@@ -212,12 +212,18 @@ size_t weight_i8_bytes(int O, int C, int KH, int KW);
 int launch_pack_weight_i8(const uint32_t* wbits, const uint32_t* wnz, const bnn_hip_wlayout& L, int O, void* w8,
                           hipStream_t s);
 bool mfma_conv_applies(const ConvP& p, int flags);
-int launch_bconv_mfma(const ConvP& p, int flags, const void* w8, hipStream_t s);
+// f4: the FP4 form (v_mfma_f32_16x16x128_f8f6f4, C % 128 == 0), `w8` then the pack of launch_pack_weight_f4
+int launch_bconv_mfma(const ConvP& p, int flags, const void* w8, hipStream_t s, bool f4);
+size_t weight_f4_bytes(int O, int C, int KH, int KW);
+int launch_pack_weight_f4(const uint32_t* wbits, const uint32_t* wnz, const bnn_hip_wlayout& L, int O, void* w4,
+                          hipStream_t s);
+bool mfma4_conv_applies(const ConvP& p, int flags);
+bool mfma4_fold_applies(const ConvP& p, int flags);
 // the same with the shortcut convolution folded in (p.ds_*; p.ds_W is not read: the 1x1 weight comes as its int8 pack)
 size_t shortcut_weight_i8_bytes(int O, int C);
 int launch_pack_shortcut_weight_i8(const uint32_t* wbits, int O, int C, void* w8, hipStream_t s);
 bool mfma_fold_applies(const ConvP& p, int flags);
-int launch_bconv_mfma_fold(const ConvP& p, int flags, const void* w8, const void* sc_w8, hipStream_t s);
+int launch_bconv_mfma_fold(const ConvP& p, int flags, const void* w8, const void* sc_w8, hipStream_t s, bool f4);
 // grouped / depthwise convolutions: pack_weight.hip (the windowed layout, L from bnn_hip_grouped_weight_layout) and
 // bconv_grouped.hip (p.C = all input channels, p.W / p.Z in that layout with S words per tap)
 int launch_pack_weight_grouped(const float* w, int O, int Cg, int groups, int center, int compute_alpha,

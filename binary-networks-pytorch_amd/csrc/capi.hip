@@ -1099,18 +1099,20 @@ int bnn_hip_pack_weight_i8(const uint32_t* wbits, const uint32_t* wnz, int O, in
   return bnn::launch_pack_weight_i8(wbits, wnz, L, O, w8, static_cast<hipStream_t>(stream));
 }
 
-int bnn_hip_bconv2d_mfma_supported(const bnn_hip_conv_desc* d, const bnn_hip_epilogue* e) {
+// The int8 and the FP4 (f4) entry points share their validation: only the admission rule and the kernel differ.
+namespace {
+int mfma_supported(const bnn_hip_conv_desc* d, const bnn_hip_epilogue* e, bool f4) {
   alignas(16) static const uint64_t operand[2] = {0, 0};  // stands in for the packed operands (never read)
   bnn::ConvP p = empty_convp();
   if (epilogue_convp(e, &p) != BNN_HIP_OK) return 0;
   const uint32_t* const w = reinterpret_cast<const uint32_t*>(operand);
   if (check_conv(d, operand, operand, w, w, &p) != BNN_HIP_OK) return 0;
   if (p.out && !aligned(p.out, 4)) return 0;
-  return bnn::mfma_conv_applies(p, d->flags) ? 1 : 0;
+  return (f4 ? bnn::mfma4_conv_applies(p, d->flags) : bnn::mfma_conv_applies(p, d->flags)) ? 1 : 0;
 }
 
-int bnn_hip_bconv2d_mfma_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const void* w8,
-                               const bnn_hip_epilogue* e, void* stream) {
+int mfma_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const void* w8,
+               const bnn_hip_epilogue* e, void* stream, bool f4) {
   bnn::ConvP p = empty_convp();
   int st = epilogue_convp(e, &p);
   if (st != BNN_HIP_OK) return st;
@@ -1119,10 +1121,45 @@ int bnn_hip_bconv2d_mfma_fused(const bnn_hip_conv_desc* d, const uint64_t* P, co
   st = check_conv(d, P, M, static_cast<const uint32_t*>(w8), static_cast<const uint32_t*>(w8), &p);
   if (st != BNN_HIP_OK) return st;
   if (p.out && !aligned(p.out, 4)) return BNN_HIP_ERR_INVALID_ARG;
-  if (!bnn::mfma_conv_applies(p, d->flags)) return BNN_HIP_ERR_UNSUPPORTED;
+  if (!(f4 ? bnn::mfma4_conv_applies(p, d->flags) : bnn::mfma_conv_applies(p, d->flags))) return BNN_HIP_ERR_UNSUPPORTED;
   g_launches.fetch_add(1, std::memory_order_relaxed);
   BNN_RANGE();
-  return bnn::launch_bconv_mfma(p, d->flags, w8, static_cast<hipStream_t>(stream));
+  return bnn::launch_bconv_mfma(p, d->flags, w8, static_cast<hipStream_t>(stream), f4);
+}
+}  // namespace
+
+int bnn_hip_bconv2d_mfma_supported(const bnn_hip_conv_desc* d, const bnn_hip_epilogue* e) {
+  return mfma_supported(d, e, false);
+}
+
+int bnn_hip_bconv2d_mfma_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const void* w8,
+                               const bnn_hip_epilogue* e, void* stream) {
+  return mfma_fused(d, P, M, w8, e, stream, false);
+}
+
+// ---- the FP4 form (bnn_hip_pack_weight_f4's pack in place of the int8 one) ----
+size_t bnn_hip_weight_f4_bytes(int O, int C, int KH, int KW) { return bnn::weight_f4_bytes(O, C, KH, KW); }
+
+int bnn_hip_pack_weight_f4(const uint32_t* wbits, const uint32_t* wnz, int O, int C, int KH, int KW, void* w4,
+                           void* stream) {
+  if (!wbits || !wnz || !w4) return BNN_HIP_ERR_INVALID_ARG;
+  bnn_hip_wlayout L;
+  const int st = bnn_hip_weight_layout(O, C, KH, KW, &L);
+  if (st != BNN_HIP_OK) return st;
+  if (bnn::weight_f4_bytes(O, C, KH, KW) == 0) return BNN_HIP_ERR_UNSUPPORTED;
+  if (!aligned(wbits, 16) || !aligned(wnz, 16) || !aligned(w4, 16)) return BNN_HIP_ERR_INVALID_ARG;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_pack_weight_f4(wbits, wnz, L, O, w4, static_cast<hipStream_t>(stream));
+}
+
+int bnn_hip_bconv2d_mfma4_supported(const bnn_hip_conv_desc* d, const bnn_hip_epilogue* e) {
+  return mfma_supported(d, e, true);
+}
+
+int bnn_hip_bconv2d_mfma4_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const void* w4,
+                                const bnn_hip_epilogue* e, void* stream) {
+  return mfma_fused(d, P, M, w4, e, stream, true);
 }
 
 // ---- the same with the shortcut convolution folded in ----
@@ -1137,7 +1174,8 @@ int bnn_hip_pack_shortcut_weight_i8(const uint32_t* wbits, int O, int C, void* s
   return bnn::launch_pack_shortcut_weight_i8(wbits, O, C, sc_w8, static_cast<hipStream_t>(stream));
 }
 
-int bnn_hip_bconv2d_mfma_fold_supported(const bnn_hip_conv_desc* d, const bnn_hip_epilogue* e) {
+namespace {
+int mfma_fold_supported(const bnn_hip_conv_desc* d, const bnn_hip_epilogue* e, bool f4) {
   alignas(16) static const uint64_t operand[2] = {0, 0};  // stands in for the packed operands (never read)
   bnn::ConvP p = empty_convp();
   if (epilogue_convp(e, &p) != BNN_HIP_OK || !p.ds_P) return 0;
@@ -1145,11 +1183,11 @@ int bnn_hip_bconv2d_mfma_fold_supported(const bnn_hip_conv_desc* d, const bnn_hi
   p.ds_W = w;  // (the shortcut's int8 pack stands in for sc_wbits in the shared validator)
   if (check_conv(d, operand, operand, w, w, &p) != BNN_HIP_OK) return 0;
   if (p.out && !aligned(p.out, 4)) return 0;
-  return bnn::mfma_fold_applies(p, d->flags) ? 1 : 0;
+  return (f4 ? bnn::mfma4_fold_applies(p, d->flags) : bnn::mfma_fold_applies(p, d->flags)) ? 1 : 0;
 }
 
-int bnn_hip_bconv2d_mfma_fold_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const void* w8,
-                                    const void* sc_w8, const bnn_hip_epilogue* e, void* stream) {
+int mfma_fold_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const void* w8, const void* sc_w8,
+                    const bnn_hip_epilogue* e, void* stream, bool f4) {
   bnn::ConvP p = empty_convp();
   int st = epilogue_convp(e, &p);
   if (st != BNN_HIP_OK) return st;
@@ -1159,10 +1197,30 @@ int bnn_hip_bconv2d_mfma_fold_fused(const bnn_hip_conv_desc* d, const uint64_t* 
   st = check_conv(d, P, M, static_cast<const uint32_t*>(w8), static_cast<const uint32_t*>(w8), &p);
   if (st != BNN_HIP_OK) return st;
   if (p.out && !aligned(p.out, 4)) return BNN_HIP_ERR_INVALID_ARG;
-  if (!bnn::mfma_fold_applies(p, d->flags)) return BNN_HIP_ERR_UNSUPPORTED;
+  if (!(f4 ? bnn::mfma4_fold_applies(p, d->flags) : bnn::mfma_fold_applies(p, d->flags))) return BNN_HIP_ERR_UNSUPPORTED;
   g_launches.fetch_add(1, std::memory_order_relaxed);
   BNN_RANGE();
-  return bnn::launch_bconv_mfma_fold(p, d->flags, w8, sc_w8, static_cast<hipStream_t>(stream));
+  return bnn::launch_bconv_mfma_fold(p, d->flags, w8, sc_w8, static_cast<hipStream_t>(stream), f4);
+}
+}  // namespace
+
+int bnn_hip_bconv2d_mfma_fold_supported(const bnn_hip_conv_desc* d, const bnn_hip_epilogue* e) {
+  return mfma_fold_supported(d, e, false);
+}
+
+int bnn_hip_bconv2d_mfma_fold_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const void* w8,
+                                    const void* sc_w8, const bnn_hip_epilogue* e, void* stream) {
+  return mfma_fold_fused(d, P, M, w8, sc_w8, e, stream, false);
+}
+
+// (the shortcut's weight stays the int8 pack: bnn_hip_pack_shortcut_weight_i8)
+int bnn_hip_bconv2d_mfma4_fold_supported(const bnn_hip_conv_desc* d, const bnn_hip_epilogue* e) {
+  return mfma_fold_supported(d, e, true);
+}
+
+int bnn_hip_bconv2d_mfma4_fold_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const void* w4,
+                                     const void* sc_w8, const bnn_hip_epilogue* e, void* stream) {
+  return mfma_fold_fused(d, P, M, w4, sc_w8, e, stream, true);
 }
 
 int bnn_hip_sign_thresholds_f32(const float* alpha, const float* bias, const float* post_scale, const float* bn_scale,

@@ -569,6 +569,35 @@ int bnn_hip_bconv2d_mfma_fold_supported(const bnn_hip_conv_desc* d, const bnn_hi
 int bnn_hip_bconv2d_mfma_fold_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const void* w8,
                                     const void* sc_w8, const bnn_hip_epilogue* epi, void* stream);
 
+/* ---- Both of the above on the FP4 matrix-core instruction (additive entry points of ABI 16; csrc/bconv_mfma.hip, the
+ * F4 form).  v_mfma_f32_16x16x128_f8f6f4 with E2M1 operands and no scales: -1, 0 and +1 are exact in E2M1 (0xA, 0x0,
+ * 0x2), every product is in {-1, 0, +1} and every partial sum is an integer of magnitude <= 9 C <= 2^20 < 2^24, so every
+ * fp32 addition is exact in any order; the accumulator converted to int is the same dot and every output bit equals
+ * bnn_hip_bconv2d_fused's.  Half the matrix cycles, half the operand bytes and half the k-steps of the int8 form.
+ *
+ * Covered: bnn_hip_bconv2d_mfma4_supported == bnn_hip_bconv2d_mfma_supported && C % 128 == 0, and
+ * bnn_hip_bconv2d_mfma4_fold_supported == bnn_hip_bconv2d_mfma_fold_supported && C % 128 == 0.  The arguments are those
+ * of the int8 twins with `w4` in place of `w8`; the folded shortcut's weight stays bnn_hip_pack_shortcut_weight_i8's
+ * `sc_w8` (its 1x1 prologue runs on the int8 instruction).
+ *
+ * bnn_hip_pack_weight_f4: wbits / wnz of bnn_hip_pack_weight_f32 -> `w4`, bnn_hip_weight_f4_bytes(O, C, KH, KW) =
+ * 9 O C / 2 bytes (0: no int8 pack for this weight shape, or C % 128 != 0), 16-byte aligned; once per weight version.
+ * Byte layout, G = C / 128:
+ *   w4[o / 64][g][tap][ct][lane][e]   E2M1 nibbles, g < G, tap = 3 ky + kx, ct < 4, lane < 64, e < 32: nibble e is the
+ *                                     low (e even) or high (e odd) half of byte e / 2 of the lane's 16-byte fragment,
+ *                                     4 KB per (64 output channels, 128-channel group, tap)
+ *       = sign(W[o = 64 (o / 64) + 16 ct + (lane & 15)][c = 128 g + 32 (lane >> 4) + e][tap])   as 0x2 / 0xA / 0x0
+ * (wnz bit ? (wbits bit ? +1 : -1) : 0).  The kernel expands the activation planes with the same channel order.     */
+size_t bnn_hip_weight_f4_bytes(int O, int C, int KH, int KW);
+int bnn_hip_pack_weight_f4(const uint32_t* wbits, const uint32_t* wnz, int O, int C, int KH, int KW, void* w4,
+                           void* stream);
+int bnn_hip_bconv2d_mfma4_supported(const bnn_hip_conv_desc* d, const bnn_hip_epilogue* epi);
+int bnn_hip_bconv2d_mfma4_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const void* w4,
+                                const bnn_hip_epilogue* epi, void* stream);
+int bnn_hip_bconv2d_mfma4_fold_supported(const bnn_hip_conv_desc* d, const bnn_hip_epilogue* epi);
+int bnn_hip_bconv2d_mfma4_fold_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const void* w4,
+                                     const void* sc_w8, const bnn_hip_epilogue* epi, void* stream);
+
 /* ---- Which kernel a convolution runs (ABI 16): the route of bnn_hip_bconv2d / _fused / _dot, for tests. ----
  * The launch ladder of csrc/bconv.hip picks one instantiation per call from the kernel size, the chunk width, the
  * epilogue, the flags and the size of the grid.  The route query walks THAT ladder (the same statements, with the

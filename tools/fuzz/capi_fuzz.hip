@@ -77,10 +77,20 @@ bool mfma_conv_applies(const ConvP& p, int) {
   check_convp(p);
   return p.KH == 3 && p.KW == 3 && p.C % 64 == 0 && p.O % 64 == 0 && !p.ds_P && !p.prelu && p.c_tot == p.O;
 }
-int launch_bconv_mfma(const ConvP& p, int flags, const void* w8, hipStream_t) {
+size_t weight_f4_bytes(int O, int C, int KH, int KW) {
+  return (weight_i8_bytes(O, C, KH, KW) != 0 && C % 128 == 0) ? (size_t)O * (size_t)C * 9 / 2 : 0;
+}
+int launch_pack_weight_f4(const uint32_t* wbits, const uint32_t* wnz, const bnn_hip_wlayout& L, int O, void* w4, hipStream_t) {
+  ++g_reached;
+  REQUIRE(wbits && wnz && w4 && al(wbits, 16) && al(wnz, 16) && al(w4, 16));
+  REQUIRE(O > 0 && O % 64 == 0 && L.taps == 9 && L.cw32 > 0 && L.cw32 % 4 == 0 && L.cwc * L.nchunk == L.cw32 && L.o_pad == O);
+  return BNN_HIP_OK;
+}
+bool mfma4_conv_applies(const ConvP& p, int flags) { return p.C % 128 == 0 && mfma_conv_applies(p, flags); }
+int launch_bconv_mfma(const ConvP& p, int flags, const void* w8, hipStream_t, bool f4) {
   ++g_reached;
   check_convp(p);
-  REQUIRE(mfma_conv_applies(p, flags));
+  REQUIRE(f4 ? mfma4_conv_applies(p, flags) : mfma_conv_applies(p, flags));
   REQUIRE((long long)p.N * p.H * p.Wd * ((p.C + 63) / 64) <= kPlaneWords);
   REQUIRE(p.P && p.M && w8 && al(p.P, 16) && al(p.M, 16) && al(w8, 16) && p.alpha);
   REQUIRE(p.out || (p.outP && p.outM));
@@ -103,10 +113,11 @@ bool mfma_fold_applies(const ConvP& p, int flags) {
   return p.KH == 3 && p.KW == 3 && p.C % 64 == 0 && p.O % 64 == 0 && p.ds_P && !p.res && !p.prelu && p.c_tot == p.O &&
          (flags & BNN_HIP_FLAG_ACT_NONNEG) && shortcut_weight_i8_bytes(p.O, p.ds_C) != 0;
 }
-int launch_bconv_mfma_fold(const ConvP& p, int flags, const void* w8, const void* sc_w8, hipStream_t) {
+bool mfma4_fold_applies(const ConvP& p, int flags) { return p.C % 128 == 0 && mfma_fold_applies(p, flags); }
+int launch_bconv_mfma_fold(const ConvP& p, int flags, const void* w8, const void* sc_w8, hipStream_t, bool f4) {
   ++g_reached;
   check_convp(p);
-  REQUIRE(mfma_fold_applies(p, flags));
+  REQUIRE(f4 ? mfma4_fold_applies(p, flags) : mfma_fold_applies(p, flags));
   REQUIRE((long long)p.N * p.H * p.Wd * ((p.C + 63) / 64) <= kPlaneWords);
   REQUIRE(p.P && p.M && w8 && sc_w8 && al(p.P, 16) && al(p.M, 16) && al(w8, 16) && al(sc_w8, 16) && p.alpha);
   REQUIRE(p.ds_P && al(p.ds_P, 8) && p.ds_alpha && p.ds_a && p.ds_b);
@@ -1088,6 +1099,21 @@ int main(int argc, char** argv) {
           const int sps = bnn_hip_pack_shortcut_weight_i8(pick_ptr<uint32_t>(), d.O, sc_c, pick_ptr<char>(), stream);
           if (!status_ok(sps)) broken("int8 shortcut pack status");
           digest = (digest ^ (uint64_t)(uint32_t)sf ^ ((uint64_t)(uint32_t)sps << 32) ^ (uint64_t)fsup) * 0x100000001B3ull;
+          // the FP4 forms of both: never wider than their int8 twins
+          const int sup4 = bnn_hip_bconv2d_mfma4_supported(dp, ep), fsup4 = bnn_hip_bconv2d_mfma4_fold_supported(dp, ep);
+          if ((sup4 != 0 && sup4 != 1) || (sup4 && !sup) || (fsup4 != 0 && fsup4 != 1) || (fsup4 && !fsup))
+            broken("mfma4 supported");
+          if ((sup4 || fsup4) && d.C % 128 != 0) broken("mfma4 took half a 128-channel group");
+          const int sm4 = bnn_hip_bconv2d_mfma4_fused(dp, pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<char>(), ep, stream);
+          if (!status_ok(sm4) || (sm4 == BNN_HIP_OK && !sup4)) broken("mfma4 conv launched where the query said no");
+          const int sf4 = bnn_hip_bconv2d_mfma4_fold_fused(dp, pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<char>(),
+                                                           pick_ptr<char>(), ep, stream);
+          if (!status_ok(sf4) || (sf4 == BNN_HIP_OK && !fsup4)) broken("mfma4 fold launched where the query said no");
+          const size_t b4 = bnn_hip_weight_f4_bytes(d.O, d.C, d.KH, d.KW);
+          if (b4 != 0 && 2 * b4 != bnn_hip_weight_i8_bytes(d.O, d.C, d.KH, d.KW)) broken("FP4 weight pack size");
+          const int sp4 = bnn_hip_pack_weight_f4(pick_ptr<uint32_t>(), pick_ptr<uint32_t>(), d.O, d.C, d.KH, d.KW, pick_ptr<char>(), stream);
+          if (!status_ok(sp4)) broken("FP4 weight pack status");
+          digest = (digest ^ (uint64_t)(uint32_t)sm4 ^ ((uint64_t)(uint32_t)sf4 << 32) ^ (uint64_t)(sup4 + 2 * fsup4 + 4 * sp4)) * 0x100000001B3ull;
         }
         st = bnn_hip_blinear(pick_int(), pick_int(), pick_int(), pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<uint32_t>(),
                              pick_ptr<uint32_t>(), pick_int(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(),
