@@ -128,7 +128,7 @@ class _TierFusion:
 
 class BlockFusion(_TierFusion):
     """The second tier of the drop-in dispatch: a residual block of ``bnn_amd.models`` (``BasicBlock``, ``Bottleneck``,
-    ``PreBasicBlock``, ``HBlock``) called on its own — inside a network that is not laid out like the reference's
+    ``PreBasicBlock``, ``PreBottleneck``, ``HBlock``) called on its own — inside a network that is not laid out like the reference's
     ``ResNet`` (a CIFAR-style three-stage ResNet-20, a custom backbone), or behind a stem the whole-model executor does
     not cover — evaluates itself as ``FusedBlocks([block])``: fp32 NCHW in -> ``pack_act`` -> the block's convolutions
     with BatchNorm / activation / residual add in their epilogues (activations between them as bit planes) -> fp32 NCHW

@@ -35,7 +35,7 @@ import torch.nn.modules.module as _mm
 
 from . import fastpath, hipops, native
 from .layers import Conv2d as BinaryConv2d
-from .models.blocks import BasicBlock, Bottleneck, HBlock, PreBasicBlock
+from .models.blocks import BasicBlock, Bottleneck, HBlock, PreBasicBlock, PreBottleneck
 from .models.resnet import ResNet
 
 
@@ -118,6 +118,8 @@ class _Conv:
     mfma_fold: dict = field(default_factory=dict)   # geometry -> this launch, with its shortcut folded in, does too
     w4: Optional[torch.Tensor] = None    # FP4 MFMA pack of the weight (the F4 form of the same kernel), built with the plan
     f4: dict = field(default_factory=dict)   # the keys of ``mfma`` / ``mfma_fold`` -> that matrix-core launch is the FP4 form
+    w4_1x1: Optional[torch.Tensor] = None    # FP4 pack of a 1x1 weight (csrc/bconv1x1_mfma.hip), built with the plan
+    mfma_1x1: dict = field(default_factory=dict)   # (geometry, epilogue) -> this 1x1 launch runs on the FP4 matrix cores
 
     def _on_matrix_cores(self, act: hipops.PackedAct, residual, out_f32: bool, out_packed: bool, thr, epi):
         """The admission of one launch to the MFMA convolution: the table of ``fastpath`` (shapes that measured faster)
@@ -177,6 +179,37 @@ class _Conv:
                     throughput=self.throughput))
         return ok, ok and self.f4[key]
 
+    # the ``epi`` switches a 1x1 launch on the FP4 kernel may carry -> their BNN_HIP_EPI_* flag (None: a tensor, no flag)
+    _EPI_1X1 = {"residual_after_act": native.EPI_RES_AFTER_ACT, "pack_before_residual": native.EPI_PACK_BEFORE_RES,
+                "pack_relu": native.EPI_PACK_RELU, "pack_scale": None, "pack_shift": None}
+
+    def _1x1_on_matrix_cores(self, act: hipops.PackedAct, residual, out_f32: bool, out_packed: bool, thr, epi) -> bool:
+        """The admission of one 1x1 launch to the FP4 kernel of csrc/bconv1x1_mfma.hip: the tables of ``fastpath``
+        (``MFMA_1X1_SHAPES`` / ``MFMA_1X1_TERNARY_SHAPES``) and the kernel's own query
+        (``bnn_hip_bconv1x1_mfma4_supported``), asked once per geometry and epilogue.  Unlike ``_on_matrix_cores`` it admits
+        the pre-activation switches — the late residual and the pack affine of a PreBottleneck's launches; a channel
+        window, a caller's ``out`` and the folded shortcut stay on the popcount kernels."""
+        if self.w4_1x1 is None or not set(epi) <= set(self._EPI_1X1):
+            return False
+        on = {k for k, v in epi.items() if v is not None and v is not False}
+        key = (tuple(act.shape), act.nonneg, residual is not None, out_f32, out_packed, thr is not None, tuple(sorted(on)))
+        ok = self.mfma_1x1.get(key)
+        if ok is None:
+            lay = self.layer
+            flags = 0
+            for k in on:
+                flags |= self._EPI_1X1[k] or 0
+            ok = self.mfma_1x1[key] = bool(
+                ("pack_scale" in on) == ("pack_shift" in on)
+                and fastpath.mfma_1x1_admitted(act.shape[1], lay.out_channels, act.shape[2], out_f32, act.nonneg)
+                and hipops.bconv1x1_mfma4_supported(
+                    act.shape, self.weight, nonneg=act.nonneg, bias=lay.bias is not None,
+                    post_scale=self.plan.scale is not None, bn=self.bn_scale is not None, residual=residual is not None,
+                    prelu=self.prelu is not None, relu=self.relu, out_f32=out_f32, out_packed=out_packed,
+                    stride=lay.stride, padding=lay.padding, dilation=lay.dilation, sign_thresholds=thr is not None,
+                    epi_flags=flags, pack_affine="pack_scale" in on))
+        return ok
+
     def run(self, act: hipops.PackedAct, *, residual=None, out_f32: bool, out_packed: bool, shortcut_w8=None, **epi):
         """``epi``: the pre-activation switches of ``hipops.bconv2d_fused`` (late residual, pack affine, ...);
         ``shortcut_w8``: the int8 pack of the weight in ``epi["shortcut"]``, where there is one."""
@@ -189,6 +222,8 @@ class _Conv:
                     bn_shift=self.bn_shift, residual=residual, prelu=self.prelu, relu=self.relu,
                     out_f32=out_f32, out_packed=out_packed, stride=lay.stride, padding=lay.padding,
                     dilation=lay.dilation, throughput=self.throughput, sign_thresholds=thr, **epi)
+        if self._1x1_on_matrix_cores(act, residual, out_f32, out_packed, thr, epi):
+            return hipops.bconv1x1_mfma4_fused(act, self.weight, self.w4_1x1, **args)
         on, f4 = self._on_matrix_cores(act, residual, out_f32, out_packed, thr, epi)
         if on:
             if f4:
@@ -239,10 +274,9 @@ class _Post:
 
 @dataclass(eq=False)
 class _Pre:
-    """PreBasicBlock: BN-conv-act, BN-conv-act, (+id)."""
+    """PreBasicBlock (K = 2) / PreBottleneck (K = 3): K times BN-conv-act, (+id)."""
     kind = "pre"
-    bn1: Tuple[torch.Tensor, torch.Tensor]  # (scale, shift) of fold_bn
-    bn2: Tuple[torch.Tensor, torch.Tensor]
+    bn: List[Tuple[torch.Tensor, torch.Tensor]]     # (scale, shift) of fold_bn: the BatchNorm in front of each convolution
     convs: List[_Conv]
     ds: Optional[_Conv] = None              # as in _Post
     pool: int = 0
@@ -291,17 +325,19 @@ class _Handoff:
     ds: Optional[hipops.PackedAct] = None
 
 
-_BLOCK_KINDS = {"BasicBlock": BasicBlock, "PreBasicBlock": PreBasicBlock, "Bottleneck": Bottleneck, "HBlock": HBlock}
+_BLOCK_KINDS = {"BasicBlock": BasicBlock, "PreBasicBlock": PreBasicBlock, "Bottleneck": Bottleneck,
+                "PreBottleneck": PreBottleneck, "HBlock": HBlock}
 _BLOCK_ATTRS = {BasicBlock: ("conv1", "bn1", "act1", "conv2", "bn2", "act2", "downsample"),
                 PreBasicBlock: ("conv1", "bn1", "act1", "conv2", "bn2", "act2", "downsample"),
                 Bottleneck: ("conv1", "bn1", "act1", "conv2", "bn2", "act2", "conv3", "bn3", "act3", "downsample"),
+                PreBottleneck: ("conv1", "bn1", "act1", "conv2", "bn2", "act2", "conv3", "bn3", "act3", "downsample"),
                 HBlock: ("conv1", "bn1", "act1", "conv2", "bn2", "act2", "conv3", "bn3", "act3", "downsample")}
 
 
 def _block_kind(blk: nn.Module):
     """The block family ``blk`` belongs to: one of this package's classes (exact type), or a class of the same NAME
     and attribute layout from another package — the reference's own ``bnn.models.layers`` blocks, which these mirror
-    attribute for attribute (res_block.py:8-56,59-118,121-167, hierarchical_block.py:8-60).  Foreign classes are
+    attribute for attribute (res_block.py:8-56,59-118,121-167,170-229, hierarchical_block.py:8-60).  Foreign classes are
     only ever fused after ``AutoFusion`` has checked the fused result against the model's own forward."""
     t = type(blk)
     if t in _BLOCK_ATTRS:
@@ -343,7 +379,8 @@ _PARKED: list = []
 class FusedResNet(nn.Module):
     """Inference executor for ``bnn_amd.models.ResNet`` built from ``BasicBlock`` (ResNet-18/34),
     ``Bottleneck`` (ResNet-50/101/152: mixed 1x1 / 3x3 binary convolutions), ``PreBasicBlock`` (the
-    pre-activation dataflow of examples/imagenet.py) or ``HBlock`` (hierarchical blocks)."""
+    pre-activation dataflow of examples/imagenet.py), ``PreBottleneck`` (that dataflow with the 1x1 / 3x3 / 1x1
+    convolutions of a Bottleneck) or ``HBlock`` (hierarchical blocks)."""
 
     def __init__(self, model: ResNet, use_mfma_stem: bool = True, overlap_shortcut: bool = True,
                  stem_fp16: bool = False, stem_exact_fp32: bool = False, throughput_mode: bool = False,
@@ -401,8 +438,11 @@ class FusedResNet(nn.Module):
         w8 = hipops.pack_weight_i8(pw) if fastpath.MFMA_CONV != "0" and tuple(pw.shape[2:]) == (3, 3) else None
         # and its FP4 form (None as well where C is no multiple of 128)
         w4 = hipops.pack_weight_f4(pw) if w8 is not None and fastpath.MFMA_F4 != "0" else None
+        # the FP4 form of a 1x1 weight (None where O is no multiple of 64 or C none of 128)
+        w4_1x1 = (hipops.pack_weight1x1_f4(pw) if fastpath.MFMA_CONV != "0" and fastpath.MFMA_1X1 != "0"
+                  and tuple(pw.shape[2:]) == (1, 1) else None)
         return _Conv(conv, plan, pw, scale, shift, relu, prelu, self._names.get(id(conv), ""), self.throughput_mode, thr,
-                     w8, w4=w4)
+                     w8, w4=w4, w4_1x1=w4_1x1)
 
     @staticmethod
     def _sign_through(act: nn.Module):
@@ -506,9 +546,10 @@ class FusedResNet(nn.Module):
             self._blocks.append(_Pool(blk))
             return
         kind = _block_kind(blk)
-        if kind is PreBasicBlock:           # BN-conv-act, BN-conv-act, (+id)   (res_block.py:147-152)
-            entry = _Pre(bn1=fold_bn(blk.bn1), bn2=fold_bn(blk.bn2),
-                         convs=[self._conv(blk.conv1, None, blk.act1), self._conv(blk.conv2, None, blk.act2)])
+        if kind is PreBasicBlock or kind is PreBottleneck:   # K times BN-conv-act, (+id)   (res_block.py:147-152,205-210)
+            ks = (1, 2) if kind is PreBasicBlock else (1, 2, 3)
+            entry = _Pre(bn=[fold_bn(getattr(blk, f"bn{i}")) for i in ks],
+                         convs=[self._conv(getattr(blk, f"conv{i}"), None, getattr(blk, f"act{i}")) for i in ks])
             self._shortcut(blk, entry)
             self._blocks.append(entry)
             return
@@ -709,10 +750,11 @@ class FusedResNet(nn.Module):
         return self._side[key]
 
     def _run_pre(self, b, nxt, t, packed, left):
-        """PreBasicBlock: the block input travels as fp32 ``t`` (shortcut) and as ``sign(bn1(t))``; the
-        latter comes out of the previous block's last epilogue (its ``pack_scale`` = this ``bn1``)."""
+        """PreBasicBlock / PreBottleneck: the block input travels as fp32 ``t`` (shortcut) and as ``sign(bn1(t))``; the
+        latter comes out of the previous block's last epilogue (its ``pack_scale`` = this ``bn1``).  Every convolution but
+        the last hands ``sign(bn_next(act(conv)))`` on as planes; the last adds the shortcut behind its activation."""
         if left is None or left.owner is not b:
-            packed = hipops.bn_act_pack(t, *b.bn1, relu=False)
+            packed = hipops.bn_act_pack(t, *b.bn[0], relu=False)
         if b.ds is not None:
             sc_in = hipops.avgpool_pack(t, b.pool) if b.pool > 1 else hipops.pack_act(t)
             idn, _ = b.ds.run(sc_in, out_f32=True, out_packed=False)
@@ -720,11 +762,13 @@ class FusedResNet(nn.Module):
             idn = b.ds_float(t)
         else:
             idn = t
-        c1, c2 = b.convs
-        _, p1 = c1.run(packed, out_f32=False, out_packed=True, pack_scale=b.bn2[0], pack_shift=b.bn2[1])
+        p1 = packed
+        for c, bn in zip(b.convs[:-1], b.bn[1:]):
+            _, p1 = c.run(p1, out_f32=False, out_packed=True, pack_scale=bn[0], pack_shift=bn[1])
+        c2 = b.convs[-1]
         if nxt is not None and nxt.kind == "pre":   # binarise for the next block's conv1 right here
             t, pk = c2.run(p1, residual=idn, out_f32=True, out_packed=True, residual_after_act=True,
-                           pack_scale=nxt.bn1[0], pack_shift=nxt.bn1[1])
+                           pack_scale=nxt.bn[0][0], pack_shift=nxt.bn[0][1])
             return t, pk, _Handoff(nxt)
         t, _ = c2.run(p1, residual=idn, out_f32=True, out_packed=False, residual_after_act=True)
         return t, None, None
@@ -992,8 +1036,8 @@ class _Split:
 
 class FusedBlocks(FusedResNet):
     """The fused executor for a bare ``nn.Sequential`` of residual blocks (``BasicBlock`` / ``Bottleneck`` /
-    ``PreBasicBlock`` / ``HBlock``, optionally ``nn.AvgPool2d`` between them): fp32 NCHW in, fp32 NCHW out, the
-    activations between the binary layers travel as bit planes exactly as inside ``FusedResNet``.  For custom
+    ``PreBasicBlock`` / ``PreBottleneck`` / ``HBlock``, optionally ``nn.AvgPool2d`` between them): fp32 NCHW in, fp32 NCHW
+    out, the activations between the binary layers travel as bit planes exactly as inside ``FusedResNet``.  For custom
     networks that keep their own stem / head, and for testing the cross-block dataflow on its own."""
 
     _stem_mfma = False      # no stem: ``forward_fresh`` does not apply

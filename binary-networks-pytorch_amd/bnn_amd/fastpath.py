@@ -150,6 +150,62 @@ def mfma_f4_admitted(key: tuple) -> bool:
     return MFMA_F4 == "all" or tuple(key) in MFMA_F4_SHAPES
 
 
+# The 1x1 convolutions of the fused ResNet executor (Bottleneck and PreBottleneck: conv1, conv3 and the shortcut) on the FP4
+# matrix-core kernel of csrc/bconv1x1_mfma.hip (a plain GEMM on v_mfma_f32_16x16x128_f8f6f4, every epilogue of
+# bnn_hip_bconv2d_fused, the same bits; bnn_hip_bconv1x1_mfma4_fused) instead of the XNOR-popcount kernels.
+# BNN_AMD_MFMA_1X1: "1" (default) — the launches listed in MFMA_1X1_SHAPES; "0" — none: exactly the launches of before;
+# "all" — every launch bnn_hip_bconv1x1_mfma4_supported takes (C % 128 == 0, O % 64 == 0).  BNN_AMD_MFMA_CONV=0 turns
+# this off too.  Read when an executor plans its layers.
+MFMA_1X1 = os.environ.get("BNN_AMD_MFMA_1X1", "1")
+# (C, O, H of the input, writes fp32) -> (popcount us, FP4 us) of that launch in kernel traces of resnet50() at batch 128,
+# one batch in flight (tools/bench_conv1x1.py, profiles/conv1x1_mfma_bench.jsonl; means of two traces each, per launch
+# where several share a key).  A shape is listed only where both FP4 traces lie below both popcount traces by more than
+# the launch's trace-to-trace gap — the rule of MFMA_F4_SHAPES.  These are launches on NON-NEGATIVE planes (a Bottleneck
+# behind ReLU: M is not read, one expansion per half-word) with an epilogue the kernel has compiled in.
+MFMA_1X1_SHAPES = {
+    (256, 64, 56, False): (44.2, 19.5),       # layer1.1 / 1.2 conv1
+    (256, 128, 56, False): (75.4, 28.9),      # layer2.0.conv1
+    (128, 512, 28, True): (104.2, 85.2),      # layer2.0 / 2.1 / 2.2 conv3
+    (128, 512, 28, False): (86.5, 61.4),      # layer2.3.conv3 (planes only: layer3.0 reads nothing else)
+    (512, 128, 28, False): (35.0, 17.4),      # layer2.1 / 2.2 / 2.3 conv1
+    (512, 256, 28, False): (57.9, 26.1),      # layer3.0.conv1
+    (512, 1024, 14, True): (39.5, 35.1),      # layer3.0 shortcut
+    (256, 1024, 14, True): (61.6, 50.1),      # layer3.0 .. 3.4 conv3
+    (256, 1024, 14, False): (49.7, 34.4),     # layer3.5.conv3 (planes only)
+    (1024, 256, 14, False): (29.6, 14.0),     # layer3.1 .. 3.5 conv1
+    (1024, 512, 14, False): (49.8, 24.5),     # layer4.0.conv1
+    (1024, 2048, 7, True): (35.2, 30.9),      # layer4.0 shortcut
+    (512, 2048, 7, True): (41.7, 35.3),       # layer4.0 / 4.1 / 4.2 conv3
+    (2048, 512, 7, False): (32.7, 19.6),      # layer4.1 / 4.2 conv1
+    # not listed: (256, 512, 28, True), the layer2.0 shortcut: 51.7 -> 59.3 us (its fp32 stores bind either way)
+}
+# The same for launches on TERNARY planes (both planes live: the pre-activation blocks binarise behind a BatchNorm: two
+# expansions per half-word, twice the plane loads), traced in resnet50(block_type=PreBottleneck, activation=nn.PReLU); the
+# epilogues are the kernel's compiled pre-activation profiles (PReLU -> next BatchNorm -> planes; PReLU -> + shortcut ->
+# fp32 and planes).
+MFMA_1X1_TERNARY_SHAPES = {
+    (256, 64, 56, False): (50.4, 34.3),       # layer1.1 / 1.2 conv1
+    (256, 128, 56, False): (89.1, 52.9),      # layer2.0.conv1
+    (128, 512, 28, True): (117.8, 98.8),      # layer2.0 .. 2.3 conv3
+    (512, 128, 28, False): (38.9, 27.3),      # layer2.1 / 2.2 / 2.3 conv1
+    (512, 256, 28, False): (65.7, 41.9),      # layer3.0.conv1
+    (256, 1024, 14, True): (72.8, 62.2),      # layer3.0 .. 3.5 conv3
+    (1024, 256, 14, False): (32.6, 20.1),     # layer3.1 .. 3.5 conv1
+    (1024, 512, 14, False): (51.9, 36.4),     # layer4.0.conv1
+    (512, 2048, 7, True): (45.0, 40.8),       # layer4.0 / 4.1 / 4.2 conv3
+    (2048, 512, 7, False): (33.4, 28.0),      # layer4.1 / 4.2 conv1
+    # not listed, the three shortcuts (BN -> fp32 on the pooled ternary planes): (256, 512, 28, True) 49.8 -> 62.5 us,
+    # (512, 1024, 14, True) 40.8 -> 41.1, (1024, 2048, 7, True) 37.3 -> 37.9
+}
+
+
+def mfma_1x1_admitted(C: int, O: int, H: int, out_f32: bool, nonneg: bool = True) -> bool:
+    if MFMA_CONV == "0" or MFMA_1X1 == "0":
+        return False
+    table = MFMA_1X1_SHAPES if nonneg else MFMA_1X1_TERNARY_SHAPES
+    return MFMA_1X1 == "all" or (C, O, H, bool(out_f32)) in table
+
+
 # The one-launch FactorizedConv kernel (csrc/fconv.hip) against the per-layer path of the same module, batch 256 on
 # MI355X (tools/bench_fconv.py -> profiles/fconv_bench.jsonl).  The admission rule, in one place: a shape (C, H, W,
 # stride) whose fused executor measured SLOWER than the per-layer path is listed here with its (per-layer us, fused us)

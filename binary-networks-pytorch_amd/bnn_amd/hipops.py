@@ -1346,6 +1346,43 @@ def bconv2d_mfma4_fused(a: PackedAct, w: PackedWeight, w4: torch.Tensor, **kw):
     return _run_fused("bnn_hip_bconv2d_mfma4_fused", a, w, (w4.data_ptr(),), "bconv2d_mfma4_fused", **kw)
 
 
+def pack_weight1x1_f4(w: PackedWeight) -> Optional[torch.Tensor]:
+    """The FP4 (E2M1) MFMA-fragment form of a packed 1x1 weight (``bnn_hip_pack_weight1x1_f4``, layout: include/bnn_hip.h:
+    ``pack_weight_f4``'s with one tap), as an int8 tensor of nibble pairs.  ``None`` where there is none (not 1x1, O no
+    multiple of 64, C no multiple of 128, a grouped pack).  One launch; ``w.alpha`` is used unchanged beside it."""
+    lib = native.require()
+    if w.windowed or w.groups != 1:
+        return None
+    O, C, KH, KW = w.shape
+    nbytes = int(lib.bnn_hip_weight1x1_f4_bytes(O, C)) if (KH, KW) == (1, 1) else 0
+    if nbytes == 0:
+        return None
+    dev = w.wbits.device
+    with torch.cuda.device(dev):
+        pack = torch.empty(nbytes, dtype=torch.int8, device=dev)
+        native.check(lib.bnn_hip_pack_weight1x1_f4(w.wbits.data_ptr(), w.wnz.data_ptr(), O, C, KH, KW, pack.data_ptr(),
+                                                   _stream(dev)), "bnn_hip_pack_weight1x1_f4")
+    return pack
+
+
+def bconv1x1_mfma4_supported(a_shape, w: PackedWeight, *, nonneg: bool = False, bias=False, post_scale=False, bn=False,
+                             residual=False, prelu=False, relu=False, out_f32=True, out_packed=False, stride=1, padding=0,
+                             dilation=1, sign_thresholds=False, shortcut=False, epi_flags: int = 0, pack_affine=False,
+                             out_c_total: int = 0) -> bool:
+    """``bconv2d_mfma_supported`` for the 1x1 convolution on the FP4 matrix cores (``bnn_hip_bconv1x1_mfma4_supported``):
+    1x1 / stride 1 / padding 0, C % 128 == 0, O % 64 == 0, every epilogue of ``bconv2d_fused`` but the folded shortcut
+    and a channel window."""
+    return _mfma_supported("bnn_hip_bconv1x1_mfma4_supported", **locals())
+
+
+def bconv1x1_mfma4_fused(a: PackedAct, w: PackedWeight, w4: torch.Tensor, **kw):
+    """``bconv2d_fused`` for a 1x1 weight with the dot on ``v_mfma_f32_16x16x128_f8f6f4`` and FP4 operands
+    (``bnn_hip_bconv1x1_mfma4_fused``): same arguments — the pre-activation switches included — same bits.
+    ``w4 = pack_weight1x1_f4(w)``.  Raises where ``bconv1x1_mfma4_supported`` says no."""
+    w4 = _opaque(w4, native.require().bnn_hip_weight1x1_f4_bytes(w.shape[0], w.shape[1]), "w4", torch.int8)
+    return _run_fused("bnn_hip_bconv1x1_mfma4_fused", a, w, (w4.data_ptr(),), "bconv1x1_mfma4_fused", **kw)
+
+
 def pack_shortcut_weight_i8(sw: PackedWeight) -> Optional[torch.Tensor]:
     """The int8 MFMA-fragment form of a shortcut's packed 1x1 weight (``bnn_hip_pack_shortcut_weight_i8``, layout:
     include/bnn_hip.h), or ``None`` where there is none (not 1x1, zero weights, O no multiple of 64, C not 64 / 128 / 256,

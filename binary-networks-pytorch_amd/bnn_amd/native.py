@@ -220,6 +220,10 @@ _PROTOTYPES = {
     "bnn_hip_bconv2d_mfma4_fused": (_i, [_conv_p, _vp, _vp, _vp, ctypes.POINTER(Epilogue), _vp]),
     "bnn_hip_bconv2d_mfma4_fold_supported": (_i, [_conv_p, ctypes.POINTER(Epilogue)]),
     "bnn_hip_bconv2d_mfma4_fold_fused": (_i, [_conv_p, _vp, _vp, _vp, _vp, ctypes.POINTER(Epilogue), _vp]),
+    "bnn_hip_weight1x1_f4_bytes": (_sz, [_i, _i]),
+    "bnn_hip_pack_weight1x1_f4": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "bnn_hip_bconv1x1_mfma4_supported": (_i, [_conv_p, ctypes.POINTER(Epilogue)]),
+    "bnn_hip_bconv1x1_mfma4_fused": (_i, [_conv_p, _vp, _vp, _vp, ctypes.POINTER(Epilogue), _vp]),
     "bnn_hip_bconv2d_route": (_i, [_conv_p, ctypes.POINTER(Epilogue), ctypes.POINTER(ConvRoute)]),
     "bnn_hip_bconv2d_dot_route": (_i, [_conv_p, ctypes.POINTER(ConvRoute)]),
     "bnn_hip_bconv2d_dot": (_i, [_conv_p] + [_vp] * 6),

@@ -31,7 +31,7 @@
 // lane group l >> 4 reads the 16 bytes that come from 32-bit plane word l >> 4 of the group.  Tile choice, pipeline and
 // epilogue are the int8 form's; the folded shortcut's 1x1 prologue stays on the int8 instruction with int32
 // accumulators of its own, dead before the main loop.
-#include "bconv_core.h"
+#include "bconv_mfma.h"
 
 #include <type_traits>
 
@@ -39,13 +39,6 @@ namespace bnn {
 
 namespace {
 
-using i32x4 = __attribute__((ext_vector_type(4))) int;
-using i32x8 = __attribute__((ext_vector_type(8))) int;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-constexpr int kMfmaThreads = 256;
-constexpr int kAccStride = 68;  // int32 per channel row of the transpose buffer: 4 rows apart = 16 banks apart
-constexpr int kAccBytes = 4 * 32 * kAccStride * 4;  // four waves x 32 channels
 constexpr int kMaxLds = 64 * 1024;
 constexpr int kPatchSlots = 4;  // patch pixels per thread (1024 pixels = the LDS limit): the plane words of the next group wait in registers
 // Folded shortcut (DS): the shortcut's dots wait in LDS behind the patch / transpose buffer while the main loop runs, as
@@ -86,31 +79,7 @@ __device__ __forceinline__ uint32_t expand4(uint32_t pw, uint32_t mw, int sh, bo
   return p | (spread4(mw, sh) * 0xFFu);  // bytes of 0 / 1 times 255: no carry between bytes
 }
 
-// FP4: 8 bits -> 8 nibbles, bit i in nibble i.  The bits go two to a byte, and each byte looks its two nibbles up in the
-// four bytes of `lut` (v_perm_b32): 0x22200200 turns a set bit into 0x2, 0x88800800 into 0x8.
-__device__ __forceinline__ uint32_t nibbles8(uint32_t word, int sh, uint32_t lut) {
-  uint32_t t = (word >> sh) & 0xFFu;
-  t = (t | (t << 12)) & 0x000F000Fu;
-  t = (t | (t << 6)) & 0x03030303u;
-  return __builtin_amdgcn_perm(lut, lut, t);
-}
-// P or M set -> 0x2, M set -> 0x8 on top of it: +1 = 0x2, -1 = 0xA (P and M are exclusive)
-__device__ __forceinline__ uint32_t expand8_f4(uint32_t pw, uint32_t mw, int sh, bool nn) {
-  if (nn) return nibbles8(pw, sh, 0x22200200u);
-  return nibbles8(pw | mw, sh, 0x22200200u) | nibbles8(mw, sh, 0x88800800u);
-}
-
-// One k-step of one 16 x 16 tile.  FP4: the operands are the low four of the instruction's eight dwords.
-template <bool F4, class Acc>
-__device__ __forceinline__ Acc mma_step(const i32x4 a, const i32x4 b, const Acc c) {
-  if constexpr (F4) {
-    const i32x8 a8{a[0], a[1], a[2], a[3], 0, 0, 0, 0}, b8{b[0], b[1], b[2], b[3], 0, 0, 0, 0};
-    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a8, b8, c, 4, 4, 0, 0, 0, 0);
-  } else {
-    return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0);
-  }
-}
-
+// (nibbles8 / expand8_f4, the FP4 expansion, and mma_step, one k-step of one 16 x 16 tile: bconv_mfma.h)
 template <bool First, class A, class B>
 __device__ __forceinline__ auto& pick(A& a, B& b) {
   if constexpr (First) return a;
@@ -487,16 +456,16 @@ __global__ __launch_bounds__(256) void pack_weight_i8_kernel(const uint32_t* __r
 // wbits / wnz -> FP4 (E2M1) A fragments (include/bnn_hip.h: bnn_hip_pack_weight_f4).  One thread per dword = eight
 // consecutive input channels of one output channel and tap: +1 -> 0x2, -1 -> 0xA, a zero weight -> 0x0.
 __global__ __launch_bounds__(256) void pack_weight_f4_kernel(const uint32_t* __restrict__ wbits,
-                                                             const uint32_t* __restrict__ wnz, int O, int cw32, int cwc,
-                                                             uint32_t* __restrict__ w4) {
-  const int groups = cw32 >> 2, nchunk = cw32 / cwc, per_o = 9 * cwc;
-  const size_t total = (size_t)O * groups * 9 * 16;  // dwords
+                                                             const uint32_t* __restrict__ wnz, int O, int taps,
+                                                             int cw32, int cwc, uint32_t* __restrict__ w4) {
+  const int groups = cw32 >> 2, nchunk = cw32 / cwc, per_o = taps * cwc;
+  const size_t total = (size_t)O * groups * taps * 16;  // dwords
   const size_t d = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (d >= total) return;
   const int e8 = (int)(d & 3), lane = (int)((d >> 2) & 63), ct = (int)((d >> 8) & 3);
   size_t rest = d >> 10;
-  const int t = (int)(rest % 9);
-  rest /= 9;
+  const int t = (int)(rest % taps);
+  rest /= taps;
   const int gi = (int)(rest % groups), ob64 = (int)(rest / groups);
   const int o = 64 * ob64 + 16 * ct + (lane & 15);
   const int c0 = 128 * gi + 32 * (lane >> 4) + 8 * e8;  // eight consecutive input channels, inside one 32-bit word
@@ -574,9 +543,9 @@ size_t weight_f4_bytes(int O, int C, int KH, int KW) {
 
 int launch_pack_weight_f4(const uint32_t* wbits, const uint32_t* wnz, const bnn_hip_wlayout& L, int O, void* w4,
                           hipStream_t s) {
-  const size_t dwords = (size_t)O * (L.cw32 >> 2) * 9 * 16;
-  hipLaunchKernelGGL(pack_weight_f4_kernel, dim3((unsigned)((dwords + 255) / 256)), dim3(256), 0, s, wbits, wnz, O, L.cw32,
-                     L.cwc, static_cast<uint32_t*>(w4));
+  const size_t dwords = (size_t)O * (L.cw32 >> 2) * L.taps * 16;  // (taps = 1: the pack of bconv1x1_mfma.hip)
+  hipLaunchKernelGGL(pack_weight_f4_kernel, dim3((unsigned)((dwords + 255) / 256)), dim3(256), 0, s, wbits, wnz, O, L.taps,
+                     L.cw32, L.cwc, static_cast<uint32_t*>(w4));
   return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
 }
 

@@ -215,10 +215,16 @@ bool mfma_conv_applies(const ConvP& p, int flags);
 // f4: the FP4 form (v_mfma_f32_16x16x128_f8f6f4, C % 128 == 0), `w8` then the pack of launch_pack_weight_f4
 int launch_bconv_mfma(const ConvP& p, int flags, const void* w8, hipStream_t s, bool f4);
 size_t weight_f4_bytes(int O, int C, int KH, int KW);
+// (L.taps = 9, or 1 for the pack of bconv1x1_mfma.hip)
 int launch_pack_weight_f4(const uint32_t* wbits, const uint32_t* wnz, const bnn_hip_wlayout& L, int O, void* w4,
                           hipStream_t s);
 bool mfma4_conv_applies(const ConvP& p, int flags);
 bool mfma4_fold_applies(const ConvP& p, int flags);
+// bconv1x1_mfma.hip: the dense 1x1 convolution on the same FP4 instruction, every epilogue of bnn_hip_bconv2d_fused.
+// `w4`: launch_pack_weight_f4 with the layout of the 1x1 weight (one tap), weight1x1_f4_bytes(O, C) = O C / 2 bytes
+size_t weight1x1_f4_bytes(int O, int C);
+bool mfma1x1_applies(const ConvP& p, int flags);
+int launch_bconv1x1_mfma(const ConvP& p, int flags, const void* w4, hipStream_t s);
 // the same with the shortcut convolution folded in (p.ds_*; p.ds_W is not read: the 1x1 weight comes as its int8 pack)
 size_t shortcut_weight_i8_bytes(int O, int C);
 int launch_pack_shortcut_weight_i8(const uint32_t* wbits, int O, int C, void* w8, hipStream_t s);

@@ -1099,20 +1099,29 @@ int bnn_hip_pack_weight_i8(const uint32_t* wbits, const uint32_t* wnz, int O, in
   return bnn::launch_pack_weight_i8(wbits, wnz, L, O, w8, static_cast<hipStream_t>(stream));
 }
 
-// The int8 and the FP4 (f4) entry points share their validation: only the admission rule and the kernel differ.
+// The int8, the FP4 and the 1x1 FP4 entry points share their validation.
 namespace {
-int mfma_supported(const bnn_hip_conv_desc* d, const bnn_hip_epilogue* e, bool f4) {
+// form: the kernel a call is for — the 3x3 kernel in its int8 or its FP4 form (bconv_mfma.hip), or the 1x1 FP4 kernel
+// (bconv1x1_mfma.hip).  Only the admission rule and the launcher differ.
+enum { kMfmaI8 = 0, kMfmaF4 = 1, kMfma1x1F4 = 2 };
+bool mfma_applies(const bnn::ConvP& p, int flags, int form) {
+  return form == kMfma1x1F4 ? bnn::mfma1x1_applies(p, flags)
+         : form == kMfmaF4  ? bnn::mfma4_conv_applies(p, flags)
+                            : bnn::mfma_conv_applies(p, flags);
+}
+
+int mfma_supported(const bnn_hip_conv_desc* d, const bnn_hip_epilogue* e, int form) {
   alignas(16) static const uint64_t operand[2] = {0, 0};  // stands in for the packed operands (never read)
   bnn::ConvP p = empty_convp();
   if (epilogue_convp(e, &p) != BNN_HIP_OK) return 0;
   const uint32_t* const w = reinterpret_cast<const uint32_t*>(operand);
   if (check_conv(d, operand, operand, w, w, &p) != BNN_HIP_OK) return 0;
   if (p.out && !aligned(p.out, 4)) return 0;
-  return (f4 ? bnn::mfma4_conv_applies(p, d->flags) : bnn::mfma_conv_applies(p, d->flags)) ? 1 : 0;
+  return mfma_applies(p, d->flags, form) ? 1 : 0;
 }
 
 int mfma_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const void* w8,
-               const bnn_hip_epilogue* e, void* stream, bool f4) {
+               const bnn_hip_epilogue* e, void* stream, int form) {
   bnn::ConvP p = empty_convp();
   int st = epilogue_convp(e, &p);
   if (st != BNN_HIP_OK) return st;
@@ -1121,20 +1130,21 @@ int mfma_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M,
   st = check_conv(d, P, M, static_cast<const uint32_t*>(w8), static_cast<const uint32_t*>(w8), &p);
   if (st != BNN_HIP_OK) return st;
   if (p.out && !aligned(p.out, 4)) return BNN_HIP_ERR_INVALID_ARG;
-  if (!(f4 ? bnn::mfma4_conv_applies(p, d->flags) : bnn::mfma_conv_applies(p, d->flags))) return BNN_HIP_ERR_UNSUPPORTED;
+  if (!mfma_applies(p, d->flags, form)) return BNN_HIP_ERR_UNSUPPORTED;
   g_launches.fetch_add(1, std::memory_order_relaxed);
   BNN_RANGE();
-  return bnn::launch_bconv_mfma(p, d->flags, w8, static_cast<hipStream_t>(stream), f4);
+  if (form == kMfma1x1F4) return bnn::launch_bconv1x1_mfma(p, d->flags, w8, static_cast<hipStream_t>(stream));
+  return bnn::launch_bconv_mfma(p, d->flags, w8, static_cast<hipStream_t>(stream), form == kMfmaF4);
 }
 }  // namespace
 
 int bnn_hip_bconv2d_mfma_supported(const bnn_hip_conv_desc* d, const bnn_hip_epilogue* e) {
-  return mfma_supported(d, e, false);
+  return mfma_supported(d, e, kMfmaI8);
 }
 
 int bnn_hip_bconv2d_mfma_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const void* w8,
                                const bnn_hip_epilogue* e, void* stream) {
-  return mfma_fused(d, P, M, w8, e, stream, false);
+  return mfma_fused(d, P, M, w8, e, stream, kMfmaI8);
 }
 
 // ---- the FP4 form (bnn_hip_pack_weight_f4's pack in place of the int8 one) ----
@@ -1154,12 +1164,37 @@ int bnn_hip_pack_weight_f4(const uint32_t* wbits, const uint32_t* wnz, int O, in
 }
 
 int bnn_hip_bconv2d_mfma4_supported(const bnn_hip_conv_desc* d, const bnn_hip_epilogue* e) {
-  return mfma_supported(d, e, true);
+  return mfma_supported(d, e, kMfmaF4);
 }
 
 int bnn_hip_bconv2d_mfma4_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const void* w4,
                                 const bnn_hip_epilogue* e, void* stream) {
-  return mfma_fused(d, P, M, w4, e, stream, true);
+  return mfma_fused(d, P, M, w4, e, stream, kMfmaF4);
+}
+
+// ---- the 1x1 convolution on the FP4 matrix cores (csrc/bconv1x1_mfma.hip) ----
+size_t bnn_hip_weight1x1_f4_bytes(int O, int C) { return bnn::weight1x1_f4_bytes(O, C); }
+
+int bnn_hip_pack_weight1x1_f4(const uint32_t* wbits, const uint32_t* wnz, int O, int C, int KH, int KW, void* w4,
+                              void* stream) {
+  if (!wbits || !wnz || !w4) return BNN_HIP_ERR_INVALID_ARG;
+  bnn_hip_wlayout L;
+  const int st = bnn_hip_weight_layout(O, C, KH, KW, &L);
+  if (st != BNN_HIP_OK) return st;
+  if (KH != 1 || KW != 1 || bnn::weight1x1_f4_bytes(O, C) == 0) return BNN_HIP_ERR_UNSUPPORTED;
+  if (!aligned(wbits, 16) || !aligned(wnz, 16) || !aligned(w4, 16)) return BNN_HIP_ERR_INVALID_ARG;
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  BNN_RANGE();
+  return bnn::launch_pack_weight_f4(wbits, wnz, L, O, w4, static_cast<hipStream_t>(stream));  // (the 3x3 pack's, one tap)
+}
+
+int bnn_hip_bconv1x1_mfma4_supported(const bnn_hip_conv_desc* d, const bnn_hip_epilogue* e) {
+  return mfma_supported(d, e, kMfma1x1F4);
+}
+
+int bnn_hip_bconv1x1_mfma4_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const void* w4,
+                                 const bnn_hip_epilogue* e, void* stream) {
+  return mfma_fused(d, P, M, w4, e, stream, kMfma1x1F4);
 }
 
 // ---- the same with the shortcut convolution folded in ----

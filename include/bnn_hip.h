@@ -61,7 +61,9 @@
 extern "C" {
 #endif
 
-/* Additive entry points of ABI 16 for the BATS FactorizedConv (no struct or signature changed): + bnn_hip_fconv_desc,
+/* Additive entry points of ABI 16 for the 1x1 convolution on the FP4 matrix cores (no struct or signature changed):
+ * + bnn_hip_weight1x1_f4_bytes, bnn_hip_pack_weight1x1_f4, bnn_hip_bconv1x1_mfma4_supported, bnn_hip_bconv1x1_mfma4_fused.
+ * Additive entry points of ABI 16 for the BATS FactorizedConv (no struct or signature changed): + bnn_hip_fconv_desc,
  * bnn_hip_fconv_stage, bnn_hip_fconv_supported, bnn_hip_fconv_fused (csrc/fconv.hip).
  * Additive entry points of ABI 16 for the Linear with binary activations and real weights (no struct or signature
  * changed): + bnn_hip_slinear_f32, bnn_hip_ste_mask_f32 (csrc/slinear.hip).
@@ -597,6 +599,35 @@ int bnn_hip_bconv2d_mfma4_fused(const bnn_hip_conv_desc* d, const uint64_t* P, c
 int bnn_hip_bconv2d_mfma4_fold_supported(const bnn_hip_conv_desc* d, const bnn_hip_epilogue* epi);
 int bnn_hip_bconv2d_mfma4_fold_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const void* w4,
                                      const void* sc_w8, const bnn_hip_epilogue* epi, void* stream);
+
+/* ---- The dense 1x1 convolution on the FP4 matrix-core instruction (additive entry points of ABI 16, no struct or
+ * signature changed; csrc/bconv1x1_mfma.hip).  The launch of bnn_hip_bconv2d_fused for KH = KW = 1 as a plain GEMM
+ * [O, C] x [C, N H W] on v_mfma_f32_16x16x128_f8f6f4 with E2M1 operands: every partial sum is an integer of magnitude
+ * <= C < 2^24, exact in fp32 in any order, and the accumulator converted to int enters the popcount kernels' epilogue, so
+ * every output bit equals bnn_hip_bconv2d_fused's.
+ *
+ * Covered (bnn_hip_bconv1x1_mfma4_supported == 1): KH = KW = 1, stride 1, padding 0, dilation 1, C % 128 == 0,
+ * O % 64 == 0, sizes within the limits of the tiled popcount kernels, N H W < 2^30; EVERY epilogue of
+ * bnn_hip_bconv2d_fused — alpha [, bias] [, post_scale] [, BatchNorm] [, residual, early or BNN_HIP_EPI_RES_AFTER_ACT]
+ * [, ReLU | PReLU] [, pack_scale / pack_shift] and the other BNN_HIP_EPI_* flags -> fp32 and / or sign planes,
+ * sign_thresholds honoured as in bnn_hip_bconv2d_mfma_fused (BatchNorm + ReLU -> planes only; ignored elsewhere).  Not
+ * covered (BNN_HIP_ERR_UNSUPPORTED, nothing launched): the folded shortcut (sc_*), a channel window (out_c_offset != 0 or
+ * out_c_total != O), BNN_HIP_FLAG_FORCE_GENERIC.  BNN_HIP_FLAG_ACT_NONNEG is honoured (M is not read); the zero weights
+ * of the pack are always honoured, with or without BNN_HIP_FLAG_WEIGHT_ZEROS.
+ *
+ * bnn_hip_pack_weight1x1_f4: wbits / wnz of bnn_hip_pack_weight_f32 for a [O, C, 1, 1] weight -> `w4`,
+ * bnn_hip_weight1x1_f4_bytes(O, C) = O C / 2 bytes (0: O % 64 != 0 or C % 128 != 0), 16-byte aligned; KH = KW = 1, else
+ * BNN_HIP_ERR_UNSUPPORTED.  Byte layout, G = C / 128 — bnn_hip_pack_weight_f4's with one tap:
+ *   w4[o / 64][g][ct][lane][e]   E2M1 nibbles, g < G, ct < 4, lane < 64, e < 32 (nibble e: low / high half of byte e / 2)
+ *       = sign(W[o = 64 (o / 64) + 16 ct + (lane & 15)][c = 128 g + 32 (lane >> 4) + e])   as 0x2 / 0xA / 0x0
+ * The existing queries keep their answers: bnn_hip_weight_f4_bytes(O, C, 1, 1) == 0 and bnn_hip_bconv2d_mfma*_supported
+ * say no to 1x1 weights, to PReLU and to a late residual.                                                              */
+size_t bnn_hip_weight1x1_f4_bytes(int O, int C);
+int bnn_hip_pack_weight1x1_f4(const uint32_t* wbits, const uint32_t* wnz, int O, int C, int KH, int KW, void* w4,
+                              void* stream);
+int bnn_hip_bconv1x1_mfma4_supported(const bnn_hip_conv_desc* d, const bnn_hip_epilogue* epi);
+int bnn_hip_bconv1x1_mfma4_fused(const bnn_hip_conv_desc* d, const uint64_t* P, const uint64_t* M, const void* w4,
+                                 const bnn_hip_epilogue* epi, void* stream);
 
 /* ---- Which kernel a convolution runs (ABI 16): the route of bnn_hip_bconv2d / _fused / _dot, for tests. ----
  * The launch ladder of csrc/bconv.hip picks one instantiation per call from the kernel size, the chunk width, the

@@ -83,7 +83,7 @@ size_t weight_f4_bytes(int O, int C, int KH, int KW) {
 int launch_pack_weight_f4(const uint32_t* wbits, const uint32_t* wnz, const bnn_hip_wlayout& L, int O, void* w4, hipStream_t) {
   ++g_reached;
   REQUIRE(wbits && wnz && w4 && al(wbits, 16) && al(wnz, 16) && al(w4, 16));
-  REQUIRE(O > 0 && O % 64 == 0 && L.taps == 9 && L.cw32 > 0 && L.cw32 % 4 == 0 && L.cwc * L.nchunk == L.cw32 && L.o_pad == O);
+  REQUIRE(O > 0 && O % 64 == 0 && (L.taps == 9 || L.taps == 1) && L.cw32 > 0 && L.cw32 % 4 == 0 && L.cwc * L.nchunk == L.cw32 && L.o_pad == O);
   return BNN_HIP_OK;
 }
 bool mfma4_conv_applies(const ConvP& p, int flags) { return p.C % 128 == 0 && mfma_conv_applies(p, flags); }
@@ -95,6 +95,27 @@ int launch_bconv_mfma(const ConvP& p, int flags, const void* w8, hipStream_t, bo
   REQUIRE(p.P && p.M && w8 && al(p.P, 16) && al(p.M, 16) && al(w8, 16) && p.alpha);
   REQUIRE(p.out || (p.outP && p.outM));
   REQUIRE((p.bn_a == nullptr) == (p.bn_b == nullptr) && (p.outP == nullptr) == (p.outM == nullptr));
+  REQUIRE(!p.outP || (al(p.outP, 8) && al(p.outM, 8)));
+  REQUIRE(!p.out || al(p.out, 4));
+  return BNN_HIP_OK;
+}
+// the 1x1 convolution on the FP4 matrix cores (csrc/bconv1x1_mfma.hip)
+size_t weight1x1_f4_bytes(int O, int C) { return (O > 0 && C > 0 && O % 64 == 0 && C % 128 == 0) ? (size_t)O * (size_t)C / 2 : 0; }
+bool mfma1x1_applies(const ConvP& p, int flags) {
+  check_convp(p);
+  return p.KH == 1 && p.KW == 1 && p.sh == 1 && p.sw == 1 && p.ph == 0 && p.pw == 0 && p.dh == 1 && p.dw == 1 &&
+         weight1x1_f4_bytes(p.O, p.C) != 0 && !p.ds_P && p.c_off == 0 && p.c_tot == p.O &&
+         !(flags & BNN_HIP_FLAG_FORCE_GENERIC);
+}
+int launch_bconv1x1_mfma(const ConvP& p, int flags, const void* w4, hipStream_t) {
+  ++g_reached;
+  check_convp(p);
+  REQUIRE(mfma1x1_applies(p, flags));
+  REQUIRE((long long)p.N * p.H * p.Wd * ((p.C + 63) / 64) <= kPlaneWords);
+  REQUIRE(p.P && p.M && w4 && al(p.P, 16) && al(p.M, 16) && al(w4, 16) && p.alpha);
+  REQUIRE(p.out || (p.outP && p.outM));
+  REQUIRE((p.bn_a == nullptr) == (p.bn_b == nullptr) && (p.outP == nullptr) == (p.outM == nullptr));
+  REQUIRE((p.pack_a == nullptr) == (p.pack_b == nullptr));
   REQUIRE(!p.outP || (al(p.outP, 8) && al(p.outM, 8)));
   REQUIRE(!p.out || al(p.out, 4));
   return BNN_HIP_OK;
@@ -1114,6 +1135,20 @@ int main(int argc, char** argv) {
           const int sp4 = bnn_hip_pack_weight_f4(pick_ptr<uint32_t>(), pick_ptr<uint32_t>(), d.O, d.C, d.KH, d.KW, pick_ptr<char>(), stream);
           if (!status_ok(sp4)) broken("FP4 weight pack status");
           digest = (digest ^ (uint64_t)(uint32_t)sm4 ^ ((uint64_t)(uint32_t)sf4 << 32) ^ (uint64_t)(sup4 + 2 * fsup4 + 4 * sp4)) * 0x100000001B3ull;
+          // the 1x1 form: a query and a launch that agree, a pack only where there is a size for it.  (Its picks replay
+          // the generator from here: every other call of a run sees the arguments it saw before this block existed.)
+          const uint64_t rng_here = g_rng;
+          const int sup1 = bnn_hip_bconv1x1_mfma4_supported(dp, ep);
+          if (sup1 != 0 && sup1 != 1) broken("mfma 1x1 supported");
+          if (sup1 && (d.KH != 1 || d.KW != 1 || d.C % 128 != 0 || d.O % 64 != 0 || sup || fsup)) broken("mfma 1x1 took another shape");
+          const int sm1 = bnn_hip_bconv1x1_mfma4_fused(dp, pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<char>(), ep, stream);
+          if (!status_ok(sm1) || (sm1 == BNN_HIP_OK && !sup1)) broken("mfma 1x1 launched where the query said no");
+          const size_t b1 = bnn_hip_weight1x1_f4_bytes(d.O, d.C);
+          if (b1 != 0 && (2 * b1 != (size_t)d.O * (size_t)d.C || b4 != 0 && 9 * b1 != b4)) broken("FP4 1x1 weight pack size");
+          const int sp1 = bnn_hip_pack_weight1x1_f4(pick_ptr<uint32_t>(), pick_ptr<uint32_t>(), d.O, d.C, d.KH, d.KW, pick_ptr<char>(), stream);
+          if (!status_ok(sp1) || (sp1 == BNN_HIP_OK && (b1 == 0 || d.KH != 1 || d.KW != 1))) broken("FP4 1x1 weight pack status");
+          digest = (digest ^ (uint64_t)(uint32_t)sm1 ^ ((uint64_t)(uint32_t)sp1 << 32) ^ (uint64_t)sup1) * 0x100000001B3ull;
+          g_rng = rng_here;
         }
         st = bnn_hip_blinear(pick_int(), pick_int(), pick_int(), pick_ptr<uint64_t>(), pick_ptr<uint64_t>(), pick_ptr<uint32_t>(),
                              pick_ptr<uint32_t>(), pick_int(), pick_ptr<float>(), pick_ptr<float>(), pick_ptr<float>(),
