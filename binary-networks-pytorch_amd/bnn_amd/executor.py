@@ -27,13 +27,14 @@ import contextlib
 import itertools
 import os
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Tuple, Union
+from typing import Dict, List, NamedTuple, Optional, Tuple, Union
 
 import torch
 import torch.nn as nn
 import torch.nn.modules.module as _mm
 
 from . import fastpath, hipops, native
+from .fastpath import Form
 from .layers import Conv2d as BinaryConv2d
 from .models.blocks import BasicBlock, Bottleneck, HBlock, PreBasicBlock, PreBottleneck
 from .models.resnet import ResNet
@@ -100,6 +101,34 @@ def tap_binary_inputs(fn):
         _TAP = prev
 
 
+class RouteKey(NamedTuple):
+    """One launch of a ``_Conv`` as ``_Conv.route`` sees it: all it asks about beyond the layer's own constants."""
+    shape: Tuple[int, ...]                 # of the input planes
+    nonneg: bool                           # the planes are non-negative (M is not read)
+    residual: bool                         # an fp32 residual is added
+    out_f32: bool
+    out_packed: bool
+    thr: bool                              # the sign bit comes from integer thresholds
+    epi: Tuple[str, ...]                   # the ``epi`` switches that are on, sorted
+    epi_off: Tuple[str, ...]               # those given as ``None`` / ``False``, sorted: present all the same
+    shortcut: Optional[Tuple[int, ...]]    # shape of the folded shortcut's planes
+    shortcut_w8: bool                      # the shortcut's weight has an int8 pack
+    throughput: bool
+
+
+# the ``epi`` switches a 1x1 launch on the FP4 kernel may carry -> their BNN_HIP_EPI_* flag (None: a tensor, no flag)
+_EPI_1X1 = {"residual_after_act": native.EPI_RES_AFTER_ACT, "pack_before_residual": native.EPI_PACK_BEFORE_RES,
+            "pack_relu": native.EPI_PACK_RELU, "pack_scale": None, "pack_shift": None}
+
+# form -> (the ``hipops`` launch, the form under which ``_Conv.packs`` holds its weight pack, takes the shortcut's int8 pack)
+_LAUNCH = {Form.POPCOUNT: ("bconv2d_fused", None, False),
+           Form.I8_3X3: ("bconv2d_mfma_fused", Form.I8_3X3, False),
+           Form.F4_3X3: ("bconv2d_mfma4_fused", Form.F4_3X3, False),
+           Form.I8_FOLD: ("bconv2d_mfma_fold_fused", Form.I8_3X3, True),
+           Form.F4_FOLD: ("bconv2d_mfma4_fold_fused", Form.F4_3X3, True),
+           Form.F4_1X1: ("bconv1x1_mfma4_fused", Form.F4_1X1, False)}
+
+
 @dataclass
 class _Conv:
     layer: BinaryConv2d
@@ -112,103 +141,77 @@ class _Conv:
     name: str = ""
     throughput: bool = False   # BNN_HIP_FLAG_THROUGHPUT: several batches in flight (PipelinedInference)
     thr: Optional[torch.Tensor] = None   # integer sign thresholds of a BN + ReLU -> planes-only epilogue
-    w8: Optional[torch.Tensor] = None    # int8 MFMA pack of the weight (csrc/bconv_mfma.hip), built with the plan
-    mfma: dict = field(default_factory=dict)   # (geometry, epilogue) -> this launch runs on the int8 matrix cores
+    # the matrix-core packs of the weight, built with the plan: I8_3X3 / F4_3X3 (csrc/bconv_mfma.hip; the fold forms read
+    # them too) and F4_1X1 (csrc/bconv1x1_mfma.hip).  A form without an entry has no pack for this weight
+    packs: Dict[Form, torch.Tensor] = field(default_factory=dict)
     sc_w8: Optional[torch.Tensor] = None  # a block's shortcut convolution: int8 pack of its 1x1 weight (built with the plan)
-    mfma_fold: dict = field(default_factory=dict)   # geometry -> this launch, with its shortcut folded in, does too
-    w4: Optional[torch.Tensor] = None    # FP4 MFMA pack of the weight (the F4 form of the same kernel), built with the plan
-    f4: dict = field(default_factory=dict)   # the keys of ``mfma`` / ``mfma_fold`` -> that matrix-core launch is the FP4 form
-    w4_1x1: Optional[torch.Tensor] = None    # FP4 pack of a 1x1 weight (csrc/bconv1x1_mfma.hip), built with the plan
-    mfma_1x1: dict = field(default_factory=dict)   # (geometry, epilogue) -> this 1x1 launch runs on the FP4 matrix cores
+    routes: Dict[RouteKey, Form] = field(default_factory=dict)   # the form of each launch seen so far, decided once
 
-    def _on_matrix_cores(self, act: hipops.PackedAct, residual, out_f32: bool, out_packed: bool, thr, epi):
-        """The admission of one launch to the MFMA convolution: the table of ``fastpath`` (shapes that measured faster)
-        and the kernel's own query, asked once per geometry.  The pre-activation switches and the folded shortcut
-        (``epi``) stay on the popcount kernels.  Returns (on the matrix cores, in the FP4 form): an admitted launch asks
-        ``fastpath.mfma_f4_admitted`` and ``bnn_hip_bconv2d_mfma4_supported`` the same way."""
-        if self.w8 is None or epi:
-            return False, False
-        key = (tuple(act.shape), act.nonneg, residual is not None, out_f32, out_packed, thr is not None)
-        ok = self.mfma.get(key)
-        if ok is None:
-            lay = self.layer
+    def route(self, act: hipops.PackedAct, residual, out_f32: bool, out_packed: bool, thr, epi, shortcut_w8) -> Form:
+        """The kernel form of one launch, decided once per ``RouteKey``: the switches and tables of ``fastpath`` (shapes
+        that measured faster) and the kernels' own queries.  Each form needs all of its line:
+
+        * ``F4_1X1``: the 1x1 FP4 pack exists; every key of ``epi`` is one of ``_EPI_1X1`` (so not a channel window, a
+          caller's ``out`` or the folded shortcut); ``pack_scale`` and ``pack_shift`` are both on or both off;
+          ``fastpath.mfma_1x1_admitted``; ``bconv1x1_mfma4_supported`` for this epilogue, flags and pack affine included.
+        * ``I8_3X3`` / ``F4_3X3``: the int8 pack exists; ``epi`` has no key at all, on or off;
+          ``fastpath.mfma_conv_admitted``; ``bconv2d_mfma_supported``.
+        * ``I8_FOLD`` / ``F4_FOLD``: no residual; the int8 pack and ``shortcut_w8`` exist; ``epi`` is exactly the shortcut;
+          fp32 and planes are both written; the layer has no bias and no post-scale, a BatchNorm, ReLU, no PReLU and a 3x3
+          kernel; ``fastpath.mfma_fold_admitted``; ``bconv2d_mfma_fold_supported``.
+        * ``POPCOUNT`` otherwise.
+
+        A 3x3 or fold launch so admitted takes the FP4 form where the FP4 pack exists too and ``fastpath.mfma_f4_admitted``
+        (its dense or fold key) and the form's ``mfma4`` query say yes.  No launch meets two of the lines — a weight has
+        a 1x1 pack or 3x3 packs, never both, and the 3x3 and fold lines want a different ``epi`` — so their order is moot."""
+        on, off, sc = (), (), None
+        if epi:
+            on = tuple(sorted([name for name, v in epi.items() if v is not None and v is not False]))
+            off = tuple(sorted(set(epi).difference(on))) if len(on) != len(epi) else ()
+            sc = tuple(epi["shortcut"][0].shape) if "shortcut" in on else None
+        k = RouteKey(tuple(act.shape), act.nonneg, residual is not None, out_f32, out_packed, thr is not None, on, off, sc,
+                     shortcut_w8 is not None, self.throughput)
+        form = self.routes.get(k)
+        if form is None:
+            form = self.routes[k] = self._decide(k)
+        return form
+
+    def _decide(self, k: RouteKey) -> Form:
+        lay, packs, w = self.layer, self.packs, self.weight
+        C, O, H = k.shape[1], lay.out_channels, k.shape[2]
+        names = set(k.epi + k.epi_off)
+        f4 = Form.F4_3X3 in packs
+        if Form.F4_1X1 in packs and names <= set(_EPI_1X1):
+            flags = sum(_EPI_1X1[name] or 0 for name in k.epi)      # one bit each
+            affine = "pack_scale" in k.epi
+            if (affine == ("pack_shift" in k.epi) and fastpath.mfma_1x1_admitted(C, O, H, k.out_f32, k.nonneg)
+                    and hipops.bconv1x1_mfma4_supported(k.shape, w, **self._epilogue(k), epi_flags=flags, pack_affine=affine)):
+                return Form.F4_1X1
+        if Form.I8_3X3 in packs and not names:
             stride = lay.stride[0] if isinstance(lay.stride, (tuple, list)) else lay.stride
-            ok = self.mfma[key] = (
-                fastpath.mfma_conv_admitted(act.shape[1], lay.out_channels, act.shape[2], stride, False)
-                and hipops.bconv2d_mfma_supported(
-                    act.shape, self.weight, nonneg=act.nonneg, bias=lay.bias is not None,
-                    post_scale=self.plan.scale is not None, bn=self.bn_scale is not None, residual=residual is not None,
-                    prelu=self.prelu is not None, relu=self.relu, out_f32=out_f32, out_packed=out_packed,
-                    stride=lay.stride, padding=lay.padding, dilation=lay.dilation, sign_thresholds=thr is not None))
-            self.f4[key] = bool(
-                ok and self.w4 is not None
-                and fastpath.mfma_f4_admitted((act.shape[1], lay.out_channels, act.shape[2], stride, False))
-                and hipops.bconv2d_mfma4_supported(
-                    act.shape, self.weight, nonneg=act.nonneg, bias=lay.bias is not None,
-                    post_scale=self.plan.scale is not None, bn=self.bn_scale is not None, residual=residual is not None,
-                    prelu=self.prelu is not None, relu=self.relu, out_f32=out_f32, out_packed=out_packed,
-                    stride=lay.stride, padding=lay.padding, dilation=lay.dilation, sign_thresholds=thr is not None))
-        return ok, ok and self.f4[key]
+            key, desc = (C, O, H, stride, False), self._epilogue(k)
+            if fastpath.mfma_conv_admitted(*key) and hipops.bconv2d_mfma_supported(k.shape, w, **desc):
+                f4 = f4 and fastpath.mfma_f4_admitted(key) and hipops.bconv2d_mfma4_supported(k.shape, w, **desc)
+                return Form.F4_3X3 if f4 else Form.I8_3X3
+        if (Form.I8_3X3 in packs and names == {"shortcut"} and k.shortcut is not None and k.shortcut_w8 and not k.residual
+                and k.out_f32 and k.out_packed and lay.bias is None and self.plan.scale is None and self.bn_scale is not None
+                and self.relu and self.prelu is None and tuple(lay.kernel_size) == (3, 3)):
+            sc_C, sc_hw = k.shortcut[1], k.shortcut[2:]
+            pooled = sc_hw == tuple(hipops.conv_out_hw(H, k.shape[3], 3, 3, lay.stride, lay.padding, lay.dilation))
+            key, desc = (C, O, H, sc_C), dict(nonneg=k.nonneg, stride=lay.stride, padding=lay.padding, dilation=lay.dilation,
+                                              unpooled_hw=None if pooled else sc_hw, throughput=k.throughput)
+            if fastpath.mfma_fold_admitted(*key) and hipops.bconv2d_mfma_fold_supported(k.shape, w, sc_C, **desc):
+                f4 = f4 and fastpath.mfma_f4_admitted(key) and hipops.bconv2d_mfma4_fold_supported(k.shape, w, sc_C, **desc)
+                return Form.F4_FOLD if f4 else Form.I8_FOLD
+        return Form.POPCOUNT
 
-    def _fold_on_matrix_cores(self, act: hipops.PackedAct, out_f32: bool, out_packed: bool, epi, sc_w8):
-        """The same for a launch with the block's shortcut folded in (``epi`` is exactly the shortcut): the table of
-        ``fastpath.MFMA_FOLD_SHAPES`` and ``bnn_hip_bconv2d_mfma_fold_supported``, asked once per geometry."""
-        if self.w8 is None or sc_w8 is None or set(epi) != {"shortcut"} or not (out_f32 and out_packed):
-            return False, False
-        sa = epi["shortcut"][0]
-        key = (tuple(act.shape), act.nonneg, tuple(sa.shape), self.throughput)
-        ok = self.mfma_fold.get(key)
-        if ok is None:
-            lay = self.layer
-            pooled = tuple(sa.shape[2:]) == tuple(hipops.conv_out_hw(act.shape[2], act.shape[3], 3, 3, lay.stride,
-                                                                     lay.padding, lay.dilation))
-            ok = self.mfma_fold[key] = bool(
-                lay.bias is None and self.plan.scale is None and self.bn_scale is not None and self.relu
-                and self.prelu is None and tuple(lay.kernel_size) == (3, 3)
-                and fastpath.mfma_fold_admitted(act.shape[1], lay.out_channels, act.shape[2], sa.shape[1])
-                and hipops.bconv2d_mfma_fold_supported(
-                    act.shape, self.weight, sa.shape[1], nonneg=act.nonneg, stride=lay.stride, padding=lay.padding,
-                    dilation=lay.dilation, unpooled_hw=None if pooled else tuple(sa.shape[2:]),
-                    throughput=self.throughput))
-            self.f4[key] = bool(
-                ok and self.w4 is not None
-                and fastpath.mfma_f4_admitted((act.shape[1], lay.out_channels, act.shape[2], sa.shape[1]))
-                and hipops.bconv2d_mfma4_fold_supported(
-                    act.shape, self.weight, sa.shape[1], nonneg=act.nonneg, stride=lay.stride, padding=lay.padding,
-                    dilation=lay.dilation, unpooled_hw=None if pooled else tuple(sa.shape[2:]),
-                    throughput=self.throughput))
-        return ok, ok and self.f4[key]
-
-    # the ``epi`` switches a 1x1 launch on the FP4 kernel may carry -> their BNN_HIP_EPI_* flag (None: a tensor, no flag)
-    _EPI_1X1 = {"residual_after_act": native.EPI_RES_AFTER_ACT, "pack_before_residual": native.EPI_PACK_BEFORE_RES,
-                "pack_relu": native.EPI_PACK_RELU, "pack_scale": None, "pack_shift": None}
-
-    def _1x1_on_matrix_cores(self, act: hipops.PackedAct, residual, out_f32: bool, out_packed: bool, thr, epi) -> bool:
-        """The admission of one 1x1 launch to the FP4 kernel of csrc/bconv1x1_mfma.hip: the tables of ``fastpath``
-        (``MFMA_1X1_SHAPES`` / ``MFMA_1X1_TERNARY_SHAPES``) and the kernel's own query
-        (``bnn_hip_bconv1x1_mfma4_supported``), asked once per geometry and epilogue.  Unlike ``_on_matrix_cores`` it admits
-        the pre-activation switches — the late residual and the pack affine of a PreBottleneck's launches; a channel
-        window, a caller's ``out`` and the folded shortcut stay on the popcount kernels."""
-        if self.w4_1x1 is None or not set(epi) <= set(self._EPI_1X1):
-            return False
-        on = {k for k, v in epi.items() if v is not None and v is not False}
-        key = (tuple(act.shape), act.nonneg, residual is not None, out_f32, out_packed, thr is not None, tuple(sorted(on)))
-        ok = self.mfma_1x1.get(key)
-        if ok is None:
-            lay = self.layer
-            flags = 0
-            for k in on:
-                flags |= self._EPI_1X1[k] or 0
-            ok = self.mfma_1x1[key] = bool(
-                ("pack_scale" in on) == ("pack_shift" in on)
-                and fastpath.mfma_1x1_admitted(act.shape[1], lay.out_channels, act.shape[2], out_f32, act.nonneg)
-                and hipops.bconv1x1_mfma4_supported(
-                    act.shape, self.weight, nonneg=act.nonneg, bias=lay.bias is not None,
-                    post_scale=self.plan.scale is not None, bn=self.bn_scale is not None, residual=residual is not None,
-                    prelu=self.prelu is not None, relu=self.relu, out_f32=out_f32, out_packed=out_packed,
-                    stride=lay.stride, padding=lay.padding, dilation=lay.dilation, sign_thresholds=thr is not None,
-                    epi_flags=flags, pack_affine="pack_scale" in on))
-        return ok
+    def _epilogue(self, k: RouteKey) -> dict:
+        """The launch ``k`` of this layer as the ``*_supported`` queries of ``hipops`` take it: what its epilogue contains."""
+        lay = self.layer
+        return dict(nonneg=k.nonneg, bias=lay.bias is not None, post_scale=self.plan.scale is not None,
+                    bn=self.bn_scale is not None, residual=k.residual, prelu=self.prelu is not None, relu=self.relu,
+                    out_f32=k.out_f32, out_packed=k.out_packed, stride=lay.stride, padding=lay.padding,
+                    dilation=lay.dilation, sign_thresholds=k.thr)
 
     def run(self, act: hipops.PackedAct, *, residual=None, out_f32: bool, out_packed: bool, shortcut_w8=None, **epi):
         """``epi``: the pre-activation switches of ``hipops.bconv2d_fused`` (late residual, pack affine, ...);
@@ -222,20 +225,9 @@ class _Conv:
                     bn_shift=self.bn_shift, residual=residual, prelu=self.prelu, relu=self.relu,
                     out_f32=out_f32, out_packed=out_packed, stride=lay.stride, padding=lay.padding,
                     dilation=lay.dilation, throughput=self.throughput, sign_thresholds=thr, **epi)
-        if self._1x1_on_matrix_cores(act, residual, out_f32, out_packed, thr, epi):
-            return hipops.bconv1x1_mfma4_fused(act, self.weight, self.w4_1x1, **args)
-        on, f4 = self._on_matrix_cores(act, residual, out_f32, out_packed, thr, epi)
-        if on:
-            if f4:
-                return hipops.bconv2d_mfma4_fused(act, self.weight, self.w4, **args)
-            return hipops.bconv2d_mfma_fused(act, self.weight, self.w8, **args)
-        if residual is None:
-            on, f4 = self._fold_on_matrix_cores(act, out_f32, out_packed, epi, shortcut_w8)
-            if on and f4:
-                return hipops.bconv2d_mfma4_fold_fused(act, self.weight, self.w4, shortcut_w8, **args)
-            if on:
-                return hipops.bconv2d_mfma_fold_fused(act, self.weight, self.w8, shortcut_w8, **args)
-        return hipops.bconv2d_fused(act, self.weight, **args)
+        launch, pack, fold = _LAUNCH[self.route(act, residual, out_f32, out_packed, thr, epi, shortcut_w8)]
+        packs = (() if pack is None else (self.packs[pack],)) + ((shortcut_w8,) if fold else ())
+        return getattr(hipops, launch)(act, self.weight, *packs, **args)
 
 
 def _plan_of(conv: nn.Module) -> fastpath.Plan:
@@ -434,15 +426,17 @@ class FusedResNet(nn.Module):
         if (self.int_thresholds and scale is not None and relu and prelu is None and conv.bias is None
                 and plan.scale is None and not pw.has_zero):
             thr = hipops.sign_thresholds(pw, scale, shift)
-        # the int8 form of a 3x3 weight, when the switch admits any launch at all (None: no such form for this weight)
-        w8 = hipops.pack_weight_i8(pw) if fastpath.MFMA_CONV != "0" and tuple(pw.shape[2:]) == (3, 3) else None
-        # and its FP4 form (None as well where C is no multiple of 128)
-        w4 = hipops.pack_weight_f4(pw) if w8 is not None and fastpath.MFMA_F4 != "0" else None
-        # the FP4 form of a 1x1 weight (None where O is no multiple of 64 or C none of 128)
-        w4_1x1 = (hipops.pack_weight1x1_f4(pw) if fastpath.MFMA_CONV != "0" and fastpath.MFMA_1X1 != "0"
-                  and tuple(pw.shape[2:]) == (1, 1) else None)
+        # the matrix-core packs the switches make worth building (FP4 of a 3x3 only beside its int8 form)
+        wanted, ksize, packs = fastpath.mfma_packs(), tuple(pw.shape[2:]), {}
+        if Form.I8_3X3 in wanted and ksize == (3, 3):
+            packs[Form.I8_3X3] = hipops.pack_weight_i8(pw)
+            if Form.F4_3X3 in wanted and packs[Form.I8_3X3] is not None:
+                packs[Form.F4_3X3] = hipops.pack_weight_f4(pw)
+        if Form.F4_1X1 in wanted and ksize == (1, 1):
+            packs[Form.F4_1X1] = hipops.pack_weight1x1_f4(pw)
+        packs = {form: pack for form, pack in packs.items() if pack is not None}     # None: no such form for this weight
         return _Conv(conv, plan, pw, scale, shift, relu, prelu, self._names.get(id(conv), ""), self.throughput_mode, thr,
-                     w8, w4=w4, w4_1x1=w4_1x1)
+                     packs)
 
     @staticmethod
     def _sign_through(act: nn.Module):
@@ -592,7 +586,7 @@ class FusedResNet(nn.Module):
         entry.ds = self._conv(conv, bn, None)
         entry.pool = k
         # the int8 form of the shortcut weight, for the fold on the matrix cores (None: no such form, or switched off)
-        if fastpath.MFMA_CONV != "0" and fastpath.MFMA_FOLD != "0":
+        if Form.I8_FOLD in fastpath.mfma_packs():
             entry.ds.sc_w8 = hipops.pack_shortcut_weight_i8(entry.ds.weight)
 
     @torch.no_grad()

@@ -47,6 +47,7 @@ of truth (reference: ``bnn/layers/conv.py:111-112`` shares it with the float mod
 """
 from __future__ import annotations
 
+import enum
 import os
 import threading
 import warnings
@@ -71,6 +72,32 @@ _stats = {"conv2d": 0, "conv1d": 0, "linear": 0, "weight_packs": 0, "conv2d_trai
 # the default is a later decision); BNN_AMD_REAL_WEIGHTS=1 or ``fastpath.REAL_WEIGHTS = True`` turns it on — read at
 # every call (``plan_conv2d_real`` / ``plan_conv2d_real_train``).  With it off nothing here runs.
 REAL_WEIGHTS = os.environ.get("BNN_AMD_REAL_WEIGHTS", "0") == "1"
+
+
+class Form(str, enum.Enum):
+    """The kernel form one binary-convolution launch of the fused ResNet executor takes (``executor._Conv.route``).  A
+    ``str`` too, so that a member hashes in C, as its value does: it is a dict key on every eager launch."""
+    POPCOUNT = "popcount"      # bnn_hip_bconv2d_fused: the XNOR-popcount kernels, every launch no other form admits
+    I8_3X3 = "int8-3x3"        # bnn_hip_bconv2d_mfma_fused
+    F4_3X3 = "fp4-3x3"         # bnn_hip_bconv2d_mfma4_fused
+    I8_FOLD = "int8-fold"      # bnn_hip_bconv2d_mfma_fold_fused: a 3x3 launch with the block's shortcut folded in
+    F4_FOLD = "fp4-fold"       # bnn_hip_bconv2d_mfma4_fold_fused
+    F4_1X1 = "fp4-1x1"         # bnn_hip_bconv1x1_mfma4_fused
+
+
+def _admitted(own: str, key: tuple, table: dict, parents: tuple = ()) -> bool:
+    """The switch rule of every matrix-core form, in one place.  ``own``: the form's switch; ``parents``: the switches
+    that turn it off too.  "0" in any of them -> no; else ``own == "all"`` -> yes; else ("1") -> ``key`` is in ``table``."""
+    return "0" not in (own, *parents) and (own == "all" or key in table)
+
+
+def mfma_packs() -> frozenset:
+    """The forms whose weight pack is worth building under the current switches, asked when an executor plans its layers:
+    ``I8_3X3`` / ``F4_3X3`` — the int8 / FP4 pack of a 3x3 weight; ``I8_FOLD`` — the int8 pack of a shortcut's 1x1 weight;
+    ``F4_1X1`` — the FP4 pack of a 1x1 weight."""
+    own = {Form.I8_3X3: MFMA_CONV, Form.F4_3X3: MFMA_F4, Form.I8_FOLD: MFMA_FOLD, Form.F4_1X1: MFMA_1X1}
+    return frozenset(form for form, switch in own.items() if "0" not in (switch, MFMA_CONV))
+
 
 # The dense 3x3 convolutions of the fused ResNet executor on the int8 matrix cores (csrc/bconv_mfma.hip: the same integer
 # dot from v_mfma_i32_16x16x64_i8, the same float epilogue, the same bits) instead of the XNOR-popcount kernels.
@@ -97,9 +124,7 @@ MFMA_CONV_SHAPES = {
 
 
 def mfma_conv_admitted(C: int, O: int, H: int, stride: int, fold: bool) -> bool:
-    if MFMA_CONV == "0":
-        return False
-    return MFMA_CONV == "all" or (C, O, H, stride, fold) in MFMA_CONV_SHAPES
+    return _admitted(MFMA_CONV, (C, O, H, stride, fold), MFMA_CONV_SHAPES)
 
 
 # The same for the last convolution of a down-sampling block with its shortcut folded in (csrc/bconv_mfma.hip, the DS form:
@@ -117,9 +142,7 @@ MFMA_FOLD_SHAPES = {           # (means of two traces each; both MFMA values lie
 
 
 def mfma_fold_admitted(C: int, O: int, H: int, sc_C: int) -> bool:
-    if MFMA_CONV == "0" or MFMA_FOLD == "0":
-        return False
-    return MFMA_FOLD == "all" or (C, O, H, sc_C) in MFMA_FOLD_SHAPES
+    return _admitted(MFMA_FOLD, (C, O, H, sc_C), MFMA_FOLD_SHAPES, parents=(MFMA_CONV,))
 
 
 # A launch already on the matrix cores (admitted above) on the FP4 form of the same kernel (csrc/bconv_mfma.hip, F4:
@@ -145,9 +168,7 @@ MFMA_F4_SHAPES = {
 
 
 def mfma_f4_admitted(key: tuple) -> bool:
-    if MFMA_F4 == "0":
-        return False
-    return MFMA_F4 == "all" or tuple(key) in MFMA_F4_SHAPES
+    return _admitted(MFMA_F4, tuple(key), MFMA_F4_SHAPES)    # (not MFMA_CONV: asked only for a launch the int8 form took)
 
 
 # The 1x1 convolutions of the fused ResNet executor (Bottleneck and PreBottleneck: conv1, conv3 and the shortcut) on the FP4
@@ -200,10 +221,8 @@ MFMA_1X1_TERNARY_SHAPES = {
 
 
 def mfma_1x1_admitted(C: int, O: int, H: int, out_f32: bool, nonneg: bool = True) -> bool:
-    if MFMA_CONV == "0" or MFMA_1X1 == "0":
-        return False
     table = MFMA_1X1_SHAPES if nonneg else MFMA_1X1_TERNARY_SHAPES
-    return MFMA_1X1 == "all" or (C, O, H, bool(out_f32)) in table
+    return _admitted(MFMA_1X1, (C, O, H, bool(out_f32)), table, parents=(MFMA_CONV,))
 
 
 # The one-launch FactorizedConv kernel (csrc/fconv.hip) against the per-layer path of the same module, batch 256 on

@@ -1263,21 +1263,19 @@ def bconv2d_fused(a: PackedAct, w: PackedWeight, **kw):
     return _run_fused("bnn_hip_bconv2d_fused", a, w, (w.wbits.data_ptr(), w.wnz.data_ptr()), "bconv2d_fused", **kw)
 
 
-def _pack_weight_mfma(w: PackedWeight, kind: str) -> Optional[torch.Tensor]:
-    """``bnn_hip_pack_weight_<kind>`` (kind = "i8" or "f4"), or ``None`` where ``bnn_hip_weight_<kind>_bytes`` is 0."""
+def _mfma_pack(w: PackedWeight, kind: str, dims: tuple, *operands) -> Optional[torch.Tensor]:
+    """The matrix-core form ``kind`` of a packed weight: ``None`` for a grouped or windowed pack and where
+    ``bnn_hip_<kind>_bytes(*dims)`` is 0, else an int8 tensor of that size filled by ``bnn_hip_pack_<kind>(*operands, it)``."""
     lib = native.require()
     if w.windowed or w.groups != 1:
         return None
-    O, C, KH, KW = w.shape
-    nbytes = int(getattr(lib, f"bnn_hip_weight_{kind}_bytes")(O, C, KH, KW))
+    nbytes = int(getattr(lib, f"bnn_hip_{kind}_bytes")(*dims))
     if nbytes == 0:
         return None
     dev = w.wbits.device
     with torch.cuda.device(dev):
         pack = torch.empty(nbytes, dtype=torch.int8, device=dev)
-        native.check(getattr(lib, f"bnn_hip_pack_weight_{kind}")(w.wbits.data_ptr(), w.wnz.data_ptr(), O, C, KH, KW,
-                                                                 pack.data_ptr(), _stream(dev)),
-                     f"bnn_hip_pack_weight_{kind}")
+        native.check(getattr(lib, f"bnn_hip_pack_{kind}")(*operands, pack.data_ptr(), _stream(dev)), f"bnn_hip_pack_{kind}")
     return pack
 
 
@@ -1285,14 +1283,14 @@ def pack_weight_i8(w: PackedWeight) -> Optional[torch.Tensor]:
     """The int8 MFMA-fragment form of a packed 3x3 weight (``bnn_hip_pack_weight_i8``, layout: include/bnn_hip.h), or
     ``None`` where there is none (not 3x3, C or O no multiple of 64, a grouped pack).  One launch; ``w.alpha`` is used
     unchanged beside it."""
-    return _pack_weight_mfma(w, "i8")
+    return _mfma_pack(w, "weight_i8", w.shape, w.wbits.data_ptr(), w.wnz.data_ptr(), *w.shape)
 
 
 def pack_weight_f4(w: PackedWeight) -> Optional[torch.Tensor]:
     """The FP4 (E2M1) MFMA-fragment form of a packed 3x3 weight (``bnn_hip_pack_weight_f4``, layout: include/bnn_hip.h):
     half the bytes of ``pack_weight_i8``, as an int8 tensor of nibble pairs.  ``None`` where there is none (as
     ``pack_weight_i8``, or C no multiple of 128)."""
-    return _pack_weight_mfma(w, "f4")
+    return _mfma_pack(w, "weight_f4", w.shape, w.wbits.data_ptr(), w.wnz.data_ptr(), *w.shape)
 
 
 def bconv2d_mfma_supported(a_shape, w: PackedWeight, *, nonneg: bool = False, bias=False, post_scale=False, bn=False,
@@ -1302,24 +1300,26 @@ def bconv2d_mfma_supported(a_shape, w: PackedWeight, *, nonneg: bool = False, bi
     """Whether ``bconv2d_mfma_fused`` takes a launch of this geometry and epilogue (``bnn_hip_bconv2d_mfma_supported``:
     host only, nothing is launched or allocated).  The epilogue is given by what it contains (truth values), not by
     tensors: an aligned stand-in pointer takes the place of each operand that is present."""
-    return _mfma_supported("bnn_hip_bconv2d_mfma_supported", **locals())
+    return _mfma_supported("bnn_hip_bconv2d_mfma_supported", a_shape, w, dict(
+        nonneg=nonneg, bias=bias, post_scale=post_scale, bn=bn, residual=residual, prelu=prelu, relu=relu, out_f32=out_f32,
+        out_packed=out_packed, stride=stride, padding=padding, dilation=dilation, sign_thresholds=sign_thresholds,
+        shortcut=shortcut, epi_flags=epi_flags, pack_affine=pack_affine, out_c_total=out_c_total))
 
 
-def _mfma_supported(_symbol, a_shape, w, nonneg, bias, post_scale, bn, residual, prelu, relu, out_f32, out_packed, stride,
-                    padding, dilation, sign_thresholds, shortcut, epi_flags, pack_affine, out_c_total) -> bool:
+def _mfma_supported(symbol: str, a_shape, w: PackedWeight, k: dict) -> bool:    # k: every keyword of the public queries
     lib = native.require()
     if w.windowed or w.groups != 1:
         return False
-    d = _desc(tuple(a_shape), w.shape, stride, padding, dilation, native.FLAG_ACT_NONNEG if nonneg else 0)
+    d = _desc(tuple(a_shape), w.shape, k["stride"], k["padding"], k["dilation"], native.FLAG_ACT_NONNEG if k["nonneg"] else 0)
     p = 0x10000   # never dereferenced
-    on = lambda v: p if v else None
-    e = native.Epilogue(alpha=p, bias=on(bias), post_scale=on(post_scale), bn_scale=on(bn), bn_shift=on(bn),
-                        residual=on(residual), prelu=on(prelu), relu=int(bool(relu)), flags=epi_flags, out_f32=on(out_f32),
-                        out_P=on(out_packed), out_M=on(out_packed), pack_scale=on(pack_affine), pack_shift=on(pack_affine),
-                        out_c_total=out_c_total, sign_thresholds=on(sign_thresholds), sc_P=on(shortcut),
-                        sc_wbits=on(shortcut), sc_alpha=on(shortcut), sc_bn_scale=on(shortcut), sc_bn_shift=on(shortcut),
-                        sc_C=64 if shortcut else 0)
-    return bool(getattr(lib, _symbol)(ctypes.byref(d), ctypes.byref(e)))
+    on = lambda name: p if k[name] else None
+    sc = on("shortcut")
+    e = native.Epilogue(alpha=p, bias=on("bias"), post_scale=on("post_scale"), bn_scale=on("bn"), bn_shift=on("bn"),
+                        residual=on("residual"), prelu=on("prelu"), relu=int(bool(k["relu"])), flags=k["epi_flags"],
+                        out_f32=on("out_f32"), out_P=on("out_packed"), out_M=on("out_packed"), pack_scale=on("pack_affine"),
+                        pack_shift=on("pack_affine"), out_c_total=k["out_c_total"], sign_thresholds=on("sign_thresholds"),
+                        sc_P=sc, sc_wbits=sc, sc_alpha=sc, sc_bn_scale=sc, sc_bn_shift=sc, sc_C=64 if sc else 0)
+    return bool(getattr(lib, symbol)(ctypes.byref(d), ctypes.byref(e)))
 
 
 def bconv2d_mfma4_supported(a_shape, w: PackedWeight, *, nonneg: bool = False, bias=False, post_scale=False, bn=False,
@@ -1328,7 +1328,10 @@ def bconv2d_mfma4_supported(a_shape, w: PackedWeight, *, nonneg: bool = False, b
                             out_c_total: int = 0) -> bool:
     """``bconv2d_mfma_supported`` for the FP4 form (``bnn_hip_bconv2d_mfma4_supported``): the same rule plus whole
     128-channel groups."""
-    return _mfma_supported("bnn_hip_bconv2d_mfma4_supported", **locals())
+    return _mfma_supported("bnn_hip_bconv2d_mfma4_supported", a_shape, w, dict(
+        nonneg=nonneg, bias=bias, post_scale=post_scale, bn=bn, residual=residual, prelu=prelu, relu=relu, out_f32=out_f32,
+        out_packed=out_packed, stride=stride, padding=padding, dilation=dilation, sign_thresholds=sign_thresholds,
+        shortcut=shortcut, epi_flags=epi_flags, pack_affine=pack_affine, out_c_total=out_c_total))
 
 
 def bconv2d_mfma_fused(a: PackedAct, w: PackedWeight, w8: torch.Tensor, **kw):
@@ -1350,19 +1353,9 @@ def pack_weight1x1_f4(w: PackedWeight) -> Optional[torch.Tensor]:
     """The FP4 (E2M1) MFMA-fragment form of a packed 1x1 weight (``bnn_hip_pack_weight1x1_f4``, layout: include/bnn_hip.h:
     ``pack_weight_f4``'s with one tap), as an int8 tensor of nibble pairs.  ``None`` where there is none (not 1x1, O no
     multiple of 64, C no multiple of 128, a grouped pack).  One launch; ``w.alpha`` is used unchanged beside it."""
-    lib = native.require()
-    if w.windowed or w.groups != 1:
+    if tuple(w.shape[2:]) != (1, 1):
         return None
-    O, C, KH, KW = w.shape
-    nbytes = int(lib.bnn_hip_weight1x1_f4_bytes(O, C)) if (KH, KW) == (1, 1) else 0
-    if nbytes == 0:
-        return None
-    dev = w.wbits.device
-    with torch.cuda.device(dev):
-        pack = torch.empty(nbytes, dtype=torch.int8, device=dev)
-        native.check(lib.bnn_hip_pack_weight1x1_f4(w.wbits.data_ptr(), w.wnz.data_ptr(), O, C, KH, KW, pack.data_ptr(),
-                                                   _stream(dev)), "bnn_hip_pack_weight1x1_f4")
-    return pack
+    return _mfma_pack(w, "weight1x1_f4", w.shape[:2], w.wbits.data_ptr(), w.wnz.data_ptr(), *w.shape)
 
 
 def bconv1x1_mfma4_supported(a_shape, w: PackedWeight, *, nonneg: bool = False, bias=False, post_scale=False, bn=False,
@@ -1372,7 +1365,10 @@ def bconv1x1_mfma4_supported(a_shape, w: PackedWeight, *, nonneg: bool = False, 
     """``bconv2d_mfma_supported`` for the 1x1 convolution on the FP4 matrix cores (``bnn_hip_bconv1x1_mfma4_supported``):
     1x1 / stride 1 / padding 0, C % 128 == 0, O % 64 == 0, every epilogue of ``bconv2d_fused`` but the folded shortcut
     and a channel window."""
-    return _mfma_supported("bnn_hip_bconv1x1_mfma4_supported", **locals())
+    return _mfma_supported("bnn_hip_bconv1x1_mfma4_supported", a_shape, w, dict(
+        nonneg=nonneg, bias=bias, post_scale=post_scale, bn=bn, residual=residual, prelu=prelu, relu=relu, out_f32=out_f32,
+        out_packed=out_packed, stride=stride, padding=padding, dilation=dilation, sign_thresholds=sign_thresholds,
+        shortcut=shortcut, epi_flags=epi_flags, pack_affine=pack_affine, out_c_total=out_c_total))
 
 
 def bconv1x1_mfma4_fused(a: PackedAct, w: PackedWeight, w4: torch.Tensor, **kw):
@@ -1387,21 +1383,9 @@ def pack_shortcut_weight_i8(sw: PackedWeight) -> Optional[torch.Tensor]:
     """The int8 MFMA-fragment form of a shortcut's packed 1x1 weight (``bnn_hip_pack_shortcut_weight_i8``, layout:
     include/bnn_hip.h), or ``None`` where there is none (not 1x1, zero weights, O no multiple of 64, C not 64 / 128 / 256,
     a grouped pack).  One launch; ``sw.alpha`` is used unchanged beside it."""
-    lib = native.require()
-    if sw.windowed or sw.groups != 1 or sw.has_zero:
+    if sw.has_zero or tuple(sw.shape[2:]) != (1, 1):
         return None
-    O, C, KH, KW = sw.shape
-    if (KH, KW) != (1, 1):
-        return None
-    nbytes = int(lib.bnn_hip_shortcut_weight_i8_bytes(O, C))
-    if nbytes == 0:
-        return None
-    dev = sw.wbits.device
-    with torch.cuda.device(dev):
-        w8 = torch.empty(nbytes, dtype=torch.int8, device=dev)
-        native.check(lib.bnn_hip_pack_shortcut_weight_i8(sw.wbits.data_ptr(), O, C, w8.data_ptr(), _stream(dev)),
-                     "bnn_hip_pack_shortcut_weight_i8")
-    return w8
+    return _mfma_pack(sw, "shortcut_weight_i8", sw.shape[:2], sw.wbits.data_ptr(), *sw.shape[:2])
 
 
 def bconv2d_mfma_fold_supported(a_shape, w: PackedWeight, sc_channels: int, *, nonneg: bool = True, stride=1, padding=1,
@@ -1409,28 +1393,30 @@ def bconv2d_mfma_fold_supported(a_shape, w: PackedWeight, sc_channels: int, *, n
     """Whether ``bconv2d_mfma_fold_fused`` takes this convolution with a folded shortcut of ``sc_channels`` input channels
     (``bnn_hip_bconv2d_mfma_fold_supported``: host only).  The epilogue is the one the fold belongs to: BatchNorm +
     shortcut + ReLU -> fp32 + sign planes.  ``unpooled_hw``: the shortcut plane comes un-pooled at this size."""
-    return _mfma_fold_supported("bnn_hip_bconv2d_mfma_fold_supported", **locals())
+    return _mfma_fold_supported("bnn_hip_bconv2d_mfma_fold_supported", a_shape, w, sc_channels, dict(
+        nonneg=nonneg, stride=stride, padding=padding, dilation=dilation, unpooled_hw=unpooled_hw, throughput=throughput))
 
 
-def _mfma_fold_supported(_symbol, a_shape, w, sc_channels, nonneg, stride, padding, dilation, unpooled_hw, throughput) -> bool:
+def _mfma_fold_supported(symbol: str, a_shape, w: PackedWeight, sc_channels: int, k: dict) -> bool:
     lib = native.require()
     if w.windowed or w.groups != 1:
         return False
-    flags = (native.FLAG_ACT_NONNEG if nonneg else 0) | (native.FLAG_WEIGHT_ZEROS if w.has_zero else 0) | \
-        (native.FLAG_THROUGHPUT if throughput else 0)
-    d = _desc(tuple(a_shape), w.shape, stride, padding, dilation, flags)
+    flags = (native.FLAG_ACT_NONNEG if k["nonneg"] else 0) | (native.FLAG_WEIGHT_ZEROS if w.has_zero else 0) | \
+        (native.FLAG_THROUGHPUT if k["throughput"] else 0)
+    d = _desc(tuple(a_shape), w.shape, k["stride"], k["padding"], k["dilation"], flags)
     p = 0x10000   # never dereferenced
-    hw = 0 if unpooled_hw is None else (int(unpooled_hw[0]) << 16) | int(unpooled_hw[1])
+    hw = 0 if k["unpooled_hw"] is None else (int(k["unpooled_hw"][0]) << 16) | int(k["unpooled_hw"][1])
     e = native.Epilogue(alpha=p, bn_scale=p, bn_shift=p, relu=1, out_f32=p, out_P=p, out_M=p, sc_P=p, sc_alpha=p,
                         sc_bn_scale=p, sc_bn_shift=p, sc_C=int(sc_channels), sc_in_hw=hw)
-    return bool(getattr(lib, _symbol)(ctypes.byref(d), ctypes.byref(e)))
+    return bool(getattr(lib, symbol)(ctypes.byref(d), ctypes.byref(e)))
 
 
 def bconv2d_mfma4_fold_supported(a_shape, w: PackedWeight, sc_channels: int, *, nonneg: bool = True, stride=1, padding=1,
                                  dilation=1, unpooled_hw: Optional[Tuple[int, int]] = None, throughput: bool = False) -> bool:
     """``bconv2d_mfma_fold_supported`` for the FP4 form (``bnn_hip_bconv2d_mfma4_fold_supported``): the same rule plus
     whole 128-channel groups."""
-    return _mfma_fold_supported("bnn_hip_bconv2d_mfma4_fold_supported", **locals())
+    return _mfma_fold_supported("bnn_hip_bconv2d_mfma4_fold_supported", a_shape, w, sc_channels, dict(
+        nonneg=nonneg, stride=stride, padding=padding, dilation=dilation, unpooled_hw=unpooled_hw, throughput=throughput))
 
 
 def _mfma_fold_fused(kind: str, what: str, a: PackedAct, w: PackedWeight, pack: torch.Tensor, sc_w8: torch.Tensor, **kw):

@@ -9,7 +9,7 @@ from bnn_amd import fastpath, native
 from bnn_amd.inference import FusedResNet, tap_binary_inputs
 from bnn_amd.pipeline import PipelinedInference
 from tests.golden import gen
-from tests.test_gpu_mfma_net import _convs, net  # noqa: F401  (the module-scoped model fixture)
+from tests.test_gpu_mfma_net import DENSE, FOLD, FP4, _convs, net  # noqa: F401  (the module-scoped model fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -34,8 +34,8 @@ def _forward(engine, x):
     y = engine(x).clone()
     launches = native.launch_count() - n0
     convs = _convs(engine)
-    on_cores = sorted(c.name for c in convs if any(c.mfma.values()) or any(c.mfma_fold.values()))
-    on_f4 = sorted(c.name for c in convs if any(c.f4.values()))
+    on_cores = sorted(c.name for c in convs if (DENSE | FOLD) & set(c.routes.values()))
+    on_f4 = sorted(c.name for c in convs if FP4 & set(c.routes.values()))
     return y, planes, launches, on_cores, on_f4
 
 
@@ -52,9 +52,10 @@ def test_fp4_on_equals_fp4_off(net, monkeypatch, n, size):  # noqa: F811
     assert len(planes0) == LAUNCHES and sorted(planes0) == sorted(planes1)
     for name in planes0:
         assert torch.equal(planes0[name][0], planes1[name][0]) and torch.equal(planes0[name][1], planes1[name][1]), name
-    # the default: only shapes of the table
+    # the default: only shapes of the table — all eleven at 224 x 224, where the table was traced
     yd, _, launchesd, coresd, f4d = _forward(_engine(net, "1", monkeypatch), x)
-    assert launchesd == LAUNCHES and coresd == cores0 and set(f4d) <= set(ON_F4) and torch.equal(yd, y0)
+    assert launchesd == LAUNCHES and coresd == cores0 and torch.equal(yd, y0)
+    assert f4d == ON_F4 if (n, size) == (2, 224) else set(f4d) <= set(ON_F4)
 
 
 def test_two_stream_graph_replay(net, monkeypatch):  # noqa: F811

@@ -9,7 +9,7 @@ from bnn_amd import fastpath, native
 from bnn_amd.inference import FusedResNet, tap_binary_inputs
 from bnn_amd.pipeline import PipelinedInference
 from tests.golden import gen
-from tests.test_gpu_mfma_net import _convs, net  # noqa: F401  (the module-scoped model fixture)
+from tests.test_gpu_mfma_net import DENSE, FOLD, _convs, net  # noqa: F401  (the module-scoped model fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -30,8 +30,8 @@ def _forward(engine, x):
     n0 = native.launch_count()
     y = engine(x).clone()
     launches = native.launch_count() - n0
-    folded = sorted(c.name for c in _convs(engine) if any(c.mfma_fold.values()))
-    on_mfma = sorted(c.name for c in _convs(engine) if any(c.mfma.values()))
+    folded = sorted(c.name for c in _convs(engine) if FOLD & set(c.routes.values()))
+    on_mfma = sorted(c.name for c in _convs(engine) if DENSE & set(c.routes.values()))
     return y, planes, launches, folded, on_mfma
 
 

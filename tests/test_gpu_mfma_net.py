@@ -6,6 +6,7 @@ import torch
 
 import bnn_amd as bnn
 from bnn_amd import fastpath, native
+from bnn_amd.executor import Form
 from bnn_amd.inference import FusedResNet, tap_binary_inputs
 from bnn_amd.models import resnet18
 from bnn_amd.ops import BasicInputBinarizer, XNORWeightBinarizer
@@ -15,6 +16,7 @@ from tests.golden import gen
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 LAUNCHES = 19
+DENSE, FOLD, FP4 = {Form.I8_3X3, Form.F4_3X3}, {Form.I8_FOLD, Form.F4_FOLD}, {Form.F4_3X3, Form.F4_FOLD}
 
 
 @pytest.fixture(scope="module")
@@ -40,7 +42,7 @@ def _forward(engine, x):
     n0 = native.launch_count()
     y = engine(x).clone()
     launches = native.launch_count() - n0
-    on_mfma = sorted(c.name for c in _convs(engine) if any(c.mfma.values()))
+    on_mfma = sorted(c.name for c in _convs(engine) if DENSE & set(c.routes.values()))
     return y, planes, launches, on_mfma
 
 

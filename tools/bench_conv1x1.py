@@ -108,6 +108,12 @@ def convs_by_name(eng):
     return out
 
 
+def fp4_form(conv):
+    """Every launch of ``conv`` was routed, and to the FP4 1x1 kernel."""
+    from bnn_amd.executor import Form
+    return bool(conv.routes) and set(conv.routes.values()) == {Form.F4_1X1}
+
+
 def timed(fn, iters, warmup):
     import torch
     for _ in range(warmup):
@@ -139,7 +145,7 @@ def bench(args):
                 if key in seen:
                     continue
                 seen.add(key)
-                fp4 = bool(c_on[name].mfma_1x1 and all(c_on[name].mfma_1x1.values()))
+                fp4 = fp4_form(c_on[name])
                 us = {"popcount": [], "fp4": []}
                 for _ in range(2):
                     us["popcount"].append(round(timed(lambda: c_off[name].run(act, **kw), args.iters, args.warmup), 2))
@@ -161,7 +167,7 @@ def forward(args):
     with torch.no_grad():
         calls, _ = record(eng, x)
         convs = convs_by_name(eng)
-        sched = [dict(layer=n, fp4=bool(convs[n].mfma_1x1 and all(convs[n].mfma_1x1.values())), **describe(convs[n], a, kw))
+        sched = [dict(layer=n, fp4=fp4_form(convs[n]), **describe(convs[n], a, kw))
                  for n, a, kw in calls]
         del calls
         for _ in range(args.steps):
