@@ -24,6 +24,7 @@ from __future__ import annotations
 
 import collections
 import contextlib
+import enum
 import itertools
 import os
 from dataclasses import dataclass, field
@@ -205,6 +206,12 @@ class _Conv:
                 return Form.F4_FOLD if f4 else Form.I8_FOLD
         return Form.POPCOUNT
 
+    def plain(self, **geometry) -> bool:
+        """A plain binary convolution (no bias, post-scale, zero weight, PReLU or ReLU) whose layer has this ``geometry``:
+        ``kernel_size`` / ``stride`` / ``padding`` / ``dilation``, whichever are given."""
+        return (self.layer.bias is None and self.plan.scale is None and not self.weight.has_zero and self.prelu is None
+                and not self.relu and all(tuple(getattr(self.layer, k)) == v for k, v in geometry.items()))
+
     def _epilogue(self, k: RouteKey) -> dict:
         """The launch ``k`` of this layer as the ``*_supported`` queries of ``hipops`` take it: what its epilogue contains."""
         lay = self.layer
@@ -275,13 +282,28 @@ class _Pre:
     ds_float: Optional[nn.Module] = None
 
 
-@dataclass
-class _HGeo:
-    """What is decided per input geometry (N, H, W) of a hierarchical block with a one-launch form."""
-    ok: bool                                # a one-launch kernel covers the geometry (_hblock_ok)
-    cl: bool                                # ... in its channel-lane form (csrc/hblock_cl.hip)
-    sc: Optional[bool] = None               # the shortcut convolution inside the launch (_run_h); None: not asked yet
-    pooled: Union[None, bool, torch.Tensor] = None   # _pooled_form: None not asked yet, False no, else its constants
+class HForm(enum.Enum):
+    """How one hierarchical block runs at one geometry (``_H.route``)."""
+    STEPS = "launch by launch"
+    ONE = "hblock_forward"
+    SHORTCUT = "hblock_shortcut_forward"        # the shortcut convolution inside the launch
+    POOLED = "hblock_pool_forward"              # the stage's pool and both binarisations behind it inside the launch
+
+
+class _HRoute(NamedTuple):
+    form: HForm
+    channel_lanes: bool = False                 # ONE / SHORTCUT in the small-image form (lanes = output channels, csrc/hblock_cl.hip)
+    pool_consts: Optional[torch.Tensor] = None  # POOLED: ``hipops.hblock_pool_consts`` of the block behind the pool
+
+
+def _hblock_env(name: str, default: str = "1") -> str:
+    """``BNN_AMD_<name>`` (INTEGRATION.md): FUSE_HBLOCK, read when an executor is built; HBLOCK_SHORTCUT, at ``refresh``;
+    HBLOCK_CL, HBLOCK_POOL and HBLOCK_POOL_MIN (pixels), when ``_H.route`` first decides a geometry.  "0" switches off."""
+    return os.environ.get("BNN_AMD_" + name, default)
+
+
+def _is_pool2x2(m: nn.Module) -> bool:
+    return isinstance(m, nn.AvgPool2d) and m.kernel_size in (2, (2, 2)) and m.stride in (2, (2, 2)) and m.padding in (0, (0, 0))
 
 
 @dataclass(eq=False)
@@ -294,10 +316,97 @@ class _H:
     convs: List[_Conv]
     ds_bn: Optional[Tuple[torch.Tensor, torch.Tensor]] = None   # shortcut: BatchNorm -> binary 1x1 (no BN behind it)
     ds: Optional[_Conv] = None
+    throughput: bool = False                # as ``_Conv.throughput``
     # filled by _link_hblocks
-    hpack: Optional[hipops.HBlockPack] = None       # constants of the one-launch form; None: the block does not qualify
+    next: Optional[object] = None           # the next block of the stage
+    end_pool: Optional[nn.Module] = None    # the ``AvgPool2d(2, 2)`` that ends the stage behind this block ...
+    behind: Optional[object] = None         # ... and the block behind that pool
+    hpack: Optional[hipops.HBlockPack] = None       # constants of the one-launch forms; None: the block does not qualify
     hsc: Optional[Tuple[torch.Tensor, torch.Tensor]] = None     # hblock_shortcut_pack of ``ds``: it runs inside the launch
-    geo: Dict[Tuple[int, int, int], _HGeo] = field(default_factory=dict)   # derived lazily, per (N, H, W)
+    routes: Dict[Tuple[int, int, int], _HRoute] = field(default_factory=dict)   # (N, H, W) -> how it runs, decided once
+
+    def route(self, N: int, H: int, W: int) -> _HRoute:
+        """How the block runs on ``N`` images of ``H`` x ``W``, decided once per geometry.  A lane form covers the geometry:
+        channel lanes iff ``BNN_AMD_HBLOCK_CL`` is not "0", ``H == 7`` or several batches are in flight (``throughput``), and
+        ``hblock_supported(..., channel_lanes=True)``; else pixel lanes iff ``hblock_supported``.  (Alone, the pixel-lane
+        kernel splits a 14 x 14 image over two workgroups and fills the chip; measured at batch 128, us per block: 7 x 7 53.6
+        vs 67.1; 14 x 14 shared 60.4 vs 72.0, alone 60.4 vs 44.8.)  Each form needs all of its line; the first that holds wins:
+
+        * ``SHORTCUT``: ``hpack``, a lane form and ``hsc`` exist; ``hblock_shortcut_supported`` in that lane form.
+        * ``POOLED``: ``hpack`` and a lane form exist; ``BNN_AMD_HBLOCK_POOL`` is not "0"; the stage ends behind the block in
+          an ``AvgPool2d(2, 2)`` and the block ``behind`` that ``_takes_planes`` of this width and has a shortcut convolution
+          (so nobody reads this block's fp32 output); ``H`` and ``W`` are even; the block keeps its width; ``H * W`` is at
+          least ``BNN_AMD_HBLOCK_POOL_MIN`` (784); the block behind does not run ``STEPS`` at the halved geometry
+          (``one_launch``); ``hblock_pool_supported``; ``hblock_pool_consts`` raises no ``NativeError`` (a scale that cannot
+          take the average's 1 / 4 exactly).  Pixel lanes only.
+        * ``ONE``: ``hpack`` and a lane form exist.
+        * ``STEPS`` otherwise.  A run under ``tap_binary_inputs`` is ``STEPS`` too and never comes here (``_run_h``)."""
+        r = self.routes.get((N, H, W))
+        if r is None:
+            r = self.routes[(N, H, W)] = self._decide(N, H, W)
+        return r
+
+    def _decide(self, N: int, H: int, W: int) -> _HRoute:
+        hp, nb = self.hpack, self.behind
+        if hp is None:
+            return _HRoute(HForm.STEPS)
+        geo = (N, hp.c_in, H, W, hp.planes, self.throughput)
+        cl = _hblock_env("HBLOCK_CL") != "0" and (H == 7 or self.throughput) and hipops.hblock_supported(*geo, channel_lanes=True)
+        if not (cl or hipops.hblock_supported(*geo)):
+            return _HRoute(HForm.STEPS)
+        if self.hsc is not None and hipops.hblock_shortcut_supported(*geo, channel_lanes=cl):
+            return _HRoute(HForm.SHORTCUT, cl)
+        if (_hblock_env("HBLOCK_POOL") != "0" and self.end_pool is not None and _takes_planes(nb, hp.planes)
+                and nb.ds is not None and H % 2 == 0 and W % 2 == 0 and hp.c_in == hp.planes
+                and H * W >= int(_hblock_env("HBLOCK_POOL_MIN", "784")) and nb.one_launch(N, H // 2, W // 2)
+                and hipops.hblock_pool_supported(*geo)):
+            with contextlib.suppress(native.NativeError):
+                return _HRoute(HForm.POOLED, False, hipops.hblock_pool_consts(nb.bn[0], nb.ds_bn, hp.planes))
+        return _HRoute(HForm.ONE, cl)
+
+    def one_launch(self, N: int, H: int, W: int) -> bool:
+        """What a producer asks before it writes this block's input planes and NO fp32 tensor (``_pool_into_hblock`` in front
+        of a shortcut BatchNorm; ``POOLED``): ``t is None`` may reach a block only where it does not run launch by launch —
+        ``STEPS`` binarises the fp32 tensor itself.  ``_run_h`` asserts it on the consumer's side."""
+        return self.route(N, H, W).form is not HForm.STEPS
+
+
+def _takes_planes(b, channels: int) -> bool:
+    """A producer of ``channels`` channels may write block ``b``'s input planes, ``sign(relu(bn1(.)))``, itself."""
+    return b is not None and b.kind == "h" and b.hpack is not None and b.relu[0] and b.hpack.c_in == channels
+
+
+def _link_hblocks(blocks: list, fuse: bool, shortcut: bool) -> None:
+    """Links every hierarchical block to its neighbours and, with ``fuse``, builds the one-launch pack of each that qualifies
+    (csrc/hblock.hip): ReLU activations (all sign planes non-negative), plain 3x3 / stride 1 / padding 1 convolutions of
+    a half, a quarter and a quarter of the block's width, a multiple of 64.  The launch also writes the NEXT block's input
+    planes when that block is a hierarchical block behind a ReLU."""
+    for b, nxt, nxt2 in zip(blocks, blocks[1:] + [None], blocks[2:] + [None, None]):
+        if b.kind != "h":
+            continue
+        if nxt is not None and nxt.kind == "pool":
+            if _is_pool2x2(nxt.mod) and nxt2 is not None:
+                b.end_pool, b.behind = nxt.mod, nxt2
+            nxt = None
+        b.next = nxt
+        convs, planes = b.convs, b.planes
+        if not (fuse and all(b.relu)
+                and all(c.plain(kernel_size=(3, 3), stride=(1, 1), padding=(1, 1), dilation=(1, 1)) for c in convs)
+                and [c.layer.out_channels * k for c, k in zip(convs, (2, 4, 4))] == [planes] * 3 and planes % 64 == 0):
+            continue
+        nbn = nxt.bn[0] if (nxt is not None and nxt.kind == "h" and nxt.relu[0]
+                            and nxt.convs[0].layer.in_channels == planes) else None
+        try:
+            b.hpack = hipops.hblock_pack(convs[0].weight, convs[1].weight, convs[2].weight, b.bn[1], b.bn[2], nbn)
+        except native.NativeError:      # a width the one-launch kernel has no instance for
+            continue
+        # a stage's first block takes its shortcut convolution into the launch (bnn_hip_hblock_shortcut_forward): a plain
+        # binary 1x1 behind its own BatchNorm (none behind it), and a next block in the stage
+        sc = b.ds
+        if (sc is not None and nbn is not None and sc.plain(kernel_size=(1, 1), stride=(1, 1), padding=(0, 0))
+                and sc.bn_scale is None and sc.layer.in_channels * 2 == planes and shortcut):
+            with contextlib.suppress(native.NativeError):
+                b.hsc = hipops.hblock_shortcut_pack(sc.weight)
 
 
 @dataclass(eq=False)
@@ -382,7 +491,7 @@ class FusedResNet(nn.Module):
         if _PARKED and not torch.cuda.is_current_stream_capturing():
             _PARKED.clear()
         # a hierarchical block as ONE launch (bnn_hip_hblock_forward) instead of a packing pass + three convolutions
-        self.fuse_hblock = fuse_hblock and os.environ.get("BNN_AMD_FUSE_HBLOCK", "1") != "0"   # ("0": launch by launch, for A/B profiles)
+        self.fuse_hblock = fuse_hblock and _hblock_env("FUSE_HBLOCK") != "0"   # ("0": launch by launch, for A/B profiles)
         # the last conv of a block writes no fp32 tensor when the next block consumes sign planes only
         self.skip_dead_f32 = skip_dead_f32
         # BN + ReLU + sign of the conv1-type layers as an integer compare of the dot (same bits, fewer instructions)
@@ -459,13 +568,10 @@ class FusedResNet(nn.Module):
         fastpath.invalidate(m, executors=False)
         if m.training:
             raise FusionError("FusedResNet is inference-only: call model.eval() first")
-        dev = m.fc.weight.device
-        if dev.type != "cuda":
+        if m.fc.weight.device.type != "cuda":
             raise FusionError("FusedResNet needs the model on a HIP device")
-        self._blocks = []
         self._split.clear()     # graphs behind the stem hold pointers to the derived data rebuilt below
         self._stem = None
-        self._names = {id(mod): name for name, mod in m.named_modules()}
         mp = m.maxpool
         self._stem_module = getattr(m, "stem_type", "basic") != "basic"   # daBNN stem (resnet.py:10-47): m.conv1 is all of it
         if not self._stem_module and isinstance(mp, nn.MaxPool2d) and isinstance(m.bn1, nn.BatchNorm2d) \
@@ -487,52 +593,17 @@ class FusedResNet(nn.Module):
         if fc_float and isinstance(ap, nn.AdaptiveAvgPool2d) and ap.output_size in (1, (1, 1)) \
                 and fc.weight.dtype == torch.float32 and fc.in_features * 16 <= 160 * 1024:
             self._head = (fc.weight.detach().t().contiguous(), None if fc.bias is None else fc.bias.detach())
-        for stage in (m.layer1, m.layer2, m.layer3, m.layer4):
-            for blk in stage:
-                self._add_block(blk)
-        self._link_hblocks()
+        self._plan(itertools.chain(m.layer1, m.layer2, m.layer3, m.layer4))
+
+    def _plan(self, blocks) -> None:
+        """The end of every ``refresh``: one record per block of ``blocks``, the hierarchical blocks linked."""
+        self._blocks = []
+        self._names = {id(mod): name for name, mod in self.model.named_modules()}
+        for blk in blocks:
+            self._add_block(blk)
+        _link_hblocks(self._blocks, self.fuse_hblock, _hblock_env("HBLOCK_SHORTCUT") != "0")
         self._graph = None
         self._sig = param_signature(self.model)
-
-    def _link_hblocks(self) -> None:
-        """One-launch form of every hierarchical block that qualifies (csrc/hblock.hip): ReLU activations (all sign
-        planes non-negative), bias-free 3x3 / stride 1 / padding 1 convolutions without post scale or zero weights.  The
-        launch also writes the NEXT block's input planes when that block is a hierarchical block behind a ReLU."""
-        if not self.fuse_hblock:
-            return
-        for i, b in enumerate(self._blocks):
-            if b.kind != "h":
-                continue
-            convs = b.convs
-            ok = all(b.relu) and all(
-                c.layer.bias is None and c.plan.scale is None and not c.weight.has_zero and c.prelu is None and not c.relu
-                and tuple(c.layer.kernel_size) == (3, 3) and tuple(c.layer.stride) == (1, 1)
-                and tuple(c.layer.padding) == (1, 1) and tuple(c.layer.dilation) == (1, 1) for c in convs)
-            planes = b.planes
-            ok = ok and convs[0].layer.out_channels * 2 == planes and convs[1].layer.out_channels * 4 == planes \
-                and convs[2].layer.out_channels * 4 == planes and planes % 64 == 0
-            if not ok:
-                continue
-            nxt = self._blocks[i + 1] if i + 1 < len(self._blocks) else None
-            nbn = nxt.bn[0] if (nxt is not None and nxt.kind == "h" and nxt.relu[0]
-                                and nxt.convs[0].layer.in_channels == planes) else None
-            try:
-                b.hpack = hipops.hblock_pack(convs[0].weight, convs[1].weight, convs[2].weight, b.bn[1], b.bn[2], nbn)
-            except native.NativeError:      # a width the one-launch kernel has no instance for
-                continue
-            # the shortcut convolution of a stage's first block inside the block's launch (bnn_hip_hblock_shortcut_forward):
-            # a plain binary 1x1 (no bias, no scale, no zero weights) behind its own BatchNorm, and a next block in the stage
-            if b.ds is not None and nbn is not None:
-                sc = b.ds
-                lay = sc.layer
-                if (lay.bias is None and sc.plan.scale is None and not sc.weight.has_zero and sc.prelu is None and not sc.relu
-                        and sc.bn_scale is None and tuple(lay.kernel_size) == (1, 1) and tuple(lay.stride) == (1, 1)
-                        and tuple(lay.padding) == (0, 0) and lay.in_channels * 2 == planes
-                        and os.environ.get("BNN_AMD_HBLOCK_SHORTCUT", "1") != "0"):
-                    try:
-                        b.hsc = hipops.hblock_shortcut_pack(sc.weight)
-                    except native.NativeError:
-                        pass
 
     def _add_block(self, blk) -> None:
         """Derive the fused form of one residual block (appends to ``self._blocks``)."""
@@ -551,7 +622,8 @@ class FusedResNet(nn.Module):
             entry = _H(planes=blk.conv1.out_channels * 2,
                        bn=[fold_bn(blk.bn1), fold_bn(blk.bn2), fold_bn(blk.bn3)],
                        relu=[self._sign_through(a) for a in (blk.act1, blk.act2, blk.act3)],
-                       convs=[self._conv(c, None, None) for c in (blk.conv1, blk.conv2, blk.conv3)])
+                       convs=[self._conv(c, None, None) for c in (blk.conv1, blk.conv2, blk.conv3)],
+                       throughput=self.throughput_mode)
             if blk.downsample is not None:  # BN -> binary 1x1 (no BN behind it)
                 bn, conv = blk.downsample[0], blk.downsample[1]
                 entry.ds_bn, entry.ds = fold_bn(bn), self._conv(conv, None, None)
@@ -602,10 +674,7 @@ class FusedResNet(nn.Module):
             # a hierarchical block behind the stem reads sign(relu(bn1(t))): the stem kernel writes THOSE planes (its own
             # packing pass over the fp32 tensor disappears); the hand-off tells _run_h whose planes they are
             b0 = self._blocks[0] if self._blocks else None
-            aff = None
-            if (b0 is not None and b0.kind == "h" and b0.hpack is not None and b0.relu[0] and b0.ds is None
-                    and not self.stem_exact_fp32 and _TAP is None and b0.hpack.c_in == 64):
-                aff = b0.bn[0]
+            aff = b0.bn[0] if (_takes_planes(b0, 64) and b0.ds is None and not self.stem_exact_fp32 and _TAP is None) else None
             t, pk = hipops.stem7x7(x, m.conv1.weight, self._stem[0], self._stem[1], exact_fp32=self.stem_exact_fp32,
                                    fp16=self.stem_fp16, out=out, pack_affine=aff)
             return t, pk, (_Handoff(b0) if aff is not None else None)
@@ -634,19 +703,17 @@ class FusedResNet(nn.Module):
         for i, b in enumerate(self._blocks):
             nxt = self._blocks[i + 1] if i < last else None
             if b.kind == "pool":
-                if t is None and left is not None and left.owner is nxt:
-                    continue                # the previous block's launch pooled and binarised its own output (_run_h)
-                fused = self._pool_into_hblock(b.mod, nxt, t)
-                if fused is not None:       # the pool + both sign planes the next stage's first block reads, one pass
-                    t, packed, left = fused
+                if t is None:               # the previous block's launch pooled and binarised its own output (POOLED)
+                    assert left is not None and left.owner is nxt and nxt.one_launch(packed.shape[0], *packed.shape[2:])
                     continue
-                t, packed, left = b.mod(t), None, None
+                # the pool + both sign planes the next stage's first block reads in one pass, where that applies
+                t, packed, left = self._pool_into_hblock(b.mod, nxt, t) or (b.mod(t), None, None)
                 continue
             if b.kind == "pre":
                 t, packed, left = self._run_pre(b, nxt, t, packed, left)
                 continue
             if b.kind == "h":
-                t, packed, left = self._run_h(b, t, packed, left, nxt, self._blocks[i + 2] if i + 2 <= last else None)
+                t, packed, left = self._run_h(b, t, packed, left)
                 continue
             assert left is None, "sign planes written for another block's first convolution"
             if packed is None:
@@ -717,9 +784,7 @@ class FusedResNet(nn.Module):
         lay, c2l = ds.layer, c2.layer
         if b.fold_recipe is None:
             b.fold_recipe = bool(
-                lay.bias is None and ds.plan.scale is None and not ds.relu and ds.prelu is None
-                and tuple(lay.kernel_size) == (1, 1) and tuple(lay.stride) == (1, 1) and tuple(lay.padding) == (0, 0)
-                and not ds.weight.has_zero and b is not self._blocks[-1] and len(b.convs) >= 2
+                ds.plain(kernel_size=(1, 1), stride=(1, 1), padding=(0, 0)) and b is not self._blocks[-1] and len(b.convs) >= 2
                 and all(c.relu and c.prelu is None for c in b.convs[:-1])
                 and c2.relu and c2.prelu is None and c2.layer.bias is None and c2.plan.scale is None)
         if not b.fold_recipe:
@@ -771,108 +836,47 @@ class FusedResNet(nn.Module):
         """``AvgPool2d(2, 2)`` in front of a hierarchical block that runs as one launch: the pooled tensor is only ever
         binarised — by the block's bn1 -> ReLU and by its shortcut's BatchNorm — so one pass writes both sets of planes
         and (when the block has a shortcut convolution) no fp32 tensor at all.  None: not that case."""
-        if (_TAP is not None or nxt is None or nxt.kind != "h" or nxt.hpack is None or t is None
-                or not isinstance(pool, nn.AvgPool2d) or pool.kernel_size not in (2, (2, 2))
-                or pool.stride not in (2, (2, 2)) or pool.padding not in (0, (0, 0))
-                or t.shape[2] % 2 or t.shape[3] % 2 or not nxt.relu[0]):
-            return None
         N, C, H, W = t.shape
-        hp = nxt.hpack
-        if C != hp.c_in or not self._hblock_ok(nxt, N, H // 2, W // 2):
+        if (_TAP is not None or not _is_pool2x2(pool) or H % 2 or W % 2 or not _takes_planes(nxt, C)
+                or not nxt.one_launch(N, H // 2, W // 2)):
             return None
         p1, p2, tp = hipops.avgpool2_bn_pack2(t, nxt.bn[0], True, nxt.ds_bn, False, out_f32=nxt.ds_bn is None)
         return tp, p1, _Handoff(nxt, p2)
 
-    def _hblock_ok(self, b, N, H, W) -> bool:
-        """Whether the one-launch kernel covers this geometry; also decides which form of it runs (``b.geo[N, H, W].cl``):
-        the small-image form (lanes = output channels, csrc/hblock_cl.hip) on 7 x 7 images, and on 14 x 14 images when other
-        work shares the GPU — there whole images per workgroup win; alone, the pixel-lane kernel splits a 14 x 14 image over
-        two workgroups and fills the chip (measured at batch 128, us per block: 7 x 7 53.6 vs 67.1; 14 x 14 shared 60.4 vs
-        72.0, alone 60.4 vs 44.8)."""
-        g = b.geo.get((N, H, W))
-        if g is None:
-            hp = b.hpack
-            cl = (os.environ.get("BNN_AMD_HBLOCK_CL", "1") != "0" and (H == 7 or self.throughput_mode)
-                  and hipops.hblock_supported(N, hp.c_in, H, W, hp.planes, self.throughput_mode, channel_lanes=True))
-            ok = cl or hipops.hblock_supported(N, hp.c_in, H, W, hp.planes, self.throughput_mode)
-            g = b.geo[(N, H, W)] = _HGeo(ok, cl)
-        return g.ok
-
-    def _pooled_form(self, b, nxt, nxt2, N, H, W):
-        """The constants of ``hipops.hblock_pool_forward`` when block ``b`` ends a stage — ``nxt`` is ``AvgPool2d(2, 2)`` and
-        ``nxt2`` a one-launch hierarchical block with a shortcut convolution, so that nobody reads ``b``'s fp32 output —
-        and the kernel covers the geometry; else None.  (Behind ``_hblock_ok(b, N, H, W)``: the geometry has its entry.)"""
-        g = b.geo[(N, H, W)]
-        hit = g.pooled
-        if hit is None:
-            hit = False
-            pool = nxt.mod if nxt is not None and nxt.kind == "pool" else None
-            hp = b.hpack
-            if (os.environ.get("BNN_AMD_HBLOCK_POOL", "1") != "0" and _TAP is None and pool is not None and nxt2 is not None
-                    and nxt2.kind == "h" and nxt2.hpack is not None and nxt2.ds is not None and nxt2.relu[0]
-                    and isinstance(pool, nn.AvgPool2d) and pool.kernel_size in (2, (2, 2)) and pool.stride in (2, (2, 2))
-                    and pool.padding in (0, (0, 0)) and H % 2 == 0 and W % 2 == 0 and hp.c_in == hp.planes
-                    and H * W >= int(os.environ.get("BNN_AMD_HBLOCK_POOL_MIN", "784"))
-                    and nxt2.hpack.c_in == hp.planes and self._hblock_ok(nxt2, N, H // 2, W // 2)
-                    and hipops.hblock_pool_supported(N, hp.c_in, H, W, hp.planes, self.throughput_mode)):
-                try:
-                    hit = hipops.hblock_pool_consts(nxt2.bn[0], nxt2.ds_bn, hp.planes)
-                except native.NativeError:      # (a scale that cannot take the average's 1 / 4 exactly)
-                    hit = False
-            g.pooled = hit
-        return None if hit is False else hit
-
-    def _run_h(self, b, t, packed=None, left=None, nxt=None, nxt2=None):
-        """HBlock: three BN-act-conv stages write their slice of the concatenated output in place, each
-        adds its slice of the shortcut and hands ``sign(act(bn_next(o_k)))`` to the next stage.  Returns
-        ``(y, planes of the next block's input | None, their _Handoff | None)``; ``packed`` / ``left``: what the previous
-        block's launch left, for this block when ``left.owner is b``.  The last block of a stage returns ``(None, planes of
-        the next stage's first block, ...)``: pooled and binarised in the same launch (``_pooled_form``)."""
+    def _run_h(self, b, t, packed=None, left=None):
+        """HBlock: three BN-act-conv stages write their slice of the concatenated output in place, each adds its slice of
+        the shortcut and hands ``sign(act(bn_next(o_k)))`` to the next stage.  Returns ``(y, planes of the next block's input
+        | None, their _Handoff | None)``; ``packed`` / ``left``: what the previous block's launch left, for this block when
+        ``left.owner is b``.  ``POOLED`` returns ``(None, planes of the next stage's first block, ...)``: its own output pooled."""
         mine = left is not None and left.owner is b     # planes the previous launch left for this block
-        if b.ds is not None:
-            sp = left.ds if mine else None
-            if sp is None:
-                sp = hipops.bn_act_pack(t, *b.ds_bn, relu=False)
-            hp = b.hpack
-            if b.hsc is not None and _TAP is None:
-                N, _, H, W = sp.shape
-                ok = self._hblock_ok(b, N, H, W)
-                g = b.geo[(N, H, W)]
-                if g.sc is None:   # (in the form of the block that _hblock_ok chose for this geometry)
-                    g.sc = ok and hipops.hblock_shortcut_supported(N, hp.c_in, H, W, hp.planes, self.throughput_mode,
-                                                                   channel_lanes=g.cl)
-                if g.sc:
-                    if not mine:
-                        packed = hipops.bn_act_pack(t, *b.bn[0], relu=True)
-                    y, pk = hipops.hblock_shortcut_forward(packed, hp, sp, b.hsc, throughput=self.throughput_mode,
-                                                           channel_lanes=g.cl)
-                    return y, pk, _Handoff(nxt)
-            idn, _ = b.ds.run(sp, out_f32=True, out_packed=False)
-        else:
-            idn = t
-        c1, c2, c3 = b.convs
-        hp = b.hpack
-        if hp is not None and _TAP is None:     # (a tap wants the planes in front of every convolution: launch by launch)
-            N, _, H, W = idn.shape
-            if self._hblock_ok(b, N, H, W):
-                if not mine:
-                    packed = hipops.bn_act_pack(t, *b.bn[0], relu=True)
-                kp = self._pooled_form(b, nxt, nxt2, N, H, W)
-                if kp is not None:
-                    p1, p2 = hipops.hblock_pool_forward(packed, hp, idn, kp, throughput=self.throughput_mode)
-                    return None, p1, _Handoff(nxt2, p2)
-                y, pk = hipops.hblock_forward(packed, hp, idn, out_packed=hp.has_next, throughput=self.throughput_mode,
-                                              channel_lanes=b.geo[(N, H, W)].cl)
-                return y, pk, (_Handoff(nxt) if pk is not None else None)
-        half = b.planes // 2
-        quarter = c2.layer.out_channels
+        sp = left.ds if mine else None                  # planes of the shortcut's BatchNorm
+        if b.ds is not None and sp is None:
+            sp = hipops.bn_act_pack(t, *b.ds_bn, relu=False)
+        N, _, H, W = (t if sp is None else sp).shape
+        # a tap wants the planes in front of every convolution: launch by launch, and no route is asked for or kept
+        r = _HRoute(HForm.STEPS) if _TAP is not None else b.route(N, H, W)
+        assert t is not None or (mine and r.form is not HForm.STEPS), "no fp32 tensor in front of a launch-by-launch block"
+        hp, thr = b.hpack, b.throughput
+        if r.form is HForm.SHORTCUT:
+            if not mine:
+                packed = hipops.bn_act_pack(t, *b.bn[0], relu=True)
+            y, pk = hipops.hblock_shortcut_forward(packed, hp, sp, b.hsc, throughput=thr, channel_lanes=r.channel_lanes)
+            return y, pk, _Handoff(b.next)
+        idn = t if sp is None else b.ds.run(sp, out_f32=True, out_packed=False)[0]
+        if r.form is not HForm.STEPS:
+            if not mine:
+                packed = hipops.bn_act_pack(t, *b.bn[0], relu=True)
+            if r.form is HForm.POOLED:
+                p1, p2 = hipops.hblock_pool_forward(packed, hp, idn, r.pool_consts, throughput=thr)
+                return None, p1, _Handoff(b.behind, p2)
+            y, pk = hipops.hblock_forward(packed, hp, idn, out_packed=hp.has_next, throughput=thr, channel_lanes=r.channel_lanes)
+            return y, pk, (_Handoff(b.next) if pk is not None else None)
+        (c1, c2, c3), half, quarter = b.convs, b.planes // 2, b.convs[1].layer.out_channels
         p = hipops.bn_act_pack(t, *b.bn[0], relu=b.relu[0])
         y = torch.empty((t.shape[0], b.planes, t.shape[2], t.shape[3]), dtype=torch.float32, device=t.device)
         late = dict(residual=idn, residual_after_act=True, pack_before_residual=True, out=y, out_f32=True)
-        _, p = c1.run(p, out_packed=True, out_c_offset=0, pack_scale=b.bn[1][0], pack_shift=b.bn[1][1],
-                      pack_relu=b.relu[1], **late)
-        _, p = c2.run(p, out_packed=True, out_c_offset=half, pack_scale=b.bn[2][0], pack_shift=b.bn[2][1],
-                      pack_relu=b.relu[2], **late)
+        for c, bn, relu, offset in zip((c1, c2), b.bn[1:], b.relu[1:], (0, half)):
+            _, p = c.run(p, out_packed=True, out_c_offset=offset, pack_scale=bn[0], pack_shift=bn[1], pack_relu=relu, **late)
         c3.run(p, out_packed=False, out_c_offset=half + quarter, **late)
         return y, None, None
 
@@ -1045,13 +1049,7 @@ class FusedBlocks(FusedResNet):
         fastpath.invalidate(self.model, executors=False)
         if self.model.training:
             raise FusionError("FusedBlocks is inference-only: call .eval() first")
-        self._blocks = []
-        self._names = {id(mod): name for name, mod in self.model.named_modules()}
-        for blk in self.model:
-            self._add_block(blk)
-        self._link_hblocks()
-        self._graph = None
-        self._sig = param_signature(self.model)
+        self._plan(self.model)
 
     @torch.no_grad()
     def _forward_impl(self, x: torch.Tensor) -> torch.Tensor:

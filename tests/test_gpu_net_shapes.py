@@ -11,8 +11,10 @@ and the judge: tests/net_shapes.py).  For every family and input:
      for several batches in flight (``throughput_mode``): the same logits and the same planes in front of every binary
      convolution.
 
-Then: the default tables route launches of the 224 x 160 input (56 x 40, 28 x 20, ... : their keys hold no width) to each
-matrix-core form, and the table reached both sides of every shape-keyed decision of bnn_amd/executor.py.
+Then: a hierarchical-block network with two blocks in its late stages at 112 x 112, where the first block of a stage meets
+7 x 7 at 256 channels (its shortcut convolution inside a channel-lane launch); the default tables route launches of the
+224 x 160 input (56 x 40, 28 x 20, ... : their keys hold no width) to each matrix-core form, and the table reached both
+sides of every shape-keyed decision of bnn_amd/executor.py.
 """
 import contextlib
 import json
@@ -20,9 +22,11 @@ import json
 import pytest
 import torch
 
+import bnn_amd as bnn
 from bnn_amd import executor, fastpath
-from bnn_amd.executor import Form
+from bnn_amd.executor import Form, HForm
 from bnn_amd.inference import FusedResNet, auto_fusion, per_layer_forward, tap_binary_inputs
+from bnn_amd.models import HBlock, ResNet
 from tests import net_shapes as ns
 from tests.test_gpu_mfma_net import DENSE, FOLD, FP4, _convs
 
@@ -38,7 +42,7 @@ MODES = {"1": ("1", "1", "1", "1"),                 # the defaults: the tables o
 JUDGED = {"per_layer": {}, "fused": {}}             # path -> {case id: Verdict.report()}
 RAN = set()                                         # (case, mode) that went through _forward
 POOLS = {}                                          # (N, C, H, W) in front of a stage's AvgPool2d -> _pool_into_hblock took it
-POOL_ASKED = set()                                  # (H, W) that _pooled_form asked hipops.hblock_pool_supported about
+POOL_ASKED = set()                                  # (H, W) that _H.route asked hipops.hblock_pool_supported about
 
 
 # ------------------------------------------------------------------------------------------------------------- fixtures
@@ -78,7 +82,7 @@ def _engine(nets, engines, family, mode, monkeypatch):
 @contextlib.contextmanager
 def _watch_pools():
     """Notes, for every AvgPool2d in front of a stage that ``_run_blocks`` reaches, whether ``_pool_into_hblock`` took it,
-    and the sizes at which ``_pooled_form`` gets as far as the kernel's own query."""
+    and the sizes at which ``_H.route`` gets as far as the pooled form's own query."""
     orig, query = FusedResNet._pool_into_hblock, executor.hipops.hblock_pool_supported
 
     def asked(N, c_in, H, W, *args, **kw):
@@ -223,6 +227,40 @@ def test_matrix_core_switches_change_no_bit(case, mode, nets, engines, monkeypat
         assert not forms & FP4
 
 
+LATE = (2, 3, 112, 112)     # HBlock stages of 1, 1, 2, 2 blocks at 28x28, 14x14, 7x7, 3x3
+LATE_RUNS = {}
+
+
+def _late(engines, monkeypatch):
+    """A hierarchical block with a shortcut convolution and a block behind it in its stage, at 7 x 7 and 256 channels (the
+    channel-lane kernel takes widths from 256 on; the table's network has one block in each of its last two stages)."""
+    if not LATE_RUNS:
+        net = bnn.prepare_binary_model(ResNet(HBlock, [1, 1, 2, 2], num_classes=1000), ns._cfg(),
+                                       custom_config_layers_name={"conv1": bnn.BConfig(), "fc": bnn.BConfig()})
+        shapes = {k: tuple(v.shape) for k, v in net.state_dict().items()}
+        net.load_state_dict({k: torch.from_numpy(v) for k, v in ns.gen.model_state(shapes, 4).items()})
+        net, x = net.eval().to(DEV), ns.input_of(LATE).to(DEV)
+        for mode in ("1", "tp"):
+            _switch(monkeypatch, mode)
+            eng = engines[("hblock_late", mode)] = FusedResNet(net, throughput_mode=mode == "tp")
+            LATE_RUNS[mode] = _forward(eng, x)
+    return LATE_RUNS
+
+
+def test_hblock_shortcut_launch_in_channel_lanes(engines, monkeypatch):
+    """No network of the table puts a hierarchical block with a shortcut convolution in front of another block of its
+    stage at a width and size the channel-lane kernel takes.  Here the run without a tap takes that launch; the tapped run
+    goes launch by launch: the same logits and planes, alone and with several batches in flight."""
+    runs = _late(engines, monkeypatch)
+    for tapped, planes, plain in runs.values():
+        assert plain.shape == (2, 1000) and torch.isfinite(plain).all() and torch.equal(plain, tapped)
+    assert torch.equal(runs["tp"][2], runs["1"][2])
+    _same_planes(runs["tp"][1], runs["1"][1])
+    shortcut = {r.channel_lanes for mode in runs for b in engines[("hblock_late", mode)]._blocks if b.kind == "h"
+                for r in b.routes.values() if r.form is HForm.SHORTCUT}
+    assert True in shortcut
+
+
 # ------------------------------------------------------------------------------------------- what the table reached
 def _ensure(nets, engines, monkeypatch, modes=tuple(MODES), cases=ns.CASES):
     """The runs above, for whatever part of the table this session has not run (a selection with -k)."""
@@ -262,26 +300,31 @@ def test_default_tables_match_at_a_foreign_width(nets, engines, monkeypatch):
 
 def test_the_table_reached_both_sides_of_every_decision(nets, engines, monkeypatch):
     _ensure(nets, engines, monkeypatch)
+    _late(engines, monkeypatch)
     missing = []
 
     def need(cond, what):
         if not cond:
             missing.append(what)
 
-    # hierarchical blocks: b.geo[(N, H, W)]
+    # hierarchical blocks: b.routes[(N, H, W)]
     pooled_hit, pooled_small, pooled_odd, lanes, pixels, refused, sc = set(), set(), set(), set(), set(), set(), set()
+    reached = set()
     for (family, *_), eng in engines.items():
         blocks = eng._blocks
         for i, b in enumerate(blocks):
-            if b.kind != "h":
+            if b.kind != "h" or b.hpack is None:
                 continue
             ends_stage = i + 1 < len(blocks) and blocks[i + 1].kind == "pool"
-            for (N, H, W), g in b.geo.items():
-                (lanes if g.cl else pixels if g.ok else refused).add((H, W))
-                if g.sc is not None:
-                    sc.add(bool(g.sc))
-                if ends_stage and g.pooled is not None:
-                    if g.pooled is not False:
+            assert ends_stage == (b.end_pool is not None) and (b.behind is blocks[i + 2] if ends_stage else b.behind is None)
+            for (N, H, W), r in b.routes.items():
+                reached.add((r.form, r.channel_lanes))
+                (lanes if r.channel_lanes else refused if r.form is HForm.STEPS else pixels).add((H, W))
+                if b.hsc is not None:
+                    sc.add(r.form is HForm.SHORTCUT)
+                if ends_stage and r.form in (HForm.POOLED, HForm.ONE):      # the pooled form was considered
+                    if r.form is HForm.POOLED:
+                        assert r.pool_consts is not None
                         pooled_hit.add((H, W))
                     elif H % 2 or W % 2:
                         pooled_odd.add((H, W))
@@ -297,13 +340,16 @@ def test_the_table_reached_both_sides_of_every_decision(nets, engines, monkeypat
          f"_pooled_form asks the kernel at even sizes of 784 pixels or more alone: asked at {sorted(POOL_ASKED)}")
     need(any(POOLS.values()), "_pool_into_hblock: a hit")
     need(any(not hit and (s[2] % 2 or s[3] % 2) for s, hit in POOLS.items()), "_pool_into_hblock: a decline at an odd size")
-    # (the channel-lane kernel is built for 7 x 7 and 14 x 14 alone: csrc/hblock_cl.hip.  _hblock_ok asks for it at H == 7,
+    # (the channel-lane kernel is built for 7 x 7 and 14 x 14 alone: csrc/hblock_cl.hip.  _H.route asks for it at H == 7,
     #  and at every size with several batches in flight; at 7 x 5 the kernel's own query says no and pixel lanes run)
     need((7, 7) in lanes, "the channel-lane form at 7 x 7")
     need(any(W != 7 for _, W in lanes), "the channel-lane form at a width other than 7")
     need((7, 5) in pixels, "channel lanes asked for at 7 x 5, refused by the kernel's query, pixel lanes taken")
     need(any(H != W for H, W in pixels), "the pixel-lane form at a non-square size")
     need(True in sc, "the shortcut convolution inside the hierarchical block's launch")
+    for form, channel_lanes in ((HForm.ONE, False), (HForm.ONE, True), (HForm.SHORTCUT, False), (HForm.SHORTCUT, True),
+                                (HForm.POOLED, False)):
+        need((form, channel_lanes) in reached, f"{form.name} in {'channel' if channel_lanes else 'pixel'} lanes")
     # (a geometry hblock_supported refuses in both forms: none exists in the table — printed below, were one to appear)
     # the folded shortcut: b.fold_geo[(images per launch, Ho, Wo)]
     fold = set()
