@@ -557,7 +557,18 @@ def stem7x7(x: torch.Tensor, w: torch.Tensor, bn_scale: torch.Tensor, bn_shift: 
     ``out = (y, PackedAct)``: write into these preallocated results of an earlier call with the same input shape
     (the static buffers a captured HIP graph of the rest of the network reads: ``FusedResNet.forward_fresh``).
     ``pack_affine = (scale, shift)``: the planes are those of ``fmaf(y, scale[c], shift[c]) > 0`` — the input of a
-    pre-activation block's first binary layer (its bn1 + ReLU) — instead of ``y > 0``; the fp32 output is unchanged."""
+    pre-activation block's first binary layer (its bn1 + ReLU) — instead of ``y > 0``; the fp32 output is unchanged.
+
+    Arithmetic and what it admits (oracle and derivation: ``tests/stem_ref.py``).  Default: both fp32 operands split
+    into fp16 ``hi + lo``, ``hi*hi + lo*hi + hi*lo`` with fp32 accumulation; the convolution is within
+    ``147 * 2^-24 * (|x| conv |w|)`` of the exact one per element — the worst case of an fp32 fmaf chain —, the fused
+    output within ``|bn_scale|`` times that plus one rounding.  Weights of any size are admitted: a channel whose largest
+    ``|w|`` is below 2^-5 is multiplied by the power of two that brings it into [1, 2) before the split and its
+    ``bn_scale`` by the inverse, inside the kernel and exactly (above 2^-5 nothing is scaled).  The image is not
+    rescaled: the bound holds for images whose largest magnitude is at most 2^15 (``hi`` stays finite) and whose typical
+    magnitude is at least 2^-8 (below that the ``lo`` halves of the pixels go subnormal and the error grows towards
+    ``fp16``'s); normalised and [0, 1] images are well inside.  ``fp16``: one product of the rounded operands, the same
+    bound with 2^-11 for 2^-24, same ranges.  ``exact_fp32``: an fp32 fmaf chain, any fp32 operands."""
     x = _require_cuda_f32(x, "stem input")
     w = _require_cuda_f32(w.detach(), "stem weight")
     if x.dim() != 4 or x.shape[1] != 3 or tuple(w.shape) != (64, 3, 7, 7):
@@ -599,8 +610,12 @@ def stem7x7(x: torch.Tensor, w: torch.Tensor, bn_scale: torch.Tensor, bn_shift: 
 
 def stem7x7_conv(x: torch.Tensor, w: torch.Tensor, fp16: bool = False) -> torch.Tensor:
     """The stem's convolution alone — conv 7x7/2/3, 3 -> 64, no bias (bnn/models/resnet.py:93,150) — on the matrix cores
-    (``bnn_hip_stem7x7_conv_f32``: the MFMA stream of ``stem7x7``, fp32-class accuracy): what a TRAINING step needs in
-    front of its batch-statistics BatchNorm.  Returns fp32 ``[N, 64, Hc, Wc]``."""
+    (``bnn_hip_stem7x7_conv_f32``: the MFMA stream of ``stem7x7``): what a TRAINING step needs in front of its
+    batch-statistics BatchNorm.  Returns fp32 ``[N, 64, Hc, Wc]``.
+    Every element is within ``147 * 2^-24 * (|x| conv |w|)`` of the exact convolution (``fp16``: 2^-11 for 2^-24) for
+    weights of any size — a channel below 2^-5 is split at a power-of-two scale and the stored value scaled back, exactly,
+    on every launch, so a training step's changing weights need no preparation — and images whose largest magnitude is at
+    most 2^15 and whose typical magnitude is at least 2^-8 (see ``stem7x7``; ``tests/stem_ref.py``)."""
     x = _require_cuda_f32(x, "stem input")
     w = _require_cuda_f32(w.detach(), "stem weight")
     if x.dim() != 4 or x.shape[1] != 3 or tuple(w.shape) != (64, 3, 7, 7):

@@ -9,8 +9,8 @@
 // Two arithmetic modes:
 //   SPLIT (default): every fp32 operand is split into two fp16 halves (x = hi + lo, 22 mantissa bits)
 //     and the product is formed as hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_f16 with fp32
-//     accumulation: measured error 2.8e-7 relative (the rounding class of an fp32 convolution) at
-//     3/16 of the matrix time of the fp32 instruction.
+//     accumulation: measured error 2.8e-7 relative at 3/16 of the matrix time of the fp32
+//     instruction (stem_rows.hip states the bound it meets and the operand ranges it is met for).
 //   exact (BNN_HIP_STEM_EXACT_FP32): v_mfma_f32_16x16x4_f32, bit-for-bit a k-ordered fp32 fmaf chain.
 // The input patch (39x35x3 floats), the whole weight matrix and the post-BN/ReLU conv tile live in LDS;
 // conv outputs never touch HBM (the library path writes and re-reads 822 MB at batch 256).  Persistent

@@ -1,7 +1,9 @@
 // stem_rows.hip — the fused stem (see stem.hip for the layer) with the max-pool done IN THE ACCUMULATORS.
 // Arithmetic as in stem_split.hip: fp32 operands split into fp16 hi + lo, product = lo*hi + hi*lo + hi*hi on
-// v_mfma_f32_16x16x32_f16 with fp32 accumulation (the rounding class of an fp32 convolution); results are
-// bit-identical to that kernel's.
+// v_mfma_f32_16x16x32_f16 with fp32 accumulation: every element within 147 * 2^-24 * (|x| conv |w|) of the exact
+// convolution, the worst case of an fp32 fmaf chain, for weights of any size (channels below 2^-5 are split at a
+// power-of-two scale: "Weight scale" below) and images of magnitude 2^-8 .. 2^15 (tests/stem_ref.py); where no channel is
+// scaled, results are bit-identical to that kernel's.
 //
 // What is different (round 3; stem_split.hip spent more cycles outside its matrix phase than inside):
 //  * the GEMM is TRANSPOSED: A = weights (16 channels x K), B = patch (K x 16 conv pixels).  A lane's four
@@ -69,11 +71,12 @@ constexpr int PER_T = (NROW + RSTEP - 1) / RSTEP;    // 9 column pairs per threa
 constexpr int PATCH_D = NROW * ROWD;                 // dwords per patch buffer
 constexpr int OFF_BITS = 2 * PATCH_D * 4;            // sign words of the tile: [2][56 pixels][2 halves] u32
 constexpr int OFF_BN = OFF_BITS + 2 * PTH * PTW * 8;  // BNN_ROWS_LEAN: BatchNorm constants [a|b][64 channels] fp32
+constexpr int OFF_WS = OFF_BN + 2 * COUT * 4;        // inverse weight scale of every channel (a power of two) [64] fp32
 #ifdef BNN_ROWS_TIMING  // per-phase shader-clock sums of every wave (debug builds): [wave][16 phases][64 lanes] u32 in LDS
-constexpr int OFF_TIME = OFF_BN + 2 * COUT * 4;
+constexpr int OFF_TIME = OFF_WS + COUT * 4;
 constexpr int LDS_BYTES = OFF_TIME + NW * 16 * 64 * 4;
 #else
-constexpr int LDS_BYTES = OFF_BN + 2 * COUT * 4;
+constexpr int LDS_BYTES = OFF_WS + COUT * 4;
 #endif
 constexpr int CONV_ROW_D = 2 * ROWD;                 // one conv row further = two input rows further
 static_assert(CONV_ROW_D + LO_D + 3 < 256, "two conv rows must stay inside ds_read2_b32's offsets");
@@ -229,8 +232,15 @@ __global__ __launch_bounds__(stemr::NT, 2) BNN_ROWS_VGPR_ATTR void stem_rows_ker
 
   // ---- once: A fragments (hi, lo) of this wave's 2 channel tiles x 6 k-steps.
   // MFMA 16x16x32 A operand: lane holds A[i = li][k = 8*lg + e]  ->  channel 16*tt + li, k-row 4*ks + lg, kx = e - 1.
+  // Weight scale.  lo = v - hi is at most 2^-11 |v|, and fp16 goes subnormal below 2^-14: the lo half of a weight below
+  // 2^-3 has already lost bits, and a channel of weights of 2^-12 is no fp32-class product any more (its planes sit behind
+  // a BatchNorm that multiplies the error back up).  So a channel whose largest |w| is below 2^-5 is multiplied by the
+  // power of two that brings that maximum into [1, 2) before the split, and its bn_a (RAW: its stored value) by the
+  // inverse: both exact.  At and above 2^-5 — every initialisation in use — the scale is 1 and the bits are those of the
+  // unscaled split (csrc/legacy/stem_split.hip).  tests/stem_ref.py: weight_scale.
   constexpr bool K16 = BNN_ROWS_K16TAIL != 0 && !HALF;
   half8 wh[KSTEPS][2], wl[KSTEPS][2];
+  float wv[KSTEPS][2][8], wmax[2] = {0.0f, 0.0f};
 #pragma unroll
   for (int ks = 0; ks < KSTEPS; ++ks) {
     const int krow = 4 * ks + lg;
@@ -246,11 +256,30 @@ __global__ __launch_bounds__(stemr::NT, 2) BNN_ROWS_VGPR_ATTR void stem_rows_ker
           const int slot = 4 * (lg & 1) + e;
           v = (lg < 2 && e < 4 && slot >= 1) ? w[((size_t)(o * CIN + CIN - 1) * KS + KS - 1) * KS + slot - 1] : 0.0f;
         }
+        wv[ks][tt][e] = v;
+        wmax[tt] = fmaxf(wmax[tt], fabsf(v));  // (a NaN weight does not raise the maximum: no scale, NaN products)
+      }
+    }
+  }
+#pragma unroll
+  for (int tt = 0; tt < 2; ++tt) {
+    // the four lane groups hold the (c, ky) rows of channel 32 * nh + 16 * tt + li between them
+    wmax[tt] = fmaxf(wmax[tt], __shfl_xor(wmax[tt], 16));
+    wmax[tt] = fmaxf(wmax[tt], __shfl_xor(wmax[tt], 32));
+    const uint32_t ex = __builtin_bit_cast(uint32_t, wmax[tt]) >> 23;  // biased exponent: 2^(ex - 127) <= max |w|
+    const bool scaled = ex >= 1u && ex <= 121u;                         // a normal number below 2^-5
+    const float up = scaled ? __builtin_bit_cast(float, (254u - ex) << 23) : 1.0f;
+    if (lg == 0)
+      reinterpret_cast<float*>(lds_rows + OFF_WS)[32 * nh + 16 * tt + li] = scaled ? __builtin_bit_cast(float, ex << 23) : 1.0f;
+#pragma unroll
+    for (int ks = 0; ks < KSTEPS; ++ks)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float v = wv[ks][tt][e] * up;
         const _Float16 h = (_Float16)v;
         wh[ks][tt][e] = h;
         wl[ks][tt][e] = (_Float16)(v - (float)h);
       }
-    }
   }
   // B operand: lane holds B[k = 8*lg + e][j = li] = patch[c][2*t + ky][2*(14*mg + lcol) + e] of conv pixel (t, 14*mg + lcol).
   // kb[ks]: byte offset of (k-row 4*ks + lg, conv row 0, column pair 14*mg + lcol); zero-weight k-rows read k-row 20.
@@ -443,7 +472,24 @@ __global__ __launch_bounds__(stemr::NT, 2) BNN_ROWS_VGPR_ATTR void stem_rows_ker
     locate(g, n, tx, ty);
     if (!(BNN_ROWS_ABL & 8)) fetch(n, tx, ty);
   }
-  __syncthreads();  // the zero fill is complete
+  __syncthreads();  // the zero fill is complete; every channel's inverse weight scale is in LDS
+  // the inverse scales in the accumulator layout (register r of tile tt -> channel 32*nh + 16*tt + 4*lg + r): folded into
+  // bn_a, or (RAW) kept for the stores
+  [[maybe_unused]] float wsi[2][4];
+  {
+    const float* ws = reinterpret_cast<const float*>(lds_rows + OFF_WS);
+    if constexpr (LEAN) {
+      if (tid < COUT) reinterpret_cast<float*>(lds_rows + OFF_BN)[tid] *= ws[tid];  // read behind the loop's first barrier
+    } else {
+#pragma unroll
+      for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float inv = ws[32 * nh + 16 * tt + 4 * lg + r];
+          if constexpr (RAW) wsi[tt][r] = inv; else ba[tt][r] *= inv;
+        }
+    }
+  }
   if (valid) commit(0);
   float carry[2][4];  // BN'd conv row above the next pooled row (row 2*py - 1), kept across tiles of a strip
 #pragma unroll
@@ -622,7 +668,7 @@ __global__ __launch_bounds__(stemr::NT, 2) BNN_ROWS_VGPR_ATTR void stem_rows_ker
             for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
               for (int r = 0; r < 4; ++r) {
-                rows_st(r_out, raw_lane, soff, acc[d][tt][r]);
+                rows_st(r_out, raw_lane, soff, acc[d][tt][r] * wsi[tt][r]);
                 soff += (r == 3 ? 13u : 1u) * (unsigned)(Hc * Wc) * 4u;
                 asm volatile("" : "+s"(soff));
               }

@@ -331,8 +331,11 @@ int bnn_hip_bn_relu_maxpool_pack_f32(const float* x, int N, int C, int H, int W,
  * x: float32 [N,3,H,W].  Outputs (either may be NULL): out_f32 [N,64,Hp,Wp] and its sign planes
  * P, M ([N,1,Hp,Wp] uint64), Hp = ((H-1)/2 + 1 - 1)/2 + 1 (56 for H = 224).
  * flags = 0: fp32 operands split into fp16 hi+lo halves (22 mantissa bits), products as
- *            hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_f16 with fp32 accumulation — error
- *            ~3e-7 relative, the rounding class of an fp32 convolution, at 3/16 of the matrix time;
+ *            hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_f16 with fp32 accumulation, at 3/16 of the matrix
+ *            time.  Every element of the convolution is within 147 * 2^-24 * (|x| conv |w|) of the exact one (the
+ *            worst case of an fp32 fmaf chain; ~3e-7 relative) for weights of any size — a channel whose largest
+ *            |w| is below 2^-5 is split at a power-of-two scale that bn_scale takes back, inside the kernel — and
+ *            images whose largest magnitude is at most 2^15 and whose typical magnitude is at least 2^-8;
  * flags = BNN_HIP_STEM_EXACT_FP32: v_mfma_f32_16x16x4_f32, bit-for-bit an fp32 fmaf chain.     */
 #define BNN_HIP_STEM_EXACT_FP32 1
 /* Plain fp16 operands, one MFMA per product, fp32 accumulation (the "fp16 MFMA stem" of BASELINE config 5):
