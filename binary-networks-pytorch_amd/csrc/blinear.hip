@@ -20,14 +20,14 @@
 // F that does not fit the LDS pass (128 words = 4096 features by default) is walked in passes; a workgroup then owns at
 // most one channel block per wave, whose accumulators live across the passes.
 //
-// Gradients.  The arithmetic class of csrc/grad.hip: the real operand (g' = alpha[o] g, rounded once in fp32; g for the
-// weight gradient) is split into three bf16 terms hi + mid + lo (truncations: 24 mantissa bits, fp32 exponent range),
-// the ternary operand is exact in bf16, three v_mfma_f32_16x16x32_bf16 per product, fp32 accumulation, smallest term
+// Gradients.  The arithmetic class of csrc/grad.hip (csrc/tgemm.h): the real operand (g' = alpha[o] g, rounded once in
+// fp32; g for the weight gradient) is split into three bf16 terms hi + mid + lo (truncations: 24 mantissa bits, fp32 exponent range),
+// the ternary operand is exact in bf16, three bf16 MFMAs (tg::mfma3) per product, fp32 accumulation, smallest term
 // first.  Both kernels decode their ternary fragments from BITS: dgrad from the forward's own weight pack (sign bit +
 // non-zero mask: no second packing launch, 1/16 of the bytes of bf16 fragments), wgrad from the P / M planes; the STE
 // mask is read from the T plane at the store.  A 64 x 32 tile of the real operand is split once per k-step by the whole
 // workgroup and shared through LDS; a wave owns 64 x 64 outputs (16 accumulator tiles).
-#include "bconv_core.h"
+#include "tgemm.h"
 
 namespace bnn {
 namespace blin {
@@ -38,41 +38,7 @@ constexpr int PASS_WORDS = 128; // default 32-bit words per row and plane of one
 constexpr int APAD = 40;        // gradient kernels: 16-bit containers per row of the 64 x 32 real-operand tile (80 B)
 constexpr int NB = 4;           // gradient kernels: 16-column tiles per wave
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using u16 = unsigned short;
-constexpr unsigned kOne = 0x3F80u, kMinusOne = 0xBF80u;   // +-1 as bf16
-
-// v = hi + mid + lo, each term the truncation of what is left to bf16 (csrc/grad.hip: split8)
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8& hi, bf16x8& mid, bf16x8& lo) {
-  unsigned h[8], m[8], l[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    h[e] = __float_as_uint(v[e]) & 0xFFFF0000u;
-    const float r1 = v[e] - __uint_as_float(h[e]);
-    m[e] = __float_as_uint(r1) & 0xFFFF0000u;
-    const float r2 = r1 - __uint_as_float(m[e]);
-    l[e] = __float_as_uint(r2);
-  }
-  u32x4 ph, pm, pl;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    ph[e] = __builtin_amdgcn_perm(h[2 * e + 1], h[2 * e], 0x07060302u);
-    pm[e] = __builtin_amdgcn_perm(m[2 * e + 1], m[2 * e], 0x07060302u);
-    pl[e] = __builtin_amdgcn_perm(l[2 * e + 1], l[2 * e], 0x07060302u);
-  }
-  hi = __builtin_bit_cast(bf16x8, ph);
-  mid = __builtin_bit_cast(bf16x8, pm);
-  lo = __builtin_bit_cast(bf16x8, pl);
-}
-
-__device__ __forceinline__ bf16x8 pack_codes(const unsigned (&c)[8]) {
-  u32x4 pk;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) pk[e] = c[2 * e] | (c[2 * e + 1] << 16);
-  return __builtin_bit_cast(bf16x8, pk);
-}
+using namespace tg;
 
 // ------------------------------------------------------------------------------------------------- forward
 template <typename XT, int CWC, bool WZ>
@@ -312,7 +278,7 @@ __global__ __launch_bounds__(256) void blinear_dgrad_kernel(const float* __restr
       v[e] = ok ? t : 0.0f;
     }
     bf16x8 hi, mid, lo;
-    split8(v, hi, mid, lo);
+    split3(v, hi, mid, lo);
     *reinterpret_cast<bf16x8*>(a_hi + frow * APAD + 8 * fkg) = hi;
     *reinterpret_cast<bf16x8*>(a_mid + frow * APAD + 8 * fkg) = mid;
     *reinterpret_cast<bf16x8*>(a_lo + frow * APAD + 8 * fkg) = lo;
@@ -325,8 +291,8 @@ __global__ __launch_bounds__(256) void blinear_dgrad_kernel(const float* __restr
       for (int e = 0; e < 8; ++e) {
         const size_t wi = wblk + boff[nb] + (size_t)e * cwc;
         const unsigned wb = wbits[wi], wz = wnz[wi];
-        const bool nzb = bok[nb] && ((wz >> bsh[nb]) & 1u);
-        code[e] = nzb ? (((wb >> bsh[nb]) & 1u) ? kOne : kMinusOne) : 0u;
+        const bool nzb = bok[nb] && ((wz >> bsh[nb]) & 1u), bit = (wb >> bsh[nb]) & 1u;
+        code[e] = nzb ? ternary_code(bit, !bit) : (u16)0;
       }
       b[nb] = pack_codes(code);
     }
@@ -338,11 +304,7 @@ __global__ __launch_bounds__(256) void blinear_dgrad_kernel(const float* __restr
       const bf16x8 am = *reinterpret_cast<const bf16x8*>(a_mid + ao);
       const bf16x8 al = *reinterpret_cast<const bf16x8*>(a_lo + ao);
 #pragma unroll
-      for (int nb = 0; nb < NB; ++nb) {   // smallest terms first
-        acc[rt][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, b[nb], acc[rt][nb], 0, 0, 0);
-        acc[rt][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, b[nb], acc[rt][nb], 0, 0, 0);
-        acc[rt][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, b[nb], acc[rt][nb], 0, 0, 0);
-      }
+      for (int nb = 0; nb < NB; ++nb) acc[rt][nb] = mfma3(ah, am, al, b[nb], acc[rt][nb]);
     }
   }
   // D layout: column = li (feature within the tile), row = 4 lg + r; the STE mask is bit f of row m of the T plane
@@ -405,7 +367,7 @@ __global__ __launch_bounds__(256) void blinear_wgrad_kernel(const float* __restr
       v[e] = ok ? t : 0.0f;
     }
     bf16x8 hi, mid, lo;
-    split8(v, hi, mid, lo);
+    split3(v, hi, mid, lo);
     *reinterpret_cast<bf16x8*>(a_hi + fo * APAD + 8 * fmg) = hi;
     *reinterpret_cast<bf16x8*>(a_mid + fo * APAD + 8 * fmg) = mid;
     *reinterpret_cast<bf16x8*>(a_lo + fo * APAD + 8 * fmg) = lo;
@@ -419,8 +381,8 @@ __global__ __launch_bounds__(256) void blinear_wgrad_kernel(const float* __restr
         // (rows past the split's end meet g = 0: any row of the split stands in for them)
         const size_t wi = (size_t)(m < m_end ? m : m_begin) * cw32 + wc[h];
         const unsigned pw = P32[wi], mw = M32[wi];
-        c0[e] = ((pw >> li) & 1u) ? kOne : ((mw >> li) & 1u) ? kMinusOne : 0u;
-        c1[e] = ((pw >> (16 + li)) & 1u) ? kOne : ((mw >> (16 + li)) & 1u) ? kMinusOne : 0u;
+        c0[e] = ternary_code((pw >> li) & 1u, (mw >> li) & 1u);
+        c1[e] = ternary_code((pw >> (16 + li)) & 1u, (mw >> (16 + li)) & 1u);
       }
       b[2 * h] = pack_codes(c0);
       b[2 * h + 1] = pack_codes(c1);
@@ -433,11 +395,7 @@ __global__ __launch_bounds__(256) void blinear_wgrad_kernel(const float* __restr
       const bf16x8 am = *reinterpret_cast<const bf16x8*>(a_mid + ao);
       const bf16x8 al = *reinterpret_cast<const bf16x8*>(a_lo + ao);
 #pragma unroll
-      for (int nb = 0; nb < NB; ++nb) {   // smallest terms first
-        acc[rt][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, b[nb], acc[rt][nb], 0, 0, 0);
-        acc[rt][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, b[nb], acc[rt][nb], 0, 0, 0);
-        acc[rt][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, b[nb], acc[rt][nb], 0, 0, 0);
-      }
+      for (int nb = 0; nb < NB; ++nb) acc[rt][nb] = mfma3(ah, am, al, b[nb], acc[rt][nb]);
     }
   }
   // D layout: column = li (feature within the tile), row = 4 lg + r (output channel within the 16-row tile)

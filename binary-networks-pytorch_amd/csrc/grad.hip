@@ -13,14 +13,13 @@
 // bf16 terms hi + mid + lo (3 x 8 = 24 mantissa bits, and bf16 has the EXPONENT RANGE OF fp32: gradients of a
 // mean-reduced loss at batch 256 are 1e-5 .. 1e-9, where an fp16 split — round 2 — lost everything below its 2^-24
 // quantum), the ternary operand is EXACT in bf16, every product of two bf16 values is exact in fp32, and each
-// product of the GEMM is three v_mfma_f32_16x16x32_bf16 with fp32 accumulation: the rounding class of an fp32
+// product of the GEMM is three bf16 MFMAs (tg::mfma3) with fp32 accumulation: the rounding class of an fp32
 // convolution at any magnitude, at 3/16 of the fp32-MFMA matrix time (the kernels are bound by the VALU work of the
 // fills, not by the matrix pipe).  alpha[o] is folded into the real operand (g' = alpha[o] * g, one fp32 multiply
 // when the tile enters LDS), so the weight operand stays ternary.
 //
-// K-slots.  A row of W <= 64 pixels is given a power-of-two slot (8, 16, 32 or 64 pixels, zero filled); a 64-pixel
-// chunk of the GEMM's pixel dimension is 64/slot consecutive image rows.  An 8-element MFMA fragment never
-// straddles an image row, and 7x7 .. 56x56 images all use >= 87.5 % of the chunk.
+// The split, the ternary codes, the order of the three MFMAs and the K-slots (rows of W <= 64 pixels in power-of-two
+// slots, 64 / slot rows per 64-pixel chunk: 7x7 .. 56x56 images all use >= 87.5 % of the chunk) are csrc/tgemm.h's.
 //
 // Measured (MI355X, ResNet-18 224x224 batch 256, tools/bench_grad.py / tools/bench_train.py, round 3): dgrad 180-400 us
 // per stride-1 layer (the library's fp32 backward: 530-630), 270-540 on the stride-2 layers (350-440), wgrad 205-335 us
@@ -37,27 +36,14 @@
 // zero-upsampled g with all nine taps (3/4 of its MFMAs and of its fill were zeros: 536 -> 380, 276 -> 206, 297 -> 144 us).  1x1 / stride 1 convolutions (the shortcut branches behind an AvgPool:
 // 0.4 % of a ResNet-18's MACs) are the same kernels with one tap and no halo; the weight-gradient kernel then
 // takes 128 input channels per workgroup instead of 32 so that a wave still has 8 accumulator tiles per g fragment.
-#include "bconv_core.h"  // buffer-descriptor helpers
+#include "tgemm.h"
 
 namespace bnn {
 
+using namespace tg;
 namespace grad {
-constexpr int NT = 256;          // 4 waves
-constexpr int APIX = 40;         // dgrad patch: halves per pixel (32 channels + 8 pad: 80 B, conflict-free b128 reads)
 constexpr int AROW = 72;         // wgrad: halves per row of 64 k-slots (+8 pad: 144 B)
-constexpr int SROW = 68;         // dgrad output staging: floats per channel row of 64 pixels
 }  // namespace grad
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using half8 = __attribute__((ext_vector_type(8))) __bf16;   // eight bf16 values: one MFMA fragment (name kept: 16 bytes)
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using u16 = unsigned short;                                   // the LDS planes are arrays of 16-bit containers
-constexpr unsigned short kBf16One = 0x3F80, kBf16MinusOne = 0xBF80;
-
-__device__ __forceinline__ half8 bf16_const8(unsigned short v) {
-  const unsigned d = (unsigned)v * 0x00010001u;
-  return __builtin_bit_cast(half8, u32x4{d, d, d, d});
-}
 
 struct GradGeo {
   int N, O, C;
@@ -65,45 +51,16 @@ struct GradGeo {
   int Hx, Wx;    // input tensor x (and gx): [N,C,Hx,Wx]
   int Hg, Wg;    // gradient tensor g:       [N,O,Hg,Wg],  Hg = (Hx - 1) / st + 1
   int st;        // convolution stride (1 or 2)
-  int slot, RR;  // pixels per row slot (pow2 >= W, >= 8); row slots per 64-pixel chunk = 64 / slot
-  int R;         // image rows a chunk advances by = min(RR, H)
-  int chunks;    // chunks per image = ceil(H / R)
-  int gshift;    // log2(slot / 8): 8-pixel groups per row slot
+  int slot, RR, R, chunks, gshift;  // tg::Slots of (H, W), field by field
   unsigned g_bytes;  // bytes of the gradient tensor g (the range of its buffer descriptor)
   unsigned x_bytes;  // bytes of x / gx
   int cw64;          // XP kernels: 64-channel groups of the bit planes that stand for x (csrc/pack_ste.hip)
   unsigned p_bytes;  // bytes of one such plane, [N][cw64][Hx][Wx] uint64
 };
 
-// v = hi + mid + lo (+ at most 2^-24 |v|): each term the TRUNCATION of what is left to bf16 (the remainders are exact
-// in fp32, so the three terms carry the leading 24 mantissa bits; truncation needs no rounding logic and one
-// v_perm_b32 packs two terms into a dword).  NaN / infinities travel in `hi` (the remainder of an infinity is NaN,
-// as in the fp32 product it stands for).
-__device__ __forceinline__ void split8(const float (&v)[8], half8& hi, half8& mid, half8& lo) {
-  unsigned h[8], m[8], l[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    h[e] = __float_as_uint(v[e]) & 0xFFFF0000u;
-    const float r1 = v[e] - __uint_as_float(h[e]);
-    m[e] = __float_as_uint(r1) & 0xFFFF0000u;
-    const float r2 = r1 - __uint_as_float(m[e]);
-    l[e] = __float_as_uint(r2);
-  }
-  u32x4 ph, pm, pl;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {  // the upper halves of two dwords -> one dword
-    ph[e] = __builtin_amdgcn_perm(h[2 * e + 1], h[2 * e], 0x07060302u);
-    pm[e] = __builtin_amdgcn_perm(m[2 * e + 1], m[2 * e], 0x07060302u);
-    pl[e] = __builtin_amdgcn_perm(l[2 * e + 1], l[2 * e], 0x07060302u);
-  }
-  hi = __builtin_bit_cast(half8, ph);
-  mid = __builtin_bit_cast(half8, pm);
-  lo = __builtin_bit_cast(half8, pl);
-}
-
 // ------------------------------------------------------------------------------------------------- weight operand
 // alpha[o] = max |What[o,:,:,:]| (What = +-alpha or 0 exactly) and sign(What) in MFMA B-fragment order for dgrad:
-//   Bp[ob][tap][cs][lane][e] = sign(What[o = 32 ob + 8 (lane>>4) + e][c = 16 cs + (lane&15)][tap])   (fp16)
+// tg::sign_frag, Bp[ob][tap][cs][lane][e] (bf16 codes)
 __global__ __launch_bounds__(64) void grad_alpha_kernel(const float* __restrict__ what, int per_o,
                                                         float* __restrict__ alpha) {
   const float* p = what + (size_t)blockIdx.x * per_o;
@@ -115,27 +72,23 @@ __global__ __launch_bounds__(64) void grad_alpha_kernel(const float* __restrict_
 }
 
 __global__ __launch_bounds__(64) void grad_pack_weight_kernel(const float* __restrict__ what, int O, int C,
-                                                              int CS, int T, half8* __restrict__ Bp) {
+                                                              int CS, int T, bf16x8* __restrict__ Bp) {
   const int lane = threadIdx.x, li = lane & 15, lg = lane >> 4;
   const int cs = blockIdx.x % CS, tap = (blockIdx.x / CS) % T, ob = blockIdx.x / (CS * T);
   const int c = 16 * cs + li;
-  unsigned short b[8];
+  u16 b[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const int o = 32 * ob + 8 * lg + e;
-    const float v = (o < O && c < C) ? what[((size_t)o * C + c) * T + tap] : 0.0f;
-    b[e] = v > 0.0f ? kBf16One : v < 0.0f ? kBf16MinusOne : (unsigned short)0;
+    b[e] = ternary_code((o < O && c < C) ? what[((size_t)o * C + c) * T + tap] : 0.0f);
   }
-  u32x4 pk;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) pk[e] = (unsigned)b[2 * e] | ((unsigned)b[2 * e + 1] << 16);
-  Bp[(size_t)blockIdx.x * 64 + lane] = __builtin_bit_cast(half8, pk);
+  Bp[sign_frag(ob, tap, cs, T, CS, lane)] = pack_codes(b);
 }
 
 // ------------------------------------------------------------------------------------------------- dgrad
 // GEMM: M = pixels (one 64-slot chunk of one image per workgroup; 32 slots per wave), N = input channels c (32 * NSUB
 // per wave, 64 * NSUB per workgroup, grid.y blocks), K = (o, tap): loop over blocks of 32 output channels; per block the
-// chunk's rows +- 1 of g' = alpha[o] * g enter LDS as fp16 hi / lo, [pixel][32 o]; 9 taps = 9 k-steps of 32.
+// chunk's rows +- 1 of g' = alpha[o] * g enter LDS as bf16 hi / mid / lo, [pixel][32 o]; 9 taps = 9 k-steps of 32.
 // Epilogue: accumulators -> LDS [c][pixel] -> coalesced NCHW stores with the STE mask 1[|x| < 1].
 // S2 (stride 2, 3x3): the four parity classes (py, px) of the x pixels are four convolutions over the GRID OF g —
 //     gx[2a + py, 2b + px] = sum over o and the taps with ky = py + 1, kx = px + 1 (mod 2) of
@@ -146,12 +99,9 @@ __global__ __launch_bounds__(64) void grad_pack_weight_kernel(const float* __res
 // XP: `xin` is not the fp32 input but its straight-through mask as a bit plane, T = |x| < 1 ([N][C/64][H][W] uint64,
 // csrc/pack_ste.hip): what a training step keeps of x for this kernel is 1 bit per element instead of 32.  Same results.
 template <int NSUB, int KS, bool S2 = false, bool XP = false>
-__global__ __launch_bounds__(grad::NT) void dgrad_kernel(const float* __restrict__ g,
-                                                            const float* __restrict__ alpha,
-                                                            const half8* __restrict__ Bp,
-                                                            const float* __restrict__ xin,
-                                                            float* __restrict__ gx, const GradGeo q) {
-  using namespace grad;
+__global__ __launch_bounds__(NT) void dgrad_kernel(const float* __restrict__ g, const float* __restrict__ alpha,
+                                                   const bf16x8* __restrict__ Bp, const float* __restrict__ xin,
+                                                   float* __restrict__ gx, const GradGeo q) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   static_assert(!S2 || KS == 3, "parity classes: 3x3 / stride 2");
   constexpr int PD = KS / 2, T = KS * KS;
@@ -178,17 +128,11 @@ __global__ __launch_bounds__(grad::NT) void dgrad_kernel(const float* __restrict
   const int ph = wave & 1, chh = wave >> 1;               // pixel half, channel half
   const int cs0 = blockIdx.y * 4 * NSUB + chh * NB;       // first 16-channel group of this wave
 
-  // A-fragment base addresses of the 4 pixel sub-tiles: pixel m = 16 s + li -> (row ry, column x) of the chunk
+  // A-fragment base addresses of the wave's 2 pixel sub-tiles: tap (ky,kx) reads patch pixel (ry+2PD-ky, x+2PD-kx); S2:
+  // (ry + dy, x + dx) from the patch's own origin
   int abase[2];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int s = 2 * ph + i;
-    const int m = 16 * s + li;
-    int ry = m / q.slot, x = m - ry * q.slot;
-    if (x >= q.W || ry >= q.R) { ry = 0; x = 0; }  // dead slot: any valid address, result is never stored
-    // tap (ky,kx) reads patch pixel (ry+2PD-ky, x+2PD-kx); S2: (ry + dy, x + dx) from the patch's own origin
-    abase[i] = S2 ? (ry * PW + x) * APIX + 8 * lg : ((ry + 2 * PD) * PW + (x + 2 * PD)) * APIX + 8 * lg;
-  }
+  for (int i = 0; i < 2; ++i) abase[i] = patch_base(16 * (2 * ph + i) + li, q.slot, q.W, q.R, PW, 1, S2 ? 0 : 2 * PD, lg);
 
   f32x4 acc[2][NB];
 #pragma unroll
@@ -206,17 +150,8 @@ __global__ __launch_bounds__(grad::NT) void dgrad_kernel(const float* __restrict
   const BufRsrc r_g = make_rsrc_sized(g, q.g_bytes);
   unsigned fvoff[FK];
   int flds[FK];
-#pragma unroll
-  for (int k = 0; k < FK; ++k) {
-    const int pix = lane + 64 * k;
-    const int pr = pix / PW, pc = pix - pr * PW;
-    // (S2: the chunk's rows of g from its own origin, one halo row / column behind)
-    const int y = S2 ? y0 + pr : y0 - PD + pr, x = S2 ? pc : pc - PD;
-    const int yg = y, xg = x;
-    const bool in = pix < PP && y >= 0 && x >= 0 && yg < q.Hg && xg < q.Wg;
-    fvoff[k] = in ? (unsigned)(yg * q.Wg + xg) * 4u : 0xFFFFFFF0u;
-    flds[k] = pix < PP ? pix * APIX + 8 * wave : -1;
-  }
+  // (S2: the chunk's rows of g from its own origin, one halo row / column behind)
+  patch_fill_roles(lane, wave, PW, PP, S2 ? y0 : y0 - PD, S2 ? 0 : -PD, q.Hg, q.Wg, fvoff, flds);
   const unsigned plane4 = (unsigned)HGg * 4u;
   // the taps of this launch: all T, or (S2) those of the parity class — ky = 1 | {0, 2}, kx = 1 | {0, 2}
   const int ntap = S2 ? (1 + py) * (1 + px) : T;
@@ -228,14 +163,14 @@ __global__ __launch_bounds__(grad::NT) void dgrad_kernel(const float* __restrict
 
   for (int ob = 0; ob < OB; ++ob) {
     __syncthreads();  // previous block's patch is consumed
-    auto load_w = [&](half8 (&dst)[NB], int tap) {
+    auto load_w = [&](bf16x8 (&dst)[NB], int tap) {
 #pragma unroll
       for (int ns = 0; ns < NB; ++ns) {
         const int cs = cs0 + ns;
-        dst[ns] = cs < CS ? Bp[((size_t)(ob * T + tap) * CS + cs) * 64 + lane] : bf16_const8(0);
+        dst[ns] = cs < CS ? Bp[sign_frag(ob, tap, cs, T, CS, lane)] : zero_frag();
       }
     };
-    half8 b[NB];
+    bf16x8 b[NB];
     load_w(b, tap_of(0));
     const int o0 = 32 * ob + 8 * wave;
     float av[8];
@@ -252,16 +187,16 @@ __global__ __launch_bounds__(grad::NT) void dgrad_kernel(const float* __restrict
       for (int e = 0; e < 8; ++e) {
         // channels past O: an out-of-range offset reads 0 (a select, not a branch: behind a branch every load is
         // waited for before the next one is issued)
-        const unsigned vo = o0 + e < q.O ? fvoff[k] : 0xFFFFFFF0u;
+        const unsigned vo = o0 + e < q.O ? fvoff[k] : kOOB;
         v[e] = buf_ld(r_g, vo, o0 + e < q.O ? soff : 0u) * av[e];
         soff += plane4;
       }
-      half8 hi, mid, lo;
-      split8(v, hi, mid, lo);
+      bf16x8 hi, mid, lo;
+      split3(v, hi, mid, lo);
       if (flds[k] >= 0) {
-        *reinterpret_cast<half8*>(pa_hi + flds[k]) = hi;
-        *reinterpret_cast<half8*>(pa_mid + flds[k]) = mid;
-        *reinterpret_cast<half8*>(pa_lo + flds[k]) = lo;
+        *reinterpret_cast<bf16x8*>(pa_hi + flds[k]) = hi;
+        *reinterpret_cast<bf16x8*>(pa_mid + flds[k]) = mid;
+        *reinterpret_cast<bf16x8*>(pa_lo + flds[k]) = lo;
       }
     }
     __syncthreads();
@@ -273,35 +208,24 @@ __global__ __launch_bounds__(grad::NT) void dgrad_kernel(const float* __restrict
       const int toff = S2 ? -((((py + 1 - ky) >> 1) * PW + ((px + 1 - kx) >> 1)) * APIX) : (ky * PW + kx) * APIX;
       // the NEXT tap's sign(W) fragments are requested before this tap's MFMAs (tap 0's before the fill): a load in
       // front of its own MFMAs exposed one L2 round trip per tap, 18 per workgroup at 64 channels
-      half8 bn[NB];
+      bf16x8 bn[NB];
 #pragma unroll
       for (int ns = 0; ns < NB; ++ns) bn[ns] = b[ns];
       if (ti + 1 < ntap) load_w(bn, tap_of(ti + 1));
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        const half8 ah = *reinterpret_cast<const half8*>(pa_hi + abase[i] - toff);
-        const half8 am = *reinterpret_cast<const half8*>(pa_mid + abase[i] - toff);
-        const half8 al = *reinterpret_cast<const half8*>(pa_lo + abase[i] - toff);
+        const bf16x8 ah = *reinterpret_cast<const bf16x8*>(pa_hi + abase[i] - toff);
+        const bf16x8 am = *reinterpret_cast<const bf16x8*>(pa_mid + abase[i] - toff);
+        const bf16x8 al = *reinterpret_cast<const bf16x8*>(pa_lo + abase[i] - toff);
 #pragma unroll
-        for (int ns = 0; ns < NB; ++ns) {  // smallest terms first
-          acc[i][ns] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, b[ns], acc[i][ns], 0, 0, 0);
-          acc[i][ns] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, b[ns], acc[i][ns], 0, 0, 0);
-          acc[i][ns] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, b[ns], acc[i][ns], 0, 0, 0);
-        }
+        for (int ns = 0; ns < NB; ++ns) acc[i][ns] = mfma3(ah, am, al, b[ns], acc[i][ns]);
       }
 #pragma unroll
       for (int ns = 0; ns < NB; ++ns) b[ns] = bn[ns];
     }
   }
   __syncthreads();  // the patch is dead: its LDS becomes the [channel][pixel] staging tile
-  // D layout: column = li (channel within the 16-group), row = 4 lg + r (pixel within the sub-tile)
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int ns = 0; ns < NB; ++ns)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        stage[((chh * NB + ns) * 16 + li) * SROW + 16 * (2 * ph + i) + 4 * lg + r] = acc[i][ns][r];
+  stage_acc(stage, acc, ph, chh, li, lg);
   __syncthreads();
   // A thread keeps ONE pixel of the chunk (its lane) and walks the channels wave, wave + 4, ...: the STE operand x of
   // all its 16 NSUB outputs is requested first (buffer loads: a dead pixel / channel is an out-of-range offset, the
@@ -309,23 +233,24 @@ __global__ __launch_bounds__(grad::NT) void dgrad_kernel(const float* __restrict
   // round trip per channel, 16 or 32 in a row (most of the kernel's time on the 56 x 56 layers).
   const int c_blk = blockIdx.y * 64 * NSUB;
   constexpr int IT = 16 * NSUB;
-  const int ery = lane >> (q.gshift + 3), ex = lane & (q.slot - 1);
+  int ery, ex;
+  const bool echunk = chunk_pixel(lane, q.slot, q.gshift, q.W, q.R, y0, q.H, ery, ex);
   // (S2: chunk pixel (a, b) of the g grid is x pixel (2a + py, 2b + px))
   const int eyy = S2 ? 2 * (y0 + ery) + py : y0 + ery, exx = S2 ? 2 * ex + px : ex;
-  const bool elive = ex < q.W && ery < q.R && y0 + ery < q.H && eyy < q.Hx && exx < q.Wx;
-  const unsigned elane = elive ? (unsigned)(eyy * q.Wx + exx) * 4u : 0xFFFFFFF0u;
+  const bool elive = echunk && eyy < q.Hx && exx < q.Wx;
+  const unsigned elane = elive ? (unsigned)(eyy * q.Wx + exx) * 4u : kOOB;
   [[maybe_unused]] const BufRsrc r_gx = make_rsrc_sized(gx, q.x_bytes);
   const unsigned xplane4 = (unsigned)HW * 4u;
   if constexpr (XP) {
     // the mask bits of this thread's pixel for channels c_blk .. c_blk + 64 NSUB - 1: one dword per 32 channels
     const BufRsrc r_t = make_rsrc_sized(xin, q.p_bytes);
-    const unsigned tlane = elive ? (unsigned)(eyy * q.Wx + exx) * 8u : 0xFFFFFFF0u;
+    const unsigned tlane = elive ? (unsigned)(eyy * q.Wx + exx) * 8u : kOOB;
     unsigned tw[2 * NSUB];
 #pragma unroll
     for (int h = 0; h < 2 * NSUB; ++h) {
       const int ch = c_blk + 32 * h;  // workgroup-uniform
       const bool ok = ch < 64 * q.cw64;
-      tw[h] = __float_as_uint(buf_ld(r_t, ok ? tlane : 0xFFFFFFF0u,
+      tw[h] = __float_as_uint(buf_ld(r_t, ok ? tlane : kOOB,
                                      ok ? (unsigned)((n * q.cw64 + (ch >> 6)) * HW) * 8u + 4u * ((ch >> 5) & 1) : 0u));
     }
 #pragma unroll
@@ -335,7 +260,7 @@ __global__ __launch_bounds__(grad::NT) void dgrad_kernel(const float* __restrict
       const int lc = wave + 4 * i;                          // channel within the block: dword lc >> 5, bit lc & 31
       [[maybe_unused]] const float r = ((tw[lc >> 5] >> (lc & 31)) & 1u) ? v : 0.0f;
 #if defined(__HIP_DEVICE_COMPILE__)
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, r), r_gx, (int)(c < q.C ? elane : 0xFFFFFFF0u),
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, r), r_gx, (int)(c < q.C ? elane : kOOB),
                                             (int)(c < q.C ? (unsigned)(n * q.C + c) * xplane4 : 0u), 0);
 #endif
     }
@@ -345,7 +270,7 @@ __global__ __launch_bounds__(grad::NT) void dgrad_kernel(const float* __restrict
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
       const int c = c_blk + wave + 4 * i;  // wave-uniform
-      xv[i] = buf_ld(r_x, c < q.C ? elane : 0xFFFFFFF0u, c < q.C ? (unsigned)(n * q.C + c) * xplane4 : 0u);
+      xv[i] = buf_ld(r_x, c < q.C ? elane : kOOB, c < q.C ? (unsigned)(n * q.C + c) * xplane4 : 0u);
     }
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
@@ -353,7 +278,7 @@ __global__ __launch_bounds__(grad::NT) void dgrad_kernel(const float* __restrict
       const float v = stage[(wave + 4 * i) * SROW + lane];
       [[maybe_unused]] const float r = fabsf(xv[i]) < 1.0f ? v : 0.0f;  // hard-tanh STE (NaN x -> 0, like masked_fill)
 #if defined(__HIP_DEVICE_COMPILE__)
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, r), r_gx, (int)(c < q.C ? elane : 0xFFFFFFF0u),
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, r), r_gx, (int)(c < q.C ? elane : kOOB),
                                             (int)(c < q.C ? (unsigned)(n * q.C + c) * xplane4 : 0u), 0);
 #endif
     }
@@ -364,18 +289,16 @@ __global__ __launch_bounds__(grad::NT) void dgrad_kernel(const float* __restrict
 // GEMM: M = 64 output channels o (one 16-row sub-tile per wave), N = 32 input channels x 9 taps (18 sub-tiles of
 // 16 columns, all of them in every wave: 72 accumulator registers), K = pixels: the workgroup walks the 64-slot
 // chunks of its share of the images (split-K over grid.x; partial sums are added by the caller).
-// Per chunk: g (fp16 hi / lo, [o][64 slots]) and sign(x) with one halo row above and below, stored THREE times,
+// Per chunk: g (bf16 hi / mid / lo, [o][64 slots]) and sign(x) with one halo row above and below, stored THREE times,
 // shifted by kx - 1 pixels, so that every tap's 8-pixel fragment is a 16-byte aligned LDS read.
 // XP: sign(x) comes from the bit planes P = x > 0 (`xin`) and M = x < 0 (`xin2`), [N][C/64][Hx][Wx] uint64, instead
 // of the fp32 tensor: 2 bits per element of saved state and of traffic.  Same values, same results.
 // SI: sign(x) fill items per thread, ceil(16 NC BR groups / 256) — a template parameter so that the fill loops are
 // straight-line code (a run-time trip count puts the loaded values behind phi copies, which wait for the loads).
 template <int ST, int KS, int NC, bool XP, int SI>
-__global__ __launch_bounds__(grad::NT, 2) void wgrad_kernel(const float* __restrict__ g,
-                                                            const float* __restrict__ xin,
-                                                            const float* __restrict__ xin2,
-                                                            float* __restrict__ part, const GradGeo q,
-                                                            int imgs_per_split) {
+__global__ __launch_bounds__(NT, 2) void wgrad_kernel(const float* __restrict__ g, const float* __restrict__ xin,
+                                                      const float* __restrict__ xin2, float* __restrict__ part,
+                                                      const GradGeo q, int imgs_per_split) {
   using namespace grad;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   constexpr int PD = KS / 2, T = KS * KS, NJ = NC * T;  // NC 16-channel sub-tiles of input channels per workgroup
@@ -417,7 +340,7 @@ __global__ __launch_bounds__(grad::NT, 2) void wgrad_kernel(const float* __restr
   const BufRsrc r_g = make_rsrc_sized(g, q.g_bytes), r_x = make_rsrc_sized(xin, XP ? q.p_bytes : q.x_bytes);
   [[maybe_unused]] const BufRsrc r_x2 = make_rsrc_sized(XP ? xin2 : xin, XP ? q.p_bytes : q.x_bytes);
   constexpr int XB = XP ? 8 : 4;          // bytes from one pixel to the next in the tensor that stands for x
-  constexpr unsigned kOOB = 0xFFFFFF00u;  // +- a few elements stays out of range (make_geo keeps the tensors below it)
+  constexpr unsigned kOOB = kOOBNear;     // the loads below add immediate element offsets to the marker
   // g: 64 channels x 8 groups of 8 k-slots = 512 items; thread t: group t & 7 of channels t >> 3 and (t >> 3) + 32
   const int g8 = tid & 7, gry = g8 >> q.gshift, gj = g8 & (groups - 1);
   const int g_nv = q.W - 8 * gj;  // elements of the group inside the row (>= 8: all)
@@ -509,11 +432,11 @@ __global__ __launch_bounds__(grad::NT, 2) void wgrad_kernel(const float* __restr
       float v[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = e < g_nv ? gq[i][e] : 0.0f;  // (past the row's end the next row was read)
-      half8 hi, mid, lo;
-      split8(v, hi, mid, lo);
-      *reinterpret_cast<half8*>(a_hi + glds[i]) = hi;
-      *reinterpret_cast<half8*>(a_mid + glds[i]) = mid;
-      *reinterpret_cast<half8*>(a_lo + glds[i]) = lo;
+      bf16x8 hi, mid, lo;
+      split3(v, hi, mid, lo);
+      *reinterpret_cast<bf16x8*>(a_hi + glds[i]) = hi;
+      *reinterpret_cast<bf16x8*>(a_mid + glds[i]) = mid;
+      *reinterpret_cast<bf16x8*>(a_lo + glds[i]) = lo;
     }
     // KS copies of sign(x): copy kx holds sx[ST*p + kx - PD] at slot p
 #pragma unroll
@@ -533,20 +456,18 @@ __global__ __launch_bounds__(grad::NT, 2) void wgrad_kernel(const float* __restr
           // hipcc 7.2 mis-lowers the multi-dword buffer-load builtins, see csrc/bconv_core.h)
           const unsigned ve = e < PD ? (xfirst[i] ? kOOB : vo - (unsigned)XB * (PD - e)) : vo + (unsigned)XB * (e - PD);
           const unsigned pw = __float_as_uint(buf_ld(r_x, ve, x_soff)), mw = __float_as_uint(buf_ld(r_x2, ve, x_soff));
-          sv[e] = (in && ((pw >> xbit[i]) & 1u)) ? kBf16One : (in && ((mw >> xbit[i]) & 1u)) ? kBf16MinusOne
-                                                                                             : (unsigned short)0;
+          sv[e] = in ? ternary_code((pw >> xbit[i]) & 1u, (mw >> xbit[i]) & 1u) : (u16)0;
         } else {
-          const float xv = in ? xq[i][e] : 0.0f;
-          sv[e] = xv > 0.0f ? kBf16One : xv < 0.0f ? kBf16MinusOne : (unsigned short)0;
+          sv[e] = ternary_code(in ? xq[i][e] : 0.0f);
         }
       }
       if (xlds[i] >= 0) {
 #pragma unroll
         for (int kx = 0; kx < KS; ++kx) {
-          u32x4 hv;
+          u16 hv[8];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) hv[e] = (unsigned)sv[ST * (2 * e) + kx] | ((unsigned)sv[ST * (2 * e + 1) + kx] << 16);
-          *reinterpret_cast<u32x4*>(bsx + kx * bplane + xlds[i] + 0) = hv;
+          for (int e = 0; e < 8; ++e) hv[e] = sv[ST * e + kx];
+          *reinterpret_cast<bf16x8*>(bsx + kx * bplane + xlds[i]) = pack_codes(hv);
         }
       }
     }
@@ -575,21 +496,19 @@ __global__ __launch_bounds__(grad::NT, 2) void wgrad_kernel(const float* __restr
     __builtin_amdgcn_sched_barrier(0);   // (the scheduler pulls the first selects of commit() — and their vmcnt wait — up here)
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      const half8 ah = *reinterpret_cast<const half8*>(a_hi + a_off[ks]);
-      const half8 am = *reinterpret_cast<const half8*>(a_mid + a_off[ks]);
-      const half8 al = *reinterpret_cast<const half8*>(a_lo + a_off[ks]);
+      const bf16x8 ah = *reinterpret_cast<const bf16x8*>(a_hi + a_off[ks]);
+      const bf16x8 am = *reinterpret_cast<const bf16x8*>(a_mid + a_off[ks]);
+      const bf16x8 al = *reinterpret_cast<const bf16x8*>(a_lo + a_off[ks]);
       // B fragments one sub-tile ahead: the LDS round trip of fragment j + 1 runs under the three MFMAs of fragment j
       auto bfrag = [&](int j) __attribute__((always_inline)) {
         const int sub = j / T, tap = j - sub * T, ky = tap / KS, kx = tap - ky * KS;
-        return *reinterpret_cast<const half8*>(bsx + kx * bplane + b_off[ks] + (sub * 16 * BR + ky) * BROW);
+        return *reinterpret_cast<const bf16x8*>(bsx + kx * bplane + b_off[ks] + (sub * 16 * BR + ky) * BROW);
       };
-      half8 b = bfrag(0);
+      bf16x8 b = bfrag(0);
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
-        const half8 bn = bfrag(j + 1 < NJ ? j + 1 : j);
-        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, b, acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, b, acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, b, acc[j], 0, 0, 0);
+        const bf16x8 bn = bfrag(j + 1 < NJ ? j + 1 : j);
+        acc[j] = mfma3(ah, am, al, b, acc[j]);
         b = bn;
       }
     }
@@ -623,21 +542,11 @@ static bool make_geo(int N, int O, int C, int Hx, int Wx, int st, bool dgrad, Gr
   // (whose four parity classes are convolutions over that grid)
   q->H = (dgrad && st == 1) ? Hx : q->Hg;
   q->W = (dgrad && st == 1) ? Wx : q->Wg;
-  if (q->W > 64) return false;
-  int slot = 8;
-  while (slot < q->W) slot *= 2;
-  q->slot = slot;
-  q->RR = 64 / slot;
-  q->R = q->RR < q->H ? q->RR : q->H;
-  q->chunks = (q->H + q->R - 1) / q->R;
-  q->gshift = 0;
-  while ((8 << q->gshift) < slot) ++q->gshift;
-  // the kernels address g, x and gx through 32-bit buffer offsets and mark dead elements with offsets >= 0xFFFFFE00
-  const unsigned long long gb = (unsigned long long)N * O * q->Hg * q->Wg * 4ull;
-  const unsigned long long xb = (unsigned long long)N * C * Hx * Wx * 4ull;
-  if (gb > 0xFFFFFE00ull || xb > 0xFFFFFE00ull) return false;
-  q->g_bytes = (unsigned)gb;
-  q->x_bytes = (unsigned)xb;
+  Slots sl;
+  if (!make_slots(q->H, q->W, &sl)) return false;
+  q->slot = sl.slot; q->RR = sl.RR; q->R = sl.R; q->chunks = sl.chunks; q->gshift = sl.gshift;
+  // the kernels address g, x and gx through 32-bit buffer offsets and mark dead elements with tg::kOOB / kOOBNear
+  if (!fits_descriptor(N, O, q->Hg, q->Wg, &q->g_bytes) || !fits_descriptor(N, C, Hx, Wx, &q->x_bytes)) return false;
   q->cw64 = (C + 63) / 64;
   q->p_bytes = (unsigned)((unsigned long long)N * q->cw64 * Hx * Wx * 8ull);   // <= x_bytes / 4
   return true;
@@ -647,7 +556,7 @@ static bool ks_ok(int ks, int stride) { return ks == 3 || (ks == 1 && stride == 
 static constexpr int kWgradNC1 = 8;  // 1x1 weight gradient: 128 input channels per workgroup
 
 size_t grad_weight_pack_bytes(int O, int C, int ks) {
-  return (size_t)((O + 31) / 32) * ks * ks * ((C + 15) / 16) * 64 * sizeof(half8);
+  return sign_frag((O + 31) / 32, 0, 0, ks * ks, (C + 15) / 16, 0) * sizeof(bf16x8);
 }
 
 int launch_grad_pack_weight(const float* what, int O, int C, int ks, void* packed, float* alpha, hipStream_t s) {
@@ -655,38 +564,34 @@ int launch_grad_pack_weight(const float* what, int O, int C, int ks, void* packe
   const int CS = (C + 15) / 16, OB = (O + 31) / 32, T = ks * ks;
   hipLaunchKernelGGL(grad_alpha_kernel, dim3(O), dim3(64), 0, s, what, C * T, alpha);
   hipLaunchKernelGGL(grad_pack_weight_kernel, dim3(OB * T * CS), dim3(64), 0, s, what, O, C, CS, T,
-                     static_cast<half8*>(packed));
+                     static_cast<bf16x8*>(packed));
   return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
 }
 
 template <int KS, bool XP>
 static int launch_dgrad_t(const float* g, const float* alpha, const void* packed, const float* xin, float* gx,
                           const GradGeo& q, hipStream_t s) {
-  using namespace grad;
   const bool s2 = q.st == 2;
   const int halo = s2 ? 1 : 2 * (KS / 2);
-  const int PP = (q.R + halo) * (q.W + halo);
-  const int nsub = q.C > 64 ? 2 : 1;
-  const size_t patch = (size_t)3 * PP * APIX * sizeof(u16);
-  const size_t stage = (size_t)64 * nsub * SROW * sizeof(float);
-  const size_t lds = patch > stage ? patch : stage;
+  const int nsub = tile_nsub(q.C);
+  const size_t lds = tile_lds_bytes(3, (q.R + halo) * (q.W + halo), nsub);
   const dim3 grid((unsigned)(q.N * q.chunks), (unsigned)((q.C + 64 * nsub - 1) / (64 * nsub)), s2 ? 4u : 1u);
   if constexpr (KS == 3) {
     if (s2) {  // four parity classes (grid.z)
       if (nsub == 2)
-        hipLaunchKernelGGL((dgrad_kernel<2, 3, true, XP>), grid, dim3(NT), lds, s, g, alpha, static_cast<const half8*>(packed),
+        hipLaunchKernelGGL((dgrad_kernel<2, 3, true, XP>), grid, dim3(NT), lds, s, g, alpha, static_cast<const bf16x8*>(packed),
                            xin, gx, q);
       else
-        hipLaunchKernelGGL((dgrad_kernel<1, 3, true, XP>), grid, dim3(NT), lds, s, g, alpha, static_cast<const half8*>(packed),
+        hipLaunchKernelGGL((dgrad_kernel<1, 3, true, XP>), grid, dim3(NT), lds, s, g, alpha, static_cast<const bf16x8*>(packed),
                            xin, gx, q);
       return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
     }
   }
   if (nsub == 2)
-    hipLaunchKernelGGL((dgrad_kernel<2, KS, false, XP>), grid, dim3(NT), lds, s, g, alpha, static_cast<const half8*>(packed), xin,
+    hipLaunchKernelGGL((dgrad_kernel<2, KS, false, XP>), grid, dim3(NT), lds, s, g, alpha, static_cast<const bf16x8*>(packed), xin,
                        gx, q);
   else
-    hipLaunchKernelGGL((dgrad_kernel<1, KS, false, XP>), grid, dim3(NT), lds, s, g, alpha, static_cast<const half8*>(packed), xin,
+    hipLaunchKernelGGL((dgrad_kernel<1, KS, false, XP>), grid, dim3(NT), lds, s, g, alpha, static_cast<const bf16x8*>(packed), xin,
                        gx, q);
   return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
 }
@@ -719,7 +624,7 @@ static int launch_wgrad_si(const dim3& grid, size_t lds, hipStream_t s, const fl
   if (KS == 3 && hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_kernel<ST, KS, NC, XP, SI>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynamicLds) != hipSuccess)
     return BNN_HIP_ERR_LAUNCH;
-  hipLaunchKernelGGL((wgrad_kernel<ST, KS, NC, XP, SI>), grid, dim3(grad::NT), lds, s, g, x1, x2, part, q, per);
+  hipLaunchKernelGGL((wgrad_kernel<ST, KS, NC, XP, SI>), grid, dim3(NT), lds, s, g, x1, x2, part, q, per);
   return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
 }
 
@@ -727,7 +632,7 @@ template <int ST, int KS, int NC, bool XP>
 static int launch_wgrad_k(const dim3& grid, size_t lds, hipStream_t s, const float* g, const float* x1, const float* x2,
                           float* part, const GradGeo& q, int per) {
   const int items = 16 * NC * (ST * q.RR + 2 * (KS / 2)) * (q.slot / 8);   // sign(x) fill items of a chunk
-  switch ((items + grad::NT - 1) / grad::NT) {
+  switch ((items + NT - 1) / NT) {
     case 1: return launch_wgrad_si<ST, KS, NC, XP, 1>(grid, lds, s, g, x1, x2, part, q, per);
     case 2: return launch_wgrad_si<ST, KS, NC, XP, 2>(grid, lds, s, g, x1, x2, part, q, per);
     case 3: return launch_wgrad_si<ST, KS, NC, XP, 3>(grid, lds, s, g, x1, x2, part, q, per);

@@ -7,10 +7,9 @@
 // s(x) is the predicate of the bit planes (csrc/pack_act.hip): x > 0 -> +1, x < 0 -> -1, everything else (+-0, NaN, the
 // zero padding) -> 0.  The GEMM has one operand that is exactly {-1,0,+1} and one real operand: the arithmetic of
 // csrc/grad.hip with the roles swapped — there the image side (g) is real and the weight side ternary, here the image
-// side is ternary and the weight side real.  The real operand is split into THREE bf16 terms hi + mid + lo (each the
-// truncation of what is left: 3 x 8 = 24 mantissa bits), the ternary operand is exact in bf16, every product is exact
-// in fp32 and each product of the GEMM is three v_mfma_f32_16x16x32_bf16 with fp32 accumulation: the rounding class of
-// an fp32 convolution.
+// side is ternary and the weight side real — as csrc/tgemm.h states it: the real operand in three truncated bf16 terms,
+// the ternary operand exact in bf16, three bf16 MFMAs (tg::mfma3) per product with fp32 accumulation: the rounding
+// class of an fp32 convolution.
 //
 // Row exponent.  bf16 has fp32's exponent RANGE but its subnormals end at 2^-133, and the remainder of a weight below
 // 2^-110 has bits under that: a plain split of W loses them.  So the packer scales every output channel o whose largest
@@ -29,30 +28,20 @@
 //           and 0 for o >= O or c >= C (pad channels);
 //     kexp[16 OS]                      int32, behind the fragments (byte offset CB * T * OS * 3 * 1024); 0 for o >= O.
 //
-// K-slots as in grad.hip: a row of the OUTPUT grid (Wo <= 64 pixels) gets a power-of-two slot of 8 .. 64 pixels, a
-// 64-slot chunk is 64 / slot consecutive output rows of one image.  Per workgroup one chunk x 64 NSUB output channels;
+// (tg::real_frag, real_frag_bytes, real_kexp compute these addresses.)
+//
+// K-slots (tg::Slots) over the OUTPUT grid (Wo <= 64 pixels).  Per workgroup one chunk x 64 NSUB output channels;
 // the K loop walks blocks of 32 input channels: the chunk's input patch (rows st*y0 - pad .., halo included) enters LDS
 // as ONE bf16 plane of s(x), [patch pixel][32 c] (80 bytes per pixel: conflict-free 16-byte reads), filled by buffer
 // loads whose out-of-range offsets ARE the zero padding; k*k taps = k*k k-steps of 32 whose A fragment is the patch
 // pixel (st * row + ky, st * column + kx).  Stride 2 reads the same patch at every second pixel.
-#include "bconv_core.h"  // buffer-descriptor helpers
+#include "tgemm.h"
 
 namespace bnn {
 
-namespace sconv {
-constexpr int NT = 256;   // 4 waves
-constexpr int APIX = 40;  // patch: halves per pixel (32 channels + 8 pad)
-constexpr int SROW = 68;  // output staging: floats per channel row of 64 pixels
-}  // namespace sconv
+using namespace tg;
 
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using half8 = __attribute__((ext_vector_type(8))) __bf16;  // eight bf16 values: one MFMA fragment (16 bytes)
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using u16 = unsigned short;
-constexpr unsigned short kBf16One = 0x3F80, kBf16MinusOne = 0xBF80;
-constexpr unsigned kOOB = 0xFFFFFFF0u;  // a lane offset no tensor of a launch reaches (make_geo)
 
 struct SGeo {
   int N, O, C;
@@ -63,29 +52,6 @@ struct SGeo {
   int gshift;        // log2(slot / 8)
   unsigned x_bytes, y_bytes;  // ranges of the buffer descriptors of x and y
 };
-
-// grad.hip: split8 — v = hi + mid + lo, each term the truncation to bf16 of what is left
-__device__ __forceinline__ void split3x8(const float (&v)[8], half8& hi, half8& mid, half8& lo) {
-  unsigned h[8], m[8], l[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    h[e] = __float_as_uint(v[e]) & 0xFFFF0000u;
-    const float r1 = v[e] - __uint_as_float(h[e]);
-    m[e] = __float_as_uint(r1) & 0xFFFF0000u;
-    const float r2 = r1 - __uint_as_float(m[e]);
-    l[e] = __float_as_uint(r2);
-  }
-  u32x4 ph, pm, pl;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {  // the upper halves of two dwords -> one dword
-    ph[e] = (h[2 * e] >> 16) | (h[2 * e + 1] & 0xFFFF0000u);
-    pm[e] = (m[2 * e] >> 16) | (m[2 * e + 1] & 0xFFFF0000u);
-    pl[e] = (l[2 * e] >> 16) | (l[2 * e + 1] & 0xFFFF0000u);
-  }
-  hi = __builtin_bit_cast(half8, ph);
-  mid = __builtin_bit_cast(half8, pm);
-  lo = __builtin_bit_cast(half8, pl);
-}
 
 }  // namespace
 
@@ -114,7 +80,7 @@ __global__ __launch_bounds__(64) void sconv_row_exp_kernel(const float* __restri
 }
 
 __global__ __launch_bounds__(64) void sconv_pack_weight_kernel(const float* __restrict__ w, int O, int C, int OS, int T,
-                                                               const int* __restrict__ kexp, half8* __restrict__ Wp) {
+                                                               const int* __restrict__ kexp, bf16x8* __restrict__ Wp) {
   const int lane = threadIdx.x, li = lane & 15, lg = lane >> 4;
   const int os = blockIdx.x % OS, tap = (blockIdx.x / OS) % T, cb = blockIdx.x / (OS * T);
   const int o = 16 * os + li;
@@ -125,9 +91,9 @@ __global__ __launch_bounds__(64) void sconv_pack_weight_kernel(const float* __re
     const int c = 32 * cb + 8 * lg + e;
     v[e] = (o < O && c < C) ? ldexpf(w[((size_t)o * C + c) * T + tap], k) : 0.0f;
   }
-  half8 hi, mid, lo;
-  split3x8(v, hi, mid, lo);
-  half8* dst = Wp + (size_t)blockIdx.x * 3 * 64 + lane;
+  bf16x8 hi, mid, lo;
+  split3(v, hi, mid, lo);
+  bf16x8* dst = Wp + real_frag(cb, tap, os, T, OS, lane);
   dst[0] = hi;
   dst[64] = mid;
   dst[128] = lo;
@@ -138,12 +104,10 @@ __global__ __launch_bounds__(64) void sconv_pack_weight_kernel(const float* __re
 // K = (c, tap).  2 x 2 register blocking as in dgrad_kernel: a wave owns two of the four 16-pixel sub-tiles and half of
 // the workgroup's 4 NSUB channel groups.  FK: 64-pixel sweeps over the patch (stride 1: <= 198 pixels, stride 2: <= 330).
 template <int NSUB, int KS, int ST>
-__global__ __launch_bounds__(sconv::NT) void sconv_kernel(const float* __restrict__ x, const half8* __restrict__ Wp,
-                                                          const int* __restrict__ kexp,
-                                                          const float* __restrict__ bias,
-                                                          const float* __restrict__ scale, float* __restrict__ y,
-                                                          const SGeo q) {
-  using namespace sconv;
+__global__ __launch_bounds__(NT) void sconv_kernel(const float* __restrict__ x, const bf16x8* __restrict__ Wp,
+                                                   const int* __restrict__ kexp, const float* __restrict__ bias,
+                                                   const float* __restrict__ scale, float* __restrict__ y,
+                                                   const SGeo q) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   constexpr int PD = KS / 2, T = KS * KS;
   constexpr int FK = ST == 2 ? 6 : 4;
@@ -160,16 +124,10 @@ __global__ __launch_bounds__(sconv::NT) void sconv_kernel(const float* __restric
   const int ph = wave & 1, chh = wave >> 1;          // pixel half, channel half
   const int os0 = blockIdx.y * 4 * NSUB + chh * NB;  // first 16-channel group of this wave
 
-  // A-fragment base addresses: output pixel m = 16 s + li -> (row ry, column ox) of the chunk -> patch pixel
-  // (ST ry + ky, ST ox + kx)
+  // A-fragment base addresses: output pixel (ry, ox) of the chunk reads patch pixel (ST ry + ky, ST ox + kx) at tap (ky, kx)
   int abase[2];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int m = 16 * (2 * ph + i) + li;
-    int ry = m / q.slot, ox = m - ry * q.slot;
-    if (ox >= q.Wg || ry >= q.R) { ry = 0; ox = 0; }  // dead slot: any valid address, the result is never stored
-    abase[i] = (ST * ry * PW + ST * ox) * APIX + 8 * lg;
-  }
+  for (int i = 0; i < 2; ++i) abase[i] = patch_base(16 * (2 * ph + i) + li, q.slot, q.Wg, q.R, PW, ST, 0, lg);
 
   f32x4 acc[2][NB];
 #pragma unroll
@@ -183,29 +141,21 @@ __global__ __launch_bounds__(sconv::NT) void sconv_kernel(const float* __restric
   const BufRsrc r_x = make_rsrc_sized(x, q.x_bytes);
   unsigned fvoff[FK];
   int flds[FK];
-#pragma unroll
-  for (int k = 0; k < FK; ++k) {
-    const int pix = lane + 64 * k;
-    const int pr = pix / PW, pc = pix - pr * PW;
-    const int yy = ST * y0 - PD + pr, xx = pc - PD;
-    const bool in = pix < PP && yy >= 0 && xx >= 0 && yy < q.Hx && xx < q.Wx;
-    fvoff[k] = in ? (unsigned)(yy * q.Wx + xx) * 4u : kOOB;
-    flds[k] = pix < PP ? pix * APIX + 8 * wave : -1;
-  }
+  patch_fill_roles(lane, wave, PW, PP, ST * y0 - PD, -PD, q.Hx, q.Wx, fvoff, flds);
   const unsigned xplane4 = (unsigned)HWx * 4u;
 
   for (int cb = 0; cb < CB; ++cb) {
     __syncthreads();  // the previous block's patch is consumed
-    auto load_w = [&](half8 (&dst)[NB][3], int tap) {
+    auto load_w = [&](bf16x8 (&dst)[NB][3], int tap) {
 #pragma unroll
       for (int ns = 0; ns < NB; ++ns) {
         const int os = os0 + ns;
-        const half8* src = Wp + ((size_t)(cb * T + tap) * OS + (os < OS ? os : 0)) * 3 * 64 + lane;
+        const bf16x8* src = Wp + real_frag(cb, tap, os < OS ? os : 0, T, OS, lane);
 #pragma unroll
-        for (int t = 0; t < 3; ++t) dst[ns][t] = os < OS ? src[64 * t] : __builtin_bit_cast(half8, u32x4{0u, 0u, 0u, 0u});
+        for (int t = 0; t < 3; ++t) dst[ns][t] = os < OS ? src[64 * t] : zero_frag();
       }
     };
-    half8 b[NB][3];
+    bf16x8 b[NB][3];
     load_w(b, 0);
     const int c0 = 32 * cb + 8 * wave;
 #pragma unroll
@@ -216,14 +166,10 @@ __global__ __launch_bounds__(sconv::NT) void sconv_kernel(const float* __restric
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         // channels past C: an out-of-range offset reads 0 (a select, not a branch)
-        const float v = buf_ld(r_x, c0 + e < q.C ? fvoff[k] : kOOB, c0 + e < q.C ? soff : 0u);
+        sv[e] = ternary_code(buf_ld(r_x, c0 + e < q.C ? fvoff[k] : kOOB, c0 + e < q.C ? soff : 0u));
         soff += xplane4;
-        sv[e] = v > 0.0f ? kBf16One : v < 0.0f ? kBf16MinusOne : (unsigned short)0;
       }
-      u32x4 pk;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) pk[e] = (unsigned)sv[2 * e] | ((unsigned)sv[2 * e + 1] << 16);
-      if (flds[k] >= 0) *reinterpret_cast<u32x4*>(pa + flds[k]) = pk;
+      if (flds[k] >= 0) *reinterpret_cast<bf16x8*>(pa + flds[k]) = pack_codes(sv);
     }
     __syncthreads();
 #pragma unroll 1
@@ -231,7 +177,7 @@ __global__ __launch_bounds__(sconv::NT) void sconv_kernel(const float* __restric
       const int ky = tap / KS, kx = tap - ky * KS;
       const int toff = (ky * PW + kx) * APIX;
       // the next tap's weight fragments are requested before this tap's MFMAs (tap 0's before the fill)
-      half8 bn[NB][3];
+      bf16x8 bn[NB][3];
 #pragma unroll
       for (int ns = 0; ns < NB; ++ns)
 #pragma unroll
@@ -239,13 +185,9 @@ __global__ __launch_bounds__(sconv::NT) void sconv_kernel(const float* __restric
       if (tap + 1 < T) load_w(bn, tap + 1);
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        const half8 a = *reinterpret_cast<const half8*>(pa + abase[i] + toff);
+        const bf16x8 a = *reinterpret_cast<const bf16x8*>(pa + abase[i] + toff);
 #pragma unroll
-        for (int ns = 0; ns < NB; ++ns) {  // smallest terms first
-          acc[i][ns] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b[ns][2], acc[i][ns], 0, 0, 0);
-          acc[i][ns] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b[ns][1], acc[i][ns], 0, 0, 0);
-          acc[i][ns] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b[ns][0], acc[i][ns], 0, 0, 0);
-        }
+        for (int ns = 0; ns < NB; ++ns) acc[i][ns] = mfma3(a, b[ns], acc[i][ns]);
       }
 #pragma unroll
       for (int ns = 0; ns < NB; ++ns)
@@ -254,20 +196,13 @@ __global__ __launch_bounds__(sconv::NT) void sconv_kernel(const float* __restric
     }
   }
   __syncthreads();  // the patch is dead: its LDS becomes the [channel][pixel] staging tile
-  // D layout: column = li (output channel within the 16-group), row = 4 lg + r (pixel within the sub-tile)
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int ns = 0; ns < NB; ++ns)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        stage[((chh * NB + ns) * 16 + li) * SROW + 16 * (2 * ph + i) + 4 * lg + r] = acc[i][ns][r];
+  stage_acc(stage, acc, ph, chh, li, lg);
   __syncthreads();
   // a thread keeps ONE pixel of the chunk (its lane) and walks the channels wave, wave + 4, ...: coalesced NCHW stores
   const int o_blk = blockIdx.y * 64 * NSUB;
   constexpr int IT = 16 * NSUB;
-  const int ery = lane >> (q.gshift + 3), ex = lane & (q.slot - 1);
-  const bool elive = ex < q.Wg && ery < q.R && y0 + ery < q.Hg;
+  int ery, ex;
+  const bool elive = chunk_pixel(lane, q.slot, q.gshift, q.Wg, q.R, y0, q.Hg, ery, ex);
   const unsigned elane = elive ? (unsigned)((y0 + ery) * q.Wg + ex) * 4u : kOOB;
   [[maybe_unused]] const BufRsrc r_y = make_rsrc_sized(y, q.y_bytes);
   const unsigned yplane4 = (unsigned)HWg * 4u;
@@ -292,54 +227,37 @@ static bool make_sgeo(int N, int O, int C, int Hx, int Wx, int ks, int st, SGeo*
   q->N = N; q->O = O; q->C = C; q->Hx = Hx; q->Wx = Wx;
   q->Hg = (Hx - 1) / st + 1;
   q->Wg = (Wx - 1) / st + 1;
-  int slot = 8;
-  while (slot < q->Wg) slot *= 2;
-  q->slot = slot;
-  const int RR = 64 / slot;
-  q->R = RR < q->Hg ? RR : q->Hg;
-  q->chunks = (q->Hg + q->R - 1) / q->R;
-  q->gshift = 0;
-  while ((8 << q->gshift) < slot) ++q->gshift;
-  // x and y are addressed through 32-bit buffer offsets; dead elements are offsets >= 0xFFFFFFF0
-  const unsigned long long xb = (unsigned long long)N * C * Hx * Wx * 4ull;
-  const unsigned long long yb = (unsigned long long)N * O * q->Hg * q->Wg * 4ull;
-  if (xb > 0xFFFFFE00ull || yb > 0xFFFFFE00ull) return false;
+  Slots sl;
+  if (!make_slots(q->Hg, q->Wg, &sl)) return false;
+  q->slot = sl.slot; q->R = sl.R; q->chunks = sl.chunks; q->gshift = sl.gshift;
+  // x and y are addressed through 32-bit buffer offsets; dead elements are the offset tg::kOOB
+  if (!fits_descriptor(N, C, Hx, Wx, &q->x_bytes) || !fits_descriptor(N, O, q->Hg, q->Wg, &q->y_bytes)) return false;
   if ((unsigned long long)N * q->chunks > 0x7FFFFFFFull) return false;
-  q->x_bytes = (unsigned)xb;
-  q->y_bytes = (unsigned)yb;
   const int PP = (st * (q->R - 1) + ks) * (Wx + 2 * (ks / 2));
   return PP <= 64 * (st == 2 ? 6 : 4);  // the sweeps of the fill cover the patch
 }
 
-static size_t sconv_fragment_bytes(int O, int C, int ks) {
-  return (size_t)((C + 31) / 32) * ks * ks * ((O + 15) / 16) * 3 * 64 * sizeof(half8);
-}
-
 size_t sconv_weight_pack_bytes(int O, int C, int ks) {
-  return sconv_fragment_bytes(O, C, ks) + (size_t)((O + 15) / 16) * 16 * sizeof(int);
+  return real_frag_bytes(O, C, ks * ks) + (size_t)((O + 15) / 16) * 16 * sizeof(int);
 }
 
 int launch_sconv_pack_weight(const float* w, int O, int C, int ks, void* packed, hipStream_t s) {
   if (ks != 1 && ks != 3) return BNN_HIP_ERR_UNSUPPORTED;
   const int CB = (C + 31) / 32, OS = (O + 15) / 16, T = ks * ks;
-  int* kexp = reinterpret_cast<int*>(static_cast<unsigned char*>(packed) + sconv_fragment_bytes(O, C, ks));
+  int* kexp = reinterpret_cast<int*>(static_cast<unsigned char*>(packed) + real_frag_bytes(O, C, T));
   hipLaunchKernelGGL(sconv_row_exp_kernel, dim3(16 * OS), dim3(64), 0, s, w, O, C * T, kexp);
   hipLaunchKernelGGL(sconv_pack_weight_kernel, dim3(CB * T * OS), dim3(64), 0, s, w, O, C, OS, T, kexp,
-                     static_cast<half8*>(packed));
+                     static_cast<bf16x8*>(packed));
   return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
 }
 
 template <int KS, int ST>
 static int launch_sconv_t(const float* x, const void* packed, const float* bias, const float* scale, float* y,
                           const SGeo& q, hipStream_t s) {
-  using namespace sconv;
-  const int nsub = q.O > 64 ? 2 : 1;
-  const int PP = (ST * (q.R - 1) + KS) * (q.Wx + 2 * (KS / 2));
-  const size_t patch = (size_t)PP * APIX * sizeof(u16);
-  const size_t stage = (size_t)64 * nsub * SROW * sizeof(float);
-  const size_t lds = patch > stage ? patch : stage;
-  const half8* Wp = static_cast<const half8*>(packed);
-  const int* kexp = reinterpret_cast<const int*>(static_cast<const unsigned char*>(packed) + sconv_fragment_bytes(q.O, q.C, KS));
+  const int nsub = tile_nsub(q.O);
+  const size_t lds = tile_lds_bytes(1, (ST * (q.R - 1) + KS) * (q.Wx + 2 * (KS / 2)), nsub);
+  const bf16x8* Wp = static_cast<const bf16x8*>(packed);
+  const int* kexp = real_kexp(packed, q.O, q.C, KS * KS);
   const dim3 grid((unsigned)(q.N * q.chunks), (unsigned)((q.O + 64 * nsub - 1) / (64 * nsub)));
   if (nsub == 2)
     hipLaunchKernelGGL((sconv_kernel<2, KS, ST>), grid, dim3(NT), lds, s, x, Wp, kexp, bias, scale, y, q);

@@ -4,11 +4,11 @@
 //
 //     out[m,o] = (sum_f s(x[m,f]) * W[o,f] + bias[o]) * scale[o]
 //
-// The arithmetic is that of csrc/sconv.hip — s(x) = +1 / -1 / 0 for x > 0 / x < 0 / anything else is exact in bf16, the
-// weight is the ksize = 1 pack of sconv.hip's packer (three bf16 terms hi + mid + lo of W * 2^kexp[o], one row exponent
-// per output channel), each product is three v_mfma_f32_16x16x32_bf16 with fp32 accumulation, the epilogue multiplies by
-// 2^-kexp[o], adds the bias, multiplies by the scale — on the tiling of a GEMM instead of a convolution's pixel slots:
-// the 1x1-image route of sconv.hip spends a 64-pixel slot on every row of x.
+// The arithmetic is that of csrc/sconv.hip (csrc/tgemm.h) — s(x) = +1 / -1 / 0 for x > 0 / x < 0 / anything else is exact
+// in bf16, the weight is the ksize = 1 pack of sconv.hip's packer (three bf16 terms hi + mid + lo of W * 2^kexp[o], one
+// row exponent per output channel), each product is three bf16 MFMAs (tg::mfma3) with fp32 accumulation, the epilogue
+// multiplies by 2^-kexp[o], adds the bias, multiplies by the scale — on the tiling of a GEMM instead of a convolution's
+// pixel slots: the 1x1-image route of sconv.hip spends a 64-pixel slot on every row of x.
 //
 // Per workgroup (256 threads) 64 rows x 64 NSUB output channels; the K loop walks blocks of 64 features: wave w reads
 // the rows 16 w .. 16 w + 15 of the tile, lane l feature l of the block — one instruction is 256 contiguous bytes of one
@@ -26,39 +26,27 @@
 //
 // ste_mask_kernel: gx[m,f] = T bit (m,f) ? gx[m,f] : +0.0f in place — the hard-tanh straight-through mask on an input
 // gradient a library GEMM produced.
-#include "bconv_core.h"  // buffer-descriptor helpers
+#include "tgemm.h"
 
 namespace bnn {
 
 namespace slinear {
-constexpr int NT = 256;   // 4 waves
 constexpr int BM = 64;    // rows per workgroup
 constexpr int BK = 64;    // features per K block: one word of the planes
 constexpr int APIT = 72;  // LDS plane: halves per row (64 features + 8 pad)
 }  // namespace slinear
 
-namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using half8 = __attribute__((ext_vector_type(8))) __bf16;  // eight bf16 values: one MFMA fragment (16 bytes)
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using u16 = unsigned short;
-constexpr unsigned kBf16One = 0x3F80u, kBf16MinusOne = 0xBF80u;
-constexpr unsigned kOOB = 0xFFFFFFF0u;  // a lane offset no tensor of a launch reaches (M * F, M * O < 2^30 elements)
-
-}  // namespace
+using namespace tg;  // (kOOB: M * F, M * O < 2^30 elements keep x and out far below the descriptor limit)
 
 // GEMM: M = rows of x (64 per workgroup), N = output channels (64 NSUB per workgroup), K = features.  blockIdx.x =
 // row tile * OB + output-channel block (the blocks that share a row tile of x are neighbours).
 template <int NSUB>
-__global__ __launch_bounds__(slinear::NT) void slinear_kernel(const float* __restrict__ x, const half8* __restrict__ Wp,
-                                                              const int* __restrict__ kexp,
-                                                              const float* __restrict__ bias,
-                                                              const float* __restrict__ scale, float* __restrict__ out,
-                                                              unsigned long long* __restrict__ P,
-                                                              unsigned long long* __restrict__ Mn,
-                                                              unsigned long long* __restrict__ T, int M, int F, int O,
-                                                              int OB) {
+__global__ __launch_bounds__(NT) void slinear_kernel(const float* __restrict__ x, const bf16x8* __restrict__ Wp,
+                                                     const int* __restrict__ kexp, const float* __restrict__ bias,
+                                                     const float* __restrict__ scale, float* __restrict__ out,
+                                                     unsigned long long* __restrict__ P,
+                                                     unsigned long long* __restrict__ Mn,
+                                                     unsigned long long* __restrict__ T, int M, int F, int O, int OB) {
   using namespace slinear;
   __shared__ __attribute__((aligned(16))) u16 pa[BM * APIT];
 
@@ -91,19 +79,19 @@ __global__ __launch_bounds__(slinear::NT) void slinear_kernel(const float* __res
   };
   load_x(0);
   // the B fragments of both k-steps of K block kb; a k-step past CB or a channel group past OS is zeros
-  auto load_w = [&](half8 (&dst)[2][NB][3], int kb) {
+  auto load_w = [&](bf16x8 (&dst)[2][NB][3], int kb) {
 #pragma unroll
     for (int st = 0; st < 2; ++st)
 #pragma unroll
       for (int ns = 0; ns < NB; ++ns) {
         const int os = os0 + ns, cb = 2 * kb + st;
         const bool live = os < OS && cb < CB;
-        const half8* src = Wp + ((size_t)(live ? cb : 0) * OS + (live ? os : 0)) * 3 * 64 + lane;
+        const bf16x8* src = Wp + real_frag(live ? cb : 0, 0, live ? os : 0, 1, OS, lane);
 #pragma unroll
-        for (int t = 0; t < 3; ++t) dst[st][ns][t] = live ? src[64 * t] : __builtin_bit_cast(half8, u32x4{0u, 0u, 0u, 0u});
+        for (int t = 0; t < 3; ++t) dst[st][ns][t] = live ? src[64 * t] : zero_frag();
       }
   };
-  half8 b[2][NB][3];
+  bf16x8 b[2][NB][3];
   load_w(b, 0);
 
   for (int kb = 0; kb < KB; ++kb) {
@@ -113,7 +101,7 @@ __global__ __launch_bounds__(slinear::NT) void slinear_kernel(const float* __res
     // s(x) of this block -> LDS, and the words of the three planes: bit `lane` of a row's word is this lane's feature
     u16* dst = pa + 16 * wave * APIT + lane;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) dst[r * APIT] = (u16)(xv[r] > 0.0f ? kBf16One : xv[r] < 0.0f ? kBf16MinusOne : 0u);
+    for (int r = 0; r < 16; ++r) dst[r * APIT] = ternary_code(xv[r]);
     if (planes) {  // workgroup-uniform
       const bool flive = BK * kb + lane < F;  // (an out-of-range load is 0: |0| < 1 would set T)
       unsigned long long wp = 0ull, wm = 0ull, wt = 0ull;
@@ -134,19 +122,15 @@ __global__ __launch_bounds__(slinear::NT) void slinear_kernel(const float* __res
     }
     __syncthreads();
     load_x(kb + 1);  // past the last block every offset is out of range: zeros nobody reads
-    half8 bn[2][NB][3];
+    bf16x8 bn[2][NB][3];
     load_w(bn, kb + 1);
 
-    auto step = [&](const half8 (&b)[NB][3], int koff) {
+    auto step = [&](const bf16x8 (&b)[NB][3], int koff) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const half8 a = *reinterpret_cast<const half8*>(pa + (16 * i + li) * APIT + koff + 8 * lg);
+        const bf16x8 a = *reinterpret_cast<const bf16x8*>(pa + (16 * i + li) * APIT + koff + 8 * lg);
 #pragma unroll
-        for (int ns = 0; ns < NB; ++ns) {  // smallest terms first
-          acc[i][ns] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b[ns][2], acc[i][ns], 0, 0, 0);
-          acc[i][ns] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b[ns][1], acc[i][ns], 0, 0, 0);
-          acc[i][ns] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b[ns][0], acc[i][ns], 0, 0, 0);
-        }
+        for (int ns = 0; ns < NB; ++ns) acc[i][ns] = mfma3(a, b[ns], acc[i][ns]);
       }
     };
     step(b[0], 0);
@@ -194,16 +178,15 @@ __global__ __launch_bounds__(256) void ste_mask_kernel(float* __restrict__ gx, c
 
 // ------------------------------------------------------------------------------------------------- host side
 // Output channels per workgroup: 128 above 64 channels (the choice of sconv.hip), else 64.
-int slinear_block_channels(int O) { return O > 64 ? 128 : 64; }
+int slinear_block_channels(int O) { return 64 * tile_nsub(O); }
 
 int launch_slinear(const float* x, const void* packed, const float* bias, const float* scale, float* out, uint64_t* P,
                    uint64_t* Mn, uint64_t* T, int M, int F, int O, hipStream_t s) {
   using namespace slinear;
   const int bc = slinear_block_channels(O);
   const int OB = (O + bc - 1) / bc, MT = (M + BM - 1) / BM;
-  const size_t CB = (size_t)((F + 31) / 32), OS = (size_t)((O + 15) / 16);
-  const half8* Wp = static_cast<const half8*>(packed);
-  const int* kexp = reinterpret_cast<const int*>(static_cast<const unsigned char*>(packed) + CB * OS * 3 * 64 * sizeof(half8));
+  const bf16x8* Wp = static_cast<const bf16x8*>(packed);
+  const int* kexp = real_kexp(packed, O, F, 1);
   auto* p = reinterpret_cast<unsigned long long*>(P);
   auto* mn = reinterpret_cast<unsigned long long*>(Mn);
   auto* t = reinterpret_cast<unsigned long long*>(T);

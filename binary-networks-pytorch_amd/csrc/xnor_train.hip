@@ -11,7 +11,7 @@
 //     backward:  dWc = dWhat * alpha * 1[|Wc| < 1] + sign(Wc) * (sum_{c,t} dWhat * sign(Wc)) / K        (compute_alpha)
 //                dWc = dWhat * 1[|Wc| < 1]                                                              (otherwise)
 //                dW  = dWc - mean_c(dWc)  when centred, else dWc
-#include "bnn_dev.h"
+#include "tgemm.h"  // the sign-fragment layout and the ternary codes of the input-gradient kernel
 
 namespace bnn {
 
@@ -113,8 +113,7 @@ __global__ __launch_bounds__(xt::NT) void xnor_weight_bwd_kernel(const float* __
 
 // What the input-gradient kernel needs of the weights, straight from W (round 5; was xnor_what_kernel -> grad_alpha_kernel
 // -> grad_pack_weight_kernel: three launches per layer and backward pass, 57 per ResNet-18 step): alpha[o] and
-// sign(Wc) in the MFMA B-fragment order of csrc/grad.hip,
-//     Bp[ob][tap][cs][lane][e] = sign(Wc[o = 32 ob + 8 (lane >> 4) + e][c = 16 cs + (lane & 15)][tap])     (bf16)
+// sign(Wc) in the MFMA B-fragment order of csrc/grad.hip (tg::sign_frag: Bp[ob][tap][cs][lane][e], bf16 codes).
 // One workgroup per output channel of the PADDED range (32 * ceil(O / 32)): channels past O and input channels past C
 // are written as zeros, so the buffer needs no clearing.  The same centring / alpha code as xnor_what_kernel: the same
 // bits as the three-launch form for finite weights (alpha there: max |What| = alpha, or 0 when every sign is 0 — see
@@ -141,11 +140,10 @@ __global__ __launch_bounds__(xt::NT) void xnor_grad_pack_kernel(const float* __r
     unsigned short b = 0;
     if (live && c < C) {
       const float v = wo[(size_t)c * taps + t] - mean[t];
-      b = is_pos(v) ? (unsigned short)0x3F80 : is_neg(v) ? (unsigned short)0xBF80 : (unsigned short)0;
+      b = tg::ternary_code(is_pos(v), is_neg(v));
       nz |= b != 0;
     }
-    const size_t blk = ((size_t)ob * taps + t) * CS + (c >> 4);
-    Bp[(blk * 64 + (c & 15) + 16 * lg) * 8 + e] = b;
+    Bp[tg::sign_frag(ob, t, c >> 4, taps, CS, (c & 15) + 16 * lg) * 8 + e] = b;
   }
   if (nz) any_nz = 1;                             // (benign race: every writer stores 1)
   __syncthreads();

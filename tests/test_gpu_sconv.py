@@ -122,6 +122,70 @@ def test_dyadic_tables_bit_for_bit(shape, k, stride):
             assert_same_bits(got, R.sconv_ref(x, w, b, s, stride), (sh, b is not None, s is not None))
 
 
+# ---- the packed weight, byte for byte ----------------------------------------------------------------------------------
+def bf16_terms(v):
+    """(hi, mid, lo) of fp32 `v` as bf16 bit patterns: each the upper 16 bits of what is left, remainders in fp32."""
+    top = lambda a: a.view(np.uint32) & np.uint32(0xFFFF0000)
+    with np.errstate(invalid="ignore"):
+        hi = top(v)
+        r1 = (v - hi.view(F32)).astype(F32)
+        mid = top(r1)
+        lo = top((r1 - mid.view(F32)).astype(F32))
+    return [(t >> np.uint32(16)).astype(np.uint16) for t in (hi, mid, lo)]
+
+
+def one_nan(bits16):
+    """Every bf16 NaN as 0x7FC0: the layout says WHERE a remainder is NaN, not which payload the subtraction gives it."""
+    b = bits16.copy()
+    b[((b & 0x7F80) == 0x7F80) & ((b & 0x007F) != 0)] = 0x7FC0
+    return b
+
+
+@pytest.mark.parametrize("O,C,k", [(17, 33, 3), (70, 31, 1)])
+def test_packed_real_weight_equals_the_documented_layout_byte_for_byte(O, C, k):
+    """The header of csrc/sconv.hip: Wp[cb][tap][os][term][lane][e] = term(W[16 os + (lane & 15)][32 cb + 8 (lane >> 4) + e]
+    [tap] * 2^kexp[o]) in hi / mid / lo order, zeros for pad channels, kexp[16 OS] behind the fragments — evaluated
+    index by index, on rows below 1 (kexp > 0, one of them deep in the range where an unscaled split loses bits), at and
+    above 1, all zero, and with one infinity (hi = the infinity, both remainders NaN, kexp 0)."""
+    T, CB, OS = k * k, -(-C // 32), -(-O // 16)
+    rng = np.random.default_rng(O * 100 + k)
+    w = (rng.standard_normal((O, C, k, k)) * 2.0 ** rng.integers(-20, 3, (O, 1, 1, 1))).astype(F32)
+    w[0] = (rng.uniform(-1, 1, (C, k, k)) * 0.99).astype(F32)           # largest magnitude below 1
+    w[1] = (rng.standard_normal((C, k, k)) * 2.0 ** -120).astype(F32)   # far below 1
+    w[2] = rng.uniform(-3, 3, (C, k, k)).astype(F32)
+    w[2, 0, 0, 0] = 1.0                                                  # at 1 and above
+    w[3] = 0.0
+    w[4] = (rng.uniform(-1, 1, (C, k, k)) * 0.5).astype(F32)
+    w[4, C - 1, k - 1, k - 1] = -np.inf                                  # finite part below 1, one infinity
+    # kexp: 1 - exponent of the row's largest magnitude when that is in (0, 1), else 0
+    m = np.abs(w.reshape(O, -1)).max(1)
+    kexp = np.zeros(16 * OS, np.int32)
+    kexp[:O] = np.where((m > 0) & (m < 1), 1 - np.frexp(m)[1], 0)
+    assert kexp[0] >= 1 and kexp[1] > 100 and kexp[2] == 0 and kexp[3] == 0 and kexp[4] == 0
+    # the fragment element at every index
+    cb, tap, os_, lane, e = np.meshgrid(np.arange(CB), np.arange(T), np.arange(OS), np.arange(64), np.arange(8), indexing="ij")
+    o, c = 16 * os_ + (lane & 15), 32 * cb + 8 * (lane >> 4) + e
+    live = (o < O) & (c < C)
+    wt = w.reshape(O, C, T)
+    v = np.where(live, np.ldexp(wt[np.minimum(o, O - 1), np.minimum(c, C - 1), tap], kexp[o]), 0).astype(F32)
+    want = np.stack(bf16_terms(v), axis=3)                               # [cb][tap][os][term][lane][e]
+    assert want.shape == (CB, T, OS, 3, 64, 8) and not live.all()
+    scaled = v[live].astype(F64)
+    fin = np.isfinite(scaled)
+    terms = [t[live][fin].astype(np.uint32) << np.uint32(16) for t in bf16_terms(v)]
+    assert (sum(t.view(F32).astype(F64) for t in terms) == scaled[fin]).all()    # the split loses nothing here
+    got = hipops.sconv_pack_weight(dev(w)).data.cpu().numpy()
+    assert got.dtype == np.uint8 and got.size == want.size * 2 + 16 * OS * 4 == R.pack_bytes_ref(O, C, k)
+    frag = got[:want.size * 2].view(np.uint16).reshape(want.shape)
+    inf_at = (o == 4) & (c == C - 1) & (tap == T - 1)
+    assert inf_at.sum() == 1 and (frag[:, :, :, 0][inf_at] == 0xFF80).all()
+    for t in (1, 2):
+        r = frag[:, :, :, t][inf_at]
+        assert ((r & 0x7F80) == 0x7F80).all() and ((r & 0x007F) != 0).all()
+    assert np.array_equal(one_nan(frag), one_nan(want))
+    assert np.array_equal(got[want.size * 2:].view(np.int32), kexp)
+
+
 # ---- random data -----------------------------------------------------------------------------------------------------
 RANDOM = [(2, 64, 64, 16, 16, 3, 1), (2, 130, 70, 9, 17, 3, 1), (2, 64, 64, 16, 16, 3, 2), (2, 130, 70, 9, 17, 3, 2),
           (2, 64, 64, 16, 16, 1, 1), (2, 130, 70, 9, 17, 1, 1)]
