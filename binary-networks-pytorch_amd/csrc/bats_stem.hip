@@ -9,7 +9,7 @@
 // The arithmetic is fixed (tests restate it):
 //     acc = 0.0f;  for c, kh, kw (in that order):  acc = fmaf(x[n, c, y + kh - 1, x + kw - 1], w[o, c, kh, kw], acc)
 //     y   = fmaxf(fmaf(acc, s[o], t[o]), 0.0f)
-//     u_k = fmaf(y, a[k][o], b[k][o]);   P bit = is_pos(u_k), M bit = is_neg(u_k)        (pack_act_multi_kernel, relu = 0)
+//     u_k = fmaf(y, a[k][o], b[k][o]);   P bit = p_bit(u_k), M bit = m_bit(u_k)        (planes.h; pack_act_multi_kernel, relu = 0)
 // A padding tap enters as x = 0.0f: for a finite weight the fmaf returns acc unchanged (acc is never -0.0f: it starts at
 // +0.0f), so padding taps contribute nothing; for a non-finite weight it is the NaN the reference's zero padding gives.
 //
@@ -18,18 +18,9 @@
 // out of the cache: every pixel is read by 9 neighbours and by every channel group); the 27 weights, the BatchNorm and the
 // 2 K affine constants of a channel are the same for the whole wave, so they are scalar loads; every lane shifts its
 // 64-channel words together and stores VP contiguous uint64 per plane, coalesced across the lanes.
-#include "bnn_dev.h"
+#include "planes.h"
 
 namespace bnn {
-
-namespace {
-
-template <int VP>
-struct alignas(4 * VP) StemVec {
-  float v[VP];
-};
-
-}  // namespace
 
 template <int VP, int K>
 __global__ __launch_bounds__(256) void stem3x3_kernel(const float* __restrict__ x, const float* __restrict__ w,
@@ -83,10 +74,10 @@ __global__ __launch_bounds__(256) void stem3x3_kernel(const float* __restrict__ 
 #pragma unroll
     for (int v = 0; v < VP; ++v) yv[v] = fmaxf(fmaf(acc[v], s, sh), 0.0f);
     if (y) {
-      StemVec<VP> out;
+      PixVec<float, VP> out;
 #pragma unroll
       for (int v = 0; v < VP; ++v) out.v[v] = yv[v];
-      *reinterpret_cast<StemVec<VP>*>(y + ((size_t)n * O + c) * HW + r) = out;
+      *reinterpret_cast<PixVec<float, VP>*>(y + ((size_t)n * O + c) * HW + r) = out;
     }
   };
 
@@ -110,8 +101,8 @@ __global__ __launch_bounds__(256) void stem3x3_kernel(const float* __restrict__ 
 #pragma unroll
           for (int v = 0; v < VP; ++v) {
             const float u = fmaf(yv[v], ca, cb);
-            pw[k][h][v] = (pw[k][h][v] << 1) | (is_pos(u) ? 1u : 0u);
-            mw[k][h][v] = (mw[k][h][v] << 1) | (is_neg(u) ? 1u : 0u);
+            pw[k][h][v] = with_p<kShiftIn>(pw[k][h][v], u, b);
+            mw[k][h][v] = with_m<kShiftIn>(mw[k][h][v], u, b);
           }
         }
       }
@@ -125,47 +116,22 @@ __global__ __launch_bounds__(256) void stem3x3_kernel(const float* __restrict__ 
 #pragma unroll
           for (int v = 0; v < VP; ++v) {
             const float u = fmaf(yv[v], ca, cb);
-            pw[k][h][v] |= (is_pos(u) ? 1u : 0u) << b;
-            mw[k][h][v] |= (is_neg(u) ? 1u : 0u) << b;
+            pw[k][h][v] = with_p<kOrAt>(pw[k][h][v], u, b);
+            mw[k][h][v] = with_m<kOrAt>(mw[k][h][v], u, b);
           }
         }
       }
     }
   }
-  const size_t o = ((size_t)n * cw64 + g) * HW + r;
+  const size_t o = word_off(n, cw64, g, HW, r);
 #pragma unroll
   for (int k = 0; k < K; ++k) {
 #pragma unroll
     for (int v = 0; v < VP; ++v) {
-      P[k * set_stride + o + v] = (uint64_t)pw[k][0][v] | ((uint64_t)pw[k][1][v] << 32);
-      M[k * set_stride + o + v] = (uint64_t)mw[k][0][v] | ((uint64_t)mw[k][1][v] << 32);
+      P[k * set_stride + o + v] = join_halves(pw[k][0][v], pw[k][1][v]);
+      M[k * set_stride + o + v] = join_halves(mw[k][0][v], mw[k][1][v]);
     }
   }
-}
-
-template <int K>
-static void launch_stem_k(const float* x, const float* w, const float* s, const float* t, const float* a, const float* b,
-                          int O, int H, int W, long long npix, int cw64, uint64_t* P, uint64_t* M, float* y,
-                          hipStream_t stream) {
-  // pixels per thread: as many as HW and the alignment of y allow (y is stored as one VP-float vector per channel; every
-  // channel plane and image of y then starts on the same alignment), and 4 K VP plane words per thread: VP = 4 up to K = 2
-  const int HW = H * W;
-  const uintptr_t ya = reinterpret_cast<uintptr_t>(y);   // (0 when y is not written)
-  const size_t set_stride = (size_t)npix * cw64;
-  auto grid = [&](long long nthr) { return dim3((unsigned)((nthr + 255) / 256), (unsigned)cw64); };
-  if constexpr (K <= 2) {
-    if (HW % 4 == 0 && (ya & 15u) == 0) {
-      hipLaunchKernelGGL((stem3x3_kernel<4, K>), grid(npix / 4), dim3(256), 0, stream, x, w, s, t, a, b, O, H, W, npix,
-                         cw64, P, M, set_stride, y);
-      return;
-    }
-  }
-  if (HW % 2 == 0 && (ya & 7u) == 0)
-    hipLaunchKernelGGL((stem3x3_kernel<2, K>), grid(npix / 2), dim3(256), 0, stream, x, w, s, t, a, b, O, H, W, npix, cw64,
-                       P, M, set_stride, y);
-  else
-    hipLaunchKernelGGL((stem3x3_kernel<1, K>), grid(npix), dim3(256), 0, stream, x, w, s, t, a, b, O, H, W, npix, cw64, P,
-                       M, set_stride, y);
 }
 
 // capi.hip has checked the pointers, 1 <= K <= 4, the sizes and ceil(O / 64) <= 65535 (grid.y).
@@ -174,13 +140,17 @@ int launch_stem3x3_bn_relu_pack(const float* x, const float* w, const float* bn_
                                 hipStream_t stream) {
   const long long npix = (long long)N * H * W;
   const int cw64 = (O + 63) / 64;
-  switch (K) {
-    case 1: launch_stem_k<1>(x, w, bn_s, bn_t, pk_a, pk_b, O, H, W, npix, cw64, P, M, y, stream); break;
-    case 2: launch_stem_k<2>(x, w, bn_s, bn_t, pk_a, pk_b, O, H, W, npix, cw64, P, M, y, stream); break;
-    case 3: launch_stem_k<3>(x, w, bn_s, bn_t, pk_a, pk_b, O, H, W, npix, cw64, P, M, y, stream); break;
-    default: launch_stem_k<4>(x, w, bn_s, bn_t, pk_a, pk_b, O, H, W, npix, cw64, P, M, y, stream); break;
-  }
-  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+  with_k(K, [&](auto kc) {
+    constexpr int KV = decltype(kc)::value;
+    // pixels per thread: as many as HW and the alignment of y allow (y is stored as one VP-float vector per channel;
+    // a null y is not written), and 4 K VP plane words per thread: VP = 4 up to K = 2
+    with_width<(KV <= 2 ? 4 : 2)>(H * W, y, sizeof(float), [&](auto vp) {
+      constexpr int VP = decltype(vp)::value;
+      hipLaunchKernelGGL((stem3x3_kernel<VP, KV>), stream_grid(npix / VP, cw64), dim3(256), 0, stream, x, w, bn_s, bn_t, pk_a,
+                         pk_b, O, H, W, npix, cw64, P, M, plane_set_stride(npix, cw64), y);
+    });
+  });
+  return launch_status();
 }
 
 }  // namespace bnn

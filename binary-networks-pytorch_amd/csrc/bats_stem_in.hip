@@ -32,7 +32,7 @@
 // Both tiles are stored with even and odd columns apart, so that the stride-2 reads of a wave are consecutive words; the
 // row strides put the two rows of a half-wave on disjoint banks.  Weights, BatchNorm and affine constants are indexed by
 // wave-uniform values only, so they are scalar loads, as in bats_stem.hip.
-#include "bnn_dev.h"
+#include "planes.h"
 
 namespace bnn {
 
@@ -214,8 +214,8 @@ __global__ __launch_bounds__(256) void gconv3x3s2_pack_kernel(const float* __res
 #pragma unroll
           for (int k = 0; k < K; ++k) {
             const float u = fmaf(v, pk_a[(size_t)k * O + o], pk_b[(size_t)k * O + o]);
-            pw[k] |= (uint64_t)(is_pos(u) ? 1u : 0u) << (o & 63);
-            mw[k] |= (uint64_t)(is_neg(u) ? 1u : 0u) << (o & 63);
+            pw[k] |= (uint64_t)p_bit(u) << (o & 63);
+            mw[k] |= (uint64_t)m_bit(u) << (o & 63);
           }
         }
       }
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(256) void gconv3x3s2_pack_kernel(const float* __res
       for (int wv = 0; wv < 4; ++wv) v |= comb[((wv * K + k) * 2 + pm) * 64 + ln];
       const int pp = p0 + (ln >> 4), qq = q0 + (ln & (kTW - 1));
       if (pp < Ho && qq < Wo)
-        (pm ? M : P)[(size_t)k * set_stride + (((size_t)n * cw64 + wd) * Ho + pp) * Wo + qq] = v;
+        (pm ? M : P)[(size_t)k * set_stride + word_off(n, cw64, wd, Ho * Wo, pp * Wo + qq)] = v;
     }
   }
 }
@@ -267,7 +267,7 @@ int launch_stem_s2x2(const float* x, const float* w1, const float* s1, const flo
   const size_t lds = (size_t)(3 * kXCS + (C1 / G) * kMCS) * sizeof(float);
   hipLaunchKernelGGL(stem_s2x2_kernel, dim3(gx, (unsigned)G), dim3(256), lds, stream, x, w1, s1, t1, w2, s2, t2, C1 / G,
                      C / G, C, H, W, H1, W1, H2, W2, tiles_w, tiles, relu_out, y);
-  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+  return launch_status();
 }
 
 // capi.hip has checked the pointers (P / M / pk_a / pk_b when K >= 1, y when K == 0), 0 <= K <= 4, the sizes, G | C, G | O,
@@ -280,23 +280,16 @@ int launch_gconv3x3s2_bn_pack(const float* x, const float* w, const float* bn_s,
   const unsigned gx = tile_grid(N, Ho, Wo, &tiles_w, &tiles);
   if (gx == 0) return BNN_HIP_ERR_UNSUPPORTED;
   const int cw64 = (O + 63) / 64;
-  const size_t set_stride = (size_t)N * cw64 * Ho * Wo;
+  const size_t set_stride = plane_set_stride((long long)N * Ho * Wo, cw64);
   size_t lds = (size_t)(C / G) * kMCS * sizeof(float);
   const size_t comb = (size_t)4 * K * 2 * 64 * sizeof(uint64_t);
   if (lds < comb) lds = comb;
   const dim3 grid(gx, (unsigned)cw64);
-#define BNN_GCONV_LAUNCH(KV)                                                                                             \
-  hipLaunchKernelGGL((gconv3x3s2_pack_kernel<KV>), grid, dim3(256), lds, stream, x, w, bn_s, bn_t, pk_a, pk_b, C / G, O / G, \
-                     C, O, H, W, Ho, Wo, tiles_w, tiles, relu_in, cw64, P, M, set_stride, y)
-  switch (K) {
-    case 0: BNN_GCONV_LAUNCH(0); break;
-    case 1: BNN_GCONV_LAUNCH(1); break;
-    case 2: BNN_GCONV_LAUNCH(2); break;
-    case 3: BNN_GCONV_LAUNCH(3); break;
-    default: BNN_GCONV_LAUNCH(4); break;
-  }
-#undef BNN_GCONV_LAUNCH
-  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+  with_k<0>(K, [&](auto kc) {
+    hipLaunchKernelGGL((gconv3x3s2_pack_kernel<decltype(kc)::value>), grid, dim3(256), lds, stream, x, w, bn_s, bn_t, pk_a,
+                       pk_b, C / G, O / G, C, O, H, W, Ho, Wo, tiles_w, tiles, relu_in, cw64, P, M, set_stride, y);
+  });
+  return launch_status();
 }
 
 }  // namespace bnn

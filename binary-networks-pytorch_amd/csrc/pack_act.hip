@@ -11,53 +11,17 @@
 // channel plane, every store is VP contiguous uint64 words of the [n][group][y][x] output
 // plane, and small images with many channels still fill the chip (parallelism = pixels/VP x
 // channel groups).
-#include <hip/hip_fp16.h>
-
-#include "bnn_dev.h"
+#include "planes.h"
 
 namespace bnn {
-
-// VP consecutive pixels of one channel, loaded with ONE instruction (4..16 bytes per lane).
-// T = float, or __half / Bf16Bits for 16-bit models and autocast (sign() of a 16-bit value is the sign of its exact fp32
-// widening).
-template <typename T, int VP>
-struct alignas(sizeof(T) * VP) PixVec {
-  T v[VP];
-};
-// The activation tensor is read exactly once: non-temporal loads (no L2 / MALL allocation).  Measured on the config-2
-// tensor (411 MB, warm clocks): 79-82 us = 5.1 TB/s with plain loads, 68.8 us = 5.97 TB/s non-temporal.
-template <typename V>
-__device__ __forceinline__ V load_once(const V* p) {
-  if constexpr (sizeof(V) == 16) {
-    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-    return __builtin_bit_cast(V, __builtin_nontemporal_load(reinterpret_cast<const u4*>(p)));
-  } else if constexpr (sizeof(V) == 8) {
-    typedef uint32_t u2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(V, __builtin_nontemporal_load(reinterpret_cast<const u2*>(p)));
-  } else if constexpr (sizeof(V) == 4) {
-    return __builtin_bit_cast(V, __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p)));
-  } else {
-    return __builtin_bit_cast(V, __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(p)));
-  }
-}
-__device__ __forceinline__ float widen(float v) { return v; }
-__device__ __forceinline__ float widen(__half v) { return __half2float(v); }
-// bf16 is the upper half of an fp32 word: the widening is one shift, exact for every value (NaN, +-0, subnormals)
-struct Bf16Bits {
-  uint16_t u;
-};
-__device__ __forceinline__ float widen(Bf16Bits v) { return __uint_as_float((uint32_t)v.u << 16); }
 
 // AFF: v = fmaf(x, bn_a[c], bn_b[c]) first (eval-mode BatchNorm in front of a pre-activation block's
 // binary conv: res_block.py:148, hierarchical_block.py:39); relu != 0: planes of sign(max(v, 0)).
 template <int VP, bool AFF = false, typename T = float>
-__global__ __launch_bounds__(256) void pack_act_kernel(const T* __restrict__ x, int C, int HW,
-                                                       long long npix, int cw64,
-                                                       uint64_t* __restrict__ P,
-                                                       uint64_t* __restrict__ M,
+__global__ __launch_bounds__(256) void pack_act_kernel(const T* __restrict__ x, int C, int HW, long long npix, int cw64,
+                                                       uint64_t* __restrict__ P, uint64_t* __restrict__ M,
                                                        const float* __restrict__ bn_a = nullptr,
-                                                       const float* __restrict__ bn_b = nullptr,
-                                                       int relu = 0) {
+                                                       const float* __restrict__ bn_b = nullptr, int relu = 0) {
   using V = PixVec<T, VP>;
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
   const long long pix0 = t * VP;
@@ -73,21 +37,19 @@ __global__ __launch_bounds__(256) void pack_act_kernel(const T* __restrict__ x, 
 #pragma unroll
     for (int v = 0; v < VP; ++v) { pw[h][v] = 0u; mw[h][v] = 0u; }
     const int c0 = g * 64 + h * 32;
-    if (c0 + 32 <= C) {
-      // full 32-channel word: walk channels high -> low so that shifting left leaves
-      // channel c0+b in bit b.
+    if (c0 + 32 <= C) {  // (the two walks of a half-word and their inserts: planes.h)
 #pragma unroll 16
       for (int b = 31; b >= 0; --b) {
         const V xv = load_once(reinterpret_cast<const V*>(xb + (size_t)(c0 + b) * HW));
         float xs[VP];
 #pragma unroll
         for (int v = 0; v < VP; ++v) xs[v] = widen(xv.v[v]);
-        const float ca = AFF && bn_a ? bn_a[c0 + b] : 1.0f, cb = AFF && bn_a ? bn_b[c0 + b] : 0.0f;
+        const Affine f = channel_affine(AFF ? bn_a : nullptr, bn_b, c0 + b);
 #pragma unroll
         for (int v = 0; v < VP; ++v) {
-          const float u = (AFF && bn_a) ? fmaf(xs[v], ca, cb) : xs[v];
-          pw[h][v] = (pw[h][v] << 1) | (is_pos(u) ? 1u : 0u);
-          mw[h][v] = (mw[h][v] << 1) | ((!(AFF && relu) && is_neg(u)) ? 1u : 0u);
+          const float u = f(xs[v]);
+          pw[h][v] = with_p<kShiftIn>(pw[h][v], u, b);
+          mw[h][v] = with_m<kShiftIn>(mw[h][v], u, b, AFF && relu);
         }
       }
     } else {
@@ -96,80 +58,54 @@ __global__ __launch_bounds__(256) void pack_act_kernel(const T* __restrict__ x, 
         float xs[VP];
 #pragma unroll
         for (int v = 0; v < VP; ++v) xs[v] = widen(xv.v[v]);
-        const float ca = AFF && bn_a ? bn_a[c0 + b] : 1.0f, cb = AFF && bn_a ? bn_b[c0 + b] : 0.0f;
+        const Affine f = channel_affine(AFF ? bn_a : nullptr, bn_b, c0 + b);
 #pragma unroll
         for (int v = 0; v < VP; ++v) {
-          const float u = (AFF && bn_a) ? fmaf(xs[v], ca, cb) : xs[v];
-          pw[h][v] |= (is_pos(u) ? 1u : 0u) << b;
-          mw[h][v] |= ((!(AFF && relu) && is_neg(u)) ? 1u : 0u) << b;
+          const float u = f(xs[v]);
+          pw[h][v] = with_p<kOrAt>(pw[h][v], u, b);
+          mw[h][v] = with_m<kOrAt>(mw[h][v], u, b, AFF && relu);
         }
       }
     }
   }
-  // planes are [n][group][y][x] uint64: the VP words of this thread are contiguous
-  const size_t o = ((size_t)n * cw64 + g) * HW + r;
+  // the VP words of this thread are contiguous
+  const size_t o = word_off(n, cw64, g, HW, r);
 #pragma unroll
   for (int v = 0; v < VP; ++v) {
-    P[o + v] = (uint64_t)pw[0][v] | ((uint64_t)pw[1][v] << 32);
-    M[o + v] = (uint64_t)mw[0][v] | ((uint64_t)mw[1][v] << 32);
+    P[o + v] = join_halves(pw[0][v], pw[1][v]);
+    M[o + v] = join_halves(mw[0][v], mw[1][v]);
   }
 }
 
-template <typename T>
-static int launch_pack_act_t(const T* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M,
-                             hipStream_t stream) {
+template <bool AFF, typename T>
+static int launch_pack_act_t(const T* x, int N, int C, int H, int W, const float* bn_a, const float* bn_b, int relu,
+                             uint64_t* P, uint64_t* M, hipStream_t stream) {
   const int HW = H * W;
   const long long npix = (long long)N * HW;
   const int cw64 = (C + 63) / 64;
-  const bool a4 = (reinterpret_cast<uintptr_t>(x) & (4 * sizeof(T) - 1)) == 0;
-  const bool a2 = (reinterpret_cast<uintptr_t>(x) & (2 * sizeof(T) - 1)) == 0;
-  auto grid = [&](long long nthr) { return dim3((unsigned)((nthr + 255) / 256), (unsigned)cw64); };
-  const float* none = nullptr;
-  if (HW % 4 == 0 && a4)
-    hipLaunchKernelGGL((pack_act_kernel<4, false, T>), grid(npix / 4), dim3(256), 0, stream, x, C, HW, npix, cw64,
-                       P, M, none, none, 0);
-  else if (HW % 2 == 0 && a2)
-    hipLaunchKernelGGL((pack_act_kernel<2, false, T>), grid(npix / 2), dim3(256), 0, stream, x, C, HW, npix, cw64,
-                       P, M, none, none, 0);
-  else
-    hipLaunchKernelGGL((pack_act_kernel<1, false, T>), grid(npix), dim3(256), 0, stream, x, C, HW, npix, cw64, P, M,
-                       none, none, 0);
-  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+  with_width(HW, x, sizeof(T), [&](auto vp) {
+    constexpr int VP = decltype(vp)::value;
+    hipLaunchKernelGGL((pack_act_kernel<VP, AFF, T>), stream_grid(npix / VP, cw64), dim3(256), 0, stream, x, C, HW, npix,
+                       cw64, P, M, bn_a, bn_b, relu);
+  });
+  return launch_status();
 }
 
-int launch_pack_act(const float* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M,
-                    hipStream_t stream) {
-  return launch_pack_act_t<float>(x, N, C, H, W, P, M, stream);
+int launch_pack_act(const float* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M, hipStream_t stream) {
+  return launch_pack_act_t<false>(x, N, C, H, W, nullptr, nullptr, 0, P, M, stream);
 }
 
-int launch_pack_act_f16(const void* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M,
-                        hipStream_t stream) {
-  return launch_pack_act_t<__half>(static_cast<const __half*>(x), N, C, H, W, P, M, stream);
+int launch_pack_act_f16(const void* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M, hipStream_t stream) {
+  return launch_pack_act_t<false>(static_cast<const __half*>(x), N, C, H, W, nullptr, nullptr, 0, P, M, stream);
 }
 
-int launch_pack_act_bf16(const void* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M,
-                         hipStream_t stream) {
-  return launch_pack_act_t<Bf16Bits>(static_cast<const Bf16Bits*>(x), N, C, H, W, P, M, stream);
+int launch_pack_act_bf16(const void* x, int N, int C, int H, int W, uint64_t* P, uint64_t* M, hipStream_t stream) {
+  return launch_pack_act_t<false>(static_cast<const Bf16Bits*>(x), N, C, H, W, nullptr, nullptr, 0, P, M, stream);
 }
 
 int launch_bn_act_pack(const float* x, int N, int C, int H, int W, const float* bn_a, const float* bn_b,
                        int relu, uint64_t* P, uint64_t* M, hipStream_t stream) {
-  const int HW = H * W;
-  const long long npix = (long long)N * HW;
-  const int cw64 = (C + 63) / 64;
-  const bool a16 = (reinterpret_cast<uintptr_t>(x) & 15u) == 0;
-  const bool a8 = (reinterpret_cast<uintptr_t>(x) & 7u) == 0;
-  auto grid = [&](long long nthr) { return dim3((unsigned)((nthr + 255) / 256), (unsigned)cw64); };
-  if (HW % 4 == 0 && a16)
-    hipLaunchKernelGGL((pack_act_kernel<4, true>), grid(npix / 4), dim3(256), 0, stream, x, C, HW, npix, cw64,
-                       P, M, bn_a, bn_b, relu);
-  else if (HW % 2 == 0 && a8)
-    hipLaunchKernelGGL((pack_act_kernel<2, true>), grid(npix / 2), dim3(256), 0, stream, x, C, HW, npix, cw64,
-                       P, M, bn_a, bn_b, relu);
-  else
-    hipLaunchKernelGGL((pack_act_kernel<1, true>), grid(npix), dim3(256), 0, stream, x, C, HW, npix, cw64, P,
-                       M, bn_a, bn_b, relu);
-  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+  return launch_pack_act_t<true>(x, N, C, H, W, bn_a, bn_b, relu, P, M, stream);
 }
 
 // K BatchNorm + sign() plane sets from ONE read of x (a BATS cell state that feeds K SepConv / DilConv operations, each
@@ -204,7 +140,7 @@ __global__ __launch_bounds__(256) void pack_act_multi_kernel(const float* __rest
     const int c0 = g * 64 + h * 32;
     if (c0 + 32 <= C) {
 #pragma unroll 8
-      for (int b = 31; b >= 0; --b) {  // high -> low: shifting left leaves channel c0 + b in bit b
+      for (int b = 31; b >= 0; --b) {
         const V xv = load_once(reinterpret_cast<const V*>(xb + (size_t)(c0 + b) * HW));
 #pragma unroll
         for (int k = 0; k < K; ++k) {
@@ -212,8 +148,8 @@ __global__ __launch_bounds__(256) void pack_act_multi_kernel(const float* __rest
 #pragma unroll
           for (int v = 0; v < VP; ++v) {
             const float u = fmaf(xv.v[v], ca, cb);
-            pw[k][h][v] = (pw[k][h][v] << 1) | (is_pos(u) ? 1u : 0u);
-            mw[k][h][v] = (mw[k][h][v] << 1) | ((!relu && is_neg(u)) ? 1u : 0u);
+            pw[k][h][v] = with_p<kShiftIn>(pw[k][h][v], u, b);
+            mw[k][h][v] = with_m<kShiftIn>(mw[k][h][v], u, b, relu);
           }
         }
       }
@@ -226,41 +162,22 @@ __global__ __launch_bounds__(256) void pack_act_multi_kernel(const float* __rest
 #pragma unroll
           for (int v = 0; v < VP; ++v) {
             const float u = fmaf(xv.v[v], ca, cb);
-            pw[k][h][v] |= (is_pos(u) ? 1u : 0u) << b;
-            mw[k][h][v] |= ((!relu && is_neg(u)) ? 1u : 0u) << b;
+            pw[k][h][v] = with_p<kOrAt>(pw[k][h][v], u, b);
+            mw[k][h][v] = with_m<kOrAt>(mw[k][h][v], u, b, relu);
           }
         }
       }
     }
   }
-  const size_t o = ((size_t)n * cw64 + g) * HW + r;
+  const size_t o = word_off(n, cw64, g, HW, r);
 #pragma unroll
   for (int k = 0; k < K; ++k) {
 #pragma unroll
     for (int v = 0; v < VP; ++v) {
-      P[k * set_stride + o + v] = (uint64_t)pw[k][0][v] | ((uint64_t)pw[k][1][v] << 32);
-      M[k * set_stride + o + v] = (uint64_t)mw[k][0][v] | ((uint64_t)mw[k][1][v] << 32);
+      P[k * set_stride + o + v] = join_halves(pw[k][0][v], pw[k][1][v]);
+      M[k * set_stride + o + v] = join_halves(mw[k][0][v], mw[k][1][v]);
     }
   }
-}
-
-template <int K>
-static void launch_multi_k(const float* x0, int C, int HW, size_t img_stride, long long npix, int cw64, uint64_t* P,
-                           uint64_t* M, const float* scale, const float* shift, int relu, hipStream_t stream) {
-  // the vector width follows HW and the alignment of the VIEW's first element (every channel plane and image then
-  // starts on the same alignment: HW and c_total HW are multiples of the width)
-  const bool a16 = (reinterpret_cast<uintptr_t>(x0) & 15u) == 0, a8 = (reinterpret_cast<uintptr_t>(x0) & 7u) == 0;
-  const size_t set_stride = (size_t)npix * cw64;
-  auto grid = [&](long long nthr) { return dim3((unsigned)((nthr + 255) / 256), (unsigned)cw64); };
-  if (K <= 2 && HW % 4 == 0 && a16)
-    hipLaunchKernelGGL((pack_act_multi_kernel<4, K>), grid(npix / 4), dim3(256), 0, stream, x0, C, HW, img_stride, npix,
-                       cw64, P, M, set_stride, scale, shift, relu);
-  else if (HW % 2 == 0 && a8)
-    hipLaunchKernelGGL((pack_act_multi_kernel<2, K>), grid(npix / 2), dim3(256), 0, stream, x0, C, HW, img_stride, npix,
-                       cw64, P, M, set_stride, scale, shift, relu);
-  else
-    hipLaunchKernelGGL((pack_act_multi_kernel<1, K>), grid(npix), dim3(256), 0, stream, x0, C, HW, img_stride, npix, cw64,
-                       P, M, set_stride, scale, shift, relu);
 }
 
 // x: the tensor's base; the view is channels [c_off, c_off + C) of c_tot (capi.hip has checked it and 1 <= K <= 4).
@@ -271,13 +188,16 @@ int launch_bn_act_pack_multi(const float* x, int c_off, int c_tot, int N, int C,
   const int cw64 = (C + 63) / 64;
   const float* x0 = x + (size_t)c_off * HW;
   const size_t img_stride = (size_t)c_tot * HW;
-  switch (K) {
-    case 1: launch_multi_k<1>(x0, C, HW, img_stride, npix, cw64, P, M, scale, shift, relu, stream); break;
-    case 2: launch_multi_k<2>(x0, C, HW, img_stride, npix, cw64, P, M, scale, shift, relu, stream); break;
-    case 3: launch_multi_k<3>(x0, C, HW, img_stride, npix, cw64, P, M, scale, shift, relu, stream); break;
-    default: launch_multi_k<4>(x0, C, HW, img_stride, npix, cw64, P, M, scale, shift, relu, stream); break;
-  }
-  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+  with_k(K, [&](auto kc) {
+    constexpr int KV = decltype(kc)::value;
+    // the vector width follows HW and the alignment of the VIEW's first element; VP = 4 only up to K = 2 (above)
+    with_width<(KV <= 2 ? 4 : 2)>(HW, x0, sizeof(float), [&](auto vp) {
+      constexpr int VP = decltype(vp)::value;
+      hipLaunchKernelGGL((pack_act_multi_kernel<VP, KV>), stream_grid(npix / VP, cw64), dim3(256), 0, stream, x0, C, HW,
+                         img_stride, npix, cw64, P, M, plane_set_stride(npix, cw64), scale, shift, relu);
+    });
+  });
+  return launch_status();
 }
 
 // The binarisation inside FactorizedReduce (bnn/models/layers/bats_ops.py:204-206: conv_1(bn(x)) at stride 2 and
@@ -295,9 +215,7 @@ __global__ __launch_bounds__(256) void pack_act_s2_kernel(const float* __restric
   const int g = blockIdx.y;
   const int HWo = Ho * Wo;
   const size_t HW = (size_t)4 * HWo;
-  const int n = (int)(q / HWo);
-  const int r = (int)(q - (long long)n * HWo);
-  const int i = r / Wo, j = r - i * Wo;
+  const auto [n, r, i, j] = out_pixel(q, HWo, Wo);
   const float* xb = x + (size_t)n * img_stride + (size_t)(2 * i) * W + 2 * j;
   uint32_t pw[2][2] = {{0u, 0u}, {0u, 0u}}, mw[2][2] = {{0u, 0u}, {0u, 0u}};  // [phase][half]
 #pragma unroll
@@ -306,20 +224,20 @@ __global__ __launch_bounds__(256) void pack_act_s2_kernel(const float* __restric
     for (int b = 0; b < 32 && c0 + b < C; ++b) {
       const float* xc = xb + (size_t)(c0 + b) * HW;
       const float v[2] = {load_once(xc), load_once(xc + W + 1)};
-      const float ca = bn_a ? bn_a[c0 + b] : 1.0f, cb = bn_a ? bn_b[c0 + b] : 0.0f;
+      const Affine f = channel_affine(bn_a, bn_b, c0 + b);
 #pragma unroll
       for (int ph = 0; ph < 2; ++ph) {
-        const float u = bn_a ? fmaf(v[ph], ca, cb) : v[ph];
-        pw[ph][h] |= (is_pos(u) ? 1u : 0u) << b;
-        mw[ph][h] |= ((!relu && is_neg(u)) ? 1u : 0u) << b;
+        const float u = f(v[ph]);
+        pw[ph][h] = with_p(pw[ph][h], u, b);
+        mw[ph][h] = with_m(mw[ph][h], u, b, relu);
       }
     }
   }
-  const size_t o = ((size_t)n * cw64 + g) * HWo + r;
+  const size_t o = word_off(n, cw64, g, HWo, r);
 #pragma unroll
   for (int ph = 0; ph < 2; ++ph) {
-    P[ph * set_stride + o] = (uint64_t)pw[ph][0] | ((uint64_t)pw[ph][1] << 32);
-    M[ph * set_stride + o] = (uint64_t)mw[ph][0] | ((uint64_t)mw[ph][1] << 32);
+    P[ph * set_stride + o] = join_halves(pw[ph][0], pw[ph][1]);
+    M[ph * set_stride + o] = join_halves(mw[ph][0], mw[ph][1]);
   }
 }
 
@@ -329,10 +247,9 @@ int launch_bn_act_pack_s2(const float* x, int c_off, int c_tot, int N, int C, in
   const int Ho = H / 2, Wo = W / 2;
   const long long npix = (long long)N * Ho * Wo;
   const int cw64 = (C + 63) / 64;
-  const dim3 grid((unsigned)((npix + 255) / 256), (unsigned)cw64);
-  hipLaunchKernelGGL(pack_act_s2_kernel, grid, dim3(256), 0, stream, x + (size_t)c_off * H * W, C, W, Ho, Wo,
-                     (size_t)c_tot * H * W, npix, cw64, P, M, (size_t)npix * cw64, bn_a, bn_b, relu);
-  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+  hipLaunchKernelGGL(pack_act_s2_kernel, stream_grid(npix, cw64), dim3(256), 0, stream, x + (size_t)c_off * H * W, C, W,
+                     Ho, Wo, (size_t)c_tot * H * W, npix, cw64, P, M, plane_set_stride(npix, cw64), bn_a, bn_b, relu);
+  return launch_status();
 }
 
 // AvgPool2d(k, stride=k, ceil_mode=True, count_include_pad=False) + sign() in one pass: the
@@ -342,18 +259,14 @@ int launch_bn_act_pack_s2(const float* x, int c_off, int c_tot, int N, int C, in
 // reference's sign is 0).  Clipped windows at the ragged edge skip their out-of-image taps and
 // divide by the taps they kept.
 // One thread = one output pixel x one 32-channel word.
-__global__ __launch_bounds__(256) void avgpool_pack_kernel(const float* __restrict__ x, int C,
-                                                           int H, int W, int k, int Ho, int Wo,
-                                                           long long npix_out, int cw32,
-                                                           uint32_t* __restrict__ P,
-                                                           uint32_t* __restrict__ M) {
+__global__ __launch_bounds__(256) void avgpool_pack_kernel(const float* __restrict__ x, int C, int H, int W, int k, int Ho,
+                                                           int Wo, long long npix_out, int cw32,
+                                                           uint32_t* __restrict__ P, uint32_t* __restrict__ M) {
   const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
   if (q >= npix_out) return;
   const int word = blockIdx.y;
   const int hw = Ho * Wo;
-  const int n = (int)(q / hw);
-  const int r = (int)(q - (long long)n * hw);
-  const int oy = r / Wo, ox = r - oy * Wo;
+  const auto [n, r, oy, ox] = out_pixel(q, hw, Wo);
   uint32_t pw = 0u, mw = 0u;
   for (int b = 0; b < 32; ++b) {
     const int c = word * 32 + b;
@@ -372,10 +285,10 @@ __global__ __launch_bounds__(256) void avgpool_pack_kernel(const float* __restri
       }
     }
     const float t = s / (float)cnt;  // (IEEE division: hipcc's default for fp32)
-    pw |= (is_pos(t) ? 1u : 0u) << b;
-    mw |= (is_neg(t) ? 1u : 0u) << b;
+    pw = with_p(pw, t, b);
+    mw = with_m(mw, t, b);
   }
-  const size_t o = ((((size_t)n * (cw32 >> 1) + (word >> 1)) * hw + r) << 1) + (word & 1);
+  const size_t o = half_off(n, cw32, word, hw, r);
   P[o] = pw;
   M[o] = mw;
 }
@@ -420,23 +333,19 @@ int launch_orpool_packed(const uint64_t* P, int N, int C, int H, int W, int k, u
   const long long nwords = (long long)N * ((C + 63) / 64) * Ho * Wo;
   hipLaunchKernelGGL(orpool_packed_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, stream, P, H, W, k,
                      Ho, Wo, nwords, outP, outM);
-  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+  return launch_status();
 }
 
 // k == 2 on even images with W % 4 == 0 (every ResNet stage transition): one thread produces two
 // adjacent outputs from one aligned float4 per input row.  Same tap order as the scalar kernel.
-__global__ __launch_bounds__(256) void avgpool2_pack_kernel(const float* __restrict__ x, int C,
-                                                            int H, int W, int Ho, int Wo,
-                                                            long long npairs, int cw32,
-                                                            uint32_t* __restrict__ P,
-                                                            uint32_t* __restrict__ M) {
+__global__ __launch_bounds__(256) void avgpool2_pack_kernel(const float* __restrict__ x, int C, int H, int W, int Ho,
+                                                            int Wo, long long npairs, int cw32,
+                                                            uint32_t* __restrict__ P, uint32_t* __restrict__ M) {
   const long long q = (long long)blockIdx.x * 256 + threadIdx.x;  // (n, oy, ox/2)
   if (q >= npairs) return;
   const int word = blockIdx.y;
   const int wp = Wo >> 1;
-  const int n = (int)(q / ((long long)Ho * wp));
-  const int rr = (int)(q - (long long)n * Ho * wp);
-  const int oy = rr / wp, t = rr - oy * wp;
+  const auto [n, rr, oy, t] = out_pixel(q, (long long)Ho * wp, wp);  // t: the pair in its row
   const int hw = Ho * Wo;
   const int r = oy * Wo + 2 * t;
   uint32_t pw0 = 0u, mw0 = 0u, pw1 = 0u, mw1 = 0u;
@@ -446,32 +355,27 @@ __global__ __launch_bounds__(256) void avgpool2_pack_kernel(const float* __restr
     const float* row = x + (((size_t)n * C + c) * H + 2 * oy) * W + 4 * t;
     const float4 u = *reinterpret_cast<const float4*>(row);
     const float4 v = *reinterpret_cast<const float4*>(row + W);
-    const float s0 = (((u.x + u.y) + v.x) + v.y) * 0.25f;  // the average: x / 4 and x * 0.25f are the same float
-    const float s1 = (((u.z + u.w) + v.z) + v.w) * 0.25f;
-    pw0 |= (is_pos(s0) ? 1u : 0u) << b;
-    mw0 |= (is_neg(s0) ? 1u : 0u) << b;
-    pw1 |= (is_pos(s1) ? 1u : 0u) << b;
-    mw1 |= (is_neg(s1) ? 1u : 0u) << b;
+    const float s0 = avg2x2(u.x, u.y, v.x, v.y), s1 = avg2x2(u.z, u.w, v.z, v.w);
+    pw0 = with_p(pw0, s0, b);
+    mw0 = with_m(mw0, s0, b);
+    pw1 = with_p(pw1, s1, b);
+    mw1 = with_m(mw1, s1, b);
   }
-  const size_t o = ((((size_t)n * (cw32 >> 1) + (word >> 1)) * hw + r) << 1) + (word & 1);
+  const size_t o = half_off(n, cw32, word, hw, r);
   P[o] = pw0; M[o] = mw0;
   P[o + 2] = pw1; M[o + 2] = mw1;
 }
 
 // k == 2 on even images whose width is not a multiple of 4 (14x14 -> 7x7): one aligned float2 per
 // input row and output.  Same tap order as the scalar kernel.
-__global__ __launch_bounds__(256) void avgpool2_pack_f2_kernel(const float* __restrict__ x, int C,
-                                                               int H, int W, int Ho, int Wo,
-                                                               long long npix_out, int cw32,
-                                                               uint32_t* __restrict__ P,
-                                                               uint32_t* __restrict__ M) {
+__global__ __launch_bounds__(256) void avgpool2_pack_f2_kernel(const float* __restrict__ x, int C, int H, int W, int Ho,
+                                                               int Wo, long long npix_out, int cw32,
+                                                               uint32_t* __restrict__ P, uint32_t* __restrict__ M) {
   const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
   if (q >= npix_out) return;
   const int word = blockIdx.y;
   const int hw = Ho * Wo;
-  const int n = (int)(q / hw);
-  const int r = (int)(q - (long long)n * hw);
-  const int oy = r / Wo, ox = r - oy * Wo;
+  const auto [n, r, oy, ox] = out_pixel(q, hw, Wo);
   uint32_t pw = 0u, mw = 0u;
   const float* base = x + (((size_t)n * C + (size_t)word * 32) * H + 2 * oy) * W + 2 * ox;
   const size_t cstride = (size_t)H * W;
@@ -480,11 +384,11 @@ __global__ __launch_bounds__(256) void avgpool2_pack_f2_kernel(const float* __re
     if (word * 32 + b >= C) break;
     const float2 u = *reinterpret_cast<const float2*>(base + b * cstride);
     const float2 v = *reinterpret_cast<const float2*>(base + b * cstride + W);
-    const float s = (((u.x + u.y) + v.x) + v.y) * 0.25f;
-    pw |= (is_pos(s) ? 1u : 0u) << b;
-    mw |= (is_neg(s) ? 1u : 0u) << b;
+    const float s = avg2x2(u.x, u.y, v.x, v.y);
+    pw = with_p(pw, s, b);
+    mw = with_m(mw, s, b);
   }
-  const size_t o = ((((size_t)n * (cw32 >> 1) + (word >> 1)) * hw + r) << 1) + (word & 1);
+  const size_t o = half_off(n, cw32, word, hw, r);
   P[o] = pw;
   M[o] = mw;
 }
@@ -496,33 +400,55 @@ int launch_avgpool_pack(const float* x, int N, int C, int H, int W, int k, uint6
   const int cw32 = 2 * ((C + 63) / 64);
   if (k == 2 && H % 2 == 0 && W % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15u) == 0) {
     const long long npairs = npix / 2;
-    hipLaunchKernelGGL(avgpool2_pack_kernel, dim3((unsigned)((npairs + 255) / 256), (unsigned)cw32),
+    hipLaunchKernelGGL(avgpool2_pack_kernel, stream_grid(npairs, cw32),
                        dim3(256), 0, stream, x, C, H, W, Ho, Wo, npairs, cw32,
                        reinterpret_cast<uint32_t*>(P), reinterpret_cast<uint32_t*>(M));
-    return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+    return launch_status();
   }
   if (k == 2 && H % 2 == 0 && W % 2 == 0 && (reinterpret_cast<uintptr_t>(x) & 7u) == 0) {
-    hipLaunchKernelGGL(avgpool2_pack_f2_kernel, dim3((unsigned)((npix + 255) / 256), (unsigned)cw32),
+    hipLaunchKernelGGL(avgpool2_pack_f2_kernel, stream_grid(npix, cw32),
                        dim3(256), 0, stream, x, C, H, W, Ho, Wo, npix, cw32,
                        reinterpret_cast<uint32_t*>(P), reinterpret_cast<uint32_t*>(M));
-    return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+    return launch_status();
   }
-  hipLaunchKernelGGL(avgpool_pack_kernel, dim3((unsigned)((npix + 255) / 256), (unsigned)cw32),
+  hipLaunchKernelGGL(avgpool_pack_kernel, stream_grid(npix, cw32),
                      dim3(256), 0, stream, x, C, H, W, k, Ho, Wo, npix, cw32,
                      reinterpret_cast<uint32_t*>(P), reinterpret_cast<uint32_t*>(M));
-  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+  return launch_status();
 }
 
 // AvgPool2d(2, 2) in front of a pre-activation stage + the sign planes of up to TWO BatchNorm branches of its result in one
 // pass (a hierarchical-block stage behind a pool, bnn_amd/models/resnet.py: the block's bn1 -> act -> conv1 and its
 // shortcut's bn -> conv1x1 both binarise the pooled tensor):
-//     t  = (((x00 + x01) + x10) + x11) / 4        ATen's avg_pool2d: window summed row by row, then divided
+//     t  = avg2x2(x00, x01, x10, x11)             ATen's avg_pool2d (planes.h)
 //     u1 = fmaf(t, a1[c], b1[c]) -> P1 / M1 (relu1: M1 = 0);   u2 = fmaf(t, a2[c], b2[c]) -> P2 / M2
 // The fp32 tensor t is written only when `out` is given (nobody reads it when both consumers take planes).
 // A workgroup = 64 consecutive output pixels x one 32-channel word; wave w of it = channels 8w .. 8w+7 of the word (lane =
 // pixel: coalesced float2 loads, 16 in flight per lane); the four 8-bit pieces meet in LDS.  Even H and W.
 // (large tensors — the 56x56 -> 28x28 transition at batch 128 — stream at 4.9 TB/s in the one-thread-per-word form below;
 // this one is for the smaller transitions, where that form has too few threads: 19.4 -> 14.3 us and 18.4 -> 11.0 us)
+// One channel of both forms: tap = the window's first element; bit b of the four words; t goes to out[o] when `store`.
+struct Bn2Words {
+  uint32_t p1, m1, p2, m2;
+};
+__device__ __forceinline__ Bn2Words pool_bn2_channel(Bn2Words w, const float* tap, int W, int c, int b, const float* a1,
+                                                     const float* b1, int relu1, const float* a2, const float* b2,
+                                                     int relu2, bool store, float* out, size_t o) {
+  const float2 u = *reinterpret_cast<const float2*>(tap);
+  const float2 v = *reinterpret_cast<const float2*>(tap + W);
+  const float t = avg2x2(u.x, u.y, v.x, v.y);
+  if (store) out[o] = t;
+  const float u1 = fmaf(t, a1[c], b1[c]);
+  w.p1 = with_p(w.p1, u1, b);
+  w.m1 = with_m(w.m1, u1, b, relu1);
+  if (a2) {
+    const float u2 = fmaf(t, a2[c], b2[c]);
+    w.p2 = with_p(w.p2, u2, b);
+    w.m2 = with_m(w.m2, u2, b, relu2);
+  }
+  return w;
+}
+
 __global__ __launch_bounds__(256) void avgpool2_bn_pack2_kernel(
     const float* __restrict__ x, int C, int H, int W, int Ho, int Wo, long long npix_out, int cw32,
     const float* __restrict__ a1, const float* __restrict__ b1, int relu1, uint32_t* __restrict__ P1,
@@ -534,15 +460,13 @@ __global__ __launch_bounds__(256) void avgpool2_bn_pack2_kernel(
   const long long q = q0 < npix_out ? q0 : npix_out - 1;  // lanes past the end copy the last pixel (nothing stored)
   const int word = blockIdx.y;
   const int hw = Ho * Wo;
-  const int n = (int)(q / hw);
-  const int r = (int)(q - (long long)n * hw);
-  const int oy = r / Wo, ox = r - oy * Wo;
+  const auto [n, r, oy, ox] = out_pixel(q, hw, Wo);
   if (wv == 0) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) pieces[k][lane] = 0u;
   }
   __syncthreads();
-  uint32_t p1 = 0u, m1 = 0u, p2 = 0u, m2 = 0u;
+  Bn2Words w = {0u, 0u, 0u, 0u};
   const int c0 = word * 32 + wv * 8;
   const float* base = x + (((size_t)n * C + (size_t)c0) * H + 2 * oy) * W + 2 * ox;
   const size_t cstride = (size_t)H * W;
@@ -550,27 +474,17 @@ __global__ __launch_bounds__(256) void avgpool2_bn_pack2_kernel(
   for (int b = 0; b < 8; ++b) {
     const int c = c0 + b;
     if (c >= C) break;
-    const float2 u = *reinterpret_cast<const float2*>(base + b * cstride);
-    const float2 v = *reinterpret_cast<const float2*>(base + b * cstride + W);
-    const float t = (((u.x + u.y) + v.x) + v.y) * 0.25f;   // (x / 4 and x * 0.25 are the same float for every x)
-    if (out && q0 < npix_out) out[((size_t)n * C + c) * hw + r] = t;
-    const float u1 = fmaf(t, a1[c], b1[c]);
-    p1 |= (is_pos(u1) ? 1u : 0u) << b;
-    m1 |= ((!relu1 && is_neg(u1)) ? 1u : 0u) << b;
-    if (a2) {
-      const float u2 = fmaf(t, a2[c], b2[c]);
-      p2 |= (is_pos(u2) ? 1u : 0u) << b;
-      m2 |= ((!relu2 && is_neg(u2)) ? 1u : 0u) << b;
-    }
+    w = pool_bn2_channel(w, base + b * cstride, W, c, b, a1, b1, relu1, a2, b2, relu2, out && q0 < npix_out, out,
+                         ((size_t)n * C + c) * hw + r);
   }
   unsigned char* pb = reinterpret_cast<unsigned char*>(&pieces[0][0]);
-  pb[(0 * 64 + lane) * 4 + wv] = (unsigned char)p1;
-  pb[(1 * 64 + lane) * 4 + wv] = (unsigned char)m1;
-  pb[(2 * 64 + lane) * 4 + wv] = (unsigned char)p2;
-  pb[(3 * 64 + lane) * 4 + wv] = (unsigned char)m2;
+  pb[(0 * 64 + lane) * 4 + wv] = (unsigned char)w.p1;
+  pb[(1 * 64 + lane) * 4 + wv] = (unsigned char)w.m1;
+  pb[(2 * 64 + lane) * 4 + wv] = (unsigned char)w.p2;
+  pb[(3 * 64 + lane) * 4 + wv] = (unsigned char)w.m2;
   __syncthreads();
   if (wv == 0 && q0 < npix_out) {
-    const size_t o = ((((size_t)n * (cw32 >> 1) + (word >> 1)) * hw + r) << 1) + (word & 1);
+    const size_t o = half_off(n, cw32, word, hw, r);
     P1[o] = pieces[0][lane];
     M1[o] = pieces[1][lane];
     if (a2) {
@@ -590,35 +504,23 @@ __global__ __launch_bounds__(256) void avgpool2_bn_pack2_wide_kernel(
   if (q >= npix_out) return;
   const int word = blockIdx.y;
   const int hw = Ho * Wo;
-  const int n = (int)(q / hw);
-  const int r = (int)(q - (long long)n * hw);
-  const int oy = r / Wo, ox = r - oy * Wo;
-  uint32_t p1 = 0u, m1 = 0u, p2 = 0u, m2 = 0u;
+  const auto [n, r, oy, ox] = out_pixel(q, hw, Wo);
+  Bn2Words w = {0u, 0u, 0u, 0u};
   const float* base = x + (((size_t)n * C + (size_t)word * 32) * H + 2 * oy) * W + 2 * ox;
   const size_t cstride = (size_t)H * W;
 #pragma unroll 8
   for (int b = 0; b < 32; ++b) {
     const int c = word * 32 + b;
     if (c >= C) break;
-    const float2 u = *reinterpret_cast<const float2*>(base + b * cstride);
-    const float2 v = *reinterpret_cast<const float2*>(base + b * cstride + W);
-    const float t = (((u.x + u.y) + v.x) + v.y) * 0.25f;
-    if (out) out[((size_t)n * C + c) * hw + r] = t;
-    const float u1 = fmaf(t, a1[c], b1[c]);
-    p1 |= (is_pos(u1) ? 1u : 0u) << b;
-    m1 |= ((!relu1 && is_neg(u1)) ? 1u : 0u) << b;
-    if (a2) {
-      const float u2 = fmaf(t, a2[c], b2[c]);
-      p2 |= (is_pos(u2) ? 1u : 0u) << b;
-      m2 |= ((!relu2 && is_neg(u2)) ? 1u : 0u) << b;
-    }
+    w = pool_bn2_channel(w, base + b * cstride, W, c, b, a1, b1, relu1, a2, b2, relu2, out != nullptr, out,
+                         ((size_t)n * C + c) * hw + r);
   }
-  const size_t o = ((((size_t)n * (cw32 >> 1) + (word >> 1)) * hw + r) << 1) + (word & 1);
-  P1[o] = p1;
-  M1[o] = m1;
+  const size_t o = half_off(n, cw32, word, hw, r);
+  P1[o] = w.p1;
+  M1[o] = w.m1;
   if (a2) {
-    P2[o] = p2;
-    M2[o] = m2;
+    P2[o] = w.p2;
+    M2[o] = w.m2;
   }
 }
 
@@ -629,17 +531,17 @@ int launch_avgpool2_bn_pack2(const float* x, int N, int C, int H, int W, const f
   const long long npix = (long long)N * Ho * Wo;
   const int cw32 = 2 * ((C + 63) / 64);
   if (npix * cw32 >= 150000LL) {  // enough threads to fill the chip with one per (pixel, word)
-    hipLaunchKernelGGL(avgpool2_bn_pack2_wide_kernel, dim3((unsigned)((npix + 255) / 256), (unsigned)cw32), dim3(256), 0,
+    hipLaunchKernelGGL(avgpool2_bn_pack2_wide_kernel, stream_grid(npix, cw32), dim3(256), 0,
                        stream, x, C, H, W, Ho, Wo, npix, cw32, a1, b1, relu1, reinterpret_cast<uint32_t*>(P1),
                        reinterpret_cast<uint32_t*>(M1), a2, b2, relu2, reinterpret_cast<uint32_t*>(P2),
                        reinterpret_cast<uint32_t*>(M2), out);
-    return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+    return launch_status();
   }
   hipLaunchKernelGGL(avgpool2_bn_pack2_kernel, dim3((unsigned)((npix + 63) / 64), (unsigned)cw32), dim3(256), 0, stream,
                      x, C, H, W, Ho, Wo, npix, cw32, a1, b1, relu1, reinterpret_cast<uint32_t*>(P1),
                      reinterpret_cast<uint32_t*>(M1), a2, b2, relu2, reinterpret_cast<uint32_t*>(P2),
                      reinterpret_cast<uint32_t*>(M2), out);
-  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+  return launch_status();
 }
 
 // Tail of the real-valued stem in ONE pass over the stem conv's output
@@ -660,9 +562,7 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_pack_kernel(
   if (q >= npix_out) return;
   const int word = blockIdx.y;
   const int hw = Ho * Wo;
-  const int n = (int)(q / hw);
-  const int r = (int)(q - (long long)n * hw);
-  const int oy = r / Wo, ox = r - oy * Wo;
+  const auto [n, r, oy, ox] = out_pixel(q, hw, Wo);
   const int y0 = oy * stride - pad, x0 = ox * stride - pad;
   uint32_t pw = 0u, mw = 0u;
   for (int b = 0; b < 32; ++b) {
@@ -682,11 +582,11 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_pack_kernel(
     }
     if (relu) m = fmaxf(m, 0.0f);
     if (out) out[((size_t)n * C + c) * hw + r] = m;
-    pw |= (is_pos(m) ? 1u : 0u) << b;
-    mw |= (is_neg(m) ? 1u : 0u) << b;
+    pw = with_p(pw, m, b);
+    mw = with_m(mw, m, b);
   }
   if (P) {
-    const size_t o = ((((size_t)n * (cw32 >> 1) + (word >> 1)) * hw + r) << 1) + (word & 1);
+    const size_t o = half_off(n, cw32, word, hw, r);
     P[o] = pw;
     M[o] = mw;
   }
@@ -703,9 +603,7 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool3s2_pack_kernel(
   if (q >= npairs) return;
   const int word = blockIdx.y;
   const int wp = Wo >> 1;
-  const int n = (int)(q / ((long long)Ho * wp));
-  const int rr = (int)(q - (long long)n * Ho * wp);
-  const int oy = rr / wp, t = rr - oy * wp;
+  const auto [n, rr, oy, t] = out_pixel(q, (long long)Ho * wp, wp);  // t: the pair in its row
   const int hw = Ho * Wo;
   const int r = oy * Wo + 2 * t;
   uint32_t pw0 = 0u, mw0 = 0u, pw1 = 0u, mw1 = 0u;
@@ -730,13 +628,13 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool3s2_pack_kernel(
     }
     if (relu) { m0 = fmaxf(m0, 0.0f); m1 = fmaxf(m1, 0.0f); }
     if (out) *reinterpret_cast<float2*>(out + ((size_t)n * C + c) * hw + r) = make_float2(m0, m1);
-    pw0 |= (is_pos(m0) ? 1u : 0u) << b;
-    mw0 |= (is_neg(m0) ? 1u : 0u) << b;
-    pw1 |= (is_pos(m1) ? 1u : 0u) << b;
-    mw1 |= (is_neg(m1) ? 1u : 0u) << b;
+    pw0 = with_p(pw0, m0, b);
+    mw0 = with_m(mw0, m0, b);
+    pw1 = with_p(pw1, m1, b);
+    mw1 = with_m(mw1, m1, b);
   }
   if (P) {
-    const size_t o = ((((size_t)n * (cw32 >> 1) + (word >> 1)) * hw + r) << 1) + (word & 1);
+    const size_t o = half_off(n, cw32, word, hw, r);
     P[o] = pw0; M[o] = mw0;
     P[o + 2] = pw1; M[o + 2] = mw1;
   }
@@ -753,16 +651,16 @@ int launch_bn_relu_maxpool_pack(const float* x, int N, int C, int H, int W, cons
       (!out || (reinterpret_cast<uintptr_t>(out) & 7u) == 0)) {
     const long long npairs = npix / 2;
     hipLaunchKernelGGL(bn_relu_maxpool3s2_pack_kernel,
-                       dim3((unsigned)((npairs + 255) / 256), (unsigned)cw32), dim3(256), 0, stream, x,
+                       stream_grid(npairs, cw32), dim3(256), 0, stream, x,
                        C, H, W, bn_a, bn_b, relu, Ho, Wo, npairs, cw32, out,
                        reinterpret_cast<uint32_t*>(P), reinterpret_cast<uint32_t*>(M));
-    return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+    return launch_status();
   }
   hipLaunchKernelGGL(bn_relu_maxpool_pack_kernel,
-                     dim3((unsigned)((npix + 255) / 256), (unsigned)cw32), dim3(256), 0, stream, x, C,
+                     stream_grid(npix, cw32), dim3(256), 0, stream, x, C,
                      H, W, bn_a, bn_b, relu, k, stride, pad, Ho, Wo, npix, cw32, out,
                      reinterpret_cast<uint32_t*>(P), reinterpret_cast<uint32_t*>(M));
-  return hipGetLastError() == hipSuccess ? BNN_HIP_OK : BNN_HIP_ERR_LAUNCH;
+  return launch_status();
 }
 
 }  // namespace bnn

@@ -168,6 +168,57 @@ def test_bn_act_pack_ste_at_the_edges_of_sign_and_mask(shape):
     assert same_planes(hipops.bn_act_pack_ste(dev(x), dev(a), dev(b)), hipops.pack_act_ste(dev(v)))
 
 
+# The affine kernel at each vector width on the smallest shapes that reach it, and on bases 4 and 8 bytes off a 16-byte
+# boundary (which demote the width).  (shape, pixels per thread on an aligned base)
+WIDTH_SHAPES = [((2, 33, 3, 3), 1),     # H W = 9: a full half-word + a one-channel ragged one
+                ((2, 33, 2, 3), 2),     # H W = 6
+                ((1, 70, 2, 2), 4)]     # H W = 4: a full group, then a 6-channel half and an empty half
+
+
+def carve(value, off):
+    """``value`` as a contiguous device tensor whose first element lies ``off`` floats into a 16-byte aligned buffer
+    (the helper of tests/test_gpu_pack_family.py)."""
+    v = torch.from_numpy(np.ascontiguousarray(value))
+    flat = torch.full((v.numel() + 8,), float("nan"), dtype=v.dtype, device=DEV)
+    assert flat.data_ptr() % 16 == 0
+    t = flat[off:off + v.numel()].view(v.shape)
+    t.copy_(v)
+    assert t.is_contiguous() and t.data_ptr() % 16 == 4 * off
+    return t
+
+
+@pytest.mark.parametrize("off", [0, 1, 2], ids=["aligned", "off4", "off8"])
+@pytest.mark.parametrize("shape,vp", WIDTH_SHAPES, ids=["x".join(map(str, s)) for s, _ in WIDTH_SHAPES])
+def test_bn_act_pack_ste_at_every_width_and_base(shape, vp, off):
+    N, C, H, W = shape
+    hw = H * W
+    t_vp = 4 if hw % 4 == 0 and off == 0 else 2 if hw % 2 == 0 and off % 2 == 0 else 1
+    assert (t_vp == vp) if off == 0 else (t_vp <= vp)
+    seed = gen.seed_of("cellops-train-widths", "x".join(map(str, shape)))
+    x = (1.5 * gen.normal(seed, shape)).astype(np.float32)
+    a = ((0.5 + gen.uniform(seed + 1, (C,))) * np.where(gen.uniform(seed + 2, (C,)) < 0.2, -1, 1)).astype(np.float32)
+    b = (0.4 * gen.normal(seed + 3, (C,))).astype(np.float32)
+    positions = [(0, 0), (H - 1, W - 1)]
+    planted = plant_affine(x, a, b, positions, rot=C - 3)       # (wraps: channels of the full and of the ragged half)
+    for aff in ((a, b), (None, None)):
+        sv = hipops.bn_act_pack_ste(carve(x, off), dev(aff[0]), dev(aff[1]))
+        v = oracle.bn_act(x, *aff)
+        Pw, Mw = oracle.pack_act(v)
+        assert np.array_equal(u64(sv.sign.P), Pw) and np.array_equal(u64(sv.sign.M), Mw), (aff[0] is not None)
+        assert np.array_equal(u64(sv.T), oracle.pack_ste_mask(v)), (aff[0] is not None)
+        if off:
+            assert same_planes(sv, hipops.bn_act_pack_ste(carve(x, 0), dev(aff[0]), dev(aff[1])))
+    sv = hipops.bn_act_pack_ste(carve(x, off), dev(a), dev(b))
+    P, M, T = u64(sv.sign.P), u64(sv.sign.M), u64(sv.T)
+    for c, j in planted:
+        for n in range(N):
+            for y, xx in positions:
+                got = tuple(int((pl[n, c // 64, y, xx] >> np.uint64(c % 64)) & np.uint64(1)) for pl in (P, M, T))
+                assert got == EDGE_BITS[j], (EDGE_CASES[j][0], n, c, got)
+    high = ~np.uint64((1 << (C % 64)) - 1)                      # channels past C in the last word stay 0
+    assert not (P[:, -1] & high).any() and not (M[:, -1] & high).any() and not (T[:, -1] & high).any()
+
+
 # ---- 2. PReLU + shuffle backward -------------------------------------------------------------------------------------
 PRELU_SHAPES = [(3, 48, 10, 6), (2, 96, 7, 9), (5, 24, 3, 3)]
 
